@@ -5,6 +5,7 @@ points in the same JSON line.
 
     python bench.py --gpus 1 --steps 5 --warmup 2                       # default workload: cfg3 (10 M pairs, UMI, depth 8, -s 2)
     python bench.py --gpus N ...                                        # starts its own N ranks (torch.distributed.run, one per GPU, RCCL)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy, to compare two builds
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...   # the driver's form
 
 A "step" = one gce_process() pass of the whole hot path (clustering scan -> pairing/UMI grouping -> scoring ->
@@ -82,6 +83,48 @@ def fetch_rows(capi, lib, eng):
     return rows, pre, post
 
 
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: at most this much in all (under 64 MB in either unit)
+
+
+def dump_outputs(out_dir, capi, lib, eng, core, budget, prefix="", extra=None):
+    """What a caller of gce_result_device holds after the last step, as out_dir/<prefix><name>.npy: float64 where values can pass 2**24,
+    float32 elsewhere.  Both Stats blocks and the record count always; the records -- row index, table fields, bases (packed bytes, the
+    pad nibble of an odd-length read masked) and qualities, padded with -1 -- all of them if they fit in `budget` bytes, else a fixed,
+    seeded sample of rows.  core: the batch's core block on the device (int32 [n_reads, 8], l_qseq in column 4)."""
+    import numpy as np
+    rows, pre, post = fetch_rows(capi, lib, eng)
+    n = len(rows["src"])
+    out = {"n_records": np.array([n], np.float64), "stats_pre": pre.as_array().astype(np.float64), "stats_post": post.as_array().astype(np.float64)}
+    out.update({k: np.asarray(v).astype(np.float64) for k, v in (extra or {}).items()})
+    L = int(core[:, 4].max().item()) if core.shape[0] else 0
+    SB = (L + 1) // 2
+    per_row = 6 * 8 + 4 * 4 + 4 * (SB + L)
+    fixed = sum(a.nbytes for a in out.values()) + 256 * (len(out) + 12)          # (+ the .npy headers)
+    k = max(0, min(n, (budget - fixed) // per_row))
+    idx = np.arange(n, dtype=np.int64) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    out["record_index"] = idx.astype(np.float64)
+    for f in ("src", "qname_src", "mate", "seq_off", "qual_off"):
+        out[f] = rows[f][idx].astype(np.float64)
+    for f in ("kind", "nm_new", "fr", "rr"):
+        out[f] = rows[f][idx].astype(np.float32)
+    src = torch.from_numpy(rows["src"][idx].astype(np.int64)).to(core.device)
+    lq = core[src, 4].cpu().numpy().astype(np.int64)
+
+    def slices(blob, off, width, lens):                     # blob[off[r] + j] for j < lens[r], -1 beyond
+        cols = np.arange(width, dtype=np.int64)[None, :]
+        have = cols < lens[:, None]
+        got = blob[np.where(have, off[:, None] + cols, 0)].astype(np.int32) if blob.size else np.zeros(have.shape, np.int32)
+        return np.where(have, got, np.int32(-1)), have
+    seq, _ = slices(rows["seq"], rows["seq_off"][idx].astype(np.int64), SB, (lq + 1) // 2)
+    odd = np.nonzero(lq % 2 == 1)[0]
+    seq[odd, lq[odd] // 2] &= 0xF0
+    out["seq"] = seq.astype(np.float32)
+    out["qual"] = slices(rows["qual"], rows["qual_off"][idx].astype(np.int64), L, lq)[0].astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 _CPU_JOBS = None      # set before the fork: the workers of the all-cores CPU baseline inherit the shards copy-on-write
 
 
@@ -120,7 +163,11 @@ def main():
     ap.add_argument("--layout", default="soa", choices=["soa", "record", "record64"], help="where a read's packed bases and qualities lie in HBM (gce_batch offsets are free-form): soa = two blobs "
                     "(bases of all reads, qualities of all reads); record = ONE blob, a read's qualities right behind its bases as in a BAM record (bam1_t: seq, then qual) -- 225 contiguous "
                     "bytes at 150 bp touch 4.5 sectors of 64 bytes where the two slices touch 5.5; record64 = the same with every record on a 64-byte boundary (256-byte stride at 150 bp: 4 sectors)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed -- both Stats blocks and a "
+                    "seeded sample of the emitted records (table fields, bases, qualities) -- as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: start the N ranks here (one process per GPU under torch.distributed.run, RCCL) and become
@@ -208,7 +255,6 @@ def main():
         et, ep = stream_ctx["ev_tid"], stream_ctx["ev_pos"]
         assert lib.gce_set_flush_events(eng, len(et), et.ctypes.data, ep.ctypes.data) == 0
 
-    n_copies = args.steps + args.warmup
     if args.layout != "soa":
         # one blob of records: [packed bases][qualities] per read; both base pointers of the batch are the blob's, the offsets tell the two apart
         SBl, Ll = (data.info["read_len"] + 1) // 2, data.info["read_len"]
@@ -221,12 +267,24 @@ def main():
         t["seq_off"] = torch.arange(n_reads, dtype=torch.int64, device=dev) * stride
         t["qual_off"] = t["seq_off"] + SBl
         t["seq"] = t["qual"] = rec[:n_reads * stride]
-        seqs = [padded_clone(t["seq"]) for _ in range(n_copies)]
-        quals = seqs
         del rec, rv
-    else:
-        seqs = [padded_clone(t["seq"]) for _ in range(n_copies)]
-        quals = [padded_clone(t["qual"]) for _ in range(n_copies)]
+    # one pristine copy of the mutable blobs per step while they fit in HBM (up to 40 % of what is free); beyond that a ring of copies,
+    # refilled from the untouched blobs in t with the clock stopped, so that --steps sets the number of timed steps whatever it is
+    blobs = ("seq",) if args.layout != "soa" else ("seq", "qual")
+    per_copy = sum(t[b].numel() * t[b].element_size() + 64 for b in blobs)
+    n_copies = min(args.steps + args.warmup, max(1, int(0.4 * torch.cuda.mem_get_info(dev)[0]) // per_copy))
+    if dist:                                                # every rank refills at the same steps: the timed region's barriers must pair up
+        nc = torch.tensor([n_copies], dtype=torch.int64, device=dev)
+        dist.all_reduce(nc, op=dist.ReduceOp.MIN)
+        n_copies = int(nc.item())
+    seqs = [padded_clone(t["seq"]) for _ in range(n_copies)]
+    quals = seqs if args.layout != "soa" else [padded_clone(t["qual"]) for _ in range(n_copies)]
+
+    def refill():                                           # the ring is used up: every copy pristine again
+        for k in range(n_copies):
+            seqs[k][:t["seq"].numel()].copy_(t["seq"])
+            if quals is not seqs:
+                quals[k][:t["qual"].numel()].copy_(t["qual"])
     t["qname"] = padded_clone(t["qname"])
 
     stats_dev = torch.zeros(2 * capi.GCE_STATS_WORDS, dtype=torch.int64, device=dev)
@@ -252,7 +310,7 @@ def main():
     timings, last_res = [], {}
 
     def step(k):
-        b = device_batch(capi, t, n_reads, seqs[k], quals[k], tick_dev)
+        b = device_batch(capi, t, n_reads, seqs[k % n_copies], quals[k % n_copies], tick_dev)
         rc = lib.gce_submit_device(eng, C.byref(b))
         rc = rc or lib.gce_process(eng)
         if rc:
@@ -282,18 +340,31 @@ def main():
             torch.cuda.synchronize()
 
     for k in range(args.warmup):
+        if k and k % n_copies == 0:
+            sync()
+            refill()
+            sync()
         step(k)
     sync()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        step(args.warmup + k)
+    elapsed, t0 = 0.0, time.perf_counter()
+    for k in range(args.warmup, args.warmup + args.steps):
+        if k and k % n_copies == 0:                         # the ring is used up: refilled with the clock stopped
+            sync()
+            elapsed += time.perf_counter() - t0
+            refill()
+            sync()
+            t0 = time.perf_counter()
+        step(k)
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     ms_per_step = elapsed * 1000.0 / args.steps
+    if args.dump_outputs:                                   # the last timed step's result, still held by the engine (outside the timed region)
+        dump_outputs(args.dump_outputs, capi, lib, eng, t["core"], DUMP_BYTES // world, prefix=("rank%d_" % rank) if world > 1 else "",
+                     extra={"stats_merged": stats_dev.cpu().numpy()} if dist else None)
     # what the N > 1 step does that the N = 1 step does not -- the Stats payload (k_depth over the rank's reads and records, two passes) and its all-reduce --
     # timed ALONE behind the timed region (max over ranks), so that value(N) / value(1) can be read like for like: ms_per_step - merge_ms is the engine pass
     merge_ms = None

@@ -98,27 +98,20 @@ def test_reference_packing_matches_fastareader_layout(oracle):
 def test_is_duplex_against_the_reference_tokenizer(oracle):
     """The one reference file on the path that compiles without htslib is src/util.h; oracle/ref_probe builds its `split`
     (the tokenizer behind Cluster::isDuplex, cluster.cpp:246-258) from the reference source in place into
-    oracle/_ref/libref_util.so.  The oracle's restatement must agree with it on every UMI shape, including the odd ones
-    (leading / trailing / doubled underscores, empty strings)."""
-    import ctypes as C
-    import itertools
+    oracle/_ref/libref_util.so, and tests/golden/reference_split.json holds its answers (make_reference_split.py).
+    The oracle's restatement must agree with them on every UMI shape, including the odd ones (leading / trailing /
+    doubled underscores, empty strings).  Where the probe is built, it must still give the stored answers."""
+    import json
     import os
-    import random
-    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_util.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libref_util.so not built (needs /root/reference at build time)")
-    ref = C.CDLL(so)
-    ref.ref_is_duplex.argtypes = [C.c_char_p, C.c_char_p]
-    ref.ref_split.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
-    buf = C.create_string_buffer(256)
-    assert ref.ref_split(b"_A__B_", b"_", buf, 256) == 4 and buf.value == b"A\n\nB\n"      # leading sep skipped, trailing one adds ""
-    alphabet = ["", "A", "AC", "_", "__", "A_", "_A", "A_C", "AC_GT", "GT_AC", "A__C", "_A_C", "A_C_", "A_C_G", "ACGT_TTGA", "TTGA_ACGT"]
-    cases = list(itertools.product(alphabet, alphabet))
-    rng = random.Random(7)
-    for _ in range(3000):
-        mk = lambda: "".join(rng.choice("ACGT_") for _ in range(rng.randint(0, 9)))
-        a = mk()
-        b = mk() if rng.random() < 0.5 else "_".join(reversed(a.split("_")))
-        cases.append((a, b))
-    for a, b in cases:
-        assert oracle.is_duplex(a, b) == bool(ref.ref_is_duplex(a.encode(), b.encode())), (a, b)
+    from golden.make_reference_split import PROBE, duplex_cases, load_probe, probe_split
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_split.json")))
+    assert ["_A__B_", "_", 4, "A\n\nB\n"] in gold["split"]                 # leading sep skipped, trailing one adds ""
+    assert [tuple(c[:2]) for c in gold["is_duplex"]] == duplex_cases()
+    for a, b, want in gold["is_duplex"]:
+        assert oracle.is_duplex(a, b) == bool(want), (a, b)
+    if os.path.exists(PROBE):
+        ref = load_probe()
+        for s, sep, n, joined in gold["split"]:
+            assert probe_split(ref, s, sep) == (n, joined), (s, sep)
+        for a, b, want in gold["is_duplex"]:
+            assert bool(ref.ref_is_duplex(a.encode(), b.encode())) == bool(want), (a, b)

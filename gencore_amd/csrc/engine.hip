@@ -58,6 +58,7 @@ struct HostRaw {
 
 struct gce_engine {
     gce_params prm{};
+    bool vote_off_logged = false;     // the stderr note that k_vote is off for this engine's parameters is printed once
     std::vector<uint32_t> target_len;
     std::string err;
     hipStream_t stream = nullptr;
@@ -734,6 +735,12 @@ static int gce_process_impl(gce_engine *e) {
         p.s_min_lb = mn;
         p.vote_ok = mn >= 0 && mx + 4 <= 120 && p.moderate_q >= 0 && p.moderate_q <= 127 && p.base_score_req <= 100 && p.q2s_swar_ok;   // (nested thresholds: k_vote's items index q2s_lut by the number of thresholds passed)
         p.vote_accept_by_qual = std::min(std::min(p.s_moderate, p.s_high), mn + 4) >= std::max(p.base_score_req, 1);
+        if (!p.vote_ok && !e->vote_off_logged) {      // every group then goes to k_score2 and the per-side kernels: say why, once per engine
+            e->vote_off_logged = true;
+            const char *why = !p.q2s_swar_ok ? "quality thresholds not nested (low <= moderate <= high <= 127)" : mn < 0 ? "a score constant below 0"
+                            : mx + 4 > 120 ? "a score constant above 116" : (p.moderate_q < 0 || p.moderate_q > 127) ? "moderate quality outside 0..127" : "base_score_req above 100";
+            fprintf(stderr, "gencore_amd: k_vote off for this engine (%s): every group goes to the per-side kernels\n", why);
+        }
     }
     memcpy(p.prefix, e->prm.umi_prefix, 32); p.prefix[31] = 0; p.prefix_len = (int)strlen(p.prefix);
     p.n_targets = (int)e->target_len.size(); p.target_len = e->d_target_len.as<uint32_t>(); p.target_cum = e->target_len.empty() ? nullptr : e->d_target_cum.as<uint64_t>();
@@ -1270,6 +1277,16 @@ int gce_stats_device(gce_engine *e, const int64_t **pre_then_post) {
 int gce_get_timing(gce_engine *e, gce_timing *out) {
     if (!e || !out) return GCE_ERR_INVALID;
     *out = e->timing;
+    return GCE_OK;
+}
+
+// k_vote's counters of the last gce_process: [0] extra vote rounds (batches with more contested columns than one round's tallies hold: one per round
+// behind the first), [1] of those the rounds that start at a side index not a multiple of 4, [2] group sides k_vote handed on to the per-side
+// kernels, [3] groups of the stream
+int gce_get_vote_counters(gce_engine *e, int64_t out[4]) {
+    if (!e || !out || !e->processed) return GCE_ERR_INVALID;
+    out[0] = (int64_t)e->h_si.vote_rounds2; out[1] = (int64_t)e->h_si.vote_rounds2_unaligned;
+    out[2] = (int64_t)(e->h_si.hand_on >> 32); out[3] = (int64_t)e->h_si.n_groups;
     return GCE_OK;
 }
 

@@ -193,21 +193,26 @@ __device__ __forceinline__ int vb_find(const uint16_t *pre, int n, int it) {    
 #define VB_FIND_ALIGNED 1
 #endif
 #define VB_PRE (VB_SIDES + 8)
-__device__ __forceinline__ int vb_find_wave(const uint16_t *pre, int n, int base, int lane, int last) {
+static_assert(VB_SIDES % 4 == 0 && VB_PRE >= VB_SIDES + 4, "vb_find_wave reads the aligned 4-entry group that holds pre[VB_SIDES]");
+// The sides searched are arr[s0 .. s0 + n] (a later round of pass B starts at side s0 > 0); the result is relative to s0.
+__device__ __forceinline__ int vb_find_wave(const uint16_t *arr, int s0, int n, int base, int lane, int last) {
     last = max(last, 0);
     const int b0 = min(base, last), it = min(base + lane, last);
-    const int pl = (int)pre[min(lane, n)];
+    const int pl = (int)arr[s0 + min(lane, n)];
     int s = __popcll(__ballot(pl <= b0)) - 1;
 #if VB_FIND_ALIGNED
-    // the four entries of the ALIGNED 8-byte group that holds pre[s + 1] (round 6: the walk read pre[s + 1 .. s + 4] -- an 8-byte LDS read on a 2-byte boundary three
-    // times out of four; SQ_LDS_UNALIGNED_STALL was a third of the kernel's LDS-active cycles).  The group's entries up to s are <= the item like pre[s] itself, so
-    // counting all four that are gives the place directly.
-    for (int g = (s + 1) >> 2;; g++) {
-        const uint2 w2 = *reinterpret_cast<const uint2 *>(pre + 4 * g);
+    // the four entries of the ALIGNED 8-byte group that holds arr[s0 + s + 1] (round 6: the walk read pre[s + 1 .. s + 4] -- an 8-byte LDS read on a 2-byte boundary three
+    // times out of four; SQ_LDS_UNALIGNED_STALL was a third of the kernel's LDS-active cycles).  The groups are formed on the array itself, not on arr + s0: with s0 % 4 != 0
+    // that was again an 8-byte read on a 2-byte boundary.  The group's entries up to s0 + s are <= the item like arr[s0 + s] itself (the prefixes ascend over the
+    // whole array, the sides in front of s0 included), so counting all four that are gives the place directly.  The last group read holds arr[s0 + n] (the round's
+    // total, larger than every item): index <= VB_SIDES + 3 < VB_PRE.
+    for (int g = (s0 + s + 1) >> 2;; g++) {
+        const uint2 w2 = *reinterpret_cast<const uint2 *>(arr + 4 * g);
         const int c = ((int)(w2.x & 0xFFFFu) <= it) + ((int)(w2.x >> 16) <= it) + ((int)(w2.y & 0xFFFFu) <= it) + ((int)(w2.y >> 16) <= it);
-        if (c < 4) { s = 4 * g + c - 1; break; }
+        if (c < 4) { s = 4 * g + c - 1 - s0; break; }
     }
 #else
+    const uint16_t *pre = arr + s0;
     for (;;) {
         const int a1 = (int)pre[s + 1], a2 = (int)pre[s + 2], a3 = (int)pre[s + 3], a4 = (int)pre[s + 4];
         const int c = (a1 <= it) + (a2 <= it) + (a3 <= it) + (a4 <= it);
@@ -508,7 +513,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
         const int it = tid + VB_T * kk;
         item_side[kk] = 0;
         if (it - lane >= n_items) continue;                                        // (wave-uniform: the second round is empty for the usual batch of <= 256 items)
-        const int s = s_ord[vb_find_wave(s_ipre, VB_SIDES, it - lane, lane, n_items - 1)];
+        const int s = s_ord[vb_find_wave(s_ipre, 0, VB_SIDES, it - lane, lane, n_items - 1)];
         item_side[kk] = s;
         if (it < n_items) {
             const VSide sd = s_side[s];
@@ -671,6 +676,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
         const unsigned long long nofit_ = ~__ballot(fits_);
         const int s1 = nofit_ ? __ffsll((long long)nofit_) - 1 : 64;                            // first side that does not fit (prefixes ascend: every later one does not either); VB_SIDES if all do
         const int c0 = s_cpre[s0], ncol = (int)s_cpre[s1] - c0, j0 = s_jpre[s0], njob = (int)s_jpre[s1] - j0;
+        if (s0 > 0 && threadIdx.x == 0) { atomicAdd(&w.si->vote_rounds2, 1ull); if (s0 & 3) atomicAdd(&w.si->vote_rounds2_unaligned, 1ull); }   // (tests: a second round is reached)
 #if VB_TPLANE
         {
             uint32_t *tp_ = &s_tal[0][0][0];
@@ -764,7 +770,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             }
         };
         for (int itb = j0 + tid - lane; itb < j0 + njob; itb += VB_T) {                 // (wave-uniform trips: the side lookup is a wave operation)
-            const int sa = s0 + vb_find_wave(s_jpre + s0, s1 - s0, itb, lane, j0 + njob - 1);
+            const int sa = s0 + vb_find_wave(s_jpre, s0, s1 - s0, itb, lane, j0 + njob - 1);
             const Item x0 = prep(itb + lane, sa);
             if (x0.on) { vote1(x0, 0); if (x0.on1) vote1(x0, 1); }
         }
@@ -820,7 +826,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             }
         };
         for (int itb = j0 + tid - lane; itb < j0 + njob; itb += 2 * VB_T) {             // (wave-uniform trips: the side lookup is a wave operation)
-            const int sa = s0 + vb_find_wave(s_jpre + s0, s1 - s0, itb, lane, j0 + njob - 1), sb2 = s0 + vb_find_wave(s_jpre + s0, s1 - s0, itb + VB_T, lane, j0 + njob - 1);
+            const int sa = s0 + vb_find_wave(s_jpre, s0, s1 - s0, itb, lane, j0 + njob - 1), sb2 = s0 + vb_find_wave(s_jpre, s0, s1 - s0, itb + VB_T, lane, j0 + njob - 1);
             const Item x0 = prep(itb + lane, sa), x1 = prep(itb + lane + VB_T, sb2);
             vote(x0); vote(x1);
         }
@@ -830,7 +836,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
         // (d) one lane per column of the round: rule cascade + reference arbitration (group.cpp:394-501)
         for (int cib = c0 + tid - lane; cib < c0 + ncol; cib += VB_T) {
             const int ci = cib + lane;
-            const int s = s0 + vb_find_wave(s_cpre + s0, s1 - s0, cib, lane, c0 + ncol - 1);
+            const int s = s0 + vb_find_wave(s_cpre, s0, s1 - s0, cib, lane, c0 + ncol - 1);
             if (ci >= c0 + ncol) continue;
             const int col = s_ccol[ci];
             const VSide sd = s_side[s];

@@ -96,6 +96,12 @@ class Engine:
         self._check(self.lib.gce_get_timing(self._h, C.byref(t)))
         return t.as_dict()
 
+    def vote_counters(self):
+        """k_vote's counters of the last finish() (gce_get_vote_counters)."""
+        v = (C.c_int64 * 4)()
+        self._check(self.lib.gce_get_vote_counters(self._h, v))
+        return dict(rounds2=v[0], rounds2_unaligned=v[1], handed_on_sides=v[2], groups=v[3])
+
     def rows(self):
         """The table of emitted records (gce_drain) as numpy copies: (dict of arrays, pre GceStats, post GceStats)."""
         r = GceResult()

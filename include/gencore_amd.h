@@ -307,6 +307,10 @@ int gce_stats_payload_device(gce_engine *e, int32_t coverage_step, int32_t n_reg
                              const int32_t *region_end, const int64_t **payload, gce_payload_layout *layout);
 
 int gce_get_timing(gce_engine *e, gce_timing *out);
+/* k_vote's counters of the last gce_process (ADDED under v3): out[0] vote rounds behind a batch's first (a batch whose contested columns do not
+ * fit one round's tallies), out[1] of those the rounds that start at a side index that is not a multiple of 4, out[2] group sides k_vote handed on
+ * to the per-side kernels, out[3] groups of the stream.  For tests and diagnostics. */
+int gce_get_vote_counters(gce_engine *e, int64_t out[4]);
 /* The two Stats blocks of the last gce_process in DEVICE memory: 2 x GCE_STATS_WORDS int64, pre then post -- for the final Stats merge
  * of a multi-GPU run (one RCCL all-reduce(sum); all fields are additive, src/stats.h:47-65) without a bounce through the host. */
 int gce_stats_device(gce_engine *e, const int64_t **pre_then_post);

@@ -7,7 +7,12 @@ import numpy as np
 
 from gencore_amd.batch import ReadBatch
 
-QUALS = [0, 2, 10, 14, 15, 16, 19, 20, 21, 29, 30, 31, 37, 40]
+QUALS = [0, 2, 10, 14, 15, 16, 19, 20, 21, 29, 30, 31, 37, 40]       # around the default thresholds 30 / 20 / 15
+
+
+def quals_around(thresholds):
+    """The quality pool for other thresholds (high, moderate, low): t - 1, t and t + 1 of each, plus 0, 2 and 40."""
+    return sorted({0, 2, 40} | {t + d for t in thresholds for d in (-1, 0, 1)})
 
 
 def _mutate(seq, rate, rng):
@@ -20,10 +25,14 @@ def _mutate(seq, rate, rng):
     return "".join(out)
 
 
-def make_case(seed, n_mol=40, umi_mode=None, period=None, deep=None, exotic=False, umi_lens=(4, 6, 8)):
-    """Returns (ReadBatch, params overrides dict, reference list [(nibble array|None, n_bases)], contig lengths)."""
+def make_case(seed, n_mol=40, umi_mode=None, period=None, deep=None, exotic=False, umi_lens=(4, 6, 8), thresholds=None, scores=None, deep_mols=1):
+    """Returns (ReadBatch, params overrides dict, reference list [(nibble array|None, n_bases)], contig lengths).
+    deep: depth of the first `deep_mols` molecules.  thresholds=(high, moderate, low) / scores=(high, moderate, low, bad): quality
+    thresholds and score constants in the overrides (Options::highQuality.., scoreOfNotOverlapped*: options.cpp:4-40); with thresholds the
+    qualities are drawn from quals_around(thresholds).  Without these options the cases are the same as before they existed."""
     from oracle import oracle_py
     rng = random.Random(seed)
+    qpool = QUALS if thresholds is None else quals_around(thresholds)
     contig_len = [rng.randint(4000, 9000), 260000, rng.randint(3000, 6000)]
     contigs = []
     for ln in contig_len:
@@ -42,7 +51,7 @@ def make_case(seed, n_mol=40, umi_mode=None, period=None, deep=None, exotic=Fals
         ins = rng.randint(max(30, L // 2), 3 * L)
         far = tid == 1 and rng.random() < 0.15
         start = rng.randint(10, contig_len[tid] - (ins if not far else 150000) - 3 * L - 20)
-        depth = deep if (deep and m == 0) else rng.choice([1, 1, 2, 3, 4, 6, 9])
+        depth = deep if (deep and m < deep_mols) else rng.choice([1, 1, 2, 3, 4, 6, 9])
         umi_a = "".join(rng.choice("ACGT") for _ in range(rng.choice(list(umi_lens))))
         umi_b = "".join(rng.choice("ACGT") for _ in range(len(umi_a)))
         cross = rng.random() < 0.08
@@ -100,8 +109,8 @@ def make_case(seed, n_mol=40, umi_mode=None, period=None, deep=None, exotic=Fals
                     du = rng.choice(["_" + du, ua + "__" + ub, du + "_", ua + "_", "_" + ua, "_", ua])
                 name += ":UMI_" + du
             mi_tag = ua if (umi_mode == "mi" and rng.random() < 0.85) else None      # MI:Z tag (bamutil.cpp:23-38); a pair without one falls back to its name
-            qf = [rng.choice(QUALS) for _ in fseq]
-            qr = [rng.choice(QUALS) for _ in rseq]
+            qf = [rng.choice(qpool) for _ in fseq]
+            qr = [rng.choice(qpool) for _ in rseq]
             if exotic:          # IUPAC codes (BAM nibbles outside A,C,G,T,N) and out-of-spec quals: generic-kernel paths
                 fseq = "".join(rng.choice("MRWSYKVHDB=") if rng.random() < 0.02 else ch for ch in fseq)
                 rseq = "".join(rng.choice("MRWSYKVHDB=") if rng.random() < 0.02 else ch for ch in rseq)
@@ -166,6 +175,10 @@ def make_case(seed, n_mol=40, umi_mode=None, period=None, deep=None, exotic=Fals
     )
     if over["duplex_only"] and over["disable_duplex"]:
         over["disable_duplex"] = 0
+    if thresholds is not None:
+        over.update(high_quality=thresholds[0], moderate_quality=thresholds[1], low_quality=thresholds[2])
+    if scores is not None:
+        over.update(score_high=scores[0], score_moderate=scores[1], score_low=scores[2], score_bad=scores[3])
     return batch, over, reference, contig_len
 
 

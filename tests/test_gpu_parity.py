@@ -807,3 +807,182 @@ def test_several_device_batches_per_process(built, seed, umi_mode):
         E.close()
     diffs = diff_results(batch, got, want) + check_output_order(batch, got.rows)
     assert not diffs, "\n".join(diffs)
+
+
+# ---------------------------------------------------------------------------------------------------------------- quality thresholds and score constants
+def run_engine_vs_oracle(batch, params, reference):
+    """run_both through one Engine kept open for its timing() and vote_counters()."""
+    from gencore_amd.engine import Engine
+    from oracle import oracle_py
+    want = oracle_py.run(batch, params, reference)
+    assert want.status == 0, want.message
+    e = Engine(params)
+    try:
+        got = e.run(batch, reference)
+        timing, counters = e.timing(), e.vote_counters()
+    finally:
+        e.close()
+    diffs = diff_results(batch, got, want) + check_output_order(batch, got.rows)
+    assert not diffs, "\n".join(diffs)
+    return got, want, timing, counters
+
+
+# (thresholds high / moderate / low, scores high / moderate / low / bad, other overrides, whether gce_process keeps k_vote on: DevParams.vote_ok)
+# Scores stay where the reference's `char` scores and the oracle's signed char agree: |score| + 4 < 128.
+PARAM_ROWS = {
+    "control": ((30, 20, 15), (8, 6, 4, 2), {}, True),
+    "cli_lowest": ((20, 15, 8), None, {}, True),                                   # options.cpp:72-100: high >= 20, moderate >= 15, low >= 8
+    "cli_highest": ((40, 35, 30), None, {}, True),                                 # high <= 40, moderate <= 35, low <= 30
+    "tied_25": ((25, 25, 25), None, {}, True),                                     # equal thresholds: the SWAR count passes all three at once
+    "tied_20_20_8": ((20, 20, 8), None, {}, True),
+    "accept_by_qual_off": (None, (10, 7, 3, 1), dict(base_score_req=10), True),    # min(7, 10, 1 + 4) < 10: vote_accept_by_qual false, s_min_lb = 1
+    "min_score_0": (None, (8, 6, 4, 0), {}, True),                                 # s_min_lb = 0: k_vote contests every column
+    "not_nested": ((15, 20, 30), None, {}, False),                                 # q2s_swar_ok false: k_score2 / k_consensus_fast / _slow only
+    "score_range": (None, (120, 6, 4, 2), {}, False),                              # 120 + 4 > 120: vote_ok false by the score range
+}
+
+
+def _row_case(row, seed, **kw):
+    thr, sc, extra, _ = PARAM_ROWS[row]
+    batch, over, reference, contig_len = fuzzgen.make_case(seed, thresholds=thr, scores=sc, **kw)
+    over.update(extra)
+    return batch, fuzzgen.make_params(over, contig_len), reference
+
+
+def _check_vote_state(row, timing, counters, err):
+    if PARAM_ROWS[row][3]:
+        assert "k_vote off" not in err
+    else:                                                                          # the fallback is taken on purpose, and said so once
+        assert err.count("k_vote off for this engine") == 1, err
+        assert counters["handed_on_sides"] > 0 and timing["score_ms"] > 0
+
+
+@pytest.mark.parametrize("seed", [800, 801, 802])
+@pytest.mark.parametrize("row", sorted(PARAM_ROWS))
+def test_quality_thresholds_and_score_constants(built, capfd, row, seed):
+    """Engine vs oracle away from the default thresholds (30 / 20 / 15) and scores (8 / 6 / 4 / 2), qualities drawn at t - 1, t, t + 1 of every
+    threshold: the SWAR threshold counts of d_qual2score / d_q2s4_biased and k_vote's items, pass A's `>= moderate` test and its s_min_lb bound,
+    k_consensus_fast's biased sums, and the rows where gce_process turns k_vote off (vote_ok) and every group goes to the fallback kernels."""
+    batch, prm, reference = _row_case(row, seed, n_mol=50)
+    got, want, timing, counters = run_engine_vs_oracle(batch, prm, reference)
+    _check_vote_state(row, timing, counters, capfd.readouterr().err)
+    assert len(got.emitted()) > 0
+
+
+@pytest.mark.parametrize("row", sorted(PARAM_ROWS))
+def test_quality_thresholds_and_score_constants_deep(built, capfd, row):
+    """The same rows on three molecules of 120 pairs each (no UMI: one group of > 64 pairs apiece): k_deep_prepare / k_vote_deep and the
+    per-side kernels under the same parameters."""
+    batch, prm, reference = _row_case(row, 810, n_mol=8, umi_mode="none", deep=120, deep_mols=3)
+    prm.skip_low_complexity_cluster_threshold = 1000
+    got, want, timing, counters = run_engine_vs_oracle(batch, prm, reference)
+    _check_vote_state(row, timing, counters, capfd.readouterr().err)
+    left = batch.core[batch.core["isize"] > 0]                                     # left reads of both strands, keyed as the clusters are
+    assert max(np.unique(left[["pos", "isize"]], return_counts=True)[1]) > 64
+
+
+def test_score_constants_out_of_the_engines_range(built):
+    """score_max + score_bias > 255 (scores + 4 on a mate-overlap match, biased by 3 - the smallest score: one byte per score in the SWAR tallies):
+    gce_process refuses the parameters with GCE_ERR_INVALID instead of computing with wrapped bytes."""
+    from gencore_amd.capi import GceError
+    from gencore_amd.engine import Engine
+    batch, over, reference, contig_len = fuzzgen.make_case(820, n_mol=10)
+    over.update(score_high=252)                                                    # 256 + 1 > 255
+    e = Engine(fuzzgen.make_params(over, contig_len))
+    try:
+        with pytest.raises(GceError) as ei:
+            e.run(batch, reference)
+        assert ei.value.status == -1
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- k_vote pass B: column pairs and rounds
+def _alt(b):
+    return {"A": "C", "C": "G", "G": "T", "T": "A"}[b]
+
+
+def vote_groups_stream(seed, groups, n_pairs=6, L=(60, 60), gap=None, spacing=1000):
+    """One contig; one cluster (one group, no UMI) per entry of `groups` = (left_cols, right_cols, overlap_mismatches): all reads equal the
+    reference with quality 37, except that the LAST pair's left / right read shows another base at left_cols / right_cols (one voter differs:
+    the column is contested in pass A) and the FIRST pair's left read another base at each left column of overlap_mismatches (a mismatch with its
+    mate inside the mate overlap: P3 forces the column on both sides).  gap: right read start - left read start (default: no overlap)."""
+    import random
+    from gencore_amd.batch import ReadBatch
+    from gencore_amd.capi import default_params
+    from oracle import oracle_py
+    rng = random.Random(seed)
+    Ll, Lr = L
+    gap = gap if gap is not None else Ll + 40
+    contig = "".join(rng.choice("ACGT") for _ in range(spacing * (len(groups) + 2)))
+    recs = []
+    for gi, (lcols, rcols, ovm) in enumerate(groups):
+        pos = spacing * (gi + 1)
+        mpos = pos + gap
+        for k in range(n_pairs):
+            ls, rs = list(contig[pos:pos + Ll]), list(contig[mpos:mpos + Lr])
+            if k == n_pairs - 1:
+                for c in lcols:
+                    ls[c] = _alt(ls[c])
+                for c in rcols:
+                    rs[c] = _alt(rs[c])
+            if k == 0:
+                for c in ovm:
+                    ls[c] = _alt(ls[c])
+            nl = sum(1 for a, b in zip(ls, contig[pos:pos + Ll]) if a != b)
+            nr = sum(1 for a, b in zip(rs, contig[mpos:mpos + Lr]) if a != b)
+            name = "g%d_p%d" % (gi, k)
+            isize = mpos + Lr - pos
+            recs.append(dict(qname=name, flag=99, tid=0, pos=pos, cigar="%dM" % Ll, mtid=0, mpos=mpos, isize=isize, seq="".join(ls), qual=[37] * Ll, nm=nl))
+            recs.append(dict(qname=name, flag=147, tid=0, pos=mpos, cigar="%dM" % Lr, mtid=0, mpos=pos, isize=-isize, seq="".join(rs), qual=[37] * Lr, nm=nr))
+    recs.sort(key=lambda r: r["pos"])
+    batch = ReadBatch.from_records(recs)
+    tl = np.asarray([len(contig)], np.uint32)
+    prm = default_params(n_targets=1, target_len=tl.ctypes.data)
+    prm._keep = tl
+    return batch, prm, [(oracle_py.pack_reference(contig), len(contig))]
+
+
+def test_vote_pass_b_odd_and_even_column_counts(built):
+    """Pass B (gce_vote.hpp, VB_COLPAIR): an item votes columns c and c + ncs2 of its side's list, ncs2 = (ncs + 1) / 2; with an odd ncs the last
+    item's second column does not exist (on1 false).  Sides with 1 and 31 contested columns (odd: the last item of every voter is half an item),
+    2 and 32 (even controls; 32 = VB_SMAX, the most a side keeps), and 33 (over VB_SMAX: the group is handed on).  Five groups of 6 pairs
+    (weight 30 <= VB_W = 96: one batch), 1 + 31 + 2 + 32 + 31 + 1 + 32 + 2 = 132 contested columns in k_vote <= VB_CCAP = 256: one round."""
+    r = lambda k, off=0: list(range(off, off + k))
+    groups = [(r(1, 7), r(31, 3), ()), (r(2, 10), r(32, 20), ()), (r(31, 1), r(1, 50), ()), (r(32, 27), r(2, 0), ()), (r(33, 2), [], ())]
+    batch, prm, reference = vote_groups_stream(900, groups)
+    got, want, timing, counters = run_engine_vs_oracle(batch, prm, reference)
+    assert counters["groups"] == 5 and counters["rounds2"] == 0
+    assert counters["handed_on_sides"] == 2                                        # the group with 33 contested columns on one side
+    assert len(got.emitted()) == 10
+
+
+def test_vote_pass_b_column_pair_across_the_mate_overlap_edge(built):
+    """An item's two columns c and c + ncs2 on either side of where the mate overlap ends.  Left reads 60M at x, right reads 60M at x + 40:
+    left columns 40..59 lie on right columns 0..19 (pair.cpp:108-120).  Group 0: the first pair's left read mismatches its mate at left columns
+    45, 50, 55 (P3 forces left 45, 50, 55 and right 5, 10, 15), the last pair's reads differ at left 10, 20, 30 and right 25, 35, 45: both
+    sides have ncs = 6, ncs2 = 3, items (10, 45) (20, 50) (30, 55) and (5, 25) (10, 35) (15, 45) -- one column inside the overlap, one outside.
+    Group 1: mismatches at left 40 and 59 (the overlap's first and last column: right 0 and 19), the last pair differs at left 39 and right 20:
+    left list 39, 40, 59 (items (39, 59) and (40, -)), right list 0, 19, 20 (items (0, 20) and (19, -)): the overlap's edges inside one item."""
+    groups = [([10, 20, 30], [25, 35, 45], (45, 50, 55)), ([39], [20], (40, 59))]
+    batch, prm, reference = vote_groups_stream(901, groups, gap=40)
+    got, want, timing, counters = run_engine_vs_oracle(batch, prm, reference)
+    assert counters["groups"] == 2 and counters["handed_on_sides"] == 0
+    assert len(got.emitted()) == 4
+
+
+@pytest.mark.parametrize("cols,s0", [((10, 10), 25), ((11, 11), 23), ((10, 9), 26), ((9, 9), 28), ((12, 12), 21)])
+def test_vote_second_round_at_every_side_alignment(built, cols, s0):
+    """Batches whose contested columns do not fit one round of tallies.  Every group has 6 pairs (weight max(6, VB_MINW = 6)): 16 groups fill a
+    batch of VB_W = 96 exactly, 32 sides.  With (left, right) contested columns per group, the first round takes the longest run of sides whose
+    columns fit VB_CCAP = 256, the second round the rest (<= VB_RCAP = 384 in all: nothing is handed on).  10 / 10: 25 sides (250), s0 = 25;
+    11 / 11: 23 sides (253), s0 = 23; 10 / 9: 13 groups = 247 + 10 = 257 > 256, s0 = 26; 9 / 9: 28 sides (252), s0 = 28; 12 / 12: 21 sides (252),
+    s0 = 21 -- s0 % 4 = 1, 3, 2, 0, 1.  vb_find_wave's 4-entry groups in the second round start at s0 rounded down to a multiple of 4; the
+    counters show that the round ran and whether it started off a multiple of 4.  Four batches per stream."""
+    n_batches = 4
+    groups = [(list(range(3, 3 + 2 * cols[0], 2)), list(range(4, 4 + 2 * cols[1], 2)), ()) for _ in range(16 * n_batches)]
+    batch, prm, reference = vote_groups_stream(910 + s0, groups)
+    got, want, timing, counters = run_engine_vs_oracle(batch, prm, reference)
+    assert counters["groups"] == 16 * n_batches and counters["handed_on_sides"] == 0
+    assert counters["rounds2"] == n_batches
+    assert counters["rounds2_unaligned"] == (n_batches if s0 % 4 else 0)

@@ -1,0 +1,167 @@
+"""The gencore command line (src/main.cpp, src/options.cpp) over the HIP engine: `python -m gencore_amd -i in.bam -o out.bam -r ref.fa ...`.
+
+Flags, defaults and validation messages are the reference's; the run is gce_run_bam_depth (one engine, or the sharded runner for several
+--devices); afterwards the two Stats summaries go to stderr and the JSON report is written (src/gencore.cpp:284-292, src/main.cpp:113-116).
+Every check happens before the library is loaded, so a bad command line never touches a GPU."""
+import argparse
+import os
+import sys
+import time
+
+from . import __version__
+
+EPILOG = """\
+Flags marked [gencore_amd] are not the reference's; every other flag, default and validation message is gencore 0.17.2's.
+-h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
+and does nothing.
+
+Known difference: the reference writes its report before its destructor writes the records still held in its output set, so its
+after_processing total_reads, total_bases, mismatches, coverage and coverage_bed leave that tail out.  This command reports every record it
+writes.  The cluster, fragment, SSCS and DCS counters and the whole before_processing block are the same either way."""
+
+
+class UsageError(Exception):
+    pass
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m gencore_amd", add_help=False, epilog=EPILOG, formatter_class=argparse.RawDescriptionHelpFormatter,
+                                description="Consensus reads from a coordinate-sorted BAM/SAM file (gencore on the MI355X).")
+    a = p.add_argument
+    # input/output
+    a("-i", "--in", dest="input", default="-", help="input sorted bam/sam file. STDIN will be read from if it's not specified")
+    a("-o", "--out", dest="output", default="-", help="output bam/sam file. STDOUT will be written to if it's not specified")
+    a("-r", "--ref", required=True, help="reference fasta file name (should be an uncompressed .fa/.fasta file)")
+    a("-b", "--bed", default="", help="bed file to specify the capturing region, none by default")
+    a("-x", "--duplex_only", action="store_true",
+      help="only output duplex consensus sequences, which means single stranded consensus sequences will be discarded.")
+    a("--no_duplex", action="store_true", help="don't merge single stranded consensus sequences to duplex consensus sequences.")
+    # UMI
+    a("-u", "--umi_prefix", default="auto", help="the prefix for UMI, if it has. None by default. Check the README for the defails of UMI formats.")
+    # thresholds
+    a("-s", "--supporting_reads", type=int, default=1,
+      help="only output consensus reads/pairs that merged by >= <supporting_reads> reads/pairs. The valud should be 1~10, and the default value is 1.")
+    a("-a", "--ratio_threshold", type=float, default=0.8,
+      help="if the ratio of the major base in a cluster is less than <ratio_threshold>, it will be further compared to the reference. "
+           "The valud should be 0.5~1.0, and the default value is 0.8")
+    a("-c", "--score_threshold", type=int, default=6,
+      help="if the score of the major base in a cluster is less than <score_threshold>, it will be further compared to the reference. "
+           "The valud should be 1~20, and the default value is 6")
+    a("-d", "--umi_diff_threshold", type=int, default=1,
+      help="if two reads with identical mapping position have UMI difference <= <umi_diff_threshold>, then they will be merged to generate a "
+           "consensus read. Default value is 1.")
+    a("-D", "--duplex_diff_threshold", type=int, default=2,
+      help="if the forward consensus and reverse consensus sequences have <= <duplex_diff_threshold> mismatches, then they will be merged to "
+           "generate a duplex consensus sequence, otherwise will be discarded. Default value is 2.")
+    a("--high_qual", type=int, default=30, help="the threshold for a quality score to be considered as high quality. Default 30 means Q30.")
+    a("--moderate_qual", type=int, default=20, help="the threshold for a quality score to be considered as moderate quality. Default 20 means Q20.")
+    a("--low_qual", type=int, default=15, help="the threshold for a quality score to be considered as low quality. Default 15 means Q15.")
+    a("--coverage_sampling", type=int, default=10000, help="the sampling rate for genome scale coverage statistics. Default 10000 means 1/10000.")
+    # reporting
+    a("-j", "--json", default="gencore.json", help="the json format report file name")
+    a("-h", "--html", default=None, help="the html format report file name (accepted; the HTML report is not written)")
+    # debugging
+    a("--debug", action="store_true", help="output some debug information to STDERR. (accepted; does nothing)")
+    a("--quit_after_contig", type=int, default=0,
+      help="stop when <quit_after_contig> contigs are processed. Only used for fast debugging. Default 0 means no limitation.")
+    a("--help", action="help", help="print this message")
+    # not the reference's
+    a("--devices", default="0", help="[gencore_amd] HIP device ordinals, comma separated: one runs one engine, several run the sharded runner "
+                                     "(an ordinal may repeat). Default 0.")
+    a("--threads", type=int, default=0, help="[gencore_amd] host threads for the file codecs; 0 = all cores. Default 0.")
+    a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
+                                           "-2 (fixed Huffman on the GPU). Default 6.")
+    return p
+
+
+def check_file_valid(path):
+    """util.h:169-178"""
+    if not os.path.exists(path):
+        raise UsageError("ERROR: file '%s' doesn't exist, quit now" % path)
+    if os.path.isdir(path):
+        raise UsageError("ERROR: '%s' is a folder, not a file, quit now" % path)
+
+
+def validate(o):
+    """main.cpp:96-98, then Options::validate (options.cpp:42-111) in its order, then the BED file (bed.cpp:112-116) and this command's own checks."""
+    def err(msg):
+        raise UsageError("ERROR: " + msg)
+    if o.duplex_only and o.no_duplex:
+        err("You cannot enable both duplex_only and no_duplex")
+    if not o.input:
+        err("input should be specified by --in1")
+    check_file_valid(o.input)
+    if o.ref.endswith(".gz"):
+        raise UsageError("reference fasta file should not be compressed.\nplease unzip %s and try again." % o.ref)
+    checks = [
+        (o.ratio_threshold > 1.0, "ratio_threshold cannot be greater than 1.0"), (o.ratio_threshold < 0.5, "ratio_threshold cannot be less than 0.5"),
+        (o.supporting_reads > 10, "supporting_reads cannot be greater than 10"), (o.supporting_reads < 1, "supporting_reads cannot be less than 1"),
+        (o.score_threshold > 10, "score_threshold cannot be greater than 10"), (o.score_threshold < 1, "score_threshold cannot be less than 1"),
+        (o.high_qual > 40, "high_qual cannot be greater than 40"), (o.high_qual < 20, "high_qual cannot be less than 20"),
+        (o.moderate_qual > 35, "moderate_qual cannot be greater than 35"), (o.moderate_qual < 15, "moderate_qual cannot be less than 15"),
+        (o.low_qual > 30, "low_qual cannot be greater than 30"), (o.low_qual < 8, "low_qual cannot be less than 8"),
+        (o.umi_diff_threshold > 10, "umi_diff_threshold cannot be greater than 10"), (o.umi_diff_threshold < 0, "umi_diff_threshold cannot be negative"),
+        (o.low_qual > o.moderate_qual, "low_qual cannot be greater than moderate_qual"),
+        (o.moderate_qual > o.high_qual, "moderate_qual cannot be greater than high_qual"),
+        (o.duplex_diff_threshold > 10, "duplex_diff_threshold cannot be greater than 10, suggest 2."),
+        (o.duplex_diff_threshold < 0, "duplex_diff_threshold cannot be less than 0, suggest 2."),
+    ]
+    for bad, msg in checks:
+        if bad:
+            err(msg)
+    if o.bed:
+        check_file_valid(o.bed)
+    if o.coverage_sampling <= 0:                    # the reference divides by it (stats.cpp:43)
+        err("coverage_sampling should be greater than 0")
+    if len(o.umi_prefix.encode()) > 31:
+        err("umi_prefix cannot be longer than 31 characters")
+    try:
+        devices = [int(x) for x in o.devices.split(",")]
+    except ValueError:
+        devices = []
+    if not devices or min(devices) < 0:
+        err("devices should be a comma separated list of HIP device ordinals, got '%s'" % o.devices)
+    if not (-2 <= o.level <= 9):
+        err("level should be -2, -1 or 0..9")
+    return devices
+
+
+def params_of(o):
+    from .capi import default_params
+    return default_params(cluster_size_req=o.supporting_reads, score_percent_req=o.ratio_threshold, base_score_req=o.score_threshold,
+                          proper_umi_diff_threshold=o.umi_diff_threshold, duplex_mismatch_threshold=o.duplex_diff_threshold,
+                          high_quality=o.high_qual, moderate_quality=o.moderate_qual, low_quality=o.low_qual,
+                          duplex_only=int(o.duplex_only), disable_duplex=int(o.no_duplex), max_contig=o.quit_after_contig, umi_prefix=o.umi_prefix)
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    o = build_parser().parse_args(argv)
+    try:
+        devices = validate(o)
+    except UsageError as e:
+        print(str(e), file=sys.stderr)
+        return 255
+    t1 = int(time.time())
+    command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
+    if o.html is not None:
+        print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
+    from .bamio import load_bed, run_bam_depth
+    from .capi import GceError
+    from .report import read_header, summary, write_json
+    try:
+        names, _ = read_header(o.input)
+        region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
+        out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
+        _, depth = run_bam_depth(o.input, out, params_of(o), devices, o.coverage_sampling, bed=o.bed or None, fasta=o.ref or None,
+                                 threads=o.threads, level=o.level)
+        sys.stderr.write("----Before gencore processing:\n" + summary(depth["pre"], False) +
+                         "\n----After gencore processing:\n" + summary(depth["post"], True))
+        sys.stderr.flush()
+        write_json(o.json, depth, names, o.coverage_sampling, command, region_names=region_names, has_bed=bool(o.bed))
+    except (GceError, OSError) as e:
+        print("ERROR: %s" % e, file=sys.stderr)
+        return 255
+    t2 = int(time.time())
+    sys.stderr.write("\n%s\ngencore_amd v%s, time used: %d seconds\n" % (command, __version__, t2 - t1))
+    return 0

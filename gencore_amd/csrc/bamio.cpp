@@ -28,6 +28,7 @@
 #include <vector>
 #include "../../include/gencore_amd.h"
 #include "gce_samtext.hpp"
+#include "gce_report.hpp"
 
 static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 

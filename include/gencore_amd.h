@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GCE_ABI_VERSION 3              /* (struct layouts and the meaning of every v3 entry point are unchanged; gce_sam_to_bam / gce_bam_to_sam and SAM text in gce_run_bam were ADDED under v3) */
+#define GCE_ABI_VERSION 3              /* (struct layouts and the meaning of every v3 entry point are unchanged; gce_sam_to_bam / gce_bam_to_sam and SAM text in gce_run_bam, the report writers and gce_bam_read_header were ADDED under v3) */
 #define GCE_NONE 0xFFFFFFFFu           /* "no record" marker in uint32 index arrays */
 #define GCE_MAX_SUPPORTING_READS 100   /* src/stats.h:15 MAX_SUPPORTING_READS */
 
@@ -507,6 +507,23 @@ typedef struct gce_depth_run {
 int gce_run_bam_depth(const char *in_path, const char *out_path, const char *fasta_path, const char *bed_path, int32_t coverage_step, const gce_params *params,
                       int32_t n_shards, const int32_t *devices, int32_t plan_mode, int threads, int level, gce_bam_run *out, gce_depth_run *depth, char err[256]);
 void gce_depth_run_free(gce_depth_run *depth);
+
+/* The reference's reports, on the host (gencore_amd/csrc/gce_report.hpp; additions under ABI v3).
+ * Replaces: JsonReporter::report (src/jsonreporter.cpp:11-44) with Stats::reportJSON (src/stats.cpp:153-193) and Bed::reportJSON
+ * (src/bed.cpp:81-100), called by Gencore::report (src/gencore.cpp:39-44,292): the same bytes from the two Stats blocks and a gce_depth_run
+ * (gce_run_bam_depth).  target_name: depth->n_targets contig names (gce_bam_read_header); region_name: depth->n_regions names in the order of
+ * depth->region_* (gce_bed_load), NULL = empty names; has_bed: a BED file was given (Options::hasBedFile) -- the "coverage_bed" block is
+ * written, regions with tid -1 left out; command: the command line as the reference joins it (src/main.cpp:101-104). */
+int gce_report_json(const char *path, const gce_stats *pre, const gce_stats *post, const gce_depth_run *depth, const char *const *target_name,
+                    const char *const *region_name, int32_t has_bed, int32_t coverage_step, const char *command, char err[256]);
+/* Replaces: Stats::print (src/stats.cpp:195-215) for one block (is_post: Gencore's mPostStats) -- the text into buf (NUL-terminated);
+ * *len = its length without the NUL.  GCE_ERR_INVALID (with *len set) if cap < *len + 1. */
+int gce_report_summary(const gce_stats *stats, int32_t is_post, char *buf, size_t cap, size_t *len);
+/* Replaces: sam_hdr_read's contig table (src/gencore.cpp:180 via htslib) for a BAM or SAM file: contig names and lengths in header order.
+ * BAM: only the BGZF members the header spans are inflated; SAM text: the @SQ lines of the '@' lines in front of the first alignment.
+ * Arrays are malloc'ed; free them with gce_bam_header_free. */
+int gce_bam_read_header(const char *path, int32_t *n_targets, char ***target_name, uint32_t **target_len, char err[256]);
+void gce_bam_header_free(int32_t n_targets, char **target_name, uint32_t *target_len);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,39 @@ def run_bam_depth(in_path, out_path, params, devices, coverage_step, bed=None, f
     return run, out
 
 
+def run_bam_passes(in_path, out_path, params, device=0, coverage_step=1000000, bed=None, fasta=None, threads=0, level=6, device_budget_bytes=0, min_passes=0, window_bytes=0):
+    """gce_run_bam_passes: run_bam_depth on one device in key-range passes, device memory bounded by the largest pass (device_budget_bytes:
+    0 = auto; min_passes forces at least that many; window_bytes: compressed bytes per window, 0 = 64 MB).  Returns (run, depth dict as
+    run_bam_depth, pass dict(n_passes, single_pass, reads_per_pass, held_max, peak_device_bytes, budget_bytes, fixed_bytes, pass_room, total_weight,
+    key_pass_s, pass_s)))."""
+    from .capi import GceDepthRun, GcePassRun
+    lib = capi.load_library()
+    run, dr, pr = GceBamRun(), GceDepthRun(), GcePassRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_run_bam_passes(str(in_path).encode(), str(out_path).encode(), str(fasta).encode() if fasta else None, str(bed).encode() if bed else None, int(coverage_step),
+                                C.byref(params), int(device), threads, level, int(device_budget_bytes), int(min_passes), int(window_bytes), C.byref(run), C.byref(dr), C.byref(pr), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    arr = lambda p, n: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].copy()
+    nb, nr = int(dr.n_bins), int(dr.n_regions)
+    out = dict(bin_off=arr(dr.bin_off, dr.n_targets + 1), pre_depth=arr(dr.pre_depth, nb), post_depth=arr(dr.post_depth, nb),
+               regions=[(dr.region_tid[k], dr.region_start[k], dr.region_end[k]) for k in range(nr)], pre_bed=arr(dr.pre_bed, nr), post_bed=arr(dr.post_bed, nr),
+               pre=bytes(dr.pre), post=bytes(dr.post), payload_bytes=int(dr.payload_bytes))
+    lib.gce_depth_run_free(C.byref(dr))
+    P = int(pr.n_passes)
+    passes = dict(n_passes=P, single_pass=bool(pr.single_pass), reads_per_pass=[int(pr.reads_per_pass[k]) for k in range(P)], held_max=int(pr.held_max),
+                  peak_device_bytes=int(pr.peak_device_bytes), budget_bytes=int(pr.budget_bytes), fixed_bytes=int(pr.fixed_bytes), pass_room=int(pr.pass_room), total_weight=int(pr.total_weight), key_pass_s=float(pr.key_pass_s), pass_s=[float(pr.pass_s[k]) for k in range(P)])
+    return run, out, passes
+
+
+def device_bytes(reset_peak=False):
+    """gce_device_bytes: (live, peak) device bytes of the engine allocations of this process."""
+    lib = capi.load_library()
+    live, peak = C.c_int64(), C.c_int64()
+    lib.gce_device_bytes(C.byref(live), C.byref(peak), 1 if reset_peak else 0)
+    return int(live.value), int(peak.value)
+
+
 def write_batch_as_bam(path, batch, target_len, target_name=None, text="@HD\tVN:1.6\tSO:coordinate\n", threads=0, level=1):
     """gce_bam_from_batch: a ReadBatch as a BAM file (synthetic inputs for the end-to-end runs)."""
     lib = capi.load_library()

@@ -1,7 +1,8 @@
 """The gencore command line (src/main.cpp, src/options.cpp) over the HIP engine: `python -m gencore_amd -i in.bam -o out.bam -r ref.fa ...`.
 
-Flags, defaults and validation messages are the reference's; the run is gce_run_bam_depth (one engine, or the sharded runner for several
---devices); afterwards the two Stats summaries go to stderr and the JSON report is written (src/gencore.cpp:284-292, src/main.cpp:113-116).
+Flags, defaults and validation messages are the reference's; the run is gce_run_bam_passes on one device (gce_run_bam_depth's single pass when
+the file fits --device_memory, key-range passes otherwise) or gce_run_bam_depth's sharded runner for several --devices); afterwards the two
+Stats summaries go to stderr and the JSON report is written (src/gencore.cpp:284-292, src/main.cpp:113-116).
 Every check happens before the library is loaded, so a bad command line never touches a GPU."""
 import argparse
 import os
@@ -68,6 +69,8 @@ def build_parser():
     # not the reference's
     a("--devices", default="0", help="[gencore_amd] HIP device ordinals, comma separated: one runs one engine, several run the sharded runner "
                                      "(an ordinal may repeat). Default 0.")
+    a("--device_memory", default="auto", help="[gencore_amd] device memory budget in GB (2^30 bytes) for one device, or auto (a fraction of the free "
+                                               "memory): a file larger than the budget is processed in key-range passes. One device only. Default auto.")
     a("--threads", type=int, default=0, help="[gencore_amd] host threads for the file codecs; 0 = all cores. Default 0.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU). Default 6.")
@@ -123,6 +126,17 @@ def validate(o):
         err("devices should be a comma separated list of HIP device ordinals, got '%s'" % o.devices)
     if not (-2 <= o.level <= 9):
         err("level should be -2, -1 or 0..9")
+    o.device_memory_bytes = 0                       # 0: auto
+    if o.device_memory != "auto":
+        try:
+            gb = float(o.device_memory)
+        except ValueError:
+            gb = float("nan")
+        if not gb > 0 or gb == float("inf"):
+            err("device_memory should be a positive number of GB or auto, got '%s'" % o.device_memory)
+        if len(devices) > 1:
+            err("device_memory works on one device; it cannot be combined with several --devices")
+        o.device_memory_bytes = max(1, int(gb * (1 << 30)))
     return devices
 
 
@@ -146,15 +160,19 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import load_bed, run_bam_depth
+    from .bamio import load_bed, run_bam_depth, run_bam_passes
     from .capi import GceError
     from .report import read_header, summary, write_json
     try:
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
-        _, depth = run_bam_depth(o.input, out, params_of(o), devices, o.coverage_sampling, bed=o.bed or None, fasta=o.ref or None,
-                                 threads=o.threads, level=o.level)
+        if len(devices) == 1:                                               # passes when the file does not fit the budget (one pass: gce_run_bam_depth)
+            _, depth, _ = run_bam_passes(o.input, out, params_of(o), devices[0], o.coverage_sampling, bed=o.bed or None, fasta=o.ref or None,
+                                         threads=o.threads, level=o.level, device_budget_bytes=o.device_memory_bytes)
+        else:
+            _, depth = run_bam_depth(o.input, out, params_of(o), devices, o.coverage_sampling, bed=o.bed or None, fasta=o.ref or None,
+                                     threads=o.threads, level=o.level)
         sys.stderr.write("----Before gencore processing:\n" + summary(depth["pre"], False) +
                          "\n----After gencore processing:\n" + summary(depth["post"], True))
         sys.stderr.flush()

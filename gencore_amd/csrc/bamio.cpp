@@ -2001,4 +2001,402 @@ int gce_run_bam_sharded(const char *in_path, const char *out_path, const char *f
     return run_bam_impl(in_path, out_path, fasta_path, params, threads, 0, level, out, err, n_shards, devices, plan_mode);
 }
 
+
+// ---- one file in key-range passes on one device (gce_passes.hpp)
+struct gce_passes;
+int gce_passes_create(int32_t device, int32_t max_contig, int32_t flush_period, gce_passes **out);
+void gce_passes_destroy(gce_passes *p);
+const char *gce_passes_error(gce_passes *p);
+int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
+int gce_passes_window(gce_passes *p, gce_engine *e, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize,
+                      uint64_t skip, int32_t n_ref, int32_t last, int32_t *cut_reached);
+int gce_passes_plan(gce_passes *p, int32_t min_passes, uint64_t budget, uint64_t reserve, int32_t *P_out, uint64_t *total_w, uint64_t *per_pass, uint64_t *fixed_out);
+int gce_passes_info(gce_passes *p, int32_t k, uint64_t *weight, const uint64_t **cuts, int32_t *n_events, const int32_t **ev_tid, const int32_t **ev_pos);
+int gce_passes_begin(gce_passes *p, gce_engine *e, int32_t k);
+int gce_passes_end(gce_passes *p, gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t *n_records, int32_t *watermark_tid, int32_t *watermark_pos);
+int gce_passes_output(gce_passes *p, gce_engine *e, void *keys_host, void *body_host);
+int gce_passes_release(gce_passes *p, gce_engine *e);
+}  // extern "C" (declarations)
+extern "C++" {
+namespace {
+// the inflated record stream of a BGZF file, window by window: a piece of compressed bytes is inflated by the host threads behind what the
+// last window left over (the record its end cut); the window handed on is its whole records, with their offsets
+struct PassReader {
+    int fd = -1; uint64_t fsz = 0, at = 0; size_t piece = 8 << 20; int T = 1;
+    std::vector<uint8_t> comp; size_t have = 0;
+    Pinned win; size_t n = 0;
+    std::vector<Block> blocks; std::vector<uint64_t> z_coff; std::vector<uint32_t> z_csize, z_usize;
+    std::string msg;
+    size_t used = 0;                                 // compressed bytes of the members handed out last
+    void reset() { at = 0; have = 0; n = 0; used = 0; }
+    // the next piece's whole BGZF members -> blocks (their bytes at comp[0 ..]); 1: members, 0: end of the file, -1: error (msg)
+    int members_next() {
+        if (used) { memmove(comp.data(), comp.data() + used, have - used); have -= used; used = 0; }
+        if (at >= fsz) { if (have) { msg = "truncated BGZF block at the end of the file"; return -1; } return 0; }
+        const size_t want = (size_t)std::min<uint64_t>(piece, fsz - at);
+        if (comp.size() < have + want) comp.resize(have + want);
+        size_t o = 0;
+        while (o < want) { const ssize_t g = pread(fd, comp.data() + have + o, want - o, (off_t)(at + o)); if (g <= 0) break; o += (size_t)g; }
+        if (o != want) { msg = "cannot read the input BAM"; return -1; }
+        at += want; have += want;
+        blocks.clear();
+        size_t c = 0; uint64_t uoff = 0;
+        while (c + 18 <= have) {
+            const uint8_t *p = comp.data() + c;
+            if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) { msg = "not a BGZF file"; return -1; }
+            const uint16_t xlen = rd16(p + 10);
+            if (c + 12 + (size_t)xlen > have) break;
+            uint32_t bsize = 0; bool found = false;
+            for (uint32_t x = 0; x + 4 <= xlen; ) {
+                const uint8_t *sf = p + 12 + x; const uint16_t sl = rd16(sf + 2);
+                if (x + 4 + (uint32_t)sl > xlen) break;
+                if (sf[0] == 'B' && sf[1] == 'C' && sl == 2) { bsize = (uint32_t)rd16(sf + 4) + 1; found = true; }
+                x += 4 + sl;
+            }
+            if (!found || bsize < 12u + xlen + 8u) { msg = "bad BGZF block"; return -1; }
+            if (c + bsize > have) break;
+            Block b; b.coff = c; b.csize = bsize; b.usize = rd32(p + bsize - 4); b.uoff = n + uoff;
+            if (b.usize > 0x10000u) { msg = "bad BGZF block (ISIZE above 64 KB)"; return -1; }
+            blocks.push_back(b); c += bsize; uoff += b.usize;
+        }
+        if (blocks.empty() && at < fsz) { msg = "BGZF block larger than a window"; return -1; }
+        used = c;
+        return 1;
+    }
+    bool last_piece() const { return at >= fsz; }
+    // (the BAM header) the next piece inflated by the host threads behind win[0, n); 1: bytes added, 0: end of the file, -1: error (msg)
+    int inflate_next() {
+        const int g = members_next();
+        if (g <= 0) return g;
+        uint64_t uoff = 0;
+        for (Block &b : blocks) { b.uoff = n + uoff; uoff += b.usize; }
+        if (n + (size_t)uoff + 64 > win.cap) {                                       // (Pinned::ensure does not keep the bytes: the carry-over moves by hand)
+            Pinned nw;
+            if (!nw.ensure(n + (size_t)uoff + 64)) { msg = "out of pinned host memory"; return -1; }
+            if (n) memcpy(nw.p, win.p, n);
+            std::swap(win.p, nw.p); std::swap(win.cap, nw.cap);
+        }
+        std::atomic<int> bad{0};
+        parallel_for(T, (int64_t)blocks.size(), [&](int, int64_t a, int64_t b2) { for (int64_t q = a; q < b2; q++) if (blocks[q].usize && !inflate_block(comp.data() + blocks[q].coff, blocks[q], win.p + blocks[q].uoff)) bad = 1; });
+        if (bad) { msg = "inflate / CRC failure"; return -1; }
+        n += (size_t)uoff;
+        return 1;
+    }
+};
+// what the merge compares per output record (the 32-byte MergeKey of gce_raw_merge_outputs)
+struct PassKey { int32_t tid, pos, mtid, mpos, isize; uint32_t gidx, size, pad; };
+static_assert(sizeof(PassKey) == 32, "PassKey mirrors MergeKey");
+inline bool pass_less(const PassKey &a, const PassKey &b) {
+    if (a.tid != b.tid) return a.tid < b.tid;
+    if (a.pos != b.pos) return a.pos < b.pos;
+    if (a.mtid != b.mtid) return a.mtid < b.mtid;
+    if (a.mpos != b.mpos) return a.mpos < b.mpos;
+    if (a.isize != b.isize) return a.isize < b.isize;
+    return a.gidx < b.gidx;
+}
+// the output file of the pass runner: the record stream arrives in pieces, in order; BGZF blocks of 0xff00 bytes (host threads, or the GPU
+// encoder for level -2 as gce_raw_deflate_output), or SAM text for a name that ends in "sam"
+struct PassWriter {
+    FILE *fo = nullptr; int level = -1, T = 1; int32_t device = 0; bool sam = false; const std::vector<std::string> *names = nullptr;
+    std::vector<uint8_t> buf; Raw<uint8_t> zbuf; std::vector<uint8_t> gz; std::string line; bool ok = true;
+    static constexpr uint64_t BS = 0xff00, CH = BS * 256;
+    ~PassWriter() { if (fo) fclose(fo); }
+    bool host_blocks(const uint8_t *src, size_t n, int lv) {
+        const int64_t nb = (int64_t)((n + BS - 1) / BS);
+        std::vector<uint32_t> zs((size_t)nb, 0);
+        parallel_for(T, nb, [&](int, int64_t x, int64_t y) { for (int64_t q = x; q < y; q++) { const uint64_t o = (uint64_t)q * BS; zs[q] = (uint32_t)deflate_block(src + o, (uint32_t)std::min<uint64_t>(BS, n - o), lv, zbuf.data() + (size_t)q * 0x10000); } });
+        for (int64_t q = 0; q < nb; q++) if (zs[q] == 0 || fwrite(zbuf.data() + (size_t)q * 0x10000, 1, zs[q], fo) != zs[q]) return false;
+        return true;
+    }
+    bool flush(size_t n) {                               // the first n bytes of buf
+        if (!n) return true;
+        if (sam) {
+            size_t o = 0;
+            while (o < n) { const uint32_t bs = rd32(buf.data() + o); line.clear(); if (!samtext::bam_to_line(buf.data() + o, *names, line) || fwrite(line.data(), 1, line.size(), fo) != line.size()) return false; o += 4ull + bs; }
+        } else if (level == -2) {
+            size_t zb = 0;
+            if (gz.size() < n + n / 8 + 64 * (n / BS + 1) + 64) gz.resize(n + n / 8 + 64 * (n / BS + 1) + 64);
+            if (gce_bgzf_deflate(device, buf.data(), n, (uint32_t)BS, gz.data(), gz.size(), &zb) != GCE_OK || fwrite(gz.data(), 1, zb, fo) != zb) return false;
+        } else if (!host_blocks(buf.data(), n, level)) return false;
+        buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)n);
+        return true;
+    }
+    bool open(const char *path, const std::string &text, const std::vector<std::string> &nm, const std::vector<uint32_t> &lens, const std::vector<uint8_t> &hdr) {
+        const size_t pl = strlen(path); sam = pl >= 3 && strcmp(path + pl - 3, "sam") == 0; names = &nm;
+        fo = fopen(path, sam ? "w" : "wb");
+        if (!fo) return false;
+        if (sam) { const std::string ht = samtext::header_text_for_sam(text, nm, lens); return fwrite(ht.data(), 1, ht.size(), fo) == ht.size(); }
+        zbuf.resize((size_t)256 * 0x10000 + 64);
+        if (!zbuf.ok()) return false;
+        if (level == -2) return host_blocks(hdr.data(), hdr.size(), 1);          // (as gce_run_bam: the header's blocks by the host)
+        buf.assign(hdr.begin(), hdr.end());
+        return true;
+    }
+    bool records(const uint8_t *p, size_t n) {           // whole records
+        if (sam) { buf.insert(buf.end(), p, p + n); return flush(buf.size()); }
+        buf.insert(buf.end(), p, p + n);
+        while (buf.size() >= CH) if (!flush((size_t)CH)) return false;
+        return true;
+    }
+    bool close() {
+        bool good = flush(buf.size());
+        if (!sam) { static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0}; good = good && fwrite(eof_block, 1, 28, fo) == 28; }
+        good = fclose(fo) == 0 && good; fo = nullptr;
+        return good;
+    }
+};
+}  // namespace
+}  // extern "C++"
+extern "C" {
+
+int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fasta_path, const char *bed_path, int32_t coverage_step, const gce_params *params,
+                       int32_t device, int threads, int level, size_t device_budget_bytes, int32_t min_passes, size_t window_bytes,
+                       gce_bam_run *out, gce_depth_run *depth, gce_pass_run *run, char err[256]) {
+    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
+    seterr("");
+    if (!in_path || !out_path || !params || !out || !depth || !run || min_passes < 0 || min_passes > 64 || coverage_step <= 0) return GCE_ERR_INVALID;
+    memset(out, 0, sizeof *out); memset(run, 0, sizeof *run); memset(depth, 0, sizeof *depth);
+    const double t_start = now_s();
+    out->rss_start_kb = status_kb("VmRSS:");
+    (void)gce_device_bytes(nullptr, nullptr, 1);
+    auto peak_now = [&] { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); return pk; };
+    const bool auto_budget = device_budget_bytes == 0;
+    uint64_t budget = device_budget_bytes;
+    if (auto_budget) {
+        size_t fr = 0, tot = 0;
+        const int r0 = gce_device_mem_info(device, &fr, &tot);
+        if (r0 != GCE_OK) { seterr("no device"); return r0; }
+        budget = (uint64_t)((double)fr * GCE_PASS_BUDGET_FRACTION);
+    }
+    run->budget_bytes = (int64_t)budget;
+    struct stat st;
+    const int fd = open(in_path, O_RDONLY);
+    if (fd < 0) { seterr("cannot open the input BAM"); return GCE_ERR_INVALID; }
+    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the input BAM"); return GCE_ERR_INVALID; }
+    const uint64_t fsz = (uint64_t)st.st_size;
+    bool is_sam = false;
+    { uint8_t m2[2] = {0, 0}; is_sam = fsz > 0 && !(fsz >= 2 && pread(fd, m2, 2, 0) == 2 && m2[0] == 0x1f && m2[1] == 0x8b); }
+    // today's single-pass path (gce_run_bam_depth), unchanged, whenever the auto budget is in force and no passes are forced: at once when even a
+    // generous bound fits (measured, DESIGN.md 4b: peak ~6.2 x inflated bytes, inflated ~4.3 - 4.7 x the file; the bound takes 6.5 x 6), otherwise
+    // after the key pass when the plan needs one pass.  SAM text is never processed in passes; with the auto budget it always runs as today.
+    const bool single_ok = auto_budget && min_passes <= 1;
+    const uint64_t est = fsz * 39 + ((uint64_t)2 << 30);
+    auto single = [&]() -> int {
+        gce_params pr1 = *params; pr1.device = device;
+        const int r1 = gce_run_bam_depth(in_path, out_path, fasta_path, bed_path, coverage_step, &pr1, 1, &device, 0, threads, level, out, depth, err);
+        run->n_passes = 1; run->single_pass = 1; run->reads_per_pass[0] = out->n_reads; run->peak_device_bytes = peak_now(); run->pass_s[0] = out->total_s;
+        return r1;
+    };
+    if (is_sam) {
+        close(fd);
+        if (min_passes > 1) { seterr("SAM text input is not processed in passes"); return GCE_ERR_INVALID; }
+        if (!auto_budget && est > budget) {
+            char m[256]; snprintf(m, sizeof m, "SAM text input of %llu bytes needs an estimated %llu device bytes, the budget is %llu: SAM input is not processed in passes (convert it to BAM)",
+                                  (unsigned long long)fsz, (unsigned long long)est, (unsigned long long)budget);
+            seterr(m); return GCE_ERR_OOM;
+        }
+        return single();
+    }
+    if (single_ok && est <= budget) { close(fd); return single(); }
+    const int T = threads > 0 ? threads : default_threads();
+    gce_engine *e = nullptr; gce_fasta *fa = nullptr; gce_passes *p = nullptr;
+    auto done = [&](int code, const char *m) { seterr(m); if (p) gce_passes_destroy(p); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); close(fd); if (code != GCE_OK) gce_depth_run_free(depth); return code; };
+    // 64 MB of compressed bytes per window by default: the GPU inflate runs one lane per BGZF member and wants thousands of members per launch
+    // (8 MB windows, ~400 members each, made a cfg3 4 M pass 2.6 s instead of ~1 s)
+    PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? window_bytes : ((size_t)64 << 20);
+    // ---- the header (the first window(s))
+    std::vector<std::string> names; std::vector<uint32_t> lens; std::string text; uint64_t hdr_end = 0;
+    for (;;) {
+        const int g = rd.inflate_next();
+        if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str());
+        const uint8_t *u = rd.win.p; const uint64_t n = rd.n;
+        if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return done(GCE_ERR_INVALID, "not a BAM stream");
+        bool complete = false;
+        if (n >= 12) {
+            uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
+            if (q + l_text + 4 <= n) {
+                const uint64_t tp = q; q += l_text;
+                const uint32_t n_ref = rd32(u + q); q += 4;
+                names.clear(); lens.clear(); bool ok = true;
+                for (uint32_t r = 0; r < n_ref && ok; r++) {
+                    if (q + 4 > n) { ok = false; break; }
+                    const uint32_t ln = rd32(u + q); q += 4;
+                    if (ln == 0 || q + ln + 4 > n) { ok = false; break; }
+                    names.emplace_back((const char *)u + q, ln - 1); q += ln; lens.push_back(rd32(u + q)); q += 4;
+                }
+                if (ok && lens.empty()) return done(GCE_ERR_INVALID, "this SAM file has no header");
+                if (ok) { complete = true; hdr_end = q; text.assign((const char *)u + tp, l_text); }
+            }
+        }
+        if (complete) break;
+        if (g == 0) return done(GCE_ERR_INVALID, fsz ? "truncated header" : "empty file");
+    }
+    const std::vector<uint8_t> hdr_raw(rd.win.p, rd.win.p + hdr_end);
+    // ---- engine and reference (src/gencore.cpp:207-220: "auto" UMI prefix from the first record's name)
+    gce_params prm = *params; prm.device = device; prm.n_targets = (int32_t)lens.size(); prm.target_len = lens.data();
+    if (strcmp(prm.umi_prefix, "auto") == 0) {
+        memset(prm.umi_prefix, 0, sizeof prm.umi_prefix);
+        while (rd.n < hdr_end + 36 || rd.n < hdr_end + 36 + rd.win.p[hdr_end + 12]) { const int g = rd.inflate_next(); if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str()); if (g == 0) break; }
+        if (rd.n >= hdr_end + 36 && rd.n >= hdr_end + 36 + rd.win.p[hdr_end + 12]) gce_detect_umi_prefix((const char *)rd.win.p + hdr_end + 36, prm.umi_prefix);
+    }
+    int rc;
+    if ((rc = gce_create(&prm, &e)) != GCE_OK) return done(rc, gce_status_message(rc));
+    if (fasta_path && *fasta_path) {
+        if ((rc = gce_fasta_load(fasta_path, threads, &fa)) != GCE_OK) return done(rc, "cannot read the FASTA file");
+        int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr;
+        gce_fasta_get(fa, &nc, &ids, &seqs, &flen);
+        for (size_t t = 0; t < lens.size(); t++)
+            for (int32_t c = 0; c < nc; c++)
+                if (names[t] == ids[c] && (rc = gce_set_reference_ascii(e, (int32_t)t, seqs[c], flen[c])) != GCE_OK) return done(rc, gce_last_error(e));
+        gce_fasta_free(fa); fa = nullptr;
+    }
+    if ((rc = gce_passes_create(device, prm.max_contig, prm.flush_period, &p)) != GCE_OK) return done(rc, "pass state");
+    // ---- depth statistics (as gce_run_bam_depth)
+    if (bed_path && *bed_path) {
+        std::vector<const char *> np; for (auto &x : names) np.push_back(x.c_str());
+        if ((rc = gce_bed_load(bed_path, (int32_t)np.size(), np.data(), &depth->n_regions, &depth->region_tid, &depth->region_start, &depth->region_end, nullptr)) != GCE_OK) return done(rc, "cannot read the BED file");
+    }
+    {
+        const int nt = (int)lens.size();
+        depth->n_targets = nt;
+        depth->bin_off = (int64_t *)calloc((size_t)nt + 1, 8);
+        if (!depth->bin_off) return done(GCE_ERR_OOM, "out of host memory");
+        for (int t = 0; t < nt; t++) depth->bin_off[t + 1] = depth->bin_off[t] + 1 + (int64_t)lens[(size_t)t] / coverage_step;
+        const int64_t nb = depth->bin_off[nt];
+        depth->n_bins = nb;
+        depth->pre_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8); depth->post_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8);
+        depth->pre_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8); depth->post_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8);
+        if (!depth->pre_depth || !depth->post_depth || !depth->pre_bed || !depth->post_bed) return done(GCE_ERR_OOM, "out of host memory");
+        depth->payload_bytes = (2 * (int64_t)GCE_STATS_WORDS + 2 * nb + 2 * (int64_t)depth->n_regions) * 8;
+    }
+    // the file from its first byte, piece by piece: its BGZF members go to the GPU (gce_passes_window inflates and indexes them there; the
+    // header's bytes are passed over); e == NULL: the key pass
+    auto stream = [&](gce_engine *x) -> int {
+        rd.reset();
+        uint64_t skip = hdr_end;
+        for (;;) {
+            const int g = rd.members_next();
+            if (g < 0) { seterr(rd.msg.c_str()); return GCE_ERR_INVALID; }
+            if (g == 0) return GCE_OK;
+            rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
+            for (const Block &b : rd.blocks) { rd.z_coff.push_back(b.coff); rd.z_csize.push_back(b.csize); rd.z_usize.push_back(b.usize); u_all += b.usize; }
+            const uint64_t sk = std::min<uint64_t>(skip, u_all);
+            int32_t cut = 0;
+            const int r2 = gce_passes_window(p, x, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, prm.n_targets,
+                                             rd.last_piece() ? 1 : 0, &cut);
+            if (r2 != GCE_OK) { seterr(gce_passes_error(p)); return r2; }
+            skip -= sk;
+            if (cut || rd.last_piece()) return GCE_OK;
+        }
+    };
+    out->open_s = now_s() - t_start;
+    // ---- key pass
+    double t0 = now_s();
+    rc = stream(nullptr);
+    std::string kmsg;                                                                // (the key pass failed: why)
+    if (rc != GCE_OK) {
+        kmsg = err ? err : "";
+        if (rc == GCE_ERR_OOM) { char mm[200]; snprintf(mm, sizeof mm, "the key pass needs more device memory than the budget of %llu bytes", (unsigned long long)budget); kmsg = mm; }
+    } else if ((uint64_t)peak_now() > budget) {
+        char m[200]; snprintf(m, sizeof m, "the key pass needs %lld device bytes, the budget is %llu", (long long)peak_now(), (unsigned long long)budget); kmsg = m; rc = GCE_ERR_OOM;
+    }
+    int32_t P = 1; uint64_t total_w = 0, room = 0, fixed = 0;
+    // beside the weights: the engine's working set that does not scale with a pass's reads (measured: a pass of 43 MB of weight on cfg3 peaked
+    // 82 MB above the fixed part), hipCUB temporaries, the GPU encoder's 16 MB pieces
+    const uint64_t reserve = ((uint64_t)96 << 20) + (level == -2 ? ((uint64_t)64 << 20) : 0);
+    if (rc == GCE_OK && (rc = gce_passes_plan(p, std::max(min_passes, 1), budget, reserve, &P, &total_w, &room, &fixed)) != GCE_OK) kmsg = gce_passes_error(p);
+    if (rc != GCE_OK && single_ok) {                                                 // nothing written yet: the file goes the way it goes today
+        gce_passes_destroy(p); p = nullptr; gce_destroy(e); e = nullptr; close(fd);
+        gce_depth_run_free(depth);
+        return single();
+    }
+    if (rc != GCE_OK) return done(rc, kmsg.c_str());
+    run->n_passes = P; run->key_pass_s = now_s() - t0; run->fixed_bytes = (int64_t)fixed; run->pass_room = (int64_t)room; run->total_weight = (int64_t)total_w;
+    if (single_ok && P == 1) {                                                       // the plan fits one pass: today's path (the key pass only measured)
+        const double kp = run->key_pass_s;
+        gce_passes_destroy(p); p = nullptr; gce_destroy(e); e = nullptr; close(fd);
+        gce_depth_run_free(depth);
+        const int r1 = single();
+        run->key_pass_s = kp; run->fixed_bytes = (int64_t)fixed; run->pass_room = (int64_t)room; run->total_weight = (int64_t)total_w;
+        return r1;
+    }
+    // ---- the passes
+    PassWriter wr; wr.level = level; wr.T = T; wr.device = device;
+    std::vector<uint8_t> hdr_out;
+    {   // BAM magic, text, contig table (SAMv1 4.2), as gce_run_bam writes it
+        auto put32 = [&](uint32_t x) { const uint8_t *q = (const uint8_t *)&x; hdr_out.insert(hdr_out.end(), q, q + 4); };
+        hdr_out.insert(hdr_out.end(), {'B', 'A', 'M', 1});
+        put32((uint32_t)text.size()); hdr_out.insert(hdr_out.end(), text.begin(), text.end());
+        put32((uint32_t)lens.size());
+        for (size_t r = 0; r < lens.size(); r++) { put32((uint32_t)names[r].size() + 1); hdr_out.insert(hdr_out.end(), names[r].begin(), names[r].end()); hdr_out.push_back(0); put32(lens[r]); }
+    }
+    if (!wr.open(out_path, text, names, lens, hdr_out)) return done(GCE_ERR_INVALID, "cannot open the output file");
+    std::vector<PassKey> hk, pk, nk; std::vector<uint8_t> hb, pb, nb2, emit;
+    std::vector<int64_t> pay_sum;
+    int64_t *acc_pre = (int64_t *)&out->pre, *acc_post = (int64_t *)&out->post;
+    for (int32_t k = 0; k < P; k++) {
+        const double tp = now_s();
+        uint64_t wk = 0;                                                             // the pass's weight: A x its record bytes + B per read -> room for its records
+        if ((rc = gce_passes_info(p, k, &wk, nullptr, nullptr, nullptr, nullptr)) != GCE_OK) return done(rc, "pass weight");
+        if ((rc = gce_raw_begin(e, (size_t)(wk / GCE_PASS_WEIGHT_A) + hdr_raw.size())) != GCE_OK) return done(rc, gce_last_error(e));
+        int32_t tk;
+        if ((rc = gce_raw_push(e, hdr_raw.data(), hdr_raw.size(), &tk)) != GCE_OK || (rc = gce_submit_wait(e, tk)) != GCE_OK) return done(rc, gce_last_error(e));
+        if ((rc = gce_passes_begin(p, e, k)) != GCE_OK) return done(rc, gce_passes_error(p));
+        rc = stream(e);
+        if (rc != GCE_OK) { const std::string m = err ? err : ""; return done(rc, m.c_str()); }
+        int64_t n_rec = 0; int32_t wt = INT32_MAX, wp = INT32_MAX;
+        if ((rc = gce_passes_end(p, e, hdr_end, prm.n_targets, &n_rec, &wt, &wp)) != GCE_OK) return done(rc, gce_passes_error(p));
+        run->reads_per_pass[k] = n_rec;
+        pk.clear(); pb.clear();
+        if (n_rec > 0) {
+            gce_result res; uint64_t body = 0; int64_t n_out = 0;
+            if ((rc = gce_process(e)) != GCE_OK) return done(rc, gce_last_error(e)[0] ? gce_last_error(e) : gce_status_message(rc));
+            gce_timing tm; if (gce_get_timing(e, &tm) == GCE_OK) out->kernel_ms += tm.total_ms;
+            if ((rc = gce_result_device(e, &res)) != GCE_OK) return done(rc, gce_last_error(e));
+            out->n_reads += res.n_reads; out->n_out += res.n_out;
+            for (int w = 0; w < GCE_STATS_WORDS; w++) { acc_pre[w] += ((const int64_t *)&res.pre)[w]; acc_post[w] += ((const int64_t *)&res.post)[w]; }
+            if ((rc = gce_raw_build_output(e, &body, &n_out)) != GCE_OK) return done(rc, gce_last_error(e));
+            const int64_t *pay = nullptr; gce_payload_layout lay;
+            if ((rc = gce_stats_payload_device(e, coverage_step, depth->n_regions, depth->region_tid, depth->region_start, depth->region_end, &pay, &lay)) != GCE_OK) return done(rc, gce_last_error(e));
+            std::vector<int64_t> host((size_t)lay.total_words);
+            if ((rc = gce_stats_payload_read(e, pay, lay.total_words, host.data())) != GCE_OK) return done(rc, gce_last_error(e));
+            if (pay_sum.empty()) pay_sum.assign(host.size(), 0);
+            if (pay_sum.size() != host.size()) return done(GCE_ERR_INVALID, "payload layout");
+            for (size_t w = 0; w < host.size(); w++) pay_sum[w] += host[w];
+            pk.resize((size_t)n_out); pb.resize((size_t)body);
+            if ((rc = gce_passes_output(p, e, pk.data(), pb.data())) != GCE_OK) return done(rc, gce_passes_error(p));
+        }
+        if ((rc = gce_passes_release(p, e)) != GCE_OK) return done(rc, "release");
+        // ---- merge: the held records and this pass's (both in bamComp order); below the watermark they are final
+        const bool last = k == P - 1;
+        auto below = [&](const PassKey &x) { return last || x.tid < wt || (x.tid == wt && x.pos < wp); };
+        nk.clear(); nb2.clear(); emit.clear();
+        size_t a = 0, b = 0, ao = 0, bo = 0;
+        while (a < hk.size() || b < pk.size()) {
+            const bool take_a = b >= pk.size() || (a < hk.size() && pass_less(hk[a], pk[b]));
+            const PassKey &x = take_a ? hk[a] : pk[b];
+            const uint8_t *src = take_a ? hb.data() + ao : pb.data() + bo;
+            if (below(x)) emit.insert(emit.end(), src, src + x.size); else { nk.push_back(x); nb2.insert(nb2.end(), src, src + x.size); }
+            if (take_a) { ao += x.size; a++; } else { bo += x.size; b++; }
+        }
+        if (ao != hb.size() || bo != pb.size()) return done(GCE_ERR_INVALID, "merge: record sizes do not add up");
+        if (!emit.empty() && !wr.records(emit.data(), emit.size())) return done(GCE_ERR_INVALID, "cannot write the output file");
+        hk.swap(nk); hb.swap(nb2);
+        run->held_max = std::max<int64_t>(run->held_max, (int64_t)hk.size());
+        run->pass_s[k] = now_s() - tp;
+    }
+    if (!wr.close()) return done(GCE_ERR_INVALID, "cannot write the output file");
+    if (!pay_sum.empty()) {
+        const int64_t nb = depth->n_bins; const int32_t nreg = depth->n_regions;
+        memcpy(&depth->pre, pay_sum.data(), sizeof(gce_stats)); memcpy(&depth->post, pay_sum.data() + GCE_STATS_WORDS, sizeof(gce_stats));
+        const int64_t *d0 = pay_sum.data() + 2 * GCE_STATS_WORDS;
+        memcpy(depth->pre_depth, d0, (size_t)nb * 8); memcpy(depth->post_depth, d0 + nb, (size_t)nb * 8);
+        memcpy(depth->pre_bed, d0 + 2 * nb, (size_t)nreg * 8); memcpy(depth->post_bed, d0 + 2 * nb + nreg, (size_t)nreg * 8);
+    }
+    run->peak_device_bytes = peak_now();
+    out->total_s = now_s() - t_start;
+    out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
+    return done(GCE_OK, "");
+}
+
 }  // extern "C"

@@ -25,20 +25,26 @@ namespace {
 // what the calling thread spent in hipMalloc / hipFree (GCE_RAW_TIMING prints it per gce_process: the question behind the sharded runner's slow boxes)
 static thread_local double t_alloc_s = 0.0; static thread_local long t_alloc_n = 0; static thread_local size_t t_alloc_bytes = 0;
 static inline double mono_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+// live / peak device bytes of the process (DevBuf, PlanBuf): gce_device_bytes
+long long g_dev_live = 0, g_dev_peak = 0;
+inline void dev_bytes_add(long long d) {
+    const long long now = __atomic_add_fetch(&g_dev_live, d, __ATOMIC_RELAXED);
+    long long pk = __atomic_load_n(&g_dev_peak, __ATOMIC_RELAXED);
+    while (now > pk && !__atomic_compare_exchange_n(&g_dev_peak, &pk, now, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
 struct DevBuf {
     void *p = nullptr; size_t cap = 0;
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap && p) return hipSuccess;
         const double t0 = mono_s();
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
+        release();
         size_t want = bytes + bytes / 8 + 256;
         hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess) { cap = want; dev_bytes_add((long long)want); } else p = nullptr;
         t_alloc_s += mono_s() - t0; t_alloc_n++; t_alloc_bytes += want;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) { (void)hipFree(p); dev_bytes_add(-(long long)cap); } p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
 };
 
@@ -1294,3 +1300,4 @@ int gce_get_vote_counters(gce_engine *e, int64_t out[4]) {
 
 #include "gce_plan.hpp"
 #include "gce_bamdev.hpp"
+#include "gce_passes.hpp"

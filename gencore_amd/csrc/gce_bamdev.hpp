@@ -34,17 +34,21 @@ __device__ __forceinline__ bool raw_plausible(const uint8_t *u, uint64_t o, uint
     if (32ull + lq + 4ull * nc + (uint64_t)(ls + 1) / 2 + (uint64_t)ls > bs) return false;
     return r[32 + lq - 1] == 0;
 }
-// records starting in [o, hi): count, optionally their offsets; returns where the chain leaves the range (~0 = broken chain)
+// records starting in [o, hi): count, optionally their offsets; returns where the chain leaves the range (~0 = broken chain).  SOFT (a window
+// of the pass runner, whose end cuts a record): a record that does not fit in n ends the chain there instead of breaking it
+template <bool SOFT = false>
 __device__ __forceinline__ uint64_t raw_walk(const uint8_t *u, uint64_t o, uint64_t hi, uint64_t n, uint32_t &cnt, uint64_t *out) {
     while (o < hi && o + 4 <= n) {
         const uint32_t bs = rb32(u + o);
-        if (bs < 32 || o + 4 + bs > n) return ~0ull;
+        if (bs < 32) return ~0ull;
+        if (o + 4 + bs > n) return SOFT ? o : ~0ull;
         if (out) out[cnt] = o;
         cnt++;
         o += 4ull + bs;
     }
     return o;
 }
+template <bool SOFT = false>
 __global__ __launch_bounds__(256) void k_raw_seg(const uint8_t *u, uint64_t first, uint64_t n, int32_t nref, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
@@ -56,14 +60,15 @@ __global__ __launch_bounds__(256) void k_raw_seg(const uint8_t *u, uint64_t firs
     }
     uint32_t c = 0;
     guess[s] = o;
-    leave[s] = raw_walk(u, o, hi, n, c, nullptr);
+    leave[s] = raw_walk<SOFT>(u, o, hi, n, c, nullptr);
     cnt[s] = c;
 }
 // every segment's guess must be where the chain of the segment in front of it leaves: flag = number of segments for which it is not
+template <bool SOFT = false>
 __global__ __launch_bounds__(256) void k_raw_check(const uint64_t *guess, const uint64_t *leave, uint64_t nseg, uint64_t n, unsigned int *bad, uint8_t *bad_of) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
-    const bool b = leave[s] == ~0ull || (s > 0 && guess[s] != leave[s - 1]) || (s == nseg - 1 && leave[s] != n);
+    const bool b = leave[s] == ~0ull || (s > 0 && guess[s] != leave[s - 1]) || (s == nseg - 1 && (SOFT ? leave[s] > n : leave[s] != n));
     bad_of[s] = b;
     if (b) atomicAdd(bad, 1u);
 }
@@ -72,6 +77,7 @@ __global__ __launch_bounds__(256) void k_raw_check(const uint64_t *guess, const 
 // segment, which also puts the NEXT segment off the chain although its own guess is right.  Every round re-walks the flagged segments
 // whose predecessor is NOT flagged (that one's chain is final, nothing it reads changes in the round) from where that chain leaves; the
 // check that follows clears the neighbours.  Rounds = the longest run of truly wrong segments (records longer than a segment).
+template <bool SOFT = false>
 __global__ __launch_bounds__(256) void k_raw_fix(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt, const uint8_t *bad_of, unsigned int *changed, unsigned int *broken) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg || s == 0 || !bad_of[s] || bad_of[s - 1]) return;
@@ -79,12 +85,13 @@ __global__ __launch_bounds__(256) void k_raw_fix(const uint8_t *u, uint64_t firs
     if (at == ~0ull) return;
     const uint64_t hi = min(n, first + s * RAW_SEG + RAW_SEG);
     uint32_t c = 0; uint64_t x = at;
-    if (at < hi) { x = raw_walk(u, at, hi, n, c, nullptr); if (x == ~0ull) { *broken = 1u; return; } }
+    if (at < hi) { x = raw_walk<SOFT>(u, at, hi, n, c, nullptr); if (x == ~0ull) { *broken = 1u; return; } }
     guess[s] = at; leave[s] = x; cnt[s] = c;
     *changed = 1u;
 }
 // the last resort (after several parallel rounds): ONE thread follows the chain from segment to segment
 // and re-walks only the segments whose guess does not lie on it
+template <bool SOFT = false>
 __global__ void k_raw_repair(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt, unsigned int *broken) {
     if (blockIdx.x || threadIdx.x) return;
     uint64_t at = first;
@@ -93,20 +100,21 @@ __global__ void k_raw_repair(const uint8_t *u, uint64_t first, uint64_t n, uint6
         if (at >= hi) { guess[s] = at; leave[s] = at; cnt[s] = 0; continue; }       // a record spans the whole segment
         if (guess[s] != at || leave[s] == ~0ull) {
             uint32_t c = 0;
-            const uint64_t x = raw_walk(u, at, hi, n, c, nullptr);
+            const uint64_t x = raw_walk<SOFT>(u, at, hi, n, c, nullptr);
             if (x == ~0ull) { *broken = 1u; return; }
             guess[s] = at; leave[s] = x; cnt[s] = c;
         }
         at = leave[s];
     }
-    if (at != n) *broken = 1u;
+    if (SOFT ? at > n : at != n) *broken = 1u;
 }
+template <bool SOFT = false>
 __global__ __launch_bounds__(256) void k_raw_offsets(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, const uint64_t *guess, const uint64_t *base, uint64_t *rec_off) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
     const uint64_t hi = min(n, first + s * RAW_SEG + RAW_SEG);
     uint32_t c = 0;
-    (void)raw_walk(u, guess[s], hi, n, c, rec_off + base[s]);
+    (void)raw_walk<SOFT>(u, guess[s], hi, n, c, rec_off + base[s]);
 }
 // bytes of an aux value behind its type byte, or ~0 (bamio.cpp aux_size)
 __device__ __forceinline__ uint64_t raw_aux_size(uint8_t type, const uint8_t *p, const uint8_t *end) {
@@ -539,8 +547,8 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
         HIPCHK(e->rw_guess.ensure(nseg * 8)); HIPCHK(e->rw_leave.ensure(nseg * 8)); HIPCHK(e->rw_cnt.ensure(nseg * 4 + 8)); HIPCHK(e->rw_base.ensure(nseg * 8 + 8)); HIPCHK(e->rw_misc.ensure(64)); HIPCHK(e->rw_bad.ensure(nseg + 8));
         HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 64, s));
         const unsigned nbs = (unsigned)((nseg + 255) / 256);
-        hipLaunchKernelGGL(k_raw_seg, dim3(nbs), dim3(256), 0, s, u, records_begin, total, n_ref, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_raw_check, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
+        hipLaunchKernelGGL(k_raw_seg<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, n_ref, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>());
+        hipLaunchKernelGGL(k_raw_check<false>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
         unsigned int flags[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
         lap("segment walks + check");
@@ -553,15 +561,15 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
         }
         for (int round = 0; flags[0] && round < 64; round++) {                           // parallel repair rounds
             HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_fix, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), (const uint8_t *)e->rw_bad.p, e->rw_misc.as<unsigned int>() + 3, e->rw_misc.as<unsigned int>() + 1);
-            hipLaunchKernelGGL(k_raw_check, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
+            hipLaunchKernelGGL(k_raw_fix<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), (const uint8_t *)e->rw_bad.p, e->rw_misc.as<unsigned int>() + 3, e->rw_misc.as<unsigned int>() + 1);
+            hipLaunchKernelGGL(k_raw_check<false>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
             HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
             if (flags[1]) return fail(e, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
         }
         lap("parallel repair");
         if (flags[0]) {
             HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_repair, dim3(1), dim3(64), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), e->rw_misc.as<unsigned int>() + 1);
+            hipLaunchKernelGGL(k_raw_repair<false>, dim3(1), dim3(64), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), e->rw_misc.as<unsigned int>() + 1);
             HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
             if (flags[1]) return fail(e, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
             lap("repair");
@@ -571,7 +579,7 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
         if (n_rec >= 0x7FFFFFF0ull) return fail(e, GCE_ERR_INVALID, "more than 2^31 records in one stream");
         lap("segments + scan");
         HIPCHK(e->rw_off.ensure((size_t)(n_rec + 1) * 8));
-        hipLaunchKernelGGL(k_raw_offsets, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_base.p, e->rw_off.as<uint64_t>());
+        hipLaunchKernelGGL(k_raw_offsets<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_base.p, e->rw_off.as<uint64_t>());
     }
     const size_t n1 = (size_t)(n_rec ? n_rec : 1);
     HIPCHK(e->b_core.ensure(n1 * sizeof(gce_core) + 64)); HIPCHK(e->b_qoff.ensure(n1 * 8 + 64)); HIPCHK(e->b_coff.ensure(n1 * 8 + 64)); HIPCHK(e->b_soff.ensure(n1 * 8 + 64)); HIPCHK(e->b_loff.ensure(n1 * 8 + 64));

@@ -9,7 +9,8 @@ Two granularities:
     order.  Every read then carries its global tick (gce_batch.tick) and every shard gets the flush events of the whole
     stream (gce_set_flush_events): which clusters a flush takes, and hence the UMI threshold a cluster gets (quirk Q1),
     comes out exactly as in the unsharded stream.  mode="range": contiguous key ranges balanced by read count;
-    mode="lpt": clusters dealt to the least loaded shard, heaviest first, weighted by depth^2 (ultra-deep hotspots)."""
+    mode="lpt": clusters dealt to the least loaded shard, heaviest first, weighted by depth^2 (ultra-deep hotspots);
+    mode="weight": contiguous key ranges balanced by the pass runner's estimate of device bytes (weighted_cuts)."""
 import numpy as np
 
 from .batch import ReadBatch
@@ -128,10 +129,60 @@ def stream_context(core, flush_period=10000):
     return tick, core["tid"][ev].astype(np.int32), core["pos"][ev].astype(np.int32)
 
 
+# the estimator of the pass runner (include/gencore_amd.h GCE_PASS_WEIGHT_A / _B): a read stands for A x its record bytes + B device bytes
+PASS_WEIGHT_A, PASS_WEIGHT_B = 6, 1024
+
+
+def cluster_key(core):
+    """(tid, left) of the cluster key as one int64, unmapped reads last (k_plan_keys)."""
+    tid = core["tid"].astype(np.int64)
+    return (np.where(tid < 0, np.int64(1) << 30, tid) << 32) | cluster_left(core).clip(0).astype(np.int64)
+
+
+def pass_weights(core, record_bytes=None):
+    """Weight of every read: A x record bytes + B.  Without the record sizes (gce_plan_shards sees the key records only) the record is its
+    fixed fields -- block_size, core, name, CIGAR, bases, qualities -- without the aux area."""
+    if record_bytes is None:
+        lq, nc, ls = (core[k].astype(np.int64) for k in ("l_qname", "n_cigar", "l_qseq"))
+        record_bytes = 36 + lq + 4 * nc + (ls + 1) // 2 + ls
+    return np.minimum(PASS_WEIGHT_A * np.asarray(record_bytes, np.int64) + PASS_WEIGHT_B, 0xFFFFFFFF).astype(np.uint64)
+
+
+def weighted_cuts(key, weight, world):
+    """world - 1 cut keys of contiguous key ranges balanced by weight (mode 2 of gce_plan_shards): cut r is the key of the first read, in key
+    order, whose inclusive weight sum passes total x r / world.  A key range takes whole keys: read i is in range searchsorted(cuts, key, right)."""
+    if len(key) == 0:
+        return np.full(world - 1, np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+    order = np.argsort(key, kind="stable")
+    srt = np.asarray(key, np.uint64)[order]
+    cum = np.cumsum(np.asarray(weight, np.uint64)[order], dtype=np.uint64)
+    total = int(cum[-1])
+    at = [min(len(srt) - 1, int(np.searchsorted(cum * np.uint64(world), np.uint64(total * r), side="right"))) for r in range(1, world)]
+    return srt[at] if at else np.zeros(0, np.uint64)
+
+
+def pass_watermarks(core, shard, world):
+    """W_k for k < world: the smallest (tid, pos) of any read of a range > k that can emit a record ((INT32_MAX, INT32_MAX) when there is
+    none).  From the reads themselves: a read's own position may lie in front of its key (isize's sign need not agree with the mates'
+    positions).  Unmapped reads (tid < 0 or pos < 0) are never written (gencore.cpp:254-265): they hold nothing back."""
+    tid, pos = core["tid"].astype(np.int64), core["pos"].astype(np.int64)
+    out = []
+    for k in range(world):
+        m = (shard > k) & (tid >= 0) & (pos >= 0)
+        if not m.any():
+            out.append((2 ** 31 - 1, 2 ** 31 - 1))
+            continue
+        v = (tid[m] << 32) + pos[m]
+        j = int(np.argmin(v))
+        out.append((int(tid[m][j]), int(pos[m][j])))
+    return out
+
+
 def plan_shards(core, world, mode="range"):
     """Shard number of every read.  All reads of one cluster key (tid, left) get the same shard; unmapped reads go last."""
-    tid = core["tid"].astype(np.int64)
-    key = (np.where(tid < 0, np.int64(1) << 30, tid) << 32) | cluster_left(core).clip(0).astype(np.int64)
+    key = cluster_key(core)
+    if mode == "weight":
+        return np.searchsorted(weighted_cuts(key.astype(np.uint64), pass_weights(core), world), key.astype(np.uint64), side="right").astype(np.int32)
     if mode == "range":
         srt = np.sort(key)
         cuts = np.asarray([srt[min(len(srt) - 1, (len(srt) * r) // world)] for r in range(1, world)], np.int64) if len(srt) else np.zeros(0, np.int64)
@@ -170,7 +221,7 @@ def plan_shards_gpu(core, world, mode="range", device=0):
     lib = capi.load_library()
     core = np.ascontiguousarray(core)
     out = np.zeros(len(core), np.int32)
-    rc = lib.gce_plan_shards(device, core.ctypes.data, len(core), world, 0 if mode == "range" else 1, out.ctypes.data)
+    rc = lib.gce_plan_shards(device, core.ctypes.data, len(core), world, {"range": 0, "lpt": 1, "weight": 2}[mode], out.ctypes.data)
     if rc != 0:
         raise capi.GceError(rc, "gce_plan_shards")
     return out

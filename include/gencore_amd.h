@@ -325,7 +325,9 @@ int gce_stats_device(gce_engine *e, const int64_t **pre_then_post);
 int gce_stream_context(int32_t device, const gce_core *core, int64_t n_reads, int32_t flush_period, uint64_t *tick_out,
                        int32_t *n_events, int32_t **ev_tid, int32_t **ev_pos);
 /* shard_out[i] in [0, world): mode 0 = contiguous key ranges of equal read count (configs[3]: the cuts fall inside contigs),
- * mode 1 = whole clusters dealt longest-processing-time first with weight reads^2 (configs[4]: ultra-deep hotspots).  world <= 64. */
+ * mode 1 = whole clusters dealt longest-processing-time first with weight reads^2 (configs[4]: ultra-deep hotspots);
+ * mode 2 = contiguous key ranges balanced by the pass runner's weight, GCE_PASS_WEIGHT_A x the record's fixed fields + GCE_PASS_WEIGHT_B
+ * (addition under ABI v3; gce_run_bam_passes plans the same way with the records' full sizes).  world <= 64. */
 int gce_plan_shards(int32_t device, const gce_core *core, int64_t n_reads, int32_t world, int32_t mode, int32_t *shard_out);
 void gce_free(void *p);
 /* Drop all submitted reads/results but keep params, reference and allocations (for repeated bench steps). */
@@ -507,6 +509,46 @@ typedef struct gce_depth_run {
 int gce_run_bam_depth(const char *in_path, const char *out_path, const char *fasta_path, const char *bed_path, int32_t coverage_step, const gce_params *params,
                       int32_t n_shards, const int32_t *devices, int32_t plan_mode, int threads, int level, gce_bam_run *out, gce_depth_run *depth, char err[256]);
 void gce_depth_run_free(gce_depth_run *depth);
+
+/* gce_run_bam_depth on ONE device for a file of any size (addition under ABI v3; gencore_amd/csrc/gce_passes.hpp): the stream is
+ * processed in P key-range passes so that device memory is bounded by the largest pass, not by the file.  A key pass streams the file once and
+ * keeps 12 bytes per read (cluster key and weight); the plan cuts the cluster keys into P contiguous ranges balanced by weight (gce_plan_shards
+ * mode 2); pass k streams the file again and keeps only the records of range k, with their global ticks and the flush events of the whole
+ * stream; its output records below the smallest (tid, pos) of any later pass's read are written, the rest are held for the next pass's merge
+ * (bamComp order with the input index as the last key, as gce_raw_merge_outputs).  Records, order, Stats, depth and BED counts equal
+ * gce_run_bam_depth's.
+ *   device_budget_bytes: 0 = auto, GCE_PASS_BUDGET_FRACTION of the device's free memory (hipMemGetInfo) when the call starts;
+ *   min_passes: at least this many passes (tests force P with it); with auto and min_passes <= 1 a file whose estimate fits in one pass runs
+ *     gce_run_bam_depth's single-pass path unchanged;
+ *   window_bytes: compressed bytes per window, 0 = 64 MB (the GPU inflate wants thousands of BGZF members per launch).
+ * GCE_ERR_OOM (before any output record is written) when the budget cannot hold the fixed part of a pass or the key pass's state, or one
+ * cluster key outweighs a pass.  With the auto budget and min_passes <= 1 the single-pass path runs whenever the plan needs one pass (or the
+ * key pass / plan cannot be made): behaviour changes only for files that do not fit.  SAM text input is not processed in passes: with the
+ * auto budget it runs the single-pass path; GCE_ERR_OOM when an explicit budget is below its estimate, GCE_ERR_INVALID when min_passes > 1.
+ * run->peak_device_bytes: the most device bytes the process's engine allocations held at once during the call (gce_device_bytes). */
+#define GCE_PASS_BUDGET_FRACTION 0.85
+/* The estimator: a read stands for GCE_PASS_WEIGHT_A x its record bytes + GCE_PASS_WEIGHT_B device bytes in a pass. */
+#define GCE_PASS_WEIGHT_A 6u
+#define GCE_PASS_WEIGHT_B 1024u
+typedef struct gce_pass_run {
+    int32_t  n_passes;
+    int32_t  single_pass;           /* 1: the single-pass path ran (auto, the estimate fits) */
+    int64_t  reads_per_pass[64];    /* records given to each pass's engine */
+    int64_t  held_max;              /* the most output records held across a pass boundary */
+    int64_t  peak_device_bytes;
+    int64_t  budget_bytes;          /* the budget the plan used */
+    int64_t  fixed_bytes;           /* device bytes live beside a pass's own: engine, reference, window buffers */
+    int64_t  pass_room;             /* weight one pass may hold: budget - fixed part - reserve (0: passes forced without a budget) */
+    int64_t  total_weight;          /* the estimator's weight of the stream (GCE_PASS_WEIGHT_A x record bytes + GCE_PASS_WEIGHT_B per read) */
+    double   key_pass_s;
+    double   pass_s[64];
+} gce_pass_run;
+int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fasta_path, const char *bed_path, int32_t coverage_step, const gce_params *params,
+                       int32_t device, int threads, int level, size_t device_budget_bytes, int32_t min_passes, size_t window_bytes,
+                       gce_bam_run *out, gce_depth_run *depth, gce_pass_run *run, char err[256]);
+/* Live and peak device bytes of the engine allocations of the whole PROCESS (every engine, every thread); reset_peak != 0 restarts the peak at
+ * the live count.  gce_run_bam_passes resets it on entry: its run->peak_device_bytes covers other engines working in the same process as well. */
+int gce_device_bytes(int64_t *live, int64_t *peak, int32_t reset_peak);
 
 /* The reference's reports, on the host (gencore_amd/csrc/gce_report.hpp; additions under ABI v3).
  * Replaces: JsonReporter::report (src/jsonreporter.cpp:11-44) with Stats::reportJSON (src/stats.cpp:153-193) and Bed::reportJSON

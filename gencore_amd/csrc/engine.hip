@@ -102,7 +102,7 @@ struct gce_engine {
     DevBuf sh_tickall, sh_shard, sh_flag, sh_sel, sh_core, sh_qoff, sh_coff, sh_soff, sh_loff, sh_nm, sh_nmt, sh_mioff, sh_tick, sh_roff, sh_nmpos, sh_keys, sh_stage; int64_t shard_n = -1;
     bool shard_cut_done = false;          // gce_raw_select_shard applied --quit_after_contig to the WHOLE stream: this engine's gce_process does not look for the cut again
     bool tab_clean = false; const void *tab_clean_ptr = nullptr;   // the bucket table is all-zero (k_scatter wipes what a step used)
-    DevBuf cl_ikey, cl_start, cl_n, cl_npairs, cl_ngroups, cl_gbase, cl_nresult, cl_hasumi;
+    DevBuf cl_ikey, cl_start, cl_n, cl_npairs, cl_ngroups, cl_gbase, cl_nresult, cl_hasumi, cl_tier;
     DevBuf members, sorted, pl, pr, pu, pg, gpl, gpr, grp_begin, grp_n, gl_cluster, g_begin, g_np;
     DevBuf slow_args, deep_list, k64, slow_list, left_list, pf_flag, pf_list, pq_flag, pq_list, p16_flag, p16_list, pd_slab, gen_flag, gen_list, score_list, gw, g_wbase, vb_start, rp_left, rp_right, rp_merge, rp_rmerge, rp_umi, rp_umilen, rp_state, rp_supp, rp_nm, rp_qsl, rp_qsr, scan_part, si;
     StreamInfo h_si{};
@@ -183,7 +183,7 @@ void gce_destroy(gce_engine *e) {
                      &e->slot, &e->score, &e->out_flag, &e->orec, &e->out_index, &e->nmx, &e->o_src, &e->o_kind, &e->o_qsrc, &e->o_nm, &e->o_fr, &e->o_rr, &e->o_mate,
                      &e->o_key, &e->o_rec, &e->o_ksoff, &e->o_kqoff, &e->o_krow, &e->o_rank64, &e->o_part3, &e->o_soff, &e->o_qoff, &e->o_seq, &e->o_qual, &e->ref_ascii, &e->lrec, &e->lout, &e->bhdr,
                      &e->blk_base, &e->ev_tid, &e->ev_pos, &e->ev_read, &e->table, &e->toff, &e->cl_ikey, &e->cl_start, &e->cl_n,
-                     &e->cl_npairs, &e->cl_ngroups, &e->cl_gbase, &e->cl_nresult, &e->cl_hasumi, &e->members, &e->sorted, &e->pl, &e->pr, &e->pu,
+                     &e->cl_npairs, &e->cl_ngroups, &e->cl_gbase, &e->cl_nresult, &e->cl_hasumi, &e->cl_tier, &e->members, &e->sorted, &e->pl, &e->pr, &e->pu,
                      &e->pg, &e->gpl, &e->gpr, &e->grp_begin, &e->grp_n, &e->gl_cluster, &e->g_begin, &e->g_np, &e->deep_list, &e->k64, &e->slow_list, &e->pf_flag, &e->pf_list, &e->pq_flag, &e->pq_list, &e->left_list, &e->slow_args, &e->pd_slab, &e->gen_flag, &e->gen_list, &e->score_list, &e->gw, &e->g_wbase, &e->vb_start, &e->rp_left, &e->rp_right, &e->rp_merge, &e->rp_rmerge,
                      &e->rp_umi, &e->rp_umilen, &e->rp_state, &e->rp_supp, &e->rp_nm, &e->rp_qsl, &e->rp_qsr, &e->scan_part, &e->si};
     for (auto *b : all) b->release();
@@ -866,9 +866,9 @@ static int gce_process_impl(gce_engine *e) {
     e->tab_clean = true;                          // k_scatter ran to the end
     const uint32_t C = (uint32_t)e->h_si.n_clusters;
     const size_t c1 = C ? C : 1;
-    ENS(cl_npairs, c1 * 4); ENS(cl_ngroups, c1 * 4); ENS(cl_gbase, c1 * 4); ENS(cl_nresult, c1 * 4); ENS(cl_hasumi, c1);
+    ENS(cl_npairs, c1 * 4); ENS(cl_ngroups, c1 * 4); ENS(cl_gbase, c1 * 4); ENS(cl_nresult, c1 * 4); ENS(cl_hasumi, c1); ENS(cl_tier, c1);
     w.cl_npairs = e->cl_npairs.as<uint32_t>(); w.cl_ngroups = e->cl_ngroups.as<uint32_t>(); w.cl_gbase = e->cl_gbase.as<uint32_t>();
-    w.cl_nresult = e->cl_nresult.as<uint32_t>(); w.cl_hasumi = e->cl_hasumi.as<uint8_t>();
+    w.cl_nresult = e->cl_nresult.as<uint32_t>(); w.cl_hasumi = e->cl_hasumi.as<uint8_t>(); w.cl_tier = e->cl_tier.as<uint8_t>();
     uint32_t NG = 0;
     bool si_behind_describe = false;               // the host's copy of StreamInfo holds what k_describe found (read-length range)
     if (C > 0 && e->dev_error == 0) {
@@ -1293,6 +1293,30 @@ int gce_get_vote_counters(gce_engine *e, int64_t out[4]) {
     if (!e || !out || !e->processed) return GCE_ERR_INVALID;
     out[0] = (int64_t)e->h_si.vote_rounds2; out[1] = (int64_t)e->h_si.vote_rounds2_unaligned;
     out[2] = (int64_t)(e->h_si.hand_on >> 32); out[3] = (int64_t)e->h_si.n_groups;
+    return GCE_OK;
+}
+
+// which pairing tier paired every cluster of the last gce_process (GCE_PAIR_TIER_*).  Host side, for tests and diagnostics: the tier bytes, the
+// cluster starts and the first pair slot of every cluster (gpl: the pairing kernels write it, nothing later does -- members[] is scratch by then)
+int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *read, int64_t *n_clusters, int64_t counts[GCE_PAIR_TIERS]) {
+    if (!e || !e->processed || e->dev_error || cap < 0) return GCE_ERR_INVALID;
+    const int64_t C = (int64_t)e->h_si.n_clusters;
+    if (n_clusters) *n_clusters = C;
+    if (counts) for (int k = 0; k < GCE_PAIR_TIERS; k++) counts[k] = 0;
+    if (C == 0) return GCE_OK;
+    if (!e->cl_tier.p || e->cl_tier.cap < (size_t)C) return fail(e, GCE_ERR_INVALID, "no pairing ran in the last gce_process");
+    (void)hipSetDevice(e->prm.device);
+    std::vector<uint8_t> t((size_t)C);
+    HIPCHK(hipMemcpy(t.data(), e->cl_tier.p, (size_t)C, hipMemcpyDeviceToHost));
+    if (counts) for (int64_t c = 0; c < C; c++) { if (t[c] >= GCE_PAIR_TIERS) return fail(e, GCE_ERR_INVALID, "a cluster has no pairing tier"); counts[t[c]]++; }
+    const int64_t m = C < cap ? C : cap;
+    if (tier) memcpy(tier, t.data(), (size_t)m);
+    if (read && m > 0) {
+        std::vector<uint32_t> st((size_t)m), pl((size_t)(e->n > 0 ? e->n : 1));
+        HIPCHK(hipMemcpy(st.data(), e->cl_start.p, (size_t)m * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pl.data(), e->gpl.p, pl.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t c = 0; c < m; c++) read[c] = (t[c] == GCE_PAIR_TIER_NEVER || st[c] >= pl.size()) ? 0xFFFFFFFFu : pl[st[c]];
+    }
     return GCE_OK;
 }
 

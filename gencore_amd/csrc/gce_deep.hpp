@@ -419,7 +419,7 @@ __global__ __launch_bounds__(PD_T) void k_pairing_deep(DevBatch b, DevParams p, 
         __syncthreads();
         if (!take || s_flag) { if (!BIG && tid == 0) w.left_list[atomicAdd(&w.si->n_slow_pair2, 1u)] = c; continue; }      // (BIG: the entry stays for the generic kernels)
         const uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
-        if (mode == THR_NEVER) { if (tid == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; if (BIG) w.left_list[li] = NONE32; } continue; }
+        if (mode == THR_NEVER) { if (tid == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; if (BIG) w.left_list[li] = NONE32; } continue; }
 #ifdef VB_PROF
         unsigned long long pd_prev_ = wall_clock64();
         if (threadIdx.x == 0) atomicAdd(&w.si->prof[30], 1ull);
@@ -483,10 +483,12 @@ __global__ __launch_bounds__(PD_T) void k_pairing_deep(DevBatch b, DevParams p, 
             for (int sidx = tid; sidx < (int)n; sidx += PD_T) {
                 const uint16_t m = s_perm[sidx];
                 const bool head = sidx == 0 || s_key[s_perm[sidx - 1]][0] != s_key[m][0] || s_key[s_perm[sidx - 1]][1] != s_key[m][1];
-                if (!head || s_rest[m] == 0) continue;                              // (a name that ends inside the window has no rest: equal windows = equal names)
-                int r = 1;
-                while (sidx + r < (int)n && s_key[s_perm[sidx + r]][0] == s_key[m][0] && s_key[s_perm[sidx + r]][1] == s_key[m][1]) r++;
-                if (r < 2) continue;
+                if (!head) continue;
+                int r = 1, rest = s_rest[m];
+                while (sidx + r < (int)n && s_key[s_perm[sidx + r]][0] == s_key[m][0] && s_key[s_perm[sidx + r]][1] == s_key[m][1]) { rest |= s_rest[s_perm[sidx + r]]; r++; }
+                // no member with a rest: equal windows = equal names (a name that ends inside the window is zero-padded there, and names hold no NUL).
+                // The HEAD's rest alone does not tell: a name that ends exactly at the window's end shares its window with every longer name it prefixes
+                if (r < 2 || rest == 0) continue;
                 if (r > 32) { toolong = 1; continue; }
                 for (int x = 1; x < r; x++) {                                       // insertion sort of the run by (rest of the name, read index)
                     const uint16_t e = s_perm[sidx + x];
@@ -674,7 +676,7 @@ __global__ __launch_bounds__(PD_T) void k_pairing_deep(DevBatch b, DevParams p, 
         PD_TICK(7);
         if (tid == 0) {
             const bool cross = d_key(b.core[w.members[start]], p).right < 0;
-            w.cl_npairs[c] = npairs; w.cl_ngroups[c] = ngroups; w.cl_hasumi[c] = (uint8_t)((any_umi ? 1 : 0) | (cross ? 2 : 0));
+            w.cl_npairs[c] = npairs; w.cl_ngroups[c] = ngroups; w.cl_hasumi[c] = (uint8_t)((any_umi ? 1 : 0) | (cross ? 2 : 0)); w.cl_tier[c] = BIG ? TIER_DEEP_DEVICE : TIER_DEEP_LDS;
             if (BIG) w.left_list[li] = NONE32;                                       // done here: struck out of the generic kernels' list
         }
     }

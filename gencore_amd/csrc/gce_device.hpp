@@ -11,6 +11,8 @@
 
 // thr_mode of a cluster instance (quirks Q1/Q2)
 enum : uint32_t { THR_PROPER = 0, THR_UNPROPER = 1, THR_NEVER = 2 };
+// the pairing tier that paired a cluster (Work.cl_tier; the values of GCE_PAIR_TIER_* in include/gencore_amd.h)
+enum : uint8_t { TIER_NEVER = 0, TIER_SUB16 = 1, TIER_SUB32 = 2, TIER_FAST = 3, TIER_DEEP_LDS = 4, TIER_DEEP_DEVICE = 5, TIER_GENERIC = 6 };
 // read class
 enum : uint8_t { CLS_DROP = 0, CLS_CLUSTERED = 1, CLS_BYPASS = 2 };
 

@@ -46,6 +46,7 @@ struct Work {
     struct TabEntry *tab; uint32_t *toff; uint64_t tsize; double tinv;   // tsize buckets (any size, not a power of two); toff is written sparsely
     // clusters
     uint32_t *cl_ikey, *cl_start, *cl_n, *cl_npairs, *cl_ngroups, *cl_gbase, *cl_nresult; uint8_t *cl_hasumi;
+    uint8_t *cl_tier;                    // which pairing tier paired the cluster (TIER_*, gce_device.hpp): one byte store next to cl_npairs, read by gce_get_pairing_tiers only
     // cluster-local arrays (indexed by cl_start + k)
     uint32_t *members, *sorted, *pl, *pr, *pu, *pg, *gpl, *gpr, *grp_begin, *grp_n;
     uint64_t *k64;                       // generic pairing scratch: 3 words per read (name window / UMI words)
@@ -137,7 +138,7 @@ __device__ void pairing_generic(const DevBatch &b, const DevParams &p, const Wor
     const uint32_t start = w.cl_start[c], n = w.cl_n[c];
     uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
     if (mode == THR_NEVER) {                      // pending after an early finishConsensus: never processed (gencore.cpp:23)
-        if (PHASE == 2 && lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; }
+        if (PHASE == 2 && lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; }
         return;
     }
     const int thr = mode == THR_PROPER ? p.proper_thr : p.unproper_thr;
@@ -310,7 +311,7 @@ __device__ void pairing_generic(const DevBatch &b, const DevParams &p, const Wor
         if (lane == 0) { w.grp_begin[start + g] = start + gbase; w.grp_n[start + g] = run; }
         gbase += run;
     }
-    if (lane == 0) { const bool cross = d_key(b.core[w.members[start]], p).right < 0; w.cl_npairs[c] = npairs; w.cl_ngroups[c] = ngroups; w.cl_hasumi[c] = (uint8_t)((any_umi ? 1 : 0) | (cross ? 2 : 0)); }
+    if (lane == 0) { const bool cross = d_key(b.core[w.members[start]], p).right < 0; w.cl_npairs[c] = npairs; w.cl_ngroups[c] = ngroups; w.cl_hasumi[c] = (uint8_t)((any_umi ? 1 : 0) | (cross ? 2 : 0)); w.cl_tier[c] = TIER_GENERIC; }
 }
 
 
@@ -334,7 +335,7 @@ __device__ __forceinline__ int popc_nonzero_bytes(uint64_t x) {
 __device__ void pairing_fast_cluster(const DevBatch &b, const DevParams &p, const Work &w, uint32_t c, int lane) {
     const uint32_t start = w.cl_start[c], n = w.cl_n[c];
     uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
-    if (mode == THR_NEVER) { if (lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; } return; }
+    if (mode == THR_NEVER) { if (lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; } return; }
     const int thr = mode == THR_PROPER ? p.proper_thr : p.unproper_thr;
     bool defer = n > 64;
     uint32_t my = NONE32; int nl = 0; const char *nm = nullptr; int ul = 0; uint64_t ui_ = 0;
@@ -519,7 +520,7 @@ __device__ void pairing_fast_cluster(const DevBatch &b, const DevParams &p, cons
         if (lane == 0) { w.grp_begin[start + g] = start + gbase; w.grp_n[start + g] = run; }
         gbase += run;
     }
-    if (lane == 0) { const bool cross = d_key(b.core[w.members[start]], p).right < 0; w.cl_npairs[c] = npairs; w.cl_ngroups[c] = ngroups; w.cl_hasumi[c] = (uint8_t)((any_umi ? 1 : 0) | (cross ? 2 : 0)); }
+    if (lane == 0) { const bool cross = d_key(b.core[w.members[start]], p).right < 0; w.cl_npairs[c] = npairs; w.cl_ngroups[c] = ngroups; w.cl_hasumi[c] = (uint8_t)((any_umi ? 1 : 0) | (cross ? 2 : 0)); w.cl_tier[c] = TIER_FAST; }
 }
 // one wave per cluster: every cluster (list == nullptr) or the clusters k_pairing_half (gce_pair2.hpp) flagged, compacted into pf_list
 __global__ __launch_bounds__(256) void k_pairing_fast(DevBatch b, DevParams p, Work w, uint32_t n_clusters, const uint32_t *list) {

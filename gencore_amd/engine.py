@@ -102,6 +102,18 @@ class Engine:
         self._check(self.lib.gce_get_vote_counters(self._h, v))
         return dict(rounds2=v[0], rounds2_unaligned=v[1], handed_on_sides=v[2], groups=v[3])
 
+    PAIR_TIERS = ("never", "sub16", "sub32", "fast", "deep_lds", "deep_device", "generic")     # GCE_PAIR_TIER_* in include/gencore_amd.h
+
+    def pairing_tiers(self):
+        """Which mate-pairing tier paired every cluster of the last finish() (gce_get_pairing_tiers): (tier, read, counts) -- per cluster the
+        tier id (an index into PAIR_TIERS) and one read of the cluster (stream index; 0xFFFFFFFF for "never"), and clusters per tier name."""
+        n = C.c_int64(0)
+        cnt = (C.c_int64 * len(self.PAIR_TIERS))()
+        self._check(self.lib.gce_get_pairing_tiers(self._h, 0, None, None, C.byref(n), cnt))
+        tier, read = np.zeros(n.value, np.uint8), np.zeros(n.value, np.uint32)
+        self._check(self.lib.gce_get_pairing_tiers(self._h, n.value, tier.ctypes.data, read.ctypes.data, C.byref(n), cnt))
+        return tier, read, dict(zip(self.PAIR_TIERS, (int(x) for x in cnt)))
+
     def rows(self):
         """The table of emitted records (gce_drain) as numpy copies: (dict of arrays, pre GceStats, post GceStats)."""
         r = GceResult()

@@ -311,6 +311,18 @@ int gce_get_timing(gce_engine *e, gce_timing *out);
  * fit one round's tallies), out[1] of those the rounds that start at a side index that is not a multiple of 4, out[2] group sides k_vote handed on
  * to the per-side kernels, out[3] groups of the stream.  For tests and diagnostics. */
 int gce_get_vote_counters(gce_engine *e, int64_t out[4]);
+/* Which mate-pairing tier paired every cluster of the last gce_process (ADDED under v3; for tests and diagnostics).  n_clusters: the cluster
+ * count; counts[k]: clusters of tier k; for the first min(cap, n_clusters) clusters, tier[c] and read[c] = one read of the cluster (the left read
+ * of its first pair slot; 0xFFFFFFFF for GCE_PAIR_TIER_NEVER), as a stream index.  Any output pointer may be NULL. */
+enum { GCE_PAIR_TIER_NEVER = 0,          /* the cluster is never processed (pending behind an early finishConsensus) */
+       GCE_PAIR_TIER_SUB16 = 1,          /* k_pairing_sub<16>: <= 16 reads, 16 lanes per cluster */
+       GCE_PAIR_TIER_SUB32 = 2,          /* k_pairing_sub<32>: 17..32 reads */
+       GCE_PAIR_TIER_FAST = 3,           /* k_pairing_fast: 33..64 reads, one wave */
+       GCE_PAIR_TIER_DEEP_LDS = 4,       /* k_pairing_deep, arrays in LDS: 65..4096 reads */
+       GCE_PAIR_TIER_DEEP_DEVICE = 5,    /* k_pairing_deep, arrays in device memory: 4097..65534 reads */
+       GCE_PAIR_TIER_GENERIC = 6,        /* the generic kernels: whatever the others hand on */
+       GCE_PAIR_TIERS = 7 };
+int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *read, int64_t *n_clusters, int64_t counts[GCE_PAIR_TIERS]);
 /* The two Stats blocks of the last gce_process in DEVICE memory: 2 x GCE_STATS_WORDS int64, pre then post -- for the final Stats merge
  * of a multi-GPU run (one RCCL all-reduce(sum); all fields are additive, src/stats.h:47-65) without a bounce through the host. */
 int gce_stats_device(gce_engine *e, const int64_t **pre_then_post);

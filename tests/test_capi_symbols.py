@@ -25,6 +25,15 @@ def test_header_symbols_exported(built):
     assert lib.gce_abi_version() == capi.GCE_ABI_VERSION
 
 
+def test_pairing_tier_ids_match_header():
+    """gce_get_pairing_tiers' tier ids (GCE_PAIR_TIER_*) are the names Engine.pairing_tiers() reports, in order."""
+    from gencore_amd.engine import Engine
+    txt = open(os.path.join(ROOT, "include", "gencore_amd.h")).read()
+    ids = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"GCE_PAIR_TIER_([A-Z0-9_]+)\s*=\s*(\d+)", txt)}
+    assert ids == {name: k for k, name in enumerate(Engine.PAIR_TIERS)}
+    assert int(re.search(r"GCE_PAIR_TIERS\s*=\s*(\d+)", txt).group(1)) == len(Engine.PAIR_TIERS)
+
+
 def test_struct_layouts_match_header(built, tmp_path):
     from gencore_amd import capi
     src = tmp_path / "probe.c"

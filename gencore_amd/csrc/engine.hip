@@ -27,6 +27,8 @@ static thread_local double t_alloc_s = 0.0; static thread_local long t_alloc_n =
 static inline double mono_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 // live / peak device bytes of the process (DevBuf, PlanBuf): gce_device_bytes
 long long g_dev_live = 0, g_dev_peak = 0;
+// the record index of the last pass runner's windows, summed (gce_passes_create zeroes it): gce_get_index_counters(NULL, ...)
+static int64_t g_pass_idx_ctr[4] = {0, 0, 0, 0};
 inline void dev_bytes_add(long long d) {
     const long long now = __atomic_add_fetch(&g_dev_live, d, __ATOMIC_RELAXED);
     long long pk = __atomic_load_n(&g_dev_peak, __ATOMIC_RELAXED);
@@ -94,6 +96,7 @@ struct gce_engine {
     // the raw BAM stream in HBM (gce_bamdev.hpp)
     DevBuf raw, rw_bad, rw_guess, rw_leave, rw_cnt, rw_base, rw_misc, rw_tmp, rw_off, rw_ncig, rw_nmpos, rw_rsize, rw_roff, rw_body;
     size_t raw_n = 0; bool raw_mode = false; int64_t raw_records = 0; uint64_t raw_body_bytes = 0;
+    int64_t idx_ctr[4] = {0, 0, 0, 0};   // the record index of the last gce_raw_finish: segments, initially flagged, parallel rounds, serial repair (gce_get_index_counters)
     DevBuf z_comp, z_dir, z_err; size_t z_n = 0; std::vector<InfDir> z_members;      // BGZF members waiting for the GPU inflate (gce_raw_push_bgzf)
     // the sharded file runner (gce_raw_attach_mirror / gce_raw_select_shard): engines that receive every push to this one's raw stream; this engine's
     // share of the stream (reads gathered from the full batch; sh_sel = their places in the whole stream)
@@ -1293,6 +1296,15 @@ int gce_get_vote_counters(gce_engine *e, int64_t out[4]) {
     if (!e || !out || !e->processed) return GCE_ERR_INVALID;
     out[0] = (int64_t)e->h_si.vote_rounds2; out[1] = (int64_t)e->h_si.vote_rounds2_unaligned;
     out[2] = (int64_t)(e->h_si.hand_on >> 32); out[3] = (int64_t)e->h_si.n_groups;
+    return GCE_OK;
+}
+
+// the GPU record index (gce_bamdev.hpp k_raw_seg .. k_raw_repair): [0] 16 KB segments, [1] of those flagged by the first check, [2] parallel
+// repair rounds (k_raw_fix + k_raw_check), [3] serial repairs (k_raw_repair).  e: its last gce_raw_finish; NULL: summed over the windows of
+// the last pass runner of the process (gce_passes_window, the key pass and every pass)
+int gce_get_index_counters(gce_engine *e, int64_t out[4]) {
+    if (!out) return GCE_ERR_INVALID;
+    for (int k = 0; k < 4; k++) out[k] = e ? e->idx_ctr[k] : __atomic_load_n(&g_pass_idx_ctr[k], __ATOMIC_RELAXED);
     return GCE_OK;
 }
 

@@ -74,20 +74,25 @@ __global__ __launch_bounds__(256) void k_raw_check(const uint64_t *guess, const 
 }
 // repair, in parallel.  A guess can be a coincidence: one byte in front of a record of contig 0 the shifted fields pass the test about once
 // in 4000 segments (block_size x 256 + the last NM byte, tid x 256 = 0 ...), and the chain walked from there leaves far behind the
-// segment, which also puts the NEXT segment off the chain although its own guess is right.  Every round re-walks the flagged segments
-// whose predecessor is NOT flagged (that one's chain is final, nothing it reads changes in the round) from where that chain leaves; the
-// check that follows clears the neighbours.  Rounds = the longest run of truly wrong segments (records longer than a segment).
+// segment, which also puts the NEXT segment off the chain although its own guess is right.  Bytes inside a long record (a B:C array of
+// record-shaped bytes) can even carry a false chain of their own across several segments, consistent from segment to segment: a segment
+// that is NOT flagged may still be wrong, when it agrees with a wrong predecessor.  Every round re-walks the flagged segments whose
+// predecessor is not flagged (nothing that predecessor holds changes in the round) from where the predecessor's chain leaves.  That start
+// is only right when every segment in front is right, so a walk from it that breaks proves nothing: the segment is left as it is (still
+// flagged) and only k_raw_repair, which walks from the first record, may call the stream damaged.  Progress: the first wrong segment is
+// always flagged and its predecessor is right and unflagged, so every round puts at least it on the chain; no flag at all means, by
+// induction from segment 0 (whose guess is the first record), that every segment is on the chain.  Rounds <= the longest run of wrong
+// segments (records longer than a segment, false chains).
 template <bool SOFT = false>
-__global__ __launch_bounds__(256) void k_raw_fix(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt, const uint8_t *bad_of, unsigned int *changed, unsigned int *broken) {
+__global__ __launch_bounds__(256) void k_raw_fix(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt, const uint8_t *bad_of) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg || s == 0 || !bad_of[s] || bad_of[s - 1]) return;
     const uint64_t at = leave[s - 1];
     if (at == ~0ull) return;
     const uint64_t hi = min(n, first + s * RAW_SEG + RAW_SEG);
     uint32_t c = 0; uint64_t x = at;
-    if (at < hi) { x = raw_walk<SOFT>(u, at, hi, n, c, nullptr); if (x == ~0ull) { *broken = 1u; return; } }
+    if (at < hi) { x = raw_walk<SOFT>(u, at, hi, n, c, nullptr); if (x == ~0ull) return; }
     guess[s] = at; leave[s] = x; cnt[s] = c;
-    *changed = 1u;
 }
 // the last resort (after several parallel rounds): ONE thread follows the chain from segment to segment
 // and re-walks only the segments whose guess does not lie on it
@@ -542,6 +547,7 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
     const uint64_t total = e->raw_n;
     HIPCHK(hipMemsetAsync((char *)e->raw.p + total, 0, 64, s));                    // the blobs are readable 16 bytes past their end
     uint64_t n_rec = 0;
+    for (int64_t &c : e->idx_ctr) c = 0;
     if (total > records_begin) {
         const uint64_t nseg = (total - records_begin + RAW_SEG - 1) / RAW_SEG;
         HIPCHK(e->rw_guess.ensure(nseg * 8)); HIPCHK(e->rw_leave.ensure(nseg * 8)); HIPCHK(e->rw_cnt.ensure(nseg * 4 + 8)); HIPCHK(e->rw_base.ensure(nseg * 8 + 8)); HIPCHK(e->rw_misc.ensure(64)); HIPCHK(e->rw_bad.ensure(nseg + 8));
@@ -551,6 +557,7 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
         hipLaunchKernelGGL(k_raw_check<false>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
         unsigned int flags[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+        e->idx_ctr[0] = (int64_t)nseg; e->idx_ctr[1] = flags[0];
         lap("segment walks + check");
         if (tprint) fprintf(stderr, "gce_raw_finish: %u of %llu segments off the chain\n", flags[0], (unsigned long long)nseg);
         if (tprint && flags[0]) {                                                       // which ones, and why
@@ -561,13 +568,14 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
         }
         for (int round = 0; flags[0] && round < 64; round++) {                           // parallel repair rounds
             HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_fix<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), (const uint8_t *)e->rw_bad.p, e->rw_misc.as<unsigned int>() + 3, e->rw_misc.as<unsigned int>() + 1);
+            hipLaunchKernelGGL(k_raw_fix<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), (const uint8_t *)e->rw_bad.p);
             hipLaunchKernelGGL(k_raw_check<false>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
             HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-            if (flags[1]) return fail(e, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
+            e->idx_ctr[2]++;
         }
         lap("parallel repair");
         if (flags[0]) {
+            e->idx_ctr[3] = 1;
             HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 16, s));
             hipLaunchKernelGGL(k_raw_repair<false>, dim3(1), dim3(64), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), e->rw_misc.as<unsigned int>() + 1);
             HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));

@@ -130,6 +130,7 @@ int gce_passes_create(int32_t device, int32_t max_contig, int32_t flush_period, 
     *out = nullptr;
     if (hipSetDevice(device) != hipSuccess) return GCE_ERR_NO_DEVICE;
     gce_passes *p = new gce_passes();
+    for (int64_t &c : g_pass_idx_ctr) __atomic_store_n(&c, (int64_t)0, __ATOMIC_RELAXED);
     p->device = device; p->max_contig = max_contig; p->period = (unsigned long long)(flush_period > 0 ? flush_period : 10000);
     if (hipStreamCreate(&p->s) != hipSuccess) { delete p; return GCE_ERR_HIP; }
     *out = p;
@@ -246,7 +247,7 @@ static int pass_records(gce_passes *p, gce_engine *e, int64_t n, int32_t *cut_re
 // the next piece of the file: `n_members` whole BGZF members in host memory (member k at comp + coff[k], csize[k] bytes, ISIZE usize[k]).  They
 // are copied to HBM and inflated by the GPU (k_bgzf_inflate, as gce_raw_push_bgzf) behind the record the last window's end cut; the first
 // `skip` inflated bytes (the BAM header) are passed over; the records are indexed by the segment walks of gce_raw_finish from the carried
-// offset (k_raw_seg / k_raw_check / k_raw_fix with a soft end: the record the window's end cuts is carried over to the next window) and
+// offset (k_raw_seg / k_raw_check / k_raw_fix / k_raw_repair with a soft end: the record the window's end cuts is carried over to the next window) and
 // go to pass_records.  last: the final piece of the file (a record cut there is a truncated stream).
 int gce_passes_window(gce_passes *p, gce_engine *e, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize,
                       uint64_t skip, int32_t n_ref, int32_t last, int32_t *cut_reached) {
@@ -290,14 +291,16 @@ int gce_passes_window(gce_passes *p, gce_engine *e, const void *comp, size_t com
         hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)p->guess.p, (const uint64_t *)p->leave.p, nseg, total, p->rmisc.as<unsigned int>(), p->bad_of.as<uint8_t>());
         unsigned int flags[2] = {0, 0};
         PCHK(hipMemcpyAsync(flags, p->rmisc.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));
+        __atomic_add_fetch(&g_pass_idx_ctr[0], (int64_t)nseg, __ATOMIC_RELAXED); __atomic_add_fetch(&g_pass_idx_ctr[1], (int64_t)flags[0], __ATOMIC_RELAXED);
         for (int round = 0; flags[0] && round < 64; round++) {
             PCHK(hipMemsetAsync(p->rmisc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_fix<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, p->guess.as<uint64_t>(), p->leave.as<uint64_t>(), p->cnt.as<uint32_t>(), (const uint8_t *)p->bad_of.p, p->rmisc.as<unsigned int>() + 3, p->rmisc.as<unsigned int>() + 1);
+            hipLaunchKernelGGL(k_raw_fix<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, p->guess.as<uint64_t>(), p->leave.as<uint64_t>(), p->cnt.as<uint32_t>(), (const uint8_t *)p->bad_of.p);
             hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)p->guess.p, (const uint64_t *)p->leave.p, nseg, total, p->rmisc.as<unsigned int>(), p->bad_of.as<uint8_t>());
             PCHK(hipMemcpyAsync(flags, p->rmisc.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));
-            if (flags[1]) return pfail(p, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
+            __atomic_add_fetch(&g_pass_idx_ctr[2], (int64_t)1, __ATOMIC_RELAXED);
         }
         if (flags[0]) {
+            __atomic_add_fetch(&g_pass_idx_ctr[3], (int64_t)1, __ATOMIC_RELAXED);
             PCHK(hipMemsetAsync(p->rmisc.p, 0, 16, s));
             hipLaunchKernelGGL(k_raw_repair<true>, dim3(1), dim3(64), 0, s, u, start, total, nseg, p->guess.as<uint64_t>(), p->leave.as<uint64_t>(), p->cnt.as<uint32_t>(), p->rmisc.as<unsigned int>() + 1);
             PCHK(hipMemcpyAsync(flags, p->rmisc.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));

@@ -102,6 +102,10 @@ class Engine:
         self._check(self.lib.gce_get_vote_counters(self._h, v))
         return dict(rounds2=v[0], rounds2_unaligned=v[1], handed_on_sides=v[2], groups=v[3])
 
+    def index_counters(self):
+        """The record index of the last gce_raw_finish (gce_get_index_counters)."""
+        return index_counters(self._h)
+
     PAIR_TIERS = ("never", "sub16", "sub32", "fast", "deep_lds", "deep_device", "generic")     # GCE_PAIR_TIER_* in include/gencore_amd.h
 
     def pairing_tiers(self):
@@ -162,6 +166,17 @@ class Engine:
         self.add_reads(batch)
         self.finish()
         return self.output(batch)
+
+
+def index_counters(handle=None):
+    """gce_get_index_counters: the GPU record index of an engine's last gce_raw_finish (handle: a raw gce_engine pointer), or with handle None
+    summed over the windows of the process's last pass runner -- dict(segments, flagged, rounds, serial)."""
+    lib = capi.load_library()
+    v = (C.c_int64 * 4)()
+    rc = lib.gce_get_index_counters(handle, v)
+    if rc != 0:
+        raise GceError(rc, "gce_get_index_counters")
+    return dict(segments=v[0], flagged=v[1], rounds=v[2], serial=v[3])
 
 
 def run_stream(batch, params, reference=None, events=None):

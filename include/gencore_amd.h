@@ -311,6 +311,10 @@ int gce_get_timing(gce_engine *e, gce_timing *out);
  * fit one round's tallies), out[1] of those the rounds that start at a side index that is not a multiple of 4, out[2] group sides k_vote handed on
  * to the per-side kernels, out[3] groups of the stream.  For tests and diagnostics. */
 int gce_get_vote_counters(gce_engine *e, int64_t out[4]);
+/* The GPU record index's counters (ADDED under v3; for tests and diagnostics): out[0] 16 KB segments, out[1] of those flagged by the first
+ * check (a guessed record start off the chain), out[2] parallel repair rounds, out[3] serial repairs (0 or 1 per index).  e: its last
+ * gce_raw_finish; e == NULL: summed over every window of the last pass runner of the process (gce_run_bam_passes, key pass and passes). */
+int gce_get_index_counters(gce_engine *e, int64_t out[4]);
 /* Which mate-pairing tier paired every cluster of the last gce_process (ADDED under v3; for tests and diagnostics).  n_clusters: the cluster
  * count; counts[k]: clusters of tier k; for the first min(cap, n_clusters) clusters, tier[c] and read[c] = one read of the cluster (the left read
  * of its first pair slot; 0xFFFFFFFF for GCE_PAIR_TIER_NEVER), as a stream index.  Any output pointer may be NULL. */

@@ -1,0 +1,552 @@
+"""Raw BAM record streams built to steer the GPU record index (gencore_amd/csrc/gce_bamdev.hpp: k_raw_seg, k_raw_check, k_raw_fix,
+k_raw_repair and the host loops of gce_raw_finish and gce_passes_window) down one path each, and a plain-Python spec of that index.
+
+The builder places records at chosen offsets relative to records_begin + k x 16384 (the index's segments) by sizing a filler aux array,
+and fills long B:C arrays with arbitrary bytes -- runs of record-shaped bytes ("fakes") that pass the index's plausibility test.  The spec
+is a transcription of the kernels, one lane at a time, and of both host loops (SOFT = false: gce_raw_finish; SOFT = true: a window of the
+pass runner); classify() reports which path a stream takes.  CPU only."""
+import struct
+
+import numpy as np
+
+import pybam
+
+SEG = 16384
+NONE = (1 << 64) - 1
+ROUNDS = 64
+POS0 = 1 << 24                     # reads of contig 0 at or above 2^24: the high byte of pos is 1, a one-byte-shifted header has l_qname 1
+TARGETS = [("chrA", 40_000_000), ("chrB", 5_000_000)]
+TEXT = "@HD\tVN:1.6\tSO:coordinate\n"
+BASES = "ACGT"
+BLOCK = 12289                      # inflated bytes per BGZF member of the files written here (not a divisor of the segment size)
+
+
+def header_bytes(targets=TARGETS, text=TEXT):
+    out = b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(targets))
+    for nm, ln in targets:
+        out += struct.pack("<i", len(nm) + 1) + nm.encode() + b"\0" + struct.pack("<i", ln)
+    return out
+
+
+def aux_all_types(i):
+    """(tag, type, value) of every aux type the readers walk over: A c C s S i I f Z H, and B with each subtype."""
+    return [("XA", "A", b"QRST"[i % 4:i % 4 + 1]), ("Xc", "c", -5 - i % 7), ("XC", "C", 200 + i % 50), ("Xs", "s", -300 - i), ("XS", "S", 60000 + i % 99),
+            ("Xi", "i", -70000 - i), ("XI", "I", 3_000_000_000 + i), ("Xf", "f", 0.5 + i), ("XZ", "Z", "z%d" % i), ("XH", "H", "1AE%03X" % i),
+            ("Bc", "B", ("c", [-1, 2, -3])), ("BC", "B", ("C", [1, 255])), ("Bs", "B", ("s", [-2, 300])), ("BS", "B", ("S", [65535])),
+            ("Bi", "B", ("i", [-9, 1 << 20])), ("BI", "B", ("I", [7, 1 << 31])), ("Bf", "B", ("f", [1.5, -2.25]))]
+
+
+def aux_double(v):
+    """an aux value of type d (8 bytes; the readers know its size, pybam does not write it)"""
+    return b"XDd" + struct.pack("<d", v)
+
+
+def aux_bc(tag, payload):
+    """tag:B:C holding `payload` verbatim (8 bytes + the payload)"""
+    return tag.encode() + b"BC" + struct.pack("<I", len(payload)) + bytes(payload)
+
+
+def fake_record(size=100, tid=0):
+    """record-shaped bytes that pass raw_plausible: block_size = size - 4, contig `tid`, name "fake", no bases, 0xFF behind"""
+    core = struct.pack("<iiBBHHHiiii", tid, 0, 5, 0, 0, 0, 0, 0, tid, 0, 0) + b"fake\0"
+    return struct.pack("<I", size - 4) + core + b"\xff" * (size - 4 - len(core))
+
+
+def fake_payload(n_fakes, lead=200, tail=3000, breaks=True, size=100):
+    """0xFF x lead, n_fakes fake records back to back, then (breaks) four zero bytes -- a block_size of 0 ends their chain -- and 0xFF x tail"""
+    return b"\xff" * lead + fake_record(size) * n_fakes + (b"\0\0\0\0" if breaks else b"") + b"\xff" * tail
+
+
+class Read:
+    """one read: the fields of pybam.record_bytes plus raw aux bytes behind the ones it writes"""
+
+    def __init__(self, i, rng, pos, tid=0, L=20, flag=None, mate_pos=None):
+        flag = flag if flag is not None else (99 if i % 2 == 0 else 147)
+        self.d = dict(qname="r%05d" % (i // 2), flag=flag, tid=tid, pos=pos, cigar="%dM" % L, mtid=tid, mpos=mate_pos if mate_pos is not None else pos,
+                      isize=(60 if flag & 0x40 else -60),
+                      seq="".join(rng.choice(list(BASES), L)), qual=[int(q) for q in rng.choice([2, 14, 20, 25, 30, 37, 40], L)], mapq=60,
+                      nm=[None, 0, 1, 2, 300, -3][i % 6], nm_type="CcSsiI"[(i // 6) % 6])
+        if self.d["nm"] is not None and self.d["nm_type"] in "Cc" and not (-128 <= self.d["nm"] <= 127 and (self.d["nm_type"] == "c" or self.d["nm"] >= 0)):
+            self.d["nm"] = 3
+        if self.d["nm"] is not None and self.d["nm"] < 0 and self.d["nm_type"] in "CSI":
+            self.d["nm"] = 4
+        if i % 4 == 1:
+            self.d["mi"] = "m%d" % (i // 8)
+        self.raw = b""
+        if i % 7 == 3:
+            self.d["aux_pre"] = aux_all_types(i)
+            self.raw = aux_double(i + 0.25)
+
+    def bytes(self):
+        rec = pybam.record_bytes(self.d)
+        return struct.pack("<i", len(rec) - 4 + len(self.raw)) + rec[4:] + self.raw
+
+
+class StreamBuilder:
+    """A BAM header, then records appended in order; offsets are relative to records_begin (the header's end) unless said otherwise."""
+
+    def __init__(self, seed=0, targets=TARGETS, text=TEXT):
+        self.rng = np.random.default_rng(seed)
+        self.targets = targets
+        self.header = header_bytes(targets, text)
+        self.body = bytearray()
+        self.reads = []                 # (offset, Read)
+        self.pos = POS0
+
+    @property
+    def first(self):
+        return len(self.header)
+
+    def here(self):
+        return len(self.body)
+
+    def read(self, **kw):
+        i = len(self.reads)
+        if i % 3 == 0:
+            self.pos += 7
+        return Read(i, self.rng, self.pos, **kw)
+
+    def add(self, r=None, raw=b""):
+        r = r or self.read()
+        r.raw += raw
+        self.reads.append((self.here(), r))
+        self.body += r.bytes()
+        return r
+
+    def add_sized(self, size, lead=b"", filler=None, tag="ML"):
+        """one record of exactly `size` bytes (4 + block_size): `lead` raw aux bytes, then a tag:B:C array whose payload is filler (bytes
+        or a function of the payload's length; default 0xFF) cut or padded with 0xFF to the length that makes the size"""
+        r = self.read()
+        base = len(r.bytes()) + len(lead) + 8
+        n = size - base
+        assert n >= 0, (size, base)
+        p = filler(n) if callable(filler) else (filler if filler is not None else b"")
+        p = (bytes(p) + b"\xff" * n)[:n]
+        return self.add(r, lead + aux_bc(tag, p))
+
+    def add_to_reach(self, target, filler=None):
+        """one record that makes the next record start at `target`"""
+        return self.add_sized(target - self.here(), filler=filler)
+
+    def fill(self, target):
+        """ordinary reads up to `target` (the last one sized to end there exactly)"""
+        while target - self.here() > 600:
+            self.add()
+        if target > self.here():
+            self.add_to_reach(target)
+
+    def stream(self):
+        return bytes(self.header) + bytes(self.body)
+
+    def record_offsets(self):
+        return [self.first + o for o, _ in self.reads]
+
+    def write_bam(self, path, block=BLOCK, level=1):
+        data = self.stream()
+        with open(path, "wb") as f:
+            for k in range(0, len(data), block):
+                f.write(pybam.bgzf_block(data[k:k + block], level))
+            f.write(pybam.EOF_BLOCK)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- the spec
+def _u32(u, o):
+    return int.from_bytes(u[o:o + 4], "little")
+
+
+class Index:
+    """the arrays of one record index (gce_bamdev.hpp) over u[first, n), nref contigs"""
+
+    def __init__(self, u, first, nref, soft):
+        self.u, self.first, self.n, self.nref, self.soft = bytes(u), first, len(u), nref, soft
+        self.nseg = (self.n - first + SEG - 1) // SEG if self.n > first else 0
+        self._candidates()
+
+    def _candidates(self):
+        """raw_plausible at every offset, and k_raw_seg's start test (two plausible records in a row, or the first one reaching the end)"""
+        n = self.n
+        a = np.frombuffer(self.u + b"\0" * 320, np.uint8).astype(np.int64)
+
+        def w32(off):
+            return a[off:off + n] | (a[off + 1:off + 1 + n] << 8) | (a[off + 2:off + 2 + n] << 16) | (a[off + 3:off + 3 + n] << 24)
+
+        def s32(x):
+            return np.where(x >= 1 << 31, x - (1 << 32), x)
+        o = np.arange(n, dtype=np.int64)
+        bs = w32(0)
+        tid, mtid, ls = s32(w32(4)), s32(w32(24)), s32(w32(20))
+        lq = a[12:12 + n]
+        nc = a[16:16 + n] | (a[17:17 + n] << 8)
+        ok = (o + 36 <= n) & (bs >= 32) & (bs <= 1 << 28) & (o + 4 + bs <= n)
+        ok &= (tid >= -1) & (tid < self.nref) & (mtid >= -1) & (mtid < self.nref) & (lq != 0) & (ls >= 0)
+        ok &= 32 + lq + 4 * nc + (ls + 1) // 2 + ls <= bs
+        name_end = np.clip(o + 4 + 32 + lq - 1, 0, len(a) - 1)
+        ok &= a[name_end] == 0
+        nxt = np.clip(o + 4 + bs, 0, n)
+        okp = np.append(ok, False)
+        self.cand = np.flatnonzero(ok & ((o + 4 + bs + 3 >= n) | okp[nxt]))
+
+    def walk(self, o, hi, offsets=None):
+        """raw_walk<SOFT>: (where the chain leaves [o, hi) or NONE, records counted)"""
+        u, n, c = self.u, self.n, 0
+        while o < hi and o + 4 <= n:
+            bs = _u32(u, o)
+            if bs < 32:
+                return NONE, c
+            if o + 4 + bs > n:
+                return (o, c) if self.soft else (NONE, c)
+            if offsets is not None:
+                offsets.append(o)
+            c += 1
+            o += 4 + bs
+        return o, c
+
+    def bounds(self, s):
+        lo = self.first + s * SEG
+        return lo, min(self.n, lo + SEG)
+
+    def seg(self):
+        """k_raw_seg"""
+        self.guess, self.leave, self.cnt = [0] * self.nseg, [0] * self.nseg, [0] * self.nseg
+        for s in range(self.nseg):
+            lo, hi = self.bounds(s)
+            o = lo
+            if s > 0:
+                k = np.searchsorted(self.cand, lo)
+                if k == len(self.cand) or self.cand[k] >= hi:
+                    self.guess[s], self.leave[s], self.cnt[s] = NONE, NONE, 0
+                    continue
+                o = int(self.cand[k])
+            self.guess[s] = o
+            self.leave[s], self.cnt[s] = self.walk(o, hi)
+
+    def check(self):
+        """k_raw_check: the flags"""
+        g, l_, n, last = self.guess, self.leave, self.n, self.nseg - 1
+        self.bad = [l_[s] == NONE or (s > 0 and g[s] != l_[s - 1]) or (s == last and (l_[s] > n if self.soft else l_[s] != n)) for s in range(self.nseg)]
+        return sum(self.bad)
+
+    def fix(self, truth=None):
+        """k_raw_fix, every lane against the arrays as the round found them: (a lane walked from a predecessor off the true chain, a lane's
+        walk broke)"""
+        g, l_, c = list(self.guess), list(self.leave), list(self.cnt)
+        wrong = broke = False
+        for s in range(1, self.nseg):
+            if not self.bad[s] or self.bad[s - 1]:
+                continue
+            at = self.leave[s - 1]
+            if at == NONE:
+                continue
+            if truth is not None and at != truth[s]:
+                wrong = True
+            hi = self.bounds(s)[1]
+            x, k = at, 0
+            if at < hi:
+                x, k = self.walk(at, hi)
+                if x == NONE:
+                    broke = True
+                    continue                          # the walk broke: the segment keeps its arrays and its flag
+            g[s], l_[s], c[s] = at, x, k
+        self.guess, self.leave, self.cnt = g, l_, c
+        return wrong, broke
+
+    def repair(self):
+        """k_raw_repair: True when the stream is damaged"""
+        at = self.first
+        for s in range(self.nseg):
+            lo, hi = self.bounds(s)
+            if at >= hi:
+                self.guess[s], self.leave[s], self.cnt[s] = at, at, 0
+                continue
+            if self.guess[s] != at or self.leave[s] == NONE:
+                x, k = self.walk(at, hi)
+                if x == NONE:
+                    return True
+                self.guess[s], self.leave[s], self.cnt[s] = at, x, k
+            at = self.leave[s]
+        return at > self.n if self.soft else at != self.n
+
+    def offsets(self):
+        """k_raw_offsets: every record start, in order"""
+        out = []
+        for s in range(self.nseg):
+            self.walk(self.guess[s], self.bounds(s)[1], out)
+        return out
+
+    def truth(self):
+        """the chain from the first record, serially: per segment the chain's first position at or behind its start (the chain's end for
+        segments behind it; None behind a break)"""
+        pos, o = [], self.first
+        while True:
+            pos.append(o)
+            if o + 4 > self.n:
+                break
+            bs = _u32(self.u, o)
+            if bs < 32 or o + 4 + bs > self.n:
+                if bs < 32 or not self.soft:
+                    pos = pos[:-1] + [None]
+                break
+            o += 4 + bs
+        ends = [p for p in pos if p is not None]
+        out = []
+        for s in range(self.nseg):
+            lo = self.bounds(s)[0]
+            k = np.searchsorted(ends, lo)
+            out.append(ends[k] if k < len(ends) else (None if pos[-1] is None else ends[-1]))
+        return out
+
+
+def classify(stream, first, n_ref, soft):
+    """The record index of stream[first:] as the GPU computes it.  soft = False: gce_raw_finish; soft = True: one window of gce_passes_window
+    (the window's end may cut a record).  Returns dict(segments, flagged (the segments the first check flags), rounds (parallel rounds run),
+    serial (k_raw_repair ran), wrong_predecessor (a fix round walked a segment from a predecessor off the true chain), fix_broke (such a
+    walk broke: before k_raw_fix left those segments flagged, the stream was refused there), error (None or the reason), offsets (absolute
+    record starts), end (where the chain leaves the last segment), guesses (k_raw_seg's starts))."""
+    ix = Index(stream, first, n_ref, soft)
+    out = dict(segments=ix.nseg, flagged=[], rounds=0, serial=False, wrong_predecessor=False, fix_broke=False, error=None, offsets=[],
+               end=min(first, ix.n), guesses=[])
+    if ix.nseg == 0:
+        return out
+    ix.seg()
+    out["guesses"] = list(ix.guess)
+    flags = ix.check()
+    out["flagged"] = [s for s in range(ix.nseg) if ix.bad[s]]
+    truth = ix.truth()
+    while flags and out["rounds"] < ROUNDS:
+        wrong, broke = ix.fix(truth)
+        out["wrong_predecessor"] |= wrong
+        out["fix_broke"] |= broke
+        flags = ix.check()
+        out["rounds"] += 1
+    if flags:
+        out["serial"] = True
+        if ix.repair():
+            out["error"] = "truncated or damaged BAM record stream"
+            return out
+    out["end"] = ix.leave[-1]
+    if soft and out["end"] > ix.n:
+        out["error"] = "truncated or damaged BAM record stream"
+        return out
+    out["offsets"] = ix.offsets()
+    return out
+
+
+def counters(res):
+    """the spec's prediction of gce_get_index_counters for one index"""
+    return dict(segments=res["segments"], flagged=len(res["flagged"]), rounds=res["rounds"], serial=int(res["serial"]))
+
+
+def _add(a, b):
+    return {k: a[k] + b[k] for k in a}
+
+
+def bgzf_members(blob):
+    """(offset, size, ISIZE) of every BGZF member of a file"""
+    out, o = [], 0
+    while o < len(blob):
+        xlen = struct.unpack_from("<H", blob, o + 10)[0]
+        bsize, x = None, 0
+        while x + 4 <= xlen:
+            si1, si2, sl = blob[o + 12 + x], blob[o + 13 + x], struct.unpack_from("<H", blob, o + 14 + x)[0]
+            if si1 == 66 and si2 == 67 and sl == 2:
+                bsize = struct.unpack_from("<H", blob, o + 16 + x)[0] + 1
+            x += 4 + sl
+        out.append((o, bsize, struct.unpack_from("<I", blob, o + bsize - 4)[0]))
+        o += bsize
+    return out
+
+
+def pass_windows(blob, window_bytes, hdr_end, n_ref):
+    """One read of a BAM file by the pass runner (gce_run_bam_passes: PassReader::members_next pieces of `window_bytes` compressed bytes,
+    gce_passes_window on each): (the windows' indexes summed as counters, the record starts (offsets in the inflated stream), an error or
+    None, the number of windows whose end cut a record)."""
+    import zlib
+    mem = bgzf_members(blob)
+    total = dict(segments=0, flagged=0, rounds=0, serial=0)
+    starts, carry, base, skip, at, k, cuts = [], b"", 0, hdr_end, 0, 0, 0
+    while at < len(blob):
+        at = min(len(blob), at + window_bytes)
+        win = []
+        while k < len(mem) and mem[k][0] + mem[k][1] <= at:
+            win.append(mem[k]); k += 1
+        last = at >= len(blob)
+        if not win and not last:
+            return total, starts, "BGZF block larger than a window", cuts
+        data = b"".join(zlib.decompress(blob[o + 18:o + c - 8], -15) for o, c, us in win if us)
+        sk = min(skip, len(data))
+        u = carry + data                    # u[0] is byte `base` of the inflated stream
+        start = end = sk
+        if len(u) > start:
+            res = classify(u, start, n_ref, True)
+            total = _add(total, counters(res))
+            if res["error"]:
+                return total, starts, res["error"], cuts
+            starts += [base + o for o in res["offsets"]]
+            end = res["end"]
+        if last and end != len(u):
+            return total, starts, "truncated record at the end of the BAM stream", cuts
+        carry, base, skip = u[end:], base + end, skip - sk
+        cuts += len(carry) > 0
+    return total, starts, None, cuts
+
+
+def min_window(blob):
+    """the smallest window_bytes the pass runner takes for a file: its largest BGZF member"""
+    return max(c for _, c, _ in bgzf_members(blob))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- named cases
+def _reads(b, n):
+    for _ in range(n):
+        b.add()
+
+
+def _fakes_to_end(lead=200):
+    """a B:C payload of 0xFF x lead' then fakes up to its last byte: their chain leaves exactly where the record ends"""
+    def f(n):
+        ld = lead + (n - lead) % 100
+        return b"\xff" * ld + fake_record() * ((n - ld) // 100)
+    return f
+
+
+def case_shifted_guess():
+    """a read of contig 0 (pos >= 2^24, isize >= 0) whose start is one byte behind a segment's start, behind a record ending in 0xFF: at the
+    segment's first byte the shifted fields pass the test (block_size x 256 + 0xFF, tid x 256 = 0, l_qname = pos >> 24 = 1, the name's NUL =
+    isize's high byte), and a real record lies exactly where the shifted block_size leads, ~40 KB on"""
+    b = StreamBuilder(1)
+    k0 = 2 * SEG + 1
+    b.fill(k0 - 700)
+    b.add_to_reach(k0)
+    r = b.add(b.read(flag=99))
+    bs = len(r.bytes()) - 4
+    b.fill(k0 - 1 + 4 + 255 + 256 * bs)
+    _reads(b, 40)
+    return b
+
+
+def case_span(m):
+    """one record of 0xFF bytes covering m whole segments (no record starts there, no plausible start either)"""
+    def make():
+        b = StreamBuilder(10 + m)
+        b.fill(SEG // 2)
+        b.add_to_reach(SEG + m * SEG + 300)
+        _reads(b, 30)
+        return b
+    return make
+
+
+def case_fake_resync():
+    """a long record whose B:C array is fakes to its last byte: their chain, guessed by every segment it covers, joins the true chain at the
+    record's end"""
+    b = StreamBuilder(3)
+    b.fill(5000)
+    b.add_to_reach(5000 + 3 * SEG + 9000, filler=_fakes_to_end())
+    _reads(b, 60)
+    return b
+
+
+def case_fake_breaks():
+    """the stream of the issue: 60 reads, one 52 KB record (ML:B:C = 200 x 0xFF, 491 fakes, four zero bytes, 3000 x 0xFF), 200 reads"""
+    b = StreamBuilder(4)
+    _reads(b, 60)
+    r = b.read()
+    r.raw += aux_bc("ML", fake_payload(491))
+    b.add(r)
+    _reads(b, 200)
+    return b
+
+
+def case_fake_breaks_in(j):
+    """a fake-laden record from ~5 KB to ~4.6 segments on whose fakes' chain breaks in segment j (covered segments: 1 .. 4)"""
+    def make():
+        b = StreamBuilder(20 + j)
+        b.fill(5000)
+        start = 5000
+        end = 4 * SEG + 10000
+        brk = j * SEG + 5000                               # the zero bytes lie about here
+        n_fakes = (brk - start - 400) // 100
+
+        def f(n):
+            return fake_payload(n_fakes, tail=n)
+        b.add_to_reach(end, filler=f)
+        _reads(b, 60)
+        return b
+    return make
+
+
+def case_two_long():
+    """two fake-laden records back to back: the first's fakes break, the second's run to its end"""
+    b = StreamBuilder(5)
+    b.fill(3000)
+    b.add_to_reach(3000 + 2 * SEG + 7000, filler=lambda n: fake_payload((n - 3500) // 100))
+    b.add_to_reach(3000 + 5 * SEG + 2000, filler=_fakes_to_end(lead=300))
+    _reads(b, 60)
+    return b
+
+
+def case_start_at_boundary(d):
+    """a record starts d bytes from a segment's first byte (d = -1, 0, 1)"""
+    def make():
+        b = StreamBuilder(30 + d)
+        b.fill(3 * SEG + d)
+        _reads(b, 80)
+        return b
+    return make
+
+
+def case_end_at_boundary(d):
+    """the stream ends d bytes behind a segment's end (d = 0, 1)"""
+    def make():
+        b = StreamBuilder(40 + d)
+        b.fill(3 * SEG + d)
+        return b
+    return make
+
+
+def case_odd_header():
+    """a header of a length that is not a multiple of 4, and a long fake-laden record"""
+    b = StreamBuilder(6, text="@HD\tVN:1.6\tSO:coordinate\n@CO\tx\n")
+    assert b.first % 4 != 0
+    b.fill(SEG - 2000)
+    b.add_to_reach(3 * SEG + 123, filler=_fakes_to_end(lead=257))
+    _reads(b, 50)
+    return b
+
+
+CASES = {
+    "shifted_guess": case_shifted_guess,
+    "span_1": case_span(1), "span_2": case_span(2), "span_63": case_span(63), "span_64": case_span(64), "span_65": case_span(65),
+    "fake_resync": case_fake_resync,
+    "fake_breaks": case_fake_breaks,
+    "fake_breaks_in_2": case_fake_breaks_in(2), "fake_breaks_in_3": case_fake_breaks_in(3), "fake_breaks_in_4": case_fake_breaks_in(4),
+    "two_long": case_two_long,
+    "start_at_boundary_m1": case_start_at_boundary(-1), "start_at_boundary_0": case_start_at_boundary(0), "start_at_boundary_p1": case_start_at_boundary(1),
+    "end_at_boundary_0": case_end_at_boundary(0), "end_at_boundary_p1": case_end_at_boundary(1),
+    "odd_header": case_odd_header,
+}
+
+
+def damaged_truncated():
+    """a fake-laden long record cut short by the end of the stream (its block_size reaches past it)"""
+    b = StreamBuilder(7)
+    b.fill(4000)
+    b.add_to_reach(4000 + 3 * SEG, filler=_fakes_to_end())
+    _reads(b, 20)
+    u = b.stream()
+    off = b.record_offsets()[-21]
+    return b, u[:off + 2 * SEG]
+
+
+def damaged_short_block():
+    """a real record whose block_size is below 32 directly behind a fake-laden long record"""
+    b = StreamBuilder(8)
+    b.fill(4000)
+    b.add_to_reach(4000 + 3 * SEG, filler=lambda n: fake_payload((n - 3500) // 100))
+    _reads(b, 20)
+    u = bytearray(b.stream())
+    off = b.record_offsets()[-20]
+    u[off:off + 4] = struct.pack("<I", 20)
+    return b, bytes(u)
+
+
+DAMAGED = {"truncated": damaged_truncated, "short_block": damaged_short_block}

@@ -25,6 +25,19 @@ def test_header_symbols_exported(built):
     assert lib.gce_abi_version() == capi.GCE_ABI_VERSION
 
 
+def test_index_counters_symbol(built):
+    """gce_get_index_counters (ABI v3) is exported, refuses a NULL output and, with no engine, reads the pass runner's window totals (no GPU
+    call: this runs without a device)."""
+    from gencore_amd import capi
+    from gencore_amd.engine import index_counters
+    lib = capi.load_library()
+    assert "gce_get_index_counters" in capi.EXPORTED_SYMBOLS and hasattr(lib, "gce_get_index_counters")
+    assert lib.gce_get_index_counters(None, None) == -1
+    c = index_counters()
+    assert sorted(c) == ["flagged", "rounds", "segments", "serial"] and all(v >= 0 for v in c.values())
+    assert c["flagged"] <= c["segments"] and c["serial"] <= c["rounds"]
+
+
 def test_pairing_tier_ids_match_header():
     """gce_get_pairing_tiers' tier ids (GCE_PAIR_TIER_*) are the names Engine.pairing_tiers() reports, in order."""
     from gencore_amd.engine import Engine

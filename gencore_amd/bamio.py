@@ -153,6 +153,21 @@ def run_bam_passes(in_path, out_path, params, device=0, coverage_step=1000000, b
     return run, out, passes
 
 
+def index_bam(bam, bai=None, device=0, threads=0, window_bytes=0):
+    """gce_bam_index: the BAI index of a coordinate-sorted BAM file, built on the GPU, written to `bai` (default: bam + ".bai").  window_bytes:
+    compressed bytes per window, 0 = 64 MB.  Returns dict(n_records, n_no_coor, n_bins, n_chunks, n_intervals, n_ref, read_s, gpu_s, write_s,
+    total_s); raises GceError (and leaves no index) on failure."""
+    from .capi import GceBaiRun
+    lib = capi.load_library()
+    bai = str(bam) + ".bai" if bai is None else str(bai)
+    r = GceBaiRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_index(str(bam).encode(), bai.encode(), int(device), int(threads), int(window_bytes), C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceBaiRun._fields_ if n != "pad"}
+
+
 def device_bytes(reset_peak=False):
     """gce_device_bytes: (live, peak) device bytes of the engine allocations of this process."""
     lib = capi.load_library()

@@ -13,6 +13,7 @@ from . import __version__
 
 EPILOG = """\
 Flags marked [gencore_amd] are not the reference's; every other flag, default and validation message is gencore 0.17.2's.
+--index (not the reference's) writes <output>.bai, the BAI index of the BAM output, built on the GPU.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -72,6 +73,8 @@ def build_parser():
     a("--device_memory", default="auto", help="[gencore_amd] device memory budget in GB (2^30 bytes) for one device, or auto (a fraction of the free "
                                                "memory): a file larger than the budget is processed in key-range passes. One device only. Default auto.")
     a("--threads", type=int, default=0, help="[gencore_amd] host threads for the file codecs; 0 = all cores. Default 0.")
+    a("--index", action="store_true", help="[gencore_amd] after the output and the report are written, index the BAM output on the GPU into "
+                                            "<output>.bai (BAI, SAMv1 5.2), on the first of --devices. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU). Default 6.")
     return p
@@ -137,6 +140,10 @@ def validate(o):
         if len(devices) > 1:
             err("device_memory works on one device; it cannot be combined with several --devices")
         o.device_memory_bytes = max(1, int(gb * (1 << 30)))
+    if o.index and o.output == "-":
+        err("--index needs an output file, not STDOUT")
+    if o.index and o.output.endswith("sam"):
+        err("--index needs BAM output, not SAM text")
     return devices
 
 
@@ -160,7 +167,7 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import load_bed, run_bam_depth, run_bam_passes
+    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes
     from .capi import GceError
     from .report import read_header, summary, write_json
     try:
@@ -177,6 +184,8 @@ def main(argv=None):
                          "\n----After gencore processing:\n" + summary(depth["post"], True))
         sys.stderr.flush()
         write_json(o.json, depth, names, o.coverage_sampling, command, region_names=region_names, has_bed=bool(o.bed))
+        if o.index:
+            index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 255

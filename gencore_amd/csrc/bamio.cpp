@@ -2400,3 +2400,121 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
 }
 
 }  // extern "C"
+
+
+// ---- the BAI index of a coordinate-sorted BAM (gce_bai.hpp)
+extern "C" {
+struct gce_bai;
+int gce_bai_create(int32_t device, gce_bai **out);
+void gce_bai_destroy(gce_bai *b);
+const char *gce_bai_error(gce_bai *b);
+int gce_bai_window(gce_bai *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t file_base,
+                   uint64_t skip, int32_t n_ref, int32_t last);
+int gce_bai_finish(gce_bai *b, int32_t n_ref, uint64_t eod, int64_t counts[5], int64_t *bad_rec, int32_t *bad_kind);
+int gce_bai_serialise(gce_bai *b, int32_t n_ref, uint8_t **out, size_t *out_bytes);
+
+int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, int threads, uint64_t window_bytes, gce_bai_run *out, char err[256]) {
+    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
+    seterr("");
+    if (!bam_path || !bai_path || !out) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    memset(out, 0, sizeof *out);
+    const double t_start = now_s();
+    const int fd = open(bam_path, O_RDONLY);
+    if (fd < 0) { seterr("cannot open the BAM file"); return GCE_ERR_INVALID; }
+    struct stat st;
+    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the BAM file"); return GCE_ERR_INVALID; }
+    const uint64_t fsz = (uint64_t)st.st_size;
+    const std::string tmp = std::string(bai_path) + ".tmp" + std::to_string((long long)getpid());
+    gce_bai *b = nullptr; FILE *fo = nullptr;
+    auto done = [&](int code, const char *m) {
+        seterr(m);
+        if (b) gce_bai_destroy(b);
+        if (fo) { fclose(fo); fo = nullptr; }
+        if (code != GCE_OK) unlink(tmp.c_str());
+        close(fd);
+        return code;
+    };
+    { uint8_t m2[4] = {0, 0, 0, 0}; if (fsz < 18 || pread(fd, m2, 4, 0) != 4 || m2[0] != 0x1f || m2[1] != 0x8b || m2[2] != 8 || !(m2[3] & 4)) return done(GCE_ERR_INVALID, "not a BGZF file"); }
+    const int T = threads > 0 ? threads : default_threads();
+    // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
+    uint64_t hdr_end = 0; int32_t n_ref = 0;
+    {
+        PassReader rh; rh.fd = fd; rh.fsz = fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
+        for (;;) {
+            const int g = rh.inflate_next();
+            if (g < 0) return done(GCE_ERR_INVALID, rh.msg.c_str());
+            const uint8_t *u = rh.win.p; const uint64_t n = rh.n;
+            if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return done(GCE_ERR_INVALID, "not a BAM stream");
+            if (n >= 12) {
+                uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
+                if (q + l_text + 4 <= n) {
+                    q += l_text;
+                    const uint32_t nr = rd32(u + q); q += 4;
+                    bool ok = nr < 0x7FFFFFFFu;
+                    for (uint32_t r = 0; r < nr && ok; r++) {
+                        if (q + 4 > n) { ok = false; break; }
+                        const uint32_t ln = rd32(u + q); q += 4;
+                        if (q + (uint64_t)ln + 4 > n) { ok = false; break; }
+                        q += ln + 4;
+                    }
+                    if (ok) { hdr_end = q; n_ref = (int32_t)nr; break; }
+                }
+            }
+            if (g == 0) return done(GCE_ERR_INVALID, "truncated BAM header");
+        }
+    }
+    out->n_ref = n_ref;
+    int rc = gce_bai_create(device, &b);
+    if (rc != GCE_OK) return done(rc, "no HIP device");
+    // ---- the file from its first byte, window by window: the host reads and finds the members, the GPU inflates and indexes them
+    PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? (size_t)window_bytes : ((size_t)64 << 20);
+    uint64_t skip = hdr_end, eod = 0;
+    double read_s = 0, gpu_s = 0;
+    for (;;) {
+        double t0 = now_s();
+        const int g = rd.members_next();
+        if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str());
+        if (g == 0) break;
+        const uint64_t file_base = rd.at - rd.have;
+        rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
+        for (const Block &k : rd.blocks) {
+            rd.z_coff.push_back(k.coff); rd.z_csize.push_back(k.csize); rd.z_usize.push_back(k.usize); u_all += k.usize;
+            if (k.usize) eod = (file_base + k.coff + k.csize) << 16;                  // rule V: just past the last non-empty member
+        }
+        const uint64_t sk = std::min<uint64_t>(skip, u_all);
+        read_s += now_s() - t0; t0 = now_s();
+        rc = gce_bai_window(b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), file_base, sk, n_ref, rd.last_piece() ? 1 : 0);
+        gpu_s += now_s() - t0;
+        if (rc != GCE_OK) return done(rc, gce_bai_error(b));
+        skip -= sk;
+        if (rd.last_piece()) break;
+    }
+    if (rd.have != rd.used) return done(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
+    if (skip) return done(GCE_ERR_INVALID, "truncated BAM header");
+    double t0 = now_s();
+    int64_t counts[5] = {0, 0, 0, 0, 0}, bad = -1; int32_t kind = 0;
+    if ((rc = gce_bai_finish(b, n_ref, eod, counts, &bad, &kind)) != GCE_OK) return done(rc, gce_bai_error(b));
+    gpu_s += now_s() - t0;
+    if (bad >= 0) {
+        static const char *why[3] = {"is out of coordinate order (records must come in (tid, pos) order, unplaced ones last)", "ends beyond 2^29, the range of a BAI index",
+                                     "names a contig the header does not have"};
+        char m[256]; snprintf(m, sizeof m, "BAM record %lld (counting from 0) %s", (long long)bad, why[kind < 3 ? kind : 0]);
+        return done(GCE_ERR_INVALID, m);
+    }
+    t0 = now_s();
+    uint8_t *bytes = nullptr; size_t nbytes = 0;
+    if ((rc = gce_bai_serialise(b, n_ref, &bytes, &nbytes)) != GCE_OK) return done(rc, "out of host memory");
+    fo = fopen(tmp.c_str(), "wb");
+    const bool wrote = fo && fwrite(bytes, 1, nbytes, fo) == nbytes;
+    free(bytes);
+    if (!wrote) return done(GCE_ERR_INVALID, "cannot write the index file");
+    const bool closed = fclose(fo) == 0; fo = nullptr;
+    if (!closed || rename(tmp.c_str(), bai_path) != 0) return done(GCE_ERR_INVALID, "cannot write the index file");
+    out->write_s = now_s() - t0;
+    out->n_records = counts[0]; out->n_no_coor = counts[1]; out->n_bins = counts[2]; out->n_chunks = counts[3]; out->n_intervals = counts[4];
+    out->read_s = read_s; out->gpu_s = gpu_s;
+    out->total_s = now_s() - t_start;
+    return done(GCE_OK, "");
+}
+
+}  // extern "C"

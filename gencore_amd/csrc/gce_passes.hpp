@@ -92,6 +92,94 @@ static hipError_t pass_grow(DevBuf &b, size_t need, size_t used, hipStream_t s) 
     return hipSuccess;
 }
 
+// one window of a BGZF file on the GPU, shared by the pass runner (gce_passes_window) and the BAI indexer (gce_bai.hpp): whole BGZF members in
+// host memory are copied to HBM and inflated (k_bgzf_inflate, as gce_raw_push_bgzf) behind the record the last window's end cut; the records of
+// [skip, total) are indexed by the segment walks of gce_raw_finish with a soft end (k_raw_seg / k_raw_check / k_raw_fix / k_raw_repair): the
+// record the window's end cuts is left for win_carry to move to the front.  win holds the inflated bytes, off the n_rec record starts.
+struct WinIdx {
+    DevBuf win, off, zc, zdir, zerr, guess, leave, cnt, base, bad_of, rmisc, ctmp; uint64_t carry_n = 0;
+    void release() { for (DevBuf *b : {&win, &off, &zc, &zdir, &zerr, &guess, &leave, &cnt, &base, &bad_of, &rmisc, &ctmp}) b->release(); carry_n = 0; }
+};
+#define WCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { msg = std::string(#call) + ": " + hipGetErrorString(_e); return _e == hipErrorOutOfMemory ? GCE_ERR_OOM : GCE_ERR_HIP; } } while (0)
+// -> *total (inflated bytes in w.win, the carried ones included), *n_rec, *end (where the window's last whole record ends).  ctr: the four index
+// counters to add to (gce_get_index_counters) or NULL.  last: the final piece of the file (a record cut there is a truncated stream).
+static int win_inflate_index(WinIdx &w, DevBuf &tmp, hipStream_t s, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize,
+                             const uint32_t *usize, uint64_t skip, int32_t n_ref, int32_t last, int64_t *ctr, uint64_t *total_out, uint64_t *n_rec_out, uint64_t *end_out, std::string &msg) {
+    std::vector<InfDir> dir; uint64_t total = w.carry_n;
+    for (int32_t k = 0; k < n_members; k++) {
+        if (coff[k] > comp_bytes || csize[k] > comp_bytes - coff[k] || usize[k] > 0x10000u) { msg = "BGZF member outside its buffer"; return GCE_ERR_INVALID; }
+        if (usize[k] == 0) continue;
+        InfDir d; d.coff = coff[k]; d.uoff = total; d.csize = csize[k]; d.usize = usize[k]; dir.push_back(d); total += usize[k];
+    }
+    if (w.carry_n && skip) return GCE_ERR_INVALID;
+    WCHK(pass_grow(w.win, (size_t)total + 64, (size_t)w.carry_n, s));
+    if (!dir.empty()) {
+        const size_t m = dir.size();
+        WCHK(w.zc.ensure(comp_bytes + 64)); WCHK(w.zdir.ensure(m * (sizeof(InfDir) + INF_NSYM) + 64)); WCHK(w.zerr.ensure(16));
+        WCHK(hipMemcpyAsync(w.zc.p, comp, comp_bytes, hipMemcpyHostToDevice, s));
+        WCHK(hipMemsetAsync((char *)w.zc.p + comp_bytes, 0, 64, s));                 // (the bit reader looks up to 32 bytes ahead)
+        WCHK(hipMemcpyAsync(w.zdir.p, dir.data(), m * sizeof(InfDir), hipMemcpyHostToDevice, s));
+        const unsigned int init[2] = {0u, 0xFFFFFFFFu};
+        WCHK(hipMemcpyAsync(w.zerr.p, init, 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((m + INF_T - 1) / INF_T)), dim3(INF_T), 0, s, w.zc.as<uint8_t>(), (const InfDir *)w.zdir.p, (uint32_t)m, w.win.as<uint8_t>(), w.zerr.as<unsigned int>(),
+                           w.zdir.as<uint8_t>() + m * sizeof(InfDir));
+        unsigned int got[2] = {0, 0};
+        WCHK(hipMemcpyAsync(got, w.zerr.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s)); WCHK(hipGetLastError());
+        if (got[0]) { char m2[96]; snprintf(m2, sizeof m2, "inflate / CRC failure in BGZF member %u of a window", got[1]); msg = m2; return GCE_ERR_INVALID; }
+    }
+    WCHK(hipMemsetAsync(w.win.as<uint8_t>() + total, 0, 64, s));
+    const uint64_t start = std::min<uint64_t>(skip, total);
+    const uint8_t *u = w.win.as<uint8_t>();
+    uint64_t n_rec = 0, end = start;
+    if (total > start) {                                                             // ---- the record index of [start, total), soft end
+        const uint64_t nseg = (total - start + RAW_SEG - 1) / RAW_SEG;
+        const unsigned nbs = (unsigned)((nseg + 255) / 256);
+        WCHK(w.guess.ensure(nseg * 8)); WCHK(w.leave.ensure(nseg * 8)); WCHK(w.cnt.ensure(nseg * 4 + 8)); WCHK(w.base.ensure(nseg * 8 + 8)); WCHK(w.bad_of.ensure(nseg + 8)); WCHK(w.rmisc.ensure(64));
+        WCHK(hipMemsetAsync(w.rmisc.p, 0, 64, s));
+        hipLaunchKernelGGL(k_raw_seg<true>, dim3(nbs), dim3(256), 0, s, u, start, total, n_ref, nseg, w.guess.as<uint64_t>(), w.leave.as<uint64_t>(), w.cnt.as<uint32_t>());
+        hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)w.guess.p, (const uint64_t *)w.leave.p, nseg, total, w.rmisc.as<unsigned int>(), w.bad_of.as<uint8_t>());
+        unsigned int flags[2] = {0, 0};
+        WCHK(hipMemcpyAsync(flags, w.rmisc.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
+        if (ctr) { __atomic_add_fetch(&ctr[0], (int64_t)nseg, __ATOMIC_RELAXED); __atomic_add_fetch(&ctr[1], (int64_t)flags[0], __ATOMIC_RELAXED); }
+        for (int round = 0; flags[0] && round < 64; round++) {
+            WCHK(hipMemsetAsync(w.rmisc.p, 0, 16, s));
+            hipLaunchKernelGGL(k_raw_fix<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, w.guess.as<uint64_t>(), w.leave.as<uint64_t>(), w.cnt.as<uint32_t>(), (const uint8_t *)w.bad_of.p);
+            hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)w.guess.p, (const uint64_t *)w.leave.p, nseg, total, w.rmisc.as<unsigned int>(), w.bad_of.as<uint8_t>());
+            WCHK(hipMemcpyAsync(flags, w.rmisc.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
+            if (ctr) __atomic_add_fetch(&ctr[2], (int64_t)1, __ATOMIC_RELAXED);
+        }
+        if (flags[0]) {
+            if (ctr) __atomic_add_fetch(&ctr[3], (int64_t)1, __ATOMIC_RELAXED);
+            WCHK(hipMemsetAsync(w.rmisc.p, 0, 16, s));
+            hipLaunchKernelGGL(k_raw_repair<true>, dim3(1), dim3(64), 0, s, u, start, total, nseg, w.guess.as<uint64_t>(), w.leave.as<uint64_t>(), w.cnt.as<uint32_t>(), w.rmisc.as<unsigned int>() + 1);
+            WCHK(hipMemcpyAsync(flags, w.rmisc.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
+            if (flags[1]) { msg = "truncated or damaged BAM record stream"; return GCE_ERR_INVALID; }
+        }
+        WCHK(dev_exclusive_sum(w.cnt.as<uint32_t>(), nseg, w.base.as<uint64_t>(), tmp, s));
+        WCHK(hipMemcpyAsync(&n_rec, w.base.as<uint64_t>() + nseg, 8, hipMemcpyDeviceToHost, s));
+        WCHK(hipMemcpyAsync(&end, w.leave.as<uint64_t>() + nseg - 1, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
+        if (end > total || n_rec >= 0x7FFFFFF0ull) { msg = "truncated or damaged BAM record stream"; return GCE_ERR_INVALID; }
+        WCHK(w.off.ensure((size_t)(n_rec + 1) * 8));
+        if (n_rec) hipLaunchKernelGGL(k_raw_offsets<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, (const uint64_t *)w.guess.p, (const uint64_t *)w.base.p, w.off.as<uint64_t>());
+        WCHK(hipStreamSynchronize(s)); WCHK(hipGetLastError());
+    }
+    if (last && end != total) { msg = "truncated record at the end of the BAM stream"; return GCE_ERR_INVALID; }
+    *total_out = total; *n_rec_out = n_rec; *end_out = end;
+    return GCE_OK;
+}
+// the record the window's end cut ([end, total) of w.win) to the front, for the next window
+static int win_carry(WinIdx &w, hipStream_t s, uint64_t total, uint64_t end, std::string &msg) {
+    w.carry_n = total - end;
+    if (w.carry_n) {
+        WCHK(w.ctmp.ensure(w.carry_n + 64));
+        WCHK(hipMemcpyAsync(w.ctmp.p, w.win.as<uint8_t>() + end, w.carry_n, hipMemcpyDeviceToDevice, s));
+        WCHK(hipMemcpyAsync(w.win.p, w.ctmp.p, w.carry_n, hipMemcpyDeviceToDevice, s));
+        WCHK(hipStreamSynchronize(s));
+    }
+    return GCE_OK;
+}
+#undef WCHK
+
 }  // namespace
 
 struct gce_passes {
@@ -99,8 +187,8 @@ struct gce_passes {
     hipStream_t s = nullptr;
     std::string err;
     // the window
-    DevBuf win, off, core, key, tick, xs, flag, sel, size, dst, misc, tmp, ev_tid, ev_pos;
-    DevBuf zc, zdir, zerr, guess, leave, cnt, base, bad_of, rmisc, ctmp; uint64_t carry_n = 0;     // GPU inflate + record index of the window
+    DevBuf core, key, tick, xs, flag, sel, size, dst, misc, tmp, ev_tid, ev_pos;
+    WinIdx w;                                                                        // GPU inflate + record index of the window
     // the stream so far: records seen, global tick, cut, first unmapped read
     uint64_t gbase = 0; unsigned long long carry = 0; int64_t cut = -1; bool unmapped_seen = false, bad = false;
     // key pass: key + weight of every read in front of the cut; the flush events
@@ -140,8 +228,8 @@ void gce_passes_destroy(gce_passes *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     (void)hipStreamSynchronize(p->s);
-    for (DevBuf *b : {&p->win, &p->off, &p->core, &p->key, &p->tick, &p->xs, &p->flag, &p->sel, &p->size, &p->dst, &p->misc, &p->tmp, &p->ev_tid, &p->ev_pos, &p->key_all, &p->w_all, &p->ptick, &p->pgidx,
-                      &p->zc, &p->zdir, &p->zerr, &p->guess, &p->leave, &p->cnt, &p->base, &p->bad_of, &p->rmisc, &p->ctmp}) b->release();
+    p->w.release();
+    for (DevBuf *b : {&p->core, &p->key, &p->tick, &p->xs, &p->flag, &p->sel, &p->size, &p->dst, &p->misc, &p->tmp, &p->ev_tid, &p->ev_pos, &p->key_all, &p->w_all, &p->ptick, &p->pgidx}) b->release();
     (void)hipStreamDestroy(p->s);
     delete p;
 }
@@ -151,7 +239,7 @@ int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes)
     return hipMemGetInfo(free_bytes, total_bytes) == hipSuccess ? GCE_OK : GCE_ERR_HIP;
 }
 
-// the records of the window (n, at p->off in p->win, on the device): e == NULL: the key pass; otherwise pass p->k, whose records go to e's raw
+// the records of the window (n, at p->w.off in p->w.win, on the device): e == NULL: the key pass; otherwise pass p->k, whose records go to e's raw
 // stream.  *cut_reached: the --quit_after_contig cut lies in this window (nothing behind it exists: the caller stops reading).
 static int pass_records(gce_passes *p, gce_engine *e, int64_t n, int32_t *cut_reached) {
     *cut_reached = 0;
@@ -162,7 +250,7 @@ static int pass_records(gce_passes *p, gce_engine *e, int64_t n, int32_t *cut_re
     const size_t n1 = (size_t)n;
     PCHK(p->core.ensure(n1 * sizeof(gce_core) + 64)); PCHK(p->key.ensure(n1 * 8)); PCHK(p->tick.ensure(n1 * 8 + 8));
     PCHK(p->xs.ensure(n1 * 8 + 16)); PCHK(p->flag.ensure(n1 + 64)); PCHK(p->sel.ensure(n1 * 4 + 64)); PCHK(p->misc.ensure(64));
-    const uint8_t *u = p->win.as<uint8_t>(); const uint64_t *off = p->off.as<uint64_t>();
+    const uint8_t *u = p->w.win.as<uint8_t>(); const uint64_t *off = p->w.off.as<uint64_t>();
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_pass_core, dim3(nb), dim3(256), 0, s, u, off, n, p->core.as<gce_core>());
     // misc: [0] the first read of contig >= max_contig, [1] the first unmapped read, [2] bad, [4..5] a count (uint64)
@@ -255,76 +343,12 @@ int gce_passes_window(gce_passes *p, gce_engine *e, const void *comp, size_t com
     *cut_reached = 0;
     if (p->cut >= 0) { *cut_reached = 1; return GCE_OK; }
     (void)hipSetDevice(p->device);
-    hipStream_t s = p->s;
-    std::vector<InfDir> dir; uint64_t total = p->carry_n;
-    for (int32_t k = 0; k < n_members; k++) {
-        if (coff[k] > comp_bytes || csize[k] > comp_bytes - coff[k] || usize[k] > 0x10000u) return pfail(p, GCE_ERR_INVALID, "BGZF member outside its buffer");
-        if (usize[k] == 0) continue;
-        InfDir d; d.coff = coff[k]; d.uoff = total; d.csize = csize[k]; d.usize = usize[k]; dir.push_back(d); total += usize[k];
-    }
-    if (p->carry_n && skip) return GCE_ERR_INVALID;
-    PCHK(pass_grow(p->win, (size_t)total + 64, (size_t)p->carry_n, s));
-    if (!dir.empty()) {
-        const size_t m = dir.size();
-        PCHK(p->zc.ensure(comp_bytes + 64)); PCHK(p->zdir.ensure(m * (sizeof(InfDir) + INF_NSYM) + 64)); PCHK(p->zerr.ensure(16));
-        PCHK(hipMemcpyAsync(p->zc.p, comp, comp_bytes, hipMemcpyHostToDevice, s));
-        PCHK(hipMemsetAsync((char *)p->zc.p + comp_bytes, 0, 64, s));                 // (the bit reader looks up to 32 bytes ahead)
-        PCHK(hipMemcpyAsync(p->zdir.p, dir.data(), m * sizeof(InfDir), hipMemcpyHostToDevice, s));
-        const unsigned int init[2] = {0u, 0xFFFFFFFFu};
-        PCHK(hipMemcpyAsync(p->zerr.p, init, 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((m + INF_T - 1) / INF_T)), dim3(INF_T), 0, s, p->zc.as<uint8_t>(), (const InfDir *)p->zdir.p, (uint32_t)m, p->win.as<uint8_t>(), p->zerr.as<unsigned int>(),
-                           p->zdir.as<uint8_t>() + m * sizeof(InfDir));
-        unsigned int got[2] = {0, 0};
-        PCHK(hipMemcpyAsync(got, p->zerr.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s)); PCHK(hipGetLastError());
-        if (got[0]) { char m2[96]; snprintf(m2, sizeof m2, "inflate / CRC failure in BGZF member %u of a window", got[1]); return pfail(p, GCE_ERR_INVALID, m2); }
-    }
-    PCHK(hipMemsetAsync(p->win.as<uint8_t>() + total, 0, 64, s));
-    const uint64_t start = std::min<uint64_t>(skip, total);
-    const uint8_t *u = p->win.as<uint8_t>();
-    uint64_t n_rec = 0, end = start;
-    if (total > start) {                                                             // ---- the record index of [start, total), soft end
-        const uint64_t nseg = (total - start + RAW_SEG - 1) / RAW_SEG;
-        const unsigned nbs = (unsigned)((nseg + 255) / 256);
-        PCHK(p->guess.ensure(nseg * 8)); PCHK(p->leave.ensure(nseg * 8)); PCHK(p->cnt.ensure(nseg * 4 + 8)); PCHK(p->base.ensure(nseg * 8 + 8)); PCHK(p->bad_of.ensure(nseg + 8)); PCHK(p->rmisc.ensure(64));
-        PCHK(hipMemsetAsync(p->rmisc.p, 0, 64, s));
-        hipLaunchKernelGGL(k_raw_seg<true>, dim3(nbs), dim3(256), 0, s, u, start, total, n_ref, nseg, p->guess.as<uint64_t>(), p->leave.as<uint64_t>(), p->cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)p->guess.p, (const uint64_t *)p->leave.p, nseg, total, p->rmisc.as<unsigned int>(), p->bad_of.as<uint8_t>());
-        unsigned int flags[2] = {0, 0};
-        PCHK(hipMemcpyAsync(flags, p->rmisc.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));
-        __atomic_add_fetch(&g_pass_idx_ctr[0], (int64_t)nseg, __ATOMIC_RELAXED); __atomic_add_fetch(&g_pass_idx_ctr[1], (int64_t)flags[0], __ATOMIC_RELAXED);
-        for (int round = 0; flags[0] && round < 64; round++) {
-            PCHK(hipMemsetAsync(p->rmisc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_fix<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, p->guess.as<uint64_t>(), p->leave.as<uint64_t>(), p->cnt.as<uint32_t>(), (const uint8_t *)p->bad_of.p);
-            hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)p->guess.p, (const uint64_t *)p->leave.p, nseg, total, p->rmisc.as<unsigned int>(), p->bad_of.as<uint8_t>());
-            PCHK(hipMemcpyAsync(flags, p->rmisc.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));
-            __atomic_add_fetch(&g_pass_idx_ctr[2], (int64_t)1, __ATOMIC_RELAXED);
-        }
-        if (flags[0]) {
-            __atomic_add_fetch(&g_pass_idx_ctr[3], (int64_t)1, __ATOMIC_RELAXED);
-            PCHK(hipMemsetAsync(p->rmisc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_repair<true>, dim3(1), dim3(64), 0, s, u, start, total, nseg, p->guess.as<uint64_t>(), p->leave.as<uint64_t>(), p->cnt.as<uint32_t>(), p->rmisc.as<unsigned int>() + 1);
-            PCHK(hipMemcpyAsync(flags, p->rmisc.p, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));
-            if (flags[1]) return pfail(p, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
-        }
-        PCHK(dev_exclusive_sum(p->cnt.as<uint32_t>(), nseg, p->base.as<uint64_t>(), p->tmp, s));
-        PCHK(hipMemcpyAsync(&n_rec, p->base.as<uint64_t>() + nseg, 8, hipMemcpyDeviceToHost, s));
-        PCHK(hipMemcpyAsync(&end, p->leave.as<uint64_t>() + nseg - 1, 8, hipMemcpyDeviceToHost, s)); PCHK(hipStreamSynchronize(s));
-        if (end > total || n_rec >= 0x7FFFFFF0ull) return pfail(p, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
-        PCHK(p->off.ensure((size_t)(n_rec + 1) * 8));
-        if (n_rec) hipLaunchKernelGGL(k_raw_offsets<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, (const uint64_t *)p->guess.p, (const uint64_t *)p->base.p, p->off.as<uint64_t>());
-        PCHK(hipStreamSynchronize(s)); PCHK(hipGetLastError());
-    }
-    if (last && end != total) return pfail(p, GCE_ERR_INVALID, "truncated record at the end of the BAM stream");
-    const int rc = pass_records(p, e, (int64_t)n_rec, cut_reached);
+    uint64_t total = 0, n_rec = 0, end = 0;
+    int rc = win_inflate_index(p->w, p->tmp, p->s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, g_pass_idx_ctr, &total, &n_rec, &end, p->err);
     if (rc != GCE_OK) return rc;
-    p->carry_n = total - end;                                                        // ---- the record the window's end cut, to the front
-    if (p->carry_n && !*cut_reached) {
-        PCHK(p->ctmp.ensure(p->carry_n + 64));
-        PCHK(hipMemcpyAsync(p->ctmp.p, u + end, p->carry_n, hipMemcpyDeviceToDevice, s));
-        PCHK(hipMemcpyAsync(p->win.p, p->ctmp.p, p->carry_n, hipMemcpyDeviceToDevice, s));
-        PCHK(hipStreamSynchronize(s));
-    }
-    return GCE_OK;
+    if ((rc = pass_records(p, e, (int64_t)n_rec, cut_reached)) != GCE_OK) return rc;
+    if (*cut_reached) { p->w.carry_n = total - end; return GCE_OK; }              // ---- the record the window's end cut, to the front
+    return win_carry(p->w, p->s, total, end, p->err);
 }
 
 // after the key pass: the plan.  budget == 0: exactly min_passes passes; otherwise P >= min_passes passes whose weight fits what the budget
@@ -386,7 +410,7 @@ int gce_passes_begin(gce_passes *p, gce_engine *e, int32_t k) {
     if (!p || !e || !e->raw_mode || k < 0 || k >= p->P) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     if (e->up_stream) PCHK(hipStreamSynchronize(e->up_stream));
-    p->k = k; p->pm = 0; p->gbase = 0; p->carry = 0; p->cut = -1; p->wm = 0x7FFFFFFFFFFFFFFFll; p->carry_n = 0;
+    p->k = k; p->pm = 0; p->gbase = 0; p->carry = 0; p->cut = -1; p->wm = 0x7FFFFFFFFFFFFFFFll; p->w.carry_n = 0;
     return GCE_OK;
 }
 // pass k's windows are in: the engine indexes its part of the stream (gce_raw_finish) and gets the reads' global ticks, the flush events of the

@@ -562,6 +562,21 @@ typedef struct gce_pass_run {
 int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fasta_path, const char *bed_path, int32_t coverage_step, const gce_params *params,
                        int32_t device, int threads, int level, size_t device_budget_bytes, int32_t min_passes, size_t window_bytes,
                        gce_bam_run *out, gce_depth_run *depth, gce_pass_run *run, char err[256]);
+/* The BAI index (SAMv1 5.2) of a coordinate-sorted BAM file, built on ONE device (addition under ABI v3; gencore_amd/csrc/gce_bai.hpp,
+ * DESIGN.md 4c).  The file is streamed in windows of window_bytes compressed bytes (0 = 64 MB) as gce_run_bam_passes streams it: the GPU inflates
+ * every window and finds its records; 24 bytes per record stay in device memory (GCE_ERR_OOM with a message when they do not fit).  The bins,
+ * chunks, linear index and per-contig counts follow DESIGN.md 4c (bins not folded into their parents, written in ascending order).  The index is
+ * written to a temporary name beside bai_path and renamed at the end: a failed call leaves no index and never touches the BAM.  GCE_ERR_INVALID
+ * with a message when the input is not BGZF or is truncated, or when a record is out of (tid, pos) order or ends beyond 2^29 (the message names
+ * the record, counting from 0).  threads: host threads for inflating the header (0 = all cores). */
+typedef struct gce_bai_run {
+    int64_t n_records;              /* records read */
+    int64_t n_no_coor;              /* records with tid < 0 */
+    int64_t n_bins, n_chunks, n_intervals;   /* written to the .bai, pseudo-bins excluded */
+    int32_t n_ref, pad;
+    double  read_s, gpu_s, write_s, total_s;
+} gce_bai_run;
+int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, int threads, uint64_t window_bytes, gce_bai_run *out, char err[256]);
 /* Live and peak device bytes of the engine allocations of the whole PROCESS (every engine, every thread); reset_peak != 0 restarts the peak at
  * the live count.  gce_run_bam_passes resets it on entry: its run->peak_device_bytes covers other engines working in the same process as well. */
 int gce_device_bytes(int64_t *live, int64_t *peak, int32_t reset_peak);

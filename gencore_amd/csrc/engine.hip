@@ -104,7 +104,7 @@ struct gce_engine {
     std::vector<gce_engine *> mirrors;
     DevBuf sh_tickall, sh_shard, sh_flag, sh_sel, sh_core, sh_qoff, sh_coff, sh_soff, sh_loff, sh_nm, sh_nmt, sh_mioff, sh_tick, sh_roff, sh_nmpos, sh_keys, sh_stage; int64_t shard_n = -1;
     bool shard_cut_done = false;          // gce_raw_select_shard applied --quit_after_contig to the WHOLE stream: this engine's gce_process does not look for the cut again
-    bool tab_clean = false; const void *tab_clean_ptr = nullptr;   // the bucket table is all-zero (k_scatter wipes what a step used)
+    bool tab_clean = false; const void *tab_clean_ptr = nullptr; size_t tab_clean_cap = 0;   // the bucket table is all-zero (k_scatter wipes what a step used)
     DevBuf cl_ikey, cl_start, cl_n, cl_npairs, cl_ngroups, cl_gbase, cl_nresult, cl_hasumi, cl_tier;
     DevBuf members, sorted, pl, pr, pu, pg, gpl, gpr, grp_begin, grp_n, gl_cluster, g_begin, g_np;
     DevBuf slow_args, deep_list, k64, slow_list, left_list, pf_flag, pf_list, pq_flag, pq_list, p16_flag, p16_list, pd_slab, gen_flag, gen_list, score_list, gw, g_wbase, vb_start, rp_left, rp_right, rp_merge, rp_rmerge, rp_umi, rp_umilen, rp_state, rp_supp, rp_nm, rp_qsl, rp_qsr, scan_part, si;
@@ -310,6 +310,7 @@ __global__ void k_add_u64(uint64_t *a, uint64_t n, uint64_t base) {
 // the caller does to prepare batch k + 1.  MI tags and gce_batch.tick travel too (their buffers grow with the batches).
 int gce_reserve(gce_engine *e, int64_t n_reads, size_t qname_bytes, size_t cigar_words, size_t seq_bytes, size_t qual_bytes) {
     if (!e || n_reads < 0) return GCE_ERR_INVALID;
+    if (e->processed) gce_reset(e);                                                // a new stream behind a processed one (as the submits do)
     if (e->host_mode || e->device_mode) return fail(e, GCE_ERR_INVALID, "gce_reserve after a submit");
     (void)hipSetDevice(e->prm.device);
     const size_t n = (size_t)n_reads;
@@ -815,10 +816,11 @@ static int gce_process_impl(gce_engine *e) {
         HIPCHK(hipMemcpyAsync(e->ev_pos.p, e->h_ev_pos.data(), e->h_ev_pos.size() * 4, hipMemcpyHostToDevice, e->stream));
     }
     hipStream_t s = e->stream;
-    // The bucket table is cleared by its users (k_scatter): a memset only for a new allocation or after a step that did not get that far.
-    if (!e->tab_clean || e->tab_clean_ptr != e->table.p) {
+    // The bucket table is cleared by its users (k_scatter): a memset only for a new allocation or after a step that did not get that far.  A new
+    // allocation may come back at the address of the one it replaced, so the capacity tells it apart too (DevBuf::ensure only ever grows it).
+    if (!e->tab_clean || e->tab_clean_ptr != e->table.p || e->tab_clean_cap != e->table.cap) {
         HIPCHK(hipMemsetAsync(e->table.p, 0, e->table.cap, s));
-        e->tab_clean_ptr = e->table.p;
+        e->tab_clean_ptr = e->table.p; e->tab_clean_cap = e->table.cap;
     }
     e->tab_clean = false;
     HIPCHK(hipEventRecord(e->ev[EV_START], s));

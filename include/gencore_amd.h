@@ -235,6 +235,8 @@ void gce_pack_reference(const char *bases, int64_t n_bases, uint8_t *nibbles_out
  * host arrays, copied.  n_events = 0 with tick given means "no flush ever fires".  Unmapped reads must follow every
  * mapped read of the stream in this mode. */
 int gce_set_flush_events(gce_engine *e, int32_t n_events, const int32_t *ev_tid, const int32_t *ev_pos);
+/*   The events stay set across gce_reset and the implicit reset of the next submit (set once for many steps of the same stream); a call
+ *   replaces them, and a stream without gce_batch.tick ignores them. */
 
 /* Replaces: the per-read loop body Gencore::addToCluster(b) (src/gencore.cpp:272,469-476) for a whole batch.
  * Host buffers are copied to HBM; the caller keeps ownership.  May be called repeatedly; batches are
@@ -265,6 +267,8 @@ int gce_result_device(gce_engine *e, gce_result *out);
  * addToCluster the same way).  With gce_submit_async the caller's buffers must stay untouched until gce_submit_wait(ticket)
  * or gce_process returns.  MI tags (gce_batch.mi / mi_off) and per-read ticks (gce_batch.tick; every batch of a stream or none) travel on this path too
  * (round 5); a batch that exceeds the reservation makes the buffers grow instead of failing. */
+/* The reservation outlives gce_reset and every later stream of the engine: each new stream is copied into the reserved buffers (grown
+ * when it is larger), through the same gce_submit / gce_submit_async path. */
 int gce_reserve(gce_engine *e, int64_t n_reads, size_t qname_bytes, size_t cigar_words, size_t seq_bytes, size_t qual_bytes);
 int gce_submit_async(gce_engine *e, const gce_batch *batch, int32_t *ticket);
 int gce_submit_wait(gce_engine *e, int32_t ticket);
@@ -346,7 +350,14 @@ int gce_stream_context(int32_t device, const gce_core *core, int64_t n_reads, in
  * (addition under ABI v3; gce_run_bam_passes plans the same way with the records' full sizes).  world <= 64. */
 int gce_plan_shards(int32_t device, const gce_core *core, int64_t n_reads, int32_t world, int32_t mode, int32_t *shard_out);
 void gce_free(void *p);
-/* Drop all submitted reads/results but keep params, reference and allocations (for repeated bench steps). */
+/* Drop all submitted reads/results but keep params, reference and allocations (for repeated bench steps).
+ * Survives a reset: the params (gce_create), every staged contig and window, the flush events of gce_set_flush_events (used only by a stream
+ * whose batches carry gce_batch.tick; bench's N > 1 path and the pass runner set them once and rely on this), a gce_reserve reservation, the
+ * device buffers (they grow, never shrink), the bucket table (all-zero again after every step that ran the clustering) and the once-per-engine
+ * "k_vote off" note.  Dropped: the submitted batches, the result table, ticks / MI tags / the raw stream and any gce_raw_select_shard choice.
+ * The first gce_reserve / gce_submit / gce_submit_device / gce_submit_async / gce_raw_begin after a gce_process (successful or failed) resets implicitly,
+ * so a new stream needs no call.  gce_reset IS needed after a refused submit that left the batches accepted before it in the engine -- a
+ * gce_submit after gce_submit_device, a batch with gce_batch.tick behind one without (or the reverse) -- or to drop a stream never processed. */
 int gce_reset(gce_engine *e);
 
 const char *gce_last_error(const gce_engine *e);   /* human-readable detail of the last failure */

@@ -1301,6 +1301,15 @@ int gce_get_vote_counters(gce_engine *e, int64_t out[4]) {
     return GCE_OK;
 }
 
+// group sides FINISHED per consensus kernel in the last gce_process: [0] k_vote (every side of a group it did not hand on), [1] k_consensus_fast,
+// [2] k_deep_prepare (deep sides without a template: nothing to vote), [3] k_vote_deep, [4] k_consensus_slow.  The five add up to 2 x groups.
+int gce_get_consensus_counters(gce_engine *e, int64_t out[5]) {
+    if (!e || !out || !e->processed) return GCE_ERR_INVALID;
+    out[0] = 2 * (int64_t)e->h_si.n_groups - (int64_t)(e->h_si.hand_on >> 32);
+    out[1] = (int64_t)e->h_si.cs_fast; out[2] = (int64_t)e->h_si.cs_prep; out[3] = (int64_t)e->h_si.cs_deep; out[4] = (int64_t)e->h_si.cs_slow;
+    return GCE_OK;
+}
+
 // the GPU record index (gce_bamdev.hpp k_raw_seg .. k_raw_repair): [0] 16 KB segments, [1] of those flagged by the first check, [2] parallel
 // repair rounds (k_raw_fix + k_raw_check), [3] serial repairs (k_raw_repair).  e: its last gce_raw_finish; NULL: summed over the windows of
 // the last pass runner of the process (gce_passes_window, the key pass and every pass)

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_deep_prepare(DevBatch b, DevParams p, W
         if (lane == 0) { atomicAdd(&w.si->prof[6], wall_clock64() - dp_t0_); atomicAdd(&w.si->prof[7], (unsigned long long)np * 100ull); atomicAdd(&w.si->prof[14], 1ull); }
 #endif
         if (lane == 0) {
-            if (sp.out == NONE32) { (is_left ? w.rp_left : w.rp_right)[gi] = NONE32; w.gen_flag[e] = DV_DONE; }
+            if (sp.out == NONE32) { (is_left ? w.rp_left : w.rp_right)[gi] = NONE32; w.gen_flag[e] = DV_DONE; atomicAdd(&w.si->cs_prep, 1u); }
             else if (sp.len <= DV_COLS && sp.nv < 65536u) {
                 DeepRec r; r.e = e; r.out = sp.out; r.nv = sp.nv; r.len_mode = (uint32_t)sp.len | (sp.left_mode ? 1u << 16 : 0u);
                 ((DeepRec *)w.deep_list)[atomicAdd(&w.si->n_deep, 1u)] = r;
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(DV_T) void k_vote_deep(DevBatch b, DevParams p, Wor
             }
             for (int col = tid; col < len; col += DV_T) oqual[col] = s_nq[col];
         }
-        if (tid == 0) { rp_out[gi] = out; w.gen_flag[e] = DV_DONE; }
+        if (tid == 0) { rp_out[gi] = out; w.gen_flag[e] = DV_DONE; atomicAdd(&w.si->cs_deep, 1u); }
         DV_TICK(5);
     }
 }

@@ -83,6 +83,7 @@ struct StreamInfo {
     unsigned long long n_p16_items;      // clusters of <= 16 reads: the quarter-wave pairing kernel's list
     unsigned long long vote_rounds2;     // k_vote: vote rounds behind a batch's first (one atomic per extra round, thread 0) -- gce_get_vote_counters
     unsigned long long vote_rounds2_unaligned;   // ... of those: rounds whose first side s0 is not a multiple of 4 (vb_find_wave's groups do not start at s0)
+    unsigned int cs_fast, cs_prep, cs_deep, cs_slow;   // group sides FINISHED by k_consensus_fast / k_deep_prepare (no template) / k_vote_deep / k_consensus_slow -- gce_get_consensus_counters
     long long pre[GCE_STATS_WORDS];
     long long post[GCE_STATS_WORDS];
     long long post_slot[GCE_PRE_SLOTS][8];  // k_out_meta's six addRead counters of the emitted records, spread the same way

@@ -1187,15 +1187,18 @@ __global__ __launch_bounds__(256) void k_consensus_slow(const SlowArgs *a) {
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     const Work &w = a->w;
     const uint32_t n_slow = (uint32_t)w.si->n_slow;
+    uint32_t n_done = 0;
     for (uint32_t idx = blockIdx.x * WAVES_PER_BLOCK + wv; idx < n_slow; idx += gridDim.x * WAVES_PER_BLOCK) {
         uint32_t e = w.slow_list[idx], gi = e >> 1; bool is_left = !(e & 1);
         if (w.gen_flag[e] == 2) continue;                                       // finished by k_vote_deep (gce_deep.hpp)
+        n_done++;
         uint32_t c = w.gl_cluster[gi], g = gi - w.cl_gbase[c], cstart = w.cl_start[c];
         uint32_t begin = w.grp_begin[cstart + g], np = w.grp_n[cstart + g];
         uint32_t out = side_consensus(a->b, a->p, w, begin, np, is_left, s_tally[wv], lane, w.rp_nm + e);
         if (lane == 0) { if (is_left) w.rp_left[gi] = out; else w.rp_right[gi] = out; }
         WAVE_SYNC();
     }
+    if (lane == 0 && n_done) atomicAdd(&w.si->cs_slow, n_done);                   // (one atomic per wave: gce_get_consensus_counters)
 }
 
 // BamUtil::getRefOffset with the single-M case ("150M") answered from the first CIGAR word
@@ -1351,16 +1354,16 @@ typedef uint16_t u16_unaligned __attribute__((aligned(1)));
 // One wave per (group, side): Group::consensusMergeBam + makeConsensus for groups of <= 64 pairs with register-resident
 // pair metadata and register tallies.  Anything else is appended to slow_list for k_consensus_slow.
 // This is the kernel behind the group kernel (gce_vote.hpp): it takes the group sides that one flags (gen_flag -> gen_list).
-__device__ void consensus_fast_side(const DevBatch &b, const DevParams &p, const Work &w, uint32_t gi, bool is_left, uint8_t *s_res_wave, int lane) {
+__device__ bool consensus_fast_side(const DevBatch &b, const DevParams &p, const Work &w, uint32_t gi, bool is_left, uint8_t *s_res_wave, int lane) {
     const uint32_t begin = w.g_begin[gi], np = w.g_np[gi];
     uint32_t *rp_out = is_left ? w.rp_left : w.rp_right;
     // deep sides (> 64 pairs, or beyond the low-complexity threshold) are not this kernel's: k_vote put them on slow_list itself when it handed their
     // group on (gce_vote.hpp, P0 -- the same test), so that k_deep_prepare can start behind k_vote instead of behind a pass of this kernel over gen_list
     const bool deep_side = !(np == 1 && w.gpr[begin] == NONE32) && (np > 64 || (int)np > p.skip_low_complexity_thr);
-    if (deep_side) return;
+    if (deep_side) return false;
     if (np == 1 && w.gpr[begin] == NONE32) {                                  // group.cpp:73-77: returned untouched
         if (lane == 0) rp_out[gi] = is_left ? w.gpl[begin] : NONE32;
-        return;
+        return true;
     }
     const uint32_t *side = is_left ? w.gpl : w.gpr;
     // ---- per-lane pair metadata
@@ -1375,7 +1378,7 @@ __device__ void consensus_fast_side(const DevBatch &b, const DevParams &p, const
         if ((nc > 1 || (nc == 1 && cig_op(c0) != 0))) cigo = b.cigar_off[rd];     // anything but a single M block is walked from memory (rare)
     }
     const unsigned long long hmask = __ballot(has);
-    if (!hmask) { if (lane == 0) rp_out[gi] = NONE32; return; }              // no read on this side: "no majority" / out == NULL
+    if (!hmask) { if (lane == 0) rp_out[gi] = NONE32; return true; }              // no read on this side: "no majority" / out == NULL
     // ---- leftReadMode (group.cpp:177-194)
     bool left_mode = is_left;
     if (!is_left) {
@@ -1406,9 +1409,9 @@ __device__ void consensus_fast_side(const DevBatch &b, const DevParams &p, const
             if (better) { best = ob; bc = oc; bl = ol; }
         }
     }
-    if ((double)bc < (double)np * 0.4 && np != 1) { if (lane == 0) rp_out[gi] = NONE32; return; }        // group.cpp:264-266
+    if ((double)bc < (double)np * 0.4 && np != 1) { if (lane == 0) rp_out[gi] = NONE32; return true; }        // group.cpp:264-266
     const uint32_t out = (uint32_t)rl32((int)rd, best);
-    if (out == NONE32) { if (lane == 0) rp_out[gi] = NONE32; return; }
+    if (out == NONE32) { if (lane == 0) rp_out[gi] = NONE32; return true; }
     const int o_pos = rl32(pos, best), o_lq = rl32(lq, best), o_nc = rl32(nc, best); const uint32_t o_c0 = (uint32_t)rl32((int)c0, best);
     const uint64_t o_cigo = rl64(cigo, best), o_so = rl64(so, best), o_qo = rl64(qo, best);
     const uint32_t *ocig = b.cigar + o_cigo;
@@ -1425,7 +1428,7 @@ __device__ void consensus_fast_side(const DevBatch &b, const DevParams &p, const
     const int nbytes = (len + 1) >> 1;
     if (nbytes > 256) {                                                       // very long template: generic kernel
         if (lane == 0) w.slow_list[atomicAdd(&w.si->n_slow, 1u)] = gi * 2 + (is_left ? 0 : 1);
-        return;
+        return false;
     }
     const int o_isz = rl32(isz, best), o_tid = rl32(rtid, best);
     // NM of the template (group.cpp:528-573), needed only at the very end: fetched now, off the critical path
@@ -1653,7 +1656,7 @@ __device__ void consensus_fast_side(const DevBatch &b, const DevParams &p, const
     WAVE_SYNC();
     if (__any(odd)) {                                                         // IUPAC nibble or qual >= 128 among the voters: generic kernel
         if (lane == 0) w.slow_list[atomicAdd(&w.si->n_slow, 1u)] = gi * 2 + (is_left ? 0 : 1);
-        return;
+        return false;
     }
     minc = wave_sum(minc);
     bool restore = false;
@@ -1670,6 +1673,7 @@ __device__ void consensus_fast_side(const DevBatch &b, const DevParams &p, const
         }
     }
     if (lane == 0) rp_out[gi] = out;
+    return true;
 }
 
 // global-memory consensus, one wave per (group, side): the sides on gen_list (grid-stride, count read on the device)
@@ -1679,11 +1683,13 @@ __global__ __launch_bounds__(256, 5) void k_consensus_fast(DevBatch b, DevParams
     // the count only exists on the device: a capped grid strides over the list (a wave takes one or two entries when the list is
     // long, and leaves at once when it is short -- launching one block per POSSIBLE entry cost more than the work itself)
     const uint32_t n = (uint32_t)(w.si->hand_on >> 32);
+    uint32_t n_done = 0;
     for (uint32_t idx = blockIdx.x * WAVES_PER_BLOCK + wv; idx < n; idx += gridDim.x * WAVES_PER_BLOCK) {
         const uint32_t e = w.gen_list[idx];
-        consensus_fast_side(b, p, w, e >> 1, !(e & 1), s_res[wv], lane);
+        if (consensus_fast_side(b, p, w, e >> 1, !(e & 1), s_res[wv], lane)) n_done++;
         WAVE_SYNC();
     }
+    if (lane == 0 && n_done) atomicAdd(&w.si->cs_fast, n_done);                   // (one atomic per wave: gce_get_consensus_counters)
 }
 
 // ===================================================================================================== finish

@@ -102,6 +102,15 @@ class Engine:
         self._check(self.lib.gce_get_vote_counters(self._h, v))
         return dict(rounds2=v[0], rounds2_unaligned=v[1], handed_on_sides=v[2], groups=v[3])
 
+    CONSENSUS_KERNELS = ("vote", "fast", "deep_prepare", "vote_deep", "slow")
+
+    def consensus_counters(self):
+        """Group sides finished per consensus kernel in the last finish() (gce_get_consensus_counters): k_vote, k_consensus_fast,
+        k_deep_prepare (deep sides without a template), k_vote_deep, k_consensus_slow."""
+        v = (C.c_int64 * len(self.CONSENSUS_KERNELS))()
+        self._check(self.lib.gce_get_consensus_counters(self._h, v))
+        return dict(zip(self.CONSENSUS_KERNELS, (int(x) for x in v)))
+
     def index_counters(self):
         """The record index of the last gce_raw_finish (gce_get_index_counters)."""
         return index_counters(self._h)

@@ -315,6 +315,10 @@ int gce_get_timing(gce_engine *e, gce_timing *out);
  * fit one round's tallies), out[1] of those the rounds that start at a side index that is not a multiple of 4, out[2] group sides k_vote handed on
  * to the per-side kernels, out[3] groups of the stream.  For tests and diagnostics. */
 int gce_get_vote_counters(gce_engine *e, int64_t out[4]);
+/* Group sides finished per consensus kernel in the last gce_process (ADDED under v3; for tests and diagnostics): out[0] k_vote (both sides of
+ * every group it did not hand on), out[1] k_consensus_fast, out[2] k_deep_prepare (deep sides without a template), out[3] k_vote_deep,
+ * out[4] k_consensus_slow.  After a gce_process without a device error the five add up to 2 x groups. */
+int gce_get_consensus_counters(gce_engine *e, int64_t out[5]);
 /* The GPU record index's counters (ADDED under v3; for tests and diagnostics): out[0] 16 KB segments, out[1] of those flagged by the first
  * check (a guessed record start off the chain), out[2] parallel repair rounds, out[3] serial repairs (0 or 1 per index).  e: its last
  * gce_raw_finish; e == NULL: summed over every window of the last pass runner of the process (gce_run_bam_passes, key pass and passes). */

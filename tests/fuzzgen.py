@@ -1,6 +1,7 @@
 """Adversarial small-stream generator for parity tests (engine vs oracle) — exercises the quirk register of
 SURVEY.md section 8 (Q1..Q14): flush cadence, unmapped / secondary / mate-unmapped reads, negative scores, absent-bin
-winners, NM revert, FR wrap, UMI parsing, singleton pairs, reference edge cases, odd CIGARs, trimmed duplicates."""
+winners, NM revert, FR wrap, UMI parsing, singleton pairs, reference edge cases, odd CIGARs, trimmed duplicates.
+Read length is NOT covered here (lengths are drawn from 20..110): tests/test_read_lengths.py holds the kernels' length edges."""
 import random
 
 import numpy as np

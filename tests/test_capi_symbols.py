@@ -38,6 +38,18 @@ def test_index_counters_symbol(built):
     assert c["flagged"] <= c["segments"] and c["serial"] <= c["rounds"]
 
 
+def test_consensus_counters_symbol(built):
+    """gce_get_consensus_counters (added under ABI v3) is exported and refuses a NULL engine or output (no GPU call: this runs without a device)."""
+    from gencore_amd import capi
+    from gencore_amd.engine import Engine
+    lib = capi.load_library()
+    assert "gce_get_consensus_counters" in capi.EXPORTED_SYMBOLS and hasattr(lib, "gce_get_consensus_counters")
+    assert lib.gce_get_consensus_counters(None, None) == -1
+    v = (C.c_int64 * 5)()
+    assert lib.gce_get_consensus_counters(None, v) == -1
+    assert len(Engine.CONSENSUS_KERNELS) == 5
+
+
 def test_pairing_tier_ids_match_header():
     """gce_get_pairing_tiers' tier ids (GCE_PAIR_TIER_*) are the names Engine.pairing_tiers() reports, in order."""
     from gencore_amd.engine import Engine

@@ -83,7 +83,8 @@ def load_fasta(path, threads=0):
 
 
 def run_bam(in_path, out_path, params, fasta=None, threads=0, chunk_reads=1 << 21, level=6):
-    """gce_run_bam: returns the GceBamRun record (stage times, Stats blocks)."""
+    """gce_run_bam: returns the GceBamRun record (stage times, Stats blocks).  level: 0..9 = zlib on the host's threads, -1 = the host's fixed-Huffman encoder, -2 = the GPU deflates the record stream with fixed codes,
+    -3 = the GPU deflates it with, per block, the smallest of dynamic codes, fixed codes and stored (never larger than -2)."""
     lib = capi.load_library()
     run = GceBamRun()
     err = (C.c_char * 256)()
@@ -95,7 +96,8 @@ def run_bam(in_path, out_path, params, fasta=None, threads=0, chunk_reads=1 << 2
 
 
 def run_bam_sharded(in_path, out_path, params, devices, fasta=None, plan_mode=0, threads=0, level=6):
-    """gce_run_bam_sharded: one engine per entry of `devices` (HIP ordinals, may repeat), planned on the GPU, tables merged."""
+    """gce_run_bam_sharded: one engine per entry of `devices` (HIP ordinals, may repeat), planned on the GPU, tables merged.  level as run_bam
+    (-2 / -3: the merged output is deflated by the GPU)."""
     lib = capi.load_library()
     run = GceBamRun()
     err = (C.c_char * 256)()
@@ -109,7 +111,7 @@ def run_bam_sharded(in_path, out_path, params, devices, fasta=None, plan_mode=0,
 
 def run_bam_depth(in_path, out_path, params, devices, coverage_step, bed=None, fasta=None, plan_mode=0, threads=0, level=6):
     """gce_run_bam_depth: gce_run_bam (one device) / gce_run_bam_sharded (several) with the depth statistics of the reference's report
-    (Options::coverageStep, Options::bedFile): returns (run, dict(bin_off, pre_depth, post_depth, regions, pre_bed, post_bed, pre, post, payload_bytes))."""
+    (Options::coverageStep, Options::bedFile; level as run_bam, -3 included): returns (run, dict(bin_off, pre_depth, post_depth, regions, pre_bed, post_bed, pre, post, payload_bytes))."""
     from .capi import GceDepthRun
     lib = capi.load_library()
     run, dr = GceBamRun(), GceDepthRun()
@@ -130,7 +132,8 @@ def run_bam_depth(in_path, out_path, params, devices, coverage_step, bed=None, f
 
 def run_bam_passes(in_path, out_path, params, device=0, coverage_step=1000000, bed=None, fasta=None, threads=0, level=6, device_budget_bytes=0, min_passes=0, window_bytes=0):
     """gce_run_bam_passes: run_bam_depth on one device in key-range passes, device memory bounded by the largest pass (device_budget_bytes:
-    0 = auto; min_passes forces at least that many; window_bytes: compressed bytes per window, 0 = 64 MB).  Returns (run, depth dict as
+    0 = auto; min_passes forces at least that many; window_bytes: compressed bytes per window, 0 = 64 MB; level as run_bam, -2 / -3: each output piece is
+    deflated by the GPU).  Returns (run, depth dict as
     run_bam_depth, pass dict(n_passes, single_pass, reads_per_pass, held_max, peak_device_bytes, budget_bytes, fixed_bytes, pass_room, total_weight,
     key_pass_s, pass_s)))."""
     from .capi import GceDepthRun, GcePassRun
@@ -166,6 +169,22 @@ def index_bam(bam, bai=None, device=0, threads=0, window_bytes=0):
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceBaiRun._fields_ if n != "pad"}
+
+
+def bgzf_deflate(data, block=0xff00, codes=1, device=0):
+    """gce_bgzf_deflate_codes: `data` (bytes-like) as BGZF members of `block` input bytes each (1..65 280), deflated on the GPU.  codes: 0 = fixed
+    Huffman codes (level -2), 1 = per block the smallest of dynamic codes, fixed codes and stored (level -3), 2 = dynamic codes wherever they fit
+    (tests).  Returns the members back to back as bytes; raises GceError."""
+    lib = capi.load_library()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    n = len(buf)
+    cap = n + n // 8 + 64 * (n // max(int(block), 1) + 2)
+    out = np.empty(max(cap, 1), np.uint8)
+    got = C.c_size_t(0)
+    rc = lib.gce_bgzf_deflate_codes(int(device), buf.ctypes.data if n else None, n, int(block), int(codes), out.ctypes.data, cap, C.byref(got))
+    if rc != 0:
+        raise GceError(rc, "gce_bgzf_deflate_codes")
+    return out[:got.value].tobytes()
 
 
 def device_bytes(reset_peak=False):

@@ -76,7 +76,7 @@ def build_parser():
     a("--index", action="store_true", help="[gencore_amd] after the output and the report are written, index the BAM output on the GPU into "
                                             "<output>.bai (BAI, SAMv1 5.2), on the first of --devices. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
-                                           "-2 (fixed Huffman on the GPU). Default 6.")
+                                           "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). Default 6.")
     return p
 
 
@@ -127,8 +127,8 @@ def validate(o):
         devices = []
     if not devices or min(devices) < 0:
         err("devices should be a comma separated list of HIP device ordinals, got '%s'" % o.devices)
-    if not (-2 <= o.level <= 9):
-        err("level should be -2, -1 or 0..9")
+    if not (-3 <= o.level <= 9):
+        err("level should be -3, -2, -1 or 0..9")
     o.device_memory_bytes = 0                       # 0: auto
     if o.device_memory != "auto":
         try:

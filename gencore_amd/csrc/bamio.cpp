@@ -1289,6 +1289,7 @@ int gce_raw_build_output(gce_engine *e, uint64_t *body_bytes, int64_t *n_out);
 int gce_raw_read_output_async(gce_engine *e, uint64_t offset, void *host, size_t bytes, int32_t *ticket);
 int gce_host_alloc(size_t bytes, void **out);
 int gce_raw_deflate_output(gce_engine *e, uint64_t *comp_bytes);
+int gce_raw_deflate_output_codes(gce_engine *e, int32_t codes, uint64_t *comp_bytes);
 int gce_raw_read_deflated_async(gce_engine *e, uint64_t offset, void *host, size_t bytes, int32_t *ticket);
 int gce_raw_attach_mirror(gce_engine *e, gce_engine *mirror);
 int gce_raw_select_shard(gce_engine *e, int32_t world, int32_t rank, int32_t plan_mode);
@@ -1752,15 +1753,16 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
     Pinned obuf[3]; int32_t otk[3] = {-1, -1, -1};
     Raw<uint8_t> zbuf; zbuf.resize((size_t)256 * 0x10000 + 64);
     if (!zbuf.ok()) return done(GCE_ERR_OOM, "out of host memory");
-    if (level == -2) {
-        // level -2: the record stream is deflated BY THE GPU (gce_deflate.hpp: fixed Huffman codes, one lane per BGZF block) -- the host compresses
-        // the header's few blocks, then only copies the file image out of HBM piece by piece and writes it
+    if (level == -2 || level == -3) {
+        // level -2 / -3: the record stream is deflated BY THE GPU (gce_deflate.hpp: one lane per BGZF block; -2 fixed Huffman codes, -3 the smallest of
+        // dynamic codes, fixed codes and stored per block) -- the host compresses the header's few blocks, then only copies the file image out of HBM
+        // piece by piece and writes it
         for (uint64_t o = 0; o < hdr.size(); o += BS) {
             const uint32_t zs = (uint32_t)deflate_block(hdr.data() + o, (uint32_t)std::min<uint64_t>(BS, hdr.size() - o), 1, zbuf.data());
             if (zs == 0 || fwrite(zbuf.data(), 1, zs, fo) != zs) return done(GCE_ERR_INVALID, "cannot write the output BAM");
         }
         uint64_t cb = 0;
-        if (body && (rc = gce_raw_deflate_output(e, &cb)) != GCE_OK) return done(rc, gce_last_error(e));
+        if (body && (rc = gce_raw_deflate_output_codes(e, level == -3 ? 1 : 0, &cb)) != GCE_OK) return done(rc, gce_last_error(e));
         const uint64_t PC = (uint64_t)16 << 20; const int64_t np2 = (int64_t)((cb + PC - 1) / PC);
         auto fetch2 = [&](int64_t pc) -> int { const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(cb, a2 + PC); if (!obuf[pc & 1].ensure((size_t)(z2 - a2) + 64)) return GCE_ERR_OOM; return gce_raw_read_deflated_async(e, a2, obuf[pc & 1].p, (size_t)(z2 - a2), &otk[pc & 1]); };
         if (np2 > 0 && (rc = fetch2(0)) != GCE_OK) return done(rc, "output piece");
@@ -2095,7 +2097,7 @@ inline bool pass_less(const PassKey &a, const PassKey &b) {
     return a.gidx < b.gidx;
 }
 // the output file of the pass runner: the record stream arrives in pieces, in order; BGZF blocks of 0xff00 bytes (host threads, or the GPU
-// encoder for level -2 as gce_raw_deflate_output), or SAM text for a name that ends in "sam"
+// encoder for levels -2 and -3 as gce_raw_deflate_output_codes), or SAM text for a name that ends in "sam"
 struct PassWriter {
     FILE *fo = nullptr; int level = -1, T = 1; int32_t device = 0; bool sam = false; const std::vector<std::string> *names = nullptr;
     std::vector<uint8_t> buf; Raw<uint8_t> zbuf; std::vector<uint8_t> gz; std::string line; bool ok = true;
@@ -2113,10 +2115,10 @@ struct PassWriter {
         if (sam) {
             size_t o = 0;
             while (o < n) { const uint32_t bs = rd32(buf.data() + o); line.clear(); if (!samtext::bam_to_line(buf.data() + o, *names, line) || fwrite(line.data(), 1, line.size(), fo) != line.size()) return false; o += 4ull + bs; }
-        } else if (level == -2) {
+        } else if (level == -2 || level == -3) {
             size_t zb = 0;
             if (gz.size() < n + n / 8 + 64 * (n / BS + 1) + 64) gz.resize(n + n / 8 + 64 * (n / BS + 1) + 64);
-            if (gce_bgzf_deflate(device, buf.data(), n, (uint32_t)BS, gz.data(), gz.size(), &zb) != GCE_OK || fwrite(gz.data(), 1, zb, fo) != zb) return false;
+            if (gce_bgzf_deflate_codes(device, buf.data(), n, (uint32_t)BS, level == -3 ? 1 : 0, gz.data(), gz.size(), &zb) != GCE_OK || fwrite(gz.data(), 1, zb, fo) != zb) return false;
         } else if (!host_blocks(buf.data(), n, level)) return false;
         buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)n);
         return true;
@@ -2128,7 +2130,7 @@ struct PassWriter {
         if (sam) { const std::string ht = samtext::header_text_for_sam(text, nm, lens); return fwrite(ht.data(), 1, ht.size(), fo) == ht.size(); }
         zbuf.resize((size_t)256 * 0x10000 + 64);
         if (!zbuf.ok()) return false;
-        if (level == -2) return host_blocks(hdr.data(), hdr.size(), 1);          // (as gce_run_bam: the header's blocks by the host)
+        if (level == -2 || level == -3) return host_blocks(hdr.data(), hdr.size(), 1);          // (as gce_run_bam: the header's blocks by the host)
         buf.assign(hdr.begin(), hdr.end());
         return true;
     }
@@ -2303,7 +2305,7 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     int32_t P = 1; uint64_t total_w = 0, room = 0, fixed = 0;
     // beside the weights: the engine's working set that does not scale with a pass's reads (measured: a pass of 43 MB of weight on cfg3 peaked
     // 82 MB above the fixed part), hipCUB temporaries, the GPU encoder's 16 MB pieces
-    const uint64_t reserve = ((uint64_t)96 << 20) + (level == -2 ? ((uint64_t)64 << 20) : 0);
+    const uint64_t reserve = ((uint64_t)96 << 20) + (level == -2 || level == -3 ? ((uint64_t)64 << 20) : 0);
     if (rc == GCE_OK && (rc = gce_passes_plan(p, std::max(min_passes, 1), budget, reserve, &P, &total_w, &room, &fixed)) != GCE_OK) kmsg = gce_passes_error(p);
     if (rc != GCE_OK && single_ok) {                                                 // nothing written yet: the file goes the way it goes today
         gce_passes_destroy(p); p = nullptr; gce_destroy(e); e = nullptr; close(fd);

@@ -495,10 +495,18 @@ int gce_bgzf_inflate(int32_t device, const void *comp, size_t comp_bytes, int32_
     return rc;
 }
 
+// either encoder of gce_deflate.hpp over `nb` blocks on stream s (codes: see gce_bgzf_deflate_codes)
+static void def_launch(int codes, uint32_t nb, hipStream_t s, const uint8_t *in, uint64_t total, uint32_t blk, uint8_t *slots, uint32_t slot, uint32_t *sizes) {
+    if (codes == 0) hipLaunchKernelGGL(k_bgzf_deflate, dim3((nb + DEF_T - 1) / DEF_T), dim3(DEF_T), 0, s, in, total, blk, nb, slots, slot, sizes);
+    else hipLaunchKernelGGL(k_bgzf_deflate_dyn, dim3((nb + DEF_T - 1) / DEF_T), dim3(DEF_T), 0, s, in, total, blk, nb, slots, slot, sizes, codes);
+}
+
 // The encoder of gce_raw_deflate_output on the caller's buffer (tests, tools): `n` bytes -> BGZF blocks of `block_bytes` input bytes each (<= 65 280),
-// back to back in out[0 .. *out_bytes); out_cap >= n + n / 8 + 64 x blocks is always enough.  Mirror of gce_bgzf_inflate.
-int gce_bgzf_deflate(int32_t device, const void *in, size_t n, uint32_t block_bytes, void *out, size_t out_cap, size_t *out_bytes) {
-    if ((n && !in) || !out_bytes || block_bytes < 1 || block_bytes > 0xff00u || (n && !out)) return GCE_ERR_INVALID;
+// back to back in out[0 .. *out_bytes); out_cap >= n + n / 8 + 64 x blocks is always enough.  Mirror of gce_bgzf_inflate.  codes: 0 = fixed Huffman
+// codes (k_bgzf_deflate), 1 = per block the smallest of dynamic codes, fixed codes and stored (k_bgzf_deflate_dyn), 2 = dynamic codes wherever they
+// fit the block's slot (tests of the degenerate trees).
+int gce_bgzf_deflate_codes(int32_t device, const void *in, size_t n, uint32_t block_bytes, int32_t codes, void *out, size_t out_cap, size_t *out_bytes) {
+    if ((n && !in) || !out_bytes || block_bytes < 1 || block_bytes > 0xff00u || (n && !out) || codes < 0 || codes > 2) return GCE_ERR_INVALID;
     *out_bytes = 0;
     if (hipSetDevice(device) != hipSuccess) return GCE_ERR_NO_DEVICE;
     if (!n) return GCE_OK;
@@ -511,7 +519,7 @@ int gce_bgzf_deflate(int32_t device, const void *in, size_t n, uint32_t block_by
     if (zi.ensure(n + 64) != hipSuccess || zs.ensure((size_t)nb * slot + 64) != hipSuccess || zz.ensure(((size_t)nb + 1) * 4) != hipSuccess || zf.ensure(((size_t)nb + 1) * 8) != hipSuccess) rc = GCE_ERR_OOM;
     if (rc == GCE_OK) {
         chk(hipMemcpy(zi.p, in, n, hipMemcpyHostToDevice)); chk(hipMemset((char *)zi.p + n, 0, 64));
-        hipLaunchKernelGGL(k_bgzf_deflate, dim3((nb + DEF_T - 1) / DEF_T), dim3(DEF_T), 0, 0, (const uint8_t *)zi.p, (uint64_t)n, block_bytes, nb, zs.as<uint8_t>(), slot, zz.as<uint32_t>());
+        def_launch(codes, nb, 0, (const uint8_t *)zi.p, (uint64_t)n, block_bytes, zs.as<uint8_t>(), slot, zz.as<uint32_t>());
         chk(hipMemset((char *)zz.p + (size_t)nb * 4, 0, 4));
         chk(dev_exclusive_sum(zz.as<uint32_t>(), (uint64_t)nb, zf.as<uint64_t>(), zt, 0));
         uint64_t csz = 0;
@@ -527,6 +535,9 @@ int gce_bgzf_deflate(int32_t device, const void *in, size_t n, uint32_t block_by
     }
     zi.release(); zs.release(); zz.release(); zo.release(); zf.release(); zt.release();
     return rc;
+}
+int gce_bgzf_deflate(int32_t device, const void *in, size_t n, uint32_t block_bytes, void *out, size_t out_cap, size_t *out_bytes) {
+    return gce_bgzf_deflate_codes(device, in, n, block_bytes, 0, out, out_cap, out_bytes);
 }
 
 // The whole stream is in HBM: index the records behind `records_begin` (the end of the BAM header), build the batch.  Afterwards the engine is
@@ -885,9 +896,10 @@ int gce_raw_merge_outputs(gce_engine **engs, int32_t n_engs, uint64_t *body_byte
 // After gce_raw_build_output (or gce_raw_merge_outputs): the record stream compressed into BGZF blocks by the GPU (gce_deflate.hpp: greedy LZ77,
 // fixed Huffman codes, one lane per block) -- replaces bgzf_write's deflate under sam_write1 (src/gencore.cpp:104).  *comp_bytes = size of the
 // file image of the records (BGZF blocks back to back; the caller writes the BAM header's blocks in front and the EOF marker behind);
-// gce_raw_read_deflated_async copies a piece of it to the host.
-int gce_raw_deflate_output(gce_engine *e, uint64_t *comp_bytes) {
-    if (!e || !e->raw_mode || !comp_bytes) return GCE_ERR_INVALID;
+// gce_raw_read_deflated_async copies a piece of it to the host.  codes: 0 = fixed codes, 1 = the smallest of dynamic / fixed / stored per block
+// (2, the forcing switch of gce_bgzf_deflate_codes for tests, is refused here).
+int gce_raw_deflate_output_codes(gce_engine *e, int32_t codes, uint64_t *comp_bytes) {
+    if (!e || !e->raw_mode || !comp_bytes || codes < 0 || codes > 1) return GCE_ERR_INVALID;
     (void)hipSetDevice(e->prm.device);
     hipStream_t s = e->stream;
     const uint64_t total = e->raw_body_bytes;
@@ -900,7 +912,7 @@ int gce_raw_deflate_output(gce_engine *e, uint64_t *comp_bytes) {
     if (nb64 >= 0x7FFFFFF0ull) return fail(e, GCE_ERR_INVALID, "output stream too large for one deflate pass");
     const uint32_t nb = (uint32_t)nb64, slot = (uint32_t)(blk + blk / 8 + 64);
     HIPCHK(e->zo_slots.ensure((size_t)nb * slot + 64)); HIPCHK(e->zo_sizes.ensure(((size_t)nb + 1) * 4)); HIPCHK(e->zo_off.ensure(((size_t)nb + 1) * 8));
-    hipLaunchKernelGGL(k_bgzf_deflate, dim3((nb + DEF_T - 1) / DEF_T), dim3(DEF_T), 0, s, (const uint8_t *)e->rw_body.p, total, (uint32_t)blk, nb, e->zo_slots.as<uint8_t>(), slot, e->zo_sizes.as<uint32_t>());
+    def_launch(codes, nb, s, (const uint8_t *)e->rw_body.p, total, (uint32_t)blk, e->zo_slots.as<uint8_t>(), slot, e->zo_sizes.as<uint32_t>());
     HIPCHK(hipMemsetAsync((char *)e->zo_sizes.p + (size_t)nb * 4, 0, 4, s));
     HIPCHK(dev_exclusive_sum(e->zo_sizes.as<uint32_t>(), (uint64_t)nb, e->zo_off.as<uint64_t>(), e->rw_tmp, s));
     uint64_t csz = 0;
@@ -913,6 +925,7 @@ int gce_raw_deflate_output(gce_engine *e, uint64_t *comp_bytes) {
     e->zo_bytes = csz; *comp_bytes = csz;
     return GCE_OK;
 }
+int gce_raw_deflate_output(gce_engine *e, uint64_t *comp_bytes) { return gce_raw_deflate_output_codes(e, 0, comp_bytes); }
 int gce_raw_read_deflated_async(gce_engine *e, uint64_t offset, void *host, size_t bytes, int32_t *ticket) {
     if (!e || !e->raw_mode || offset + bytes > e->zo_bytes || (!host && bytes)) return GCE_ERR_INVALID;
     (void)hipSetDevice(e->prm.device);

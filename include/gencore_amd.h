@@ -488,6 +488,14 @@ int gce_raw_read_output_async(gce_engine *e, uint64_t offset, void *host, size_t
 int gce_raw_deflate_output(gce_engine *e, uint64_t *comp_bytes);
 int gce_raw_read_deflated_async(gce_engine *e, uint64_t offset, void *host, size_t bytes, int32_t *ticket);
 int gce_bgzf_deflate(int32_t device, const void *in, size_t n, uint32_t block_bytes, void *out, size_t out_cap, size_t *out_bytes);
+/* The same two with the choice of entropy coder -- replaces the Huffman stage of bgzf_write's deflate under sam_write1 (src/gencore.cpp:104 via
+ * htslib).  codes 0: fixed codes (the two functions above are this case).  codes 1: the same tokens, and per block the SMALLEST of dynamic Huffman
+ * codes (length-limited to 12 bits, header included), fixed codes and a stored block, each priced exactly from the block's symbol histogram before
+ * a byte is written: never larger than codes 0, block for block (k_bgzf_deflate_dyn; what gce_run_bam does for `level == -3`).  codes 2: dynamic
+ * codes wherever they fit the block's slot and a BGZF member (gce_bgzf_deflate_codes only: tests of the degenerate trees; the engine call refuses it).
+ * out_cap as for gce_bgzf_deflate.  (Additions under ABI v3.) */
+int gce_raw_deflate_output_codes(gce_engine *e, int32_t codes, uint64_t *comp_bytes);
+int gce_bgzf_deflate_codes(int32_t device, const void *in, size_t n, uint32_t block_bytes, int32_t codes, void *out, size_t out_cap, size_t *out_bytes);
 int gce_host_alloc(size_t bytes, void **out);
 void gce_host_free(void *p);
 

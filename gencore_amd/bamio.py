@@ -171,6 +171,21 @@ def index_bam(bam, bai=None, device=0, threads=0, window_bytes=0):
     return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceBaiRun._fields_ if n != "pad"}
 
 
+def sort_bam(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_sort: an unsorted BAM file into coordinate order on the GPU (what `samtools sort` does in front of the reference), written to
+    `out`.  level as run_bam; window_bytes: compressed bytes per window, 0 = 64 MB; device_budget_bytes: 0 = no limit beyond the device (the
+    sort is in-core).  Returns dict(n_records, n_no_coor, n_descents, inflated_bytes, out_bytes, peak_device_bytes, n_ref, read_s,
+    inflate_index_s, sort_s, gather_s, write_s, total_s); raises GceError (and leaves no output) on failure."""
+    from .capi import GceSortRun
+    lib = capi.load_library()
+    r = GceSortRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_sort(str(bam).encode(), str(out).encode(), int(device), int(threads), int(level), int(window_bytes), int(device_budget_bytes), C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceSortRun._fields_ if n != "pad"}
+
+
 def bgzf_deflate(data, block=0xff00, codes=1, device=0):
     """gce_bgzf_deflate_codes: `data` (bytes-like) as BGZF members of `block` input bytes each (1..65 280), deflated on the GPU.  codes: 0 = fixed
     Huffman codes (level -2), 1 = per block the smallest of dynamic codes, fixed codes and stored (level -3), 2 = dynamic codes wherever they fit

@@ -14,6 +14,8 @@ from . import __version__
 EPILOG = """\
 Flags marked [gencore_amd] are not the reference's; every other flag, default and validation message is gencore 0.17.2's.
 --index (not the reference's) writes <output>.bai, the BAI index of the BAM output, built on the GPU.
+--sort (not the reference's) takes a BAM in any order, as an aligner writes it: the GPU sorts it by coordinate into a temporary BAM first
+(what `samtools sort` does in front of the reference), and the run reads that file.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -75,6 +77,8 @@ def build_parser():
     a("--threads", type=int, default=0, help="[gencore_amd] host threads for the file codecs; 0 = all cores. Default 0.")
     a("--index", action="store_true", help="[gencore_amd] after the output and the report are written, index the BAM output on the GPU into "
                                             "<output>.bai (BAI, SAMv1 5.2), on the first of --devices. Off by default.")
+    a("--sort", action="store_true", help="[gencore_amd] the input BAM is not coordinate-sorted: sort it on the GPU first (on the first of --devices, into a "
+                                           "temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). Default 6.")
     return p
@@ -96,7 +100,13 @@ def validate(o):
         err("You cannot enable both duplex_only and no_duplex")
     if not o.input:
         err("input should be specified by --in1")
+    if o.sort and o.input == "-":
+        err("--sort needs an input file, not STDIN")
     check_file_valid(o.input)
+    if o.sort:
+        with open(o.input, "rb") as f:
+            if f.read(2) != b"\x1f\x8b":
+                err("--sort needs BAM input, not SAM text")
     if o.ref.endswith(".gz"):
         raise UsageError("reference fasta file should not be compressed.\nplease unzip %s and try again." % o.ref)
     checks = [
@@ -167,10 +177,17 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes
+    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam
     from .capi import GceError
     from .report import read_header, summary, write_json
+    sorted_tmp = None
     try:
+        if o.sort:                                                          # the runners below read the sorted temporary file, unchanged
+            import tempfile
+            fd, sorted_tmp = tempfile.mkstemp(suffix=".bam", prefix="gencore_sort_", dir=None if o.output == "-" else (os.path.dirname(os.path.abspath(o.output))))
+            os.close(fd)
+            sort_bam(o.input, sorted_tmp, device=devices[0], threads=o.threads, level=-2)
+            o.input = sorted_tmp
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
@@ -189,6 +206,9 @@ def main(argv=None):
     except (GceError, OSError) as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 255
+    finally:
+        if sorted_tmp is not None and os.path.exists(sorted_tmp):
+            os.remove(sorted_tmp)
     t2 = int(time.time())
     sys.stderr.write("\n%s\ngencore_amd v%s, time used: %d seconds\n" % (command, __version__, t2 - t1))
     return 0

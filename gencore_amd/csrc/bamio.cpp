@@ -2520,3 +2520,172 @@ int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, in
 }
 
 }  // extern "C"
+
+
+// ---- an unsorted BAM into coordinate order (gce_sort.hpp)
+extern "C" {
+struct gce_sort;
+int gce_sort_create(int32_t device, size_t device_budget_bytes, gce_sort **out);
+void gce_sort_destroy(gce_sort *b);
+const char *gce_sort_error(gce_sort *b);
+int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                    int32_t n_ref, int32_t last, uint64_t est_bytes);
+int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int64_t counts[3], int64_t *bad_rec, uint64_t *out_bytes, double times[2]);
+int gce_sort_read(gce_sort *b, uint64_t offset, size_t bytes, int32_t codes, void *host, size_t host_cap, size_t *got);
+}  // extern "C" (declarations)
+extern "C++" {
+namespace {
+// rule H: the header text (up to its first NUL) with SO:coordinate in its @HD line
+std::string sort_header_text(const uint8_t *t, size_t l_text) {
+    std::string text((const char *)t, strnlen((const char *)t, l_text));
+    if (text.compare(0, 3, "@HD") != 0) return "@HD\tVN:1.6\tSO:coordinate\n" + text;
+    size_t eol = text.find('\n'); if (eol == std::string::npos) eol = text.size();
+    const size_t so = text.find("\tSO:");
+    if (so == std::string::npos || so >= eol) { text.insert(eol, "\tSO:coordinate"); return text; }
+    size_t ve = text.find('\t', so + 4); if (ve == std::string::npos || ve > eol) ve = eol;
+    text.replace(so + 4, ve - (so + 4), "coordinate");
+    return text;
+}
+}  // namespace
+}  // extern "C++"
+extern "C" {
+
+int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, gce_sort_run *out, char err[256]) {
+    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
+    seterr("");
+    if (!in_path || !out_path || !out) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    memset(out, 0, sizeof *out);
+    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    const double t_start = now_s();
+    const int fd = open(in_path, O_RDONLY);
+    if (fd < 0) { seterr("cannot open the input BAM"); return GCE_ERR_INVALID; }
+    struct stat st;
+    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the input BAM"); return GCE_ERR_INVALID; }
+    const uint64_t fsz = (uint64_t)st.st_size;
+    const std::string tmp = std::string(out_path) + ".tmp" + std::to_string((long long)getpid());
+    gce_sort *b = nullptr; PassWriter pw; bool tmp_made = false;
+    auto done = [&](int code, const char *m) {
+        const std::string keep(m ? m : "");                                          // (m may point into b)
+        if (b) gce_sort_destroy(b);
+        if (pw.fo) { fclose(pw.fo); pw.fo = nullptr; }
+        if (code != GCE_OK && tmp_made) unlink(tmp.c_str());
+        close(fd);
+        seterr(keep.c_str());
+        return code;
+    };
+    {   // the output may not be the input (by name or by file)
+        struct stat so;
+        bool same = stat(out_path, &so) == 0 && so.st_dev == st.st_dev && so.st_ino == st.st_ino;
+        char *ri = realpath(in_path, nullptr), *ro = realpath(out_path, nullptr);
+        if (ri && ro && strcmp(ri, ro) == 0) same = true;
+        free(ri); free(ro);
+        if (same) return done(GCE_ERR_INVALID, "the output path is the input file: gce_bam_sort does not sort in place");
+    }
+    { uint8_t m2[4] = {0, 0, 0, 0}; const bool got = fsz >= 4 && pread(fd, m2, 4, 0) == 4;
+      if (fsz > 0 && !(got && m2[0] == 0x1f && m2[1] == 0x8b)) return done(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
+      if (fsz < 18 || m2[2] != 8 || !(m2[3] & 4)) return done(GCE_ERR_INVALID, "not a BGZF file"); }
+    const int T = threads > 0 ? threads : default_threads();
+    // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
+    uint64_t hdr_end = 0; int32_t n_ref = 0; std::vector<uint8_t> hdr;
+    {
+        PassReader rh; rh.fd = fd; rh.fsz = fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
+        for (;;) {
+            const int g = rh.inflate_next();
+            if (g < 0) return done(GCE_ERR_INVALID, rh.msg.c_str());
+            const uint8_t *u = rh.win.p; const uint64_t n = rh.n;
+            if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return done(GCE_ERR_INVALID, "not a BAM stream");
+            if (n >= 12) {
+                uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
+                if (q + l_text + 4 <= n) {
+                    q += l_text;
+                    const uint32_t nr = rd32(u + q); q += 4;
+                    bool ok = nr < 0x7FFFFFFFu;
+                    for (uint32_t r = 0; r < nr && ok; r++) {
+                        if (q + 4 > n) { ok = false; break; }
+                        const uint32_t ln = rd32(u + q); q += 4;
+                        if (q + (uint64_t)ln + 4 > n) { ok = false; break; }
+                        q += ln + 4;
+                    }
+                    if (ok) {                                                        // rule H: the text rewritten, the contig table as it is
+                        hdr_end = q; n_ref = (int32_t)nr;
+                        const std::string text = sort_header_text(u + 8, l_text);
+                        const uint32_t lt = (uint32_t)text.size();
+                        hdr.assign(u, u + 4); hdr.insert(hdr.end(), (const uint8_t *)&lt, (const uint8_t *)&lt + 4);
+                        hdr.insert(hdr.end(), text.begin(), text.end()); hdr.insert(hdr.end(), u + 8 + l_text, u + q);
+                        break;
+                    }
+                }
+            }
+            if (g == 0) return done(GCE_ERR_INVALID, "truncated BAM header");
+        }
+    }
+    out->n_ref = n_ref;
+    (void)gce_device_bytes(nullptr, nullptr, 1);
+    int rc = gce_sort_create(device, device_budget_bytes, &b);
+    if (rc != GCE_OK) return done(rc, "no HIP device");
+    // ---- the file from its first byte, window by window: the host reads and finds the members, the GPU inflates, indexes and keys them
+    PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? (size_t)window_bytes : ((size_t)64 << 20);
+    uint64_t skip = hdr_end, comp_seen = 0, infl_seen = 0;
+    for (;;) {
+        double t0 = now_s();
+        const int g = rd.members_next();
+        if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str());
+        if (g == 0) break;
+        rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
+        for (const Block &k : rd.blocks) { rd.z_coff.push_back(k.coff); rd.z_csize.push_back(k.csize); rd.z_usize.push_back(k.usize); u_all += k.usize; }
+        const uint64_t sk = std::min<uint64_t>(skip, u_all);
+        comp_seen += rd.used; infl_seen += u_all;
+        // the whole file's inflated bytes, from the ISIZE totals so far and the file size
+        const uint64_t est = comp_seen ? (uint64_t)((double)infl_seen * ((double)fsz / (double)comp_seen)) : 0;
+        out->read_s += now_s() - t0; t0 = now_s();
+        rc = gce_sort_window(b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0, est);
+        out->inflate_index_s += now_s() - t0;
+        if (rc != GCE_OK) return done(rc, gce_sort_error(b));
+        skip -= sk;
+        if (rd.last_piece()) break;
+    }
+    if (rd.have != rd.used) return done(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
+    if (skip) return done(GCE_ERR_INVALID, "truncated BAM header");
+    // ---- sort, scan, gather.  The output comes back in pieces that are multiples of 0xff00: 8192 members when the GPU deflates them (one
+    // lane per member), 1024 when the host threads do
+    const int32_t codes = level == -3 ? 1 : level == -2 ? 0 : -1;
+    const uint64_t BS = PassWriter::BS, piece = BS * (codes >= 0 ? 8192 : 1024);
+    int64_t counts[3] = {0, 0, 0}, bad = -1; uint64_t total = 0; double times[2] = {0, 0};
+    if ((rc = gce_sort_finish(b, n_ref, codes, piece, counts, &bad, &total, times)) != GCE_OK) return done(rc, gce_sort_error(b));
+    if (bad >= 0) {
+        char m[256]; snprintf(m, sizeof m, "BAM record %lld (counting from 0) names a contig the header does not have", (long long)bad);
+        return done(GCE_ERR_INVALID, m);
+    }
+    out->sort_s = times[0]; out->gather_s = times[1];
+    out->n_records = counts[0]; out->n_no_coor = counts[1]; out->n_descents = counts[2]; out->inflated_bytes = (int64_t)total;
+    // ---- rule F: the header in members of its own, the record stream in members of 0xff00 bytes, the EOF marker
+    double t0 = now_s();
+    Pinned hb;
+    const size_t pmax = (size_t)std::min<uint64_t>(piece, total), hcap = codes >= 0 ? pmax + pmax / 8 + 64 * (pmax / BS + 2) : pmax;
+    if (total && !hb.ensure(hcap)) return done(GCE_ERR_OOM, "out of pinned host memory");
+    pw.level = level; pw.T = T; pw.device = device;
+    pw.zbuf.resize((size_t)256 * 0x10000 + 64);
+    if (!pw.zbuf.ok()) return done(GCE_ERR_OOM, "out of host memory");
+    pw.fo = fopen(tmp.c_str(), "wb");
+    if (!pw.fo) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    tmp_made = true;
+    auto host_members = [&](const uint8_t *p, size_t n, int lv) {                    // (PassWriter::host_blocks takes 256 members a call)
+        for (size_t o = 0; o < n; o += (size_t)PassWriter::CH) if (!pw.host_blocks(p + o, std::min<size_t>((size_t)PassWriter::CH, n - o), lv)) return false;
+        return true;
+    };
+    if (!host_members(hdr.data(), hdr.size(), codes >= 0 ? 1 : level)) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    for (uint64_t o = 0; o < total; o += piece) {
+        const size_t nb = (size_t)std::min<uint64_t>(piece, total - o); size_t got = 0;
+        if ((rc = gce_sort_read(b, o, nb, codes, hb.p, hb.cap, &got)) != GCE_OK) return done(rc, gce_sort_error(b));
+        if (codes >= 0 ? fwrite(hb.p, 1, got, pw.fo) != got : !host_members(hb.p, got, level)) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    }
+    if (!pw.close()) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    { struct stat so; out->out_bytes = stat(tmp.c_str(), &so) == 0 ? (int64_t)so.st_size : 0; }
+    if (rename(tmp.c_str(), out_path) != 0) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    out->write_s = now_s() - t0;
+    { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); out->peak_device_bytes = pk; }
+    out->total_s = now_s() - t_start;
+    return done(GCE_OK, "");
+}
+
+}  // extern "C"

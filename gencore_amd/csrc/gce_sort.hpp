@@ -1,0 +1,295 @@
+// gce_sort.hpp — an unsorted BAM into coordinate order on the GPU (gce_bam_sort).  The file is streamed window by window as the
+// BAI indexer streams it (win_inflate_index / win_carry, gce_passes.hpp).  Per window:
+//   k_sort_keys     one thread per record: the 64-bit key t << 33 | p << 1 | r of rule S (t: tid, n_ref for an unplaced record; p: pos + 1 as
+//                   unsigned; r: the reverse-strand bit), the record's size (4 + block_size) and its offset in the resident stream; the first
+//                   record whose tid the header does not have (atomicMin); the unplaced records; the descents (records whose key is below their
+//                   predecessor's, the first record of a window against the last one of the window before)
+//   one device-to-device copy appends the window's whole records to the resident record buffer
+// Resident across windows: the inflated record bytes and 8 + 4 + 8 bytes per record.  After the last window (gce_sort_finish):
+//   hipcub::DeviceRadixSort::SortPairs(key, index) over the key bits in use (stable: the input index needs no key bits), the sizes gathered
+//   in sorted order, dev_exclusive_sum -> the destination offsets, and
+//   k_sort_gather   the record bytes into a second buffer in the new order: 16 lanes per record, 16-byte stores aligned on the DESTINATION
+//                   (the bytes in front of the first aligned chunk and behind the last one go as single bytes), source read unaligned
+// gce_sort_read hands the sorted stream out in pieces: raw, or as BGZF members of 0xff00 input bytes deflated on the device (def_launch,
+// k_deflate_pack).  In-core: about 2 x the inflated record bytes + 20 bytes per record + one window; a file beyond that is GCE_ERR_OOM (an
+// external merge sort is out of scope).  tests/pysort.py models the rules.
+#pragma once
+
+namespace {
+
+#define SORT_MAX_RECORDS 0xFFFFFFF0ull
+
+// misc: [0] the first record with tid >= n_ref (atomicMin), [1] unplaced records, [2] descents
+__global__ __launch_bounds__(256) void k_sort_keys(const uint8_t *u, const uint64_t *off, int64_t n, uint64_t start, uint64_t res_base, uint64_t gbase, int32_t n_ref,
+                                                   unsigned long long *key, uint32_t *size, uint64_t *roff, unsigned long long *misc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    bool unplaced = false, descent = false;
+    if (live) {
+        const uint64_t o = off[i];
+        const uint8_t *r = u + o + 4;
+        const int32_t tid = (int32_t)rb32(r), pos = (int32_t)rb32(r + 4);
+        const uint32_t flag = rb16(r + 14);
+        if (tid >= n_ref) atomicMin(misc, (unsigned long long)(gbase + (uint64_t)i));
+        unplaced = tid < 0;
+        const unsigned long long t = (unsigned long long)(uint32_t)(tid < 0 || tid >= n_ref ? n_ref : tid);
+        const unsigned long long k = t << 33 | (unsigned long long)(uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1u);
+        const uint64_t g = gbase + (uint64_t)i;
+        key[g] = k; size[g] = 4u + rb32(u + o); roff[g] = res_base + (o - start);
+        if (g > 0) {                                                                  // (the predecessor of a window's first record: the last key of the window before, resident)
+            unsigned long long kp;
+            if (i > 0) {
+                const uint8_t *q = u + off[i - 1] + 4;
+                const int32_t ptid = (int32_t)rb32(q);
+                const unsigned long long pt = (unsigned long long)(uint32_t)(ptid < 0 || ptid >= n_ref ? n_ref : ptid);
+                kp = pt << 33 | (unsigned long long)(uint32_t)((int32_t)rb32(q + 4) + 1) << 1 | ((rb16(q + 14) >> 4) & 1u);
+            } else kp = key[g - 1];
+            descent = k < kp;
+        }
+    }
+    const unsigned long long bu = __ballot(unplaced), bd = __ballot(descent);
+    if (lane_id() == 0) {
+        if (bu) atomicAdd(misc + 1, (unsigned long long)__popcll(bu));
+        if (bd) atomicAdd(misc + 2, (unsigned long long)__popcll(bd));
+    }
+}
+__global__ __launch_bounds__(256) void k_sort_iota(uint32_t *idx, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) idx[i] = (uint32_t)i;
+}
+__global__ __launch_bounds__(256) void k_sort_sizes(const uint32_t *size, const uint32_t *sidx, uint64_t n, uint32_t *ssize) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) ssize[j] = size[sidx[j]];
+}
+// 16 lanes per record of the sorted order: record j = input record sidx[j], ssize[j] bytes from src + roff[sidx[j]] to out + dst[j].  The
+// stores are 16 bytes wide and aligned on the destination: head = the bytes in front of the first 16-byte boundary (one byte per lane),
+// then whole chunks (each lane reads its 16 source bytes unaligned), then the bytes behind the last boundary (one byte per lane).  Every
+// read stays inside [s, s + sz) and every write inside [d, d + sz), for any size and any pair of alignments.
+__global__ __launch_bounds__(256) void k_sort_gather(const uint8_t *src, const uint64_t *roff, const uint32_t *sidx, const uint32_t *ssize, const uint64_t *dst, uint64_t n, uint8_t *out) {
+    const uint32_t sub = threadIdx.x & 15u;
+    for (uint64_t j = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4; j < n; j += ((uint64_t)gridDim.x * blockDim.x) >> 4) {
+        const uint8_t *s = src + roff[sidx[j]]; uint8_t *d = out + dst[j];
+        const uint32_t sz = ssize[j];
+        const uint32_t head = min(sz, (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u));
+        const uint32_t nchunk = (sz - head) >> 4, tail = head + (nchunk << 4);
+        if (sub < head) d[sub] = s[sub];
+        for (uint32_t c = sub; c < nchunk; c += 16) {
+            const uint32_t q = head + (c << 4);
+            uint4 v;
+            v.x = rb32(s + q); v.y = rb32(s + q + 4); v.z = rb32(s + q + 8); v.w = rb32(s + q + 12);
+            *reinterpret_cast<uint4 *>(d + q) = v;
+        }
+        if (tail + sub < sz) d[tail + sub] = s[tail + sub];
+    }
+}
+
+}  // namespace
+
+struct gce_sort {
+    int32_t device = 0;
+    hipStream_t s = nullptr;
+    std::string err;
+    uint64_t budget = 0;                                                              // device bytes the process may hold (0: no limit beyond the device)
+    WinIdx w; DevBuf tmp, misc;                                                       // the window; the counters of k_sort_keys
+    DevBuf rec, key, size, off; uint64_t rec_n = 0, n = 0;                            // resident: the records' bytes, key / size / offset of each
+    DevBuf out; uint64_t out_n = 0;                                                   // the sorted stream (gce_sort_finish)
+    DevBuf zs, zz, zf, zo;                                                            // a piece's deflate slots, sizes, offsets, packed members
+};
+
+static int sfail(gce_sort *b, int code, const std::string &m) { if (b) b->err = m; return code; }
+static int sort_oom(gce_sort *b, const char *what, uint64_t add) {
+    char m[256];                                                                      // (the footprint first: a long `what` is cut off, not the formula)
+    snprintf(m, sizeof m, "out of device memory: the sort is in-core and needs about 2 x the inflated record bytes + 20 bytes per record + one window (%lld bytes live, budget %llu, %llu more for %s)",
+             __atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), (unsigned long long)b->budget, (unsigned long long)add, what);
+    return sfail(b, GCE_ERR_OOM, m);
+}
+#define SCHK(call) do { hipError_t _e = (call); if (_e == hipErrorOutOfMemory) return sort_oom(b, #call, 0); if (_e != hipSuccess) return sfail(b, GCE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); } while (0)
+// may `add` more device bytes be taken?  (the live count of gce_device_bytes against the budget, before the allocation)
+static bool sort_room(const gce_sort *b, uint64_t add) {
+    return !b->budget || (uint64_t)std::max<long long>(__atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), 0) + add <= b->budget;
+}
+// `buf` holds at least `need` bytes, its first `used` ones kept; a new buffer has exactly max(need, target) bytes (DevBuf::ensure would add an
+// eighth, and the resident record buffer is the sort's largest: it is sized once from the caller's estimate, so that it seldom grows)
+static int sort_grow(gce_sort *b, DevBuf &buf, size_t need, size_t used, size_t target, const char *what) {
+    if (need <= buf.cap && buf.p) return GCE_OK;
+    const size_t want = std::max(need, target) + 256;
+    if (!sort_room(b, want)) return sort_oom(b, what, want);
+    DevBuf nb;
+    hipError_t r = hipMalloc(&nb.p, want);
+    if (r != hipSuccess) { nb.p = nullptr; return r == hipErrorOutOfMemory ? sort_oom(b, what, want) : sfail(b, GCE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(r)); }
+    nb.cap = want; dev_bytes_add((long long)want);
+    if (used && (r = hipMemcpyAsync(nb.p, buf.p, used, hipMemcpyDeviceToDevice, b->s)) != hipSuccess) { nb.release(); return sfail(b, GCE_ERR_HIP, hipGetErrorString(r)); }
+    if ((r = hipStreamSynchronize(b->s)) != hipSuccess) { nb.release(); return sfail(b, GCE_ERR_HIP, hipGetErrorString(r)); }
+    buf.release(); buf = nb;
+    return GCE_OK;
+}
+// the slots of one deflated piece of `piece` input bytes
+static uint32_t sort_slot() { return 0xff00u + 0xff00u / 8 + 64; }
+
+extern "C" {
+
+int gce_sort_create(int32_t device, size_t device_budget_bytes, gce_sort **out) {
+    if (!out) return GCE_ERR_INVALID;
+    *out = nullptr;
+    if (hipSetDevice(device) != hipSuccess) return GCE_ERR_NO_DEVICE;
+    gce_sort *b = new gce_sort();
+    b->device = device; b->budget = (uint64_t)device_budget_bytes;
+    if (hipStreamCreate(&b->s) != hipSuccess) { delete b; return GCE_ERR_HIP; }
+    *out = b;
+    return GCE_OK;
+}
+void gce_sort_destroy(gce_sort *b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    (void)hipStreamSynchronize(b->s);
+    b->w.release();
+    for (DevBuf *x : {&b->tmp, &b->misc, &b->rec, &b->key, &b->size, &b->off, &b->out, &b->zs, &b->zz, &b->zf, &b->zo}) x->release();
+    (void)hipStreamDestroy(b->s);
+    delete b;
+}
+const char *gce_sort_error(gce_sort *b) { return b ? b->err.c_str() : ""; }
+
+// the next piece of the file, as gce_bai_window takes it.  est_bytes: the caller's estimate of the whole file's inflated bytes (the members'
+// ISIZE totals so far scaled to the file size): the resident buffers are sized from it when they are first made, or grow.
+int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                    int32_t n_ref, int32_t last, uint64_t est_bytes) {
+    if (!b || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    {   // the window's own buffers, before win_inflate_index makes them: the inflated bytes (pass_grow takes half as much again) and the compressed ones
+        uint64_t u_all = b->w.carry_n; for (int32_t k = 0; k < n_members; k++) u_all += usize[k];
+        uint64_t add = 0;
+        if (u_all + 64 > b->w.win.cap) add += (u_all + 64) * 27 / 16 + 256;
+        if (comp_bytes + 64 > b->w.zc.cap) add += (comp_bytes + 64) * 9 / 8 + 256;
+        if (add && !sort_room(b, add)) return sort_oom(b, "a window of the file", add);
+    }
+    if (!b->misc.p) {
+        if (!sort_room(b, 512)) return sort_oom(b, "the sort's counters", 512);
+        SCHK(b->misc.ensure(64));
+        const unsigned long long init[3] = {~0ull, 0ull, 0ull};
+        SCHK(hipMemcpyAsync(b->misc.p, init, sizeof init, hipMemcpyHostToDevice, s)); SCHK(hipStreamSynchronize(s));
+    }
+    uint64_t total = 0, n_rec = 0, end = 0;
+    int rc = win_inflate_index(b->w, b->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, b->err);
+    if (rc == GCE_ERR_OOM) return sort_oom(b, "a window of the file", 0);
+    if (rc != GCE_OK) return rc;
+    if (n_rec) {
+        const uint64_t start = std::min<uint64_t>(skip, total), add = end - start, n1 = b->n + n_rec;
+        if (n1 >= SORT_MAX_RECORDS) return sfail(b, GCE_ERR_INVALID, "more than 2^32 - 16 records in one BAM file");
+        // the estimates: the file's record bytes (never below what is known), and its records at the bytes per record seen so far, 1/16 added
+        const uint64_t eb = std::max<uint64_t>(est_bytes, b->rec_n + add), en = (uint64_t)((double)n1 * ((double)eb / (double)(b->rec_n + add)));
+        if ((rc = sort_grow(b, b->rec, (size_t)(b->rec_n + add + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
+        const size_t tn = (size_t)(en + en / 16 + 64);
+        if ((rc = sort_grow(b, b->key, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' keys")) != GCE_OK) return rc;
+        if ((rc = sort_grow(b, b->size, (size_t)n1 * 4, (size_t)b->n * 4, tn * 4, "the records' sizes")) != GCE_OK) return rc;
+        if ((rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
+        hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.off.p, (int64_t)n_rec, start, b->rec_n, b->n, n_ref,
+                           b->key.as<unsigned long long>(), b->size.as<uint32_t>(), b->off.as<uint64_t>(), b->misc.as<unsigned long long>());
+        SCHK(hipGetLastError());
+        SCHK(hipMemcpyAsync(b->rec.as<uint8_t>() + b->rec_n, b->w.win.as<uint8_t>() + start, add, hipMemcpyDeviceToDevice, s));
+        b->rec_n += add; b->n = n1;
+    }
+    return win_carry(b->w, s, total, end, b->err);
+}
+
+// after the last window: sort, scan, gather.  counts: records, unplaced records, descents; *bad_rec: the first record whose tid the header
+// does not have (-1: none; nothing is sorted then); *out_bytes: the sorted stream's bytes; times: seconds of the sort (keys, sizes, scan) and
+// of the gather kernel.  codes >= 0: the buffers gce_sort_read deflates pieces of up to piece_bytes with are made here, so that running out
+// of device memory is known before the caller opens its output.
+int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int64_t counts[3], int64_t *bad_rec, uint64_t *out_bytes, double times[2]) {
+    if (!b || n_ref < 0 || !counts || !bad_rec || !out_bytes || !times || codes > 1) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    SCHK(hipStreamSynchronize(s));
+    b->w.release();                                                                   // (the last window is done with)
+    *bad_rec = -1; *out_bytes = 0; times[0] = times[1] = 0;
+    counts[0] = (int64_t)b->n; counts[1] = counts[2] = 0;
+    const uint64_t n = b->n;
+    if (n == 0) return GCE_OK;
+    unsigned long long h[3];
+    SCHK(hipMemcpyAsync(h, b->misc.p, sizeof h, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    if (h[0] != ~0ull) { *bad_rec = (int64_t)h[0]; return GCE_OK; }
+    counts[1] = (int64_t)h[1]; counts[2] = (int64_t)h[2];
+    double t0 = mono_s();
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    int end_bit = 33; for (uint32_t v = (uint32_t)n_ref; v; v >>= 1) end_bit++;
+    ScopedBuf sidx, ssize, dst;
+    int rc;
+    {
+        ScopedBuf idx, skey, st;
+        if (!sort_room(b, n * 18)) return sort_oom(b, "the radix sort of the keys", n * 18);
+        SCHK(idx.ensure(n * 4)); SCHK(sidx.ensure(n * 4)); SCHK(skey.ensure(n * 8));
+        hipLaunchKernelGGL(k_sort_iota, dim3(nb), dim3(256), 0, s, idx.as<uint32_t>(), n);
+        size_t tb = 0;
+        SCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->key.as<unsigned long long>(), skey.as<unsigned long long>(), idx.as<uint32_t>(), sidx.as<uint32_t>(), n, 0, end_bit, s));
+        if (!sort_room(b, tb + tb / 8 + 320)) return sort_oom(b, "the radix sort of the keys", tb);
+        SCHK(st.ensure(tb + 64));
+        SCHK(hipcub::DeviceRadixSort::SortPairs(st.p, tb, b->key.as<unsigned long long>(), skey.as<unsigned long long>(), idx.as<uint32_t>(), sidx.as<uint32_t>(), n, 0, end_bit, s));
+        SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    }
+    b->key.release();
+    if (!sort_room(b, n * 14)) return sort_oom(b, "the destination offsets", n * 14);
+    SCHK(ssize.ensure(n * 4)); SCHK(dst.ensure((n + 1) * 8));
+    hipLaunchKernelGGL(k_sort_sizes, dim3(nb), dim3(256), 0, s, (const uint32_t *)b->size.p, (const uint32_t *)sidx.p, n, ssize.as<uint32_t>());
+    SCHK(dev_exclusive_sum(ssize.as<uint32_t>(), n, dst.as<uint64_t>(), b->tmp, s));
+    uint64_t total = 0;
+    SCHK(hipMemcpyAsync(&total, dst.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    if (total != b->rec_n) return sfail(b, GCE_ERR_INVALID, "sort: the records' sizes do not add up to the resident stream");
+    b->size.release();
+    times[0] = mono_s() - t0;
+    if ((rc = sort_grow(b, b->out, (size_t)total + 64, 0, 0, "the sorted record bytes")) != GCE_OK) return rc;
+    SCHK(hipMemsetAsync(b->out.as<uint8_t>() + total, 0, 64, s));                    // (the deflate kernels may look a few bytes ahead)
+    SCHK(hipStreamSynchronize(s));
+    t0 = mono_s();                                                                    // (gather_s: the kernel alone, not the output buffer's hipMalloc)
+    hipLaunchKernelGGL(k_sort_gather, dim3((unsigned)std::min<uint64_t>((n + 15) / 16, 65535u)), dim3(256), 0, s, (const uint8_t *)b->rec.p, (const uint64_t *)b->off.p, (const uint32_t *)sidx.p,
+                       (const uint32_t *)ssize.p, (const uint64_t *)dst.p, n, b->out.as<uint8_t>());
+    SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    times[1] = mono_s() - t0;
+    b->rec.release(); b->off.release();
+    b->out_n = total; *out_bytes = total;
+    if (codes >= 0 && piece_bytes) {
+        const uint64_t pb = std::min<uint64_t>(piece_bytes, total), pn = (pb + 0xff00u - 1) / 0xff00u;
+        const uint64_t add = (pn * sort_slot() + 64) * 9 / 4 + pn * 14 + 2048;
+        if (!sort_room(b, add)) return sort_oom(b, "deflating a piece of the output", add);
+        SCHK(b->zs.ensure((size_t)pn * sort_slot() + 64)); SCHK(b->zo.ensure((size_t)pn * sort_slot() + 64)); SCHK(b->zz.ensure(((size_t)pn + 1) * 4)); SCHK(b->zf.ensure(((size_t)pn + 1) * 8));
+    }
+    return GCE_OK;
+}
+
+// bytes [offset, offset + bytes) of the sorted stream to `host`: codes < 0: as they are; 0 / 1: as BGZF members of 0xff00 input bytes each,
+// deflated on the device with fixed codes / the smallest of dynamic, fixed and stored per member (offset: a multiple of 0xff00).  *got: the
+// bytes written to host (at most host_cap: n + n / 8 + 64 per member is always enough).
+int gce_sort_read(gce_sort *b, uint64_t offset, size_t bytes, int32_t codes, void *host, size_t host_cap, size_t *got) {
+    if (!b || !got || codes > 1 || offset > b->out_n || bytes > b->out_n - offset || (bytes && !host)) return GCE_ERR_INVALID;
+    *got = 0;
+    if (!bytes) return GCE_OK;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    const uint8_t *in = b->out.as<uint8_t>() + offset;
+    if (codes < 0) {
+        if (bytes > host_cap) return GCE_ERR_INVALID;
+        SCHK(hipMemcpyAsync(host, in, bytes, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s));
+        *got = bytes;
+        return GCE_OK;
+    }
+    if (offset % 0xff00u) return GCE_ERR_INVALID;
+    const uint64_t nb64 = (bytes + 0xff00u - 1) / 0xff00u;
+    if (nb64 >= 0x7FFFFFF0ull) return GCE_ERR_INVALID;
+    const uint32_t nb = (uint32_t)nb64, slot = sort_slot();
+    // (gce_sort_finish made the four buffers for the largest piece: nothing grows here, behind the caller's open output)
+    if ((size_t)nb * slot + 64 > b->zs.cap || (size_t)nb * slot + 64 > b->zo.cap || ((size_t)nb + 1) * 4 > b->zz.cap || ((size_t)nb + 1) * 8 > b->zf.cap)
+        return sfail(b, GCE_ERR_INVALID, "sort: a piece larger than gce_sort_finish was told");
+    def_launch(codes, nb, s, in, (uint64_t)bytes, 0xff00u, b->zs.as<uint8_t>(), slot, b->zz.as<uint32_t>());
+    SCHK(hipMemsetAsync((char *)b->zz.p + (size_t)nb * 4, 0, 4, s));
+    SCHK(dev_exclusive_sum(b->zz.as<uint32_t>(), (uint64_t)nb, b->zf.as<uint64_t>(), b->tmp, s));
+    uint64_t csz = 0;
+    SCHK(hipMemcpyAsync(&csz, b->zf.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s));
+    if (csz > host_cap) return sfail(b, GCE_ERR_INVALID, "sort: a deflated piece is larger than its host buffer");
+    if (csz + 64 > b->zo.cap) return sfail(b, GCE_ERR_INVALID, "sort: a deflated piece is larger than its device buffer");
+    hipLaunchKernelGGL(k_deflate_pack, dim3(std::min<uint32_t>((nb + 3) / 4, 16384u)), dim3(256), 0, s, (const uint8_t *)b->zs.p, slot, (const uint32_t *)b->zz.p, (const uint64_t *)b->zf.p, nb, b->zo.as<uint8_t>());
+    SCHK(hipMemcpyAsync(host, b->zo.p, csz, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    *got = (size_t)csz;
+    return GCE_OK;
+}
+
+}  // extern "C"

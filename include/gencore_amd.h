@@ -600,6 +600,27 @@ typedef struct gce_bai_run {
     double  read_s, gpu_s, write_s, total_s;
 } gce_bai_run;
 int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, int threads, uint64_t window_bytes, gce_bai_run *out, char err[256]);
+/* An unsorted BAM file into coordinate order on ONE device (addition under ABI v3; gencore_amd/csrc/gce_sort.hpp).
+ * Replaces: nothing in the reference's source -- it stands in for the `samtools sort` the reference's README asks for in front of gencore (every
+ * runner here stops with GCE_ERR_UNSORTED otherwise).  The file is streamed in windows of window_bytes compressed bytes (0 = 64 MB) as
+ * gce_bam_index streams it; the GPU inflates every window, finds its records and keys them; records are ordered by (tid with the unplaced ones
+ * last, pos + 1, reverse-strand bit, input index), their bytes are moved unchanged, and the header's @HD line gets SO:coordinate (DESIGN.md 4d,
+ * rules S / R / H / F).  level: as gce_run_bam, -3..9 (-2 / -3: the GPU deflates the record stream; the members hold 0xff00 input bytes each).
+ * The sort is in-core: about 2 x the inflated record bytes + 20 bytes per record + one window of device memory; device_budget_bytes (0 = no
+ * limit beyond the device) bounds the process's live device bytes (gce_device_bytes) and is checked before every growth of a buffer that scales with the file or
+ * the window: GCE_ERR_OOM with a
+ * message that states the footprint, before any output exists.  The output is written to a temporary name beside out_path and renamed at the end: a
+ * failed call leaves neither an output nor a temporary file and never touches the input; an out_path that resolves to the input is refused.
+ * GCE_ERR_INVALID with a message for SAM text ("gce_bam_sort reads BAM, not SAM text"), a file that is not BGZF or is truncated, and a record
+ * whose tid the header does not have (the message names the record, counting from 0). */
+typedef struct gce_sort_run {
+    int64_t n_records, n_no_coor, n_descents;   /* n_descents == 0: the input was already in rule S's order */
+    int64_t inflated_bytes, out_bytes, peak_device_bytes;   /* record bytes sorted; size of the file written; gce_device_bytes' peak during the call */
+    int32_t n_ref, pad;
+    double  read_s, inflate_index_s, sort_s, gather_s, write_s, total_s;
+} gce_sort_run;
+int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
+                 size_t device_budget_bytes, gce_sort_run *out, char err[256]);
 /* Live and peak device bytes of the engine allocations of the whole PROCESS (every engine, every thread); reset_peak != 0 restarts the peak at
  * the live count.  gce_run_bam_passes resets it on entry: its run->peak_device_bytes covers other engines working in the same process as well. */
 int gce_device_bytes(int64_t *live, int64_t *peak, int32_t reset_peak);

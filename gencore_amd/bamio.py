@@ -174,7 +174,7 @@ def index_bam(bam, bai=None, device=0, threads=0, window_bytes=0):
 def sort_bam(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):
     """gce_bam_sort: an unsorted BAM file into coordinate order on the GPU (what `samtools sort` does in front of the reference), written to
     `out`.  level as run_bam; window_bytes: compressed bytes per window, 0 = 64 MB; device_budget_bytes: 0 = no limit beyond the device (the
-    sort is in-core).  Returns dict(n_records, n_no_coor, n_descents, inflated_bytes, out_bytes, peak_device_bytes, n_ref, read_s,
+    sort is in-core; sort_bam_passes takes a file beyond that).  Returns dict(n_records, n_no_coor, n_descents, inflated_bytes, out_bytes, peak_device_bytes, n_ref, read_s,
     inflate_index_s, sort_s, gather_s, write_s, total_s); raises GceError (and leaves no output) on failure."""
     from .capi import GceSortRun
     lib = capi.load_library()
@@ -184,6 +184,26 @@ def sort_bam(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_bud
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceSortRun._fields_ if n != "pad"}
+
+
+def sort_bam_passes(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0, min_passes=0):
+    """gce_bam_sort_passes: sort_bam for a file of any size: in-core when that fits device_budget_bytes (0 = auto, a fraction of the free device
+    memory) and min_passes <= 1, otherwise in output-range passes over the file (at least min_passes of them); the output's bytes are
+    sort_bam's.  Returns sort_bam's dict plus n_passes, in_core, pass_bytes, resident_bytes, key_pass_s, plan_s and pass_s (a list of n_passes
+    entries); raises GceError (and leaves no output) on failure."""
+    from .capi import GceSortPassRun, GceSortRun
+    lib = capi.load_library()
+    r, pr = GceSortRun(), GceSortPassRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_sort_passes(str(bam).encode(), str(out).encode(), int(device), int(threads), int(level), int(window_bytes), int(device_budget_bytes), int(min_passes),
+                                 C.byref(r), C.byref(pr), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    d = {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceSortRun._fields_ if n != "pad"}
+    P = int(pr.n_passes)
+    d.update(n_passes=P, in_core=int(pr.in_core), pass_bytes=int(pr.pass_bytes), resident_bytes=int(pr.resident_bytes), key_pass_s=float(pr.key_pass_s), plan_s=float(pr.plan_s),
+             pass_s=[float(pr.pass_s[k]) for k in range(P)])
+    return d
 
 
 def bgzf_deflate(data, block=0xff00, codes=1, device=0):

@@ -15,7 +15,8 @@ EPILOG = """\
 Flags marked [gencore_amd] are not the reference's; every other flag, default and validation message is gencore 0.17.2's.
 --index (not the reference's) writes <output>.bai, the BAI index of the BAM output, built on the GPU.
 --sort (not the reference's) takes a BAM in any order, as an aligner writes it: the GPU sorts it by coordinate into a temporary BAM first
-(what `samtools sort` does in front of the reference), and the run reads that file.
+(what `samtools sort` does in front of the reference), and the run reads that file.  --device_memory bounds the sort as it bounds the run: a
+file that does not fit is sorted in output-range passes over the input.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -73,7 +74,8 @@ def build_parser():
     a("--devices", default="0", help="[gencore_amd] HIP device ordinals, comma separated: one runs one engine, several run the sharded runner "
                                      "(an ordinal may repeat). Default 0.")
     a("--device_memory", default="auto", help="[gencore_amd] device memory budget in GB (2^30 bytes) for one device, or auto (a fraction of the free "
-                                               "memory): a file larger than the budget is processed in key-range passes. One device only. Default auto.")
+                                               "memory): a file larger than the budget is processed in key-range passes, and sorted (--sort) in output-range passes. One device only. "
+                                               "Default auto.")
     a("--threads", type=int, default=0, help="[gencore_amd] host threads for the file codecs; 0 = all cores. Default 0.")
     a("--index", action="store_true", help="[gencore_amd] after the output and the report are written, index the BAM output on the GPU into "
                                             "<output>.bai (BAI, SAMv1 5.2), on the first of --devices. Off by default.")
@@ -177,7 +179,7 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam
+    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = None
@@ -186,7 +188,7 @@ def main(argv=None):
             import tempfile
             fd, sorted_tmp = tempfile.mkstemp(suffix=".bam", prefix="gencore_sort_", dir=None if o.output == "-" else (os.path.dirname(os.path.abspath(o.output))))
             os.close(fd)
-            sort_bam(o.input, sorted_tmp, device=devices[0], threads=o.threads, level=-2)
+            sort_bam_passes(o.input, sorted_tmp, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
             o.input = sorted_tmp
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None

@@ -2532,6 +2532,14 @@ int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_
                     int32_t n_ref, int32_t last, uint64_t est_bytes);
 int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int64_t counts[3], int64_t *bad_rec, uint64_t *out_bytes, double times[2]);
 int gce_sort_read(gce_sort *b, uint64_t offset, size_t bytes, int32_t codes, void *host, size_t host_cap, size_t *got);
+int gce_sort_key_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, uint64_t est_bytes);
+int gce_sort_plan(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int32_t min_passes, int64_t counts[3], int64_t *bad_rec, uint64_t *total_out, int32_t *n_passes,
+                  uint64_t *pass_bytes, uint64_t *resident, double *plan_s);
+int gce_sort_pass_begin(gce_sort *b, uint64_t lo, uint64_t hi);
+int gce_sort_pass_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                         int32_t n_ref, int32_t last);
+int gce_sort_pass_end(gce_sort *b, double *scatter_s);
 }  // extern "C" (declarations)
 extern "C++" {
 namespace {
@@ -2546,54 +2554,48 @@ std::string sort_header_text(const uint8_t *t, size_t l_text) {
     text.replace(so + 4, ve - (so + 4), "coordinate");
     return text;
 }
-}  // namespace
-}  // extern "C++"
-extern "C" {
 
-int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, gce_sort_run *out, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
-    if (!in_path || !out_path || !out) { seterr("bad argument"); return GCE_ERR_INVALID; }
-    memset(out, 0, sizeof *out);
-    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
-    const double t_start = now_s();
-    const int fd = open(in_path, O_RDONLY);
-    if (fd < 0) { seterr("cannot open the input BAM"); return GCE_ERR_INVALID; }
-    struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the input BAM"); return GCE_ERR_INVALID; }
-    const uint64_t fsz = (uint64_t)st.st_size;
-    const std::string tmp = std::string(out_path) + ".tmp" + std::to_string((long long)getpid());
-    gce_sort *b = nullptr; PassWriter pw; bool tmp_made = false;
-    auto done = [&](int code, const char *m) {
-        const std::string keep(m ? m : "");                                          // (m may point into b)
-        if (b) gce_sort_destroy(b);
+// what gce_bam_sort and gce_bam_sort_passes share: the input's checks and header (rule H), the file streamed window by window, the output
+// (rule F: the header in members of its own, the record stream in members of 0xff00 bytes, the EOF marker) under a temporary name
+struct SortJob {
+    int fd = -1; uint64_t fsz = 0; struct stat st{}; std::string tmp, msg; bool tmp_made = false;
+    gce_sort *b = nullptr; PassWriter pw; Pinned hb;
+    int T = 1, level = 0; int32_t device = 0, codes = -1, n_ref = 0; uint64_t window_bytes = 0, hdr_end = 0, piece = 0;
+    std::vector<uint8_t> hdr;
+    int fail(int code, const std::string &m) { msg = m; return code; }
+    // everything is let go; a failed call leaves no output
+    void close_all(int code) {
+        if (b) { gce_sort_destroy(b); b = nullptr; }
         if (pw.fo) { fclose(pw.fo); pw.fo = nullptr; }
         if (code != GCE_OK && tmp_made) unlink(tmp.c_str());
-        close(fd);
-        seterr(keep.c_str());
-        return code;
-    };
-    {   // the output may not be the input (by name or by file)
-        struct stat so;
-        bool same = stat(out_path, &so) == 0 && so.st_dev == st.st_dev && so.st_ino == st.st_ino;
-        char *ri = realpath(in_path, nullptr), *ro = realpath(out_path, nullptr);
-        if (ri && ro && strcmp(ri, ro) == 0) same = true;
-        free(ri); free(ro);
-        if (same) return done(GCE_ERR_INVALID, "the output path is the input file: gce_bam_sort does not sort in place");
+        if (fd >= 0) { ::close(fd); fd = -1; }
     }
-    { uint8_t m2[4] = {0, 0, 0, 0}; const bool got = fsz >= 4 && pread(fd, m2, 4, 0) == 4;
-      if (fsz > 0 && !(got && m2[0] == 0x1f && m2[1] == 0x8b)) return done(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
-      if (fsz < 18 || m2[2] != 8 || !(m2[3] & 4)) return done(GCE_ERR_INVALID, "not a BGZF file"); }
-    const int T = threads > 0 ? threads : default_threads();
-    // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
-    uint64_t hdr_end = 0; int32_t n_ref = 0; std::vector<uint8_t> hdr;
-    {
+    int open_input(const char *in_path, const char *out_path, int threads, int lv, uint64_t wb, int32_t dev) {
+        level = lv; window_bytes = wb; device = dev;
+        fd = open(in_path, O_RDONLY);
+        if (fd < 0) return fail(GCE_ERR_INVALID, "cannot open the input BAM");
+        if (fstat(fd, &st) != 0 || st.st_size < 0) return fail(GCE_ERR_INVALID, "cannot stat the input BAM");
+        fsz = (uint64_t)st.st_size;
+        tmp = std::string(out_path) + ".tmp" + std::to_string((long long)getpid());
+        {   // the output may not be the input (by name or by file)
+            struct stat so;
+            bool same = stat(out_path, &so) == 0 && so.st_dev == st.st_dev && so.st_ino == st.st_ino;
+            char *ri = realpath(in_path, nullptr), *ro = realpath(out_path, nullptr);
+            if (ri && ro && strcmp(ri, ro) == 0) same = true;
+            free(ri); free(ro);
+            if (same) return fail(GCE_ERR_INVALID, "the output path is the input file: gce_bam_sort does not sort in place");
+        }
+        { uint8_t m2[4] = {0, 0, 0, 0}; const bool got = fsz >= 4 && pread(fd, m2, 4, 0) == 4;
+          if (fsz > 0 && !(got && m2[0] == 0x1f && m2[1] == 0x8b)) return fail(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
+          if (fsz < 18 || m2[2] != 8 || !(m2[3] & 4)) return fail(GCE_ERR_INVALID, "not a BGZF file"); }
+        T = threads > 0 ? threads : default_threads();
+        // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
         PassReader rh; rh.fd = fd; rh.fsz = fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
         for (;;) {
             const int g = rh.inflate_next();
-            if (g < 0) return done(GCE_ERR_INVALID, rh.msg.c_str());
+            if (g < 0) return fail(GCE_ERR_INVALID, rh.msg);
             const uint8_t *u = rh.win.p; const uint64_t n = rh.n;
-            if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return done(GCE_ERR_INVALID, "not a BAM stream");
+            if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return fail(GCE_ERR_INVALID, "not a BAM stream");
             if (n >= 12) {
                 uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
                 if (q + l_text + 4 <= n) {
@@ -2612,80 +2614,201 @@ int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int 
                         const uint32_t lt = (uint32_t)text.size();
                         hdr.assign(u, u + 4); hdr.insert(hdr.end(), (const uint8_t *)&lt, (const uint8_t *)&lt + 4);
                         hdr.insert(hdr.end(), text.begin(), text.end()); hdr.insert(hdr.end(), u + 8 + l_text, u + q);
-                        break;
+                        return GCE_OK;
                     }
                 }
             }
-            if (g == 0) return done(GCE_ERR_INVALID, "truncated BAM header");
+            if (g == 0) return fail(GCE_ERR_INVALID, "truncated BAM header");
         }
     }
+    // the file from its first byte, window by window: the host reads and finds the members, window(rd, skip, est) hands them to the GPU.
+    // est: the whole file's inflated bytes, from the ISIZE totals so far and the file size.  read_s / gpu_s: the two sides' seconds, added to.
+    template <class F> int stream(double *read_s, double *gpu_s, F &&window) {
+        PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? (size_t)window_bytes : ((size_t)64 << 20);
+        uint64_t skip = hdr_end, comp_seen = 0, infl_seen = 0;
+        for (;;) {
+            double t0 = now_s();
+            const int g = rd.members_next();
+            if (g < 0) return fail(GCE_ERR_INVALID, rd.msg);
+            if (g == 0) break;
+            rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
+            for (const Block &k : rd.blocks) { rd.z_coff.push_back(k.coff); rd.z_csize.push_back(k.csize); rd.z_usize.push_back(k.usize); u_all += k.usize; }
+            const uint64_t sk = std::min<uint64_t>(skip, u_all);
+            comp_seen += rd.used; infl_seen += u_all;
+            const uint64_t est = comp_seen ? (uint64_t)((double)infl_seen * ((double)fsz / (double)comp_seen)) : 0;
+            *read_s += now_s() - t0; t0 = now_s();
+            const int rc = window(rd, sk, est);
+            *gpu_s += now_s() - t0;
+            if (rc != GCE_OK) return fail(rc, gce_sort_error(b));
+            skip -= sk;
+            if (rd.last_piece()) break;
+        }
+        if (rd.have != rd.used) return fail(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
+        if (skip) return fail(GCE_ERR_INVALID, "truncated BAM header");
+        return GCE_OK;
+    }
+    // The output comes back in pieces that are multiples of 0xff00: 8192 members when the GPU deflates them (one lane per member), 1024 when
+    // the host threads do
+    void set_pieces() { codes = level == -3 ? 1 : level == -2 ? 0 : -1; piece = PassWriter::BS * (codes >= 0 ? 8192 : 1024); }
+    bool host_members(const uint8_t *p, size_t n, int lv) {                          // (PassWriter::host_blocks takes 256 members a call)
+        for (size_t o = 0; o < n; o += (size_t)PassWriter::CH) if (!pw.host_blocks(p + o, std::min<size_t>((size_t)PassWriter::CH, n - o), lv)) return false;
+        return true;
+    }
+    // the temporary file with the header's members; largest: the most bytes one write_range call will be asked for
+    int begin_output(uint64_t largest) {
+        const size_t pmax = (size_t)std::min<uint64_t>(piece, largest), hcap = codes >= 0 ? pmax + pmax / 8 + 64 * (pmax / PassWriter::BS + 2) : pmax;
+        if (largest && !hb.ensure(hcap)) return fail(GCE_ERR_OOM, "out of pinned host memory");
+        pw.level = level; pw.T = T; pw.device = device;
+        pw.zbuf.resize((size_t)256 * 0x10000 + 64);
+        if (!pw.zbuf.ok()) return fail(GCE_ERR_OOM, "out of host memory");
+        pw.fo = fopen(tmp.c_str(), "wb");
+        if (!pw.fo) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        tmp_made = true;
+        if (!host_members(hdr.data(), hdr.size(), codes >= 0 ? 1 : level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        return GCE_OK;
+    }
+    // the first n bytes gce_sort_read has to give, piece by piece, as members of 0xff00 bytes
+    int write_range(uint64_t n) {
+        for (uint64_t o = 0; o < n; o += piece) {
+            const size_t nb = (size_t)std::min<uint64_t>(piece, n - o); size_t got = 0;
+            const int rc = gce_sort_read(b, o, nb, codes, hb.p, hb.cap, &got);
+            if (rc != GCE_OK) return fail(rc, gce_sort_error(b));
+            if (codes >= 0 ? fwrite(hb.p, 1, got, pw.fo) != got : !host_members(hb.p, got, level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        }
+        return GCE_OK;
+    }
+    int end_output(const char *out_path, int64_t *out_bytes) {
+        if (!pw.close()) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        { struct stat so; *out_bytes = stat(tmp.c_str(), &so) == 0 ? (int64_t)so.st_size : 0; }
+        if (rename(tmp.c_str(), out_path) != 0) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        return GCE_OK;
+    }
+};
+}  // namespace
+}  // extern "C++"
+extern "C" {
+
+int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, gce_sort_run *out, char err[256]) {
+    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
+    seterr("");
+    if (!in_path || !out_path || !out) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    memset(out, 0, sizeof *out);
+    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    const double t_start = now_s();
+    SortJob j;
+    auto done = [&](int code) { j.close_all(code); seterr(j.msg.c_str()); return code; };
+    int rc = j.open_input(in_path, out_path, threads, level, window_bytes, device);
+    if (rc != GCE_OK) return done(rc);
+    const int32_t n_ref = j.n_ref;
     out->n_ref = n_ref;
     (void)gce_device_bytes(nullptr, nullptr, 1);
-    int rc = gce_sort_create(device, device_budget_bytes, &b);
-    if (rc != GCE_OK) return done(rc, "no HIP device");
+    if ((rc = gce_sort_create(device, device_budget_bytes, &j.b)) != GCE_OK) return done(j.fail(rc, "no HIP device"));
     // ---- the file from its first byte, window by window: the host reads and finds the members, the GPU inflates, indexes and keys them
-    PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? (size_t)window_bytes : ((size_t)64 << 20);
-    uint64_t skip = hdr_end, comp_seen = 0, infl_seen = 0;
-    for (;;) {
-        double t0 = now_s();
-        const int g = rd.members_next();
-        if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str());
-        if (g == 0) break;
-        rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
-        for (const Block &k : rd.blocks) { rd.z_coff.push_back(k.coff); rd.z_csize.push_back(k.csize); rd.z_usize.push_back(k.usize); u_all += k.usize; }
-        const uint64_t sk = std::min<uint64_t>(skip, u_all);
-        comp_seen += rd.used; infl_seen += u_all;
-        // the whole file's inflated bytes, from the ISIZE totals so far and the file size
-        const uint64_t est = comp_seen ? (uint64_t)((double)infl_seen * ((double)fsz / (double)comp_seen)) : 0;
-        out->read_s += now_s() - t0; t0 = now_s();
-        rc = gce_sort_window(b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0, est);
-        out->inflate_index_s += now_s() - t0;
-        if (rc != GCE_OK) return done(rc, gce_sort_error(b));
-        skip -= sk;
-        if (rd.last_piece()) break;
-    }
-    if (rd.have != rd.used) return done(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
-    if (skip) return done(GCE_ERR_INVALID, "truncated BAM header");
-    // ---- sort, scan, gather.  The output comes back in pieces that are multiples of 0xff00: 8192 members when the GPU deflates them (one
-    // lane per member), 1024 when the host threads do
-    const int32_t codes = level == -3 ? 1 : level == -2 ? 0 : -1;
-    const uint64_t BS = PassWriter::BS, piece = BS * (codes >= 0 ? 8192 : 1024);
+    rc = j.stream(&out->read_s, &out->inflate_index_s, [&](PassReader &rd, uint64_t sk, uint64_t est) {
+        return gce_sort_window(j.b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0, est); });
+    if (rc != GCE_OK) return done(rc);
+    // ---- sort, scan, gather
+    j.set_pieces();
     int64_t counts[3] = {0, 0, 0}, bad = -1; uint64_t total = 0; double times[2] = {0, 0};
-    if ((rc = gce_sort_finish(b, n_ref, codes, piece, counts, &bad, &total, times)) != GCE_OK) return done(rc, gce_sort_error(b));
+    if ((rc = gce_sort_finish(j.b, n_ref, j.codes, j.piece, counts, &bad, &total, times)) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
     if (bad >= 0) {
         char m[256]; snprintf(m, sizeof m, "BAM record %lld (counting from 0) names a contig the header does not have", (long long)bad);
-        return done(GCE_ERR_INVALID, m);
+        return done(j.fail(GCE_ERR_INVALID, m));
     }
     out->sort_s = times[0]; out->gather_s = times[1];
     out->n_records = counts[0]; out->n_no_coor = counts[1]; out->n_descents = counts[2]; out->inflated_bytes = (int64_t)total;
-    // ---- rule F: the header in members of its own, the record stream in members of 0xff00 bytes, the EOF marker
-    double t0 = now_s();
-    Pinned hb;
-    const size_t pmax = (size_t)std::min<uint64_t>(piece, total), hcap = codes >= 0 ? pmax + pmax / 8 + 64 * (pmax / BS + 2) : pmax;
-    if (total && !hb.ensure(hcap)) return done(GCE_ERR_OOM, "out of pinned host memory");
-    pw.level = level; pw.T = T; pw.device = device;
-    pw.zbuf.resize((size_t)256 * 0x10000 + 64);
-    if (!pw.zbuf.ok()) return done(GCE_ERR_OOM, "out of host memory");
-    pw.fo = fopen(tmp.c_str(), "wb");
-    if (!pw.fo) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-    tmp_made = true;
-    auto host_members = [&](const uint8_t *p, size_t n, int lv) {                    // (PassWriter::host_blocks takes 256 members a call)
-        for (size_t o = 0; o < n; o += (size_t)PassWriter::CH) if (!pw.host_blocks(p + o, std::min<size_t>((size_t)PassWriter::CH, n - o), lv)) return false;
-        return true;
-    };
-    if (!host_members(hdr.data(), hdr.size(), codes >= 0 ? 1 : level)) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-    for (uint64_t o = 0; o < total; o += piece) {
-        const size_t nb = (size_t)std::min<uint64_t>(piece, total - o); size_t got = 0;
-        if ((rc = gce_sort_read(b, o, nb, codes, hb.p, hb.cap, &got)) != GCE_OK) return done(rc, gce_sort_error(b));
-        if (codes >= 0 ? fwrite(hb.p, 1, got, pw.fo) != got : !host_members(hb.p, got, level)) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-    }
-    if (!pw.close()) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-    { struct stat so; out->out_bytes = stat(tmp.c_str(), &so) == 0 ? (int64_t)so.st_size : 0; }
-    if (rename(tmp.c_str(), out_path) != 0) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    // ---- rule F
+    const double t0 = now_s();
+    if ((rc = j.begin_output(total)) != GCE_OK || (rc = j.write_range(total)) != GCE_OK || (rc = j.end_output(out_path, &out->out_bytes)) != GCE_OK) return done(rc);
     out->write_s = now_s() - t0;
     { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); out->peak_device_bytes = pk; }
     out->total_s = now_s() - t_start;
-    return done(GCE_OK, "");
+    return done(GCE_OK);
+}
+
+// gce_bam_sort for a file of any size: in-core when that fits the budget, otherwise in output-range passes: a key pass
+// (gce_sort_key_window), the plan (gce_sort_plan), then per pass the file once more (gce_sort_pass_*) and that range of the output written.
+int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, int32_t min_passes,
+                        gce_sort_run *out, gce_sort_pass_run *run, char err[256]) {
+    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
+    seterr("");
+    if (!in_path || !out_path || !out || !run || min_passes < 0 || min_passes > 64) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    memset(out, 0, sizeof *out); memset(run, 0, sizeof *run);
+    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    const double t_start = now_s();
+    uint64_t budget = device_budget_bytes;
+    if (!budget) {
+        size_t fr = 0, tot = 0;
+        const int r0 = gce_device_mem_info(device, &fr, &tot);
+        if (r0 != GCE_OK) { seterr("no HIP device"); return r0; }
+        budget = std::max<uint64_t>((uint64_t)((double)fr * GCE_PASS_BUDGET_FRACTION), 1);
+    }
+    const uint64_t M = PassWriter::BS;
+    // ---- in-core first, unless passes are forced or even the compressed file is beyond half the budget (in-core holds the inflated records twice)
+    if (min_passes <= 1) {
+        struct stat sf;
+        const bool hopeless = stat(in_path, &sf) == 0 && sf.st_size > 0 && (uint64_t)sf.st_size > budget / 2;
+        if (!hopeless) {
+            const int r1 = gce_bam_sort(in_path, out_path, device, threads, level, window_bytes, (size_t)budget, out, err);
+            if (r1 != GCE_ERR_OOM) {
+                if (r1 == GCE_OK) {
+                    const uint64_t total = (uint64_t)out->inflated_bytes;
+                    run->in_core = 1; run->pass_bytes = (int64_t)((total + M - 1) / M * M); run->n_passes = total ? 1 : 0; run->resident_bytes = out->peak_device_bytes;
+                    run->pass_s[0] = out->sort_s + out->gather_s + out->write_s;
+                }
+                return r1;
+            }
+            seterr(""); memset(out, 0, sizeof *out);                                 // (GCE_ERR_OOM leaves no output)
+        }
+    }
+    SortJob j;
+    auto done = [&](int code) { j.close_all(code); seterr(j.msg.c_str()); return code; };
+    int rc = j.open_input(in_path, out_path, threads, level, window_bytes, device);
+    if (rc != GCE_OK) return done(rc);
+    const int32_t n_ref = j.n_ref;
+    out->n_ref = n_ref;
+    (void)gce_device_bytes(nullptr, nullptr, 1);
+    if ((rc = gce_sort_create(device, (size_t)budget, &j.b)) != GCE_OK) return done(j.fail(rc, "no HIP device"));
+    // ---- the key pass: key and size of every record
+    double t0 = now_s();
+    rc = j.stream(&out->read_s, &out->inflate_index_s, [&](PassReader &rd, uint64_t sk, uint64_t est) {
+        return gce_sort_key_window(j.b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0, est); });
+    if (rc != GCE_OK) return done(rc);
+    run->key_pass_s = now_s() - t0;
+    // ---- the plan: the order, every record's destination, the cuts
+    j.set_pieces();
+    int64_t counts[3] = {0, 0, 0}, bad = -1; uint64_t total = 0, pass_bytes = 0, resident = 0; int32_t P = 0;
+    if ((rc = gce_sort_plan(j.b, n_ref, j.codes, j.piece, min_passes, counts, &bad, &total, &P, &pass_bytes, &resident, &run->plan_s)) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+    if (bad >= 0) {
+        char m[256]; snprintf(m, sizeof m, "BAM record %lld (counting from 0) names a contig the header does not have", (long long)bad);
+        return done(j.fail(GCE_ERR_INVALID, m));
+    }
+    out->sort_s = run->plan_s;
+    out->n_records = counts[0]; out->n_no_coor = counts[1]; out->n_descents = counts[2]; out->inflated_bytes = (int64_t)total;
+    run->n_passes = P; run->pass_bytes = (int64_t)pass_bytes; run->resident_bytes = (int64_t)resident;
+    // ---- rule F, one output range per pass: the member layout is the in-core sort's, because pass_bytes is a multiple of 0xff00
+    if ((rc = j.begin_output(pass_bytes)) != GCE_OK) return done(rc);
+    for (int32_t k = 0; k < P; k++) {
+        t0 = now_s();
+        const uint64_t lo = (uint64_t)k * pass_bytes, hi = std::min<uint64_t>(lo + pass_bytes, total);
+        if ((rc = gce_sort_pass_begin(j.b, lo, hi)) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+        rc = j.stream(&out->read_s, &out->inflate_index_s, [&](PassReader &rd, uint64_t sk, uint64_t) {
+            return gce_sort_pass_window(j.b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0); });
+        if (rc != GCE_OK) return done(rc);
+        double sc = 0;
+        if ((rc = gce_sort_pass_end(j.b, &sc)) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+        out->gather_s += sc; out->inflate_index_s -= sc;
+        const double tw = now_s();
+        if ((rc = j.write_range(hi - lo)) != GCE_OK) return done(rc);
+        out->write_s += now_s() - tw;
+        run->pass_s[k] = now_s() - t0;
+    }
+    t0 = now_s();
+    if ((rc = j.end_output(out_path, &out->out_bytes)) != GCE_OK) return done(rc);
+    out->write_s += now_s() - t0;
+    { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); out->peak_device_bytes = pk; }
+    out->total_s = now_s() - t_start;
+    return done(GCE_OK);
 }
 
 }  // extern "C"

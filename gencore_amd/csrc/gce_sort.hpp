@@ -11,8 +11,17 @@
 //   k_sort_gather   the record bytes into a second buffer in the new order: 16 lanes per record, 16-byte stores aligned on the DESTINATION
 //                   (the bytes in front of the first aligned chunk and behind the last one go as single bytes), source read unaligned
 // gce_sort_read hands the sorted stream out in pieces: raw, or as BGZF members of 0xff00 input bytes deflated on the device (def_launch,
-// k_deflate_pack).  In-core: about 2 x the inflated record bytes + 20 bytes per record + one window; a file beyond that is GCE_ERR_OOM (an
-// external merge sort is out of scope).  tests/pysort.py models the rules.
+// k_deflate_pack).  In-core: about 2 x the inflated record bytes + 20 bytes per record + one window; a file beyond that is GCE_ERR_OOM.
+//
+// A file beyond that is sorted in output-range passes (gce_bam_sort_passes): the key pass streams the file the same way but keeps only key and
+// size of every record (gce_sort_key_window); gce_sort_plan sorts and scans as above and inverts the order,
+//   k_sort_dest     dest[sidx[j]] = dst[j]: the destination byte offset of every record in INPUT order, the only thing resident afterwards,
+// and cuts the sorted stream [0, total) into passes of pass_bytes (a multiple of 0xff00: cuts fall on rule F's member boundaries, not on
+// record boundaries).  Pass k streams the file again from its first byte (gce_sort_pass_begin / _window / _end); per window
+//   k_sort_scatter  16 lanes per window record: the part of [dest, dest + size) inside the pass's range [lo, hi) goes to the pass buffer with
+//                   k_sort_gather's copy (a record that straddles a cut is written partly by each pass it touches); the bytes written are
+//                   summed, so that a pass whose records do not tile its range (the input changed) is refused
+// and gce_sort_read hands the pass buffer out as it hands out the in-core stream.  tests/pysort.py models the rules.
 #pragma once
 
 namespace {
@@ -35,7 +44,8 @@ __global__ __launch_bounds__(256) void k_sort_keys(const uint8_t *u, const uint6
         const unsigned long long t = (unsigned long long)(uint32_t)(tid < 0 || tid >= n_ref ? n_ref : tid);
         const unsigned long long k = t << 33 | (unsigned long long)(uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1u);
         const uint64_t g = gbase + (uint64_t)i;
-        key[g] = k; size[g] = 4u + rb32(u + o); roff[g] = res_base + (o - start);
+        key[g] = k; size[g] = 4u + rb32(u + o);
+        if (roff) roff[g] = res_base + (o - start);                                  // (NULL in the key pass of the output-range passes: no record bytes stay resident)
         if (g > 0) {                                                                  // (the predecessor of a window's first record: the last key of the window before, resident)
             unsigned long long kp;
             if (i > 0) {
@@ -61,25 +71,63 @@ __global__ __launch_bounds__(256) void k_sort_sizes(const uint32_t *size, const 
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) ssize[j] = size[sidx[j]];
 }
-// 16 lanes per record of the sorted order: record j = input record sidx[j], ssize[j] bytes from src + roff[sidx[j]] to out + dst[j].  The
-// stores are 16 bytes wide and aligned on the destination: head = the bytes in front of the first 16-byte boundary (one byte per lane),
-// then whole chunks (each lane reads its 16 source bytes unaligned), then the bytes behind the last boundary (one byte per lane).  Every
-// read stays inside [s, s + sz) and every write inside [d, d + sz), for any size and any pair of alignments.
+// the copy of one record (or of a stretch of one) by its 16 lanes: sz bytes from s to d.  The stores are 16 bytes wide and aligned on the
+// destination: head = the bytes in front of the first 16-byte boundary (one byte per lane), then whole chunks (each lane reads its 16 source
+// bytes unaligned), then the bytes behind the last boundary (one byte per lane).  Every read stays inside [s, s + sz) and every write inside
+// [d, d + sz), for any size and any pair of alignments.
+__device__ __forceinline__ void sort_copy16(const uint8_t *s, uint8_t *d, uint32_t sz, uint32_t sub) {
+    const uint32_t head = min(sz, (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u));
+    const uint32_t nchunk = (sz - head) >> 4, tail = head + (nchunk << 4);
+    if (sub < head) d[sub] = s[sub];
+    for (uint32_t c = sub; c < nchunk; c += 16) {
+        const uint32_t q = head + (c << 4);
+        uint4 v;
+        v.x = rb32(s + q); v.y = rb32(s + q + 4); v.z = rb32(s + q + 8); v.w = rb32(s + q + 12);
+        *reinterpret_cast<uint4 *>(d + q) = v;
+    }
+    if (tail + sub < sz) d[tail + sub] = s[tail + sub];
+}
+// 16 lanes per record of the sorted order: record j = input record sidx[j], ssize[j] bytes from src + roff[sidx[j]] to out + dst[j] (sort_copy16)
 __global__ __launch_bounds__(256) void k_sort_gather(const uint8_t *src, const uint64_t *roff, const uint32_t *sidx, const uint32_t *ssize, const uint64_t *dst, uint64_t n, uint8_t *out) {
     const uint32_t sub = threadIdx.x & 15u;
-    for (uint64_t j = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4; j < n; j += ((uint64_t)gridDim.x * blockDim.x) >> 4) {
-        const uint8_t *s = src + roff[sidx[j]]; uint8_t *d = out + dst[j];
-        const uint32_t sz = ssize[j];
-        const uint32_t head = min(sz, (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u));
-        const uint32_t nchunk = (sz - head) >> 4, tail = head + (nchunk << 4);
-        if (sub < head) d[sub] = s[sub];
-        for (uint32_t c = sub; c < nchunk; c += 16) {
-            const uint32_t q = head + (c << 4);
-            uint4 v;
-            v.x = rb32(s + q); v.y = rb32(s + q + 4); v.z = rb32(s + q + 8); v.w = rb32(s + q + 12);
-            *reinterpret_cast<uint4 *>(d + q) = v;
+    for (uint64_t j = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4; j < n; j += ((uint64_t)gridDim.x * blockDim.x) >> 4)
+        sort_copy16(src + roff[sidx[j]], out + dst[j], ssize[j], sub);
+}
+// the inverse of the sorted order: the destination byte offset of every record in input order
+__global__ __launch_bounds__(256) void k_sort_dest(const uint32_t *sidx, const uint64_t *dst, uint64_t n, uint64_t *dest) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) dest[sidx[j]] = dst[j];
+}
+// one pass of the output-range passes over one window: 16 lanes per window record (a wave takes four records at a time, so that its trip
+// count is uniform).  Record i is global record gbase + i, sz bytes (its own block_size) for [d, d + sz) of the sorted stream, d = dest[gbase + i].
+// Outside [lo, hi): nothing to do ((P - 1) / P of the records).  Otherwise the stretch [max(d, lo), min(d + sz, hi)) goes to out at - lo, the
+// source advanced by the same clip: reads stay inside the record, writes inside [0, hi - lo).  misc: [0] |= 1 for a record whose
+// [d, d + sz) leaves [0, total] (nothing is copied); [1] += the bytes written.
+__global__ __launch_bounds__(256) void k_sort_scatter(const uint8_t *u, const uint64_t *off, uint64_t n, const uint64_t *dest, uint64_t gbase, uint64_t lo, uint64_t hi, uint64_t total,
+                                                      uint8_t *out, unsigned long long *misc) {
+    const uint32_t lane = threadIdx.x & 63u, sub = lane & 15u;
+    const uint64_t step = (((uint64_t)gridDim.x * blockDim.x) >> 6) << 2;
+    for (uint64_t j0 = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; j0 < n; j0 += step) {
+        const uint64_t j = j0 + (lane >> 4);
+        unsigned long long len = 0; bool bad = false;
+        if (j < n) {
+            const uint8_t *s = u + off[j];
+            const uint64_t sz = 4ull + rb32(s), d = dest[gbase + j];
+            if (d > total || sz > total - d) bad = true;
+            else {
+                const uint64_t a = max(d, lo), z = min(d + sz, hi);
+                if (a < z) {
+                    sort_copy16(s + (a - d), out + (a - lo), (uint32_t)(z - a), sub);
+                    if (sub == 0) len = z - a;
+                }
+            }
         }
-        if (tail + sub < sz) d[tail + sub] = s[tail + sub];
+        const unsigned long long bb = __ballot(bad);
+        len += __shfl_xor(len, 16); len += __shfl_xor(len, 32);
+        if (lane == 0) {
+            if (bb) atomicOr(misc, 1ull);
+            if (len) atomicAdd(misc + 1, len);
+        }
     }
 }
 
@@ -94,12 +142,17 @@ struct gce_sort {
     DevBuf rec, key, size, off; uint64_t rec_n = 0, n = 0;                            // resident: the records' bytes, key / size / offset of each
     DevBuf out; uint64_t out_n = 0;                                                   // the sorted stream (gce_sort_finish)
     DevBuf zs, zz, zf, zo;                                                            // a piece's deflate slots, sizes, offsets, packed members
+    // the output-range passes: no record bytes resident (rec_n counts them); after gce_sort_plan only dest; `out` is the pass buffer
+    bool passes = false;
+    DevBuf dest, pmisc; uint64_t total = 0, win_need = 0;                             // dest: 8 bytes per record; win_need: the device bytes a window took in the key pass
+    uint64_t p_lo = 0, p_hi = 0, p_g = 0; bool p_open = false; double p_scatter_s = 0;
 };
 
 static int sfail(gce_sort *b, int code, const std::string &m) { if (b) b->err = m; return code; }
 static int sort_oom(gce_sort *b, const char *what, uint64_t add) {
     char m[256];                                                                      // (the footprint first: a long `what` is cut off, not the formula)
-    snprintf(m, sizeof m, "out of device memory: the sort is in-core and needs about 2 x the inflated record bytes + 20 bytes per record + one window (%lld bytes live, budget %llu, %llu more for %s)",
+    snprintf(m, sizeof m, b->passes ? "out of device memory: the sort in output-range passes needs 8 bytes per record + one window + one pass of at least one BGZF member (about 44 bytes per record for its plan) (%lld bytes live, budget %llu, %llu more for %s)"
+                                    : "out of device memory: the sort is in-core and needs about 2 x the inflated record bytes + 20 bytes per record + one window (%lld bytes live, budget %llu, %llu more for %s)",
              __atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), (unsigned long long)b->budget, (unsigned long long)add, what);
     return sfail(b, GCE_ERR_OOM, m);
 }
@@ -125,6 +178,20 @@ static int sort_grow(gce_sort *b, DevBuf &buf, size_t need, size_t used, size_t 
 }
 // the slots of one deflated piece of `piece` input bytes
 static uint32_t sort_slot() { return 0xff00u + 0xff00u / 8 + 64; }
+// the device bytes of the four buffers gce_sort_read deflates a piece of pn members with, as DevBuf::ensure takes them
+static uint64_t sort_deflate_need(uint64_t pn) { return (pn * sort_slot() + 64) * 9 / 4 + pn * 14 + 2048; }
+static int sort_deflate_bufs(gce_sort *b, uint64_t piece_bytes) {
+    const uint64_t pn = (piece_bytes + 0xff00u - 1) / 0xff00u;
+    if (!sort_room(b, sort_deflate_need(pn))) return sort_oom(b, "deflating a piece of the output", sort_deflate_need(pn));
+    SCHK(b->zs.ensure((size_t)pn * sort_slot() + 64)); SCHK(b->zo.ensure((size_t)pn * sort_slot() + 64)); SCHK(b->zz.ensure(((size_t)pn + 1) * 4)); SCHK(b->zf.ensure(((size_t)pn + 1) * 8));
+    return GCE_OK;
+}
+// the device bytes a window holds (a window that grows holds its old inflated bytes beside the new ones for a moment: pass_grow)
+static uint64_t sort_win_need(const WinIdx &w, const DevBuf &tmp) {
+    uint64_t a = w.win.cap + tmp.cap;
+    for (const DevBuf *x : {&w.win, &w.off, &w.zc, &w.zdir, &w.zerr, &w.guess, &w.leave, &w.cnt, &w.base, &w.bad_of, &w.rmisc, &w.ctmp}) a += x->cap;
+    return a;
+}
 
 extern "C" {
 
@@ -143,7 +210,7 @@ void gce_sort_destroy(gce_sort *b) {
     (void)hipSetDevice(b->device);
     (void)hipStreamSynchronize(b->s);
     b->w.release();
-    for (DevBuf *x : {&b->tmp, &b->misc, &b->rec, &b->key, &b->size, &b->off, &b->out, &b->zs, &b->zz, &b->zf, &b->zo}) x->release();
+    for (DevBuf *x : {&b->tmp, &b->misc, &b->rec, &b->key, &b->size, &b->off, &b->out, &b->zs, &b->zz, &b->zf, &b->zo, &b->dest, &b->pmisc}) x->release();
     (void)hipStreamDestroy(b->s);
     delete b;
 }
@@ -151,8 +218,8 @@ const char *gce_sort_error(gce_sort *b) { return b ? b->err.c_str() : ""; }
 
 // the next piece of the file, as gce_bai_window takes it.  est_bytes: the caller's estimate of the whole file's inflated bytes (the members'
 // ISIZE totals so far scaled to the file size): the resident buffers are sized from it when they are first made, or grow.
-int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
-                    int32_t n_ref, int32_t last, uint64_t est_bytes) {
+static int sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                       int32_t n_ref, int32_t last, uint64_t est_bytes) {
     if (!b || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
@@ -178,43 +245,41 @@ int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_
         if (n1 >= SORT_MAX_RECORDS) return sfail(b, GCE_ERR_INVALID, "more than 2^32 - 16 records in one BAM file");
         // the estimates: the file's record bytes (never below what is known), and its records at the bytes per record seen so far, 1/16 added
         const uint64_t eb = std::max<uint64_t>(est_bytes, b->rec_n + add), en = (uint64_t)((double)n1 * ((double)eb / (double)(b->rec_n + add)));
-        if ((rc = sort_grow(b, b->rec, (size_t)(b->rec_n + add + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
+        if (!b->passes && (rc = sort_grow(b, b->rec, (size_t)(b->rec_n + add + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
         const size_t tn = (size_t)(en + en / 16 + 64);
         if ((rc = sort_grow(b, b->key, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' keys")) != GCE_OK) return rc;
         if ((rc = sort_grow(b, b->size, (size_t)n1 * 4, (size_t)b->n * 4, tn * 4, "the records' sizes")) != GCE_OK) return rc;
-        if ((rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
+        if (!b->passes && (rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
         hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.off.p, (int64_t)n_rec, start, b->rec_n, b->n, n_ref,
                            b->key.as<unsigned long long>(), b->size.as<uint32_t>(), b->off.as<uint64_t>(), b->misc.as<unsigned long long>());
         SCHK(hipGetLastError());
-        SCHK(hipMemcpyAsync(b->rec.as<uint8_t>() + b->rec_n, b->w.win.as<uint8_t>() + start, add, hipMemcpyDeviceToDevice, s));
+        if (!b->passes) SCHK(hipMemcpyAsync(b->rec.as<uint8_t>() + b->rec_n, b->w.win.as<uint8_t>() + start, add, hipMemcpyDeviceToDevice, s));
         b->rec_n += add; b->n = n1;
     }
-    return win_carry(b->w, s, total, end, b->err);
+    rc = win_carry(b->w, s, total, end, b->err);
+    b->win_need = std::max(b->win_need, sort_win_need(b->w, b->tmp));
+    return rc;
+}
+int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                    int32_t n_ref, int32_t last, uint64_t est_bytes) {
+    if (b && b->passes) return GCE_ERR_INVALID;
+    return sort_window(b, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, est_bytes);
+}
+// the key pass of the output-range passes: gce_sort_window without the record bytes and their offsets (12 bytes per record stay resident)
+int gce_sort_key_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, uint64_t est_bytes) {
+    if (!b || b->rec.p || b->dest.p) return GCE_ERR_INVALID;
+    b->passes = true;
+    return sort_window(b, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, est_bytes);
 }
 
-// after the last window: sort, scan, gather.  counts: records, unplaced records, descents; *bad_rec: the first record whose tid the header
-// does not have (-1: none; nothing is sorted then); *out_bytes: the sorted stream's bytes; times: seconds of the sort (keys, sizes, scan) and
-// of the gather kernel.  codes >= 0: the buffers gce_sort_read deflates pieces of up to piece_bytes with are made here, so that running out
-// of device memory is known before the caller opens its output.
-int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int64_t counts[3], int64_t *bad_rec, uint64_t *out_bytes, double times[2]) {
-    if (!b || n_ref < 0 || !counts || !bad_rec || !out_bytes || !times || codes > 1) return GCE_ERR_INVALID;
-    (void)hipSetDevice(b->device);
+// the order and where it puts every record: sidx[j] = the input record at place j, ssize[j] its size, dst[j] its byte offset in the sorted
+// stream (dst[n] = *total).  Keys and sizes are released on the way.
+static int sort_order(gce_sort *b, int32_t n_ref, ScopedBuf &sidx, ScopedBuf &ssize, ScopedBuf &dst, uint64_t *total_out) {
     hipStream_t s = b->s;
-    SCHK(hipStreamSynchronize(s));
-    b->w.release();                                                                   // (the last window is done with)
-    *bad_rec = -1; *out_bytes = 0; times[0] = times[1] = 0;
-    counts[0] = (int64_t)b->n; counts[1] = counts[2] = 0;
     const uint64_t n = b->n;
-    if (n == 0) return GCE_OK;
-    unsigned long long h[3];
-    SCHK(hipMemcpyAsync(h, b->misc.p, sizeof h, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
-    if (h[0] != ~0ull) { *bad_rec = (int64_t)h[0]; return GCE_OK; }
-    counts[1] = (int64_t)h[1]; counts[2] = (int64_t)h[2];
-    double t0 = mono_s();
     const unsigned nb = (unsigned)((n + 255) / 256);
     int end_bit = 33; for (uint32_t v = (uint32_t)n_ref; v; v >>= 1) end_bit++;
-    ScopedBuf sidx, ssize, dst;
-    int rc;
     {
         ScopedBuf idx, skey, st;
         if (!sort_room(b, n * 18)) return sort_oom(b, "the radix sort of the keys", n * 18);
@@ -236,6 +301,40 @@ int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_by
     SCHK(hipMemcpyAsync(&total, dst.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
     if (total != b->rec_n) return sfail(b, GCE_ERR_INVALID, "sort: the records' sizes do not add up to the resident stream");
     b->size.release();
+    *total_out = total;
+    return GCE_OK;
+}
+// after the last window, both ways: the counters of k_sort_keys.  *bad_rec >= 0: nothing is sorted
+static int sort_counts(gce_sort *b, int64_t counts[3], int64_t *bad_rec) {
+    hipStream_t s = b->s;
+    *bad_rec = -1;
+    counts[0] = (int64_t)b->n; counts[1] = counts[2] = 0;
+    if (b->n == 0) return GCE_OK;
+    unsigned long long h[3];
+    SCHK(hipMemcpyAsync(h, b->misc.p, sizeof h, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    if (h[0] != ~0ull) { *bad_rec = (int64_t)h[0]; return GCE_OK; }
+    counts[1] = (int64_t)h[1]; counts[2] = (int64_t)h[2];
+    return GCE_OK;
+}
+
+// after the last window: sort, scan, gather.  counts: records, unplaced records, descents; *bad_rec: the first record whose tid the header
+// does not have (-1: none; nothing is sorted then); *out_bytes: the sorted stream's bytes; times: seconds of the sort (keys, sizes, scan) and
+// of the gather kernel.  codes >= 0: the buffers gce_sort_read deflates pieces of up to piece_bytes with are made here, so that running out
+// of device memory is known before the caller opens its output.
+int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int64_t counts[3], int64_t *bad_rec, uint64_t *out_bytes, double times[2]) {
+    if (!b || b->passes || n_ref < 0 || !counts || !bad_rec || !out_bytes || !times || codes > 1) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    SCHK(hipStreamSynchronize(s));
+    b->w.release();                                                                   // (the last window is done with)
+    *out_bytes = 0; times[0] = times[1] = 0;
+    int rc = sort_counts(b, counts, bad_rec);
+    if (rc != GCE_OK || b->n == 0 || *bad_rec >= 0) return rc;
+    const uint64_t n = b->n;
+    double t0 = mono_s();
+    ScopedBuf sidx, ssize, dst;
+    uint64_t total = 0;
+    if ((rc = sort_order(b, n_ref, sidx, ssize, dst, &total)) != GCE_OK) return rc;
     times[0] = mono_s() - t0;
     if ((rc = sort_grow(b, b->out, (size_t)total + 64, 0, 0, "the sorted record bytes")) != GCE_OK) return rc;
     SCHK(hipMemsetAsync(b->out.as<uint8_t>() + total, 0, 64, s));                    // (the deflate kernels may look a few bytes ahead)
@@ -247,12 +346,106 @@ int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_by
     times[1] = mono_s() - t0;
     b->rec.release(); b->off.release();
     b->out_n = total; *out_bytes = total;
-    if (codes >= 0 && piece_bytes) {
-        const uint64_t pb = std::min<uint64_t>(piece_bytes, total), pn = (pb + 0xff00u - 1) / 0xff00u;
-        const uint64_t add = (pn * sort_slot() + 64) * 9 / 4 + pn * 14 + 2048;
-        if (!sort_room(b, add)) return sort_oom(b, "deflating a piece of the output", add);
-        SCHK(b->zs.ensure((size_t)pn * sort_slot() + 64)); SCHK(b->zo.ensure((size_t)pn * sort_slot() + 64)); SCHK(b->zz.ensure(((size_t)pn + 1) * 4)); SCHK(b->zf.ensure(((size_t)pn + 1) * 8));
+    if (codes >= 0 && piece_bytes) return sort_deflate_bufs(b, std::min<uint64_t>(piece_bytes, total));
+    return GCE_OK;
+}
+
+// after the last window of the key pass: sort and scan as gce_sort_finish, then the inverse (k_sort_dest) and the pass cuts.  counts / *bad_rec
+// as gce_sort_finish; *total: the sorted stream's bytes.  P = max(min_passes, 1), raised until dest + one window (what a window took in the
+// key pass) + the pass buffer + the deflate buffers of its largest piece fit the budget, 64 at most; *pass_bytes = ceil(total / P) rounded up
+// to a multiple of 0xff00, *n_passes = ceil(total / pass_bytes).  The pass buffer and the deflate buffers are made here, so that running out
+// of device memory is known before the caller opens its output.  *resident: the device bytes held from here on, a window's aside.
+int gce_sort_plan(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int32_t min_passes, int64_t counts[3], int64_t *bad_rec, uint64_t *total_out, int32_t *n_passes,
+                  uint64_t *pass_bytes, uint64_t *resident, double *plan_s) {
+    if (!b || !b->passes || b->dest.p || n_ref < 0 || !counts || !bad_rec || !total_out || !n_passes || !pass_bytes || !resident || !plan_s || codes > 1 || min_passes > 64) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    SCHK(hipStreamSynchronize(s));
+    b->w.release();                                                                   // (the plan's scratch takes its place; the passes make it again)
+    *total_out = 0; *n_passes = 0; *pass_bytes = 0; *resident = 0; *plan_s = 0;
+    int rc = sort_counts(b, counts, bad_rec);
+    if (rc != GCE_OK || b->n == 0 || *bad_rec >= 0) return rc;
+    const uint64_t n = b->n;
+    const double t0 = mono_s();
+    uint64_t total = 0;
+    {
+        ScopedBuf sidx, ssize, dst;
+        if ((rc = sort_order(b, n_ref, sidx, ssize, dst, &total)) != GCE_OK) return rc;
+        if ((rc = sort_grow(b, b->dest, (size_t)n * 8, 0, 0, "the records' destinations")) != GCE_OK) return rc;
+        hipLaunchKernelGGL(k_sort_dest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t *)sidx.p, (const uint64_t *)dst.p, n, b->dest.as<uint64_t>());
+        SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
     }
+    if (!b->pmisc.p) { if (!sort_room(b, 512)) return sort_oom(b, "the passes' counters", 512); SCHK(b->pmisc.ensure(64)); }
+    b->total = total;
+    // ---- the cuts: the smallest P from min_passes on whose pass fits
+    const uint64_t M = 0xff00u, slack = 65536;                                       // (slack: dev_exclusive_sum's scratch, allocator rounding)
+    const uint64_t live = (uint64_t)std::max<long long>(__atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), 0);
+    auto pass_need = [&](uint64_t pb) { return pb + 64 + 256 + (codes >= 0 && piece_bytes ? sort_deflate_need((std::min<uint64_t>(piece_bytes, pb) + M - 1) / M) : 0); };
+    uint64_t P = (uint64_t)std::max<int32_t>(min_passes, 1), pb = 0;
+    for (;; P++) {
+        pb = ((total + P - 1) / P + M - 1) / M * M;
+        if (!b->budget || live + b->win_need + slack + pass_need(pb) <= b->budget) break;
+        if (P == 64 || pb == M) return sort_oom(b, "a window and one pass of the output", b->win_need + slack + pass_need(pb));
+    }
+    *total_out = total; *pass_bytes = pb; *n_passes = (int32_t)((total + pb - 1) / pb);
+    if ((rc = sort_grow(b, b->out, (size_t)pb + 64, 0, 0, "one pass of the sorted record bytes")) != GCE_OK) return rc;
+    if (codes >= 0 && piece_bytes && (rc = sort_deflate_bufs(b, std::min<uint64_t>(piece_bytes, pb))) != GCE_OK) return rc;
+    *resident = (uint64_t)std::max<long long>(__atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), 0);
+    *plan_s = mono_s() - t0;
+    return GCE_OK;
+}
+
+// pass k of the output-range passes: bytes [lo, hi) of the sorted stream (lo a multiple of 0xff00) are collected in the pass buffer while the
+// file goes by once more, window by window, from its first byte; after gce_sort_pass_end, gce_sort_read hands them out (offsets from lo).
+int gce_sort_pass_begin(gce_sort *b, uint64_t lo, uint64_t hi) {
+    if (!b || !b->passes || !b->dest.p || b->p_open || lo >= hi || hi > b->total || lo % 0xff00u || hi - lo + 64 > b->out.cap) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    b->p_lo = lo; b->p_hi = hi; b->p_g = 0; b->p_scatter_s = 0; b->out_n = 0; b->p_open = true;
+    b->w.carry_n = 0;
+    SCHK(hipMemsetAsync(b->pmisc.p, 0, 64, s));
+    SCHK(hipMemsetAsync(b->out.as<uint8_t>() + (hi - lo), 0, 64, s));                // (the deflate kernels may look a few bytes ahead)
+    return GCE_OK;
+}
+int gce_sort_pass_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                         int32_t n_ref, int32_t last) {
+    if (!b || !b->p_open || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    {   // (as gce_sort_window)
+        uint64_t u_all = b->w.carry_n; for (int32_t k = 0; k < n_members; k++) u_all += usize[k];
+        uint64_t add = 0;
+        if (u_all + 64 > b->w.win.cap) add += (u_all + 64) * 27 / 16 + 256;
+        if (comp_bytes + 64 > b->w.zc.cap) add += (comp_bytes + 64) * 9 / 8 + 256;
+        if (add && !sort_room(b, add)) return sort_oom(b, "a window of the file", add);
+    }
+    uint64_t total = 0, n_rec = 0, end = 0;
+    int rc = win_inflate_index(b->w, b->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, b->err);
+    if (rc == GCE_ERR_OOM) return sort_oom(b, "a window of the file", 0);
+    if (rc != GCE_OK) return rc;
+    if (n_rec) {
+        if (n_rec > b->n - b->p_g) return sfail(b, GCE_ERR_INVALID, "the input changed while it was being sorted (more records than the key pass saw)");
+        const double t0 = mono_s();
+        hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)std::min<uint64_t>((n_rec + 15) / 16, 65535u)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.off.p, n_rec,
+                           (const uint64_t *)b->dest.p, b->p_g, b->p_lo, b->p_hi, b->total, b->out.as<uint8_t>(), b->pmisc.as<unsigned long long>());
+        SCHK(hipGetLastError()); SCHK(hipStreamSynchronize(s));
+        b->p_scatter_s += mono_s() - t0;
+        b->p_g += n_rec;
+    }
+    return win_carry(b->w, s, total, end, b->err);
+}
+// *scatter_s: the seconds of the pass's k_sort_scatter launches.  A pass that saw another record count than the key pass, a record outside
+// [0, total] or whose records did not write every byte of [lo, hi) once is GCE_ERR_INVALID.
+int gce_sort_pass_end(gce_sort *b, double *scatter_s) {
+    if (!b || !b->p_open) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    b->p_open = false;
+    unsigned long long h[2] = {0, 0};
+    SCHK(hipMemcpyAsync(h, b->pmisc.p, sizeof h, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
+    if (b->p_g != b->n || h[0] || h[1] != b->p_hi - b->p_lo) return sfail(b, GCE_ERR_INVALID, "the input changed while it was being sorted");
+    b->out_n = b->p_hi - b->p_lo;
+    if (scatter_s) *scatter_s = b->p_scatter_s;
     return GCE_OK;
 }
 

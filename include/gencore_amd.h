@@ -621,6 +621,28 @@ typedef struct gce_sort_run {
 } gce_sort_run;
 int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
                  size_t device_budget_bytes, gce_sort_run *out, char err[256]);
+/* gce_bam_sort for a file beyond its in-core limit, on ONE device (addition under ABI v3; gencore_amd/csrc/gce_sort.hpp): the same
+ * output, byte for byte.  device_budget_bytes: 0 = auto, GCE_PASS_BUDGET_FRACTION of the device's free memory when the call starts, as in
+ * gce_run_bam_passes.  With min_passes <= 1, gce_bam_sort is tried with that budget first, unless even the compressed file is beyond half of it
+ * (run->in_core = 1 when it wrote the output).  On its GCE_ERR_OOM, or with min_passes >= 2, the file is sorted in output-range passes: a key
+ * pass streams it and keeps key and size of every record (12 bytes per record + one window); the plan sorts the keys, scans the sizes and keeps
+ * the destination byte offset of every record in input order (8 bytes per record resident from then on; about 44 bytes per record at its
+ * peak); the sorted stream [0, total) is cut into P ranges of pass_bytes, P = max(min_passes, what the budget needs), at most 64,
+ * pass_bytes = ceil(total / P) rounded up to a multiple of 0xff00, n_passes = ceil(total / pass_bytes); every pass streams the file again
+ * from its first byte, the GPU moves the bytes that fall into the pass's range (a record that straddles a cut partly in each pass) and that
+ * range is written as gce_bam_sort writes it.  No sorted runs are spilled to host memory or disk and nothing is merged on the host; host
+ * buffers do not grow with the file.  GCE_ERR_OOM, with a message that states this footprint, before any output exists when the budget cannot
+ * hold the plan, or the destinations + one window + a pass of one BGZF member with its deflate buffers.  GCE_ERR_INVALID ("the input changed
+ * while it was being sorted") when a pass sees other records than the key pass saw.  Temporary file, rename and the other refusals:
+ * gce_bam_sort's, in its words.  *out as gce_bam_sort fills it: sort_s is the plan, gather_s the sum of the passes' k_sort_scatter launches,
+ * read_s / inflate_index_s / write_s sums over the key pass and every pass, peak_device_bytes the peak of the path that wrote the output. */
+typedef struct gce_sort_pass_run {
+    int32_t n_passes, in_core;                  /* in_core: gce_bam_sort wrote the output (then n_passes is 1, or 0 for a file without records) */
+    int64_t pass_bytes, resident_bytes;         /* resident_bytes: device bytes held while the passes run, a window's aside (in_core: the peak) */
+    double  key_pass_s, plan_s, pass_s[64];     /* pass_s[k]: pass k, its range written (in_core: [0] = sort + gather + write) */
+} gce_sort_pass_run;
+int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
+                        size_t device_budget_bytes, int32_t min_passes, gce_sort_run *out, gce_sort_pass_run *run, char err[256]);
 /* Live and peak device bytes of the engine allocations of the whole PROCESS (every engine, every thread); reset_peak != 0 restarts the peak at
  * the live count.  gce_run_bam_passes resets it on entry: its run->peak_device_bytes covers other engines working in the same process as well. */
 int gce_device_bytes(int64_t *live, int64_t *peak, int32_t reset_peak);

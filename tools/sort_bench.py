@@ -3,7 +3,11 @@
 shuffled) -> sort_bam at level -2 in fresh child processes (one warm-up, three timed, median) -> profiles/sort_bam.json with the stage times
 of gce_sort_run, the gather kernel's time from a rocprofv3 --kernel-trace --stats run of its own, and one device-to-device hipMemcpyAsync of
 the same bytes in the same process as the yardstick.
-    python tools/sort_bench.py [--workload cfg3] [--pairs 4000000] [--threads 0] [--dir DIR] [--out profiles/sort_bam.json]"""
+    python tools/sort_bench.py [--workload cfg3] [--pairs 4000000] [--threads 0] [--dir DIR] [--out profiles/sort_bam.json]
+--passes measures gce_bam_sort_passes on the same file instead: T(P) for P = 1 (in-core), 2 and 4 (sort_bam_passes with min_passes = P, one
+warm-up, --reps timed runs each, median) and k_sort_scatter's time from one rocprofv3 --kernel-trace --stats run at --min-passes, beside
+the same device-to-device copy -> profiles/sort_bam_passes.json.  An unsorted.bam already in --dir is used as it is.
+    python tools/sort_bench.py --passes [--min-passes 2] [--reps 3] [--dir DIR] [--out profiles/sort_bam_passes.json]"""
 import argparse
 import csv
 import ctypes as C
@@ -57,33 +61,28 @@ def aligner_order(batch):
 
 
 def child(args):
-    from gencore_amd.bamio import sort_bam
+    from gencore_amd.bamio import sort_bam, sort_bam_passes
     out = os.path.join(args.child, "sorted_%d.bam" % os.getpid())
-    r = sort_bam(os.path.join(args.child, "unsorted.bam"), out, device=0, threads=args.threads, level=-2)
+    if args.child_min_passes < 0:
+        r = sort_bam(os.path.join(args.child, "unsorted.bam"), out, device=0, threads=args.threads, level=-2)
+    else:
+        r = sort_bam_passes(os.path.join(args.child, "unsorted.bam"), out, device=0, threads=args.threads, level=-2, min_passes=args.child_min_passes)
     os.remove(out)
     r["d2d_copy_s"] = d2d_copy_s(r["inflated_bytes"])
     print(json.dumps(r), flush=True)
 
 
-def run_child(args, tmp, prefix=()):
-    p = subprocess.run(["timeout", "-k", "10", "600"] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--threads", str(args.threads)], stdout=subprocess.PIPE, universal_newlines=True)
+def run_child(args, tmp, prefix=(), min_passes=-1):
+    p = subprocess.run(["timeout", "-k", "10", "600"] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--threads", str(args.threads),
+                                                                      "--child-min-passes", str(min_passes)], stdout=subprocess.PIPE, universal_newlines=True)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:
         raise SystemExit("sort_bench: a child run failed (exit %d)" % p.returncode)
     return json.loads(lines[-1])
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="cfg3")
-    ap.add_argument("--pairs", type=int, default=4_000_000)
-    ap.add_argument("--threads", type=int, default=0)
-    ap.add_argument("--dir", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sort_bam.json"))
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
-    if args.child is not None:
-        return child(args)
+def make_input(args, src):
+    """the workload's stream in aligner order as a BAM file at src; -> the seconds it took to write"""
     import torch
     from gencore_amd import synth
     from gencore_amd.bamio import write_batch_as_bam
@@ -92,13 +91,77 @@ def main():
     tl = np.asarray(d.target_len, np.uint32)
     names = ["chr%d" % (i + 1) for i in range(len(tl))]
     unsorted = aligner_order(batch)
-    tmp = args.dir or tempfile.mkdtemp(prefix="gce_sort_")
-    src = os.path.join(tmp, "unsorted.bam")
     t0 = time.time()
     write_batch_as_bam(src, unsorted, tl, names, text="@HD\tVN:1.6\tSO:unsorted\n", threads=args.threads, level=1)
     make_s = time.time() - t0
     print("sort_bench: %d records written in aligner order (%.1f s)" % (unsorted.n, make_s), flush=True)
-    del d, batch, unsorted
+    return make_s
+
+
+def kernel_rows(prof, name):
+    rows = []
+    for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
+        rows += [r for r in csv.DictReader(open(f)) if name in r["Name"]]
+    if not rows:
+        raise SystemExit("sort_bench: no %s row in rocprofv3's *kernel_stats.csv under %s" % (name, prof))
+    return rows
+
+
+def passes_mode(args, tmp, src, make_s):
+    run_child(args, tmp, min_passes=1)                           # warm-up: page cache, code objects
+    med = lambda rs, k: sorted(r[k] for r in rs)[len(rs) // 2]
+    per_p = {}
+    for P in (1, 2, 4):
+        rs = [run_child(args, tmp, min_passes=P) for _ in range(args.reps)]
+        print("sort_bench: min_passes %d: total_s %s" % (P, [round(r["total_s"], 3) for r in rs]), flush=True)
+        r0 = rs[0]
+        assert r0["in_core"] == (1 if P == 1 else 0) and (P == 1 or r0["n_passes"] == P), r0
+        per_p[P] = dict(n_passes=r0["n_passes"], in_core=r0["in_core"], pass_bytes=r0["pass_bytes"], resident_bytes=r0["resident_bytes"], peak_device_bytes=r0["peak_device_bytes"],
+                        total_s=round(med(rs, "total_s"), 4), total_s_all=[round(r["total_s"], 4) for r in rs],
+                        stage_s_median={k: round(med(rs, k), 4) for k in ("read_s", "inflate_index_s", "sort_s", "gather_s", "write_s", "key_pass_s", "plan_s")},
+                        pass_s=[round(x, 4) for x in r0["pass_s"]], d2d_copy_s=med(rs, "d2d_copy_s"))
+    prof = os.path.join(tmp, "prof_passes")
+    rp = run_child(args, tmp, prefix=["rocprofv3", "--kernel-trace", "--stats", "-d", prof, "-o", "sort", "--output-format", "csv", "--"], min_passes=args.min_passes)
+    row = kernel_rows(prof, "k_sort_scatter")[0]
+    nbytes = rp["inflated_bytes"]
+    scatter_s = float(row["TotalDurationNs"]) * 1e-9
+    copy_s = per_p[1]["d2d_copy_s"]
+    res = dict(workload=args.workload, pairs=int(args.pairs), records=rp["n_records"], in_bam_bytes=os.path.getsize(src), inflated_bytes=nbytes, level=-2, reps=args.reps,
+               make_input_s=round(make_s, 2), T={str(P): per_p[P]["total_s"] for P in per_p}, runs={str(P): per_p[P] for P in per_p},
+               scatter_kernel=dict(source="rocprofv3 --kernel-trace --stats, a run of its own at min_passes %d" % args.min_passes, n_passes=rp["n_passes"], calls=int(row["Calls"]),
+                                   seconds=scatter_s, bytes_moved=2 * nbytes, gb_per_s=round(2 * nbytes / scatter_s / 1e9, 1),
+                                   note="all launches of all passes together move every record byte once; the launches also walk the records outside their pass's range"),
+               d2d_copy=dict(source="one hipMemcpyAsync device-to-device of inflated_bytes in the sorting process, best of 5", seconds=round(copy_s, 6),
+                             gb_per_s=round(2 * nbytes / copy_s / 1e9, 1)))
+    res["scatter_over_copy"] = round(res["scatter_kernel"]["gb_per_s"] / res["d2d_copy"]["gb_per_s"], 3)
+    json.dump(res, open(args.out, "w"), indent=1)
+    print(json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="cfg3")
+    ap.add_argument("--pairs", type=int, default=4_000_000)
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--dir", default=None)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--passes", action="store_true")
+    ap.add_argument("--min-passes", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--child-min-passes", type=int, default=-1)
+    args = ap.parse_args()
+    if args.child is not None:
+        return child(args)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sort_bam_passes.json" if args.passes else "sort_bam.json")
+    tmp = args.dir or tempfile.mkdtemp(prefix="gce_sort_")
+    src = os.path.join(tmp, "unsorted.bam")
+    make_s = 0.0
+    if not os.path.exists(src):
+        make_s = make_input(args, src)
+    if args.passes:
+        return passes_mode(args, tmp, src, make_s)
     run_child(args, tmp)                                         # warm-up: page cache, code objects
     runs = [run_child(args, tmp) for _ in range(3)]
     print("sort_bench: total_s of the timed runs: %s" % [round(r["total_s"], 3) for r in runs], flush=True)
@@ -106,11 +169,7 @@ def main():
     r0 = runs[0]
     prof = os.path.join(tmp, "prof")
     run_child(args, tmp, prefix=["rocprofv3", "--kernel-trace", "--stats", "-d", prof, "-o", "sort", "--output-format", "csv", "--"])
-    rows = []
-    for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
-        rows += [r for r in csv.DictReader(open(f)) if "k_sort_gather" in r["Name"]]
-    if not rows:
-        raise SystemExit("sort_bench: no k_sort_gather row in rocprofv3's *kernel_stats.csv under %s" % prof)
+    rows = kernel_rows(prof, "k_sort_gather")
     gather_s = float(rows[0]["AverageNs"]) * 1e-9
     nbytes = r0["inflated_bytes"]
     res = dict(workload=args.workload, pairs=int(args.pairs), records=r0["n_records"], n_descents=r0["n_descents"], in_bam_bytes=os.path.getsize(src), inflated_bytes=nbytes,

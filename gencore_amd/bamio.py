@@ -186,6 +186,43 @@ def sort_bam(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_bud
     return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceSortRun._fields_ if n != "pad"}
 
 
+def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):
+    """gce_sam_sort: SAM text in any order into the coordinate-sorted BAM on the GPU, the file sam_to_bam + sort_bam write, without the BAM in
+    between: the GPU turns the alignment lines into records (parse_sam) and sorts them.  window_bytes: text bytes per window, 0 = 64 MB, a value above 1 GB
+    is taken as 1 GB (line starts are 32-bit offsets into the window), and a window grows to hold one line; in-core only (sam_to_bam, then sort_bam_passes, take a file beyond device_budget_bytes).  Returns sort_bam's dict plus n_host_lines (the
+    lines with floating-point values, which the host re-parsed); raises GceError (and leaves no output) on failure."""
+    from .capi import GceSortRun
+    lib = capi.load_library()
+    r = GceSortRun()
+    nh = C.c_int64(0)
+    err = (C.c_char * 256)()
+    rc = lib.gce_sam_sort(str(sam).encode(), str(out).encode(), int(device), int(threads), int(level), int(window_bytes), int(device_budget_bytes), C.byref(r), C.byref(nh), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    d = {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceSortRun._fields_ if n != "pad"}
+    d["n_host_lines"] = int(nh.value)
+    return d
+
+
+def parse_sam(text, ref_names, device=0, out_cap=None):
+    """gce_sam_parse: the alignment lines of `text` (bytes, no `@` lines) as BAM records, made on the GPU.  Returns dict(records (bytes),
+    n_records, n_host_lines); raises GceError -- .bad_line is the first malformed line, counting from 0 over the lines that are records, and
+    .needed the bytes a too small out_cap should have been."""
+    lib = capi.load_library()
+    text = bytes(text)
+    names = (C.c_char_p * max(len(ref_names), 1))(*[n.encode() if isinstance(n, str) else n for n in ref_names])
+    cap = len(text) * 2 + 64 * (text.count(b"\n") + 2) if out_cap is None else int(out_cap)
+    out = np.empty(max(cap, 1), np.uint8)
+    ob, nr, nh, bad = C.c_size_t(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+    err = (C.c_char * 256)()
+    rc = lib.gce_sam_parse(int(device), text, len(text), len(ref_names), names, out.ctypes.data, cap, C.byref(ob), C.byref(nr), C.byref(nh), C.byref(bad), err)
+    if rc != 0:
+        e = GceError(rc, err.value.decode(errors="replace"))
+        e.bad_line, e.needed = int(bad.value), int(ob.value)
+        raise e
+    return dict(records=out[:ob.value].tobytes(), n_records=int(nr.value), n_host_lines=int(nh.value))
+
+
 def sort_bam_passes(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0, min_passes=0):
     """gce_bam_sort_passes: sort_bam for a file of any size: in-core when that fits device_budget_bytes (0 = auto, a fraction of the free device
     memory) and min_passes <= 1, otherwise in output-range passes over the file (at least min_passes of them); the output's bytes are

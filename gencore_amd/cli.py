@@ -17,6 +17,8 @@ Flags marked [gencore_amd] are not the reference's; every other flag, default an
 --sort (not the reference's) takes a BAM in any order, as an aligner writes it: the GPU sorts it by coordinate into a temporary BAM first
 (what `samtools sort` does in front of the reference), and the run reads that file.  --device_memory bounds the sort as it bounds the run: a
 file that does not fit is sorted in output-range passes over the input.
+--sort_sam (not the reference's) takes SAM text in any order, an aligner's output as it is: the GPU turns its lines into BAM records and sorts
+them into the temporary BAM that --sort would make, without a BAM written in between.  In-core only, within --device_memory.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -81,6 +83,8 @@ def build_parser():
                                             "<output>.bai (BAI, SAMv1 5.2), on the first of --devices. Off by default.")
     a("--sort", action="store_true", help="[gencore_amd] the input BAM is not coordinate-sorted: sort it on the GPU first (on the first of --devices, into a "
                                            "temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
+    a("--sort_sam", action="store_true", help="[gencore_amd] the input is SAM text that is not coordinate-sorted: parse and sort it on the GPU first (on the first of "
+                                               "--devices, into a temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). Default 6.")
     return p
@@ -104,11 +108,19 @@ def validate(o):
         err("input should be specified by --in1")
     if o.sort and o.input == "-":
         err("--sort needs an input file, not STDIN")
+    if o.sort_sam and not o.sort and o.input == "-":
+        err("--sort_sam needs an input file, not STDIN")
     check_file_valid(o.input)
     if o.sort:
         with open(o.input, "rb") as f:
             if f.read(2) != b"\x1f\x8b":
                 err("--sort needs BAM input, not SAM text")
+    if o.sort and o.sort_sam:
+        err("--sort and --sort_sam cannot be combined")
+    if o.sort_sam:
+        with open(o.input, "rb") as f:
+            if f.read(2) == b"\x1f\x8b":
+                err("--sort_sam needs SAM text input, not BAM")
     if o.ref.endswith(".gz"):
         raise UsageError("reference fasta file should not be compressed.\nplease unzip %s and try again." % o.ref)
     checks = [
@@ -179,16 +191,17 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes
+    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = None
     try:
-        if o.sort:                                                          # the runners below read the sorted temporary file, unchanged
+        if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged
             import tempfile
             fd, sorted_tmp = tempfile.mkstemp(suffix=".bam", prefix="gencore_sort_", dir=None if o.output == "-" else (os.path.dirname(os.path.abspath(o.output))))
             os.close(fd)
-            sort_bam_passes(o.input, sorted_tmp, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
+            sorter = sort_bam_passes if o.sort else sort_sam               # (--sort_sam: the same file, made from text; in-core only)
+            sorter(o.input, sorted_tmp, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
             o.input = sorted_tmp
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None

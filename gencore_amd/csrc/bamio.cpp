@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -2540,6 +2541,9 @@ int gce_sort_pass_begin(gce_sort *b, uint64_t lo, uint64_t hi);
 int gce_sort_pass_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                          int32_t n_ref, int32_t last);
 int gce_sort_pass_end(gce_sort *b, double *scatter_s);
+int gce_sort_sam_contigs(gce_sort *b, int32_t n_ref, const char *const *ref_name);
+int gce_sort_sam_window(gce_sort *b, const char *text, size_t n, int32_t n_ref, uint64_t est_bytes, int64_t *n_host_lines, int64_t *bad_line, uint64_t *bad_start, double *parse_s,
+                        uint64_t *resident_bytes);
 }  // extern "C" (declarations)
 extern "C++" {
 namespace {
@@ -2570,11 +2574,11 @@ struct SortJob {
         if (code != GCE_OK && tmp_made) unlink(tmp.c_str());
         if (fd >= 0) { ::close(fd); fd = -1; }
     }
-    int open_input(const char *in_path, const char *out_path, int threads, int lv, uint64_t wb, int32_t dev) {
-        level = lv; window_bytes = wb; device = dev;
+    // the input opened, the temporary name made, an output that is the input refused.  who: the entry point; what: the input's kind
+    int open_paths(const char *in_path, const char *out_path, const char *who, const char *what) {
         fd = open(in_path, O_RDONLY);
-        if (fd < 0) return fail(GCE_ERR_INVALID, "cannot open the input BAM");
-        if (fstat(fd, &st) != 0 || st.st_size < 0) return fail(GCE_ERR_INVALID, "cannot stat the input BAM");
+        if (fd < 0) return fail(GCE_ERR_INVALID, std::string("cannot open the input ") + what);
+        if (fstat(fd, &st) != 0 || st.st_size < 0) return fail(GCE_ERR_INVALID, std::string("cannot stat the input ") + what);
         fsz = (uint64_t)st.st_size;
         tmp = std::string(out_path) + ".tmp" + std::to_string((long long)getpid());
         {   // the output may not be the input (by name or by file)
@@ -2583,8 +2587,13 @@ struct SortJob {
             char *ri = realpath(in_path, nullptr), *ro = realpath(out_path, nullptr);
             if (ri && ro && strcmp(ri, ro) == 0) same = true;
             free(ri); free(ro);
-            if (same) return fail(GCE_ERR_INVALID, "the output path is the input file: gce_bam_sort does not sort in place");
+            if (same) return fail(GCE_ERR_INVALID, std::string("the output path is the input file: ") + who + " does not sort in place");
         }
+        return GCE_OK;
+    }
+    int open_input(const char *in_path, const char *out_path, int threads, int lv, uint64_t wb, int32_t dev) {
+        level = lv; window_bytes = wb; device = dev;
+        { const int rc = open_paths(in_path, out_path, "gce_bam_sort", "BAM"); if (rc != GCE_OK) return rc; }
         { uint8_t m2[4] = {0, 0, 0, 0}; const bool got = fsz >= 4 && pread(fd, m2, 4, 0) == 4;
           if (fsz > 0 && !(got && m2[0] == 0x1f && m2[1] == 0x8b)) return fail(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
           if (fsz < 18 || m2[2] != 8 || !(m2[3] & 4)) return fail(GCE_ERR_INVALID, "not a BGZF file"); }
@@ -2718,6 +2727,107 @@ int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int 
     out->sort_s = times[0]; out->gather_s = times[1];
     out->n_records = counts[0]; out->n_no_coor = counts[1]; out->n_descents = counts[2]; out->inflated_bytes = (int64_t)total;
     // ---- rule F
+    const double t0 = now_s();
+    if ((rc = j.begin_output(total)) != GCE_OK || (rc = j.write_range(total)) != GCE_OK || (rc = j.end_output(out_path, &out->out_bytes)) != GCE_OK) return done(rc);
+    out->write_s = now_s() - t0;
+    { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); out->peak_device_bytes = pk; }
+    out->total_s = now_s() - t_start;
+    return done(GCE_OK);
+}
+
+// SAM text in any order into the coordinate-sorted BAM, file to file.  Replaces: gce_sam_to_bam (host threads, the whole text
+// and the whole record stream in host memory, a BAM written and read again) in front of gce_bam_sort -- what `samtools sort` does with an
+// aligner's SAM output in front of the reference.  The text is read in windows cut at their last line feed; the `@` lines make the header as
+// gce_sam_to_bam makes it, then rule H; the alignment lines become records on the GPU (gce_sort_sam_window), behind the resident ones; from
+// there on it is gce_bam_sort.
+int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, gce_sort_run *out, int64_t *n_host_lines,
+                 char err[256]) {
+    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
+    seterr("");
+    if (!in_path || !out_path || !out || !n_host_lines) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    memset(out, 0, sizeof *out); *n_host_lines = 0;
+    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    const double t_start = now_s();
+    SortJob j;
+    auto done = [&](int code) { j.close_all(code); seterr(j.msg.c_str()); return code; };
+    j.level = level; j.device = device; j.window_bytes = window_bytes; j.T = threads > 0 ? threads : default_threads();
+    int rc = j.open_paths(in_path, out_path, "gce_sam_sort", "SAM");
+    if (rc != GCE_OK) return done(rc);
+    { uint8_t m2[2] = {0, 0}; if (j.fsz >= 2 && pread(j.fd, m2, 2, 0) == 2 && m2[0] == 0x1f && m2[1] == 0x8b) return done(j.fail(GCE_ERR_INVALID, "gce_sam_sort reads SAM text, not BAM")); }
+    (void)gce_device_bytes(nullptr, nullptr, 1);
+    if ((rc = gce_sort_create(device, device_budget_bytes, &j.b)) != GCE_OK) return done(j.fail(rc, "no HIP device"));
+    const uint64_t W = window_bytes ? std::min<uint64_t>(window_bytes, (uint64_t)1 << 30) : ((uint64_t)64 << 20), LONGEST = (uint64_t)256 << 20;
+    std::unique_ptr<Pinned> buf(new Pinned());                                       // the window: what the last one left over, then the next piece of the file
+    uint64_t have = 0, at = 0, base = 0, text_seen = 0, rec_bytes = 0;                              // base: the file offset of buf[0]
+    bool in_header = true; std::string text; std::vector<std::string> names; std::vector<uint32_t> lens; int32_t n_ref = 0;
+    // the line that starts at file offset `o`, counting from 1 over the file (an error's path only: the file is read once more up to there)
+    auto line_number = [&](uint64_t o) {
+        long long ln = 1; std::vector<char> pb((size_t)1 << 20);
+        for (uint64_t a = 0; a < o;) { const ssize_t g = pread(j.fd, pb.data(), (size_t)std::min<uint64_t>(pb.size(), o - a), (off_t)a); if (g <= 0) break; ln += (long long)std::count(pb.data(), pb.data() + g, '\n'); a += (uint64_t)g; }
+        return ln;
+    };
+    for (bool last = j.fsz == 0; ;) {
+        double t0 = now_s();
+        if (!last) {
+            const uint64_t want = std::min<uint64_t>(W, j.fsz - at);
+            if (have + want + 64 > buf->cap) {
+                std::unique_ptr<Pinned> nb(new Pinned());
+                if (!nb->ensure((size_t)(have + want + 64))) return done(j.fail(GCE_ERR_OOM, "out of pinned host memory"));
+                if (have) memcpy(nb->p, buf->p, (size_t)have);
+                buf.swap(nb);
+            }
+            for (uint64_t g = 0; g < want;) { const ssize_t r = pread(j.fd, buf->p + have + g, (size_t)(want - g), (off_t)(at + g)); if (r <= 0) return done(j.fail(GCE_ERR_INVALID, "cannot read the input SAM")); g += (uint64_t)r; }
+            have += want; at += want; last = at >= j.fsz;
+        }
+        const char *cur = (const char *)buf->p;
+        uint64_t lim = have;
+        if (!last) {
+            const char *nl = have ? (const char *)memrchr(cur, '\n', (size_t)have) : nullptr;
+            lim = nl ? (uint64_t)(nl - cur) + 1 : 0;
+            if (!nl && have > LONGEST) return done(j.fail(GCE_ERR_INVALID, "SAM line longer than 256 MB"));
+        }
+        out->read_s += now_s() - t0;
+        uint64_t p = 0;
+        if (in_header) {
+            while (p < lim && cur[p] == '@') { const char *q = (const char *)memchr(cur + p, '\n', (size_t)(lim - p)); const uint64_t z = q ? (uint64_t)(q - cur) + 1 : lim; text.append(cur + p, (size_t)(z - p)); if (!q) text.push_back('\n'); p = z; }
+            if (p < lim || last) {
+                in_header = false;
+                if (!samtext::parse_header_text(text, names, lens)) return done(j.fail(GCE_ERR_INVALID, "bad @SQ line"));
+                n_ref = (int32_t)lens.size(); out->n_ref = n_ref; j.n_ref = n_ref;
+                const std::string ht = sort_header_text((const uint8_t *)text.data(), text.size());      // rule H
+                auto put32 = [&](uint32_t x) { const uint8_t *q = (const uint8_t *)&x; j.hdr.insert(j.hdr.end(), q, q + 4); };
+                j.hdr.assign({'B', 'A', 'M', 1});
+                put32((uint32_t)ht.size()); j.hdr.insert(j.hdr.end(), ht.begin(), ht.end());
+                put32((uint32_t)lens.size());
+                for (size_t r = 0; r < lens.size(); r++) { put32((uint32_t)names[r].size() + 1); j.hdr.insert(j.hdr.end(), names[r].begin(), names[r].end()); j.hdr.push_back(0); put32(lens[r]); }
+                std::vector<const char *> np; for (const std::string &x : names) np.push_back(x.c_str());
+                if ((rc = gce_sort_sam_contigs(j.b, n_ref, np.data())) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+            }
+        }
+        if (!in_header && p < lim) {
+            // the whole file's record bytes, from the records the text so far gave (the first window: unknown, the buffers hold just that window)
+            const uint64_t est = text_seen ? (uint64_t)((double)rec_bytes * ((double)j.fsz / (double)text_seen)) : 0;
+            text_seen += lim - p;
+            int64_t bad = -1; uint64_t bad_start = 0; double ps = 0;
+            rc = gce_sort_sam_window(j.b, cur + p, (size_t)(lim - p), n_ref, est, n_host_lines, &bad, &bad_start, &ps, &rec_bytes);
+            out->inflate_index_s += ps;                                              // (the parse kernels and the host patch; the copy of the text, the buffers' growth and k_sort_keys are in total_s only)
+            if (rc != GCE_OK) {
+                std::string m = gce_sort_error(j.b);
+                if (bad >= 0) m += " (line " + std::to_string(line_number(base + p + bad_start)) + ")";
+                return done(j.fail(rc, m));
+            }
+        }
+        if (lim) { if (lim < have) memmove(buf->p, buf->p + lim, (size_t)(have - lim)); have -= lim; base += lim; }
+        if (last) break;
+    }
+    buf.reset();
+    // ---- sort, scan, gather: gce_bam_sort from here on
+    j.set_pieces();
+    int64_t counts[3] = {0, 0, 0}, bad = -1; uint64_t total = 0; double times[2] = {0, 0};
+    if ((rc = gce_sort_finish(j.b, n_ref, j.codes, j.piece, counts, &bad, &total, times)) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+    if (bad >= 0) return done(j.fail(GCE_ERR_INVALID, "a record names a contig the header does not have"));
+    out->sort_s = times[0]; out->gather_s = times[1];
+    out->n_records = counts[0]; out->n_no_coor = counts[1]; out->n_descents = counts[2]; out->inflated_bytes = (int64_t)total;
     const double t0 = now_s();
     if ((rc = j.begin_output(total)) != GCE_OK || (rc = j.write_range(total)) != GCE_OK || (rc = j.end_output(out_path, &out->out_bytes)) != GCE_OK) return done(rc);
     out->write_s = now_s() - t0;

@@ -1349,4 +1349,5 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_bamdev.hpp"
 #include "gce_passes.hpp"
 #include "gce_bai.hpp"
+#include "gce_samdev.hpp"
 #include "gce_sort.hpp"

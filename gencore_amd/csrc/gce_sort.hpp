@@ -146,12 +146,15 @@ struct gce_sort {
     bool passes = false;
     DevBuf dest, pmisc; uint64_t total = 0, win_need = 0;                             // dest: 8 bytes per record; win_need: the device bytes a window took in the key pass
     uint64_t p_lo = 0, p_hi = 0, p_g = 0; bool p_open = false; double p_scatter_s = 0;
+    // SAM text in (gce_sam_sort, gce_samdev.hpp): the window is text, its records are written straight into `rec`
+    bool sam_text = false; SamDev sam;
 };
 
 static int sfail(gce_sort *b, int code, const std::string &m) { if (b) b->err = m; return code; }
 static int sort_oom(gce_sort *b, const char *what, uint64_t add) {
     char m[256];                                                                      // (the footprint first: a long `what` is cut off, not the formula)
-    snprintf(m, sizeof m, b->passes ? "out of device memory: the sort in output-range passes needs 8 bytes per record + one window + one pass of at least one BGZF member (about 44 bytes per record for its plan) (%lld bytes live, budget %llu, %llu more for %s)"
+    snprintf(m, sizeof m, b->sam_text ? "out of device memory: SAM text is sorted in-core only (else gce_sam_to_bam, then gce_bam_sort_passes): 2 x the record bytes + 20 per record + a window of 2 per text byte + 41 per line (%lld live, budget %llu, %llu more for %s)" :
+                          b->passes ? "out of device memory: the sort in output-range passes needs 8 bytes per record + one window + one pass of at least one BGZF member (about 44 bytes per record for its plan) (%lld bytes live, budget %llu, %llu more for %s)"
                                     : "out of device memory: the sort is in-core and needs about 2 x the inflated record bytes + 20 bytes per record + one window (%lld bytes live, budget %llu, %llu more for %s)",
              __atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), (unsigned long long)b->budget, (unsigned long long)add, what);
     return sfail(b, GCE_ERR_OOM, m);
@@ -209,7 +212,7 @@ void gce_sort_destroy(gce_sort *b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     (void)hipStreamSynchronize(b->s);
-    b->w.release();
+    b->w.release(); b->sam.release();
     for (DevBuf *x : {&b->tmp, &b->misc, &b->rec, &b->key, &b->size, &b->off, &b->out, &b->zs, &b->zz, &b->zf, &b->zo, &b->dest, &b->pmisc}) x->release();
     (void)hipStreamDestroy(b->s);
     delete b;
@@ -273,6 +276,69 @@ int gce_sort_key_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_
     return sort_window(b, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, est_bytes);
 }
 
+// SAM text in (gce_sam_sort): the contig names once, then window after window of whole alignment lines (host memory, n < 2^32).  The lines
+// become BAM records on the device (gce_samdev.hpp), written behind the resident records; their starts are what w.off is to gce_sort_window.
+// *bad_line >= 0: the window's first bad line (counting its record lines from 0), *bad_start its first byte in text, the error line_to_bam's
+// message for it; nothing of the window is kept.  *n_host_lines: the lines the host re-parsed (floating-point values); it and *parse_s are
+// added to.  *resident_bytes: the record bytes held so far.
+int gce_sort_sam_contigs(gce_sort *b, int32_t n_ref, const char *const *ref_name) {
+    if (!b || n_ref < 0 || (n_ref && !ref_name) || b->passes) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    b->sam_text = true;
+    std::vector<std::string> names; for (int32_t k = 0; k < n_ref; k++) names.emplace_back(ref_name[k] ? ref_name[k] : "");
+    uint64_t nb = 0; for (const std::string &x : names) nb += x.size() + 8;
+    if (!sort_room(b, nb + nb / 4 + 1024)) return sort_oom(b, "the contig names", nb + nb / 4 + 1024);
+    const int rc = sam_contigs(b->sam, b->s, names, b->err);
+    return rc == GCE_ERR_OOM ? sort_oom(b, "the contig names", 0) : rc;
+}
+int gce_sort_sam_window(gce_sort *b, const char *text, size_t n, int32_t n_ref, uint64_t est_bytes, int64_t *n_host_lines, int64_t *bad_line, uint64_t *bad_start, double *parse_s,
+                        uint64_t *resident_bytes) {
+    if (!b || !resident_bytes || !b->sam_text || b->passes || (n && !text) || n >= 0xFFFFFF00ull || !n_host_lines || !bad_line || !bad_start || !parse_s) return GCE_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    hipStream_t s = b->s;
+    SamDev &d = b->sam;
+    *bad_line = -1; *bad_start = 0;
+    if (!b->misc.p) {
+        if (!sort_room(b, 512)) return sort_oom(b, "the sort's counters", 512);
+        SCHK(b->misc.ensure(64));
+        const unsigned long long init[3] = {~0ull, 0ull, 0ull};
+        SCHK(hipMemcpyAsync(b->misc.p, init, sizeof init, hipMemcpyHostToDevice, s)); SCHK(hipStreamSynchronize(s));
+    }
+    const double k0 = d.kernel_s;
+    auto grown = [&](uint64_t need) { const uint64_t held = d.held(); return need > held ? need - held : 0; };
+    { const uint64_t add = grown(sam_win_need(n, 0)); if (add && !sort_room(b, add)) return sort_oom(b, "a window of SAM text", add); }
+    int rc = sam_lines(d, b->tmp, s, text, n, b->err);
+    if (rc == GCE_ERR_OOM) return sort_oom(b, "a window of SAM text", 0);
+    if (rc != GCE_OK) return rc;
+    { const uint64_t add = grown(sam_win_need(n, d.nl)); if (add && !sort_room(b, add)) return sort_oom(b, "the lines of a window of SAM text", add); }
+    rc = sam_sizes(d, b->tmp, s, b->err);
+    if (rc == GCE_ERR_OOM) return sort_oom(b, "the lines of a window of SAM text", 0);
+    if (rc != GCE_OK) return rc;
+    if (d.n_host) { const uint64_t add = (d.host_bytes + d.n_host * 8 + 64) * 9 / 8 + 512; if (add > d.hstage.cap + d.hsoff.cap && !sort_room(b, add)) return sort_oom(b, "the host's records of the lines with floating-point values", add); }
+    if (d.bad >= 0) { *bad_line = d.bad; *bad_start = d.bad_start; *parse_s += d.kernel_s - k0; return sfail(b, GCE_ERR_INVALID, sam_line_message(d, text, n, d.bad_start)); }
+    const uint64_t n_rec = d.nl, add = d.total;
+    if (n_rec) {
+        const uint64_t n1 = b->n + n_rec;
+        if (n1 >= SORT_MAX_RECORDS) return sfail(b, GCE_ERR_INVALID, "more than 2^32 - 16 records in one SAM file");
+        const uint64_t eb = std::max<uint64_t>(est_bytes, b->rec_n + add), en = (uint64_t)((double)n1 * ((double)eb / (double)(b->rec_n + add)));
+        if ((rc = sort_grow(b, b->rec, (size_t)(b->rec_n + add + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
+        const size_t tn = (size_t)(en + en / 16 + 64);
+        if ((rc = sort_grow(b, b->key, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' keys")) != GCE_OK) return rc;
+        if ((rc = sort_grow(b, b->size, (size_t)n1 * 4, (size_t)b->n * 4, tn * 4, "the records' sizes")) != GCE_OK) return rc;
+        if ((rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
+        uint8_t *dst = b->rec.as<uint8_t>() + b->rec_n;
+        if ((rc = sam_emit(d, s, text, dst, b->err)) != GCE_OK) return rc;
+        hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)dst, (const uint64_t *)d.roff.p, (int64_t)n_rec, (uint64_t)0, b->rec_n, b->n, n_ref,
+                           b->key.as<unsigned long long>(), b->size.as<uint32_t>(), b->off.as<uint64_t>(), b->misc.as<unsigned long long>());
+        SCHK(hipGetLastError()); SCHK(hipStreamSynchronize(s));
+        b->rec_n += add; b->n = n1;
+    }
+    *n_host_lines += (int64_t)d.n_host; *parse_s += d.kernel_s - k0;
+    b->win_need = std::max(b->win_need, d.held());
+    *resident_bytes = b->rec_n;
+    return GCE_OK;
+}
+
 // the order and where it puts every record: sidx[j] = the input record at place j, ssize[j] its size, dst[j] its byte offset in the sorted
 // stream (dst[n] = *total).  Keys and sizes are released on the way.
 static int sort_order(gce_sort *b, int32_t n_ref, ScopedBuf &sidx, ScopedBuf &ssize, ScopedBuf &dst, uint64_t *total_out) {
@@ -326,7 +392,7 @@ int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_by
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
     SCHK(hipStreamSynchronize(s));
-    b->w.release();                                                                   // (the last window is done with)
+    b->w.release(); b->sam.release();                                                 // (the last window is done with)
     *out_bytes = 0; times[0] = times[1] = 0;
     int rc = sort_counts(b, counts, bad_rec);
     if (rc != GCE_OK || b->n == 0 || *bad_rec >= 0) return rc;

@@ -643,6 +643,30 @@ typedef struct gce_sort_pass_run {
 } gce_sort_pass_run;
 int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
                         size_t device_budget_bytes, int32_t min_passes, gce_sort_run *out, gce_sort_pass_run *run, char err[256]);
+/* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
+ * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
+ * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;
+ * a last line may lack its line feed, a '\r' in front of a line feed is dropped, empty lines and lines of one '\r' are no records.
+ * ref_name[0, n_ref): the contigs in the header's order.  out receives the BAM records (block_size first) of the lines, in line order and back
+ * to back: the bytes gce_sam_to_bam writes for them.  *n_records: the lines that became records; *n_host_lines: those of them that hold an `f`,
+ * `d` or `B:f` value, which the host re-parsed for strtof / strtod's rounding -- no other line is parsed on the host.  GCE_ERR_INVALID with the
+ * host parser's message for a malformed line: *bad_line is the first one, counting from 0 over the lines that are records (-1 otherwise) and
+ * nothing is written.  GCE_ERR_OOM when out_cap is too small: *out_bytes is the size needed. */
+int gce_sam_parse(int32_t device, const char *text, size_t n, int32_t n_ref, const char *const *ref_name, void *out, size_t out_cap,
+                  size_t *out_bytes, int64_t *n_records, int64_t *n_host_lines, int64_t *bad_line, char err[256]);
+/* SAM text in any order into the coordinate-sorted BAM on ONE device, file to file (addition under ABI v3).
+ * Replaces: gce_sam_to_bam followed by gce_bam_sort -- the `samtools sort` of an aligner's SAM output that the reference's README asks for --
+ * and writes the same file, byte for byte, for every level, without the intermediate BAM: the text is read in windows of window_bytes (0 = 64 MB;
+ * a window grows to hold one line, "SAM line longer than 256 MB" beyond that; values above 1 GB are taken as 1 GB) cut at their last line feed,
+ * the `@` lines give the header as gce_sam_to_bam makes it (then rule H), the GPU turns the alignment lines into records behind the resident ones
+ * (gce_sam_parse's kernels) and sorts as gce_bam_sort does (rules S / R / F, temporary file and rename, budget checks).  Host buffers do not
+ * grow with the file.  In-core only: GCE_ERR_OOM before any output, with a message that states the footprint and names the way out
+ * (gce_sam_to_bam, then gce_bam_sort_passes).  A malformed line: the host parser's message followed by " (line N)", N counting from 1 over the
+ * file, header lines included.  A file that starts with the gzip magic: "gce_sam_sort reads SAM text, not BAM".  A failed call leaves neither an
+ * output nor a temporary file.  *out as gce_bam_sort fills it; inflate_index_s: the parse kernels and the host's patch of the lines counted in
+ * *n_host_lines (gce_sam_parse) -- not the copy of the text to the device, the growth of the resident buffers or the keys, which total_s holds. */
+int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
+                 size_t device_budget_bytes, gce_sort_run *out, int64_t *n_host_lines, char err[256]);
 /* Live and peak device bytes of the engine allocations of the whole PROCESS (every engine, every thread); reset_peak != 0 restarts the peak at
  * the live count.  gce_run_bam_passes resets it on entry: its run->peak_device_bytes covers other engines working in the same process as well. */
 int gce_device_bytes(int64_t *live, int64_t *peak, int32_t reset_peak);

@@ -7,13 +7,20 @@ the same bytes in the same process as the yardstick.
 --passes measures gce_bam_sort_passes on the same file instead: T(P) for P = 1 (in-core), 2 and 4 (sort_bam_passes with min_passes = P, one
 warm-up, --reps timed runs each, median) and k_sort_scatter's time from one rocprofv3 --kernel-trace --stats run at --min-passes, beside
 the same device-to-device copy -> profiles/sort_bam_passes.json.  An unsorted.bam already in --dir is used as it is.
-    python tools/sort_bench.py --passes [--min-passes 2] [--reps 3] [--dir DIR] [--out profiles/sort_bam_passes.json]"""
+    python tools/sort_bench.py --passes [--min-passes 2] [--reps 3] [--dir DIR] [--out profiles/sort_bam_passes.json]
+--sam measures gce_sam_sort: the same stream as SAM text (bam_to_sam of unsorted.bam -> unsorted.sam), sort_sam against the
+composition sam_to_bam (level 1, 16 threads) + sort_bam, both at level -2.  Every run is a fresh child process under its own time limit; the
+two variants are interleaved, one warm-up and --reps timed runs each, medians.  One rocprofv3 --kernel-trace --stats run of sort_sam in a
+process of its own gives the k_sam_* kernels' times and the parse rate in text bytes per second -> profiles/sort_sam.json.  --lib PATH: the
+composition's children load that build of the library (the parent commit's, for the yardstick); sort_sam always runs this tree's.
+    python tools/sort_bench.py --sam [--reps 3] [--lib PATH] [--dir DIR] [--out profiles/sort_sam.json]"""
 import argparse
 import csv
 import ctypes as C
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -72,9 +79,35 @@ def child(args):
     print(json.dumps(r), flush=True)
 
 
-def run_child(args, tmp, prefix=(), min_passes=-1):
+def child_sam(args):
+    """one variant of --sam on unsorted.sam: `sort_sam`, or `compose` = sam_to_bam (level 1, 16 threads) + sort_bam; both write level -2"""
+    from gencore_amd.bamio import sam_to_bam, sort_bam, sort_sam
+    sam = os.path.join(args.child, "unsorted.sam")
+    out = os.path.join(args.child, "sorted_%d.bam" % os.getpid())
+    t0 = time.perf_counter()
+    if args.child_sam == "sort_sam":
+        r = sort_sam(sam, out, device=0, threads=args.threads, level=-2)
+        r["wall_s"] = time.perf_counter() - t0
+    else:
+        mid = os.path.join(args.child, "mid_%d.bam" % os.getpid())
+        sam_to_bam(sam, mid, threads=16, level=1)
+        t1 = time.perf_counter()
+        r = sort_bam(mid, out, device=0, threads=args.threads, level=-2)
+        r["wall_s"] = time.perf_counter() - t0
+        r["sam_to_bam_s"] = t1 - t0
+        r["mid_bam_bytes"] = os.path.getsize(mid)
+        os.remove(mid)
+    os.remove(out)
+    print(json.dumps(r), flush=True)
+
+
+def run_child(args, tmp, prefix=(), min_passes=-1, sam=None, lib=None):
+    env = dict(os.environ)
+    if lib:
+        env["GCE_LIB"] = lib
     p = subprocess.run(["timeout", "-k", "10", "600"] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--threads", str(args.threads),
-                                                                      "--child-min-passes", str(min_passes)], stdout=subprocess.PIPE, universal_newlines=True)
+                                                                      "--child-min-passes", str(min_passes)] + (["--child-sam", sam] if sam else []),
+                       stdout=subprocess.PIPE, universal_newlines=True, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:
         raise SystemExit("sort_bench: a child run failed (exit %d)" % p.returncode)
@@ -138,6 +171,49 @@ def passes_mode(args, tmp, src, make_s):
     print(json.dumps(res))
 
 
+def sam_mode(args, tmp, src, make_s):
+    sam = os.path.join(tmp, "unsorted.sam")
+    if not os.path.exists(sam):                                   # host only, in a child of its own
+        p = subprocess.run(["timeout", "-k", "10", "900", sys.executable, "-c", "import sys; sys.path.insert(0, %r); from gencore_amd.bamio import bam_to_sam; bam_to_sam(%r, %r, threads=%d)"
+                            % (ROOT, src, sam, args.threads)])
+        if p.returncode != 0:
+            raise SystemExit("sort_bench: bam_to_sam failed (exit %d)" % p.returncode)
+    text_bytes = os.path.getsize(sam)
+    variants = (("sort_sam", None), ("compose", args.lib))
+    for v, lib in variants:                                       # warm-up: page cache, code objects
+        run_child(args, tmp, sam=v, lib=lib)
+    runs = {"sort_sam": [], "compose": []}
+    for _ in range(args.reps):                                    # interleaved: a drift of the machine falls on both
+        for v, lib in variants:
+            runs[v].append(run_child(args, tmp, sam=v, lib=lib))
+    med = lambda rs, k: sorted(r[k] for r in rs)[len(rs) // 2]
+    for v in runs:
+        print("sort_bench: %s: wall_s %s" % (v, [round(r["wall_s"], 3) for r in runs[v]]), flush=True)
+    a, b = runs["sort_sam"], runs["compose"]
+    assert a[0]["n_records"] == b[0]["n_records"] and a[0]["out_bytes"] == b[0]["out_bytes"], (a[0], b[0])
+    stages = ("read_s", "inflate_index_s", "sort_s", "gather_s", "write_s", "total_s", "wall_s")
+    prof = os.path.join(tmp, "prof_sam")
+    rp = run_child(args, tmp, prefix=["rocprofv3", "--kernel-trace", "--stats", "-d", prof, "-o", "sort", "--output-format", "csv", "--"], sam="sort_sam")
+    kern = {}
+    for r in kernel_rows(prof, "k_sam_"):
+        name = re.search(r"k_sam_\w+", r["Name"]).group(0)         # (the CSV holds the demangled name: "(anonymous namespace)::k_sam_size(...)")
+        k = kern.setdefault(name, dict(calls=0, seconds=0.0))
+        k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9
+    parse_s = sum(k["seconds"] for k in kern.values())
+    res = dict(workload=args.workload, pairs=int(args.pairs), records=a[0]["n_records"], text_bytes=text_bytes, record_bytes=a[0]["inflated_bytes"], out_bam_bytes=a[0]["out_bytes"], level=-2,
+               reps=args.reps, make_input_s=round(make_s, 2), n_host_lines=a[0]["n_host_lines"],
+               sort_sam=dict(wall_s=round(med(a, "wall_s"), 4), wall_s_all=[round(r["wall_s"], 4) for r in a], peak_device_bytes=a[0]["peak_device_bytes"],
+                             stage_s_median={k: round(med(a, k), 4) for k in stages}),
+               composition=dict(library=args.lib or "this tree's", sam_to_bam="level 1, 16 threads", wall_s=round(med(b, "wall_s"), 4), wall_s_all=[round(r["wall_s"], 4) for r in b],
+                                sam_to_bam_s=round(med(b, "sam_to_bam_s"), 4), mid_bam_bytes=b[0]["mid_bam_bytes"], peak_device_bytes=b[0]["peak_device_bytes"],
+                                stage_s_median={k: round(med(b, k), 4) for k in stages}),
+               parse_kernels=dict(source="rocprofv3 --kernel-trace --stats, a run of sort_sam in a process of its own", kernels={n: dict(calls=k["calls"], seconds=round(k["seconds"], 6)) for n, k in sorted(kern.items())},
+                                  seconds=round(parse_s, 6), text_gb_per_s=round(text_bytes / parse_s / 1e9, 2), n_host_lines=rp["n_host_lines"]))
+    res["composition_over_sort_sam"] = round(res["composition"]["wall_s"] / res["sort_sam"]["wall_s"], 3)
+    json.dump(res, open(args.out, "w"), indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="cfg3")
@@ -148,18 +224,23 @@ def main():
     ap.add_argument("--passes", action="store_true")
     ap.add_argument("--min-passes", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--sam", action="store_true")
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--child-sam", default=None, choices=["sort_sam", "compose"])
     ap.add_argument("--child", default=None)
     ap.add_argument("--child-min-passes", type=int, default=-1)
     args = ap.parse_args()
     if args.child is not None:
-        return child(args)
+        return child_sam(args) if args.child_sam else child(args)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "sort_bam_passes.json" if args.passes else "sort_bam.json")
+        args.out = os.path.join(ROOT, "profiles", "sort_sam.json" if args.sam else "sort_bam_passes.json" if args.passes else "sort_bam.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_sort_")
     src = os.path.join(tmp, "unsorted.bam")
     make_s = 0.0
     if not os.path.exists(src):
         make_s = make_input(args, src)
+    if args.sam:
+        return sam_mode(args, tmp, src, make_s)
     if args.passes:
         return passes_mode(args, tmp, src, make_s)
     run_child(args, tmp)                                         # warm-up: page cache, code objects

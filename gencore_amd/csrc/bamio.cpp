@@ -1,15 +1,23 @@
-// bamio.cpp — BGZF/BAM reader and writer + FASTA loader behind the C-ABI (include/gencore_amd.h, "files" section).  BGZF members are
-// decoded by the raw-deflate decoder below with zlib as fallback and arbiter, their CRC-32 by carry-less multiplication (zlib where the
-// CPU has no PCLMULQDQ); the writer deflates with zlib (levels 0..9) or the fixed-Huffman encoder below (level -1).
+// bamio.cpp — the file side of the C-ABI (include/gencore_amd.h, "files" section), in two halves.
 //
-// Replaces on the host what the reference does through htslib and FastaReader around the hot path:
-//   sam_open / sam_hdr_read / sam_read1        src/gencore.cpp:164-205      -> gce_bam_open (+ gce_bam_chunk: records -> gce_batch)
+// Host only: the whole-file BAM reader (gce_bam_open / gce_bam_chunk: records -> gce_batch) and writer (gce_bam_write), SAM text <-> BAM
+// (gce_samtext.hpp), the FASTA and BED loaders, the reports (gce_report.hpp).  They replace what the reference does through htslib and
+// FastaReader around the hot path:
+//   sam_open / sam_hdr_read / sam_read1        src/gencore.cpp:164-205      -> gce_bam_open (+ gce_bam_chunk)
 //   sam_hdr_write / sam_write1 / sam_close     src/gencore.cpp:187-190,104  -> gce_bam_write (result rows -> records -> BGZF)
 //   FastaReader::readAll / readNext / to4bits  src/fastareader.cpp:57-104,139-152,157-168 -> gce_fasta_load
-// htslib itself is a pinned dependency that is absent from /root/reference; the formats are the published ones (SAMv1 section 4:
-// BGZF = concatenated gzip members with a "BC" extra field, BAM record layout), restated here.
+// htslib itself is a pinned dependency that is absent from the reference tree; the formats are the published ones (SAMv1 section 4).
+//
+// Drivers of the GPU: the file-to-file runners gce_run_bam (+ sharded, depth), gce_run_bam_passes, gce_bam_index, gce_bam_sort,
+// gce_bam_sort_passes and gce_sam_sort.  This file launches no kernel itself: the runners read the file, find its BGZF members and hand
+// them, window by window, to the engine's entry points in engine.hip (gce_raw_*, gce_passes_*, gce_bai_*, gce_sort_*), which inflate, index,
+// process, sort and deflate in HBM; the output comes back in pieces and is written here.
+//
+// One copy of each shared piece: member framing, the BAM header, the member codec, the EOF member and the file helpers are in
+// gce_bgzf.hpp; PassReader (a file's members, piece by piece), for_each_window (the window loop of the index and sort runners) and
+// write_members (a piece deflated into 0xff00-byte members on all host threads, written in order) are below.
 // Everything that scales with the file is spread over `threads` host threads: inflate per BGZF block, the struct-of-arrays fill
-// per record range, record rebuild + deflate per output block.  No GPU code in this file.
+// per record range, record rebuild + deflate per output block.
 #include <zlib.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -28,14 +36,13 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/gencore_amd.h"
+#include "gce_bgzf.hpp"
 #include "gce_samtext.hpp"
 #include "gce_report.hpp"
 
 static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
 namespace {
-
-struct Block { uint64_t coff; uint32_t csize, usize; uint64_t uoff; };
 
 // host threads when the caller does not say: the CPUs this process may run on (affinity mask / cgroup quota), at most 64 -- on the
 // 256-thread box the measurements were made on, inflate and deflate stop scaling near 64 threads and lose 30 % at 256
@@ -51,76 +58,12 @@ int default_threads() {
     return std::min(n, 64);
 }
 
-inline uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | p[1] << 8); }
-inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-inline int32_t rdi32(const uint8_t *p) { int32_t v; memcpy(&v, p, 4); return v; }
-
 template <class F> void parallel_for(int threads, int64_t n, F f) {          // f(thread, begin, end) over contiguous ranges
     threads = (int)std::max<int64_t>(1, std::min<int64_t>(threads, n));
     if (threads == 1) { f(0, (int64_t)0, n); return; }
     std::vector<std::thread> th;
     for (int t = 0; t < threads; t++) th.emplace_back([=] { f(t, n * t / threads, n * (t + 1) / threads); });
     for (auto &x : th) x.join();
-}
-
-// ---- CRC-32 (gzip polynomial, reflected) by carry-less multiplication: "Fast CRC Computation for Generic Polynomials Using PCLMULQDQ"
-// (Gopal et al., Intel 2009) -- fold four 128-bit lanes over 64 input bytes a step, fold the lanes together, reduce 128 -> 64 -> 32
-// bits (Barrett).  zlib 1.2.11's table-driven crc32 runs at 1.0 GB/s per thread, which made the checksum 45 % of a BGZF block's
-// inflate time (zlib inflates BAM data at ~0.8 GB/s).  Used only when the CPU has PCLMULQDQ and a self-check against zlib passes;
-// tails and short buffers stay with zlib.
-#if defined(__x86_64__)
-#include <immintrin.h>
-__attribute__((target("pclmul,sse4.1"))) inline __m128i crc_fold(__m128i acc, __m128i k, __m128i next) {   // acc * x^distance mod P, plus the next 16 bytes
-    return _mm_xor_si128(_mm_xor_si128(_mm_clmulepi64_si128(acc, k, 0x00), _mm_clmulepi64_si128(acc, k, 0x11)), next);
-}
-__attribute__((target("pclmul,sse4.1"))) uint32_t crc32_clmul_state(const uint8_t *buf, size_t len /* >= 64, multiple of 16 */, uint32_t state) {
-    // x^(n) mod P constants of the paper for the bit-reflected gzip polynomial: fold distances 4 x 128 (+-32), 128 (+-32), 64, and P / mu
-    const __m128i k_fold4 = _mm_set_epi64x(0x01c6e41596ll, 0x0154442bd4ll), k_fold1 = _mm_set_epi64x(0x00ccaa009ell, 0x01751997d0ll);
-    const __m128i k_64 = _mm_set_epi64x(0, 0x0163cd6124ll), k_poly = _mm_set_epi64x(0x01f7011641ll, 0x01db710641ll);
-    const __m128i *p = reinterpret_cast<const __m128i *>(buf);
-    __m128i a0 = _mm_xor_si128(_mm_loadu_si128(p), _mm_cvtsi32_si128((int)state)), a1 = _mm_loadu_si128(p + 1), a2 = _mm_loadu_si128(p + 2), a3 = _mm_loadu_si128(p + 3);
-    p += 4; len -= 64;
-    for (; len >= 64; p += 4, len -= 64) {
-        a0 = crc_fold(a0, k_fold4, _mm_loadu_si128(p)); a1 = crc_fold(a1, k_fold4, _mm_loadu_si128(p + 1));
-        a2 = crc_fold(a2, k_fold4, _mm_loadu_si128(p + 2)); a3 = crc_fold(a3, k_fold4, _mm_loadu_si128(p + 3));
-    }
-    a0 = crc_fold(a0, k_fold1, a1); a0 = crc_fold(a0, k_fold1, a2); a0 = crc_fold(a0, k_fold1, a3);
-    for (; len >= 16; p += 1, len -= 16) a0 = crc_fold(a0, k_fold1, _mm_loadu_si128(p));
-    // 128 -> 64 bits
-    const __m128i low32 = _mm_setr_epi32(~0, 0, ~0, 0);
-    __m128i t = _mm_xor_si128(_mm_srli_si128(a0, 8), _mm_clmulepi64_si128(a0, k_fold1, 0x10));
-    t = _mm_xor_si128(_mm_srli_si128(t, 4), _mm_clmulepi64_si128(_mm_and_si128(t, low32), k_64, 0x00));
-    // Barrett reduction 64 -> 32 bits
-    __m128i q = _mm_clmulepi64_si128(_mm_and_si128(t, low32), k_poly, 0x10);
-    q = _mm_clmulepi64_si128(_mm_and_si128(q, low32), k_poly, 0x00);
-    return (uint32_t)_mm_extract_epi32(_mm_xor_si128(t, q), 1);
-}
-bool crc32_clmul_usable() {
-    static const bool ok = [] {
-        if (!__builtin_cpu_supports("pclmul") || !__builtin_cpu_supports("sse4.1")) return false;
-        uint8_t tmp[1024 + 16];
-        uint32_t x = 0x9E3779B9u;
-        for (size_t i = 0; i < sizeof tmp; i++) { x = x * 1664525u + 1013904223u; tmp[i] = (uint8_t)(x >> 24); }
-        for (size_t off = 0; off < 3; off++)
-            for (size_t n : {(size_t)64, (size_t)80, (size_t)128, (size_t)1008, (size_t)1024}) {
-                const uint32_t want = (uint32_t)crc32(crc32(0L, Z_NULL, 0), tmp + off, (uInt)n);
-                if ((uint32_t)~crc32_clmul_state(tmp + off, n, 0xFFFFFFFFu) != want) return false;
-            }
-        return true;
-    }();
-    return ok;
-}
-#else
-bool crc32_clmul_usable() { return false; }
-uint32_t crc32_clmul_state(const uint8_t *, size_t, uint32_t s) { return s; }
-#endif
-// CRC-32 of a whole buffer (what a gzip member stores)
-uint32_t crc32_buf(const uint8_t *buf, size_t n) {
-    uint32_t c = (uint32_t)crc32(0L, Z_NULL, 0);
-    size_t done = 0;
-    if (n >= 64 && crc32_clmul_usable()) { done = n & ~(size_t)15; c = ~crc32_clmul_state(buf, done, 0xFFFFFFFFu); }
-    while (done < n) { const size_t m = std::min<size_t>(n - done, 1u << 30); c = (uint32_t)crc32(c, buf + done, (uInt)m); done += m; }
-    return c;
 }
 
 template <class V> bool read_file(const char *path, V &out) {
@@ -133,320 +76,6 @@ template <class V> bool read_file(const char *path, V &out) {
     const size_t got = sz > 0 ? fread(out.data(), 1, (size_t)sz, f) : 0;
     fclose(f);
     return got == (size_t)std::max(0l, sz);
-}
-
-// ---- raw-deflate decoder for BGZF members (RFC 1951), used in front of zlib: 64-bit bit buffer refilled eight bytes at a time, one
-// table look-up per symbol (10-bit primary table + subtables for literals/lengths, 8-bit + subtables for distances), matches copied
-// in 8-byte words.  A BGZF member is self-contained (empty window at its start, <= 64 KB out), every output byte is bounds-checked,
-// and the caller verifies the member's CRC-32 -- whatever this decoder does not handle (incomplete Huffman codes, damaged streams)
-// or gets wrong falls back to zlib's inflate, which stays the arbiter of what a valid stream is.
-namespace fastinf {
-enum : uint32_t { K_INVALID = 0, K_LIT = 1, K_LEN = 2, K_EOB = 4, K_SUB = 8, K_DIST = 6 };   // (K_LIT and K_SUB are single bits: tested with one AND)
-constexpr int LIT_BITS = 10, DIST_BITS = 8, LIT_CAP = (1 << LIT_BITS) + 1024, DIST_CAP = (1 << DIST_BITS) + 512;
-// entry: bits 0..7 code bits to consume | 8..11 kind | 12..15 extra bits (K_SUB: subtable bits) | 16..31 value (literal, base, subtable start)
-inline uint32_t mk(uint32_t kind, uint32_t bits, uint32_t extra, uint32_t value) { return bits | kind << 8 | extra << 12 | value << 16; }
-const uint16_t LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-const uint8_t LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-const uint16_t DIST_BASE[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-const uint8_t DIST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-
-inline uint32_t sym_entry_litlen(int sym, uint32_t bits) {
-    if (sym < 256) return mk(K_LIT, bits, 0, (uint32_t)sym);
-    if (sym == 256) return mk(K_EOB, bits, 0, 0);
-    if (sym <= 285) return mk(K_LEN, bits, LEN_EXTRA[sym - 257], LEN_BASE[sym - 257]);
-    return mk(K_INVALID, bits, 0, 0);
-}
-inline uint32_t sym_entry_dist(int sym, uint32_t bits) {
-    if (sym < 30) return mk(K_DIST, bits, DIST_EXTRA[sym], DIST_BASE[sym]);
-    return mk(K_INVALID, bits, 0, 0);
-}
-inline uint32_t rev_bits(uint32_t code, int len) { uint32_t r = 0; for (int i = 0; i < len; i++) { r = r << 1 | (code & 1); code >>= 1; } return r; }
-
-// canonical Huffman code of `lens` -> look-up table.  Only COMPLETE codes are taken (Kraft sum exactly 1); returns false otherwise.
-template <class EntryOf> bool build_table(const uint8_t *lens, int nsym, int primary, uint32_t *table, int cap, EntryOf entry_of) {
-    int count[16] = {0};
-    for (int s = 0; s < nsym; s++) count[lens[s]]++;
-    count[0] = 0;
-    uint32_t kraft = 0;
-    for (int l = 1; l <= 15; l++) kraft += (uint32_t)count[l] << (15 - l);
-    if (kraft != (1u << 15)) return false;
-    uint32_t next_code[16]; { uint32_t code = 0; for (int l = 1; l <= 15; l++) { code = (code + (uint32_t)count[l - 1]) << 1; next_code[l] = code; } }
-    // reversed code of every coded symbol; the longest code behind every primary prefix
-    uint16_t rcode[288]; uint8_t sub_bits[1 << LIT_BITS];
-    const int np = 1 << primary;
-    memset(sub_bits, 0, (size_t)np);
-    for (int s = 0; s < nsym; s++) {
-        const int l = lens[s];
-        if (!l) continue;
-        const uint32_t r = rev_bits(next_code[l]++, l);
-        rcode[s] = (uint16_t)r;
-        if (l > primary) { uint8_t &b = sub_bits[r & (uint32_t)(np - 1)]; b = (uint8_t)std::max<int>(b, l - primary); }
-    }
-    int used = np;
-    for (int i = 0; i < np; i++) {
-        if (!sub_bits[i]) continue;
-        if (used + (1 << sub_bits[i]) > cap) return false;
-        table[i] = mk(K_SUB, (uint32_t)primary, sub_bits[i], (uint32_t)used);
-        used += 1 << sub_bits[i];
-    }
-    for (int s = 0; s < nsym; s++) {
-        const int l = lens[s];
-        if (!l) continue;
-        const uint32_t r = rcode[s];
-        if (l <= primary) { const uint32_t e = entry_of(s, (uint32_t)l); for (uint32_t i = r; i < (uint32_t)np; i += 1u << l) table[i] = e; }
-        else {
-            const uint32_t pi = r & (uint32_t)(np - 1), sb = sub_bits[pi], start = table[pi] >> 16, e = entry_of(s, (uint32_t)(l - primary));
-            for (uint32_t i = r >> primary; i < (1u << sb); i += 1u << (l - primary)) table[start + i] = e;
-        }
-    }
-    return true;
-}
-
-struct Tables { uint32_t lit[LIT_CAP], dist[DIST_CAP]; };
-const Tables *fixed_tables() {
-    static const Tables *t = [] {
-        Tables *x = new Tables;
-        uint8_t l[288]; for (int i = 0; i < 288; i++) l[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
-        uint8_t d[32]; for (int i = 0; i < 32; i++) d[i] = 5;
-        build_table(l, 288, LIT_BITS, x->lit, LIT_CAP, sym_entry_litlen); build_table(d, 32, DIST_BITS, x->dist, DIST_CAP, sym_entry_dist);
-        return x;
-    }();
-    return t;
-}
-
-// src[0, n): raw deflate; dst[0, want): exactly `want` bytes must come out.  src must be readable up to src + n + 8 (a BGZF member's
-// CRC-32 and ISIZE follow its deflate data).  false = not handled (the caller runs zlib).
-bool inflate_raw(const uint8_t *src, size_t n, uint8_t *dst, size_t want) {
-    const uint8_t *in = src, *const in_end = src + n;
-    uint8_t *out = dst, *const out_end = dst + want;
-    uint64_t bb = 0; int nb = 0;                                              // bit buffer, valid bits
-    const uint8_t *const lim = in_end + 8;                                    // readable up to here (the member's CRC-32 and ISIZE)
-    auto refill = [&]() -> bool {                                             // >= 56 valid bits afterwards; bits past the deflate data are whatever follows
-        uint64_t w = 0;                                                       // it (or zeros) -- a stream that needs them fails the position check at the end
-        if (in + 8 <= lim) memcpy(&w, in, 8);
-        else { if (in > lim) return false; for (int i = 0; in + i < lim; i++) w |= (uint64_t)in[i] << (8 * i); }
-        bb |= w << nb; in += (63 - nb) >> 3; nb |= 56;
-        return true;
-    };
-    Tables dyn;
-    for (bool last = false; !last;) {
-        if (!refill()) return false;
-        last = bb & 1; const uint32_t type = (uint32_t)(bb >> 1) & 3; bb >>= 3; nb -= 3;
-        if (type == 0) {                                                      // stored
-            const int drop = nb & 7; bb >>= drop; nb -= drop;
-            if (!refill()) return false;
-            const uint32_t len = (uint32_t)bb & 0xFFFF, nlen = (uint32_t)(bb >> 16) & 0xFFFF; bb >>= 32; nb -= 32;
-            if ((len ^ nlen) != 0xFFFF) return false;
-            const uint8_t *p = in - (nb >> 3);                                // first byte not yet consumed (nb is a multiple of 8 here)
-            if ((size_t)(in_end - p) < len || p > in_end || (size_t)(out_end - out) < len) return false;
-            memcpy(out, p, len); out += len; in = p + len; bb = 0; nb = 0;
-            continue;
-        }
-        const uint32_t *lit, *dist;
-        if (type == 1) { const Tables *f = fixed_tables(); lit = f->lit; dist = f->dist; }
-        else if (type == 2) {
-            const int hlit = (int)(bb & 31) + 257, hdist = (int)(bb >> 5 & 31) + 1, hclen = (int)(bb >> 10 & 15) + 4; bb >>= 14; nb -= 14;
-            if (hlit > 286 || hdist > 30) return false;
-            static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-            uint8_t cl[19] = {0};
-            for (int i = 0; i < hclen; i++) { if (nb < 3 && !refill()) return false; cl[order[i]] = (uint8_t)(bb & 7); bb >>= 3; nb -= 3; }
-            uint32_t clt[1 << 7];
-            if (!build_table(cl, 19, 7, clt, 1 << 7, [](int s, uint32_t bits) { return mk(K_LIT, bits, 0, (uint32_t)s); })) return false;
-            uint8_t lens[288 + 32]; int k = 0;
-            memset(lens, 0, sizeof lens);
-            while (k < hlit + hdist) {
-                if (!refill()) return false;
-                const uint32_t e = clt[bb & 127]; const int s = (int)(e >> 16); bb >>= (e & 0xFF); nb -= (int)(e & 0xFF);
-                if (s < 16) { lens[k++] = (uint8_t)s; continue; }
-                int rep; uint8_t v = 0;
-                if (s == 16) { if (k == 0) return false; v = lens[k - 1]; rep = 3 + (int)(bb & 3); bb >>= 2; nb -= 2; }
-                else if (s == 17) { rep = 3 + (int)(bb & 7); bb >>= 3; nb -= 3; }
-                else { rep = 11 + (int)(bb & 127); bb >>= 7; nb -= 7; }
-                if (k + rep > hlit + hdist) return false;
-                memset(lens + k, v, (size_t)rep); k += rep;
-            }
-            if (lens[256] == 0) return false;                                 // no end-of-block code
-            uint8_t dl[32]; memset(dl, 0, sizeof dl); memcpy(dl, lens + hlit, (size_t)hdist);
-            memset(lens + hlit, 0, (size_t)(288 - hlit));
-            if (!build_table(lens, 288, LIT_BITS, dyn.lit, LIT_CAP, sym_entry_litlen)) return false;
-            if (!build_table(dl, 32, DIST_BITS, dyn.dist, DIST_CAP, sym_entry_dist)) return false;      // (a lone distance code: zlib's business)
-            lit = dyn.lit; dist = dyn.dist;
-        } else return false;
-        for (;;) {                                                            // symbols of the block
-            if (!refill()) return false;                                      // >= 56 bits: a length/distance pair needs at most 15 + 5 + 15 + 13 = 48
-            uint32_t e = lit[bb & ((1u << LIT_BITS) - 1)];
-            if (e & (K_LIT << 8)) {                                           // literals first: up to four from one refill (<= 10 + 3 x 10 + ... bits of the 56)
-                if (out_end - out < 4) { if (out >= out_end) return false; bb >>= (e & 0xFF); nb -= (int)(e & 0xFF); *out++ = (uint8_t)(e >> 16); continue; }
-                bb >>= (e & 0xFF); nb -= (int)(e & 0xFF); *out++ = (uint8_t)(e >> 16);
-                e = lit[bb & ((1u << LIT_BITS) - 1)];
-                if (!(e & (K_LIT << 8))) continue;
-                bb >>= (e & 0xFF); nb -= (int)(e & 0xFF); *out++ = (uint8_t)(e >> 16);
-                e = lit[bb & ((1u << LIT_BITS) - 1)];
-                if (!(e & (K_LIT << 8))) continue;
-                bb >>= (e & 0xFF); nb -= (int)(e & 0xFF); *out++ = (uint8_t)(e >> 16);
-                e = lit[bb & ((1u << LIT_BITS) - 1)];
-                if (!(e & (K_LIT << 8))) continue;
-                bb >>= (e & 0xFF); nb -= (int)(e & 0xFF); *out++ = (uint8_t)(e >> 16);
-                continue;
-            }
-            if (e & (K_SUB << 8)) { bb >>= LIT_BITS; nb -= LIT_BITS; e = lit[(e >> 16) + (uint32_t)(bb & ((1u << ((e >> 12) & 15)) - 1))]; }
-            bb >>= (e & 0xFF); nb -= (int)(e & 0xFF);
-            const uint32_t kind = (e >> 8) & 15;
-            if (kind == K_LIT) { if (out >= out_end) return false; *out++ = (uint8_t)(e >> 16); continue; }      // (a literal with a long code)
-            if (kind == K_EOB) break;
-            if (kind != K_LEN) return false;
-            const uint32_t xl = (e >> 12) & 15, length = (e >> 16) + (uint32_t)(bb & ((1u << xl) - 1)); bb >>= xl; nb -= (int)xl;
-            uint32_t d = dist[bb & ((1u << DIST_BITS) - 1)];
-            if (d & (K_SUB << 8)) { bb >>= DIST_BITS; nb -= DIST_BITS; d = dist[(d >> 16) + (uint32_t)(bb & ((1u << ((d >> 12) & 15)) - 1))]; }
-            bb >>= (d & 0xFF); nb -= (int)(d & 0xFF);
-            if (((d >> 8) & 15) != K_DIST) return false;
-            const uint32_t xd = (d >> 12) & 15, distance = (d >> 16) + (uint32_t)(bb & ((1u << xd) - 1)); bb >>= xd; nb -= (int)xd;
-            if (nb < 0) return false;                                         // ran past what the refill provided
-            if (distance > (size_t)(out - dst) || length > (size_t)(out_end - out)) return false;
-            const uint8_t *from = out - distance;
-            if (distance >= 8 && (size_t)(out_end - out) >= length + 8) {     // whole words (may run up to 7 bytes over the match, inside the member)
-                uint8_t *o = out; const uint8_t *f = from;
-                for (uint32_t c = 0; c < length; c += 8) { uint64_t w; memcpy(&w, f + c, 8); memcpy(o + c, &w, 8); }
-            } else if (distance == 1) memset(out, from[0], length);           // a run of one byte (quality strings are full of them)
-            else for (uint32_t c = 0; c < length; c++) out[c] = from[c];
-            out += length;
-        }
-        if (nb < 0) return false;
-    }
-    if ((size_t)(in - src) * 8 - (size_t)nb > n * 8) return false;            // consumed bits past the end of the deflate data
-    return out == out_end;
-}
-}  // namespace fastinf
-
-// one raw-deflate BGZF member -> dst (usize bytes); checks the CRC
-bool inflate_block(const uint8_t *src, const Block &b, uint8_t *dst) {
-    const uint16_t xlen = rd16(src + 10);
-    const uint8_t *cdata = src + 12 + xlen;
-    const uint32_t clen = b.csize - 12 - xlen - 8;
-    static const bool zlib_only = getenv("GCE_BAM_ZLIB_ONLY") != nullptr;     // (A/B and tests)
-    if (!zlib_only && fastinf::inflate_raw(cdata, clen, dst, b.usize) && crc32_buf(dst, b.usize) == rd32(src + b.csize - 8)) return true;
-    z_stream zs; memset(&zs, 0, sizeof zs);
-    if (inflateInit2(&zs, -15) != Z_OK) return false;
-    zs.next_in = const_cast<uint8_t *>(cdata); zs.avail_in = clen; zs.next_out = dst; zs.avail_out = b.usize;
-    const int rc = inflate(&zs, Z_FINISH);
-    inflateEnd(&zs);
-    if (rc != Z_STREAM_END || zs.total_out != b.usize) return false;
-    return crc32_buf(dst, b.usize) == rd32(src + b.csize - 8);
-}
-
-// ---- "level 1" raw-deflate encoder for BGZF members: greedy LZ77 over a 2^13-entry hash of 4-byte strings (the member is its own
-// window: positions fit 16 bits), ONE fixed-Huffman block (RFC 1951 3.2.6) -- no code construction, a 64-bit bit accumulator.  Gives
-// up (returns 0) when the result would not fit a BGZF member; the caller then takes zlib as before.
-namespace fastdef {
-struct Codes {
-    uint16_t lit[286]; uint8_t lit_bits[286];              // literal / end-of-block codes, bit-reversed for the LSB-first stream
-    uint32_t len[259]; uint8_t len_bits[259];              // match length 3..258: code + extra bits in one word
-    uint8_t dcode[512];                                    // distance - 1 -> distance code (zlib's two-level index)
-};
-inline uint32_t rev(uint32_t code, int len) { uint32_t r = 0; for (int i = 0; i < len; i++) { r = r << 1 | (code & 1); code >>= 1; } return r; }
-const Codes &codes() {
-    static const Codes c = [] {
-        Codes x; memset(&x, 0, sizeof x);
-        auto fixed = [](int s, uint32_t &code, int &bits) {
-            if (s < 144) { code = 0x30 + (uint32_t)s; bits = 8; } else if (s < 256) { code = 0x190 + (uint32_t)(s - 144); bits = 9; }
-            else if (s < 280) { code = (uint32_t)(s - 256); bits = 7; } else { code = 0xC0 + (uint32_t)(s - 280); bits = 8; }
-        };
-        for (int s = 0; s <= 256; s++) { uint32_t code; int bits; fixed(s, code, bits); x.lit[s] = (uint16_t)rev(code, bits); x.lit_bits[s] = (uint8_t)bits; }
-        for (int L = 3; L <= 258; L++) {
-            int idx = 28; while (fastinf::LEN_BASE[idx] > L) idx--;
-            if (L == 258) idx = 28;
-            uint32_t code; int bits; fixed(257 + idx, code, bits);
-            x.len[L] = rev(code, bits) | (uint32_t)(L - fastinf::LEN_BASE[idx]) << bits; x.len_bits[L] = (uint8_t)(bits + fastinf::LEN_EXTRA[idx]);
-        }
-        for (int d = 1; d <= 32768; d++) {
-            int dc = 29; while (fastinf::DIST_BASE[dc] > d) dc--;
-            const int k = d - 1;
-            x.dcode[k < 256 ? k : 256 + (k >> 7)] = (uint8_t)dc;           // (all distances that share an index share a code)
-        }
-        return x;
-    }();
-    return c;
-}
-// src[0, n), n <= 65535 -> dst[0, cap); returns the size or 0
-size_t deflate_fixed(const uint8_t *src, uint32_t n, uint8_t *dst, size_t cap) {
-    const Codes &c = codes();
-    uint16_t head[1 << 13];
-    memset(head, 0, sizeof head);
-    uint8_t *out = dst, *const out_end = dst + cap;
-    uint64_t acc = 0; int nacc = 0;
-    auto put = [&](uint64_t v, int bits) -> bool {                            // bits <= 31 per call
-        acc |= v << nacc; nacc += bits;
-        if (nacc >= 32) { if (out + 4 > out_end) return false; const uint32_t w = (uint32_t)acc; memcpy(out, &w, 4); out += 4; acc >>= 32; nacc -= 32; }
-        return true;
-    };
-    if (!put(1 | 1 << 1, 3)) return 0;                                        // BFINAL = 1, BTYPE = 01
-    uint32_t i = 0;
-    while (i + 4 <= n) {
-        uint32_t cur; memcpy(&cur, src + i, 4);
-        const uint32_t h = (cur * 2654435761u) >> 19;
-        const uint32_t cand = head[h];
-        head[h] = (uint16_t)(i + 1);
-        uint32_t at;
-        if (cand && (memcpy(&at, src + cand - 1, 4), at == cur) && i - (cand - 1) <= 32768u) {
-            const uint8_t *a = src + i, *b = src + cand - 1;
-            const uint32_t maxlen = std::min<uint32_t>(258u, n - i);
-            uint32_t len = 4;
-            while (len + 8 <= maxlen) { uint64_t x, y; memcpy(&x, a + len, 8); memcpy(&y, b + len, 8); if (x != y) { len += (uint32_t)__builtin_ctzll(x ^ y) >> 3; goto done; } len += 8; }
-            while (len < maxlen && a[len] == b[len]) len++;
-        done:
-            const uint32_t d = i - (cand - 1), dc = c.dcode[d - 1 < 256 ? d - 1 : 256 + ((d - 1) >> 7)];
-            if (!put(c.len[len], c.len_bits[len])) return 0;
-            if (!put(rev(dc, 5) | (uint64_t)(d - fastinf::DIST_BASE[dc]) << 5, 5 + fastinf::DIST_EXTRA[dc])) return 0;
-            i += len;
-        } else {
-            if (!put(c.lit[src[i]], c.lit_bits[src[i]])) return 0;
-            i++;
-        }
-    }
-    for (; i < n; i++) if (!put(c.lit[src[i]], c.lit_bits[src[i]])) return 0;
-    if (!put(c.lit[256], c.lit_bits[256])) return 0;
-    while (nacc > 0) { if (out >= out_end) return 0; *out++ = (uint8_t)acc; acc >>= 8; nacc -= 8; }
-    return (size_t)(out - dst);
-}
-}  // namespace fastdef
-
-// one BGZF member from `n` (<= 0xff00) bytes; returns its size
-size_t deflate_block(const uint8_t *src, uint32_t n, int level, uint8_t *dst /* >= 0x10000 + 64 */) {
-    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-    memcpy(dst, head, 16);
-    static const bool zlib_only = getenv("GCE_BAM_ZLIB_ONLY") != nullptr;
-    if (level < 0 && !zlib_only) {                                            // level -1, "fastest": the fixed-Huffman encoder above
-        const size_t clen = fastdef::deflate_fixed(src, n, dst + 18, 0x10000 - 18 - 8);
-        if (clen) {
-            const size_t total = 18 + clen + 8;
-            const uint16_t bsize = (uint16_t)(total - 1);
-            memcpy(dst + 16, &bsize, 2);
-            const uint32_t crc = crc32_buf(src, n);
-            memcpy(dst + 18 + clen, &crc, 4); memcpy(dst + 18 + clen + 4, &n, 4);
-            return total;
-        }
-    }
-    if (level < 0) level = 1;
-    if (level > 9) level = 9;
-    z_stream zs; memset(&zs, 0, sizeof zs);
-    deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
-    zs.next_in = const_cast<uint8_t *>(src); zs.avail_in = n; zs.next_out = dst + 18; zs.avail_out = 0x10000 - 18 - 8;
-    int rc = deflate(&zs, Z_FINISH);
-    if (rc != Z_STREAM_END) {                                                 // incompressible: store
-        deflateEnd(&zs); memset(&zs, 0, sizeof zs);
-        deflateInit2(&zs, 0, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
-        zs.next_in = const_cast<uint8_t *>(src); zs.avail_in = n; zs.next_out = dst + 18; zs.avail_out = 0x10000 - 18 - 8;
-        rc = deflate(&zs, Z_FINISH);
-    }
-    const size_t clen = zs.total_out;
-    deflateEnd(&zs);
-    if (rc != Z_STREAM_END) return 0;                                         // (cannot happen for <= 0xff00 bytes stored; the caller reports it)
-    const size_t total = 18 + clen + 8;
-    const uint16_t bsize = (uint16_t)(total - 1);
-    memcpy(dst + 16, &bsize, 2);
-    const uint32_t crc = crc32_buf(src, n);
-    memcpy(dst + 18 + clen, &crc, 4); memcpy(dst + 18 + clen + 4, &n, 4);
-    return total;
 }
 
 // a growable buffer that is NOT value-initialised (std::vector::resize would write gigabytes of zeros on one thread)
@@ -493,8 +122,8 @@ bool read_file_parallel(const char *path, Raw<uint8_t> &out, int threads) {
     const int64_t piece = 8 << 20;
     parallel_for(threads, (sz + piece - 1) / piece, [&](int, int64_t a, int64_t e) {
         for (int64_t k = a; k < e; k++) {
-            int64_t off = k * piece; const int64_t end = std::min(sz, off + piece);
-            while (off < end) { const ssize_t got = pread(fd, out.data() + off, (size_t)(end - off), (off_t)off); if (got <= 0) { bad = 1; return; } off += got; }
+            const int64_t off = k * piece, end = std::min(sz, off + piece);
+            if (pread_full(fd, out.data() + off, (size_t)(end - off), (uint64_t)off) != (size_t)(end - off)) { bad = 1; return; }
         }
     });
     close(fd);
@@ -561,10 +190,23 @@ int write_bgzf(const char *path, const Raw<uint8_t> &body, int T, int level) {
     FILE *f = fopen(path, "wb");
     if (!f) return GCE_ERR_INVALID;
     for (int64_t k = 0; k < nb; k++) if (fwrite(z.data() + (size_t)k * 0x10000, 1, zs[k], f) != zs[k]) { fclose(f); return GCE_ERR_INVALID; }
-    static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool eof_ok = fwrite(eof_block, 1, 28, f) == 28;                         // (a full disk must not pass for a finished BAM: the reference exits when sam_write1 / sam_close fail)
+    const bool eof_ok = fwrite(BGZF_EOF, 1, 28, f) == 28;                          // (a full disk must not pass for a finished BAM: the reference exits when sam_write1 / sam_close fail)
     if (fclose(f) != 0 || !eof_ok) return GCE_ERR_INVALID;
     return GCE_OK;
+}
+
+// What the file-to-file runners write: src[0, n) as BGZF members of 0xff00 bytes, deflated by all host threads 256 members a round (the
+// slots of zbuf: 256 * 0x10000 + 64 bytes) and written in order.  false: a member could not be deflated or written.
+constexpr uint64_t MEMBER_BYTES = 0xff00, ROUND_BYTES = MEMBER_BYTES * 256;
+bool write_members(FILE *fo, const uint8_t *src, size_t n, int level, int T, uint8_t *zbuf) {
+    for (size_t o = 0; o < n; o += (size_t)ROUND_BYTES) {
+        const size_t m = std::min<size_t>((size_t)ROUND_BYTES, n - o);
+        const int64_t nb = (int64_t)((m + MEMBER_BYTES - 1) / MEMBER_BYTES);
+        uint32_t zs[256] = {0};
+        parallel_for(T, nb, [&](int, int64_t x, int64_t y) { for (int64_t q = x; q < y; q++) { const uint64_t a = (uint64_t)q * MEMBER_BYTES; zs[q] = (uint32_t)deflate_block(src + o + a, (uint32_t)std::min<uint64_t>(MEMBER_BYTES, m - a), level, zbuf + (size_t)q * 0x10000); } });
+        for (int64_t q = 0; q < nb; q++) if (zs[q] == 0 || fwrite(zbuf + (size_t)q * 0x10000, 1, zs[q], fo) != zs[q]) return false;
+    }
+    return true;
 }
 
 }  // namespace
@@ -597,22 +239,15 @@ int gce_bam_open(const char *path, int threads, gce_bam **out) {
     std::vector<Block> blocks;
     uint64_t off = 0, uoff = 0;
     while (off + 18 <= z.size()) {
-        const uint8_t *p = z.data() + off;
-        if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) { f->err = "not a BGZF file"; return GCE_ERR_INVALID; }
-        const uint16_t xlen = rd16(p + 10);
-        if (off + 12 + (uint64_t)xlen + 8 > z.size()) { f->err = "truncated BGZF block header"; return GCE_ERR_INVALID; }   // the extra field (and the trailer) must lie inside the file
-        uint32_t bsize = 0; bool found = false;
-        for (uint32_t x = 0; x + 4 <= xlen; ) {
-            const uint8_t *s = p + 12 + x; const uint16_t sl = rd16(s + 2);
-            if (x + 4 + (uint32_t)sl > xlen) break;                                 // a subfield that runs past the extra field
-            if (s[0] == 'B' && s[1] == 'C' && sl == 2) { bsize = (uint32_t)rd16(s + 4) + 1; found = true; }
-            x += 4 + sl;
+        Member m;
+        const Scan sc = scan_member(z.data(), z.size(), (size_t)off, m);
+        if (sc != Scan::Member) {                                                       // the whole file is here: a member that needs more bytes is cut by the file's end
+            const bool header_cut = off + 12 + (uint64_t)m.xlen + 8 > z.size();         // the extra field (and the trailer) must lie inside the file
+            f->err = sc == Scan::NotBgzf ? scan_message(sc) : header_cut ? "truncated BGZF block header" : sc == Scan::More ? "bad BGZF block" : scan_message(sc);
+            return GCE_ERR_INVALID;
         }
-        if (!found || off + bsize > z.size() || bsize < 12u + xlen + 8u) { f->err = "bad BGZF block"; return GCE_ERR_INVALID; }
-        Block b; b.coff = off; b.csize = bsize; b.usize = rd32(p + bsize - 4); b.uoff = uoff;
-        if (b.usize > 0x10000u) { f->err = "bad BGZF block (ISIZE above 64 KB)"; return GCE_ERR_INVALID; }   // the format's limit: the sum of these sizes the buffer below
-        blocks.push_back(b);
-        off += bsize; uoff += b.usize;
+        blocks.push_back(Block{off, m.bsize, m.isize, uoff});
+        off += m.bsize; uoff += m.isize;
     }
     if (off != z.size()) { f->err = "trailing bytes after the last BGZF block"; return GCE_ERR_INVALID; }
     f->u.resize(uoff + 64);
@@ -631,19 +266,13 @@ int gce_bam_open(const char *path, int threads, gce_bam **out) {
     z.release();
     // ---- header (SAMv1 4.2)
     const uint8_t *u = f->u.data(); const uint64_t n = uoff;
-    if (n < 12 || memcmp(u, "BAM\1", 4) != 0) { f->err = "not a BAM stream"; return GCE_ERR_INVALID; }
-    uint64_t p = 4;
-    const uint32_t l_text = rd32(u + p); p += 4;
-    if (p + l_text + 4 > n) { f->err = "truncated header"; return GCE_ERR_INVALID; }
-    f->text.assign((const char *)u + p, l_text); p += l_text;
-    const uint32_t n_ref = rd32(u + p); p += 4;
-    for (uint32_t r = 0; r < n_ref; r++) {
-        if (p + 4 > n) { f->err = "truncated header"; return GCE_ERR_INVALID; }
-        const uint32_t ln = rd32(u + p); p += 4;
-        if (p + ln + 4 > n || ln == 0) { f->err = "truncated header"; return GCE_ERR_INVALID; }
-        f->names.emplace_back((const char *)u + p, ln - 1); p += ln;
-        f->lens.push_back(rd32(u + p)); p += 4;
-    }
+    BamHeader bh;
+    const Hdr hs = parse_bam_header(u, n, Contigs::Collect, bh, &f->names, &f->lens);
+    if (hs == Hdr::NotBam || n < 12) { f->err = "not a BAM stream"; return GCE_ERR_INVALID; }
+    if (hs != Hdr::Complete) { f->err = "truncated header"; return GCE_ERR_INVALID; }
+    f->text.assign((const char *)u + bh.text_off, bh.l_text);
+    uint64_t p = bh.hdr_end;
+    const uint32_t n_ref = bh.n_ref;
     for (auto &s : f->names) f->name_ptr.push_back(s.c_str());
     // ---- record index.  The records form a chain (every block_size leads to the next record): one dependent cache miss per record
     //      when walked by one thread.  The stream is cut into segments instead; every segment is walked from a GUESSED record start
@@ -1338,7 +967,8 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
     const uint64_t fsz = (uint64_t)st.st_size;
     gce_engine *e = nullptr; gce_fasta *fa = nullptr; FILE *fo = nullptr;
     std::vector<gce_engine *> mir;                      // the engines of shards 1 .. n_shards - 1 (they receive every push made to e)
-    auto done = [&](int code, const char *m) { seterr(m); for (auto *x : mir) if (x) gce_destroy(x); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); if (fo) fclose(fo); close(fd); return code; };
+    std::thread reader; ssize_t got_next = 0; bool reader_on = false;      // the BAM branch's read-ahead of the next piece (start_read); done joins it
+    auto done = [&](int code, const char *m) { if (reader_on) { reader.join(); reader_on = false; } seterr(m); for (auto *x : mir) if (x) gce_destroy(x); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); if (fo) fclose(fo); close(fd); return code; };
     const size_t PIECE = (size_t)(chunk_reads > 0 && chunk_reads < (1 << 16) ? (1 << 20) : (8 << 20));       // compressed bytes per window (tests shrink it through chunk_reads)
     // GCE_BAM_HOST_INFLATE=1: the BGZF members are inflated by the host threads (the path of the first half of round 3); default: they go to
     // HBM compressed and the GPU inflates them (gce_raw_push_bgzf) -- the host inflates only the window(s) that hold the BAM header
@@ -1357,7 +987,6 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
     uint64_t hdr_end = 0; bool have_header = false;
     gce_params prm = *params;
     Raw<uint8_t> head;                                  // the inflated start of the stream until the header is complete (usually one window)
-    std::thread reader; ssize_t got_next = 0; bool reader_on = false;
     auto start_read = [&](int slot, size_t keep) {
         const uint64_t at = file_off; const size_t want = (size_t)std::min<uint64_t>(PIECE, fsz - at);
         reader_on = true;
@@ -1366,7 +995,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
             static const size_t RP = getenv("GCE_READ_PARTS") ? (size_t)atoi(getenv("GCE_READ_PARTS")) : 4;
             const int R = (int)std::max<size_t>(1, std::min<size_t>({RP, (size_t)T, want >> 20}));
             std::vector<size_t> done_(R, 0); std::vector<std::thread> sub;
-            auto part = [&](int r) { const size_t a = want * (size_t)r / R, z2 = want * (size_t)(r + 1) / R; size_t o = a; while (o < z2) { const ssize_t g = pread(fd, comp[slot].p + keep + o, z2 - o, (off_t)(at + o)); if (g <= 0) break; o += (size_t)g; } done_[r] = o - a; };
+            auto part = [&](int r) { const size_t a = want * (size_t)r / R, z2 = want * (size_t)(r + 1) / R; done_[r] = pread_full(fd, comp[slot].p + keep + a, z2 - a, at + a); };
             for (int r = 1; r < R; r++) sub.emplace_back(part, r);
             part(0);
             for (auto &t : sub) t.join();
@@ -1417,19 +1046,9 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         for (gce_engine *x : mir) if ((r2 = gce_raw_attach_mirror(e, x)) != GCE_OK) { emsg = gce_last_error(x); return r2; }
         return GCE_OK;
     };
-    auto bam_header_bytes = [&]() {                                                       // BAM magic, text, contig table (SAMv1 4.2)
-        std::vector<uint8_t> hdr;
-        auto put32 = [&](uint32_t x) { const uint8_t *p = (const uint8_t *)&x; hdr.insert(hdr.end(), p, p + 4); };
-        hdr.insert(hdr.end(), {'B', 'A', 'M', 1});
-        put32((uint32_t)text.size()); hdr.insert(hdr.end(), text.begin(), text.end());
-        put32((uint32_t)lens.size());
-        for (size_t r = 0; r < lens.size(); r++) { put32((uint32_t)names[r].size() + 1); hdr.insert(hdr.end(), names[r].begin(), names[r].end()); hdr.push_back(0); put32(lens[r]); }
-        return hdr;
-    };
     uint64_t pushed = 0;
     // sam_open(in, "r") takes either format (src/gencore.cpp:164): a file that does not start with the gzip magic is SAM text
-    bool is_sam = false;
-    { uint8_t m2[2] = {0, 0}; is_sam = fsz > 0 && !(fsz >= 2 && pread(fd, m2, 2, 0) == 2 && m2[0] == 0x1f && m2[1] == 0x8b); }
+    const bool is_sam = fsz > 0 && !looks_gzip(fd, fsz);
     if (is_sam) {
         // Pieces of the text are cut at line feeds; the '@' lines in front give the header text and the contig table; alignment lines become BAM
         // records on all host threads (gce_samtext.hpp) in a pinned window that goes to HBM like an inflated BAM window, behind BAM header bytes
@@ -1438,7 +1057,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         std::vector<std::vector<uint8_t>> parts((size_t)T); std::vector<std::string> perr((size_t)T);
         const size_t TP = PIECE < ((size_t)8 << 20) ? PIECE : ((size_t)64 << 20);          // text bytes per piece (tests: 1 MB pieces that cut lines)
         std::thread rd; bool rd_on = false; ssize_t rd_got = 0;
-        auto read_into = [&](char *dst, size_t want, uint64_t off) { const double r0 = now_s(); size_t o = 0; while (o < want) { const ssize_t g = pread(fd, dst + o, want - o, (off_t)(off + o)); if (g <= 0) break; o += (size_t)g; } rd_got = (ssize_t)o; t_read += now_s() - r0; };
+        auto read_into = [&](char *dst, size_t want, uint64_t off) { const double r0 = now_s(); rd_got = (ssize_t)pread_full(fd, dst, want, off); t_read += now_s() - r0; };
         auto bail = [&](int code, const char *m) { if (rd_on) { rd.join(); rd_on = false; } return done(code, m); };
         size_t n = 0;                                                                      // bytes in tbuf[kb]: what the last piece left over + this piece
         {
@@ -1478,7 +1097,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
                     std::string fq;
                     if (p < lim) { const char *q = cur + p; const char *t = (const char *)memchr(q, '\t', lim - p); if (t) fq.assign(q, t); }
                     if ((rc = setup_engine(fq.empty() ? nullptr : fq.c_str(), (size_t)std::max<uint64_t>(fsz + (1u << 20), 1u << 20))) != GCE_OK) return bail(rc, emsg.c_str());
-                    const std::vector<uint8_t> hb = bam_header_bytes();
+                    const std::vector<uint8_t> hb = bam_header_bytes(text, names, lens);
                     hdr_end = hb.size();
                     int32_t tk; if ((rc = gce_raw_push(e, hb.data(), hb.size(), &tk)) != GCE_OK || (rc = gce_submit_wait(e, tk)) != GCE_OK) return bail(rc, gce_last_error(e));
                     pushed += hb.size();
@@ -1530,23 +1149,11 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         // ---- BGZF members of this piece
         blocks.clear();
         size_t off = 0; uint64_t uoff = 0;
-        while (off + 18 <= have) {
-            const uint8_t *p = z + off;
-            if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return done(GCE_ERR_INVALID, "not a BGZF file");
-            const uint16_t xlen = rd16(p + 10);
-            if (off + 12 + (size_t)xlen > have) break;
-            uint32_t bsize = 0; bool found = false;
-            for (uint32_t x = 0; x + 4 <= xlen; ) {
-                const uint8_t *sf = p + 12 + x; const uint16_t sl = rd16(sf + 2);
-                if (x + 4 + (uint32_t)sl > xlen) break;
-                if (sf[0] == 'B' && sf[1] == 'C' && sl == 2) { bsize = (uint32_t)rd16(sf + 4) + 1; found = true; }
-                x += 4 + sl;
-            }
-            if (!found || bsize < 12u + xlen + 8u) return done(GCE_ERR_INVALID, "bad BGZF block");
-            if (off + bsize > have) break;                                              // cut by the piece border: carried over
-            Block b; b.coff = off; b.csize = bsize; b.usize = rd32(p + bsize - 4); b.uoff = uoff;
-            if (b.usize > 0x10000u) return done(GCE_ERR_INVALID, "bad BGZF block (ISIZE above 64 KB)");
-            blocks.push_back(b); off += bsize; uoff += b.usize;
+        for (Member m;;) {
+            const Scan sc = scan_member(z, have, off, m);
+            if (sc == Scan::More) break;                                                // cut by the piece border: carried over
+            if (sc != Scan::Member) return done(GCE_ERR_INVALID, scan_message(sc));
+            blocks.push_back(Block{off, m.bsize, m.isize, uoff}); off += m.bsize; uoff += m.isize;
         }
         const bool last = file_off >= fsz;
         if (last && off != have) return done(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
@@ -1560,57 +1167,45 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         if (have_header && gpu_inflate) {                                               // this piece's members: to HBM as they are
             z_coff.clear(); z_csize.clear(); z_usize.clear();
             for (const Block &bk : blocks) { z_coff.push_back(bk.coff); z_csize.push_back(bk.csize); z_usize.push_back(bk.usize); }
-            if ((rc = gce_raw_push_bgzf(e, z, off, (int32_t)blocks.size(), z_coff.data(), z_csize.data(), z_usize.data(), &comp_ticket[cs])) != GCE_OK) { if (reader_on) reader.join(); return done(rc, gce_last_error(e)); }
+            if ((rc = gce_raw_push_bgzf(e, z, off, (int32_t)blocks.size(), z_coff.data(), z_csize.data(), z_usize.data(), &comp_ticket[cs])) != GCE_OK) return done(rc, gce_last_error(e));
             pushed += uoff;
             if (reader_on) { reader.join(); reader_on = false; have = carry + (size_t)got_next; } else have = 0;
             k++;
             continue;
         }
-        if (win_ticket[ws] >= 0) { const double w0 = now_s(); if ((rc = gce_submit_wait(e, win_ticket[ws])) != GCE_OK) { if (reader_on) reader.join(); return done(rc, gce_last_error(e)); } t_wait += now_s() - w0; win_ticket[ws] = -1; }
-        if (!win[ws].ensure((size_t)uoff + 64)) { if (reader_on) reader.join(); return done(GCE_ERR_OOM, "out of pinned host memory"); }
+        if (win_ticket[ws] >= 0) { const double w0 = now_s(); if ((rc = gce_submit_wait(e, win_ticket[ws])) != GCE_OK) return done(rc, gce_last_error(e)); t_wait += now_s() - w0; win_ticket[ws] = -1; }
+        if (!win[ws].ensure((size_t)uoff + 64)) return done(GCE_ERR_OOM, "out of pinned host memory");
         const double i0 = now_s();
         std::atomic<int> bad{0};
         parallel_for(T, (int64_t)blocks.size(), [&](int, int64_t a, int64_t b2) { for (int64_t q = a; q < b2; q++) if (blocks[q].usize && !inflate_block(z + blocks[q].coff, blocks[q], win[ws].p + blocks[q].uoff)) bad = 1; });
         t_inflate += now_s() - i0;
-        if (bad) { if (reader_on) reader.join(); return done(GCE_ERR_INVALID, "inflate / CRC failure"); }
+        if (bad) return done(GCE_ERR_INVALID, "inflate / CRC failure");
         // ---- header (first window(s)), engine, reference
         if (!have_header) {
             const size_t old = head.size();
-            Raw<uint8_t> h2; h2.resize(old + (size_t)uoff + 1); if (!h2.ok()) { if (reader_on) reader.join(); return done(GCE_ERR_OOM, "out of host memory"); }
+            Raw<uint8_t> h2; h2.resize(old + (size_t)uoff + 1); if (!h2.ok()) return done(GCE_ERR_OOM, "out of host memory");
             if (old) memcpy(h2.data(), head.data(), old);
             memcpy(h2.data() + old, win[ws].p, (size_t)uoff); h2.n = old + (size_t)uoff; head = std::move(h2);
             const uint8_t *u = head.data(); const uint64_t n = head.size();
-            bool complete = false;
-            if (n >= 12 && memcmp(u, "BAM\1", 4) != 0) { if (reader_on) reader.join(); return done(GCE_ERR_INVALID, "not a BAM stream"); }
-            if (n >= 12) {
-                uint64_t p = 4; const uint32_t l_text = rd32(u + p); p += 4;
-                if (p + l_text + 4 <= n) {
-                    const uint64_t tp = p; p += l_text;
-                    const uint32_t n_ref = rd32(u + p); p += 4;
-                    names.clear(); lens.clear(); bool ok = true;
-                    for (uint32_t r = 0; r < n_ref && ok; r++) {
-                        if (p + 4 > n) { ok = false; break; }
-                        const uint32_t ln = rd32(u + p); p += 4;
-                        if (ln == 0 || p + ln + 4 > n) { ok = false; break; }
-                        names.emplace_back((const char *)u + p, ln - 1); p += ln; lens.push_back(rd32(u + p)); p += 4;
-                    }
-                    if (ok && lens.empty()) { if (reader_on) reader.join(); return done(GCE_ERR_INVALID, "this SAM file has no header"); }      // src/gencore.cpp:186-189 (n_targets == 0), as the SAM-text branch does
-                    if (ok) { complete = true; hdr_end = p; text.assign((const char *)u + tp, l_text); }
-                }
-            }
-            if (!complete && last) { if (reader_on) reader.join(); return done(GCE_ERR_INVALID, "truncated header"); }
+            BamHeader bh;
+            const Hdr hs = n >= 12 ? parse_bam_header(u, n, Contigs::Collect, bh, &names, &lens) : Hdr::Incomplete;      // (this runner looks at the magic only once 12 bytes are there)
+            if (hs == Hdr::NotBam) return done(GCE_ERR_INVALID, "not a BAM stream");
+            const bool complete = hs == Hdr::Complete;
+            if (complete && lens.empty()) return done(GCE_ERR_INVALID, "this SAM file has no header");      // src/gencore.cpp:186-189 (n_targets == 0), as the SAM-text branch does
+            if (complete) { hdr_end = bh.hdr_end; text.assign((const char *)u + bh.text_off, bh.l_text); }
+            if (!complete && last) return done(GCE_ERR_INVALID, "truncated header");
             if (complete) {
                 const char *fq = nullptr;                                                 // src/gencore.cpp:207-220: the first record's name
                 if (hdr_end + 36 < n) { const uint32_t lq = u[hdr_end + 12]; if (hdr_end + 36 + lq <= n) fq = (const char *)u + hdr_end + 36; }
-                if ((rc = setup_engine(fq, (size_t)std::max<uint64_t>(fsz * 5, head.size()))) != GCE_OK) { if (reader_on) reader.join(); return done(rc, emsg.c_str()); }
+                if ((rc = setup_engine(fq, (size_t)std::max<uint64_t>(fsz * 5, head.size()))) != GCE_OK) return done(rc, emsg.c_str());
                 // what was inflated so far goes up in one piece (normally: this very window)
-                if (old) { int32_t tk; if ((rc = gce_raw_push(e, head.data(), old, &tk)) != GCE_OK || (rc = gce_submit_wait(e, tk)) != GCE_OK) { if (reader_on) reader.join(); return done(rc, gce_last_error(e)); } pushed += old; }
+                if (old) { int32_t tk; if ((rc = gce_raw_push(e, head.data(), old, &tk)) != GCE_OK || (rc = gce_submit_wait(e, tk)) != GCE_OK) return done(rc, gce_last_error(e)); pushed += old; }
                 head.release();
                 lap("gce_raw_begin + first push");
             }
         }
         if (have_header && uoff) {
-            if ((rc = gce_raw_push(e, win[ws].p, (size_t)uoff, &win_ticket[ws])) != GCE_OK) { if (reader_on) reader.join(); return done(rc, gce_last_error(e)); }
+            if ((rc = gce_raw_push(e, win[ws].p, (size_t)uoff, &win_ticket[ws])) != GCE_OK) return done(rc, gce_last_error(e));
             pushed += uoff;
         }
         if (reader_on) { reader.join(); reader_on = false; have = carry + (size_t)got_next; } else have = 0;
@@ -1746,10 +1341,10 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
         return done(GCE_OK, "");
     }
-    const std::vector<uint8_t> hdr = bam_header_bytes();
+    const std::vector<uint8_t> hdr = bam_header_bytes(text, names, lens);
     fo = fopen(out_path, "wb");
     if (!fo) return done(GCE_ERR_INVALID, "cannot open the output BAM");
-    const uint64_t BS = 0xff00, OC = BS * 256, total = hdr.size() + body;
+    const uint64_t OC = ROUND_BYTES, total = hdr.size() + body;
     const int64_t npieces = (int64_t)((total + OC - 1) / OC);
     Pinned obuf[3]; int32_t otk[3] = {-1, -1, -1};
     Raw<uint8_t> zbuf; zbuf.resize((size_t)256 * 0x10000 + 64);
@@ -1758,10 +1353,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         // level -2 / -3: the record stream is deflated BY THE GPU (gce_deflate.hpp: one lane per BGZF block; -2 fixed Huffman codes, -3 the smallest of
         // dynamic codes, fixed codes and stored per block) -- the host compresses the header's few blocks, then only copies the file image out of HBM
         // piece by piece and writes it
-        for (uint64_t o = 0; o < hdr.size(); o += BS) {
-            const uint32_t zs = (uint32_t)deflate_block(hdr.data() + o, (uint32_t)std::min<uint64_t>(BS, hdr.size() - o), 1, zbuf.data());
-            if (zs == 0 || fwrite(zbuf.data(), 1, zs, fo) != zs) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-        }
+        if (!write_members(fo, hdr.data(), hdr.size(), 1, T, zbuf.data())) return done(GCE_ERR_INVALID, "cannot write the output BAM");
         uint64_t cb = 0;
         if (body && (rc = gce_raw_deflate_output_codes(e, level == -3 ? 1 : 0, &cb)) != GCE_OK) return done(rc, gce_last_error(e));
         const uint64_t PC = (uint64_t)16 << 20; const int64_t np2 = (int64_t)((cb + PC - 1) / PC);
@@ -1773,8 +1365,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
             const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(cb, a2 + PC);
             if (fwrite(obuf[pc & 1].p, 1, (size_t)(z2 - a2), fo) != (size_t)(z2 - a2)) return done(GCE_ERR_INVALID, "cannot write the output BAM");
         }
-        static const uint8_t eof2[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const bool eof_ok2 = fwrite(eof2, 1, 28, fo) == 28;
+        const bool eof_ok2 = fwrite(BGZF_EOF, 1, 28, fo) == 28;
         const bool closed2 = fclose(fo) == 0; fo = nullptr;
         if (!eof_ok2 || !closed2) return done(GCE_ERR_INVALID, "cannot write the output BAM");
         out->write_s = now_s() - t0;
@@ -1796,14 +1387,9 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         if (pc + 1 < npieces && (rc = fetch(pc + 1)) != GCE_OK) return done(rc, "output piece");
         if (otk[pc % 3] >= 0 && (rc = gce_submit_wait(e, otk[pc % 3])) != GCE_OK) return done(rc, gce_last_error(e));
         const uint64_t a = (uint64_t)pc * OC, z2 = std::min<uint64_t>(total, a + OC);
-        const int64_t nb = (int64_t)((z2 - a + BS - 1) / BS);
-        std::vector<uint32_t> zs((size_t)nb, 0);
-        const uint8_t *src = obuf[pc % 3].p;
-        parallel_for(T, nb, [&](int, int64_t x, int64_t y) { for (int64_t q = x; q < y; q++) { const uint64_t o = (uint64_t)q * BS; zs[q] = (uint32_t)deflate_block(src + o, (uint32_t)std::min<uint64_t>(BS, z2 - a - o), level, zbuf.data() + (size_t)q * 0x10000); } });
-        for (int64_t q = 0; q < nb; q++) { if (zs[q] == 0 || fwrite(zbuf.data() + (size_t)q * 0x10000, 1, zs[q], fo) != zs[q]) return done(GCE_ERR_INVALID, "cannot write the output BAM"); }
+        if (!write_members(fo, obuf[pc % 3].p, (size_t)(z2 - a), level, T, zbuf.data())) return done(GCE_ERR_INVALID, "cannot write the output BAM");
     }
-    static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool eof_ok = fwrite(eof_block, 1, 28, fo) == 28;
+    const bool eof_ok = fwrite(BGZF_EOF, 1, 28, fo) == 28;
     const bool closed = fclose(fo) == 0; fo = nullptr;
     if (!eof_ok || !closed) return done(GCE_ERR_INVALID, "cannot write the output BAM");
     out->write_s = now_s() - t0;
@@ -2038,35 +1624,27 @@ struct PassReader {
         if (at >= fsz) { if (have) { msg = "truncated BGZF block at the end of the file"; return -1; } return 0; }
         const size_t want = (size_t)std::min<uint64_t>(piece, fsz - at);
         if (comp.size() < have + want) comp.resize(have + want);
-        size_t o = 0;
-        while (o < want) { const ssize_t g = pread(fd, comp.data() + have + o, want - o, (off_t)(at + o)); if (g <= 0) break; o += (size_t)g; }
-        if (o != want) { msg = "cannot read the input BAM"; return -1; }
+        if (pread_full(fd, comp.data() + have, want, at) != want) { msg = "cannot read the input BAM"; return -1; }
         at += want; have += want;
         blocks.clear();
         size_t c = 0; uint64_t uoff = 0;
-        while (c + 18 <= have) {
-            const uint8_t *p = comp.data() + c;
-            if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) { msg = "not a BGZF file"; return -1; }
-            const uint16_t xlen = rd16(p + 10);
-            if (c + 12 + (size_t)xlen > have) break;
-            uint32_t bsize = 0; bool found = false;
-            for (uint32_t x = 0; x + 4 <= xlen; ) {
-                const uint8_t *sf = p + 12 + x; const uint16_t sl = rd16(sf + 2);
-                if (x + 4 + (uint32_t)sl > xlen) break;
-                if (sf[0] == 'B' && sf[1] == 'C' && sl == 2) { bsize = (uint32_t)rd16(sf + 4) + 1; found = true; }
-                x += 4 + sl;
-            }
-            if (!found || bsize < 12u + xlen + 8u) { msg = "bad BGZF block"; return -1; }
-            if (c + bsize > have) break;
-            Block b; b.coff = c; b.csize = bsize; b.usize = rd32(p + bsize - 4); b.uoff = n + uoff;
-            if (b.usize > 0x10000u) { msg = "bad BGZF block (ISIZE above 64 KB)"; return -1; }
-            blocks.push_back(b); c += bsize; uoff += b.usize;
+        for (Member m;;) {
+            const Scan sc = scan_member(comp.data(), have, c, m);
+            if (sc == Scan::More) break;                                                // cut by the piece's end: it stays for the next piece
+            if (sc != Scan::Member) { msg = scan_message(sc); return -1; }
+            blocks.push_back(Block{c, m.bsize, m.isize, n + uoff}); c += m.bsize; uoff += m.isize;
         }
         if (blocks.empty() && at < fsz) { msg = "BGZF block larger than a window"; return -1; }
         used = c;
         return 1;
     }
     bool last_piece() const { return at >= fsz; }
+    // blocks as the arrays the GPU entry points take (z_coff, z_csize, z_usize); returns the members' inflated bytes
+    uint64_t member_arrays() {
+        z_coff.clear(); z_csize.clear(); z_usize.clear(); uint64_t u_all = 0;
+        for (const Block &b : blocks) { z_coff.push_back(b.coff); z_csize.push_back(b.csize); z_usize.push_back(b.usize); u_all += b.usize; }
+        return u_all;
+    }
     // (the BAM header) the next piece inflated by the host threads behind win[0, n); 1: bytes added, 0: end of the file, -1: error (msg)
     int inflate_next() {
         const int g = members_next();
@@ -2086,6 +1664,29 @@ struct PassReader {
         return 1;
     }
 };
+// A BGZF file from its first byte, window by window, for the index and sort runners: the host reads a piece and finds its members, the
+// first hdr_end inflated bytes (the BAM header) are passed over, window(rd, u_all, sk) hands the members to the GPU (u_all: their inflated
+// bytes, sk: how many of those belong to the header); then the end-of-file checks.  read_s / gpu_s: the two sides' seconds, added to.
+// Returns GCE_OK, GCE_ERR_INVALID with msg set, or what `window` returned with msg left alone (the caller asks its GPU object why).
+template <class F> int for_each_window(PassReader &rd, uint64_t hdr_end, double *read_s, double *gpu_s, std::string &msg, F &&window) {
+    uint64_t skip = hdr_end;
+    for (;;) {
+        double t0 = now_s();
+        const int g = rd.members_next();
+        if (g < 0) { msg = rd.msg; return GCE_ERR_INVALID; }
+        if (g == 0) break;
+        const uint64_t u_all = rd.member_arrays(), sk = std::min<uint64_t>(skip, u_all);
+        *read_s += now_s() - t0; t0 = now_s();
+        const int rc = window(rd, u_all, sk);
+        *gpu_s += now_s() - t0;
+        if (rc != GCE_OK) return rc;
+        skip -= sk;
+        if (rd.last_piece()) break;
+    }
+    if (rd.have != rd.used) { msg = "truncated BGZF block at the end of the file"; return GCE_ERR_INVALID; }
+    if (skip) { msg = "truncated BAM header"; return GCE_ERR_INVALID; }
+    return GCE_OK;
+}
 // what the merge compares per output record (the 32-byte MergeKey of gce_raw_merge_outputs)
 struct PassKey { int32_t tid, pos, mtid, mpos, isize; uint32_t gidx, size, pad; };
 static_assert(sizeof(PassKey) == 32, "PassKey mirrors MergeKey");
@@ -2102,15 +1703,9 @@ inline bool pass_less(const PassKey &a, const PassKey &b) {
 struct PassWriter {
     FILE *fo = nullptr; int level = -1, T = 1; int32_t device = 0; bool sam = false; const std::vector<std::string> *names = nullptr;
     std::vector<uint8_t> buf; Raw<uint8_t> zbuf; std::vector<uint8_t> gz; std::string line; bool ok = true;
-    static constexpr uint64_t BS = 0xff00, CH = BS * 256;
+    static constexpr uint64_t BS = MEMBER_BYTES, CH = ROUND_BYTES;
     ~PassWriter() { if (fo) fclose(fo); }
-    bool host_blocks(const uint8_t *src, size_t n, int lv) {
-        const int64_t nb = (int64_t)((n + BS - 1) / BS);
-        std::vector<uint32_t> zs((size_t)nb, 0);
-        parallel_for(T, nb, [&](int, int64_t x, int64_t y) { for (int64_t q = x; q < y; q++) { const uint64_t o = (uint64_t)q * BS; zs[q] = (uint32_t)deflate_block(src + o, (uint32_t)std::min<uint64_t>(BS, n - o), lv, zbuf.data() + (size_t)q * 0x10000); } });
-        for (int64_t q = 0; q < nb; q++) if (zs[q] == 0 || fwrite(zbuf.data() + (size_t)q * 0x10000, 1, zs[q], fo) != zs[q]) return false;
-        return true;
-    }
+    bool host_blocks(const uint8_t *src, size_t n, int lv) { return write_members(fo, src, n, lv, T, zbuf.data()); }
     bool flush(size_t n) {                               // the first n bytes of buf
         if (!n) return true;
         if (sam) {
@@ -2143,7 +1738,7 @@ struct PassWriter {
     }
     bool close() {
         bool good = flush(buf.size());
-        if (!sam) { static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0}; good = good && fwrite(eof_block, 1, 28, fo) == 28; }
+        if (!sam) good = good && fwrite(BGZF_EOF, 1, 28, fo) == 28;
         good = fclose(fo) == 0 && good; fo = nullptr;
         return good;
     }
@@ -2177,8 +1772,7 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     if (fd < 0) { seterr("cannot open the input BAM"); return GCE_ERR_INVALID; }
     if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the input BAM"); return GCE_ERR_INVALID; }
     const uint64_t fsz = (uint64_t)st.st_size;
-    bool is_sam = false;
-    { uint8_t m2[2] = {0, 0}; is_sam = fsz > 0 && !(fsz >= 2 && pread(fd, m2, 2, 0) == 2 && m2[0] == 0x1f && m2[1] == 0x8b); }
+    const bool is_sam = fsz > 0 && !looks_gzip(fd, fsz);
     // today's single-pass path (gce_run_bam_depth), unchanged, whenever the auto budget is in force and no passes are forced: at once when even a
     // generous bound fits (measured, DESIGN.md 4b: peak ~6.2 x inflated bytes, inflated ~4.3 - 4.7 x the file; the bound takes 6.5 x 6), otherwise
     // after the key pass when the plan needs one pass.  SAM text is never processed in passes; with the auto budget it always runs as today.
@@ -2212,26 +1806,11 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     for (;;) {
         const int g = rd.inflate_next();
         if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str());
-        const uint8_t *u = rd.win.p; const uint64_t n = rd.n;
-        if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return done(GCE_ERR_INVALID, "not a BAM stream");
-        bool complete = false;
-        if (n >= 12) {
-            uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
-            if (q + l_text + 4 <= n) {
-                const uint64_t tp = q; q += l_text;
-                const uint32_t n_ref = rd32(u + q); q += 4;
-                names.clear(); lens.clear(); bool ok = true;
-                for (uint32_t r = 0; r < n_ref && ok; r++) {
-                    if (q + 4 > n) { ok = false; break; }
-                    const uint32_t ln = rd32(u + q); q += 4;
-                    if (ln == 0 || q + ln + 4 > n) { ok = false; break; }
-                    names.emplace_back((const char *)u + q, ln - 1); q += ln; lens.push_back(rd32(u + q)); q += 4;
-                }
-                if (ok && lens.empty()) return done(GCE_ERR_INVALID, "this SAM file has no header");
-                if (ok) { complete = true; hdr_end = q; text.assign((const char *)u + tp, l_text); }
-            }
-        }
-        if (complete) break;
+        BamHeader bh;
+        const Hdr hs = parse_bam_header(rd.win.p, rd.n, Contigs::Collect, bh, &names, &lens);
+        if (hs == Hdr::NotBam) return done(GCE_ERR_INVALID, "not a BAM stream");
+        if (hs == Hdr::Complete && lens.empty()) return done(GCE_ERR_INVALID, "this SAM file has no header");
+        if (hs == Hdr::Complete) { hdr_end = bh.hdr_end; text.assign((const char *)rd.win.p + bh.text_off, bh.l_text); break; }
         if (g == 0) return done(GCE_ERR_INVALID, fsz ? "truncated header" : "empty file");
     }
     const std::vector<uint8_t> hdr_raw(rd.win.p, rd.win.p + hdr_end);
@@ -2281,9 +1860,7 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
             const int g = rd.members_next();
             if (g < 0) { seterr(rd.msg.c_str()); return GCE_ERR_INVALID; }
             if (g == 0) return GCE_OK;
-            rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
-            for (const Block &b : rd.blocks) { rd.z_coff.push_back(b.coff); rd.z_csize.push_back(b.csize); rd.z_usize.push_back(b.usize); u_all += b.usize; }
-            const uint64_t sk = std::min<uint64_t>(skip, u_all);
+            const uint64_t sk = std::min<uint64_t>(skip, rd.member_arrays());
             int32_t cut = 0;
             const int r2 = gce_passes_window(p, x, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, prm.n_targets,
                                              rd.last_piece() ? 1 : 0, &cut);
@@ -2325,15 +1902,7 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     }
     // ---- the passes
     PassWriter wr; wr.level = level; wr.T = T; wr.device = device;
-    std::vector<uint8_t> hdr_out;
-    {   // BAM magic, text, contig table (SAMv1 4.2), as gce_run_bam writes it
-        auto put32 = [&](uint32_t x) { const uint8_t *q = (const uint8_t *)&x; hdr_out.insert(hdr_out.end(), q, q + 4); };
-        hdr_out.insert(hdr_out.end(), {'B', 'A', 'M', 1});
-        put32((uint32_t)text.size()); hdr_out.insert(hdr_out.end(), text.begin(), text.end());
-        put32((uint32_t)lens.size());
-        for (size_t r = 0; r < lens.size(); r++) { put32((uint32_t)names[r].size() + 1); hdr_out.insert(hdr_out.end(), names[r].begin(), names[r].end()); hdr_out.push_back(0); put32(lens[r]); }
-    }
-    if (!wr.open(out_path, text, names, lens, hdr_out)) return done(GCE_ERR_INVALID, "cannot open the output file");
+    if (!wr.open(out_path, text, names, lens, bam_header_bytes(text, names, lens))) return done(GCE_ERR_INVALID, "cannot open the output file");
     std::vector<PassKey> hk, pk, nk; std::vector<uint8_t> hb, pb, nb2, emit;
     std::vector<int64_t> pay_sum;
     int64_t *acc_pre = (int64_t *)&out->pre, *acc_post = (int64_t *)&out->post;
@@ -2437,7 +2006,7 @@ int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, in
         close(fd);
         return code;
     };
-    { uint8_t m2[4] = {0, 0, 0, 0}; if (fsz < 18 || pread(fd, m2, 4, 0) != 4 || m2[0] != 0x1f || m2[1] != 0x8b || m2[2] != 8 || !(m2[3] & 4)) return done(GCE_ERR_INVALID, "not a BGZF file"); }
+    if (!starts_bgzf(fd, fsz)) return done(GCE_ERR_INVALID, "not a BGZF file");
     const int T = threads > 0 ? threads : default_threads();
     // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
     uint64_t hdr_end = 0; int32_t n_ref = 0;
@@ -2446,23 +2015,10 @@ int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, in
         for (;;) {
             const int g = rh.inflate_next();
             if (g < 0) return done(GCE_ERR_INVALID, rh.msg.c_str());
-            const uint8_t *u = rh.win.p; const uint64_t n = rh.n;
-            if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return done(GCE_ERR_INVALID, "not a BAM stream");
-            if (n >= 12) {
-                uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
-                if (q + l_text + 4 <= n) {
-                    q += l_text;
-                    const uint32_t nr = rd32(u + q); q += 4;
-                    bool ok = nr < 0x7FFFFFFFu;
-                    for (uint32_t r = 0; r < nr && ok; r++) {
-                        if (q + 4 > n) { ok = false; break; }
-                        const uint32_t ln = rd32(u + q); q += 4;
-                        if (q + (uint64_t)ln + 4 > n) { ok = false; break; }
-                        q += ln + 4;
-                    }
-                    if (ok) { hdr_end = q; n_ref = (int32_t)nr; break; }
-                }
-            }
+            BamHeader bh;
+            const Hdr hs = parse_bam_header(rh.win.p, rh.n, Contigs::Skip, bh);
+            if (hs == Hdr::NotBam) return done(GCE_ERR_INVALID, "not a BAM stream");
+            if (hs == Hdr::Complete) { hdr_end = bh.hdr_end; n_ref = (int32_t)bh.n_ref; break; }
             if (g == 0) return done(GCE_ERR_INVALID, "truncated BAM header");
         }
     }
@@ -2471,29 +2027,15 @@ int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, in
     if (rc != GCE_OK) return done(rc, "no HIP device");
     // ---- the file from its first byte, window by window: the host reads and finds the members, the GPU inflates and indexes them
     PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? (size_t)window_bytes : ((size_t)64 << 20);
-    uint64_t skip = hdr_end, eod = 0;
+    uint64_t eod = 0;
     double read_s = 0, gpu_s = 0;
-    for (;;) {
-        double t0 = now_s();
-        const int g = rd.members_next();
-        if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str());
-        if (g == 0) break;
-        const uint64_t file_base = rd.at - rd.have;
-        rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
-        for (const Block &k : rd.blocks) {
-            rd.z_coff.push_back(k.coff); rd.z_csize.push_back(k.csize); rd.z_usize.push_back(k.usize); u_all += k.usize;
-            if (k.usize) eod = (file_base + k.coff + k.csize) << 16;                  // rule V: just past the last non-empty member
-        }
-        const uint64_t sk = std::min<uint64_t>(skip, u_all);
-        read_s += now_s() - t0; t0 = now_s();
-        rc = gce_bai_window(b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), file_base, sk, n_ref, rd.last_piece() ? 1 : 0);
-        gpu_s += now_s() - t0;
-        if (rc != GCE_OK) return done(rc, gce_bai_error(b));
-        skip -= sk;
-        if (rd.last_piece()) break;
-    }
-    if (rd.have != rd.used) return done(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
-    if (skip) return done(GCE_ERR_INVALID, "truncated BAM header");
+    std::string wmsg;
+    rc = for_each_window(rd, hdr_end, &read_s, &gpu_s, wmsg, [&](PassReader &r, uint64_t, uint64_t sk) {
+        const uint64_t file_base = r.at - r.have;
+        for (const Block &k : r.blocks) if (k.usize) eod = (file_base + k.coff + k.csize) << 16;      // rule V: just past the last non-empty member
+        return gce_bai_window(b, r.comp.data(), r.used, (int32_t)r.blocks.size(), r.z_coff.data(), r.z_csize.data(), r.z_usize.data(), file_base, sk, n_ref, r.last_piece() ? 1 : 0);
+    });
+    if (rc != GCE_OK) return done(rc, wmsg.empty() ? gce_bai_error(b) : wmsg.c_str());
     double t0 = now_s();
     int64_t counts[5] = {0, 0, 0, 0, 0}, bad = -1; int32_t kind = 0;
     if ((rc = gce_bai_finish(b, n_ref, eod, counts, &bad, &kind)) != GCE_OK) return done(rc, gce_bai_error(b));
@@ -2594,38 +2136,25 @@ struct SortJob {
     int open_input(const char *in_path, const char *out_path, int threads, int lv, uint64_t wb, int32_t dev) {
         level = lv; window_bytes = wb; device = dev;
         { const int rc = open_paths(in_path, out_path, "gce_bam_sort", "BAM"); if (rc != GCE_OK) return rc; }
-        { uint8_t m2[4] = {0, 0, 0, 0}; const bool got = fsz >= 4 && pread(fd, m2, 4, 0) == 4;
-          if (fsz > 0 && !(got && m2[0] == 0x1f && m2[1] == 0x8b)) return fail(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
-          if (fsz < 18 || m2[2] != 8 || !(m2[3] & 4)) return fail(GCE_ERR_INVALID, "not a BGZF file"); }
+        if (fsz > 0 && !(fsz >= 4 && looks_gzip(fd, fsz))) return fail(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
+        if (!starts_bgzf(fd, fsz)) return fail(GCE_ERR_INVALID, "not a BGZF file");
         T = threads > 0 ? threads : default_threads();
         // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
         PassReader rh; rh.fd = fd; rh.fsz = fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
         for (;;) {
             const int g = rh.inflate_next();
             if (g < 0) return fail(GCE_ERR_INVALID, rh.msg);
-            const uint8_t *u = rh.win.p; const uint64_t n = rh.n;
-            if (n >= 4 && memcmp(u, "BAM\1", 4) != 0) return fail(GCE_ERR_INVALID, "not a BAM stream");
-            if (n >= 12) {
-                uint64_t q = 4; const uint32_t l_text = rd32(u + q); q += 4;
-                if (q + l_text + 4 <= n) {
-                    q += l_text;
-                    const uint32_t nr = rd32(u + q); q += 4;
-                    bool ok = nr < 0x7FFFFFFFu;
-                    for (uint32_t r = 0; r < nr && ok; r++) {
-                        if (q + 4 > n) { ok = false; break; }
-                        const uint32_t ln = rd32(u + q); q += 4;
-                        if (q + (uint64_t)ln + 4 > n) { ok = false; break; }
-                        q += ln + 4;
-                    }
-                    if (ok) {                                                        // rule H: the text rewritten, the contig table as it is
-                        hdr_end = q; n_ref = (int32_t)nr;
-                        const std::string text = sort_header_text(u + 8, l_text);
-                        const uint32_t lt = (uint32_t)text.size();
-                        hdr.assign(u, u + 4); hdr.insert(hdr.end(), (const uint8_t *)&lt, (const uint8_t *)&lt + 4);
-                        hdr.insert(hdr.end(), text.begin(), text.end()); hdr.insert(hdr.end(), u + 8 + l_text, u + q);
-                        return GCE_OK;
-                    }
-                }
+            const uint8_t *u = rh.win.p;
+            BamHeader bh;
+            const Hdr hs = parse_bam_header(u, rh.n, Contigs::Skip, bh);
+            if (hs == Hdr::NotBam) return fail(GCE_ERR_INVALID, "not a BAM stream");
+            if (hs == Hdr::Complete) {                                               // rule H: the text rewritten, the contig table as it is
+                hdr_end = bh.hdr_end; n_ref = (int32_t)bh.n_ref;
+                const std::string text = sort_header_text(u + bh.text_off, bh.l_text);
+                const uint32_t lt = (uint32_t)text.size();
+                hdr.assign(u, u + 4); hdr.insert(hdr.end(), (const uint8_t *)&lt, (const uint8_t *)&lt + 4);
+                hdr.insert(hdr.end(), text.begin(), text.end()); hdr.insert(hdr.end(), u + bh.text_off + bh.l_text, u + bh.hdr_end);
+                return GCE_OK;
             }
             if (g == 0) return fail(GCE_ERR_INVALID, "truncated BAM header");
         }
@@ -2634,35 +2163,17 @@ struct SortJob {
     // est: the whole file's inflated bytes, from the ISIZE totals so far and the file size.  read_s / gpu_s: the two sides' seconds, added to.
     template <class F> int stream(double *read_s, double *gpu_s, F &&window) {
         PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? (size_t)window_bytes : ((size_t)64 << 20);
-        uint64_t skip = hdr_end, comp_seen = 0, infl_seen = 0;
-        for (;;) {
-            double t0 = now_s();
-            const int g = rd.members_next();
-            if (g < 0) return fail(GCE_ERR_INVALID, rd.msg);
-            if (g == 0) break;
-            rd.z_coff.clear(); rd.z_csize.clear(); rd.z_usize.clear(); uint64_t u_all = 0;
-            for (const Block &k : rd.blocks) { rd.z_coff.push_back(k.coff); rd.z_csize.push_back(k.csize); rd.z_usize.push_back(k.usize); u_all += k.usize; }
-            const uint64_t sk = std::min<uint64_t>(skip, u_all);
-            comp_seen += rd.used; infl_seen += u_all;
-            const uint64_t est = comp_seen ? (uint64_t)((double)infl_seen * ((double)fsz / (double)comp_seen)) : 0;
-            *read_s += now_s() - t0; t0 = now_s();
-            const int rc = window(rd, sk, est);
-            *gpu_s += now_s() - t0;
-            if (rc != GCE_OK) return fail(rc, gce_sort_error(b));
-            skip -= sk;
-            if (rd.last_piece()) break;
-        }
-        if (rd.have != rd.used) return fail(GCE_ERR_INVALID, "truncated BGZF block at the end of the file");
-        if (skip) return fail(GCE_ERR_INVALID, "truncated BAM header");
-        return GCE_OK;
+        uint64_t comp_seen = 0, infl_seen = 0;
+        msg.clear();
+        const int rc = for_each_window(rd, hdr_end, read_s, gpu_s, msg, [&](PassReader &r, uint64_t u_all, uint64_t sk) {
+            comp_seen += r.used; infl_seen += u_all;
+            return window(r, sk, comp_seen ? (uint64_t)((double)infl_seen * ((double)fsz / (double)comp_seen)) : 0);
+        });
+        return rc != GCE_OK && msg.empty() ? fail(rc, gce_sort_error(b)) : rc;
     }
     // The output comes back in pieces that are multiples of 0xff00: 8192 members when the GPU deflates them (one lane per member), 1024 when
     // the host threads do
     void set_pieces() { codes = level == -3 ? 1 : level == -2 ? 0 : -1; piece = PassWriter::BS * (codes >= 0 ? 8192 : 1024); }
-    bool host_members(const uint8_t *p, size_t n, int lv) {                          // (PassWriter::host_blocks takes 256 members a call)
-        for (size_t o = 0; o < n; o += (size_t)PassWriter::CH) if (!pw.host_blocks(p + o, std::min<size_t>((size_t)PassWriter::CH, n - o), lv)) return false;
-        return true;
-    }
     // the temporary file with the header's members; largest: the most bytes one write_range call will be asked for
     int begin_output(uint64_t largest) {
         const size_t pmax = (size_t)std::min<uint64_t>(piece, largest), hcap = codes >= 0 ? pmax + pmax / 8 + 64 * (pmax / PassWriter::BS + 2) : pmax;
@@ -2673,7 +2184,7 @@ struct SortJob {
         pw.fo = fopen(tmp.c_str(), "wb");
         if (!pw.fo) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
         tmp_made = true;
-        if (!host_members(hdr.data(), hdr.size(), codes >= 0 ? 1 : level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        if (!pw.host_blocks(hdr.data(), hdr.size(), codes >= 0 ? 1 : level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
         return GCE_OK;
     }
     // the first n bytes gce_sort_read has to give, piece by piece, as members of 0xff00 bytes
@@ -2682,7 +2193,7 @@ struct SortJob {
             const size_t nb = (size_t)std::min<uint64_t>(piece, n - o); size_t got = 0;
             const int rc = gce_sort_read(b, o, nb, codes, hb.p, hb.cap, &got);
             if (rc != GCE_OK) return fail(rc, gce_sort_error(b));
-            if (codes >= 0 ? fwrite(hb.p, 1, got, pw.fo) != got : !host_members(hb.p, got, level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+            if (codes >= 0 ? fwrite(hb.p, 1, got, pw.fo) != got : !pw.host_blocks(hb.p, got, level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
         }
         return GCE_OK;
     }
@@ -2753,7 +2264,7 @@ int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int 
     j.level = level; j.device = device; j.window_bytes = window_bytes; j.T = threads > 0 ? threads : default_threads();
     int rc = j.open_paths(in_path, out_path, "gce_sam_sort", "SAM");
     if (rc != GCE_OK) return done(rc);
-    { uint8_t m2[2] = {0, 0}; if (j.fsz >= 2 && pread(j.fd, m2, 2, 0) == 2 && m2[0] == 0x1f && m2[1] == 0x8b) return done(j.fail(GCE_ERR_INVALID, "gce_sam_sort reads SAM text, not BAM")); }
+    if (looks_gzip(j.fd, j.fsz)) return done(j.fail(GCE_ERR_INVALID, "gce_sam_sort reads SAM text, not BAM"));
     (void)gce_device_bytes(nullptr, nullptr, 1);
     if ((rc = gce_sort_create(device, device_budget_bytes, &j.b)) != GCE_OK) return done(j.fail(rc, "no HIP device"));
     const uint64_t W = window_bytes ? std::min<uint64_t>(window_bytes, (uint64_t)1 << 30) : ((uint64_t)64 << 20), LONGEST = (uint64_t)256 << 20;
@@ -2776,7 +2287,7 @@ int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int 
                 if (have) memcpy(nb->p, buf->p, (size_t)have);
                 buf.swap(nb);
             }
-            for (uint64_t g = 0; g < want;) { const ssize_t r = pread(j.fd, buf->p + have + g, (size_t)(want - g), (off_t)(at + g)); if (r <= 0) return done(j.fail(GCE_ERR_INVALID, "cannot read the input SAM")); g += (uint64_t)r; }
+            if (pread_full(j.fd, buf->p + have, (size_t)want, at) != (size_t)want) return done(j.fail(GCE_ERR_INVALID, "cannot read the input SAM"));
             have += want; at += want; last = at >= j.fsz;
         }
         const char *cur = (const char *)buf->p;
@@ -2795,11 +2306,7 @@ int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int 
                 if (!samtext::parse_header_text(text, names, lens)) return done(j.fail(GCE_ERR_INVALID, "bad @SQ line"));
                 n_ref = (int32_t)lens.size(); out->n_ref = n_ref; j.n_ref = n_ref;
                 const std::string ht = sort_header_text((const uint8_t *)text.data(), text.size());      // rule H
-                auto put32 = [&](uint32_t x) { const uint8_t *q = (const uint8_t *)&x; j.hdr.insert(j.hdr.end(), q, q + 4); };
-                j.hdr.assign({'B', 'A', 'M', 1});
-                put32((uint32_t)ht.size()); j.hdr.insert(j.hdr.end(), ht.begin(), ht.end());
-                put32((uint32_t)lens.size());
-                for (size_t r = 0; r < lens.size(); r++) { put32((uint32_t)names[r].size() + 1); j.hdr.insert(j.hdr.end(), names[r].begin(), names[r].end()); j.hdr.push_back(0); put32(lens[r]); }
+                j.hdr = bam_header_bytes(ht, names, lens);
                 std::vector<const char *> np; for (const std::string &x : names) np.push_back(x.c_str());
                 if ((rc = gce_sort_sam_contigs(j.b, n_ref, np.data())) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
             }

@@ -106,6 +106,14 @@ def test_bad_files_are_rejected(built, tmp_path):
     bad.write_bytes(bytes(raw))
     with pytest.raises(GceError):
         BamFile(str(bad))
+    # the file cut inside its first member: within the extra field or the room of the trailer behind it, and further in
+    whole = good.read_bytes()
+    for cut, msg in ((18, "truncated BGZF block header"), (25, "truncated BGZF block header"), (26, "bad BGZF block"), (60, "bad BGZF block"),
+                     (17, "trailing bytes after the last BGZF block")):
+        bad.write_bytes(whole[:cut])
+        with pytest.raises(GceError) as e:
+            BamFile(str(bad))
+        assert str(e.value).endswith(": " + msg), (cut, str(e.value))
 
 
 @pytest.mark.parametrize("level,strategy", [(0, "default"), (1, "default"), (9, "default"), (6, "fixed"), (6, "huffman"), (6, "rle"), (1, "filtered")])

@@ -8,7 +8,9 @@
 //   * canonical Huffman decoding without lookup tables (the count of codes per length, 15 x 10 bits and 15 x 6 bits, lives in registers;
 //     only the symbol permutation -- 288 + 32 entries of 16 bits -- lies in LDS, one column per lane): a table of 2^9 entries per lane
 //     would be 64 KB per wave;
-//   * stored, fixed and dynamic blocks, any number of them per member;
+//   * stored, fixed and dynamic blocks, any number of them per member; of the code sets of a dynamic block exactly those zlib's inflate takes
+//     (complete ones; a literal / length or distance set of one code of one bit; a distance set of no code), so that no member passes here
+//     that the host path and every other reader refuse;
 //   * output straight into the raw stream in HBM: literals byte by byte, matches eight bytes at a time when the distance allows it (a lane
 //     reads back what it wrote itself: ordinary program order);
 //   * CRC-32 of the member (slicing-by-8, tables in LDS, shared by the wave) and its ISIZE are checked; a member that fails any check raises
@@ -81,9 +83,12 @@ __device__ __forceinline__ int inf_decode(InfBits &in, const InfCnt &c, const ui
     return -1;
 }
 
-// lengths[0..n) (this member's scratch in device memory) -> counts + symbol permutation; false: over-subscribed or (for more than one code) incomplete
+// lengths[0..n) (this member's scratch in device memory) -> counts + symbol permutation; false: a set zlib's inflate_table refuses.
+// Complete sets are taken.  An incomplete one only where `lone` allows it (the literal / length and the distance set, never the code length
+// code), and then only with no code at all (the distance set of a block of literals) or with exactly one code of ONE bit: a lone code of
+// two bits or more decodes here as well as anywhere, but no other reader takes the member.
 template <int BITS, int PER>
-__device__ bool inf_construct(const uint8_t *len, int n, InfCnt &c, uint16_t *sym, uint16_t *offs /* 16 entries, column */) {
+__device__ bool inf_construct(const uint8_t *len, int n, InfCnt &c, uint16_t *sym, uint16_t *offs /* 16 entries, column */, bool lone) {
     for (int l = 0; l <= 15; l++) offs[l * INF_T] = 0;
     for (int s = 0; s < n; s++) offs[len[s] * INF_T]++;                       // (counts, parked in offs)
     int left = 1; uint32_t cnt[16];
@@ -97,7 +102,9 @@ __device__ bool inf_construct(const uint8_t *len, int n, InfCnt &c, uint16_t *sy
 #pragma unroll
     for (int l = 1; l <= 15; l++) { offs[l * INF_T] = (uint16_t)o; o += cnt[l]; }
     for (int s = 0; s < n; s++) { const int l = len[s]; if (l) { sym[offs[l * INF_T] * INF_T] = (uint16_t)s; offs[l * INF_T]++; } }
-    return left == 0 || (int)cnt[0] + 1 >= n;                                         // complete, or a single code (RFC 1951 allows one distance code of one bit)
+    if (left == 0) return true;
+    const int coded = n - (int)cnt[0];
+    return lone && (coded == 0 || (coded == 1 && cnt[1] == 1));
 }
 
 __device__ __forceinline__ uint32_t inf_crc_word(const uint32_t (*tab)[256], uint32_t crc, uint64_t w) {
@@ -160,8 +167,8 @@ __global__ __launch_bounds__(INF_T) void k_bgzf_inflate(const uint8_t *comp, con
                 if (type == 1) {                                                      // fixed codes (RFC 1951 3.2.6)
                     for (int s = 0; s < 288; s++) len[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
                     for (int s = 0; s < 30; s++) len[(288 + s)] = 5;
-                    if (!inf_construct<10, 3>(len, 288, cl, sym_l, offs)) { ok = false; break; }
-                    (void)inf_construct<6, 5>(len + 288, 30, cd, sym_d, offs);
+                    if (!inf_construct<10, 3>(len, 288, cl, sym_l, offs, true)) { ok = false; break; }
+                    (void)inf_construct<6, 5>(len + 288, 30, cd, sym_d, offs, true);              // (30 of the 32 five-bit codes: 30 and 31 decode to nothing)
                 } else {                                                              // dynamic codes (3.2.7)
                     const int nlen = (int)in.take(5) + 257, ndist = (int)in.take(5) + 1, ncode = (int)in.take(4) + 4;
                     if (nlen > 286 || ndist > 30) { ok = false; break; }
@@ -169,12 +176,12 @@ __global__ __launch_bounds__(INF_T) void k_bgzf_inflate(const uint8_t *comp, con
                     for (int k = 0; k < ncode; k++) { if (in.cnt < 3) in.refill(); len[INF_CLORD[k]] = (uint8_t)in.take(3); }
                     InfCnt cc;
                     uint16_t *sym_c = sym_d;                                          // the code length code's permutation: in the distance part, which is rebuilt below
-                    if (!inf_construct<10, 3>(len, 19, cc, sym_c, offs)) { ok = false; break; }
+                    if (!inf_construct<10, 3>(len, 19, cc, sym_c, offs, false)) { ok = false; break; }
                     int idx = 0;
                     while (idx < nlen + ndist) {
                         in.refill();
                         const int s = inf_decode<10, 3>(in, cc, sym_c);
-                        if (s < 0) { ok = false; break; }
+                        if (s < 0 || in.over()) { ok = false; break; }                  // (over(): a header that runs on behind the member reads no further than a symbol would)
                         if (s < 16) len[idx++] = (uint8_t)s;
                         else {
                             int prev = 0, rep;
@@ -191,8 +198,8 @@ __global__ __launch_bounds__(INF_T) void k_bgzf_inflate(const uint8_t *comp, con
                     for (int k = ndist - 1; k >= 0; k--) len[(288 + k)] = len[(nlen + k)];
                     for (int k = nlen; k < 288; k++) len[k] = 0;
                     for (int k = ndist; k < 30; k++) len[(288 + k)] = 0;
-                    if (!inf_construct<10, 3>(len, 288, cl, sym_l, offs)) { ok = false; break; }
-                    if (!inf_construct<6, 5>(len + 288, 30, cd, sym_d, offs)) { ok = false; break; }
+                    if (!inf_construct<10, 3>(len, 288, cl, sym_l, offs, true)) { ok = false; break; }
+                    if (!inf_construct<6, 5>(len + 288, 30, cd, sym_d, offs, true)) { ok = false; break; }
                 }
                 // ---- the block's symbols
                 for (;;) {

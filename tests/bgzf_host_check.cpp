@@ -6,6 +6,10 @@
 //   hdr NAME           DIR/NAME at every prefix length, once per dialect: "L=notbam", "L=incomplete" or
 //                      "L=complete:text_off:l_text:n_ref:hdr_end[:name/length ...]" (the names only where the dialect collects them)
 //   codec NAME LEVEL   DIR/NAME through deflate_block, scan_member and inflate_block; the member is appended to DIR/NAME.LEVEL.gz
+//   inflate NAME USIZE DIR/NAME, one member in a heap block of exactly its bytes, through inflate_block into a heap block of exactly USIZE
+//                      bytes: "ok:<CRC-32 of the output, hex>" or "refused" (inflate_raw's word copies stay below out_end by their own condition);
+//                      then the table decoder alone, fastinf::inflate_raw, on blocks of the same kind: "raw:ok:<CRC-32>" or "raw:refused"
+//                      (inflate_block hides it: whatever it refuses or gets wrong goes to zlib)
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -73,6 +77,21 @@ static bool codec_case(const std::string &dir, const std::string &name, int leve
     return ok;
 }
 
+static void inflate_case(const std::string &dir, const std::string &name, uint32_t usize) {
+    const std::string d = slurp(dir + "/" + name);
+    Exact src(d, d.size());
+    uint8_t *dst = (uint8_t *)malloc(usize ? usize : 1);
+    Block b; b.coff = 0; b.csize = (uint32_t)d.size(); b.usize = usize; b.uoff = 0;
+    if (inflate_block(src.p, b, dst)) printf("inflate %s ok:%08lx", name.c_str(), (unsigned long)crc32(crc32(0L, Z_NULL, 0), dst, usize));
+    else printf("inflate %s refused", name.c_str());
+    free(dst);
+    dst = (uint8_t *)malloc(usize ? usize : 1);
+    const uint32_t xlen = rd16(src.p + 10);
+    if (fastinf::inflate_raw(src.p + 12 + xlen, d.size() - 12 - xlen - 8, dst, usize)) printf(" raw:ok:%08lx\n", (unsigned long)crc32(crc32(0L, Z_NULL, 0), dst, usize));
+    else printf(" raw:refused\n");
+    free(dst);
+}
+
 int main(int argc, char **argv) {
     if (argc != 2) { fprintf(stderr, "usage: bgzf_host_check DIR\n"); return 2; }
     const std::string dir = argv[1];
@@ -81,6 +100,7 @@ int main(int argc, char **argv) {
     while (man >> kind >> name) {
         if (kind == "scan") scan_case(name, slurp(dir + "/" + name));
         else if (kind == "hdr") { const std::string d = slurp(dir + "/" + name); hdr_case(name, d, Contigs::Collect); hdr_case(name, d, Contigs::Skip); }
+        else if (kind == "inflate") { uint32_t usize = 0; man >> usize; inflate_case(dir, name, usize); }
         else if (kind == "codec") { int level = 0; man >> level; ok = codec_case(dir, name, level) && ok; }
         else { fprintf(stderr, "unknown case kind %s\n", kind.c_str()); return 2; }
     }

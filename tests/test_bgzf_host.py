@@ -11,6 +11,7 @@ import zlib
 
 import pytest
 
+import deflatecraft
 import pybam
 import recordstreams
 
@@ -198,10 +199,18 @@ CODEC_SIZES = (0, 1, 0xff00, 0x10000)
 CODEC_LEVELS = (-1, 1, 6)
 
 
+# the valid members whose code sets are incomplete: the table decoder takes complete sets alone and hands these to zlib by design
+ZLIBS_BUSINESS = ("single_dist_len1", "no_dist_literal_only", "only_eob_len1", "hclen5")          # (hclen5: no distance code either)
+
+
 # ------------------------------------------------------------------------------------------------------------------------ the program
 def test_host_check_under_sanitizers(tmp_path):
     """bgzf_host_check.cpp (scan_member, parse_bam_header, deflate_block / inflate_block of gce_bgzf.hpp; every input in a heap block of its
-    exact size) built with -fsanitize=address,undefined: its lines are the models' lines, the members it deflates are gzip's"""
+    exact size) built with -fsanitize=address,undefined: its lines are the models' lines, the members it deflates are gzip's.  The
+    hand-built members of deflatecraft go through inflate_block twice, once with the table decoder in front of zlib and once with zlib
+    alone (GCE_BAM_ZLIB_ONLY): the valid ones come out with the catalogue's bytes, the others are refused, both times.  The table decoder
+    is also called on its own: it delivers every valid member's bytes itself, but for the four whose code sets are incomplete, and
+    refuses every invalid one."""
     cxx = shutil.which("g++") or shutil.which("c++")
     if cxx is None:
         cxx = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
@@ -220,15 +229,23 @@ def test_host_check_under_sanitizers(tmp_path):
         (d / ("d%d" % n)).write_bytes(codec_data(n))
         for lv in CODEC_LEVELS:
             man.append("codec d%d %d" % (n, lv)); want.append("codec d%d %d ok" % (n, lv))
+    for name, m, usize, expected in deflatecraft.cases():
+        (d / ("c_" + name)).write_bytes(m); man.append("inflate c_%s %d" % (name, usize))
+        verdict = "refused" if expected is None else "ok:%08x" % (zlib.crc32(expected) & 0xFFFFFFFF)
+        want.append("inflate c_%s %s raw:%s" % (name, verdict, "refused" if name in ZLIBS_BUSINESS else verdict))
     want += ["eof ok", "header_bytes ok"]
     (d / "manifest").write_text("\n".join(man) + "\n")
-    r = subprocess.run(["timeout", "-k", "10", "300", exe, str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    got = r.stdout.splitlines()
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        assert g == w, (g[:300], w[:300])
+    for zlib_only in (False, True):
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+        env.pop("GCE_BAM_ZLIB_ONLY", None)
+        if zlib_only:
+            env["GCE_BAM_ZLIB_ONLY"] = "1"
+        r = subprocess.run(["timeout", "-k", "10", "300", exe, str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=env)
+        assert r.returncode == 0, (zlib_only, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+        got = r.stdout.splitlines()
+        assert len(got) == len(want), zlib_only
+        for g, w in zip(got, want):
+            assert g == w, (zlib_only, g[:300], w[:300])
     for n in CODEC_SIZES:
         for lv in CODEC_LEVELS:
             z = (d / ("d%d.%d.gz" % (n, lv))).read_bytes()

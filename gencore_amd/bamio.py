@@ -223,6 +223,39 @@ def parse_sam(text, ref_names, device=0, out_cap=None):
     return dict(records=out[:ob.value].tobytes(), n_records=int(nr.value), n_host_lines=int(nh.value))
 
 
+def format_sam(records, ref_names, device=0, out_cap=None):
+    """gce_sam_format: whole BAM records (bytes, block_size first, back to back) as SAM alignment lines, made on the GPU.  Returns dict(text
+    (bytes), n_records, n_host_records); raises GceError -- .bad_record is the first record the writer refuses, counting from 0, and .needed
+    the bytes a too small out_cap should have been."""
+    lib = capi.load_library()
+    rec = np.frombuffer(bytes(records), np.uint8)
+    names = (C.c_char_p * max(len(ref_names), 1))(*[n.encode() if isinstance(n, str) else n for n in ref_names])
+    ob, nr, nh, bad = C.c_size_t(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+    err = (C.c_char * 256)()
+    if out_cap is None:                                        # the size first: a line may be many times its record (a B array of small values)
+        rc = lib.gce_sam_format(int(device), rec.ctypes.data if len(rec) else None, len(rec), len(ref_names), names, None, 0, C.byref(ob), C.byref(nr), C.byref(nh), C.byref(bad), err)
+        cap = int(ob.value)
+    else:
+        rc, cap = -4, int(out_cap)
+    out = np.empty(max(cap, 1), np.uint8)
+    if rc == -4:
+        rc = lib.gce_sam_format(int(device), rec.ctypes.data if len(rec) else None, len(rec), len(ref_names), names, out.ctypes.data, cap, C.byref(ob), C.byref(nr), C.byref(nh), C.byref(bad), err)
+    if rc != 0:
+        e = GceError(rc, err.value.decode(errors="replace"))
+        e.bad_record, e.needed = int(bad.value), int(ob.value)
+        raise e
+    return dict(text=out[:ob.value].tobytes(), n_records=int(nr.value), n_host_records=int(nh.value))
+
+
+def sam_format_counters():
+    """gce_get_sam_format_counters: [records formatted on the device, records the host formatted for it, formatter runs, text bytes] of this
+    process."""
+    lib = capi.load_library()
+    out = (C.c_int64 * 4)()
+    lib.gce_get_sam_format_counters(out)
+    return [int(x) for x in out]
+
+
 def sort_bam_passes(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0, min_passes=0):
     """gce_bam_sort_passes: sort_bam for a file of any size: in-core when that fits device_budget_bytes (0 = auto, a fraction of the free device
     memory) and min_passes <= 1, otherwise in output-range passes over the file (at least min_passes of them); the output's bytes are

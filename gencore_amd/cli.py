@@ -86,7 +86,8 @@ def build_parser():
     a("--sort_sam", action="store_true", help="[gencore_amd] the input is SAM text that is not coordinate-sorted: parse and sort it on the GPU first (on the first of "
                                                "--devices, into a temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
-                                           "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). Default 6.")
+                                           "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
+                                           "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
     return p
 
 

@@ -1308,11 +1308,36 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
     const size_t opl = strlen(out_path);
     if (opl >= 3 && strcmp(out_path + opl - 3, "sam") == 0) {
         // an output name that ends in "sam" is written as SAM text (src/gencore.cpp:170-173: sam_open(out, "w")): the header text (with @SQ
-        // lines from the contig table if it has none), then the record stream piece by piece, records -> lines on all host threads
+        // lines from the contig table if it has none), then the record stream piece by piece, records -> lines on all host threads -- or, at
+        // level -2 / -3, the lines made by the GPU (the same bytes)
         fo = fopen(out_path, "w");
         if (!fo) return done(GCE_ERR_INVALID, "cannot open the output SAM");
         const std::string ht = samtext::header_text_for_sam(text, names, lens);
         if (fwrite(ht.data(), 1, ht.size(), fo) != ht.size()) return done(GCE_ERR_INVALID, "cannot write the output SAM");
+        if (level == -2 || level == -3) {
+            // level -2 / -3: the lines are made BY THE GPU from the record stream in HBM (gce_samfmt.hpp: one thread per record for the fields,
+            // 16 lanes per record for SEQ and QUAL) -- the host only copies the text out piece by piece and writes it
+            uint64_t tb = 0;
+            std::vector<const char *> np; for (auto &x : names) np.push_back(x.c_str());
+            if (body && (rc = gce_raw_format_output(e, (int32_t)np.size(), np.data(), &tb)) != GCE_OK) return done(rc, gce_last_error(e)[0] ? gce_last_error(e) : gce_status_message(rc));
+            const uint64_t PC = PIECE < ((size_t)8 << 20) ? ((uint64_t)64 << 10) : ((uint64_t)16 << 20);   // (tests: the small pieces)
+            const int64_t np2 = (int64_t)((tb + PC - 1) / PC);
+            Pinned tbuf[2]; int32_t ttk[2] = {-1, -1};
+            auto fetch2 = [&](int64_t pc) -> int { const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(tb, a2 + PC); if (!tbuf[pc & 1].ensure((size_t)(z2 - a2) + 64)) return GCE_ERR_OOM; return gce_raw_read_text_async(e, a2, tbuf[pc & 1].p, (size_t)(z2 - a2), &ttk[pc & 1]); };
+            if (np2 > 0 && (rc = fetch2(0)) != GCE_OK) return done(rc, "output piece");
+            for (int64_t pc = 0; pc < np2; pc++) {
+                if ((rc = gce_submit_wait(e, ttk[pc & 1])) != GCE_OK) return done(rc, gce_last_error(e));
+                if (pc + 1 < np2 && (rc = fetch2(pc + 1)) != GCE_OK) return done(rc, "output piece");
+                const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(tb, a2 + PC);
+                if (fwrite(tbuf[pc & 1].p, 1, (size_t)(z2 - a2), fo) != (size_t)(z2 - a2)) return done(GCE_ERR_INVALID, "cannot write the output SAM");
+            }
+            const bool closed2 = fclose(fo) == 0; fo = nullptr;
+            if (!closed2) return done(GCE_ERR_INVALID, "cannot write the output SAM");
+            out->write_s = now_s() - t0;
+            out->total_s = now_s() - t_start;
+            out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
+            return done(GCE_OK, "");
+        }
         const uint64_t OC = PIECE < ((size_t)8 << 20) ? ((uint64_t)64 << 10) : ((uint64_t)16 << 20);       // (tests: pieces that cut records)
         const int64_t npieces = (int64_t)((body + OC - 1) / OC);
         Pinned obuf[2]; int32_t otk[2] = {-1, -1};
@@ -1699,7 +1724,7 @@ inline bool pass_less(const PassKey &a, const PassKey &b) {
     return a.gidx < b.gidx;
 }
 // the output file of the pass runner: the record stream arrives in pieces, in order; BGZF blocks of 0xff00 bytes (host threads, or the GPU
-// encoder for levels -2 and -3 as gce_raw_deflate_output_codes), or SAM text for a name that ends in "sam"
+// encoder for levels -2 and -3 as gce_raw_deflate_output_codes), or SAM text for a name that ends in "sam" (by gce_sam_format at levels -2 and -3)
 struct PassWriter {
     FILE *fo = nullptr; int level = -1, T = 1; int32_t device = 0; bool sam = false; const std::vector<std::string> *names = nullptr;
     std::vector<uint8_t> buf; Raw<uint8_t> zbuf; std::vector<uint8_t> gz; std::string line; bool ok = true;
@@ -1708,7 +1733,13 @@ struct PassWriter {
     bool host_blocks(const uint8_t *src, size_t n, int lv) { return write_members(fo, src, n, lv, T, zbuf.data()); }
     bool flush(size_t n) {                               // the first n bytes of buf
         if (!n) return true;
-        if (sam) {
+        if (sam && (level == -2 || level == -3)) {       // the lines by the GPU (gce_samfmt.hpp), as the BAM levels below take the GPU's deflate
+            std::vector<const char *> np; for (auto &x : *names) np.push_back(x.c_str());
+            size_t tb = 0; int64_t nr = 0, nh = 0, bad = -1;
+            int rc = gce_sam_format(device, buf.data(), n, (int32_t)np.size(), np.data(), gz.data(), gz.size(), &tb, &nr, &nh, &bad, nullptr);
+            if (rc == GCE_ERR_OOM && tb > gz.size()) { gz.resize(tb); rc = gce_sam_format(device, buf.data(), n, (int32_t)np.size(), np.data(), gz.data(), gz.size(), &tb, &nr, &nh, &bad, nullptr); }
+            if (rc != GCE_OK || fwrite(gz.data(), 1, tb, fo) != tb) return false;
+        } else if (sam) {
             size_t o = 0;
             while (o < n) { const uint32_t bs = rd32(buf.data() + o); line.clear(); if (!samtext::bam_to_line(buf.data() + o, *names, line) || fwrite(line.data(), 1, line.size(), fo) != line.size()) return false; o += 4ull + bs; }
         } else if (level == -2 || level == -3) {

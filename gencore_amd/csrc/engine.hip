@@ -101,6 +101,7 @@ struct gce_engine {
     // the sharded file runner (gce_raw_attach_mirror / gce_raw_select_shard): engines that receive every push to this one's raw stream; this engine's
     // share of the stream (reads gathered from the full batch; sh_sel = their places in the whole stream)
     DevBuf zo_slots, zo_sizes, zo_off, zo_out; uint64_t zo_bytes = 0;            // the output stream as BGZF blocks (gce_raw_deflate_output)
+    DevBuf sf_text; uint64_t sf_bytes = 0; int64_t raw_body_nrec = -1;           // the output stream as SAM text (gce_raw_format_output); rw_roff holds raw_body_nrec + 1 record starts of rw_body (-1: nobody kept them)
     std::vector<gce_engine *> mirrors;
     DevBuf sh_tickall, sh_shard, sh_flag, sh_sel, sh_core, sh_qoff, sh_coff, sh_soff, sh_loff, sh_nm, sh_nmt, sh_mioff, sh_tick, sh_roff, sh_nmpos, sh_keys, sh_stage; int64_t shard_n = -1;
     bool shard_cut_done = false;          // gce_raw_select_shard applied --quit_after_contig to the WHOLE stream: this engine's gce_process does not look for the cut again
@@ -190,7 +191,7 @@ void gce_destroy(gce_engine *e) {
                      &e->pg, &e->gpl, &e->gpr, &e->grp_begin, &e->grp_n, &e->gl_cluster, &e->g_begin, &e->g_np, &e->deep_list, &e->k64, &e->slow_list, &e->pf_flag, &e->pf_list, &e->pq_flag, &e->pq_list, &e->left_list, &e->slow_args, &e->pd_slab, &e->gen_flag, &e->gen_list, &e->score_list, &e->gw, &e->g_wbase, &e->vb_start, &e->rp_left, &e->rp_right, &e->rp_merge, &e->rp_rmerge,
                      &e->rp_umi, &e->rp_umilen, &e->rp_state, &e->rp_supp, &e->rp_nm, &e->rp_qsl, &e->rp_qsr, &e->scan_part, &e->si};
     for (auto *b : all) b->release();
-    for (DevBuf *b : {&e->z_comp, &e->z_dir, &e->z_err, &e->raw, &e->rw_bad, &e->rw_guess, &e->rw_leave, &e->rw_cnt, &e->rw_base, &e->rw_misc, &e->rw_tmp, &e->rw_off, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body}) b->release();
+    for (DevBuf *b : {&e->z_comp, &e->z_dir, &e->z_err, &e->raw, &e->rw_bad, &e->rw_guess, &e->rw_leave, &e->rw_cnt, &e->rw_base, &e->rw_misc, &e->rw_tmp, &e->rw_off, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body, &e->sf_text}) b->release();
     for (DevBuf *b : {&e->zo_slots, &e->zo_sizes, &e->zo_off, &e->zo_out, &e->p16_flag, &e->p16_list}) b->release();
     for (DevBuf *b : {&e->sh_tickall, &e->sh_shard, &e->sh_flag, &e->sh_sel, &e->sh_core, &e->sh_qoff, &e->sh_coff, &e->sh_soff, &e->sh_loff, &e->sh_nm, &e->sh_nmt, &e->sh_mioff, &e->sh_tick, &e->sh_roff, &e->sh_nmpos, &e->sh_keys, &e->sh_stage}) b->release();
     for (DevBuf *b : {&e->dp_binoff, &e->dp_regoff, &e->dp_rs, &e->dp_re, &e->dp_pmax, &e->dp_sorted, &e->dp_depth, &e->dp_bed, &e->dp_where}) b->release();
@@ -1350,4 +1351,5 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_passes.hpp"
 #include "gce_bai.hpp"
 #include "gce_samdev.hpp"
+#include "gce_samfmt.hpp"
 #include "gce_sort.hpp"

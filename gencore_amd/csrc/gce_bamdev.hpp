@@ -645,6 +645,7 @@ int gce_raw_build_output(gce_engine *e, uint64_t *body_bytes, int64_t *n_out) {
     hipStream_t s = e->stream;
     const uint64_t no = (uint64_t)e->n_out;
     *body_bytes = 0; if (n_out) *n_out = e->n_out;
+    e->raw_body_nrec = -1;
     if (!no) return GCE_OK;
     HIPCHK(e->rw_rsize.ensure((no + 1) * 8)); HIPCHK(e->rw_roff.ensure((no + 1) * 8));
     const uint8_t *u = e->raw.as<uint8_t>();
@@ -659,7 +660,7 @@ int gce_raw_build_output(gce_engine *e, uint64_t *body_bytes, int64_t *n_out) {
     hipLaunchKernelGGL(k_rec_nm, dim3(nb), dim3(256), 0, s, u, (const uint64_t *)e->rw_off.p, (const uint32_t *)e->rw_nmpos.p, r, no, (const uint64_t *)e->rw_roff.p, e->rw_body.as<uint8_t>());
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    e->raw_body_bytes = total;
+    e->raw_body_bytes = total; e->raw_body_nrec = (int64_t)no;                       // (rw_roff: the record starts, for gce_raw_format_output)
     *body_bytes = total;
     return GCE_OK;
 }
@@ -793,6 +794,7 @@ int gce_raw_merge_outputs(gce_engine **engs, int32_t n_engs, uint64_t *body_byte
     if (!engs || n_engs < 1 || !body_bytes) return GCE_ERR_INVALID;
     gce_engine *e = engs[0];
     for (int r = 0; r < n_engs; r++) if (!engs[r] || !engs[r]->raw_mode || !engs[r]->processed || engs[r]->dev_error) return GCE_ERR_INVALID;
+    e->raw_body_nrec = -1;
     std::vector<std::vector<MergeKey>> keys((size_t)n_engs);
     std::vector<uint64_t> base((size_t)n_engs + 1, 0);                              // where shard r's stream lies in the staging buffer
     int64_t total_out = 0, total_reads = 0;
@@ -860,8 +862,13 @@ int gce_raw_merge_outputs(gce_engine **engs, int32_t n_engs, uint64_t *body_byte
         HIPCHK(e->rw_body.ensure(total + 64));
         hipLaunchKernelGGL(k_merge_copy, dim3((unsigned)std::min<uint64_t>(((uint64_t)total_out + 15) / 16, 65535u)), dim3(256), 0, s, (const uint8_t *)e->sh_stage.p, (const uint64_t *)d_from.p, (const uint64_t *)d_to.p,
                            (const uint32_t *)d_size.p, (uint64_t)total_out, e->rw_body.as<uint8_t>());
+        // the merged stream's record starts stay behind for gce_raw_format_output (engs[0]'s own were read into the keys above)
+        HIPCHK(e->rw_roff.ensure(((size_t)total_out + 1) * 8));
+        HIPCHK(hipMemcpyAsync(e->rw_roff.p, d_to.p, (size_t)total_out * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(e->rw_roff.as<uint64_t>() + total_out, &total, 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipGetLastError());
+        e->raw_body_nrec = total_out;
         d_from.release(); d_to.release(); d_size.release();
     }
     e->sh_stage.release();

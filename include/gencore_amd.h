@@ -413,7 +413,9 @@ int gce_bam_from_batch(const char *path, const gce_batch *batch, int32_t n_targe
  * name that ends in "sam" is opened with sam_open(out, "w") and sam_write1 prints text (src/gencore.cpp:164-173,180,187,205,104).
  * gce_run_bam does the same: an input that does not start with the gzip magic is read as SAM text (header lines, then one alignment per
  * line, converted to BAM records on the host threads and pushed to the GPU like an inflated BAM window), an output name that ends in
- * "sam" is written as text.  The two functions below are the conversion alone, on the host (no engine, no GPU).  Conventions of htslib
+ * "sam" is written as text -- at level -2 / -3 by the GPU (gce_raw_format_output below: the lines are made in HBM from the output record
+ * stream, the host copies and writes them), at every other level by samtext::bam_to_line on the host's threads; the file's bytes are the
+ * same either way.  The two functions below are the conversion alone, on the host (no engine, no GPU).  Conventions of htslib
  * that the path can see are kept: an integer tag is stored in the smallest type that holds it ('C' for NM 0..255: src/group.cpp:569
  * patches NM only as 'C'), bin = reg2bin(pos, pos + reference length), QUAL '*' = 0xFF bytes, an unknown RNAME = -1. */
 int gce_sam_to_bam(const char *sam_path, const char *bam_path, int threads, int level, char err[256]);
@@ -667,6 +669,30 @@ int gce_sam_parse(int32_t device, const char *text, size_t n, int32_t n_ref, con
  * *n_host_lines (gce_sam_parse) -- not the copy of the text to the device, the growth of the resident buffers or the keys, which total_s holds. */
 int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
                  size_t device_budget_bytes, gce_sort_run *out, int64_t *n_host_lines, char err[256]);
+/* Whole BAM records through the GPU's line writer (addition under ABI v3; gencore_amd/csrc/gce_samfmt.hpp): the mirror of
+ * gce_sam_parse.  Replaces: htslib's sam_write1 / sam_format1 under the reference when its output name ends in "sam" (sam_open(out, "w"),
+ * src/gencore.cpp:170-173,104), which this library had on host threads only (gce_bam_to_sam, gce_run_bam's SAM output).  records[0, n): whole
+ * BAM records, each with block_size first, back to back, in host memory.  ref_name[0, n_ref): the contigs in the header's order.  out receives
+ * their lines (line feed included) in record order: the bytes gce_bam_to_sam writes for them.  *n_records: the records; *n_host_records: those
+ * of them that hold an `f`, `d` or `B:f` value, which the host printed for %g -- no other record is formatted on the host.  GCE_ERR_INVALID
+ * with the message "bad record in the output stream" for a record the host writer refuses (a block_size below 32, a record that runs past n,
+ * fields that overrun block_size, an optional field that is cut or of an unknown type): *bad_record is the first one, counting from 0 (-1
+ * otherwise) and nothing is written.  GCE_ERR_OOM when out_cap is too small: *out_bytes is the size needed.  Arguments are checked before
+ * any device is touched. */
+int gce_sam_format(int32_t device, const void *records, size_t n, int32_t n_ref, const char *const *ref_name, void *out, size_t out_cap,
+                   size_t *out_bytes, int64_t *n_records, int64_t *n_host_records, int64_t *bad_record, char err[256]);
+/* The output record stream (gce_raw_build_output, or gce_raw_merge_outputs on engs[0]) as SAM text made BY THE GPU, in HBM (addition under ABI
+ * v3) -- replaces sam_write1's text under sam_open(out, "w") (src/gencore.cpp:170-173,104 via htslib): gce_sam_format's kernels over the
+ * resident stream, the record starts taken from what the build / merge left behind, or from a walk of the block sizes when they are not
+ * there.  *text_bytes = the size of the alignment lines; gce_raw_read_text_async copies a piece of them out (ticket -> gce_submit_wait).
+ * The caller writes the header text in front: what gce_run_bam does for an output name that ends in "sam" at `level == -2` or `-3`. */
+int gce_raw_format_output(gce_engine *e, int32_t n_ref, const char *const *ref_name, uint64_t *text_bytes);
+int gce_raw_read_text_async(gce_engine *e, uint64_t offset, void *host, size_t bytes, int32_t *ticket);
+/* The GPU line writer's counters (addition under ABI v3; for tests and diagnostics, as gce_get_index_counters), process-wide since the process
+ * started -- they tell sam_write1's text made by the GPU from the host's (src/gencore.cpp:104): out[0] records formatted on the device,
+ * out[1] records the host formatted for it, out[2] formatter runs (one per gce_sam_format / gce_raw_format_output call that had records),
+ * out[3] text bytes produced. */
+int gce_get_sam_format_counters(int64_t out[4]);
 /* Live and peak device bytes of the engine allocations of the whole PROCESS (every engine, every thread); reset_peak != 0 restarts the peak at
  * the live count.  gce_run_bam_passes resets it on entry: its run->peak_device_bytes covers other engines working in the same process as well. */
 int gce_device_bytes(int64_t *live, int64_t *peak, int32_t reset_peak);

@@ -38,6 +38,7 @@
 #include "../../include/gencore_amd.h"
 #include "gce_bgzf.hpp"
 #include "gce_samtext.hpp"
+#include "gce_fileout.hpp"
 #include "gce_report.hpp"
 
 static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
@@ -56,14 +57,6 @@ int default_threads() {
         fclose(f);
     }
     return std::min(n, 64);
-}
-
-template <class F> void parallel_for(int threads, int64_t n, F f) {          // f(thread, begin, end) over contiguous ranges
-    threads = (int)std::max<int64_t>(1, std::min<int64_t>(threads, n));
-    if (threads == 1) { f(0, (int64_t)0, n); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; t++) th.emplace_back([=] { f(t, n * t / threads, n * (t + 1) / threads); });
-    for (auto &x : th) x.join();
 }
 
 template <class V> bool read_file(const char *path, V &out) {
@@ -195,19 +188,8 @@ int write_bgzf(const char *path, const Raw<uint8_t> &body, int T, int level) {
     return GCE_OK;
 }
 
-// What the file-to-file runners write: src[0, n) as BGZF members of 0xff00 bytes, deflated by all host threads 256 members a round (the
-// slots of zbuf: 256 * 0x10000 + 64 bytes) and written in order.  false: a member could not be deflated or written.
-constexpr uint64_t MEMBER_BYTES = 0xff00, ROUND_BYTES = MEMBER_BYTES * 256;
-bool write_members(FILE *fo, const uint8_t *src, size_t n, int level, int T, uint8_t *zbuf) {
-    for (size_t o = 0; o < n; o += (size_t)ROUND_BYTES) {
-        const size_t m = std::min<size_t>((size_t)ROUND_BYTES, n - o);
-        const int64_t nb = (int64_t)((m + MEMBER_BYTES - 1) / MEMBER_BYTES);
-        uint32_t zs[256] = {0};
-        parallel_for(T, nb, [&](int, int64_t x, int64_t y) { for (int64_t q = x; q < y; q++) { const uint64_t a = (uint64_t)q * MEMBER_BYTES; zs[q] = (uint32_t)deflate_block(src + o + a, (uint32_t)std::min<uint64_t>(MEMBER_BYTES, m - a), level, zbuf + (size_t)q * 0x10000); } });
-        for (int64_t q = 0; q < nb; q++) if (zs[q] == 0 || fwrite(zbuf + (size_t)q * 0x10000, 1, zs[q], fo) != zs[q]) return false;
-    }
-    return true;
-}
+// the message of a C-ABI call into its caller's buffer
+void set_err(char err[256], const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } }
 
 }  // namespace
 
@@ -579,8 +561,8 @@ int gce_bam_from_batch(const char *path, const gce_batch *b, int32_t n_targets, 
 // SAM text -> BAM and back on the host alone (no engine, no GPU): what sam_read1 / sam_write1 do when the reference is given SAM text
 // (src/gencore.cpp:164-173,205,104 via htslib); gce_run_bam takes and writes SAM text through the same line functions (gce_samtext.hpp).
 int gce_sam_to_bam(const char *sam_path, const char *bam_path, int threads, int level, char err[256]) {
-    auto fail = [&](const char *m) { if (err) { strncpy(err, m, 255); err[255] = 0; } return GCE_ERR_INVALID; };
-    if (err) err[0] = 0;
+    auto fail = [&](const char *m) { set_err(err, m); return GCE_ERR_INVALID; };
+    set_err(err, "");
     if (!sam_path || !bam_path) return GCE_ERR_INVALID;
     const int T = threads > 0 ? threads : default_threads();
     std::vector<char> tx;
@@ -592,27 +574,9 @@ int gce_sam_to_bam(const char *sam_path, const char *bam_path, int threads, int 
     std::vector<std::string> names; std::vector<uint32_t> lens;
     if (!samtext::parse_header_text(text, names, lens)) return fail("bad @SQ line");
     samtext::NameMap nmap; nmap.build(names);
-    std::vector<std::vector<uint8_t>> parts((size_t)T); std::vector<std::string> perr((size_t)T);
-    std::vector<size_t> cut((size_t)T + 1, lim); cut[0] = p;
-    for (int t = 1; t < T; t++) { size_t c = p + (lim - p) * (size_t)t / (size_t)T; if (c > p) { const char *q = (const char *)memchr(d + c - 1, '\n', lim - (c - 1)); c = q ? (size_t)(q - d) + 1 : lim; } cut[(size_t)t] = std::max(c, cut[(size_t)t - 1]); }
-    std::atomic<int> bad{0};
-    parallel_for(T, T, [&](int, int64_t a, int64_t b2) {
-        for (int64_t t = a; t < b2; t++) {
-            size_t x = cut[(size_t)t]; const size_t xe = cut[(size_t)t + 1];
-            while (x < xe) {
-                const char *q = (const char *)memchr(d + x, '\n', lim - x); const size_t le = q ? (size_t)(q - d) : lim;
-                if (le > x && !(le == x + 1 && d[x] == '\r') && !samtext::line_to_bam(d + x, d + le, nmap, parts[(size_t)t], perr[(size_t)t])) { bad = 1; return; }
-                x = le + 1;
-            }
-        }
-    });
-    if (bad) { for (auto &m : perr) if (!m.empty()) return fail(m.c_str()); return fail("malformed SAM line"); }
-    std::vector<uint8_t> hdr;
-    auto put32 = [&](uint32_t x) { const uint8_t *q = (const uint8_t *)&x; hdr.insert(hdr.end(), q, q + 4); };
-    hdr.insert(hdr.end(), {'B', 'A', 'M', 1});
-    put32((uint32_t)text.size()); hdr.insert(hdr.end(), text.begin(), text.end());
-    put32((uint32_t)lens.size());
-    for (size_t r = 0; r < lens.size(); r++) { put32((uint32_t)names[r].size() + 1); hdr.insert(hdr.end(), names[r].begin(), names[r].end()); hdr.push_back(0); put32(lens[r]); }
+    std::vector<std::vector<uint8_t>> parts; std::vector<std::string> perr;
+    if (const char *m = lines_to_records(d, p, lim, T, nmap, parts, perr)) return fail(m);
+    const std::vector<uint8_t> hdr = bam_header_bytes(text, names, lens);
     size_t tot = hdr.size(); for (auto &v : parts) tot += v.size();
     Raw<uint8_t> body; body.resize(tot);
     if (!body.ok()) return GCE_ERR_OOM;
@@ -624,23 +588,20 @@ int gce_sam_to_bam(const char *sam_path, const char *bam_path, int threads, int 
 }
 
 int gce_bam_to_sam(const char *bam_path, const char *sam_path, int threads, char err[256]) {
-    auto fail = [&](const char *m) { if (err) { strncpy(err, m, 255); err[255] = 0; } return GCE_ERR_INVALID; };
-    if (err) err[0] = 0;
+    auto fail = [&](const char *m) { set_err(err, m); return GCE_ERR_INVALID; };
+    set_err(err, "");
     if (!bam_path || !sam_path) return GCE_ERR_INVALID;
     const int T = threads > 0 ? threads : default_threads();
     gce_bam *f = nullptr;
     const int rc = gce_bam_open(bam_path, T, &f);
     if (rc != GCE_OK) { fail(f ? f->err.c_str() : "cannot open the input BAM"); if (f) gce_bam_close(f); return rc; }
-    FILE *fo = fopen(sam_path, "w");
-    if (!fo) { gce_bam_close(f); return fail("cannot open the output SAM"); }
-    const std::string ht = samtext::header_text_for_sam(f->text, f->names, f->lens);
-    bool ok = fwrite(ht.data(), 1, ht.size(), fo) == ht.size();
-    std::vector<std::string> lines((size_t)T);
-    std::atomic<int> bad{0};
-    const size_t nr = f->rec.size();
-    parallel_for(T, T, [&](int, int64_t x, int64_t y) { for (int64_t t = x; t < y; t++) { std::string &L = lines[(size_t)t]; const size_t ra = nr * (size_t)t / (size_t)T, rb = nr * (size_t)(t + 1) / (size_t)T; for (size_t q = ra; q < rb; q++) if (!samtext::bam_to_line(f->u.data() + f->rec[q], f->names, L)) { bad = 1; return; } } });
-    for (int t = 0; t < T && ok && !bad; t++) ok = fwrite(lines[(size_t)t].data(), 1, lines[(size_t)t].size(), fo) == lines[(size_t)t].size();
-    ok = (fclose(fo) == 0) && ok;
+    OutFile of;
+    if (!of.open(sam_path, true)) { gce_bam_close(f); return fail("cannot open the output SAM"); }
+    bool ok = of.sam_header(f->text, f->names, f->lens);
+    std::vector<std::string> lines;
+    const bool bad = !records_to_lines(f->u.data(), f->rec, f->names, T, lines);
+    for (int t = 0; t < T && ok && !bad; t++) ok = of.write(lines[(size_t)t].data(), lines[(size_t)t].size());
+    ok = of.close() && ok;
     gce_bam_close(f);
     if (bad) return fail("bad record in the input BAM");
     return ok ? GCE_OK : fail("cannot write the output SAM");
@@ -845,37 +806,77 @@ void gce_bed_free(int32_t n_regions, int32_t *tid, int32_t *start, int32_t *end,
     if (name) { for (int32_t k = 0; k < n_regions; k++) free(name[k]); free(name); }
 }
 
+extern "C++" {
+namespace {
+// ---- what every runner does once the contig table is known
+inline bool umi_auto(const gce_params &prm) { return strcmp(prm.umi_prefix, "auto") == 0; }
+// the contig table into the engine's parameters; the "auto" UMI prefix from the first record's name, or none without one (src/gencore.cpp:207-220)
+void file_params(gce_params &prm, int32_t n_targets, const uint32_t *target_len, const char *first_qname) {
+    prm.n_targets = n_targets; prm.target_len = target_len;
+    if (!umi_auto(prm)) return;
+    memset(prm.umi_prefix, 0, sizeof prm.umi_prefix);
+    if (first_qname) gce_detect_umi_prefix(first_qname, prm.umi_prefix);
+}
+inline bool same_name(const char *a, const char *b) { return strcmp(a, b) == 0; }
+inline bool same_name(const std::string &a, const char *b) { return a == b; }
+// Reference::getData looks contigs up by BAM target name (reference.cpp:43-53): every contig of names[0, n) that the loaded FASTA has goes to
+// the engine; the first status that is not GCE_OK is returned (gce_last_error(e) says why)
+template <class Name> int set_reference(gce_engine *e, const gce_fasta *fa, const Name *names, size_t n) {
+    int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr; int rc;
+    gce_fasta_get(fa, &nc, &ids, &seqs, &flen);
+    for (size_t t = 0; t < n; t++)
+        for (int32_t c = 0; c < nc; c++)
+            if (same_name(names[t], ids[c]) && (rc = gce_set_reference_ascii(e, (int32_t)t, seqs[c], flen[c])) != GCE_OK) return rc;
+    return GCE_OK;
+}
+// the depth report's arrays (freed by gce_depth_run_free), n_regions being set: bins of coverage_step per contig, contigs back to back.  false: out of host memory
+bool depth_alloc(gce_depth_run *depth, const std::vector<uint32_t> &lens, int32_t coverage_step) {
+    const int nt = (int)lens.size();
+    depth->n_targets = nt;
+    depth->bin_off = (int64_t *)calloc((size_t)nt + 1, 8);
+    if (!depth->bin_off) return false;
+    for (int t = 0; t < nt; t++) depth->bin_off[t + 1] = depth->bin_off[t] + 1 + (int64_t)lens[(size_t)t] / coverage_step;
+    const int64_t nb = depth->bin_off[nt];
+    depth->n_bins = nb;
+    depth->pre_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8); depth->post_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8);
+    depth->pre_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8); depth->post_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8);
+    depth->payload_bytes = (2 * (int64_t)GCE_STATS_WORDS + 2 * nb + 2 * (int64_t)depth->n_regions) * 8;
+    return depth->pre_depth && depth->post_depth && depth->pre_bed && depth->post_bed;
+}
+// the payload's words (gce_payload_layout: two Stats blocks in stats_words words, then the depth and BED blocks) into those arrays
+void depth_unpack(gce_depth_run *depth, const int64_t *words, int64_t stats_words) {
+    const int64_t nb = depth->n_bins; const int32_t nreg = depth->n_regions;
+    memcpy(&depth->pre, words, sizeof(gce_stats)); memcpy(&depth->post, words + GCE_STATS_WORDS, sizeof(gce_stats));
+    const int64_t *d0 = words + stats_words;
+    memcpy(depth->pre_depth, d0, (size_t)nb * 8); memcpy(depth->post_depth, d0 + nb, (size_t)nb * 8);
+    memcpy(depth->pre_bed, d0 + 2 * nb, (size_t)nreg * 8); memcpy(depth->post_bed, d0 + 2 * nb + nreg, (size_t)nreg * 8);
+}
+}  // namespace
+}  // extern "C++"
+
 // Gencore::consensus() for a sorted BAM (src/gencore.cpp:162-293) through the C-ABI.
 // The whole-file path of round 2 (gce_bam_open: everything inflated and indexed on the host, struct-of-arrays chunks, gce_bam_write): kept as
 // gce_run_bam_hostcodec for callers that want the host codec end to end and as the fallback of gce_run_bam.
 int gce_run_bam_hostcodec(const char *in_path, const char *out_path, const char *fasta_path, const gce_params *params, int threads,
                 int64_t chunk_reads, int level, gce_bam_run *out, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
+    set_err(err, "");
     if (!in_path || !out_path || !params || !out) return GCE_ERR_INVALID;
     memset(out, 0, sizeof *out);
     const double t_start = now_s();
     gce_bam *f = nullptr; gce_engine *e = nullptr; gce_fasta *fa = nullptr;
     int rc = gce_bam_open(in_path, threads, &f);
-    auto done = [&](int code, const char *m) { seterr(m); if (e) gce_destroy(e); if (f) gce_bam_close(f); if (fa) gce_fasta_free(fa); return code; };
+    auto done = [&](int code, const char *m) { set_err(err, m); if (e) gce_destroy(e); if (f) gce_bam_close(f); if (fa) gce_fasta_free(fa); return code; };
     if (rc != GCE_OK) return done(rc, f ? gce_bam_error(f) : "open failed");
     out->open_s = now_s() - t_start;
     gce_bam_info bi; gce_bam_get_info(f, &bi);
     out->read_s = bi.read_s; out->inflate_s = bi.inflate_s; out->index_s = bi.index_s;
     gce_params prm = *params;
-    prm.n_targets = bi.n_targets; prm.target_len = bi.target_len;
-    if (strcmp(prm.umi_prefix, "auto") == 0) {                                   // src/gencore.cpp:207-220
-        memset(prm.umi_prefix, 0, sizeof prm.umi_prefix);
-        if (bi.n_records > 0) { gce_batch one; if (gce_bam_chunk(f, 0, 1, 0, &one) == GCE_OK) gce_detect_umi_prefix(one.qname, prm.umi_prefix); }
-    }
+    gce_batch one;
+    file_params(prm, bi.n_targets, bi.target_len, umi_auto(prm) && bi.n_records > 0 && gce_bam_chunk(f, 0, 1, 0, &one) == GCE_OK ? one.qname : nullptr);
     if ((rc = gce_create(&prm, &e)) != GCE_OK) return done(rc, gce_status_message(rc));
     if (fasta_path && *fasta_path) {
         if ((rc = gce_fasta_load(fasta_path, threads, &fa)) != GCE_OK) return done(rc, "cannot read the FASTA file");
-        int32_t nc; const char *const *ids; const char *const *seqs; const int64_t *lens;
-        gce_fasta_get(fa, &nc, &ids, &seqs, &lens);
-        for (int32_t t = 0; t < bi.n_targets; t++)                               // Reference::getData looks contigs up by BAM target name (reference.cpp:43-53)
-            for (int32_t c = 0; c < nc; c++)
-                if (strcmp(ids[c], bi.target_name[t]) == 0 && (rc = gce_set_reference_ascii(e, t, seqs[c], lens[c])) != GCE_OK) return done(rc, gce_last_error(e));
+        if ((rc = set_reference(e, fa, bi.target_name, (size_t)bi.n_targets)) != GCE_OK) return done(rc, gce_last_error(e));
     }
     double t0 = now_s();
     if ((rc = gce_reserve(e, bi.n_records, bi.qname_bytes, bi.cigar_words, bi.seq_bytes, bi.qual_bytes)) != GCE_OK) return done(rc, gce_last_error(e));     // (MI tags travel on the streamed path since round 5)
@@ -953,22 +954,21 @@ extern "C" {
 static int run_bam_impl(const char *in_path, const char *out_path, const char *fasta_path, const gce_params *params, int threads,
                         int64_t chunk_reads, int level, gce_bam_run *out, char err[256], int32_t n_shards, const int32_t *devices, int32_t plan_mode,
                         const char *bed_path = nullptr, int32_t coverage_step = 0, gce_depth_run *depth = nullptr) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
+    set_err(err, "");
     if (!in_path || !out_path || !params || !out) return GCE_ERR_INVALID;
     memset(out, 0, sizeof *out);
     out->rss_start_kb = status_kb("VmRSS:");
     const double t_start = now_s();
     const int T = threads > 0 ? threads : default_threads();
     const int fd = open(in_path, O_RDONLY);
-    if (fd < 0) { seterr("cannot open the input BAM"); return GCE_ERR_INVALID; }
+    if (fd < 0) { set_err(err, "cannot open the input BAM"); return GCE_ERR_INVALID; }
     struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the input BAM"); return GCE_ERR_INVALID; }
+    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); set_err(err, "cannot stat the input BAM"); return GCE_ERR_INVALID; }
     const uint64_t fsz = (uint64_t)st.st_size;
-    gce_engine *e = nullptr; gce_fasta *fa = nullptr; FILE *fo = nullptr;
+    gce_engine *e = nullptr; gce_fasta *fa = nullptr; OutFile of;
     std::vector<gce_engine *> mir;                      // the engines of shards 1 .. n_shards - 1 (they receive every push made to e)
     std::thread reader; ssize_t got_next = 0; bool reader_on = false;      // the BAM branch's read-ahead of the next piece (start_read); done joins it
-    auto done = [&](int code, const char *m) { if (reader_on) { reader.join(); reader_on = false; } seterr(m); for (auto *x : mir) if (x) gce_destroy(x); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); if (fo) fclose(fo); close(fd); return code; };
+    auto done = [&](int code, const char *m) { if (reader_on) { reader.join(); reader_on = false; } set_err(err, m); for (auto *x : mir) if (x) gce_destroy(x); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); of.drop(); close(fd); return code; };
     const size_t PIECE = (size_t)(chunk_reads > 0 && chunk_reads < (1 << 16) ? (1 << 20) : (8 << 20));       // compressed bytes per window (tests shrink it through chunk_reads)
     // GCE_BAM_HOST_INFLATE=1: the BGZF members are inflated by the host threads (the path of the first half of round 3); default: they go to
     // HBM compressed and the GPU inflates them (gce_raw_push_bgzf) -- the host inflates only the window(s) that hold the BAM header
@@ -1008,11 +1008,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
     // the contig table is known (BAM header / SAM header lines): engine, reference, raw stream.  first_qname: the first record's name or NULL
     auto setup_engine = [&](const char *first_qname, size_t capacity) -> int {
         have_header = true;
-        prm.n_targets = (int32_t)lens.size(); prm.target_len = lens.data();
-        if (strcmp(prm.umi_prefix, "auto") == 0) {                                       // src/gencore.cpp:207-220: the first record's name
-            memset(prm.umi_prefix, 0, sizeof prm.umi_prefix);
-            if (first_qname) gce_detect_umi_prefix(first_qname, prm.umi_prefix);
-        }
+        file_params(prm, (int32_t)lens.size(), lens.data(), first_qname);
         if (getenv("GCE_RAW_TIMING")) fprintf(stderr, "gce_run_bam: RSS before gce_create %ld MB (entry %ld MB)\n", status_kb("VmRSS:") >> 10, (long)(out->rss_start_kb >> 10));
         lap("up to the header");
         int r2;
@@ -1020,11 +1016,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         // One host thread per engine: gce_create, the reference, and the raw stream's buffers (gce_raw_begin: a few GB of hipMalloc per engine, 0.15 s per GB on a
         // fresh process -- the four engines of a sharded run, set up one after the other, were 0.4 - 1.7 s of "input pipeline" on some boxes) side by side; on a
         // multi-GPU node every device allocates for itself.  The FASTA file is read once, in front.
-        int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr;
-        if (fasta_path && *fasta_path) {
-            if ((r2 = gce_fasta_load(fasta_path, threads, &fa)) != GCE_OK) { emsg = "cannot read the FASTA file"; return r2; }
-            gce_fasta_get(fa, &nc, &ids, &seqs, &flen);
-        }
+        if (fasta_path && *fasta_path && (r2 = gce_fasta_load(fasta_path, threads, &fa)) != GCE_OK) { emsg = "cannot read the FASTA file"; return r2; }
         std::vector<gce_engine *> made((size_t)std::max(n_shards, 1), nullptr);
         std::vector<int> rcs((size_t)made.size(), GCE_OK); std::vector<std::string> msgs(made.size());
         auto setup = [&](int32_t r) {
@@ -1032,9 +1024,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
             gce_engine *x = nullptr; int c2;
             if ((c2 = gce_create(&pr, &x)) != GCE_OK) { rcs[(size_t)r] = c2; msgs[(size_t)r] = gce_status_message(c2); return; }
             made[(size_t)r] = x;
-            for (size_t t = 0; t < lens.size() && fa; t++)                               // Reference::getData looks contigs up by BAM target name (reference.cpp:43-53)
-                for (int32_t c = 0; c < nc; c++)
-                    if (names[t] == ids[c] && (c2 = gce_set_reference_ascii(x, (int32_t)t, seqs[c], flen[c])) != GCE_OK) { rcs[(size_t)r] = c2; msgs[(size_t)r] = gce_last_error(x); return; }
+            if (fa && (c2 = set_reference(x, fa, names.data(), lens.size())) != GCE_OK) { rcs[(size_t)r] = c2; msgs[(size_t)r] = gce_last_error(x); return; }
             if ((c2 = gce_raw_begin(x, capacity)) != GCE_OK) { rcs[(size_t)r] = c2; msgs[(size_t)r] = gce_last_error(x); }
         };
         if (made.size() == 1) setup(0);
@@ -1054,7 +1044,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         // records on all host threads (gce_samtext.hpp) in a pinned window that goes to HBM like an inflated BAM window, behind BAM header bytes
         // made from the SAM header: from there on the stream is the one a BAM file gives.
         Raw<char> tbuf[2]; uint64_t at = 0; bool in_header = true; samtext::NameMap nmap; int wk = 0, kb = 0;
-        std::vector<std::vector<uint8_t>> parts((size_t)T); std::vector<std::string> perr((size_t)T);
+        std::vector<std::vector<uint8_t>> parts; std::vector<std::string> perr;
         const size_t TP = PIECE < ((size_t)8 << 20) ? PIECE : ((size_t)64 << 20);          // text bytes per piece (tests: 1 MB pieces that cut lines)
         std::thread rd; bool rd_on = false; ssize_t rd_got = 0;
         auto read_into = [&](char *dst, size_t want, uint64_t off) { const double r0 = now_s(); rd_got = (ssize_t)pread_full(fd, dst, want, off); t_read += now_s() - r0; };
@@ -1105,23 +1095,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
             }
             if (!in_header && p < lim) {
                 const double i0 = now_s();
-                const char *d = cur;
-                std::vector<size_t> cut((size_t)T + 1, lim);                              // thread t converts the lines that START in [cut[t], cut[t + 1])
-                cut[0] = p;
-                for (int t = 1; t < T; t++) { size_t c = p + (lim - p) * (size_t)t / (size_t)T; if (c > p) { const char *q = (const char *)memchr(d + c - 1, '\n', lim - (c - 1)); c = q ? (size_t)(q - d) + 1 : lim; } cut[(size_t)t] = std::max(c, cut[(size_t)t - 1]); }
-                std::atomic<int> bad{0};
-                parallel_for(T, T, [&](int, int64_t a, int64_t b2) {
-                    for (int64_t t = a; t < b2; t++) {
-                        std::vector<uint8_t> &o = parts[(size_t)t]; o.clear();
-                        size_t x = cut[(size_t)t]; const size_t xe = cut[(size_t)t + 1];
-                        while (x < xe) {
-                            const char *q = (const char *)memchr(d + x, '\n', lim - x); const size_t le = q ? (size_t)(q - d) : lim;
-                            if (le > x && !(le == x + 1 && d[x] == '\r') && !samtext::line_to_bam(d + x, d + le, nmap, o, perr[(size_t)t])) { bad = 1; return; }
-                            x = le + 1;
-                        }
-                    }
-                });
-                if (bad) { for (auto &m : perr) if (!m.empty()) return bail(GCE_ERR_INVALID, m.c_str()); return bail(GCE_ERR_INVALID, "malformed SAM line"); }
+                if (const char *m = lines_to_records(cur, p, lim, T, nmap, parts, perr)) return bail(GCE_ERR_INVALID, m);
                 size_t tot = 0; std::vector<size_t> po((size_t)T + 1, 0);
                 for (int t = 0; t < T; t++) { po[(size_t)t] = tot; tot += parts[(size_t)t].size(); }
                 if (tot) {
@@ -1229,17 +1203,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
             std::vector<const char *> np; for (auto &x : names) np.push_back(x.c_str());
             if ((rc = gce_bed_load(bed_path, (int32_t)np.size(), np.data(), &depth->n_regions, &depth->region_tid, &depth->region_start, &depth->region_end, nullptr)) != GCE_OK) return done(rc, "cannot read the BED file");
         }
-        const int nt = (int)lens.size();
-        depth->n_targets = nt;
-        depth->bin_off = (int64_t *)calloc((size_t)nt + 1, 8);
-        if (!depth->bin_off) return done(GCE_ERR_OOM, "out of host memory");
-        for (int t = 0; t < nt; t++) depth->bin_off[t + 1] = depth->bin_off[t] + 1 + (int64_t)lens[(size_t)t] / coverage_step;
-        const int64_t nb = depth->bin_off[nt];
-        depth->n_bins = nb;
-        depth->pre_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8); depth->post_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8);
-        depth->pre_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8); depth->post_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8);
-        if (!depth->pre_depth || !depth->post_depth || !depth->pre_bed || !depth->post_bed) return done(GCE_ERR_OOM, "out of host memory");
-        depth->payload_bytes = (2 * (int64_t)GCE_STATS_WORDS + 2 * nb + 2 * (int64_t)depth->n_regions) * 8;
+        if (!depth_alloc(depth, lens, coverage_step)) return done(GCE_ERR_OOM, "out of host memory");
     }
     auto engine_payload = [&](gce_engine *x) -> int {
         if (!depth) return GCE_OK;
@@ -1297,126 +1261,55 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
         if ((rc = gce_stats_payload_sum(all.data(), (int32_t)all.size(), &pay, &lay)) != GCE_OK) return done(rc, gce_last_error(e));
         std::vector<int64_t> host((size_t)lay.total_words);
         if ((rc = gce_stats_payload_read(e, pay, lay.total_words, host.data())) != GCE_OK) return done(rc, gce_last_error(e));
-        const int64_t nb = depth->n_bins; const int32_t nreg = depth->n_regions;
-        if (lay.n_bins != nb || lay.n_regions != nreg) return done(GCE_ERR_INVALID, "payload layout");
-        memcpy(&depth->pre, host.data(), sizeof(gce_stats)); memcpy(&depth->post, host.data() + GCE_STATS_WORDS, sizeof(gce_stats));
-        const int64_t *d0 = host.data() + lay.stats_words;
-        memcpy(depth->pre_depth, d0, (size_t)nb * 8); memcpy(depth->post_depth, d0 + nb, (size_t)nb * 8);
-        memcpy(depth->pre_bed, d0 + 2 * nb, (size_t)nreg * 8); memcpy(depth->post_bed, d0 + 2 * nb + nreg, (size_t)nreg * 8);
+        if (lay.n_bins != depth->n_bins || lay.n_regions != depth->n_regions) return done(GCE_ERR_INVALID, "payload layout");
+        depth_unpack(depth, host.data(), lay.stats_words);
     }
-    // ---- the output file: header bytes + the record stream from HBM, in pieces; deflate by all threads, written in order
-    const size_t opl = strlen(out_path);
-    if (opl >= 3 && strcmp(out_path + opl - 3, "sam") == 0) {
-        // an output name that ends in "sam" is written as SAM text (src/gencore.cpp:170-173: sam_open(out, "w")): the header text (with @SQ
-        // lines from the contig table if it has none), then the record stream piece by piece, records -> lines on all host threads -- or, at
-        // level -2 / -3, the lines made by the GPU (the same bytes)
-        fo = fopen(out_path, "w");
-        if (!fo) return done(GCE_ERR_INVALID, "cannot open the output SAM");
-        const std::string ht = samtext::header_text_for_sam(text, names, lens);
-        if (fwrite(ht.data(), 1, ht.size(), fo) != ht.size()) return done(GCE_ERR_INVALID, "cannot write the output SAM");
-        if (level == -2 || level == -3) {
-            // level -2 / -3: the lines are made BY THE GPU from the record stream in HBM (gce_samfmt.hpp: one thread per record for the fields,
-            // 16 lanes per record for SEQ and QUAL) -- the host only copies the text out piece by piece and writes it
+    // ---- the output file: its header, then a stream in HBM walked in pieces (pump_pieces), each piece handed to what writes it.  A name that ends
+    //      in "sam" is written as SAM text (src/gencore.cpp:170-173: sam_open(out, "w")), any other as BGZF members.  Levels -2 / -3: the stream is what
+    //      the GPU made of the records -- the lines (gce_samfmt.hpp) or the deflated file image (gce_deflate.hpp: -2 fixed Huffman codes, -3 the smallest
+    //      of dynamic codes, fixed codes and stored per block) -- and the host only copies it out and writes it.  Other levels: the stream is the records,
+    //      made into lines or, behind the header's bytes, deflated into members of 0xff00 bytes by all host threads.
+    const bool gpu_out = level == -2 || level == -3;
+    if (!of.open(out_path, OutFile::named_sam(out_path))) return done(GCE_ERR_INVALID, of.sam ? "cannot open the output SAM" : "cannot open the output BAM");
+    const char *const cannot = of.sam ? "cannot write the output SAM" : "cannot write the output BAM";
+    const char *why = "output piece";                                                      // what a walk that ends early says: a fetch's words, unless wait or sink put theirs
+    Pinned obuf[2];
+    const uint64_t SMALL = PIECE < ((size_t)8 << 20) ? ((uint64_t)64 << 10) : ((uint64_t)16 << 20);   // pieces of text and of records for lines (tests: small ones that cut records)
+    auto records = [&](uint64_t o, uint8_t *dst, size_t n, int32_t *tk) { return gce_raw_read_output_async(e, o, dst, n, tk); };
+    auto wait = [&](int32_t tk) { const int r = gce_submit_wait(e, tk); if (r != GCE_OK) why = gce_last_error(e); return r; };
+    auto written = [&](bool ok) -> int { if (ok) return GCE_OK; why = cannot; return GCE_ERR_INVALID; };
+    auto write = [&](const uint8_t *p, size_t n) { return written(of.write(p, n)); };
+    if (of.sam) {
+        if (!of.sam_header(text, names, lens)) return done(GCE_ERR_INVALID, cannot);
+        if (gpu_out) {
             uint64_t tb = 0;
             std::vector<const char *> np; for (auto &x : names) np.push_back(x.c_str());
             if (body && (rc = gce_raw_format_output(e, (int32_t)np.size(), np.data(), &tb)) != GCE_OK) return done(rc, gce_last_error(e)[0] ? gce_last_error(e) : gce_status_message(rc));
-            const uint64_t PC = PIECE < ((size_t)8 << 20) ? ((uint64_t)64 << 10) : ((uint64_t)16 << 20);   // (tests: the small pieces)
-            const int64_t np2 = (int64_t)((tb + PC - 1) / PC);
-            Pinned tbuf[2]; int32_t ttk[2] = {-1, -1};
-            auto fetch2 = [&](int64_t pc) -> int { const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(tb, a2 + PC); if (!tbuf[pc & 1].ensure((size_t)(z2 - a2) + 64)) return GCE_ERR_OOM; return gce_raw_read_text_async(e, a2, tbuf[pc & 1].p, (size_t)(z2 - a2), &ttk[pc & 1]); };
-            if (np2 > 0 && (rc = fetch2(0)) != GCE_OK) return done(rc, "output piece");
-            for (int64_t pc = 0; pc < np2; pc++) {
-                if ((rc = gce_submit_wait(e, ttk[pc & 1])) != GCE_OK) return done(rc, gce_last_error(e));
-                if (pc + 1 < np2 && (rc = fetch2(pc + 1)) != GCE_OK) return done(rc, "output piece");
-                const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(tb, a2 + PC);
-                if (fwrite(tbuf[pc & 1].p, 1, (size_t)(z2 - a2), fo) != (size_t)(z2 - a2)) return done(GCE_ERR_INVALID, "cannot write the output SAM");
-            }
-            const bool closed2 = fclose(fo) == 0; fo = nullptr;
-            if (!closed2) return done(GCE_ERR_INVALID, "cannot write the output SAM");
-            out->write_s = now_s() - t0;
-            out->total_s = now_s() - t_start;
-            out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
-            return done(GCE_OK, "");
+            rc = pump_pieces(nullptr, 0, tb, SMALL, obuf, [&](uint64_t o, uint8_t *dst, size_t n, int32_t *tk) { return gce_raw_read_text_async(e, o, dst, n, tk); }, wait, write);
+        } else {
+            std::vector<uint8_t> cur; std::vector<uint64_t> ro; std::vector<std::string> lines;
+            rc = pump_pieces(nullptr, 0, body, SMALL, obuf, records, wait, [&](const uint8_t *p, size_t n) -> int {
+                cur.insert(cur.end(), p, p + n);                                           // behind the record a piece border cut
+                const size_t o = whole_records(cur.data(), cur.size(), ro);
+                if (o == SIZE_MAX || !records_to_lines(cur.data(), ro, names, T, lines)) { why = "bad record in the output stream"; return GCE_ERR_INVALID; }
+                for (const std::string &L : lines) if (!of.write(L.data(), L.size())) return written(false);
+                cur.erase(cur.begin(), cur.begin() + (ptrdiff_t)o);
+                return GCE_OK;
+            });
+            if (rc == GCE_OK && !cur.empty()) { rc = GCE_ERR_INVALID; why = "truncated record at the end of the output stream"; }
         }
-        const uint64_t OC = PIECE < ((size_t)8 << 20) ? ((uint64_t)64 << 10) : ((uint64_t)16 << 20);       // (tests: pieces that cut records)
-        const int64_t npieces = (int64_t)((body + OC - 1) / OC);
-        Pinned obuf[2]; int32_t otk[2] = {-1, -1};
-        auto fetch = [&](int64_t pc) -> int { const uint64_t a2 = (uint64_t)pc * OC, z2 = std::min<uint64_t>(body, a2 + OC); if (!obuf[pc & 1].ensure((size_t)(z2 - a2) + 64)) return GCE_ERR_OOM; return gce_raw_read_output_async(e, a2, obuf[pc & 1].p, (size_t)(z2 - a2), &otk[pc & 1]); };
-        std::vector<uint8_t> cur; std::vector<uint64_t> ro; std::vector<std::string> lines((size_t)T);
-        if (npieces > 0 && (rc = fetch(0)) != GCE_OK) return done(rc, "output piece");
-        for (int64_t pc = 0; pc < npieces; pc++) {
-            if (otk[pc & 1] >= 0 && (rc = gce_submit_wait(e, otk[pc & 1])) != GCE_OK) return done(rc, gce_last_error(e));
-            const uint64_t a2 = (uint64_t)pc * OC, z2 = std::min<uint64_t>(body, a2 + OC);
-            cur.insert(cur.end(), obuf[pc & 1].p, obuf[pc & 1].p + (z2 - a2));                // behind the record a piece border cut
-            if (pc + 1 < npieces && (rc = fetch(pc + 1)) != GCE_OK) return done(rc, "output piece");
-            ro.clear();
-            uint64_t o = 0;
-            while (o + 4 <= cur.size()) { const uint32_t bs = rd32(cur.data() + o); if (bs < 32) return done(GCE_ERR_INVALID, "bad record in the output stream"); if (o + 4 + bs > cur.size()) break; ro.push_back(o); o += 4ull + bs; }
-            std::atomic<int> bad{0};
-            parallel_for(T, T, [&](int, int64_t x, int64_t y) { for (int64_t t = x; t < y; t++) { std::string &L = lines[(size_t)t]; L.clear(); const size_t ra = ro.size() * (size_t)t / (size_t)T, rb = ro.size() * (size_t)(t + 1) / (size_t)T; for (size_t q = ra; q < rb; q++) if (!samtext::bam_to_line(cur.data() + ro[q], names, L)) { bad = 1; return; } } });
-            if (bad) return done(GCE_ERR_INVALID, "bad record in the output stream");
-            for (int t = 0; t < T; t++) if (!lines[(size_t)t].empty() && fwrite(lines[(size_t)t].data(), 1, lines[(size_t)t].size(), fo) != lines[(size_t)t].size()) return done(GCE_ERR_INVALID, "cannot write the output SAM");
-            cur.erase(cur.begin(), cur.begin() + (ptrdiff_t)o);
-        }
-        if (!cur.empty()) return done(GCE_ERR_INVALID, "truncated record at the end of the output stream");
-        const bool closed = fclose(fo) == 0; fo = nullptr;
-        if (!closed) return done(GCE_ERR_INVALID, "cannot write the output SAM");
-        out->write_s = now_s() - t0;
-        out->total_s = now_s() - t_start;
-        out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
-        return done(GCE_OK, "");
+    } else {
+        const std::vector<uint8_t> hdr = bam_header_bytes(text, names, lens);
+        if (!of.reserve()) return done(GCE_ERR_OOM, "out of host memory");
+        if (gpu_out) {
+            uint64_t cb = 0;
+            if (!of.header_members(hdr, level, true, T)) return done(GCE_ERR_INVALID, cannot);
+            if (body && (rc = gce_raw_deflate_output_codes(e, level == -3 ? 1 : 0, &cb)) != GCE_OK) return done(rc, gce_last_error(e));
+            rc = pump_pieces(nullptr, 0, cb, (uint64_t)16 << 20, obuf, [&](uint64_t o, uint8_t *dst, size_t n, int32_t *tk) { return gce_raw_read_deflated_async(e, o, dst, n, tk); }, wait, write);
+        } else rc = pump_pieces(hdr.data(), hdr.size(), body, ROUND_BYTES, obuf, records, wait, [&](const uint8_t *p, size_t n) { return written(of.members(p, n, level, T)); });
     }
-    const std::vector<uint8_t> hdr = bam_header_bytes(text, names, lens);
-    fo = fopen(out_path, "wb");
-    if (!fo) return done(GCE_ERR_INVALID, "cannot open the output BAM");
-    const uint64_t OC = ROUND_BYTES, total = hdr.size() + body;
-    const int64_t npieces = (int64_t)((total + OC - 1) / OC);
-    Pinned obuf[3]; int32_t otk[3] = {-1, -1, -1};
-    Raw<uint8_t> zbuf; zbuf.resize((size_t)256 * 0x10000 + 64);
-    if (!zbuf.ok()) return done(GCE_ERR_OOM, "out of host memory");
-    if (level == -2 || level == -3) {
-        // level -2 / -3: the record stream is deflated BY THE GPU (gce_deflate.hpp: one lane per BGZF block; -2 fixed Huffman codes, -3 the smallest of
-        // dynamic codes, fixed codes and stored per block) -- the host compresses the header's few blocks, then only copies the file image out of HBM
-        // piece by piece and writes it
-        if (!write_members(fo, hdr.data(), hdr.size(), 1, T, zbuf.data())) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-        uint64_t cb = 0;
-        if (body && (rc = gce_raw_deflate_output_codes(e, level == -3 ? 1 : 0, &cb)) != GCE_OK) return done(rc, gce_last_error(e));
-        const uint64_t PC = (uint64_t)16 << 20; const int64_t np2 = (int64_t)((cb + PC - 1) / PC);
-        auto fetch2 = [&](int64_t pc) -> int { const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(cb, a2 + PC); if (!obuf[pc & 1].ensure((size_t)(z2 - a2) + 64)) return GCE_ERR_OOM; return gce_raw_read_deflated_async(e, a2, obuf[pc & 1].p, (size_t)(z2 - a2), &otk[pc & 1]); };
-        if (np2 > 0 && (rc = fetch2(0)) != GCE_OK) return done(rc, "output piece");
-        for (int64_t pc = 0; pc < np2; pc++) {
-            if ((rc = gce_submit_wait(e, otk[pc & 1])) != GCE_OK) return done(rc, gce_last_error(e));
-            if (pc + 1 < np2 && (rc = fetch2(pc + 1)) != GCE_OK) return done(rc, "output piece");
-            const uint64_t a2 = (uint64_t)pc * PC, z2 = std::min<uint64_t>(cb, a2 + PC);
-            if (fwrite(obuf[pc & 1].p, 1, (size_t)(z2 - a2), fo) != (size_t)(z2 - a2)) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-        }
-        const bool eof_ok2 = fwrite(BGZF_EOF, 1, 28, fo) == 28;
-        const bool closed2 = fclose(fo) == 0; fo = nullptr;
-        if (!eof_ok2 || !closed2) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-        out->write_s = now_s() - t0;
-        out->total_s = now_s() - t_start;
-        out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
-        return done(GCE_OK, "");
-    }
-    auto fetch = [&](int64_t pc) -> int {                                                 // piece pc of (header ++ body) into obuf[pc % 3]
-        const uint64_t a = (uint64_t)pc * OC, z2 = std::min<uint64_t>(total, a + OC);
-        Pinned &b = obuf[pc % 3];
-        if (!b.ensure((size_t)(z2 - a) + 64)) return GCE_ERR_OOM;
-        uint64_t at = a;
-        if (at < hdr.size()) { const uint64_t hn = std::min<uint64_t>(hdr.size(), z2) - at; memcpy(b.p, hdr.data() + at, hn); at += hn; }
-        if (at < z2) return gce_raw_read_output_async(e, at - hdr.size(), b.p + (at - a), (size_t)(z2 - at), &otk[pc % 3]);
-        otk[pc % 3] = -1; return GCE_OK;
-    };
-    if (npieces > 0 && (rc = fetch(0)) != GCE_OK) return done(rc, "output piece");
-    for (int64_t pc = 0; pc < npieces; pc++) {
-        if (pc + 1 < npieces && (rc = fetch(pc + 1)) != GCE_OK) return done(rc, "output piece");
-        if (otk[pc % 3] >= 0 && (rc = gce_submit_wait(e, otk[pc % 3])) != GCE_OK) return done(rc, gce_last_error(e));
-        const uint64_t a = (uint64_t)pc * OC, z2 = std::min<uint64_t>(total, a + OC);
-        if (!write_members(fo, obuf[pc % 3].p, (size_t)(z2 - a), level, T, zbuf.data())) return done(GCE_ERR_INVALID, "cannot write the output BAM");
-    }
-    const bool eof_ok = fwrite(BGZF_EOF, 1, 28, fo) == 28;
-    const bool closed = fclose(fo) == 0; fo = nullptr;
-    if (!eof_ok || !closed) return done(GCE_ERR_INVALID, "cannot write the output BAM");
+    if (rc != GCE_OK) return done(rc, why);
+    if (!of.close()) return done(GCE_ERR_INVALID, cannot);
     out->write_s = now_s() - t0;
     out->total_s = now_s() - t_start;
     out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
@@ -1433,8 +1326,7 @@ static int run_bam_impl(const char *in_path, const char *out_path, const char *f
 // RCCL all-reduce instead, bench.py).  The result equals gce_run_bam's: same records, same order, same Stats.
 int gce_run_bam_sharded_hostcodec(const char *in_path, const char *out_path, const char *fasta_path, const gce_params *params, int32_t n_shards, const int32_t *devices,
                                   int32_t plan_mode, int threads, int level, gce_bam_run *out, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
+    set_err(err, "");
     if (!in_path || !out_path || !params || !out || n_shards < 1 || n_shards > 64 || !devices) return GCE_ERR_INVALID;
     memset(out, 0, sizeof *out);
     const double t_start = now_s();
@@ -1442,17 +1334,15 @@ int gce_run_bam_sharded_hostcodec(const char *in_path, const char *out_path, con
     std::vector<gce_engine *> eng((size_t)n_shards, nullptr);
     int32_t *ev_tid = nullptr, *ev_pos = nullptr;
     int rc = gce_bam_open(in_path, threads, &f);
-    auto done = [&](int code, const char *m) { seterr(m); for (auto *e : eng) if (e) gce_destroy(e); if (f) gce_bam_close(f); if (fa) gce_fasta_free(fa); gce_free(ev_tid); gce_free(ev_pos); return code; };
+    auto done = [&](int code, const char *m) { set_err(err, m); for (auto *e : eng) if (e) gce_destroy(e); if (f) gce_bam_close(f); if (fa) gce_fasta_free(fa); gce_free(ev_tid); gce_free(ev_pos); return code; };
     if (rc != GCE_OK) return done(rc, f ? gce_bam_error(f) : "open failed");
     out->open_s = now_s() - t_start;
     gce_bam_info bi; gce_bam_get_info(f, &bi);
     out->read_s = bi.read_s; out->inflate_s = bi.inflate_s; out->index_s = bi.index_s;
     gce_params prm = *params;
-    prm.n_targets = bi.n_targets; prm.target_len = bi.target_len; prm.tick_offset = 0; prm.trailing_flush = 0;
-    if (strcmp(prm.umi_prefix, "auto") == 0) {                                   // src/gencore.cpp:207-220
-        memset(prm.umi_prefix, 0, sizeof prm.umi_prefix);
-        if (bi.n_records > 0) { gce_batch one; if (gce_bam_chunk(f, 0, 1, 0, &one) == GCE_OK) gce_detect_umi_prefix(one.qname, prm.umi_prefix); }
-    }
+    prm.tick_offset = 0; prm.trailing_flush = 0;
+    gce_batch one;
+    file_params(prm, bi.n_targets, bi.target_len, umi_auto(prm) && bi.n_records > 0 && gce_bam_chunk(f, 0, 1, 0, &one) == GCE_OK ? one.qname : nullptr);
     const int64_t n = bi.n_records;
     const int T = f->threads;
     const uint8_t *u = f->u.data();
@@ -1723,56 +1613,50 @@ inline bool pass_less(const PassKey &a, const PassKey &b) {
     if (a.isize != b.isize) return a.isize < b.isize;
     return a.gidx < b.gidx;
 }
-// the output file of the pass runner: the record stream arrives in pieces, in order; BGZF blocks of 0xff00 bytes (host threads, or the GPU
-// encoder for levels -2 and -3 as gce_raw_deflate_output_codes), or SAM text for a name that ends in "sam" (by gce_sam_format at levels -2 and -3)
+// the output of the pass runner (and, for its members and its close, of the sort runners): the record stream arrives in pieces of whole
+// records, in order; it is written a round of members at a time -- by the host threads, or at levels -2 and -3 by the GPU encoder as
+// gce_raw_deflate_output_codes -- or, to a SAM file, piece by piece as lines (by gce_sam_format at levels -2 and -3)
 struct PassWriter {
-    FILE *fo = nullptr; int level = -1, T = 1; int32_t device = 0; bool sam = false; const std::vector<std::string> *names = nullptr;
-    std::vector<uint8_t> buf; Raw<uint8_t> zbuf; std::vector<uint8_t> gz; std::string line; bool ok = true;
+    OutFile out; int level = -1, T = 1; int32_t device = 0; const std::vector<std::string> *names = nullptr;
+    std::vector<uint8_t> buf, gz; std::vector<uint64_t> ro; std::vector<std::string> lines;
     static constexpr uint64_t BS = MEMBER_BYTES, CH = ROUND_BYTES;
-    ~PassWriter() { if (fo) fclose(fo); }
-    bool host_blocks(const uint8_t *src, size_t n, int lv) { return write_members(fo, src, n, lv, T, zbuf.data()); }
+    bool gpu() const { return level == -2 || level == -3; }
     bool flush(size_t n) {                               // the first n bytes of buf
         if (!n) return true;
-        if (sam && (level == -2 || level == -3)) {       // the lines by the GPU (gce_samfmt.hpp), as the BAM levels below take the GPU's deflate
+        if (out.sam && gpu()) {                          // the lines by the GPU (gce_samfmt.hpp), as the BAM levels below take the GPU's deflate
             std::vector<const char *> np; for (auto &x : *names) np.push_back(x.c_str());
             size_t tb = 0; int64_t nr = 0, nh = 0, bad = -1;
             int rc = gce_sam_format(device, buf.data(), n, (int32_t)np.size(), np.data(), gz.data(), gz.size(), &tb, &nr, &nh, &bad, nullptr);
             if (rc == GCE_ERR_OOM && tb > gz.size()) { gz.resize(tb); rc = gce_sam_format(device, buf.data(), n, (int32_t)np.size(), np.data(), gz.data(), gz.size(), &tb, &nr, &nh, &bad, nullptr); }
-            if (rc != GCE_OK || fwrite(gz.data(), 1, tb, fo) != tb) return false;
-        } else if (sam) {
-            size_t o = 0;
-            while (o < n) { const uint32_t bs = rd32(buf.data() + o); line.clear(); if (!samtext::bam_to_line(buf.data() + o, *names, line) || fwrite(line.data(), 1, line.size(), fo) != line.size()) return false; o += 4ull + bs; }
-        } else if (level == -2 || level == -3) {
+            if (rc != GCE_OK || !out.write(gz.data(), tb)) return false;
+        } else if (out.sam) {
+            if (whole_records(buf.data(), n, ro) != n || !records_to_lines(buf.data(), ro, *names, T, lines)) return false;
+            for (const std::string &L : lines) if (!out.write(L.data(), L.size())) return false;
+        } else if (gpu()) {
             size_t zb = 0;
             if (gz.size() < n + n / 8 + 64 * (n / BS + 1) + 64) gz.resize(n + n / 8 + 64 * (n / BS + 1) + 64);
-            if (gce_bgzf_deflate_codes(device, buf.data(), n, (uint32_t)BS, level == -3 ? 1 : 0, gz.data(), gz.size(), &zb) != GCE_OK || fwrite(gz.data(), 1, zb, fo) != zb) return false;
-        } else if (!host_blocks(buf.data(), n, level)) return false;
+            if (gce_bgzf_deflate_codes(device, buf.data(), n, (uint32_t)BS, level == -3 ? 1 : 0, gz.data(), gz.size(), &zb) != GCE_OK || !out.write(gz.data(), zb)) return false;
+        } else if (!out.members(buf.data(), n, level, T)) return false;
         buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)n);
         return true;
     }
+    // the header: a SAM file's text; at levels -2 / -3 members of its own; at host levels it goes in front of the records, into their members
     bool open(const char *path, const std::string &text, const std::vector<std::string> &nm, const std::vector<uint32_t> &lens, const std::vector<uint8_t> &hdr) {
-        const size_t pl = strlen(path); sam = pl >= 3 && strcmp(path + pl - 3, "sam") == 0; names = &nm;
-        fo = fopen(path, sam ? "w" : "wb");
-        if (!fo) return false;
-        if (sam) { const std::string ht = samtext::header_text_for_sam(text, nm, lens); return fwrite(ht.data(), 1, ht.size(), fo) == ht.size(); }
-        zbuf.resize((size_t)256 * 0x10000 + 64);
-        if (!zbuf.ok()) return false;
-        if (level == -2 || level == -3) return host_blocks(hdr.data(), hdr.size(), 1);          // (as gce_run_bam: the header's blocks by the host)
+        names = &nm;
+        if (!out.open(path, OutFile::named_sam(path))) return false;
+        if (out.sam) return out.sam_header(text, nm, lens);
+        if (!out.reserve()) return false;
+        if (gpu()) return out.header_members(hdr, level, true, T);
         buf.assign(hdr.begin(), hdr.end());
         return true;
     }
     bool records(const uint8_t *p, size_t n) {           // whole records
-        if (sam) { buf.insert(buf.end(), p, p + n); return flush(buf.size()); }
         buf.insert(buf.end(), p, p + n);
+        if (out.sam) return flush(buf.size());
         while (buf.size() >= CH) if (!flush((size_t)CH)) return false;
         return true;
     }
-    bool close() {
-        bool good = flush(buf.size());
-        if (!sam) good = good && fwrite(BGZF_EOF, 1, 28, fo) == 28;
-        good = fclose(fo) == 0 && good; fo = nullptr;
-        return good;
-    }
+    bool close() { const bool good = flush(buf.size()); return out.close() && good; }
 };
 }  // namespace
 }  // extern "C++"
@@ -1781,8 +1665,7 @@ extern "C" {
 int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fasta_path, const char *bed_path, int32_t coverage_step, const gce_params *params,
                        int32_t device, int threads, int level, size_t device_budget_bytes, int32_t min_passes, size_t window_bytes,
                        gce_bam_run *out, gce_depth_run *depth, gce_pass_run *run, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
+    set_err(err, "");
     if (!in_path || !out_path || !params || !out || !depth || !run || min_passes < 0 || min_passes > 64 || coverage_step <= 0) return GCE_ERR_INVALID;
     memset(out, 0, sizeof *out); memset(run, 0, sizeof *run); memset(depth, 0, sizeof *depth);
     const double t_start = now_s();
@@ -1794,14 +1677,14 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     if (auto_budget) {
         size_t fr = 0, tot = 0;
         const int r0 = gce_device_mem_info(device, &fr, &tot);
-        if (r0 != GCE_OK) { seterr("no device"); return r0; }
+        if (r0 != GCE_OK) { set_err(err, "no device"); return r0; }
         budget = (uint64_t)((double)fr * GCE_PASS_BUDGET_FRACTION);
     }
     run->budget_bytes = (int64_t)budget;
     struct stat st;
     const int fd = open(in_path, O_RDONLY);
-    if (fd < 0) { seterr("cannot open the input BAM"); return GCE_ERR_INVALID; }
-    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the input BAM"); return GCE_ERR_INVALID; }
+    if (fd < 0) { set_err(err, "cannot open the input BAM"); return GCE_ERR_INVALID; }
+    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); set_err(err, "cannot stat the input BAM"); return GCE_ERR_INVALID; }
     const uint64_t fsz = (uint64_t)st.st_size;
     const bool is_sam = fsz > 0 && !looks_gzip(fd, fsz);
     // today's single-pass path (gce_run_bam_depth), unchanged, whenever the auto budget is in force and no passes are forced: at once when even a
@@ -1817,18 +1700,18 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     };
     if (is_sam) {
         close(fd);
-        if (min_passes > 1) { seterr("SAM text input is not processed in passes"); return GCE_ERR_INVALID; }
+        if (min_passes > 1) { set_err(err, "SAM text input is not processed in passes"); return GCE_ERR_INVALID; }
         if (!auto_budget && est > budget) {
             char m[256]; snprintf(m, sizeof m, "SAM text input of %llu bytes needs an estimated %llu device bytes, the budget is %llu: SAM input is not processed in passes (convert it to BAM)",
                                   (unsigned long long)fsz, (unsigned long long)est, (unsigned long long)budget);
-            seterr(m); return GCE_ERR_OOM;
+            set_err(err, m); return GCE_ERR_OOM;
         }
         return single();
     }
     if (single_ok && est <= budget) { close(fd); return single(); }
     const int T = threads > 0 ? threads : default_threads();
     gce_engine *e = nullptr; gce_fasta *fa = nullptr; gce_passes *p = nullptr;
-    auto done = [&](int code, const char *m) { seterr(m); if (p) gce_passes_destroy(p); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); close(fd); if (code != GCE_OK) gce_depth_run_free(depth); return code; };
+    auto done = [&](int code, const char *m) { set_err(err, m); if (p) gce_passes_destroy(p); if (e) gce_destroy(e); if (fa) gce_fasta_free(fa); close(fd); if (code != GCE_OK) gce_depth_run_free(depth); return code; };
     // 64 MB of compressed bytes per window by default: the GPU inflate runs one lane per BGZF member and wants thousands of members per launch
     // (8 MB windows, ~400 members each, made a cfg3 4 M pass 2.6 s instead of ~1 s)
     PassReader rd; rd.fd = fd; rd.fsz = fsz; rd.T = T; rd.piece = window_bytes > 0 ? window_bytes : ((size_t)64 << 20);
@@ -1846,21 +1729,15 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
     }
     const std::vector<uint8_t> hdr_raw(rd.win.p, rd.win.p + hdr_end);
     // ---- engine and reference (src/gencore.cpp:207-220: "auto" UMI prefix from the first record's name)
-    gce_params prm = *params; prm.device = device; prm.n_targets = (int32_t)lens.size(); prm.target_len = lens.data();
-    if (strcmp(prm.umi_prefix, "auto") == 0) {
-        memset(prm.umi_prefix, 0, sizeof prm.umi_prefix);
-        while (rd.n < hdr_end + 36 || rd.n < hdr_end + 36 + rd.win.p[hdr_end + 12]) { const int g = rd.inflate_next(); if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str()); if (g == 0) break; }
-        if (rd.n >= hdr_end + 36 && rd.n >= hdr_end + 36 + rd.win.p[hdr_end + 12]) gce_detect_umi_prefix((const char *)rd.win.p + hdr_end + 36, prm.umi_prefix);
-    }
+    gce_params prm = *params; prm.device = device;
+    auto name_there = [&] { return rd.n >= hdr_end + 36 && rd.n >= hdr_end + 36 + rd.win.p[hdr_end + 12]; };
+    if (umi_auto(prm)) while (!name_there()) { const int g = rd.inflate_next(); if (g < 0) return done(GCE_ERR_INVALID, rd.msg.c_str()); if (g == 0) break; }
+    file_params(prm, (int32_t)lens.size(), lens.data(), name_there() ? (const char *)rd.win.p + hdr_end + 36 : nullptr);
     int rc;
     if ((rc = gce_create(&prm, &e)) != GCE_OK) return done(rc, gce_status_message(rc));
     if (fasta_path && *fasta_path) {
         if ((rc = gce_fasta_load(fasta_path, threads, &fa)) != GCE_OK) return done(rc, "cannot read the FASTA file");
-        int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr;
-        gce_fasta_get(fa, &nc, &ids, &seqs, &flen);
-        for (size_t t = 0; t < lens.size(); t++)
-            for (int32_t c = 0; c < nc; c++)
-                if (names[t] == ids[c] && (rc = gce_set_reference_ascii(e, (int32_t)t, seqs[c], flen[c])) != GCE_OK) return done(rc, gce_last_error(e));
+        if ((rc = set_reference(e, fa, names.data(), lens.size())) != GCE_OK) return done(rc, gce_last_error(e));
         gce_fasta_free(fa); fa = nullptr;
     }
     if ((rc = gce_passes_create(device, prm.max_contig, prm.flush_period, &p)) != GCE_OK) return done(rc, "pass state");
@@ -1869,19 +1746,7 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
         std::vector<const char *> np; for (auto &x : names) np.push_back(x.c_str());
         if ((rc = gce_bed_load(bed_path, (int32_t)np.size(), np.data(), &depth->n_regions, &depth->region_tid, &depth->region_start, &depth->region_end, nullptr)) != GCE_OK) return done(rc, "cannot read the BED file");
     }
-    {
-        const int nt = (int)lens.size();
-        depth->n_targets = nt;
-        depth->bin_off = (int64_t *)calloc((size_t)nt + 1, 8);
-        if (!depth->bin_off) return done(GCE_ERR_OOM, "out of host memory");
-        for (int t = 0; t < nt; t++) depth->bin_off[t + 1] = depth->bin_off[t] + 1 + (int64_t)lens[(size_t)t] / coverage_step;
-        const int64_t nb = depth->bin_off[nt];
-        depth->n_bins = nb;
-        depth->pre_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8); depth->post_depth = (int64_t *)calloc((size_t)std::max<int64_t>(nb, 1), 8);
-        depth->pre_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8); depth->post_bed = (int64_t *)calloc((size_t)std::max(depth->n_regions, 1), 8);
-        if (!depth->pre_depth || !depth->post_depth || !depth->pre_bed || !depth->post_bed) return done(GCE_ERR_OOM, "out of host memory");
-        depth->payload_bytes = (2 * (int64_t)GCE_STATS_WORDS + 2 * nb + 2 * (int64_t)depth->n_regions) * 8;
-    }
+    if (!depth_alloc(depth, lens, coverage_step)) return done(GCE_ERR_OOM, "out of host memory");
     // the file from its first byte, piece by piece: its BGZF members go to the GPU (gce_passes_window inflates and indexes them there; the
     // header's bytes are passed over); e == NULL: the key pass
     auto stream = [&](gce_engine *x) -> int {
@@ -1889,13 +1754,13 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
         uint64_t skip = hdr_end;
         for (;;) {
             const int g = rd.members_next();
-            if (g < 0) { seterr(rd.msg.c_str()); return GCE_ERR_INVALID; }
+            if (g < 0) { set_err(err, rd.msg.c_str()); return GCE_ERR_INVALID; }
             if (g == 0) return GCE_OK;
             const uint64_t sk = std::min<uint64_t>(skip, rd.member_arrays());
             int32_t cut = 0;
             const int r2 = gce_passes_window(p, x, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, prm.n_targets,
                                              rd.last_piece() ? 1 : 0, &cut);
-            if (r2 != GCE_OK) { seterr(gce_passes_error(p)); return r2; }
+            if (r2 != GCE_OK) { set_err(err, gce_passes_error(p)); return r2; }
             skip -= sk;
             if (cut || rd.last_piece()) return GCE_OK;
         }
@@ -1989,13 +1854,7 @@ int gce_run_bam_passes(const char *in_path, const char *out_path, const char *fa
         run->pass_s[k] = now_s() - tp;
     }
     if (!wr.close()) return done(GCE_ERR_INVALID, "cannot write the output file");
-    if (!pay_sum.empty()) {
-        const int64_t nb = depth->n_bins; const int32_t nreg = depth->n_regions;
-        memcpy(&depth->pre, pay_sum.data(), sizeof(gce_stats)); memcpy(&depth->post, pay_sum.data() + GCE_STATS_WORDS, sizeof(gce_stats));
-        const int64_t *d0 = pay_sum.data() + 2 * GCE_STATS_WORDS;
-        memcpy(depth->pre_depth, d0, (size_t)nb * 8); memcpy(depth->post_depth, d0 + nb, (size_t)nb * 8);
-        memcpy(depth->pre_bed, d0 + 2 * nb, (size_t)nreg * 8); memcpy(depth->post_bed, d0 + 2 * nb + nreg, (size_t)nreg * 8);
-    }
+    if (!pay_sum.empty()) depth_unpack(depth, pay_sum.data(), 2 * GCE_STATS_WORDS);
     run->peak_device_bytes = peak_now();
     out->total_s = now_s() - t_start;
     out->peak_rss_kb = status_kb("VmHWM:"); out->rss_end_kb = status_kb("VmRSS:");
@@ -2017,20 +1876,19 @@ int gce_bai_finish(gce_bai *b, int32_t n_ref, uint64_t eod, int64_t counts[5], i
 int gce_bai_serialise(gce_bai *b, int32_t n_ref, uint8_t **out, size_t *out_bytes);
 
 int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, int threads, uint64_t window_bytes, gce_bai_run *out, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
-    if (!bam_path || !bai_path || !out) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    set_err(err, "");
+    if (!bam_path || !bai_path || !out) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
     memset(out, 0, sizeof *out);
     const double t_start = now_s();
     const int fd = open(bam_path, O_RDONLY);
-    if (fd < 0) { seterr("cannot open the BAM file"); return GCE_ERR_INVALID; }
+    if (fd < 0) { set_err(err, "cannot open the BAM file"); return GCE_ERR_INVALID; }
     struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); seterr("cannot stat the BAM file"); return GCE_ERR_INVALID; }
+    if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); set_err(err, "cannot stat the BAM file"); return GCE_ERR_INVALID; }
     const uint64_t fsz = (uint64_t)st.st_size;
     const std::string tmp = std::string(bai_path) + ".tmp" + std::to_string((long long)getpid());
     gce_bai *b = nullptr; FILE *fo = nullptr;
     auto done = [&](int code, const char *m) {
-        seterr(m);
+        set_err(err, m);
         if (b) gce_bai_destroy(b);
         if (fo) { fclose(fo); fo = nullptr; }
         if (code != GCE_OK) unlink(tmp.c_str());
@@ -2143,7 +2001,7 @@ struct SortJob {
     // everything is let go; a failed call leaves no output
     void close_all(int code) {
         if (b) { gce_sort_destroy(b); b = nullptr; }
-        if (pw.fo) { fclose(pw.fo); pw.fo = nullptr; }
+        pw.out.drop();
         if (code != GCE_OK && tmp_made) unlink(tmp.c_str());
         if (fd >= 0) { ::close(fd); fd = -1; }
     }
@@ -2210,12 +2068,10 @@ struct SortJob {
         const size_t pmax = (size_t)std::min<uint64_t>(piece, largest), hcap = codes >= 0 ? pmax + pmax / 8 + 64 * (pmax / PassWriter::BS + 2) : pmax;
         if (largest && !hb.ensure(hcap)) return fail(GCE_ERR_OOM, "out of pinned host memory");
         pw.level = level; pw.T = T; pw.device = device;
-        pw.zbuf.resize((size_t)256 * 0x10000 + 64);
-        if (!pw.zbuf.ok()) return fail(GCE_ERR_OOM, "out of host memory");
-        pw.fo = fopen(tmp.c_str(), "wb");
-        if (!pw.fo) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        if (!pw.out.reserve()) return fail(GCE_ERR_OOM, "out of host memory");
+        if (!pw.out.open(tmp.c_str(), false)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
         tmp_made = true;
-        if (!pw.host_blocks(hdr.data(), hdr.size(), codes >= 0 ? 1 : level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+        if (!pw.out.header_members(hdr, level, codes >= 0, T)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
         return GCE_OK;
     }
     // the first n bytes gce_sort_read has to give, piece by piece, as members of 0xff00 bytes
@@ -2224,7 +2080,7 @@ struct SortJob {
             const size_t nb = (size_t)std::min<uint64_t>(piece, n - o); size_t got = 0;
             const int rc = gce_sort_read(b, o, nb, codes, hb.p, hb.cap, &got);
             if (rc != GCE_OK) return fail(rc, gce_sort_error(b));
-            if (codes >= 0 ? fwrite(hb.p, 1, got, pw.fo) != got : !pw.host_blocks(hb.p, got, level)) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
+            if (!(codes >= 0 ? pw.out.write(hb.p, got) : pw.out.members(hb.p, got, level, T))) return fail(GCE_ERR_INVALID, "cannot write the output BAM");
         }
         return GCE_OK;
     }
@@ -2240,14 +2096,13 @@ struct SortJob {
 extern "C" {
 
 int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, gce_sort_run *out, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
-    if (!in_path || !out_path || !out) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    set_err(err, "");
+    if (!in_path || !out_path || !out) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
     memset(out, 0, sizeof *out);
-    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    if (level < -3 || level > 9) { set_err(err, "level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
     const double t_start = now_s();
     SortJob j;
-    auto done = [&](int code) { j.close_all(code); seterr(j.msg.c_str()); return code; };
+    auto done = [&](int code) { j.close_all(code); set_err(err, j.msg.c_str()); return code; };
     int rc = j.open_input(in_path, out_path, threads, level, window_bytes, device);
     if (rc != GCE_OK) return done(rc);
     const int32_t n_ref = j.n_ref;
@@ -2284,14 +2139,13 @@ int gce_bam_sort(const char *in_path, const char *out_path, int32_t device, int 
 // there on it is gce_bam_sort.
 int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, gce_sort_run *out, int64_t *n_host_lines,
                  char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
-    if (!in_path || !out_path || !out || !n_host_lines) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    set_err(err, "");
+    if (!in_path || !out_path || !out || !n_host_lines) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
     memset(out, 0, sizeof *out); *n_host_lines = 0;
-    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    if (level < -3 || level > 9) { set_err(err, "level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
     const double t_start = now_s();
     SortJob j;
-    auto done = [&](int code) { j.close_all(code); seterr(j.msg.c_str()); return code; };
+    auto done = [&](int code) { j.close_all(code); set_err(err, j.msg.c_str()); return code; };
     j.level = level; j.device = device; j.window_bytes = window_bytes; j.T = threads > 0 ? threads : default_threads();
     int rc = j.open_paths(in_path, out_path, "gce_sam_sort", "SAM");
     if (rc != GCE_OK) return done(rc);
@@ -2378,17 +2232,16 @@ int gce_sam_sort(const char *in_path, const char *out_path, int32_t device, int 
 // (gce_sort_key_window), the plan (gce_sort_plan), then per pass the file once more (gce_sort_pass_*) and that range of the output written.
 int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes, int32_t min_passes,
                         gce_sort_run *out, gce_sort_pass_run *run, char err[256]) {
-    auto seterr = [&](const char *m) { if (err) { strncpy(err, m ? m : "", 255); err[255] = 0; } };
-    seterr("");
-    if (!in_path || !out_path || !out || !run || min_passes < 0 || min_passes > 64) { seterr("bad argument"); return GCE_ERR_INVALID; }
+    set_err(err, "");
+    if (!in_path || !out_path || !out || !run || min_passes < 0 || min_passes > 64) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
     memset(out, 0, sizeof *out); memset(run, 0, sizeof *run);
-    if (level < -3 || level > 9) { seterr("level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    if (level < -3 || level > 9) { set_err(err, "level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
     const double t_start = now_s();
     uint64_t budget = device_budget_bytes;
     if (!budget) {
         size_t fr = 0, tot = 0;
         const int r0 = gce_device_mem_info(device, &fr, &tot);
-        if (r0 != GCE_OK) { seterr("no HIP device"); return r0; }
+        if (r0 != GCE_OK) { set_err(err, "no HIP device"); return r0; }
         budget = std::max<uint64_t>((uint64_t)((double)fr * GCE_PASS_BUDGET_FRACTION), 1);
     }
     const uint64_t M = PassWriter::BS;
@@ -2406,11 +2259,11 @@ int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t devic
                 }
                 return r1;
             }
-            seterr(""); memset(out, 0, sizeof *out);                                 // (GCE_ERR_OOM leaves no output)
+            set_err(err, ""); memset(out, 0, sizeof *out);                                 // (GCE_ERR_OOM leaves no output)
         }
     }
     SortJob j;
-    auto done = [&](int code) { j.close_all(code); seterr(j.msg.c_str()); return code; };
+    auto done = [&](int code) { j.close_all(code); set_err(err, j.msg.c_str()); return code; };
     int rc = j.open_input(in_path, out_path, threads, level, window_bytes, device);
     if (rc != GCE_OK) return done(rc);
     const int32_t n_ref = j.n_ref;

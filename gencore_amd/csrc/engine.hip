@@ -36,11 +36,11 @@ inline void dev_bytes_add(long long d) {
 }
 struct DevBuf {
     void *p = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap && p) return hipSuccess;
+    static size_t padded(size_t bytes) { return bytes + bytes / 8 + 256; }            // what ensure takes for `bytes`
+    hipError_t ensure(size_t bytes) { return bytes <= cap && p ? hipSuccess : take(padded(bytes)); }
+    hipError_t take(size_t want) {                                                    // exactly `want` bytes; what it held is freed
         const double t0 = mono_s();
         release();
-        size_t want = bytes + bytes / 8 + 256;
         hipError_t e = hipMalloc(&p, want);
         if (e == hipSuccess) { cap = want; dev_bytes_add((long long)want); } else p = nullptr;
         t_alloc_s += mono_s() - t0; t_alloc_n++; t_alloc_bytes += want;
@@ -49,10 +49,13 @@ struct DevBuf {
     void release() { if (p) { (void)hipFree(p); dev_bytes_add(-(long long)cap); } p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
 };
+struct ScopedBuf : DevBuf { ~ScopedBuf() { release(); } };                            // the device buffers of one call
 
 enum { EV_START = 0, EV_CLUSTER, EV_CSR, EV_DESCRIBE, EV_PAIRING, EV_SCORE, EV_CONSENSUS, EV_FINISH, EV_OUTPUT, EV_COUNT };
 
 }  // namespace
+
+#include "gce_devstream.hpp"
 
 // host buffer that is NOT value-initialised: the drained bases / qualities are hundreds of MB that the copy from the device overwrites
 struct HostRaw {
@@ -94,7 +97,7 @@ struct gce_engine {
     int64_t n_out = 0; size_t out_seq_bytes = 0, out_qual_bytes = 0; int dev_error = 0; uint32_t dev_error_read = 0;
     DevBuf lrec, lout, bhdr, blk_base, ev_tid, ev_pos, ev_read, table, toff;
     // the raw BAM stream in HBM (gce_bamdev.hpp)
-    DevBuf raw, rw_bad, rw_guess, rw_leave, rw_cnt, rw_base, rw_misc, rw_tmp, rw_off, rw_ncig, rw_nmpos, rw_rsize, rw_roff, rw_body;
+    DevBuf raw, rw_tmp, rw_ncig, rw_nmpos, rw_rsize, rw_roff, rw_body; RecIdx rw;      // rw: the record index (rw.off: the record starts), rw.misc also the scratch words of the file layer
     size_t raw_n = 0; bool raw_mode = false; int64_t raw_records = 0; uint64_t raw_body_bytes = 0;
     int64_t idx_ctr[4] = {0, 0, 0, 0};   // the record index of the last gce_raw_finish: segments, initially flagged, parallel rounds, serial repair (gce_get_index_counters)
     DevBuf z_comp, z_dir, z_err; size_t z_n = 0; std::vector<InfDir> z_members;      // BGZF members waiting for the GPU inflate (gce_raw_push_bgzf)
@@ -191,7 +194,8 @@ void gce_destroy(gce_engine *e) {
                      &e->pg, &e->gpl, &e->gpr, &e->grp_begin, &e->grp_n, &e->gl_cluster, &e->g_begin, &e->g_np, &e->deep_list, &e->k64, &e->slow_list, &e->pf_flag, &e->pf_list, &e->pq_flag, &e->pq_list, &e->left_list, &e->slow_args, &e->pd_slab, &e->gen_flag, &e->gen_list, &e->score_list, &e->gw, &e->g_wbase, &e->vb_start, &e->rp_left, &e->rp_right, &e->rp_merge, &e->rp_rmerge,
                      &e->rp_umi, &e->rp_umilen, &e->rp_state, &e->rp_supp, &e->rp_nm, &e->rp_qsl, &e->rp_qsr, &e->scan_part, &e->si};
     for (auto *b : all) b->release();
-    for (DevBuf *b : {&e->z_comp, &e->z_dir, &e->z_err, &e->raw, &e->rw_bad, &e->rw_guess, &e->rw_leave, &e->rw_cnt, &e->rw_base, &e->rw_misc, &e->rw_tmp, &e->rw_off, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body, &e->sf_text}) b->release();
+    for (DevBuf *b : {&e->z_comp, &e->z_dir, &e->z_err, &e->raw, &e->rw_tmp, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body, &e->sf_text}) b->release();
+    e->rw.release();
     for (DevBuf *b : {&e->zo_slots, &e->zo_sizes, &e->zo_off, &e->zo_out, &e->p16_flag, &e->p16_list}) b->release();
     for (DevBuf *b : {&e->sh_tickall, &e->sh_shard, &e->sh_flag, &e->sh_sel, &e->sh_core, &e->sh_qoff, &e->sh_coff, &e->sh_soff, &e->sh_loff, &e->sh_nm, &e->sh_nmt, &e->sh_mioff, &e->sh_tick, &e->sh_roff, &e->sh_nmpos, &e->sh_keys, &e->sh_stage}) b->release();
     for (DevBuf *b : {&e->dp_binoff, &e->dp_regoff, &e->dp_rs, &e->dp_re, &e->dp_pmax, &e->dp_sorted, &e->dp_depth, &e->dp_bed, &e->dp_where}) b->release();
@@ -1352,4 +1356,5 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_bai.hpp"
 #include "gce_samdev.hpp"
 #include "gce_samfmt.hpp"
+#undef MCHK
 #include "gce_sort.hpp"

@@ -1,6 +1,6 @@
 // gce_bai.hpp — the BAI index of a coordinate-sorted BAM on the GPU (gce_bam_index).  The file is streamed window by window as
 // the pass runner streams it (win_inflate_index / win_carry, gce_passes.hpp): the host hands whole BGZF members, the GPU inflates them behind the
-// record the last window's end cut and finds the record starts.  Per record one 24-byte fact stays resident (BaiFact: tid, pos, end, bin,
+// record the last window's end cut and finds the record starts (dev_inflate_members, dev_record_index: gce_devstream.hpp).  Per record one 24-byte fact stays resident (BaiFact: tid, pos, end, bin,
 // mapped bit, start virtual offset); nothing else of a window outlives it.  After the last window:
 //   k_bai_check     the first record that breaks (tid, pos) order or BAI's range (atomicMin), run heads, contig spans, the mapped bits
 //   k_bai_runs      one chunk per run of records with one (tid, bin); hipcub::DeviceRadixSort orders them by (tid, bin), stable: file order
@@ -16,7 +16,6 @@ namespace {
 struct BaiFact { int32_t tid, pos, end; uint32_t bin_m; uint64_t voff; };     // bin_m: bin | mapped << 16; end saturates at INT32_MAX
 static_assert(sizeof(BaiFact) == 24, "BaiFact is 24 bytes");
 #define BAI_MAX_END (1ll << 29)
-struct ScopedBuf : DevBuf { ~ScopedBuf() { release(); } };                      // the device buffers of one gce_bai_finish call
 
 __device__ __forceinline__ uint32_t bai_reg2bin(int64_t beg, int64_t end) {
     --end;
@@ -218,7 +217,7 @@ int gce_bai_window(gce_bai *b, const void *comp, size_t comp_bytes, int32_t n_me
         BCHK(b->mem.ensure(mu.size() * 16 + 64));
         BCHK(hipMemcpyAsync(b->mem.p, mu.data(), mu.size() * 8, hipMemcpyHostToDevice, s));
         BCHK(hipMemcpyAsync(b->mem.as<uint64_t>() + mu.size(), mc.data(), mc.size() * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_bai_facts, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.off.p, (int64_t)n_rec, carry_n, b->carry_voff,
+        hipLaunchKernelGGL(k_bai_facts, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.idx.off.p, (int64_t)n_rec, carry_n, b->carry_voff,
                            (const uint64_t *)b->mem.p, (const uint64_t *)b->mem.as<uint64_t>() + mu.size(), n_mem, b->facts.as<BaiFact>() + b->n);
         BCHK(hipGetLastError());
         b->n += (int64_t)n_rec;

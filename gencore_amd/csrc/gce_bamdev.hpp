@@ -17,110 +17,6 @@
 
 namespace {
 
-typedef uint32_t rb_u32u __attribute__((aligned(1)));
-typedef uint16_t rb_u16u __attribute__((aligned(1)));
-__device__ __forceinline__ uint32_t rb32(const uint8_t *p) { return *(const rb_u32u *)p; }
-__device__ __forceinline__ uint32_t rb16(const uint8_t *p) { return *(const rb_u16u *)p; }
-#define RAW_SEG (16u << 10)
-
-// does a record start at o?  (bamio.cpp's test: sane block_size, contig ids inside the header's, a NUL-terminated name, the fixed fields fit)
-__device__ __forceinline__ bool raw_plausible(const uint8_t *u, uint64_t o, uint64_t n, int32_t nref) {
-    if (o + 36 > n) return false;
-    const uint32_t bs = rb32(u + o);
-    if (bs < 32 || bs > (1u << 28) || o + 4 + bs > n) return false;
-    const uint8_t *r = u + o + 4;
-    const int32_t tid = (int32_t)rb32(r), mtid = (int32_t)rb32(r + 20), ls = (int32_t)rb32(r + 16); const uint32_t lq = r[8], nc = rb16(r + 12);
-    if (tid < -1 || tid >= nref || mtid < -1 || mtid >= nref || lq == 0 || ls < 0) return false;
-    if (32ull + lq + 4ull * nc + (uint64_t)(ls + 1) / 2 + (uint64_t)ls > bs) return false;
-    return r[32 + lq - 1] == 0;
-}
-// records starting in [o, hi): count, optionally their offsets; returns where the chain leaves the range (~0 = broken chain).  SOFT (a window
-// of the pass runner, whose end cuts a record): a record that does not fit in n ends the chain there instead of breaking it
-template <bool SOFT = false>
-__device__ __forceinline__ uint64_t raw_walk(const uint8_t *u, uint64_t o, uint64_t hi, uint64_t n, uint32_t &cnt, uint64_t *out) {
-    while (o < hi && o + 4 <= n) {
-        const uint32_t bs = rb32(u + o);
-        if (bs < 32) return ~0ull;
-        if (o + 4 + bs > n) return SOFT ? o : ~0ull;
-        if (out) out[cnt] = o;
-        cnt++;
-        o += 4ull + bs;
-    }
-    return o;
-}
-template <bool SOFT = false>
-__global__ __launch_bounds__(256) void k_raw_seg(const uint8_t *u, uint64_t first, uint64_t n, int32_t nref, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt) {
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nseg) return;
-    const uint64_t lo = first + s * RAW_SEG, hi = min(n, lo + RAW_SEG);
-    uint64_t o = lo;
-    if (s > 0) {                                                   // a guessed start: two sane records in a row (the first segment starts on the first record)
-        while (o < hi && !(raw_plausible(u, o, n, nref) && (o + 4 + rb32(u + o) + 3 >= n || raw_plausible(u, o + 4 + rb32(u + o), n, nref)))) o++;
-        if (o >= hi) { guess[s] = ~0ull; leave[s] = ~0ull; cnt[s] = 0; return; }
-    }
-    uint32_t c = 0;
-    guess[s] = o;
-    leave[s] = raw_walk<SOFT>(u, o, hi, n, c, nullptr);
-    cnt[s] = c;
-}
-// every segment's guess must be where the chain of the segment in front of it leaves: flag = number of segments for which it is not
-template <bool SOFT = false>
-__global__ __launch_bounds__(256) void k_raw_check(const uint64_t *guess, const uint64_t *leave, uint64_t nseg, uint64_t n, unsigned int *bad, uint8_t *bad_of) {
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nseg) return;
-    const bool b = leave[s] == ~0ull || (s > 0 && guess[s] != leave[s - 1]) || (s == nseg - 1 && (SOFT ? leave[s] > n : leave[s] != n));
-    bad_of[s] = b;
-    if (b) atomicAdd(bad, 1u);
-}
-// repair, in parallel.  A guess can be a coincidence: one byte in front of a record of contig 0 the shifted fields pass the test about once
-// in 4000 segments (block_size x 256 + the last NM byte, tid x 256 = 0 ...), and the chain walked from there leaves far behind the
-// segment, which also puts the NEXT segment off the chain although its own guess is right.  Bytes inside a long record (a B:C array of
-// record-shaped bytes) can even carry a false chain of their own across several segments, consistent from segment to segment: a segment
-// that is NOT flagged may still be wrong, when it agrees with a wrong predecessor.  Every round re-walks the flagged segments whose
-// predecessor is not flagged (nothing that predecessor holds changes in the round) from where the predecessor's chain leaves.  That start
-// is only right when every segment in front is right, so a walk from it that breaks proves nothing: the segment is left as it is (still
-// flagged) and only k_raw_repair, which walks from the first record, may call the stream damaged.  Progress: the first wrong segment is
-// always flagged and its predecessor is right and unflagged, so every round puts at least it on the chain; no flag at all means, by
-// induction from segment 0 (whose guess is the first record), that every segment is on the chain.  Rounds <= the longest run of wrong
-// segments (records longer than a segment, false chains).
-template <bool SOFT = false>
-__global__ __launch_bounds__(256) void k_raw_fix(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt, const uint8_t *bad_of) {
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nseg || s == 0 || !bad_of[s] || bad_of[s - 1]) return;
-    const uint64_t at = leave[s - 1];
-    if (at == ~0ull) return;
-    const uint64_t hi = min(n, first + s * RAW_SEG + RAW_SEG);
-    uint32_t c = 0; uint64_t x = at;
-    if (at < hi) { x = raw_walk<SOFT>(u, at, hi, n, c, nullptr); if (x == ~0ull) return; }
-    guess[s] = at; leave[s] = x; cnt[s] = c;
-}
-// the last resort (after several parallel rounds): ONE thread follows the chain from segment to segment
-// and re-walks only the segments whose guess does not lie on it
-template <bool SOFT = false>
-__global__ void k_raw_repair(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, uint64_t *guess, uint64_t *leave, uint32_t *cnt, unsigned int *broken) {
-    if (blockIdx.x || threadIdx.x) return;
-    uint64_t at = first;
-    for (uint64_t s = 0; s < nseg; s++) {
-        const uint64_t lo = first + s * RAW_SEG, hi = min(n, lo + RAW_SEG);
-        if (at >= hi) { guess[s] = at; leave[s] = at; cnt[s] = 0; continue; }       // a record spans the whole segment
-        if (guess[s] != at || leave[s] == ~0ull) {
-            uint32_t c = 0;
-            const uint64_t x = raw_walk<SOFT>(u, at, hi, n, c, nullptr);
-            if (x == ~0ull) { *broken = 1u; return; }
-            guess[s] = at; leave[s] = x; cnt[s] = c;
-        }
-        at = leave[s];
-    }
-    if (SOFT ? at > n : at != n) *broken = 1u;
-}
-template <bool SOFT = false>
-__global__ __launch_bounds__(256) void k_raw_offsets(const uint8_t *u, uint64_t first, uint64_t n, uint64_t nseg, const uint64_t *guess, const uint64_t *base, uint64_t *rec_off) {
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nseg) return;
-    const uint64_t hi = min(n, first + s * RAW_SEG + RAW_SEG);
-    uint32_t c = 0;
-    (void)raw_walk<SOFT>(u, guess[s], hi, n, c, rec_off + base[s]);
-}
 // bytes of an aux value behind its type byte, or ~0 (bamio.cpp aux_size)
 __device__ __forceinline__ uint64_t raw_aux_size(uint8_t type, const uint8_t *p, const uint8_t *end) {
     switch (type) {
@@ -287,65 +183,6 @@ __global__ void k_add_i64(long long *acc, const long long *x, int n) { const int
 }  // namespace
 
 
-// ---- prefix sums and compaction of the file layer on the engine's own scan kernels (gce_cluster.hpp: tiles of 2048, one block over the tile
-//      totals): exclusive sums out[0 .. n] (out[n] = the total) of n 32- or 64-bit values, three launches; flagged indices, three launches
-namespace {
-template <class T> __global__ __launch_bounds__(256) void k_xs_reduce(const T *in, uint64_t n, uint64_t *part) {
-    __shared__ uint64_t s4[4];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE; uint64_t v = 0;
-    for (int k = 0; k < SCAN_TILE / 256; k++) { const uint64_t i = base + k * 256 + threadIdx.x; v += i < n ? (uint64_t)in[i] : 0ull; }
-    v = (uint64_t)wave_sum64((long long)v);
-    if (lane_id() == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = s4[0] + s4[1] + s4[2] + s4[3];
-}
-template <class T> __global__ __launch_bounds__(256) void k_xs_apply(const T *in, uint64_t n, const uint64_t *part, uint64_t *out) {
-    __shared__ uint64_t s_w[4]; __shared__ uint64_t s_carry;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = part[blockIdx.x];
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
-    for (int k = 0; k < SCAN_TILE / 256; k++) {
-        const uint64_t i = base + k * 256 + threadIdx.x;
-        const uint64_t v = i < n ? (uint64_t)in[i] : 0ull; uint64_t x = v;
-        for (int q = 1; q < 64; q <<= 1) { const uint64_t t = (uint64_t)__shfl_up((long long)x, q); if (lane >= q) x += t; }
-        if (lane == 63) s_w[wv] = x;
-        __syncthreads();
-        uint64_t woff = 0;
-        for (int q = 0; q < wv; q++) woff += s_w[q];
-        const uint64_t carry = s_carry, ex = carry + woff + x - v;
-        if (i < n) out[i] = ex;
-        if (i + 1 == n) out[n] = ex + v;                                              // the total behind the last element
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = carry + woff + x;
-        __syncthreads();
-    }
-}
-}  // namespace
-template <class T> static hipError_t dev_exclusive_sum(const T *in, uint64_t n, uint64_t *out, DevBuf &tmp, hipStream_t s) {
-    if (n == 0) return hipMemsetAsync(out, 0, 8, s);
-    const unsigned nb = (unsigned)((n + SCAN_TILE - 1) / SCAN_TILE);
-    hipError_t e = tmp.ensure((size_t)nb * 8 + 64);
-    if (e != hipSuccess) return e;
-    uint64_t *part = tmp.as<uint64_t>();
-    hipLaunchKernelGGL(k_xs_reduce<T>, dim3(nb), dim3(256), 0, s, in, n, part);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, part, (uint64_t)nb, (unsigned long long *)(part + nb), (unsigned long long *)(part + nb + 1));
-    hipLaunchKernelGGL(k_xs_apply<T>, dim3(nb), dim3(256), 0, s, in, n, (const uint64_t *)part, out);
-    return hipGetLastError();
-}
-// indices (ascending) of the set flags -> out, their number -> *count (device memory)
-static hipError_t dev_select_flagged(const uint8_t *flag, uint64_t n, uint32_t *out, unsigned long long *count, DevBuf &tmp, hipStream_t s) {
-    if (n == 0) return hipMemsetAsync(count, 0, 8, s);
-    const unsigned nb = (unsigned)((n + SCAN_TILE - 1) / SCAN_TILE);
-    hipError_t e = tmp.ensure((size_t)nb * 8 + 64);
-    if (e != hipSuccess) return e;
-    uint64_t *part = tmp.as<uint64_t>();
-    hipLaunchKernelGGL(k_flag_reduce, dim3(nb), dim3(256), 0, s, flag, n, part);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, part, (uint64_t)nb, count, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(k_flag_apply, dim3(nb), dim3(256), 0, s, flag, n, (const uint64_t *)part, out);
-    return hipGetLastError();
-}
-
 extern "C" {
 
 int gce_raw_begin(gce_engine *e, size_t capacity_hint) {
@@ -357,8 +194,8 @@ int gce_raw_begin(gce_engine *e, size_t capacity_hint) {
     {   // the per-record arrays, sized for the most records the stream can hold (a record with bases is > 96 bytes): allocated NOW, beside
         // the host's first inflate, instead of in gce_raw_finish on the critical path (hipMalloc of gigabytes takes tens of milliseconds)
         const size_t n1 = capacity_hint / 96 + 1024, nseg = capacity_hint / RAW_SEG + 16;
-        HIPCHK(e->rw_guess.ensure(nseg * 8)); HIPCHK(e->rw_leave.ensure(nseg * 8)); HIPCHK(e->rw_cnt.ensure(nseg * 4 + 8)); HIPCHK(e->rw_base.ensure(nseg * 8 + 8)); HIPCHK(e->rw_misc.ensure(64));
-        HIPCHK(e->rw_off.ensure((n1 + 1) * 8));
+        HIPCHK(e->rw.guess.ensure(nseg * 8)); HIPCHK(e->rw.leave.ensure(nseg * 8)); HIPCHK(e->rw.cnt.ensure(nseg * 4 + 8)); HIPCHK(e->rw.base.ensure(nseg * 8 + 8)); HIPCHK(e->rw.misc.ensure(64));
+        HIPCHK(e->rw.off.ensure((n1 + 1) * 8));
         HIPCHK(e->b_core.ensure(n1 * sizeof(gce_core) + 64)); HIPCHK(e->b_qoff.ensure(n1 * 8 + 64)); HIPCHK(e->b_coff.ensure((n1 + 1) * 8 + 64)); HIPCHK(e->b_soff.ensure(n1 * 8 + 64)); HIPCHK(e->b_loff.ensure(n1 * 8 + 64));
         HIPCHK(e->b_nm.ensure(n1 * 4 + 64)); HIPCHK(e->b_nmt.ensure(n1 + 64)); HIPCHK(e->b_mioff.ensure(n1 * 8 + 64)); HIPCHK(e->rw_ncig.ensure(n1 * 4 + 64)); HIPCHK(e->rw_nmpos.ensure(n1 * 4 + 64));
         HIPCHK(e->b_cigar.ensure(n1 * 8 + 64));
@@ -371,14 +208,9 @@ int gce_raw_begin(gce_engine *e, size_t capacity_hint) {
 int gce_raw_push(gce_engine *e, const void *host, size_t bytes, int32_t *ticket) {
     if (!e || !e->raw_mode || (!host && bytes)) return GCE_ERR_INVALID;
     (void)hipSetDevice(e->prm.device);
-    if (e->raw_n + bytes + 256 > e->raw.cap) {                                     // grow: the copies so far are in flight on the same stream, the move queues behind them
-        DevBuf nb;
-        HIPCHK(nb.ensure((e->raw_n + bytes) * 2 + 256));
-        const size_t keep = std::min(e->raw_n, e->raw.cap);                        // (members waiting for the GPU inflate have places, not bytes yet: they may lie past the old buffer)
-        if (keep) HIPCHK(hipMemcpyAsync(nb.p, e->raw.p, keep, hipMemcpyDeviceToDevice, e->up_stream));
-        HIPCHK(hipStreamSynchronize(e->up_stream));
-        e->raw.release(); e->raw = nb; nb.p = nullptr; nb.cap = 0;
-    }
+    // grow: the copies so far are in flight on the same stream, the move queues behind them (members waiting for the GPU inflate have places,
+    // not bytes yet: they may lie past the old buffer)
+    HIPCHK(dev_grow_keep(e->raw, e->raw_n + bytes + 256, std::min(e->raw_n, e->raw.cap), DevBuf::padded((e->raw_n + bytes) * 2 + 256), e->up_stream));
     if (bytes) HIPCHK(hipMemcpyAsync((char *)e->raw.p + e->raw_n, host, bytes, hipMemcpyHostToDevice, e->up_stream));
     e->raw_n += bytes;
     hipEvent_t ev;
@@ -398,13 +230,8 @@ int gce_raw_push_bgzf(gce_engine *e, const void *comp, size_t comp_bytes, int32_
     for (int32_t k = 0; k < n_members; k++)                                             // every member is looked at before anything is queued or counted
         if (coff[k] > comp_bytes || csize[k] > comp_bytes - coff[k] || usize[k] > 0x10000u) return fail(e, GCE_ERR_INVALID, "BGZF member outside its buffer");
     (void)hipSetDevice(e->prm.device);
-    if (e->z_n + comp_bytes + 64 > e->z_comp.cap) {
-        DevBuf nb;
-        HIPCHK(nb.ensure(std::max<size_t>((e->z_n + comp_bytes) * 2, e->raw.cap / 4) + 64));     // (gce_raw_begin sized the raw stream for ~5 x the file: a quarter of it holds the file, no second growth)
-        if (e->z_n) HIPCHK(hipMemcpyAsync(nb.p, e->z_comp.p, e->z_n, hipMemcpyDeviceToDevice, e->up_stream));
-        HIPCHK(hipStreamSynchronize(e->up_stream));
-        e->z_comp.release(); e->z_comp = nb; nb.p = nullptr; nb.cap = 0;
-    }
+    // (gce_raw_begin sized the raw stream for ~5 x the file: a quarter of it holds the file, no second growth)
+    HIPCHK(dev_grow_keep(e->z_comp, e->z_n + comp_bytes + 64, e->z_n, DevBuf::padded(std::max<size_t>((e->z_n + comp_bytes) * 2, e->raw.cap / 4) + 64), e->up_stream));
     if (comp_bytes) HIPCHK(hipMemcpyAsync((char *)e->z_comp.p + e->z_n, comp, comp_bytes, hipMemcpyHostToDevice, e->up_stream));
     for (int32_t k = 0; k < n_members; k++) {
         if (usize[k] == 0) continue;
@@ -425,39 +252,14 @@ int gce_raw_push_bgzf(gce_engine *e, const void *comp, size_t comp_bytes, int32_
 static int raw_inflate_pending(gce_engine *e) {
     if (e->z_members.empty()) return GCE_OK;
     hipStream_t s = e->stream;
-    if (e->raw_n + 256 > e->raw.cap) {
-        DevBuf nb;
-        HIPCHK(nb.ensure(e->raw_n + 256));
-        const size_t keep = std::min(e->raw_n, e->raw.cap);                        // (everything so far: host windows may lie between the members' places)
-        if (keep) HIPCHK(hipMemcpyAsync(nb.p, e->raw.p, keep, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        e->raw.release(); e->raw = nb; nb.p = nullptr; nb.cap = 0;
-    }
-    const size_t n = e->z_members.size(), LAUNCH = (size_t)1 << 18;                // members per launch: bounds the code-length scratch (320 bytes per member of a launch)
-    HIPCHK(e->z_dir.ensure(n * sizeof(InfDir) + std::min(n, LAUNCH) * INF_NSYM)); HIPCHK(e->z_err.ensure(16));
-    HIPCHK(hipMemcpyAsync(e->z_dir.p, e->z_members.data(), n * sizeof(InfDir), hipMemcpyHostToDevice, s));
-    const unsigned int init[2] = {0u, 0xFFFFFFFFu};
-    HIPCHK(hipMemcpyAsync(e->z_err.p, init, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync((char *)e->z_comp.p + e->z_n, 0, 64, s));                 // (the bit reader looks up to 32 bytes ahead)
-    unsigned int got[2] = {0, 0}; uint32_t bad_member = 0xFFFFFFFFu;
-    for (size_t base = 0; base < n; base += LAUNCH) {
-        const size_t m = std::min(LAUNCH, n - base);
-        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((m + INF_T - 1) / INF_T)), dim3(INF_T), 0, s, e->z_comp.as<uint8_t>(), (const InfDir *)e->z_dir.p + base, (uint32_t)m, e->raw.as<uint8_t>(), e->z_err.as<unsigned int>(),
-                           e->z_dir.as<uint8_t>() + n * sizeof(InfDir));
-        if (base + LAUNCH < n) {                                                   // (the member number of a failure is relative to its launch: fetch it per launch when there are several)
-            HIPCHK(hipMemcpyAsync(got, e->z_err.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-            if (got[0]) { bad_member = (uint32_t)base + got[1]; break; }
-        }
-    }
-    if (bad_member == 0xFFFFFFFFu) {
-        HIPCHK(hipMemcpyAsync(got, e->z_err.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (got[0]) bad_member = (uint32_t)((n - 1) / LAUNCH * LAUNCH) + got[1];
-    }
-    HIPCHK(hipGetLastError());
+    // (everything so far is kept: host windows may lie between the members' places)
+    HIPCHK(dev_grow_keep(e->raw, e->raw_n + 256, std::min(e->raw_n, e->raw.cap), DevBuf::padded(e->raw_n + 256), s));
+    int64_t bad = -1; std::string msg;
+    const int rc = dev_inflate_members(e->z_comp.as<uint8_t>(), e->z_n, e->z_members.data(), e->z_members.size(), e->raw.as<uint8_t>(), e->z_dir, e->z_err, s, &bad, msg);
+    if (rc != GCE_OK) return fail(e, rc, msg);
     e->z_comp.release();                                                           // (the compressed copy of the file: not needed while the stream is processed)
     e->z_members.clear(); e->z_n = 0;
-    if (bad_member != 0xFFFFFFFFu) { char m[96]; snprintf(m, sizeof m, "inflate / CRC failure in BGZF member %u of the GPU batch", bad_member); return fail(e, GCE_ERR_INVALID, m); }
+    if (bad >= 0) { char m[96]; snprintf(m, sizeof m, "inflate / CRC failure in BGZF member %u of the GPU batch", (uint32_t)bad); return fail(e, GCE_ERR_INVALID, m); }
     return GCE_OK;
 }
 
@@ -473,32 +275,15 @@ int gce_bgzf_inflate(int32_t device, const void *comp, size_t comp_bytes, int32_
         InfDir d; d.coff = coff[k]; d.uoff = total; d.csize = csize[k]; d.usize = usize[k]; dir.push_back(d); total += usize[k];
     }
     if (dir.empty()) return GCE_OK;
-    DevBuf zc, zd, ze, zo;
-    int rc = GCE_OK;
-    auto chk = [&](hipError_t x) { if (x != hipSuccess && rc == GCE_OK) rc = GCE_ERR_HIP; };
-    if (zc.ensure(comp_bytes + 64) != hipSuccess || zd.ensure(dir.size() * (sizeof(InfDir) + INF_NSYM)) != hipSuccess || ze.ensure(16) != hipSuccess || zo.ensure(total + 64) != hipSuccess) rc = GCE_ERR_OOM;
-    if (rc == GCE_OK) {
-        chk(hipMemcpy(zc.p, comp, comp_bytes, hipMemcpyHostToDevice)); chk(hipMemset((char *)zc.p + comp_bytes, 0, 64));
-        chk(hipMemcpy(zd.p, dir.data(), dir.size() * sizeof(InfDir), hipMemcpyHostToDevice));
-        const unsigned int init[2] = {0u, 0xFFFFFFFFu};
-        chk(hipMemcpy(ze.p, init, 8, hipMemcpyHostToDevice));
-        if (rc == GCE_OK) {
-            hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((dir.size() + INF_T - 1) / INF_T)), dim3(INF_T), 0, 0, zc.as<uint8_t>(), (const InfDir *)zd.p, (uint32_t)dir.size(), zo.as<uint8_t>(), ze.as<unsigned int>(), zd.as<uint8_t>() + dir.size() * sizeof(InfDir));
-            chk(hipDeviceSynchronize()); chk(hipGetLastError());
-            unsigned int got[2] = {0, 0};
-            chk(hipMemcpy(got, ze.p, 8, hipMemcpyDeviceToHost));
-            if (total) chk(hipMemcpy(out, zo.p, total, hipMemcpyDeviceToHost));
-            if (rc == GCE_OK && got[0]) { if (first_bad) *first_bad = (int32_t)got[1]; rc = GCE_ERR_INVALID; }
-        }
-    }
-    zc.release(); zd.release(); ze.release(); zo.release();
-    return rc;
-}
-
-// either encoder of gce_deflate.hpp over `nb` blocks on stream s (codes: see gce_bgzf_deflate_codes)
-static void def_launch(int codes, uint32_t nb, hipStream_t s, const uint8_t *in, uint64_t total, uint32_t blk, uint8_t *slots, uint32_t slot, uint32_t *sizes) {
-    if (codes == 0) hipLaunchKernelGGL(k_bgzf_deflate, dim3((nb + DEF_T - 1) / DEF_T), dim3(DEF_T), 0, s, in, total, blk, nb, slots, slot, sizes);
-    else hipLaunchKernelGGL(k_bgzf_deflate_dyn, dim3((nb + DEF_T - 1) / DEF_T), dim3(DEF_T), 0, s, in, total, blk, nb, slots, slot, sizes, codes);
+    ScopedBuf zc, zd, ze, zo;
+    if (zc.ensure(comp_bytes + 64) != hipSuccess || zo.ensure(total + 64) != hipSuccess) return GCE_ERR_OOM;
+    if (hipMemcpy(zc.p, comp, comp_bytes, hipMemcpyHostToDevice) != hipSuccess) return GCE_ERR_HIP;
+    int64_t bad = -1; std::string msg;
+    const int rc = dev_inflate_members(zc.as<uint8_t>(), comp_bytes, dir.data(), dir.size(), zo.as<uint8_t>(), zd, ze, 0, &bad, msg);
+    if (rc != GCE_OK) return rc;
+    if (total && hipMemcpy(out, zo.p, total, hipMemcpyDeviceToHost) != hipSuccess) return GCE_ERR_HIP;
+    if (bad >= 0) { if (first_bad) *first_bad = (int32_t)bad; return GCE_ERR_INVALID; }
+    return GCE_OK;
 }
 
 // The encoder of gce_raw_deflate_output on the caller's buffer (tests, tools): `n` bytes -> BGZF blocks of `block_bytes` input bytes each (<= 65 280),
@@ -513,28 +298,18 @@ int gce_bgzf_deflate_codes(int32_t device, const void *in, size_t n, uint32_t bl
     const uint64_t nb64 = (n + block_bytes - 1) / block_bytes;
     if (nb64 >= 0x7FFFFFF0ull) return GCE_ERR_INVALID;
     const uint32_t nb = (uint32_t)nb64, slot = block_bytes + block_bytes / 8 + 64;
-    DevBuf zi, zs, zz, zo, zf, zt;
-    int rc = GCE_OK;
-    auto chk = [&](hipError_t x) { if (x != hipSuccess && rc == GCE_OK) rc = GCE_ERR_HIP; };
-    if (zi.ensure(n + 64) != hipSuccess || zs.ensure((size_t)nb * slot + 64) != hipSuccess || zz.ensure(((size_t)nb + 1) * 4) != hipSuccess || zf.ensure(((size_t)nb + 1) * 8) != hipSuccess) rc = GCE_ERR_OOM;
-    if (rc == GCE_OK) {
-        chk(hipMemcpy(zi.p, in, n, hipMemcpyHostToDevice)); chk(hipMemset((char *)zi.p + n, 0, 64));
-        def_launch(codes, nb, 0, (const uint8_t *)zi.p, (uint64_t)n, block_bytes, zs.as<uint8_t>(), slot, zz.as<uint32_t>());
-        chk(hipMemset((char *)zz.p + (size_t)nb * 4, 0, 4));
-        chk(dev_exclusive_sum(zz.as<uint32_t>(), (uint64_t)nb, zf.as<uint64_t>(), zt, 0));
-        uint64_t csz = 0;
-        if (rc == GCE_OK) chk(hipMemcpy(&csz, zf.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost));
-        if (rc == GCE_OK && csz > out_cap) rc = GCE_ERR_INVALID;
-        if (rc == GCE_OK && zo.ensure(csz + 64) != hipSuccess) rc = GCE_ERR_OOM;
-        if (rc == GCE_OK) {
-            hipLaunchKernelGGL(k_deflate_pack, dim3(std::min<uint32_t>((nb + 3) / 4, 16384u)), dim3(256), 0, 0, (const uint8_t *)zs.p, slot, (const uint32_t *)zz.p, (const uint64_t *)zf.p, nb, zo.as<uint8_t>());
-            chk(hipDeviceSynchronize()); chk(hipGetLastError());
-            chk(hipMemcpy(out, zo.p, csz, hipMemcpyDeviceToHost));
-            if (rc == GCE_OK) *out_bytes = (size_t)csz;
-        }
-    }
-    zi.release(); zs.release(); zz.release(); zo.release(); zf.release(); zt.release();
-    return rc;
+    ScopedBuf zi, zs, zz, zo, zf, zt;
+    if (zi.ensure(n + 64) != hipSuccess || zs.ensure((size_t)nb * slot + 64) != hipSuccess || zz.ensure(((size_t)nb + 1) * 4) != hipSuccess || zf.ensure(((size_t)nb + 1) * 8) != hipSuccess) return GCE_ERR_OOM;
+    if (hipMemcpy(zi.p, in, n, hipMemcpyHostToDevice) != hipSuccess || hipMemset((char *)zi.p + n, 0, 64) != hipSuccess) return GCE_ERR_HIP;
+    uint64_t csz = 0; std::string msg;
+    const int rc = dev_deflate_members(codes, (const uint8_t *)zi.p, (uint64_t)n, block_bytes, nb, zs.as<uint8_t>(), slot, zz.as<uint32_t>(), zf.as<uint64_t>(), zt, 0, &csz, msg);
+    if (rc != GCE_OK) return rc;
+    if (csz > out_cap) return GCE_ERR_INVALID;
+    if (zo.ensure(csz + 64) != hipSuccess) return GCE_ERR_OOM;
+    dev_deflate_pack((const uint8_t *)zs.p, slot, (const uint32_t *)zz.p, (const uint64_t *)zf.p, nb, zo.as<uint8_t>(), 0);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(out, zo.p, csz, hipMemcpyDeviceToHost) != hipSuccess) return GCE_ERR_HIP;
+    *out_bytes = (size_t)csz;
+    return GCE_OK;
 }
 int gce_bgzf_deflate(int32_t device, const void *in, size_t n, uint32_t block_bytes, void *out, size_t out_cap, size_t *out_bytes) {
     return gce_bgzf_deflate_codes(device, in, n, block_bytes, 0, out, out_cap, out_bytes);
@@ -560,45 +335,11 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
     uint64_t n_rec = 0;
     for (int64_t &c : e->idx_ctr) c = 0;
     if (total > records_begin) {
-        const uint64_t nseg = (total - records_begin + RAW_SEG - 1) / RAW_SEG;
-        HIPCHK(e->rw_guess.ensure(nseg * 8)); HIPCHK(e->rw_leave.ensure(nseg * 8)); HIPCHK(e->rw_cnt.ensure(nseg * 4 + 8)); HIPCHK(e->rw_base.ensure(nseg * 8 + 8)); HIPCHK(e->rw_misc.ensure(64)); HIPCHK(e->rw_bad.ensure(nseg + 8));
-        HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 64, s));
-        const unsigned nbs = (unsigned)((nseg + 255) / 256);
-        hipLaunchKernelGGL(k_raw_seg<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, n_ref, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_raw_check<false>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
-        unsigned int flags[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-        e->idx_ctr[0] = (int64_t)nseg; e->idx_ctr[1] = flags[0];
-        lap("segment walks + check");
-        if (tprint) fprintf(stderr, "gce_raw_finish: %u of %llu segments off the chain\n", flags[0], (unsigned long long)nseg);
-        if (tprint && flags[0]) {                                                       // which ones, and why
-            std::vector<uint64_t> g(nseg), l(nseg);
-            (void)hipMemcpy(g.data(), e->rw_guess.p, nseg * 8, hipMemcpyDeviceToHost); (void)hipMemcpy(l.data(), e->rw_leave.p, nseg * 8, hipMemcpyDeviceToHost);
-            int shown = 0;
-            for (uint64_t q = 1; q < nseg && shown < 6; q++) if (l[q] == ~0ull || g[q] != l[q - 1]) { fprintf(stderr, "  segment %llu [%llu, +16K): guess %lld, chain enters at %lld, leaves %lld\n", (unsigned long long)q, (unsigned long long)(records_begin + q * RAW_SEG), (long long)g[q], (long long)l[q - 1], (long long)l[q]); shown++; }
-        }
-        for (int round = 0; flags[0] && round < 64; round++) {                           // parallel repair rounds
-            HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_fix<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), (const uint8_t *)e->rw_bad.p);
-            hipLaunchKernelGGL(k_raw_check<false>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_leave.p, nseg, total, e->rw_misc.as<unsigned int>(), e->rw_bad.as<uint8_t>());
-            HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-            e->idx_ctr[2]++;
-        }
-        lap("parallel repair");
-        if (flags[0]) {
-            e->idx_ctr[3] = 1;
-            HIPCHK(hipMemsetAsync(e->rw_misc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_repair<false>, dim3(1), dim3(64), 0, s, u, records_begin, total, nseg, e->rw_guess.as<uint64_t>(), e->rw_leave.as<uint64_t>(), e->rw_cnt.as<uint32_t>(), e->rw_misc.as<unsigned int>() + 1);
-            HIPCHK(hipMemcpyAsync(flags, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-            if (flags[1]) return fail(e, GCE_ERR_INVALID, "truncated or damaged BAM record stream");
-            lap("repair");
-        }
-        HIPCHK(dev_exclusive_sum(e->rw_cnt.as<uint32_t>(), nseg, e->rw_base.as<uint64_t>(), e->rw_tmp, s));      // exclusive scan of the segments' record counts: the total comes out as base[nseg]
-        HIPCHK(hipMemcpyAsync(&n_rec, e->rw_base.as<uint64_t>() + nseg, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-        if (n_rec >= 0x7FFFFFF0ull) return fail(e, GCE_ERR_INVALID, "more than 2^31 records in one stream");
-        lap("segments + scan");
-        HIPCHK(e->rw_off.ensure((size_t)(n_rec + 1) * 8));
-        hipLaunchKernelGGL(k_raw_offsets<false>, dim3(nbs), dim3(256), 0, s, u, records_begin, total, nseg, (const uint64_t *)e->rw_guess.p, (const uint64_t *)e->rw_base.p, e->rw_off.as<uint64_t>());
+        std::string msg; uint64_t end = 0;
+        const int rc = dev_record_index<false>(e->rw, e->rw_tmp, s, u, records_begin, total, n_ref, e->idx_ctr, &n_rec, &end, msg);
+        if (tprint) fprintf(stderr, "gce_raw_finish: %lld of %lld segments off the chain\n", (long long)e->idx_ctr[1], (long long)e->idx_ctr[0]);
+        if (rc != GCE_OK) return fail(e, rc, msg);
+        lap("record index");
     }
     const size_t n1 = (size_t)(n_rec ? n_rec : 1);
     HIPCHK(e->b_core.ensure(n1 * sizeof(gce_core) + 64)); HIPCHK(e->b_qoff.ensure(n1 * 8 + 64)); HIPCHK(e->b_coff.ensure(n1 * 8 + 64)); HIPCHK(e->b_soff.ensure(n1 * 8 + 64)); HIPCHK(e->b_loff.ensure(n1 * 8 + 64));
@@ -608,20 +349,20 @@ int gce_raw_finish(gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t
     unsigned int have_mi = 0;
     if (n_rec) {
         RawSoA o{e->b_core.as<gce_core>(), e->b_qoff.as<uint64_t>(), e->b_soff.as<uint64_t>(), e->b_loff.as<uint64_t>(), e->b_mioff.as<uint64_t>(), e->rw_ncig.as<uint32_t>(), e->rw_nmpos.as<uint32_t>(),
-                 e->b_nm.as<int32_t>(), e->b_nmt.as<uint8_t>(), e->rw_misc.as<unsigned int>() + 2, e->rw_misc.as<unsigned int>() + 4, n_ref};
-        HIPCHK(hipMemsetAsync(e->rw_misc.as<unsigned int>() + 4, 0xFF, 4, s));
+                 e->b_nm.as<int32_t>(), e->b_nmt.as<uint8_t>(), e->rw.misc.as<unsigned int>() + 2, e->rw.misc.as<unsigned int>() + 4, n_ref};
+        HIPCHK(hipMemsetAsync(e->rw.misc.as<unsigned int>() + 4, 0xFF, 4, s));
         const unsigned nbr = (unsigned)((n_rec + 255) / 256);
-        hipLaunchKernelGGL(k_raw_fill, dim3(nbr), dim3(256), 0, s, u, (const uint64_t *)e->rw_off.p, n_rec, o);
+        hipLaunchKernelGGL(k_raw_fill, dim3(nbr), dim3(256), 0, s, u, (const uint64_t *)e->rw.off.p, n_rec, o);
         HIPCHK(e->b_coff.ensure((n1 + 1) * 8 + 64));
         HIPCHK(dev_exclusive_sum(e->rw_ncig.as<uint32_t>(), n_rec, e->b_coff.as<uint64_t>(), e->rw_tmp, s));
         HIPCHK(hipMemcpyAsync(&cig_words, e->b_coff.as<uint64_t>() + n_rec, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&have_mi, e->rw_misc.as<unsigned int>() + 2, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&have_mi, e->rw.misc.as<unsigned int>() + 2, 4, hipMemcpyDeviceToHost, s));
         unsigned int bad_rec = NONE32;
-        HIPCHK(hipMemcpyAsync(&bad_rec, e->rw_misc.as<unsigned int>() + 4, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&bad_rec, e->rw.misc.as<unsigned int>() + 4, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (bad_rec != NONE32) { char m[96]; snprintf(m, sizeof m, "inconsistent record lengths (record %u)", bad_rec); return fail(e, GCE_ERR_INVALID, m); }
         HIPCHK(e->b_cigar.ensure((size_t)cig_words * 4 + 64));
-        hipLaunchKernelGGL(k_raw_cigar, dim3(nbr), dim3(256), 0, s, u, (const uint64_t *)e->rw_off.p, n_rec, (const uint64_t *)e->b_coff.p, e->b_cigar.as<uint32_t>());
+        hipLaunchKernelGGL(k_raw_cigar, dim3(nbr), dim3(256), 0, s, u, (const uint64_t *)e->rw.off.p, n_rec, (const uint64_t *)e->b_coff.p, e->b_cigar.as<uint32_t>());
     } else HIPCHK(e->b_cigar.ensure(64));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
@@ -651,13 +392,13 @@ int gce_raw_build_output(gce_engine *e, uint64_t *body_bytes, int64_t *n_out) {
     const uint8_t *u = e->raw.as<uint8_t>();
     RawOut r{e->o_src.as<uint32_t>(), e->o_qsrc.as<uint32_t>(), e->o_nm.as<int32_t>(), e->o_fr.as<int16_t>(), e->o_rr.as<int16_t>()};
     const unsigned nb = (unsigned)((no + 255) / 256);
-    hipLaunchKernelGGL(k_rec_size, dim3(nb), dim3(256), 0, s, u, (const uint64_t *)e->rw_off.p, r, no, e->rw_rsize.as<uint64_t>());
+    hipLaunchKernelGGL(k_rec_size, dim3(nb), dim3(256), 0, s, u, (const uint64_t *)e->rw.off.p, r, no, e->rw_rsize.as<uint64_t>());
     HIPCHK(dev_exclusive_sum(e->rw_rsize.as<uint64_t>(), no, e->rw_roff.as<uint64_t>(), e->rw_tmp, s));
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, e->rw_roff.as<uint64_t>() + no, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
     HIPCHK(e->rw_body.ensure(total + 64));
-    hipLaunchKernelGGL(k_rec_build, dim3((unsigned)std::min<uint64_t>((no + 15) / 16, 65535u)), dim3(256), 0, s, u, (const uint64_t *)e->rw_off.p, (const uint32_t *)e->rw_nmpos.p, r, no, (const uint64_t *)e->rw_roff.p, e->rw_body.as<uint8_t>());
-    hipLaunchKernelGGL(k_rec_nm, dim3(nb), dim3(256), 0, s, u, (const uint64_t *)e->rw_off.p, (const uint32_t *)e->rw_nmpos.p, r, no, (const uint64_t *)e->rw_roff.p, e->rw_body.as<uint8_t>());
+    hipLaunchKernelGGL(k_rec_build, dim3((unsigned)std::min<uint64_t>((no + 15) / 16, 65535u)), dim3(256), 0, s, u, (const uint64_t *)e->rw.off.p, (const uint32_t *)e->rw_nmpos.p, r, no, (const uint64_t *)e->rw_roff.p, e->rw_body.as<uint8_t>());
+    hipLaunchKernelGGL(k_rec_nm, dim3(nb), dim3(256), 0, s, u, (const uint64_t *)e->rw.off.p, (const uint32_t *)e->rw_nmpos.p, r, no, (const uint64_t *)e->rw_roff.p, e->rw_body.as<uint8_t>());
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     e->raw_body_bytes = total; e->raw_body_nrec = (int64_t)no;                       // (rw_roff: the record starts, for gce_raw_format_output)
@@ -708,9 +449,9 @@ int gce_raw_select_shard(gce_engine *e, int32_t world, int32_t rank, int32_t pla
     e->shard_cut_done = false;
     if (e->prm.max_contig > 0) {
         unsigned int first = NONE32;
-        HIPCHK(hipMemcpyAsync(e->rw_misc.p, &first, 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_first_contig_ge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const gce_core *)e->b_core.as<gce_core>(), n, e->prm.max_contig, (unsigned int *)e->rw_misc.p);
-        HIPCHK(hipMemcpyAsync(&first, e->rw_misc.p, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpyAsync(e->rw.misc.p, &first, 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_first_contig_ge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const gce_core *)e->b_core.as<gce_core>(), n, e->prm.max_contig, (unsigned int *)e->rw.misc.p);
+        HIPCHK(hipMemcpyAsync(&first, e->rw.misc.p, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
         if (first != NONE32) { cut = (int64_t)first; n = cut; }
         e->shard_cut_done = rank != 0 || cut < 0;
     }
@@ -732,15 +473,15 @@ int gce_raw_select_shard(gce_engine *e, int32_t world, int32_t rank, int32_t pla
         HIPCHK(hipMemsetAsync(e->sh_flag.as<uint8_t>() + cut, rank == 0 ? 1 : 0, 1, s));
         HIPCHK(hipMemsetAsync(e->sh_tickall.as<uint64_t>() + cut, 0, 8, s));
     }
-    HIPCHK(dev_select_flagged(e->sh_flag.as<uint8_t>(), (uint64_t)(n + (cut >= 0 ? 1 : 0)), e->sh_sel.as<uint32_t>(), (unsigned long long *)e->rw_misc.p, e->rw_tmp, s));
+    HIPCHK(dev_select_flagged(e->sh_flag.as<uint8_t>(), (uint64_t)(n + (cut >= 0 ? 1 : 0)), e->sh_sel.as<uint32_t>(), (unsigned long long *)e->rw.misc.p, e->rw_tmp, s));
     int64_t m = 0;
-    HIPCHK(hipMemcpyAsync(&m, e->rw_misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(&m, e->rw.misc.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
     const size_t m1 = (size_t)(m > 0 ? m : 1);
     HIPCHK(e->sh_core.ensure(m1 * sizeof(gce_core) + 64)); HIPCHK(e->sh_qoff.ensure(m1 * 8 + 64)); HIPCHK(e->sh_coff.ensure(m1 * 8 + 64)); HIPCHK(e->sh_soff.ensure(m1 * 8 + 64)); HIPCHK(e->sh_loff.ensure(m1 * 8 + 64));
     HIPCHK(e->sh_nm.ensure(m1 * 4 + 64)); HIPCHK(e->sh_nmt.ensure(m1 + 64)); HIPCHK(e->sh_mioff.ensure(m1 * 8 + 64)); HIPCHK(e->sh_tick.ensure(m1 * 8 + 64)); HIPCHK(e->sh_roff.ensure(m1 * 8 + 64)); HIPCHK(e->sh_nmpos.ensure(m1 * 4 + 64));
     gce_batch &d = e->dev_batch;
     if (m > 0) {
-        ShardSrc a{d.core, d.qname_off, d.cigar_off, d.seq_off, d.qual_off, d.mi_off, (const uint64_t *)e->sh_tickall.p, (const uint64_t *)e->rw_off.p, d.nm, d.nm_type, (const uint32_t *)e->rw_nmpos.p};
+        ShardSrc a{d.core, d.qname_off, d.cigar_off, d.seq_off, d.qual_off, d.mi_off, (const uint64_t *)e->sh_tickall.p, (const uint64_t *)e->rw.off.p, d.nm, d.nm_type, (const uint32_t *)e->rw_nmpos.p};
         ShardDst o{e->sh_core.as<gce_core>(), e->sh_qoff.as<uint64_t>(), e->sh_coff.as<uint64_t>(), e->sh_soff.as<uint64_t>(), e->sh_loff.as<uint64_t>(), e->sh_mioff.as<uint64_t>(), e->sh_tick.as<uint64_t>(),
                    e->sh_roff.as<uint64_t>(), e->sh_nm.as<int32_t>(), e->sh_nmt.as<uint8_t>(), e->sh_nmpos.as<uint32_t>()};
         hipLaunchKernelGGL(k_shard_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const uint32_t *)e->sh_sel.p, m, a, o);
@@ -750,7 +491,7 @@ int gce_raw_select_shard(gce_engine *e, int32_t world, int32_t rank, int32_t pla
     d.n_reads = m; d.core = e->sh_core.as<gce_core>(); d.qname_off = e->sh_qoff.as<uint64_t>(); d.cigar_off = e->sh_coff.as<uint64_t>(); d.seq_off = e->sh_soff.as<uint64_t>(); d.qual_off = e->sh_loff.as<uint64_t>();
     d.nm = e->sh_nm.as<int32_t>(); d.nm_type = e->sh_nmt.as<uint8_t>(); if (d.mi_off) d.mi_off = e->sh_mioff.as<uint64_t>();
     d.tick = e->sh_tick.as<uint64_t>();
-    std::swap(e->rw_off, e->sh_roff); std::swap(e->rw_nmpos, e->sh_nmpos);          // gce_raw_build_output looks records up by the batch's (now: the shard's) read index
+    std::swap(e->rw.off, e->sh_roff); std::swap(e->rw_nmpos, e->sh_nmpos);          // gce_raw_build_output looks records up by the batch's (now: the shard's) read index
     e->have_tick = true; e->raw_records = m; e->shard_n = m;
     e->sh_tickall.release(); e->sh_shard.release(); e->sh_flag.release();
     return GCE_OK;
@@ -919,13 +660,11 @@ int gce_raw_deflate_output_codes(gce_engine *e, int32_t codes, uint64_t *comp_by
     if (nb64 >= 0x7FFFFFF0ull) return fail(e, GCE_ERR_INVALID, "output stream too large for one deflate pass");
     const uint32_t nb = (uint32_t)nb64, slot = (uint32_t)(blk + blk / 8 + 64);
     HIPCHK(e->zo_slots.ensure((size_t)nb * slot + 64)); HIPCHK(e->zo_sizes.ensure(((size_t)nb + 1) * 4)); HIPCHK(e->zo_off.ensure(((size_t)nb + 1) * 8));
-    def_launch(codes, nb, s, (const uint8_t *)e->rw_body.p, total, (uint32_t)blk, e->zo_slots.as<uint8_t>(), slot, e->zo_sizes.as<uint32_t>());
-    HIPCHK(hipMemsetAsync((char *)e->zo_sizes.p + (size_t)nb * 4, 0, 4, s));
-    HIPCHK(dev_exclusive_sum(e->zo_sizes.as<uint32_t>(), (uint64_t)nb, e->zo_off.as<uint64_t>(), e->rw_tmp, s));
-    uint64_t csz = 0;
-    HIPCHK(hipMemcpyAsync(&csz, e->zo_off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    uint64_t csz = 0; std::string msg;
+    const int rc = dev_deflate_members(codes, (const uint8_t *)e->rw_body.p, total, (uint32_t)blk, nb, e->zo_slots.as<uint8_t>(), slot, e->zo_sizes.as<uint32_t>(), e->zo_off.as<uint64_t>(), e->rw_tmp, s, &csz, msg);
+    if (rc != GCE_OK) return fail(e, rc, msg);
     HIPCHK(e->zo_out.ensure(csz + 64));
-    hipLaunchKernelGGL(k_deflate_pack, dim3(std::min<uint32_t>((nb + 3) / 4, 16384u)), dim3(256), 0, s, (const uint8_t *)e->zo_slots.p, slot, (const uint32_t *)e->zo_sizes.p, (const uint64_t *)e->zo_off.p, nb, e->zo_out.as<uint8_t>());
+    dev_deflate_pack((const uint8_t *)e->zo_slots.p, slot, (const uint32_t *)e->zo_sizes.p, (const uint64_t *)e->zo_off.p, nb, e->zo_out.as<uint8_t>(), s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     e->zo_slots.release();

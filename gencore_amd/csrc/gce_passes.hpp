@@ -6,7 +6,7 @@
 //   pass k     per window: the records of range k (and, in pass 0, the cut read) appended to the engine's raw stream with their global ticks
 //              and places in the whole stream; the smallest (tid, pos) of any read of a later range (the watermark W_k)
 // A window arrives as whole BGZF members of the file, is inflated by the GPU behind the record the last window's end cut and indexed by the
-// segment walks of gce_raw_finish (with a soft end: the record the window's end cuts is carried over in HBM to the next window).  The
+// record index of gce_devstream.hpp (dev_record_index, with a soft end: the record the window's end cuts is carried over in HBM to the next window).  The
 // per-read decisions reuse the planner's kernels (k_plan_keys, k_plan_range) and the cut of gce_process (k_first_contig_ge): every pass sees
 // the same key, tick and event as the whole stream does.
 #pragma once
@@ -80,27 +80,26 @@ __global__ void k_pass_range_w(const unsigned long long *key, const uint32_t *w,
     atomicAdd(sum + s, (unsigned long long)w[i]);
 }
 
-// a device buffer that keeps its first `used` bytes when it grows
-static hipError_t pass_grow(DevBuf &b, size_t need, size_t used, hipStream_t s) {
-    if (need <= b.cap && b.p) return hipSuccess;
-    DevBuf nb;
-    hipError_t r = nb.ensure(need + need / 2);
-    if (r != hipSuccess) return r;
-    if (used && (r = hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, s)) != hipSuccess) { nb.release(); return r; }
-    if ((r = hipStreamSynchronize(s)) != hipSuccess) { nb.release(); return r; }
-    b.release(); b = nb;
-    return hipSuccess;
-}
+// a device buffer that keeps its first `used` bytes when it grows: half as much again as is needed (and DevBuf's eighth)
+static hipError_t pass_grow(DevBuf &b, size_t need, size_t used, hipStream_t s) { return dev_grow_keep(b, need, used, DevBuf::padded(need + need / 2), s); }
 
-// one window of a BGZF file on the GPU, shared by the pass runner (gce_passes_window) and the BAI indexer (gce_bai.hpp): whole BGZF members in
-// host memory are copied to HBM and inflated (k_bgzf_inflate, as gce_raw_push_bgzf) behind the record the last window's end cut; the records of
-// [skip, total) are indexed by the segment walks of gce_raw_finish with a soft end (k_raw_seg / k_raw_check / k_raw_fix / k_raw_repair): the
-// record the window's end cuts is left for win_carry to move to the front.  win holds the inflated bytes, off the n_rec record starts.
+// one window of a BGZF file on the GPU, shared by the pass runner (gce_passes_window), the BAI indexer (gce_bai.hpp) and the sort (gce_sort.hpp):
+// whole BGZF members in host memory are copied to HBM and inflated (dev_inflate_members, as gce_raw_push_bgzf) behind the record the last
+// window's end cut; the records of [skip, total) are indexed by dev_record_index with a soft end: the record the window's end cuts is left
+// for win_carry to move to the front.  win holds the inflated bytes, idx.off the n_rec record starts.
 struct WinIdx {
-    DevBuf win, off, zc, zdir, zerr, guess, leave, cnt, base, bad_of, rmisc, ctmp; uint64_t carry_n = 0;
-    void release() { for (DevBuf *b : {&win, &off, &zc, &zdir, &zerr, &guess, &leave, &cnt, &base, &bad_of, &rmisc, &ctmp}) b->release(); carry_n = 0; }
+    DevBuf win, zc, zdir, zerr, ctmp; RecIdx idx; uint64_t carry_n = 0;
+    void release() { for (DevBuf *b : {&win, &zc, &zdir, &zerr, &ctmp}) b->release(); idx.release(); carry_n = 0; }
+    uint64_t held() const { uint64_t a = 0; for (const DevBuf *b : {&win, &zc, &zdir, &zerr, &ctmp, &idx.guess, &idx.leave, &idx.cnt, &idx.base, &idx.bad_of, &idx.misc, &idx.off}) a += b->cap; return a; }
 };
-#define WCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { msg = std::string(#call) + ": " + hipGetErrorString(_e); return _e == hipErrorOutOfMemory ? GCE_ERR_OOM : GCE_ERR_HIP; } } while (0)
+// the device bytes the next window takes beyond what w holds: its inflated bytes (u_all of them, the carried ones included) as pass_grow makes
+// the buffer (3/2 x 9/8 = 27/16) and its compressed bytes as DevBuf::ensure does (9/8), each only where the buffer has to grow
+static uint64_t win_room(const WinIdx &w, uint64_t comp_bytes, uint64_t u_all) {
+    uint64_t add = 0;
+    if (u_all + 64 > w.win.cap) add += (u_all + 64) * 27 / 16 + 256;
+    if (comp_bytes + 64 > w.zc.cap) add += (comp_bytes + 64) * 9 / 8 + 256;
+    return add;
+}
 // -> *total (inflated bytes in w.win, the carried ones included), *n_rec, *end (where the window's last whole record ends).  ctr: the four index
 // counters to add to (gce_get_index_counters) or NULL.  last: the final piece of the file (a record cut there is a truncated stream).
 static int win_inflate_index(WinIdx &w, DevBuf &tmp, hipStream_t s, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize,
@@ -112,56 +111,24 @@ static int win_inflate_index(WinIdx &w, DevBuf &tmp, hipStream_t s, const void *
         InfDir d; d.coff = coff[k]; d.uoff = total; d.csize = csize[k]; d.usize = usize[k]; dir.push_back(d); total += usize[k];
     }
     if (w.carry_n && skip) return GCE_ERR_INVALID;
-    WCHK(pass_grow(w.win, (size_t)total + 64, (size_t)w.carry_n, s));
+    MCHK(pass_grow(w.win, (size_t)total + 64, (size_t)w.carry_n, s));
     if (!dir.empty()) {
-        const size_t m = dir.size();
-        WCHK(w.zc.ensure(comp_bytes + 64)); WCHK(w.zdir.ensure(m * (sizeof(InfDir) + INF_NSYM) + 64)); WCHK(w.zerr.ensure(16));
-        WCHK(hipMemcpyAsync(w.zc.p, comp, comp_bytes, hipMemcpyHostToDevice, s));
-        WCHK(hipMemsetAsync((char *)w.zc.p + comp_bytes, 0, 64, s));                 // (the bit reader looks up to 32 bytes ahead)
-        WCHK(hipMemcpyAsync(w.zdir.p, dir.data(), m * sizeof(InfDir), hipMemcpyHostToDevice, s));
-        const unsigned int init[2] = {0u, 0xFFFFFFFFu};
-        WCHK(hipMemcpyAsync(w.zerr.p, init, 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((m + INF_T - 1) / INF_T)), dim3(INF_T), 0, s, w.zc.as<uint8_t>(), (const InfDir *)w.zdir.p, (uint32_t)m, w.win.as<uint8_t>(), w.zerr.as<unsigned int>(),
-                           w.zdir.as<uint8_t>() + m * sizeof(InfDir));
-        unsigned int got[2] = {0, 0};
-        WCHK(hipMemcpyAsync(got, w.zerr.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s)); WCHK(hipGetLastError());
-        if (got[0]) { char m2[96]; snprintf(m2, sizeof m2, "inflate / CRC failure in BGZF member %u of a window", got[1]); msg = m2; return GCE_ERR_INVALID; }
+        MCHK(w.zc.ensure(comp_bytes + 64)); MCHK(w.zdir.ensure(dir.size() * (sizeof(InfDir) + INF_NSYM) + 64));   // (a window's directory scratch has 64 spare bytes)
+        MCHK(hipMemcpyAsync(w.zc.p, comp, comp_bytes, hipMemcpyHostToDevice, s));
+        int64_t bad = -1;
+        const int rc = dev_inflate_members(w.zc.as<uint8_t>(), comp_bytes, dir.data(), dir.size(), w.win.as<uint8_t>(), w.zdir, w.zerr, s, &bad, msg);
+        if (rc != GCE_OK) return rc;
+        if (bad >= 0) { char m2[96]; snprintf(m2, sizeof m2, "inflate / CRC failure in BGZF member %u of a window", (uint32_t)bad); msg = m2; return GCE_ERR_INVALID; }
     }
-    WCHK(hipMemsetAsync(w.win.as<uint8_t>() + total, 0, 64, s));
+    MCHK(hipMemsetAsync(w.win.as<uint8_t>() + total, 0, 64, s));
     const uint64_t start = std::min<uint64_t>(skip, total);
-    const uint8_t *u = w.win.as<uint8_t>();
     uint64_t n_rec = 0, end = start;
     if (total > start) {                                                             // ---- the record index of [start, total), soft end
-        const uint64_t nseg = (total - start + RAW_SEG - 1) / RAW_SEG;
-        const unsigned nbs = (unsigned)((nseg + 255) / 256);
-        WCHK(w.guess.ensure(nseg * 8)); WCHK(w.leave.ensure(nseg * 8)); WCHK(w.cnt.ensure(nseg * 4 + 8)); WCHK(w.base.ensure(nseg * 8 + 8)); WCHK(w.bad_of.ensure(nseg + 8)); WCHK(w.rmisc.ensure(64));
-        WCHK(hipMemsetAsync(w.rmisc.p, 0, 64, s));
-        hipLaunchKernelGGL(k_raw_seg<true>, dim3(nbs), dim3(256), 0, s, u, start, total, n_ref, nseg, w.guess.as<uint64_t>(), w.leave.as<uint64_t>(), w.cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)w.guess.p, (const uint64_t *)w.leave.p, nseg, total, w.rmisc.as<unsigned int>(), w.bad_of.as<uint8_t>());
-        unsigned int flags[2] = {0, 0};
-        WCHK(hipMemcpyAsync(flags, w.rmisc.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
-        if (ctr) { __atomic_add_fetch(&ctr[0], (int64_t)nseg, __ATOMIC_RELAXED); __atomic_add_fetch(&ctr[1], (int64_t)flags[0], __ATOMIC_RELAXED); }
-        for (int round = 0; flags[0] && round < 64; round++) {
-            WCHK(hipMemsetAsync(w.rmisc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_fix<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, w.guess.as<uint64_t>(), w.leave.as<uint64_t>(), w.cnt.as<uint32_t>(), (const uint8_t *)w.bad_of.p);
-            hipLaunchKernelGGL(k_raw_check<true>, dim3(nbs), dim3(256), 0, s, (const uint64_t *)w.guess.p, (const uint64_t *)w.leave.p, nseg, total, w.rmisc.as<unsigned int>(), w.bad_of.as<uint8_t>());
-            WCHK(hipMemcpyAsync(flags, w.rmisc.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
-            if (ctr) __atomic_add_fetch(&ctr[2], (int64_t)1, __ATOMIC_RELAXED);
-        }
-        if (flags[0]) {
-            if (ctr) __atomic_add_fetch(&ctr[3], (int64_t)1, __ATOMIC_RELAXED);
-            WCHK(hipMemsetAsync(w.rmisc.p, 0, 16, s));
-            hipLaunchKernelGGL(k_raw_repair<true>, dim3(1), dim3(64), 0, s, u, start, total, nseg, w.guess.as<uint64_t>(), w.leave.as<uint64_t>(), w.cnt.as<uint32_t>(), w.rmisc.as<unsigned int>() + 1);
-            WCHK(hipMemcpyAsync(flags, w.rmisc.p, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
-            if (flags[1]) { msg = "truncated or damaged BAM record stream"; return GCE_ERR_INVALID; }
-        }
-        WCHK(dev_exclusive_sum(w.cnt.as<uint32_t>(), nseg, w.base.as<uint64_t>(), tmp, s));
-        WCHK(hipMemcpyAsync(&n_rec, w.base.as<uint64_t>() + nseg, 8, hipMemcpyDeviceToHost, s));
-        WCHK(hipMemcpyAsync(&end, w.leave.as<uint64_t>() + nseg - 1, 8, hipMemcpyDeviceToHost, s)); WCHK(hipStreamSynchronize(s));
-        if (end > total || n_rec >= 0x7FFFFFF0ull) { msg = "truncated or damaged BAM record stream"; return GCE_ERR_INVALID; }
-        WCHK(w.off.ensure((size_t)(n_rec + 1) * 8));
-        if (n_rec) hipLaunchKernelGGL(k_raw_offsets<true>, dim3(nbs), dim3(256), 0, s, u, start, total, nseg, (const uint64_t *)w.guess.p, (const uint64_t *)w.base.p, w.off.as<uint64_t>());
-        WCHK(hipStreamSynchronize(s)); WCHK(hipGetLastError());
+        int64_t c[4];
+        const int rc = dev_record_index<true>(w.idx, tmp, s, w.win.as<uint8_t>(), start, total, n_ref, c, &n_rec, &end, msg);
+        if (ctr) for (int k = 0; k < 4; k++) __atomic_add_fetch(&ctr[k], c[k], __ATOMIC_RELAXED);
+        if (rc != GCE_OK) return rc;
+        MCHK(hipStreamSynchronize(s)); MCHK(hipGetLastError());
     }
     if (last && end != total) { msg = "truncated record at the end of the BAM stream"; return GCE_ERR_INVALID; }
     *total_out = total; *n_rec_out = n_rec; *end_out = end;
@@ -171,14 +138,13 @@ static int win_inflate_index(WinIdx &w, DevBuf &tmp, hipStream_t s, const void *
 static int win_carry(WinIdx &w, hipStream_t s, uint64_t total, uint64_t end, std::string &msg) {
     w.carry_n = total - end;
     if (w.carry_n) {
-        WCHK(w.ctmp.ensure(w.carry_n + 64));
-        WCHK(hipMemcpyAsync(w.ctmp.p, w.win.as<uint8_t>() + end, w.carry_n, hipMemcpyDeviceToDevice, s));
-        WCHK(hipMemcpyAsync(w.win.p, w.ctmp.p, w.carry_n, hipMemcpyDeviceToDevice, s));
-        WCHK(hipStreamSynchronize(s));
+        MCHK(w.ctmp.ensure(w.carry_n + 64));
+        MCHK(hipMemcpyAsync(w.ctmp.p, w.win.as<uint8_t>() + end, w.carry_n, hipMemcpyDeviceToDevice, s));
+        MCHK(hipMemcpyAsync(w.win.p, w.ctmp.p, w.carry_n, hipMemcpyDeviceToDevice, s));
+        MCHK(hipStreamSynchronize(s));
     }
     return GCE_OK;
 }
-#undef WCHK
 
 }  // namespace
 
@@ -239,7 +205,7 @@ int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes)
     return hipMemGetInfo(free_bytes, total_bytes) == hipSuccess ? GCE_OK : GCE_ERR_HIP;
 }
 
-// the records of the window (n, at p->w.off in p->w.win, on the device): e == NULL: the key pass; otherwise pass p->k, whose records go to e's raw
+// the records of the window (n, at p->w.idx.off in p->w.win, on the device): e == NULL: the key pass; otherwise pass p->k, whose records go to e's raw
 // stream.  *cut_reached: the --quit_after_contig cut lies in this window (nothing behind it exists: the caller stops reading).
 static int pass_records(gce_passes *p, gce_engine *e, int64_t n, int32_t *cut_reached) {
     *cut_reached = 0;
@@ -250,7 +216,7 @@ static int pass_records(gce_passes *p, gce_engine *e, int64_t n, int32_t *cut_re
     const size_t n1 = (size_t)n;
     PCHK(p->core.ensure(n1 * sizeof(gce_core) + 64)); PCHK(p->key.ensure(n1 * 8)); PCHK(p->tick.ensure(n1 * 8 + 8));
     PCHK(p->xs.ensure(n1 * 8 + 16)); PCHK(p->flag.ensure(n1 + 64)); PCHK(p->sel.ensure(n1 * 4 + 64)); PCHK(p->misc.ensure(64));
-    const uint8_t *u = p->w.win.as<uint8_t>(); const uint64_t *off = p->w.off.as<uint64_t>();
+    const uint8_t *u = p->w.win.as<uint8_t>(); const uint64_t *off = p->w.idx.off.as<uint64_t>();
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_pass_core, dim3(nb), dim3(256), 0, s, u, off, n, p->core.as<gce_core>());
     // misc: [0] the first read of contig >= max_contig, [1] the first unmapped read, [2] bad, [4..5] a count (uint64)
@@ -333,9 +299,9 @@ static int pass_records(gce_passes *p, gce_engine *e, int64_t n, int32_t *cut_re
 }
 
 // the next piece of the file: `n_members` whole BGZF members in host memory (member k at comp + coff[k], csize[k] bytes, ISIZE usize[k]).  They
-// are copied to HBM and inflated by the GPU (k_bgzf_inflate, as gce_raw_push_bgzf) behind the record the last window's end cut; the first
-// `skip` inflated bytes (the BAM header) are passed over; the records are indexed by the segment walks of gce_raw_finish from the carried
-// offset (k_raw_seg / k_raw_check / k_raw_fix / k_raw_repair with a soft end: the record the window's end cuts is carried over to the next window) and
+// are copied to HBM and inflated by the GPU (dev_inflate_members, as gce_raw_push_bgzf) behind the record the last window's end cut; the first
+// `skip` inflated bytes (the BAM header) are passed over; the records are indexed from the carried offset (dev_record_index of
+// gce_devstream.hpp with a soft end: the record the window's end cuts is carried over to the next window) and
 // go to pass_records.  last: the final piece of the file (a record cut there is a truncated stream).
 int gce_passes_window(gce_passes *p, gce_engine *e, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize,
                       uint64_t skip, int32_t n_ref, int32_t last, int32_t *cut_reached) {
@@ -459,7 +425,7 @@ int gce_passes_release(gce_passes *p, gce_engine *e) {
     (void)hipStreamSynchronize(e->stream);
     e->dev_batch = gce_batch{};
     for (DevBuf *b : {&e->b_core, &e->b_qoff, &e->b_qname, &e->b_coff, &e->b_cigar, &e->b_soff, &e->b_seq, &e->b_loff, &e->b_qual, &e->b_nm, &e->b_nmt, &e->b_mioff, &e->b_mi, &e->b_tick,
-                      &e->raw, &e->rw_bad, &e->rw_guess, &e->rw_leave, &e->rw_cnt, &e->rw_base, &e->rw_off, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body, &e->o_src, &e->o_qsrc, &e->o_nm, &e->o_fr, &e->o_rr})
+                      &e->raw, &e->rw.bad_of, &e->rw.guess, &e->rw.leave, &e->rw.cnt, &e->rw.base, &e->rw.off, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body, &e->o_src, &e->o_qsrc, &e->o_nm, &e->o_fr, &e->o_rr})
         b->release();
     p->ptick.release(); p->pgidx.release();
     return gce_reset(e);

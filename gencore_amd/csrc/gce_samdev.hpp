@@ -343,8 +343,9 @@ struct SamDev {
 // the device bytes a window of n text bytes and nl lines takes, as DevBuf::ensure makes them: the text and the flags, 41 bytes per line
 // (the staging of the host's records is counted apart: SamDev::host_bytes)
 static uint64_t sam_win_need(uint64_t n, uint64_t nl) { return ((n + 128) * 2 + nl * 45 + 4096) * 9 / 8 + 13 * 256; }
+// ... and that staging: the records and their 8-byte starts, as DevBuf::ensure makes the two buffers
+static uint64_t sam_host_need(const SamDev &d) { return (d.host_bytes + d.n_host * 8 + 64) * 9 / 8 + 512; }
 
-#define MCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { msg = std::string(#call) + ": " + hipGetErrorString(_e); return _e == hipErrorOutOfMemory ? GCE_ERR_OOM : GCE_ERR_HIP; } } while (0)
 static int sam_contigs(SamDev &d, hipStream_t s, const std::vector<std::string> &names, std::string &msg) {
     d.nmap.build(names);
     std::vector<uint32_t> idx(names.size()); std::iota(idx.begin(), idx.end(), 0u);
@@ -459,7 +460,6 @@ static int sam_emit(SamDev &d, hipStream_t s, const char *text, uint8_t *out, st
     d.kernel_s += mono_s() - t0;
     return GCE_OK;
 }
-#undef MCHK
 
 }  // namespace
 

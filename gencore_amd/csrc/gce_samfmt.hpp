@@ -296,7 +296,6 @@ struct SamFmt {
     void release() { for (DevBuf *b : {&size, &hostf, &oseq, &loff, &hlist, &misc, &nblob, &noff, &hmeta, &hsoff, &hstage, &htoff, &htext}) b->release(); }
 };
 
-#define MCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { msg = std::string(#call) + ": " + hipGetErrorString(_e); return _e == hipErrorOutOfMemory ? GCE_ERR_OOM : GCE_ERR_HIP; } } while (0)
 static int samfmt_names(SamFmt &d, hipStream_t s, const std::vector<std::string> &names, std::string &msg) {
     std::vector<uint8_t> blob; std::vector<uint32_t> off;
     for (const std::string &x : names) { off.push_back((uint32_t)blob.size()); blob.insert(blob.end(), x.begin(), x.end()); }
@@ -366,7 +365,6 @@ static int samfmt_emit(SamFmt &d, hipStream_t s, const uint8_t *rec, uint64_t n,
     __atomic_add_fetch(&g_samfmt_ctr[2], 1, __ATOMIC_RELAXED); __atomic_add_fetch(&g_samfmt_ctr[3], (int64_t)d.total, __ATOMIC_RELAXED);
     return GCE_OK;
 }
-#undef MCHK
 
 static bool samfmt_names_ok(int32_t n_ref, const char *const *ref_name, std::vector<std::string> &names) {      // (offsets into the blob and SEQ's place in a line are 32 bits)
     uint64_t sum = 0;
@@ -431,10 +429,10 @@ int gce_raw_format_output(gce_engine *e, int32_t n_ref, const char *const *ref_n
     uint64_t nr = (uint64_t)std::max<int64_t>(e->raw_body_nrec, 0);
     if (e->raw_body_nrec < 0 || e->rw_roff.cap < (nr + 1) * 8) {                      // nobody kept the starts: follow the block sizes
         const uint64_t cap = total / 36 + 1;
-        HIPCHK(e->rw_roff.ensure((cap + 1) * 8)); HIPCHK(e->rw_misc.ensure(64));
-        hipLaunchKernelGGL(k_samfmt_walk, dim3(1), dim3(64), 0, s, rec, total, e->rw_roff.as<uint64_t>(), cap, e->rw_misc.as<unsigned long long>());
+        HIPCHK(e->rw_roff.ensure((cap + 1) * 8)); HIPCHK(e->rw.misc.ensure(64));
+        hipLaunchKernelGGL(k_samfmt_walk, dim3(1), dim3(64), 0, s, rec, total, e->rw_roff.as<uint64_t>(), cap, e->rw.misc.as<unsigned long long>());
         unsigned long long res[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(res, e->rw_misc.p, sizeof res, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(res, e->rw.misc.p, sizeof res, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipGetLastError());
         if (res[1] != ~0ull || res[0] > cap) return fail(e, GCE_ERR_INVALID, "bad record in the output stream");
         nr = res[0]; e->raw_body_nrec = (int64_t)nr;
     }

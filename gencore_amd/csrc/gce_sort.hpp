@@ -10,8 +10,8 @@
 //   in sorted order, dev_exclusive_sum -> the destination offsets, and
 //   k_sort_gather   the record bytes into a second buffer in the new order: 16 lanes per record, 16-byte stores aligned on the DESTINATION
 //                   (the bytes in front of the first aligned chunk and behind the last one go as single bytes), source read unaligned
-// gce_sort_read hands the sorted stream out in pieces: raw, or as BGZF members of 0xff00 input bytes deflated on the device (def_launch,
-// k_deflate_pack).  In-core: about 2 x the inflated record bytes + 20 bytes per record + one window; a file beyond that is GCE_ERR_OOM.
+// gce_sort_read hands the sorted stream out in pieces: raw, or as BGZF members of 0xff00 input bytes deflated on the device (dev_deflate_members,
+// dev_deflate_pack).  In-core: about 2 x the inflated record bytes + 20 bytes per record + one window; a file beyond that is GCE_ERR_OOM.
 //
 // A file beyond that is sorted in output-range passes (gce_bam_sort_passes): the key pass streams the file the same way but keeps only key and
 // size of every record (gce_sort_key_window); gce_sort_plan sorts and scans as above and inverts the order,
@@ -170,14 +170,10 @@ static int sort_grow(gce_sort *b, DevBuf &buf, size_t need, size_t used, size_t 
     if (need <= buf.cap && buf.p) return GCE_OK;
     const size_t want = std::max(need, target) + 256;
     if (!sort_room(b, want)) return sort_oom(b, what, want);
-    DevBuf nb;
-    hipError_t r = hipMalloc(&nb.p, want);
-    if (r != hipSuccess) { nb.p = nullptr; return r == hipErrorOutOfMemory ? sort_oom(b, what, want) : sfail(b, GCE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(r)); }
-    nb.cap = want; dev_bytes_add((long long)want);
-    if (used && (r = hipMemcpyAsync(nb.p, buf.p, used, hipMemcpyDeviceToDevice, b->s)) != hipSuccess) { nb.release(); return sfail(b, GCE_ERR_HIP, hipGetErrorString(r)); }
-    if ((r = hipStreamSynchronize(b->s)) != hipSuccess) { nb.release(); return sfail(b, GCE_ERR_HIP, hipGetErrorString(r)); }
-    buf.release(); buf = nb;
-    return GCE_OK;
+    bool in_alloc = false;
+    const hipError_t r = dev_grow_keep(buf, need, used, want, b->s, &in_alloc);
+    if (r == hipErrorOutOfMemory && in_alloc) return sort_oom(b, what, want);
+    return r == hipSuccess ? GCE_OK : sfail(b, GCE_ERR_HIP, std::string(in_alloc ? "hipMalloc: " : "") + hipGetErrorString(r));
 }
 // the slots of one deflated piece of `piece` input bytes
 static uint32_t sort_slot() { return 0xff00u + 0xff00u / 8 + 64; }
@@ -190,10 +186,35 @@ static int sort_deflate_bufs(gce_sort *b, uint64_t piece_bytes) {
     return GCE_OK;
 }
 // the device bytes a window holds (a window that grows holds its old inflated bytes beside the new ones for a moment: pass_grow)
-static uint64_t sort_win_need(const WinIdx &w, const DevBuf &tmp) {
-    uint64_t a = w.win.cap + tmp.cap;
-    for (const DevBuf *x : {&w.win, &w.off, &w.zc, &w.zdir, &w.zerr, &w.guess, &w.leave, &w.cnt, &w.base, &w.bad_of, &w.rmisc, &w.ctmp}) a += x->cap;
-    return a;
+static uint64_t sort_win_need(const WinIdx &w, const DevBuf &tmp) { return w.win.cap + tmp.cap + w.held(); }
+// before win_inflate_index makes the window's own buffers: is there room for them (win_room)?
+static int sort_win_check(gce_sort *b, size_t comp_bytes, int32_t n_members, const uint32_t *usize) {
+    uint64_t u_all = b->w.carry_n; for (int32_t k = 0; k < n_members; k++) u_all += usize[k];
+    const uint64_t add = win_room(b->w, comp_bytes, u_all);
+    return add && !sort_room(b, add) ? sort_oom(b, "a window of the file", add) : GCE_OK;
+}
+// the counters of k_sort_keys, made and set on first use
+static int sort_counters_init(gce_sort *b) {
+    if (b->misc.p) return GCE_OK;
+    if (!sort_room(b, 512)) return sort_oom(b, "the sort's counters", 512);
+    SCHK(b->misc.ensure(64));
+    const unsigned long long init[3] = {~0ull, 0ull, 0ull};
+    SCHK(hipMemcpyAsync(b->misc.p, init, sizeof init, hipMemcpyHostToDevice, b->s)); SCHK(hipStreamSynchronize(b->s));
+    return GCE_OK;
+}
+// room for n_rec more records of add_bytes bytes behind the resident ones (the output-range passes keep neither the bytes nor their offsets).
+// A buffer that has to be made or grown is sized from the estimates: the file's record bytes (est_bytes, never below what is known), and its
+// records at the bytes per record seen so far, 1/16 added to each.
+static int sort_take(gce_sort *b, uint64_t n_rec, uint64_t add_bytes, uint64_t est_bytes) {
+    const uint64_t n1 = b->n + n_rec, have = b->rec_n + add_bytes;
+    const uint64_t eb = std::max<uint64_t>(est_bytes, have), en = (uint64_t)((double)n1 * ((double)eb / (double)have));
+    const size_t tn = (size_t)(en + en / 16 + 64);
+    int rc;
+    if (!b->passes && (rc = sort_grow(b, b->rec, (size_t)(have + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
+    if ((rc = sort_grow(b, b->key, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' keys")) != GCE_OK) return rc;
+    if ((rc = sort_grow(b, b->size, (size_t)n1 * 4, (size_t)b->n * 4, tn * 4, "the records' sizes")) != GCE_OK) return rc;
+    if (!b->passes && (rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
+    return GCE_OK;
 }
 
 extern "C" {
@@ -226,34 +247,17 @@ static int sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t
     if (!b || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
-    {   // the window's own buffers, before win_inflate_index makes them: the inflated bytes (pass_grow takes half as much again) and the compressed ones
-        uint64_t u_all = b->w.carry_n; for (int32_t k = 0; k < n_members; k++) u_all += usize[k];
-        uint64_t add = 0;
-        if (u_all + 64 > b->w.win.cap) add += (u_all + 64) * 27 / 16 + 256;
-        if (comp_bytes + 64 > b->w.zc.cap) add += (comp_bytes + 64) * 9 / 8 + 256;
-        if (add && !sort_room(b, add)) return sort_oom(b, "a window of the file", add);
-    }
-    if (!b->misc.p) {
-        if (!sort_room(b, 512)) return sort_oom(b, "the sort's counters", 512);
-        SCHK(b->misc.ensure(64));
-        const unsigned long long init[3] = {~0ull, 0ull, 0ull};
-        SCHK(hipMemcpyAsync(b->misc.p, init, sizeof init, hipMemcpyHostToDevice, s)); SCHK(hipStreamSynchronize(s));
-    }
+    int rc;
+    if ((rc = sort_win_check(b, comp_bytes, n_members, usize)) != GCE_OK || (rc = sort_counters_init(b)) != GCE_OK) return rc;
     uint64_t total = 0, n_rec = 0, end = 0;
-    int rc = win_inflate_index(b->w, b->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, b->err);
+    rc = win_inflate_index(b->w, b->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, b->err);
     if (rc == GCE_ERR_OOM) return sort_oom(b, "a window of the file", 0);
     if (rc != GCE_OK) return rc;
     if (n_rec) {
         const uint64_t start = std::min<uint64_t>(skip, total), add = end - start, n1 = b->n + n_rec;
         if (n1 >= SORT_MAX_RECORDS) return sfail(b, GCE_ERR_INVALID, "more than 2^32 - 16 records in one BAM file");
-        // the estimates: the file's record bytes (never below what is known), and its records at the bytes per record seen so far, 1/16 added
-        const uint64_t eb = std::max<uint64_t>(est_bytes, b->rec_n + add), en = (uint64_t)((double)n1 * ((double)eb / (double)(b->rec_n + add)));
-        if (!b->passes && (rc = sort_grow(b, b->rec, (size_t)(b->rec_n + add + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
-        const size_t tn = (size_t)(en + en / 16 + 64);
-        if ((rc = sort_grow(b, b->key, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' keys")) != GCE_OK) return rc;
-        if ((rc = sort_grow(b, b->size, (size_t)n1 * 4, (size_t)b->n * 4, tn * 4, "the records' sizes")) != GCE_OK) return rc;
-        if (!b->passes && (rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
-        hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.off.p, (int64_t)n_rec, start, b->rec_n, b->n, n_ref,
+        if ((rc = sort_take(b, n_rec, add, est_bytes)) != GCE_OK) return rc;
+        hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.idx.off.p, (int64_t)n_rec, start, b->rec_n, b->n, n_ref,
                            b->key.as<unsigned long long>(), b->size.as<uint32_t>(), b->off.as<uint64_t>(), b->misc.as<unsigned long long>());
         SCHK(hipGetLastError());
         if (!b->passes) SCHK(hipMemcpyAsync(b->rec.as<uint8_t>() + b->rec_n, b->w.win.as<uint8_t>() + start, add, hipMemcpyDeviceToDevice, s));
@@ -277,7 +281,7 @@ int gce_sort_key_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_
 }
 
 // SAM text in (gce_sam_sort): the contig names once, then window after window of whole alignment lines (host memory, n < 2^32).  The lines
-// become BAM records on the device (gce_samdev.hpp), written behind the resident records; their starts are what w.off is to gce_sort_window.
+// become BAM records on the device (gce_samdev.hpp), written behind the resident records; their starts are what w.idx.off is to gce_sort_window.
 // *bad_line >= 0: the window's first bad line (counting its record lines from 0), *bad_start its first byte in text, the error line_to_bam's
 // message for it; nothing of the window is kept.  *n_host_lines: the lines the host re-parsed (floating-point values); it and *parse_s are
 // added to.  *resident_bytes: the record bytes held so far.
@@ -298,34 +302,25 @@ int gce_sort_sam_window(gce_sort *b, const char *text, size_t n, int32_t n_ref, 
     hipStream_t s = b->s;
     SamDev &d = b->sam;
     *bad_line = -1; *bad_start = 0;
-    if (!b->misc.p) {
-        if (!sort_room(b, 512)) return sort_oom(b, "the sort's counters", 512);
-        SCHK(b->misc.ensure(64));
-        const unsigned long long init[3] = {~0ull, 0ull, 0ull};
-        SCHK(hipMemcpyAsync(b->misc.p, init, sizeof init, hipMemcpyHostToDevice, s)); SCHK(hipStreamSynchronize(s));
-    }
+    int rc = sort_counters_init(b);
+    if (rc != GCE_OK) return rc;
     const double k0 = d.kernel_s;
     auto grown = [&](uint64_t need) { const uint64_t held = d.held(); return need > held ? need - held : 0; };
     { const uint64_t add = grown(sam_win_need(n, 0)); if (add && !sort_room(b, add)) return sort_oom(b, "a window of SAM text", add); }
-    int rc = sam_lines(d, b->tmp, s, text, n, b->err);
+    rc = sam_lines(d, b->tmp, s, text, n, b->err);
     if (rc == GCE_ERR_OOM) return sort_oom(b, "a window of SAM text", 0);
     if (rc != GCE_OK) return rc;
     { const uint64_t add = grown(sam_win_need(n, d.nl)); if (add && !sort_room(b, add)) return sort_oom(b, "the lines of a window of SAM text", add); }
     rc = sam_sizes(d, b->tmp, s, b->err);
     if (rc == GCE_ERR_OOM) return sort_oom(b, "the lines of a window of SAM text", 0);
     if (rc != GCE_OK) return rc;
-    if (d.n_host) { const uint64_t add = (d.host_bytes + d.n_host * 8 + 64) * 9 / 8 + 512; if (add > d.hstage.cap + d.hsoff.cap && !sort_room(b, add)) return sort_oom(b, "the host's records of the lines with floating-point values", add); }
+    if (d.n_host) { const uint64_t add = sam_host_need(d); if (add > d.hstage.cap + d.hsoff.cap && !sort_room(b, add)) return sort_oom(b, "the host's records of the lines with floating-point values", add); }
     if (d.bad >= 0) { *bad_line = d.bad; *bad_start = d.bad_start; *parse_s += d.kernel_s - k0; return sfail(b, GCE_ERR_INVALID, sam_line_message(d, text, n, d.bad_start)); }
     const uint64_t n_rec = d.nl, add = d.total;
     if (n_rec) {
         const uint64_t n1 = b->n + n_rec;
         if (n1 >= SORT_MAX_RECORDS) return sfail(b, GCE_ERR_INVALID, "more than 2^32 - 16 records in one SAM file");
-        const uint64_t eb = std::max<uint64_t>(est_bytes, b->rec_n + add), en = (uint64_t)((double)n1 * ((double)eb / (double)(b->rec_n + add)));
-        if ((rc = sort_grow(b, b->rec, (size_t)(b->rec_n + add + 64), (size_t)b->rec_n, (size_t)(eb + eb / 16 + 64), "the resident record bytes")) != GCE_OK) return rc;
-        const size_t tn = (size_t)(en + en / 16 + 64);
-        if ((rc = sort_grow(b, b->key, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' keys")) != GCE_OK) return rc;
-        if ((rc = sort_grow(b, b->size, (size_t)n1 * 4, (size_t)b->n * 4, tn * 4, "the records' sizes")) != GCE_OK) return rc;
-        if ((rc = sort_grow(b, b->off, (size_t)n1 * 8, (size_t)b->n * 8, tn * 8, "the records' offsets")) != GCE_OK) return rc;
+        if ((rc = sort_take(b, n_rec, add, est_bytes)) != GCE_OK) return rc;
         uint8_t *dst = b->rec.as<uint8_t>() + b->rec_n;
         if ((rc = sam_emit(d, s, text, dst, b->err)) != GCE_OK) return rc;
         hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, (const uint8_t *)dst, (const uint64_t *)d.roff.p, (int64_t)n_rec, (uint64_t)0, b->rec_n, b->n, n_ref,
@@ -478,21 +473,16 @@ int gce_sort_pass_window(gce_sort *b, const void *comp, size_t comp_bytes, int32
     if (!b || !b->p_open || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
-    {   // (as gce_sort_window)
-        uint64_t u_all = b->w.carry_n; for (int32_t k = 0; k < n_members; k++) u_all += usize[k];
-        uint64_t add = 0;
-        if (u_all + 64 > b->w.win.cap) add += (u_all + 64) * 27 / 16 + 256;
-        if (comp_bytes + 64 > b->w.zc.cap) add += (comp_bytes + 64) * 9 / 8 + 256;
-        if (add && !sort_room(b, add)) return sort_oom(b, "a window of the file", add);
-    }
+    int rc = sort_win_check(b, comp_bytes, n_members, usize);
+    if (rc != GCE_OK) return rc;
     uint64_t total = 0, n_rec = 0, end = 0;
-    int rc = win_inflate_index(b->w, b->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, b->err);
+    rc = win_inflate_index(b->w, b->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, b->err);
     if (rc == GCE_ERR_OOM) return sort_oom(b, "a window of the file", 0);
     if (rc != GCE_OK) return rc;
     if (n_rec) {
         if (n_rec > b->n - b->p_g) return sfail(b, GCE_ERR_INVALID, "the input changed while it was being sorted (more records than the key pass saw)");
         const double t0 = mono_s();
-        hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)std::min<uint64_t>((n_rec + 15) / 16, 65535u)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.off.p, n_rec,
+        hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)std::min<uint64_t>((n_rec + 15) / 16, 65535u)), dim3(256), 0, s, (const uint8_t *)b->w.win.p, (const uint64_t *)b->w.idx.off.p, n_rec,
                            (const uint64_t *)b->dest.p, b->p_g, b->p_lo, b->p_hi, b->total, b->out.as<uint8_t>(), b->pmisc.as<unsigned long long>());
         SCHK(hipGetLastError()); SCHK(hipStreamSynchronize(s));
         b->p_scatter_s += mono_s() - t0;
@@ -538,14 +528,13 @@ int gce_sort_read(gce_sort *b, uint64_t offset, size_t bytes, int32_t codes, voi
     // (gce_sort_finish made the four buffers for the largest piece: nothing grows here, behind the caller's open output)
     if ((size_t)nb * slot + 64 > b->zs.cap || (size_t)nb * slot + 64 > b->zo.cap || ((size_t)nb + 1) * 4 > b->zz.cap || ((size_t)nb + 1) * 8 > b->zf.cap)
         return sfail(b, GCE_ERR_INVALID, "sort: a piece larger than gce_sort_finish was told");
-    def_launch(codes, nb, s, in, (uint64_t)bytes, 0xff00u, b->zs.as<uint8_t>(), slot, b->zz.as<uint32_t>());
-    SCHK(hipMemsetAsync((char *)b->zz.p + (size_t)nb * 4, 0, 4, s));
-    SCHK(dev_exclusive_sum(b->zz.as<uint32_t>(), (uint64_t)nb, b->zf.as<uint64_t>(), b->tmp, s));
     uint64_t csz = 0;
-    SCHK(hipMemcpyAsync(&csz, b->zf.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s));
+    const int rc = dev_deflate_members(codes, in, (uint64_t)bytes, 0xff00u, nb, b->zs.as<uint8_t>(), slot, b->zz.as<uint32_t>(), b->zf.as<uint64_t>(), b->tmp, s, &csz, b->err);
+    if (rc == GCE_ERR_OOM) return sort_oom(b, std::string(b->err, 0, b->err.rfind(": ")).c_str(), 0);   // (as SCHK: the call that ran out of memory)
+    if (rc != GCE_OK) return rc;
     if (csz > host_cap) return sfail(b, GCE_ERR_INVALID, "sort: a deflated piece is larger than its host buffer");
     if (csz + 64 > b->zo.cap) return sfail(b, GCE_ERR_INVALID, "sort: a deflated piece is larger than its device buffer");
-    hipLaunchKernelGGL(k_deflate_pack, dim3(std::min<uint32_t>((nb + 3) / 4, 16384u)), dim3(256), 0, s, (const uint8_t *)b->zs.p, slot, (const uint32_t *)b->zz.p, (const uint64_t *)b->zf.p, nb, b->zo.as<uint8_t>());
+    dev_deflate_pack((const uint8_t *)b->zs.p, slot, (const uint32_t *)b->zz.p, (const uint64_t *)b->zf.p, nb, b->zo.as<uint8_t>(), s);
     SCHK(hipMemcpyAsync(host, b->zo.p, csz, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
     *got = (size_t)csz;
     return GCE_OK;

@@ -1082,6 +1082,7 @@ static int gce_process_impl(gce_engine *e) {
         o.fr = e->o_fr.as<int16_t>(); o.rr = e->o_rr.as<int16_t>(); o.mate = e->o_mate.as<uint32_t>();
         o.seq_off = e->o_soff.as<uint64_t>(); o.qual_off = e->o_qoff.as<uint64_t>(); o.seq = e->o_seq.as<uint8_t>(); o.qual = e->o_qual.as<uint8_t>();
         o.key = e->o_key.as<OutKey>(); o.rec = e->o_rec.as<OutRec>(); o.ksoff = e->o_ksoff.as<uint64_t>(); o.kqoff = e->o_kqoff.as<uint64_t>(); o.krow = e->o_krow.as<uint32_t>(); o.rank64 = e->o_rank64.as<uint32_t>(); o.part3 = e->o_part3.as<uint64_t>();
+        if (e->h_si.n_raw > 0 && C > 0) hipLaunchKernelGGL(k_raw_emit, dim3(cdiv(C, 256)), dim3(256), 0, s, b, p, w, C);      // gencore.cpp:401-407 (malformed input only)
         hipLaunchKernelGGL(k_stats, dim3(1024), dim3(256), 0, s, b, w, (NG > 0 ? C : 0u), NG);     // Stats: clusters, groups  (round 5: on the second stream beside the output kernels it hid its 50 us and stretched k_out_reduce / k_out_partials by as much: not kept)
         CANARY("k_stats");
         hipLaunchKernelGGL(k_out_reduce, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o);

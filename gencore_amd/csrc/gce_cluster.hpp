@@ -45,12 +45,16 @@ struct __attribute__((aligned(8))) LeadOut { uint32_t h, rb; };     // bucket; f
 #define LO_OWNER 0x80000000u
 
 // thr_mode of an instance (see DESIGN.md "flush rule in closed form")
+// ikey: instance in bits 0..29 (exotic entries hold 29), IKEY_RAW = the key has left < 0, bit 31 = second segment.  A cluster with left < 0 that
+// no periodic walk takes is not clustered by UMI at finishConsensus: its pairs are written as they are (gencore.cpp:401-407) -> THR_RAW, k_raw_emit.
+#define IKEY_RAW (1u << 30)
 __device__ __forceinline__ uint32_t d_thr_mode(uint32_t ikey, const StreamInfo *si, const DevParams &p) {
-    uint32_t inst = ikey & 0x7FFFFFFFu, seg_b = ikey >> 31;
+    uint32_t inst = ikey & 0x3FFFFFFFu, seg_b = ikey >> 31;
     if (!seg_b) {
         if ((int)(inst + 1) <= si->n_events_a) return THR_PROPER;
-        if (si->first_unmapped != NONE32) return THR_UNPROPER;
-        return p.trailing_flush ? THR_PROPER : THR_UNPROPER;
+        if (si->first_unmapped != NONE32) return (ikey & IKEY_RAW) ? THR_RAW : THR_UNPROPER;
+        if (p.trailing_flush) return THR_PROPER;
+        return (ikey & IKEY_RAW) ? THR_RAW : THR_UNPROPER;
     }
     return ((int)(inst + 1) <= si->n_events) ? THR_PROPER : THR_NEVER;
 }
@@ -400,7 +404,7 @@ __global__ __launch_bounds__(256) void k_leaders(DevBatch b, DevParams p, Work w
             if (takes(w.ev_tid[mid], w.ev_pos[mid])) z = mid; else a = mid + 1;
         }
         const bool implied = e <= a;                                                        // (f = a + 1, 1-based: the instance every early read of the key gets)
-        const uint32_t ikey = (seg_b ? 0x80000000u : 0u) | (uint32_t)max(e, a);
+        const uint32_t ikey = (seg_b ? 0x80000000u : 0u) | (key.left < 0 ? IKEY_RAW : 0u) | (uint32_t)max(e, a);   // (left < 0 never packs: kw == 0, an exotic entry)
         const bool normal = fits && implied;
         bool owner = false, exotic = !normal, first_miss = true; uint32_t rbase = 0;
         auto next_probe = [&]() {
@@ -435,7 +439,7 @@ __global__ __launch_bounds__(256) void k_leaders(DevBatch b, DevParams p, Work w
         if (exotic) {
             // EXOTIC: instance + claiming read in the word, the count in the entry's second word (CAS, then a 64-bit add)
             const unsigned long long tk = d_exotic_key(ikey, idx);
-            if ((ikey & 0x7FFFFFFFu) >= (1u << 29)) raise_error(w.si, GCE_ERR_INVALID, idx);                // > 2^29 flush events
+            if ((ikey & 0x3FFFFFFFu) >= (1u << 29)) raise_error(w.si, GCE_ERR_INVALID, idx);                // > 2^29 flush events
             for (;;) {
                 const unsigned long long c = atomicCAS(&w.tab[h].key, 0ull, tk);
                 if (c == 0ull) { owner = true; break; }
@@ -445,6 +449,7 @@ __global__ __launch_bounds__(256) void k_leaders(DevBatch b, DevParams p, Work w
                 next_probe();
             }
             rbase = (uint32_t)atomicAdd(&w.tab[h].ic, (unsigned long long)in.r.runlen | (owner ? (unsigned long long)ikey << 32 : 0ull));
+            if (owner && (ikey & IKEY_RAW)) atomicAdd(&w.si->n_raw, 1u);
         }
         LeadOut o; o.h = (uint32_t)h; o.rb = rbase | (owner ? LO_OWNER : 0u);
         w.lout[LR] = o;

@@ -419,7 +419,7 @@ __global__ __launch_bounds__(PD_T) void k_pairing_deep(DevBatch b, DevParams p, 
         __syncthreads();
         if (!take || s_flag) { if (!BIG && tid == 0) w.left_list[atomicAdd(&w.si->n_slow_pair2, 1u)] = c; continue; }      // (BIG: the entry stays for the generic kernels)
         const uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
-        if (mode == THR_NEVER) { if (tid == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; if (BIG) w.left_list[li] = NONE32; } continue; }
+        if (mode >= THR_NEVER) { if (tid == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; if (BIG) w.left_list[li] = NONE32; } continue; }
 #ifdef VB_PROF
         unsigned long long pd_prev_ = wall_clock64();
         if (threadIdx.x == 0) atomicAdd(&w.si->prof[30], 1ull);

@@ -10,7 +10,7 @@
 #define EMPTY64 0xFFFFFFFFFFFFFFFFull
 
 // thr_mode of a cluster instance (quirks Q1/Q2)
-enum : uint32_t { THR_PROPER = 0, THR_UNPROPER = 1, THR_NEVER = 2 };
+enum : uint32_t { THR_PROPER = 0, THR_UNPROPER = 1, THR_NEVER = 2, THR_RAW = 3 };   // (>= THR_NEVER: no pairing tier works on the cluster)
 // the pairing tier that paired a cluster (Work.cl_tier; the values of GCE_PAIR_TIER_* in include/gencore_amd.h)
 enum : uint8_t { TIER_NEVER = 0, TIER_SUB16 = 1, TIER_SUB32 = 2, TIER_FAST = 3, TIER_DEEP_LDS = 4, TIER_DEEP_DEVICE = 5, TIER_GENERIC = 6 };
 // read class
@@ -83,6 +83,7 @@ struct StreamInfo {
     unsigned long long n_p16_items;      // clusters of <= 16 reads: the quarter-wave pairing kernel's list
     unsigned long long vote_rounds2;     // k_vote: vote rounds behind a batch's first (one atomic per extra round, thread 0) -- gce_get_vote_counters
     unsigned long long vote_rounds2_unaligned;   // ... of those: rounds whose first side s0 is not a multiple of 4 (vb_find_wave's groups do not start at s0)
+    unsigned int n_raw;                  // clusters with left < 0 (k_leaders): finishConsensus writes their pairs as they are (k_raw_emit runs only when there are some)
     unsigned int cs_fast, cs_prep, cs_deep, cs_slow;   // group sides FINISHED by k_consensus_fast / k_deep_prepare (no template) / k_vote_deep / k_consensus_slow -- gce_get_consensus_counters
     long long pre[GCE_STATS_WORDS];
     long long post[GCE_STATS_WORDS];

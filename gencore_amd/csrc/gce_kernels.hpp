@@ -137,7 +137,7 @@ template <int PHASE>
 __device__ void pairing_generic(const DevBatch &b, const DevParams &p, const Work &w, uint32_t c, int lane, uint32_t ib0 = 0, uint32_t ibstep = 1) {
     const uint32_t start = w.cl_start[c], n = w.cl_n[c];
     uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
-    if (mode == THR_NEVER) {                      // pending after an early finishConsensus: never processed (gencore.cpp:23)
+    if (mode >= THR_NEVER) {                      // pending after an early finishConsensus: never processed (gencore.cpp:23); THR_RAW: k_raw_emit's
         if (PHASE == 2 && lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; }
         return;
     }
@@ -335,7 +335,7 @@ __device__ __forceinline__ int popc_nonzero_bytes(uint64_t x) {
 __device__ void pairing_fast_cluster(const DevBatch &b, const DevParams &p, const Work &w, uint32_t c, int lane) {
     const uint32_t start = w.cl_start[c], n = w.cl_n[c];
     uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
-    if (mode == THR_NEVER) { if (lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; } return; }
+    if (mode >= THR_NEVER) { if (lane == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; } return; }
     const int thr = mode == THR_PROPER ? p.proper_thr : p.unproper_thr;
     bool defer = n > 64;
     uint32_t my = NONE32; int nl = 0; const char *nm = nullptr; int ul = 0; uint64_t ui_ = 0;
@@ -1942,6 +1942,42 @@ __global__ __launch_bounds__(256) void k_finish(DevBatch b, DevParams p, Work w,
     for (uint32_t k = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6); k < n; k += gridDim.x * WAVES_PER_BLOCK) {
         finish_cluster(b, p, w, list[k], lane);
         WAVE_SYNC();
+    }
+}
+
+// ===================================================================================================== clusters written as they are
+// finishConsensus on a cluster with left < 0 (gencore.cpp:401-407): every Pair of the name map goes to outputPair as Cluster::addRead built it
+// (cluster.cpp:260-273: the first read of a name is the left one, every later one replaces the right one -- Pair::setRight checks its UMI,
+// pair.cpp:195-216), without clusterByUMI: no group, no consensus, no tag, no Stats but outputPair's addMolecule(1, PE).  Such keys need a
+// malformed mate position (mpos == -1 on the read's own contig); one thread per cluster, launched only when k_leaders met one.
+__global__ __launch_bounds__(256) void k_raw_emit(DevBatch b, DevParams p, Work w, uint32_t n_clusters) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_clusters || d_thr_mode(w.cl_ikey[c], w.si, p) != THR_RAW) return;
+    const uint32_t start = w.cl_start[c], n = w.cl_n[c];
+    auto same = [&](const char *x, const char *y) { int k = 0; while (x[k] && x[k] == y[k]) k++; return x[k] == y[k]; };
+    for (uint32_t a = 0; a < n; a++) {
+        const uint32_t ra = w.members[start + a];
+        const char *qa = d_qname(b, ra);
+        bool first = true;
+        for (uint32_t x = 0; x < n && first; x++) { const uint32_t rx = w.members[start + x]; if (rx < ra && same(qa, d_qname(b, rx))) first = false; }
+        if (!first) continue;
+        uint32_t right = NONE32, prev = ra; uint64_t pu = w.uinfo[ra];
+        for (;;) {                                                                       // the name's later reads in arrival order
+            uint32_t nx = NONE32;
+            for (uint32_t x = 0; x < n; x++) { const uint32_t rx = w.members[start + x]; if (rx > prev && rx < nx && same(qa, d_qname(b, rx))) nx = rx; }
+            if (nx == NONE32) break;
+            const uint64_t u = w.uinfo[nx];
+            const int ul = uinfo_len(u), pl = uinfo_len(pu);
+            bool eq = ul == pl;
+            if (eq) { const char *s1 = uinfo_ptr(b, u), *s2 = uinfo_ptr(b, pu); for (int k = 0; k < ul; k++) eq = eq && s1[k] == s2[k]; }
+            if (pl != 0 && !eq) raise_error(w.si, GCE_ERR_UMI_MISMATCH, nx); else pu = u;
+            right = nx; prev = nx;
+        }
+        OutRec o; o.nm_new = -1; o.fr = -1; o.rr = -1; o.pad = 0;
+        w.out_flag[ra] = 1; o.qname_src = ra; o.mate = right; w.orec[ra] = o;
+        if (right != NONE32) { w.out_flag[right] = 1; o.qname_src = right; o.mate = ra; w.orec[right] = o; }
+        atomicAdd((unsigned long long *)&w.si->post[8], 1ull); atomicAdd((unsigned long long *)&w.si->post[14 + 1], 1ull);
+        atomicAdd((unsigned long long *)&w.si->post[right != NONE32 ? 10 : 9], 1ull);
     }
 }
 

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void k_pairing_sub(DevBatch b, DevParams p, Wo
     if (live) {
         start = w.cl_start[c]; n = w.cl_n[c];
         const uint32_t mode = d_thr_mode(w.cl_ikey[c], w.si, p);
-        if (mode == THR_NEVER) { if (hl == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; } live = false; }   // gencore.cpp:23
+        if (mode >= THR_NEVER) { if (hl == 0) { w.cl_npairs[c] = 0; w.cl_ngroups[c] = 0; w.cl_hasumi[c] = 0; w.cl_tier[c] = TIER_NEVER; } live = false; }   // gencore.cpp:23
         thr = mode == THR_PROPER ? p.proper_thr : p.unproper_thr;
     }
     uint32_t my = NONE32; int nl = 0; const char *nm = nullptr; int ul = 0;

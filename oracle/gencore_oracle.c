@@ -810,6 +810,22 @@ static void cluster_by_umi(Ctx *c, OCluster *cl, int umi_diff_threshold, int cro
     free(single);
 }
 
+/* The pairs of a cluster as Cluster::addRead built them (cluster.cpp:260-273), handed to outputPair one by one     gencore.cpp:402-407 */
+static void emit_pairs_as_they_are(Ctx *c, OCluster *cl) {
+    g_sort_ctx = c;
+    qsort(cl->reads, (size_t)cl->n, sizeof(uint32_t), cmp_read_qname);
+    for (int i = 0; i < cl->n && !c->failed;) {
+        int j = i + 1;
+        while (j < cl->n && strcmp(qname_of(c, cl->reads[i]), qname_of(c, cl->reads[j])) == 0) j++;
+        OPair p; memset(&p, 0, sizeof p);
+        p.left = p.right = NONE; p.merge_reads = 1;
+        pair_set_left(c, &p, cl->reads[i]);
+        for (int k = i + 1; k < j; k++) pair_set_right(c, &p, cl->reads[k]);
+        if (!c->failed) output_pair(c, &p);
+        i = j;
+    }
+}
+
 /* ----------------------------------------------------------------------------------------- stream driver */
 
 static uint64_t key_hash(int32_t tid, int32_t left, int64_t right) {
@@ -893,12 +909,16 @@ static void periodic_flush(Ctx *c, int32_t tid, int32_t pos) {
 }
 
 /* Gencore::finishConsensus                                                            gencore.cpp:392-434 */
-static void finish_consensus(Ctx *c, int umi_diff_threshold) {
+static void finish_consensus(Ctx *c, int umi_diff_threshold, int as_periodic) {
     qsort(c->pending, (size_t)c->n_pending, sizeof(OCluster *), cmp_cluster_key);
     for (int64_t i = 0; i < c->n_pending; i++) {
         OCluster *cl = c->pending[i];
-        /* tid < 0 || left < 0 clusters ("unmapped", :401-407) cannot exist: such reads never reach addToCluster */
-        cluster_by_umi(c, cl, umi_diff_threshold, cl->right < 0);                          /* :409, threshold quirk Q1 */
+        /* :401-407 "for unmapped reads, we just store them": tid < 0 cannot exist (such reads never reach addToCluster), left < 0 can -- a read
+         * with mtid == tid, mpos == -1 and isize < 0 has left = mpos (:300-303).  Its pairs are written as they are, in the order of the name map,
+         * without clusterByUMI: no grouping, no consensus, no tag, no Stats but outputPair's own.  The periodic walk knows no such exception (:355),
+         * and a trailing flush stands for a later slice's periodic walk. */
+        if (cl->left < 0 && !as_periodic) emit_pairs_as_they_are(c, cl);
+        else cluster_by_umi(c, cl, umi_diff_threshold, cl->right < 0);                     /* :409, threshold quirk Q1 */
         cluster_free(cl);
     }
     c->n_pending = 0;
@@ -975,7 +995,7 @@ int orc_run_shard(const gce_params *prm, const orc_reference *ref, gce_batch *ba
         last_tid = k->tid; last_pos = k->pos;
         if (k->tid < 0 || k->pos < 0) {                     /* :255-266: unmapped reads are dropped */
             if (!out_set_cleared) {
-                if (!finished) { finished = 1; finish_consensus(&ctx, prm->unproper_umi_diff_threshold); }
+                if (!finished) { finished = 1; finish_consensus(&ctx, prm->unproper_umi_diff_threshold, 0); }
                 out_set_cleared = 1;
             }
             continue;
@@ -987,7 +1007,7 @@ int orc_run_shard(const gce_params *prm, const orc_reference *ref, gce_batch *ba
         /* :276-279.  In a coordinate-sharded run a flush event of a LATER slice (larger tid) would have drained
          * everything pending here through the periodic path, i.e. with -d instead of the end-of-file threshold. */
         while (!finished && ctx.next_ev < ctx.n_ev) { periodic_flush(&ctx, ctx.ev_tid[ctx.next_ev], ctx.ev_pos[ctx.next_ev]); ctx.next_ev++; }   /* later shards' events */
-        if (!finished) { finished = 1; finish_consensus(&ctx, (prm->trailing_flush && !batch->tick) ? prm->proper_umi_diff_threshold : prm->unproper_umi_diff_threshold); }
+        if (!finished) { const int tf = prm->trailing_flush && !batch->tick; finished = 1; finish_consensus(&ctx, tf ? prm->proper_umi_diff_threshold : prm->unproper_umi_diff_threshold, tf); }
     }
     /* clusters still pending after an earlier finish are never processed (released in ~Gencore, gencore.cpp:23) */
     for (int64_t i = 0; i < ctx.n_pending; i++) cluster_free(ctx.pending[i]);

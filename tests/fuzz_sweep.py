@@ -1,5 +1,6 @@
 """Fuzz sweep: tests/fuzzgen.py cases over a range of seeds the test-suite does not hold, engine vs oracle (every record, both
-Stats blocks, order, error status).  Run on the GPU box:  python tests/fuzz_sweep.py [first_seed] [count] [n_mol] [summary.json]
+Stats blocks, order, error status).  Run on the GPU box:  python tests/fuzz_sweep.py [first_seed] [count] [n_mol] [summary.json] [--blocks K]
+--blocks K draws n_mol large enough for K or more scan blocks of cluster formation (1024 reads each; a molecule is ~7 reads): streams that leave one block.
 The summary (seed range, streams, reads, records, error-path streams, mismatches with their seeds) is the artefact that goes to profiles/."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,10 +11,15 @@ from gencore_amd.capi import GceError
 from gencore_amd.engine import run_stream
 from oracle import oracle_py
 
+blocks = 0
+if "--blocks" in sys.argv:
+    k_ = sys.argv.index("--blocks"); blocks = int(sys.argv[k_ + 1]); del sys.argv[k_:k_ + 2]
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 300
 n_mol = int(sys.argv[3]) if len(sys.argv) > 3 else 60
 summary_path = sys.argv[4] if len(sys.argv) > 4 else None
+if blocks:
+    n_mol = max(n_mol, -(-blocks * 1024 // 6))               # 6 reads per molecule at the least (276 reads at n_mol = 40, 4210 at 600)
 bad, bad_seeds, n_reads, n_rec, n_err, modes, t0 = 0, [], 0, 0, 0, {}, time.time()
 for seed in range(first, first + count):
     kw = dict(n_mol=n_mol + seed % 40, exotic=seed % 3 == 0)

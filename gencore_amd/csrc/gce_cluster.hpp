@@ -375,7 +375,8 @@ __global__ __launch_bounds__(256) void k_leaders(DevBatch b, DevParams p, Work w
         const int j0 = min(max(g - 1, 0), ev_last), j1 = min(g, ev_last), j2 = min(g + 1, ev_last);
         const int T0 = w.ev_tid[j0], P0 = w.ev_pos[j0], T1 = w.ev_tid[j1], P1 = w.ev_pos[j1], T2 = w.ev_tid[j2], P2 = w.ev_pos[j2];
         // NORMAL clusters (implied instance, first segment, key inside the header's contigs): the bucket word in the cluster's HOME
-        // bucket identifies it by itself.  x = genome-linear left * 8 + way(right) is injective in (tid, left) up to the way, home = x mod T,
+        // bucket identifies it by itself.  x = genome-linear left * 8 + way(right) is injective in (tid, left) up to the way AS LONG AS left lies inside its
+        // contig (a read that starts behind its contig's declared end has the next contig's x: such keys go the exotic way), home = x mod T,
         // so (x div T, right - left + 1) is all that is left of the key: word = OCC | x div T | delta1 | reads so far (field widths from the
         // stream's size, DevParams.nw_*).  ONE read-modify-write per leader run: a CAS from 0 claims the bucket, a CAS from (word) to
         // (word + run length) joins it and returns the run's first rank in the same trip; no second word, no look at anybody's record.
@@ -386,7 +387,7 @@ __global__ __launch_bounds__(256) void k_leaders(DevBatch b, DevParams p, Work w
         const int cb = p.nw_cb, bd = p.nw_bd;
         const long long delta1 = key.right - (long long)key.left + 1;
         bool fits = false; uint64_t h = 0; unsigned long long id_w = 0, cur = 0;
-        if (p.nw_ok && in.r.kw != 0ull && !seg_b && key.tid < p.n_targets) {
+        if (p.nw_ok && in.r.kw != 0ull && !seg_b && key.tid < p.n_targets && (uint32_t)key.left < p.target_len[key.tid]) {
             uint64_t q;
             d_divmod(d_tab_index(key, 0u, p), w.tsize, w.tinv, q, h);
             fits = (q >> (62 - cb - bd)) == 0 && ((uint64_t)delta1 >> bd) == 0;

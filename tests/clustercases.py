@@ -552,6 +552,24 @@ def _negative_left_pending(name, unmapped_at=None, trailing=0):
     return c
 
 
+def _nopack_behind_contig_end():
+    """Clusters that start behind the declared end of their contig: contig 0 has 250 bases and clusters at 100..399, contig 1 has none and clusters at 0..149, contig 2
+    clusters at 0..149 inside it.  In genome-linear coordinates (the sum of the contig lengths in front + left) the clusters of contig 0 from 250 on, those of contig
+    1 and those of contig 2 lie on the SAME 150 places with the same right - left: an identity made of the linear place and the span alone would count three
+    clusters as one."""
+    contigs = (250, 0, 1000, 1 << 20)
+    b = build([dense(1200, 0, 100), dense(600, 5000, 0, tid=1), dense(600, 6000, 0, tid=2), dense(800, 7000, 100, tid=3)])
+    cm, left, right = keys_of(b.core, contigs)
+    tid = b.core["tid"].astype(np.int64)
+    lin = np.concatenate([[0], np.cumsum(contigs)])[tid] + left
+    keys = np.unique(np.stack([tid, left, right - left, lin], axis=1)[cm], axis=0)
+    places, cnt = np.unique(keys[:, 2:], axis=0, return_counts=True)
+    behind = cm & (left >= np.asarray(contigs, np.int64)[tid])
+    return _case("nopack:behind_contig_end", b, 50, dict(behind_the_end=int(behind.sum()) == 600 + 600, three_keys_on_one_place=int((cnt == 3).sum()) == 150,
+                                                         four_blocks=-(-b.n // SB) == 4), contig_len=contigs)
+
+
+_register("nopack:behind_contig_end", _nopack_behind_contig_end)
 _register("nopack:negative_left_pending", functools.partial(_negative_left_pending, "nopack:negative_left_pending"))
 _register("nopack:negative_left_pending_unmapped", functools.partial(_negative_left_pending, "nopack:negative_left_pending_unmapped", 2300))
 _register("nopack:negative_left_pending_trailing", functools.partial(_negative_left_pending, "nopack:negative_left_pending_trailing", None, 1))

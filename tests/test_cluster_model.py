@@ -63,6 +63,7 @@ FROZEN = {
     "nopack:beyond_contig": "a5845338f49bb3df",
     "nopack:negative_left": "13bc98b76f417a3e",
     "nopack:tid_beyond_header": "0afdcab22d2412e2",
+    "nopack:behind_contig_end": "1c66cc1562eeb5db",
     "nopack:no_contigs_events": "cca66e707424cdc9",
     "nopack:no_contigs_odd": "2d3cb586ef69267a",
     "delta1:overflow": "e5c4b48358f80bfe",

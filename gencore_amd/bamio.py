@@ -186,6 +186,36 @@ def sort_bam(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_bud
     return {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in GceSortRun._fields_ if n != "pad"}
 
 
+class CalmdRun:
+    """gce_calmd_run as an object: one attribute per field (counters and bytes as int, times as float)."""
+
+    def __init__(self, r):
+        for n, t in type(r)._fields_:
+            if n != "pad":
+                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+
+    def as_dict(self):
+        return dict(vars(self))
+
+
+def calmd_bam(in_path, out_path, fasta, device=0, threads=0, level=6, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_calmd: NM and MD of every record of a BAM file recomputed against `fasta` on the GPU (what `samtools calmd` does behind the
+    reference, whose consensus records keep one read's MD), written to `out_path`; records the rules leave alone (unmapped, no CIGAR, a contig
+    the FASTA lacks, ...) and the header are copied byte for byte, in the input's order.  level as run_bam; window_bytes: compressed bytes per
+    window, 0 = 64 MB; device_budget_bytes: 0 = no limit beyond the device (the pass is in-core).  Returns a CalmdRun (n_records, n_rewritten,
+    n_unchanged, n_no_ref, n_nm_changed, n_md_changed, inflated_bytes, out_record_bytes, out_bytes, peak_device_bytes, n_ref, read_s,
+    inflate_index_s, calmd_s, write_s, total_s); raises GceError with the library's message (and leaves no output) on failure."""
+    from .capi import GceCalmdRun
+    lib = capi.load_library()
+    r = GceCalmdRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_calmd(str(in_path).encode(), str(out_path).encode(), str(fasta).encode(), int(device), int(threads), int(level), int(window_bytes), int(device_budget_bytes),
+                           C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    return CalmdRun(r)
+
+
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):
     """gce_sam_sort: SAM text in any order into the coordinate-sorted BAM on the GPU, the file sam_to_bam + sort_bam write, without the BAM in
     between: the GPU turns the alignment lines into records (parse_sam) and sorts them.  window_bytes: text bytes per window, 0 = 64 MB, a value above 1 GB

@@ -19,6 +19,12 @@ Flags marked [gencore_amd] are not the reference's; every other flag, default an
 file that does not fit is sorted in output-range passes over the input.
 --sort_sam (not the reference's) takes SAM text in any order, an aligner's output as it is: the GPU turns its lines into BAM records and sorts
 them into the temporary BAM that --sort would make, without a BAM written in between.  In-core only, within --device_memory.
+--calmd (not the reference's) makes NM and MD of the BAM output true: a consensus record takes its optional fields from one read of its cluster,
+so its MD:Z describes that read and not the voted bases, and its NM is patched only where it was stored as type C.  After the output and the
+report are written the GPU recomputes both against -r (what `samtools calmd` does behind the reference) and the result replaces the output.
+The report is not changed by it.
+--calmd_in (not the reference's) recomputes NM and MD of the input BAM the same way first, into a temporary BAM: an input whose records lack NM
+stops the run with GCE_ERR_NM_MISSING otherwise.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -85,6 +91,12 @@ def build_parser():
                                            "temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
     a("--sort_sam", action="store_true", help="[gencore_amd] the input is SAM text that is not coordinate-sorted: parse and sort it on the GPU first (on the first of "
                                                "--devices, into a temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
+    a("--calmd", action="store_true", help="[gencore_amd] after the output and the report are written (and before --index), recompute NM and MD of every record of "
+                                            "the BAM output against -r on the GPU (on the first of --devices, at --level, within --device_memory), through a temporary file beside "
+                                            "the output that is renamed over it. The report is not changed by it. Off by default.")
+    a("--calmd_in", action="store_true", help="[gencore_amd] recompute NM and MD of the input BAM against -r on the GPU first (after --sort / --sort_sam; on the first of --devices, "
+                                               "into a temporary BAM beside the output that is removed afterwards), then run on that file: an input without NM "
+                                               "becomes runnable. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -111,7 +123,13 @@ def validate(o):
         err("--sort needs an input file, not STDIN")
     if o.sort_sam and not o.sort and o.input == "-":
         err("--sort_sam needs an input file, not STDIN")
+    if o.calmd_in and o.input == "-":
+        err("--calmd_in needs an input file, not STDIN")
     check_file_valid(o.input)
+    if o.calmd_in and not o.sort_sam:
+        with open(o.input, "rb") as f:
+            if f.read(2) != b"\x1f\x8b":
+                err("--calmd_in needs BAM input, not SAM text")
     if o.sort:
         with open(o.input, "rb") as f:
             if f.read(2) != b"\x1f\x8b":
@@ -169,6 +187,10 @@ def validate(o):
         err("--index needs an output file, not STDOUT")
     if o.index and o.output.endswith("sam"):
         err("--index needs BAM output, not SAM text")
+    if o.calmd and o.output == "-":
+        err("--calmd needs an output file, not STDOUT")
+    if o.calmd and o.output.endswith("sam"):
+        err("--calmd needs BAM output, not SAM text")
     return devices
 
 
@@ -192,10 +214,11 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam
+    from .bamio import calmd_bam, index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam
     from .capi import GceError
     from .report import read_header, summary, write_json
-    sorted_tmp = None
+    sorted_tmp = calmd_tmp = out_tmp = None
+    tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged
             import tempfile
@@ -204,6 +227,12 @@ def main(argv=None):
             sorter = sort_bam_passes if o.sort else sort_sam               # (--sort_sam: the same file, made from text; in-core only)
             sorter(o.input, sorted_tmp, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
             o.input = sorted_tmp
+        if o.calmd_in:                                                      # as --sort: the runners read the temporary file
+            import tempfile
+            fd, calmd_tmp = tempfile.mkstemp(suffix=".bam", prefix="gencore_calmd_", dir=tmp_dir)
+            os.close(fd)
+            calmd_bam(o.input, calmd_tmp, o.ref, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
+            o.input = calmd_tmp
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
@@ -217,14 +246,21 @@ def main(argv=None):
                          "\n----After gencore processing:\n" + summary(depth["post"], True))
         sys.stderr.flush()
         write_json(o.json, depth, names, o.coverage_sampling, command, region_names=region_names, has_bed=bool(o.bed))
+        if o.calmd:
+            out_tmp = o.output + ".calmd%d" % os.getpid()
+            r = calmd_bam(o.output, out_tmp, o.ref, device=devices[0], threads=o.threads, level=o.level, device_budget_bytes=o.device_memory_bytes)
+            os.replace(out_tmp, o.output)
+            sys.stderr.write("calmd: %d records rewritten, NM changed in %d, MD changed in %d\n" % (r.n_rewritten, r.n_nm_changed, r.n_md_changed))
         if o.index:
             index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:
-        print("ERROR: %s" % e, file=sys.stderr)
+        hint = "; --calmd_in recomputes the input's NM (and MD) against -r on the GPU first" if getattr(e, "status", 0) == -12 and not o.calmd_in else ""
+        print("ERROR: %s%s" % (e, hint), file=sys.stderr)
         return 255
     finally:
-        if sorted_tmp is not None and os.path.exists(sorted_tmp):
-            os.remove(sorted_tmp)
+        for tmp in (sorted_tmp, calmd_tmp, out_tmp):
+            if tmp is not None and os.path.exists(tmp):
+                os.remove(tmp)
     t2 = int(time.time())
     sys.stderr.write("\n%s\ngencore_amd v%s, time used: %d seconds\n" % (command, __version__, t2 - t1))
     return 0

@@ -1997,6 +1997,7 @@ struct SortJob {
     gce_sort *b = nullptr; PassWriter pw; Pinned hb;
     int T = 1, level = 0; int32_t device = 0, codes = -1, n_ref = 0; uint64_t window_bytes = 0, hdr_end = 0, piece = 0;
     std::vector<uint8_t> hdr;
+    const char *who = "gce_bam_sort"; bool keep_header = false; std::vector<std::string> names;   // gce_bam_calmd: the header byte for byte, its contig names kept
     int fail(int code, const std::string &m) { msg = m; return code; }
     // everything is let go; a failed call leaves no output
     void close_all(int code) {
@@ -2018,14 +2019,14 @@ struct SortJob {
             char *ri = realpath(in_path, nullptr), *ro = realpath(out_path, nullptr);
             if (ri && ro && strcmp(ri, ro) == 0) same = true;
             free(ri); free(ro);
-            if (same) return fail(GCE_ERR_INVALID, std::string("the output path is the input file: ") + who + " does not sort in place");
+            if (same) return fail(GCE_ERR_INVALID, std::string("the output path is the input file: ") + who + (keep_header ? " does not rewrite a file in place" : " does not sort in place"));
         }
         return GCE_OK;
     }
     int open_input(const char *in_path, const char *out_path, int threads, int lv, uint64_t wb, int32_t dev) {
         level = lv; window_bytes = wb; device = dev;
-        { const int rc = open_paths(in_path, out_path, "gce_bam_sort", "BAM"); if (rc != GCE_OK) return rc; }
-        if (fsz > 0 && !(fsz >= 4 && looks_gzip(fd, fsz))) return fail(GCE_ERR_INVALID, "gce_bam_sort reads BAM, not SAM text");
+        { const int rc = open_paths(in_path, out_path, who, "BAM"); if (rc != GCE_OK) return rc; }
+        if (fsz > 0 && !(fsz >= 4 && looks_gzip(fd, fsz))) return fail(GCE_ERR_INVALID, std::string(who) + " reads BAM, not SAM text");
         if (!starts_bgzf(fd, fsz)) return fail(GCE_ERR_INVALID, "not a BGZF file");
         T = threads > 0 ? threads : default_threads();
         // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
@@ -2035,10 +2036,11 @@ struct SortJob {
             if (g < 0) return fail(GCE_ERR_INVALID, rh.msg);
             const uint8_t *u = rh.win.p;
             BamHeader bh;
-            const Hdr hs = parse_bam_header(u, rh.n, Contigs::Skip, bh);
+            const Hdr hs = parse_bam_header(u, rh.n, Contigs::Skip, bh, keep_header ? &names : nullptr);
             if (hs == Hdr::NotBam) return fail(GCE_ERR_INVALID, "not a BAM stream");
             if (hs == Hdr::Complete) {                                               // rule H: the text rewritten, the contig table as it is
                 hdr_end = bh.hdr_end; n_ref = (int32_t)bh.n_ref;
+                if (keep_header) { hdr.assign(u, u + bh.hdr_end); return GCE_OK; }
                 const std::string text = sort_header_text(u + bh.text_off, bh.l_text);
                 const uint32_t lt = (uint32_t)text.size();
                 hdr.assign(u, u + 4); hdr.insert(hdr.end(), (const uint8_t *)&lt, (const uint8_t *)&lt + 4);
@@ -2307,6 +2309,66 @@ int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t devic
     t0 = now_s();
     if ((rc = j.end_output(out_path, &out->out_bytes)) != GCE_OK) return done(rc);
     out->write_s += now_s() - t0;
+    { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); out->peak_device_bytes = pk; }
+    out->total_s = now_s() - t_start;
+    return done(GCE_OK);
+}
+
+// ---- NM and MD recomputed against the reference (gce_calmd.hpp)
+int gce_sort_calmd_ref(gce_sort *b, int32_t n_ref, const char *const *seq, const int64_t *len);
+int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                          int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s);
+int gce_sort_calmd_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int64_t counts[6], uint64_t *in_bytes, uint64_t *out_bytes);
+
+int gce_bam_calmd(const char *in_path, const char *out_path, const char *fasta_path, int32_t device, int threads, int level, uint64_t window_bytes, size_t device_budget_bytes,
+                  gce_calmd_run *out, char err[256]) {
+    set_err(err, "");
+    if (!in_path || !out_path || !fasta_path || !out) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
+    memset(out, 0, sizeof *out);
+    if (level < -3 || level > 9) { set_err(err, "level should be -3, -2, -1 or 0..9"); return GCE_ERR_INVALID; }
+    { struct stat sf; if (stat(fasta_path, &sf) != 0 || S_ISDIR(sf.st_mode)) { set_err(err, "cannot open the reference FASTA"); return GCE_ERR_INVALID; } }
+    const double t_start = now_s();
+    SortJob j; j.who = "gce_bam_calmd"; j.keep_header = true;
+    gce_fasta *fa = nullptr;
+    auto done = [&](int code) { j.close_all(code); if (fa) gce_fasta_free(fa); set_err(err, j.msg.c_str()); return code; };
+    int rc = j.open_input(in_path, out_path, threads, level, window_bytes, device);
+    if (rc != GCE_OK) return done(rc);
+    const int32_t n_ref = j.n_ref;
+    out->n_ref = n_ref;
+    // ---- rule R: the contigs by the header's names
+    double t0 = now_s();
+    if ((rc = gce_fasta_load(fasta_path, j.T, &fa)) != GCE_OK) return done(j.fail(rc, "cannot read the reference FASTA"));
+    std::vector<const char *> seq((size_t)n_ref, nullptr); std::vector<int64_t> len((size_t)n_ref, -1);
+    {
+        int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr;
+        gce_fasta_get(fa, &nc, &ids, &seqs, &flen);
+        std::unordered_map<std::string, int32_t> where;
+        for (int32_t c = 0; c < nc; c++) where.emplace(ids[c], c);
+        for (int32_t t = 0; t < n_ref; t++) {
+            auto it = where.find(j.names[(size_t)t].c_str());                          // (the name up to its first NUL)
+            if (it != where.end()) { seq[(size_t)t] = seqs[it->second]; len[(size_t)t] = flen[it->second]; }
+        }
+    }
+    out->read_s += now_s() - t0;
+    (void)gce_device_bytes(nullptr, nullptr, 1);
+    if ((rc = gce_sort_create(device, device_budget_bytes, &j.b)) != GCE_OK) return done(j.fail(rc, "no HIP device"));
+    if ((rc = gce_sort_calmd_ref(j.b, n_ref, seq.data(), len.data())) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+    gce_fasta_free(fa); fa = nullptr;
+    // ---- the file from its first byte, window by window: the GPU inflates, indexes and rewrites the records behind the resident output
+    rc = j.stream(&out->read_s, &out->inflate_index_s, [&](PassReader &rd, uint64_t sk, uint64_t est) {
+        return gce_sort_calmd_window(j.b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0, est,
+                                     &out->calmd_s); });
+    if (rc != GCE_OK) return done(rc);
+    out->inflate_index_s -= out->calmd_s;
+    j.set_pieces();
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0}; uint64_t in_bytes = 0, total = 0;
+    if ((rc = gce_sort_calmd_finish(j.b, j.codes, j.piece, counts, &in_bytes, &total)) != GCE_OK) return done(j.fail(rc, gce_sort_error(j.b)));
+    out->n_records = counts[0]; out->n_rewritten = counts[1]; out->n_unchanged = counts[2]; out->n_no_ref = counts[3]; out->n_nm_changed = counts[4]; out->n_md_changed = counts[5];
+    out->inflated_bytes = (int64_t)in_bytes; out->out_record_bytes = (int64_t)total;
+    // ---- rule F
+    t0 = now_s();
+    if ((rc = j.begin_output(total)) != GCE_OK || (rc = j.write_range(total)) != GCE_OK || (rc = j.end_output(out_path, &out->out_bytes)) != GCE_OK) return done(rc);
+    out->write_s = now_s() - t0;
     { int64_t pk = 0; (void)gce_device_bytes(nullptr, &pk, 0); out->peak_device_bytes = pk; }
     out->total_s = now_s() - t_start;
     return done(GCE_OK);

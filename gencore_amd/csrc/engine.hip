@@ -1359,3 +1359,4 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_samfmt.hpp"
 #undef MCHK
 #include "gce_sort.hpp"
+#include "gce_calmd.hpp"

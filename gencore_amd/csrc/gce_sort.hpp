@@ -23,6 +23,7 @@
 //                   summed, so that a pass whose records do not tile its range (the input changed) is refused
 // and gce_sort_read hands the pass buffer out as it hands out the in-core stream.  tests/pysort.py models the rules.
 #pragma once
+#include "gce_copy16.hpp"                                                           // sort_copy16: the 16-lane copy k_sort_gather and k_sort_scatter use
 
 namespace {
 
@@ -70,22 +71,6 @@ __global__ __launch_bounds__(256) void k_sort_iota(uint32_t *idx, uint64_t n) {
 __global__ __launch_bounds__(256) void k_sort_sizes(const uint32_t *size, const uint32_t *sidx, uint64_t n, uint32_t *ssize) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) ssize[j] = size[sidx[j]];
-}
-// the copy of one record (or of a stretch of one) by its 16 lanes: sz bytes from s to d.  The stores are 16 bytes wide and aligned on the
-// destination: head = the bytes in front of the first 16-byte boundary (one byte per lane), then whole chunks (each lane reads its 16 source
-// bytes unaligned), then the bytes behind the last boundary (one byte per lane).  Every read stays inside [s, s + sz) and every write inside
-// [d, d + sz), for any size and any pair of alignments.
-__device__ __forceinline__ void sort_copy16(const uint8_t *s, uint8_t *d, uint32_t sz, uint32_t sub) {
-    const uint32_t head = min(sz, (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u));
-    const uint32_t nchunk = (sz - head) >> 4, tail = head + (nchunk << 4);
-    if (sub < head) d[sub] = s[sub];
-    for (uint32_t c = sub; c < nchunk; c += 16) {
-        const uint32_t q = head + (c << 4);
-        uint4 v;
-        v.x = rb32(s + q); v.y = rb32(s + q + 4); v.z = rb32(s + q + 8); v.w = rb32(s + q + 12);
-        *reinterpret_cast<uint4 *>(d + q) = v;
-    }
-    if (tail + sub < sz) d[tail + sub] = s[tail + sub];
 }
 // 16 lanes per record of the sorted order: record j = input record sidx[j], ssize[j] bytes from src + roff[sidx[j]] to out + dst[j] (sort_copy16)
 __global__ __launch_bounds__(256) void k_sort_gather(const uint8_t *src, const uint64_t *roff, const uint32_t *sidx, const uint32_t *ssize, const uint64_t *dst, uint64_t n, uint8_t *out) {
@@ -148,12 +133,15 @@ struct gce_sort {
     uint64_t p_lo = 0, p_hi = 0, p_g = 0; bool p_open = false; double p_scatter_s = 0;
     // SAM text in (gce_sam_sort, gce_samdev.hpp): the window is text, its records are written straight into `rec`
     bool sam_text = false; SamDev sam;
+    // calmd (gce_bam_calmd, gce_calmd.hpp): nothing is sorted; every window's records are rewritten straight into `out`, behind the ones before
+    bool calmd = false; DevBuf cm_blob, cm_tab, cm_size, cm_meta, cm_dst; uint64_t cm_in = 0;   // the reference and its table; a window's sizes, descriptions, destinations
 };
 
 static int sfail(gce_sort *b, int code, const std::string &m) { if (b) b->err = m; return code; }
 static int sort_oom(gce_sort *b, const char *what, uint64_t add) {
     char m[256];                                                                      // (the footprint first: a long `what` is cut off, not the formula)
-    snprintf(m, sizeof m, b->sam_text ? "out of device memory: SAM text is sorted in-core only (else gce_sam_to_bam, then gce_bam_sort_passes): 2 x the record bytes + 20 per record + a window of 2 per text byte + 41 per line (%lld live, budget %llu, %llu more for %s)" :
+    snprintf(m, sizeof m, b->calmd ? "out of device memory: calmd is in-core and needs about the output record bytes + the reference bases + 40 bytes per window record + one window (%lld bytes live, budget %llu, %llu more for %s)" :
+                          b->sam_text ? "out of device memory: SAM text is sorted in-core only (else gce_sam_to_bam, then gce_bam_sort_passes): 2 x the record bytes + 20 per record + a window of 2 per text byte + 41 per line (%lld live, budget %llu, %llu more for %s)" :
                           b->passes ? "out of device memory: the sort in output-range passes needs 8 bytes per record + one window + one pass of at least one BGZF member (about 44 bytes per record for its plan) (%lld bytes live, budget %llu, %llu more for %s)"
                                     : "out of device memory: the sort is in-core and needs about 2 x the inflated record bytes + 20 bytes per record + one window (%lld bytes live, budget %llu, %llu more for %s)",
              __atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), (unsigned long long)b->budget, (unsigned long long)add, what);
@@ -234,7 +222,7 @@ void gce_sort_destroy(gce_sort *b) {
     (void)hipSetDevice(b->device);
     (void)hipStreamSynchronize(b->s);
     b->w.release(); b->sam.release();
-    for (DevBuf *x : {&b->tmp, &b->misc, &b->rec, &b->key, &b->size, &b->off, &b->out, &b->zs, &b->zz, &b->zf, &b->zo, &b->dest, &b->pmisc}) x->release();
+    for (DevBuf *x : {&b->tmp, &b->misc, &b->rec, &b->key, &b->size, &b->off, &b->out, &b->zs, &b->zz, &b->zf, &b->zo, &b->dest, &b->pmisc, &b->cm_blob, &b->cm_tab, &b->cm_size, &b->cm_meta, &b->cm_dst}) x->release();
     (void)hipStreamDestroy(b->s);
     delete b;
 }

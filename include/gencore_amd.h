@@ -645,6 +645,29 @@ typedef struct gce_sort_pass_run {
 } gce_sort_pass_run;
 int gce_bam_sort_passes(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
                         size_t device_budget_bytes, int32_t min_passes, gce_sort_run *out, gce_sort_pass_run *run, char err[256]);
+/* NM and MD of every record recomputed against the reference on ONE device, file to file (addition under ABI v3; gencore_amd/csrc/gce_calmd.hpp,
+ * DESIGN.md 4g).  Replaces: nothing in the reference's source -- it stands in for the `samtools calmd` a pipeline runs behind the reference,
+ * whose consensus records carry the MD:Z of one read of their cluster and an NM it patches only when stored as type C (src/group.cpp:531-570),
+ * and in front of it for an input without NM (every runner here stops with GCE_ERR_NM_MISSING otherwise, src/group.cpp:532-535).  The file is
+ * streamed in windows of window_bytes compressed bytes (0 = 64 MB) as gce_bam_sort streams it; the GPU inflates every window, finds its
+ * records, walks each eligible record's CIGAR over its bases and the contig (rules E / R / W), drops every NM and MD field and appends
+ * NM (type C, S or I, the smallest that holds it) and MD:Z (rule T); every other byte of the record, every ineligible record (unmapped, no
+ * CIGAR, no bases, a contig the FASTA lacks: n_no_ref, ...) and the header stay as they are, in the input's order.  fasta_path: as
+ * gce_run_bam reads it (gce_fasta_load); contigs are matched to the header by name.  level and the file's layout (rule F): gce_bam_sort's.
+ * In-core: about the output record bytes + the reference bases + 40 bytes per window record + one window of device memory;
+ * device_budget_bytes (0 = no limit beyond the device) is checked before every growth: GCE_ERR_OOM with a message that states this
+ * footprint, before any output exists.  Temporary file, rename and an out_path that resolves to the input: as gce_bam_sort.
+ * GCE_ERR_INVALID with a message for a NULL path, a level outside -3..9 and a fasta_path that does not exist (all before a device is
+ * touched), for SAM text ("gce_bam_calmd reads BAM, not SAM text"), a file that is not BGZF or is truncated, and a record whose optional
+ * fields do not tile its block_size (the message names the lowest such record, counting from 0; no output is written). */
+typedef struct gce_calmd_run {
+    int64_t n_records, n_rewritten, n_unchanged, n_no_ref, n_nm_changed, n_md_changed;   /* n_unchanged = n_records - n_rewritten; n_no_ref of those: the FASTA lacks the contig */
+    int64_t inflated_bytes, out_record_bytes, out_bytes, peak_device_bytes;   /* record bytes read / written; size of the file written; gce_device_bytes' peak during the call */
+    int32_t n_ref, pad;
+    double  read_s, inflate_index_s, calmd_s, write_s, total_s;   /* read_s holds the FASTA's load; calmd_s: the k_md_* kernels and their scan */
+} gce_calmd_run;
+int gce_bam_calmd(const char *in_path, const char *out_path, const char *fasta_path, int32_t device, int threads, int level,
+                  uint64_t window_bytes, size_t device_budget_bytes, gce_calmd_run *out, char err[256]);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

@@ -100,7 +100,7 @@ STATUS_NAMES = {
 EXPORTED_SYMBOLS = [
     "gce_params_default", "gce_detect_umi_prefix", "gce_create", "gce_destroy", "gce_set_reference", "gce_set_reference_ascii", "gce_set_reference_window",
     "gce_pack_reference", "gce_set_flush_events", "gce_submit", "gce_submit_device", "gce_process", "gce_drain", "gce_result_device",
-    "gce_get_timing", "gce_get_vote_counters", "gce_get_consensus_counters", "gce_get_index_counters", "gce_get_pairing_tiers", "gce_reset", "gce_last_error", "gce_status_message", "gce_abi_version",
+    "gce_get_timing", "gce_get_vote_counters", "gce_get_consensus_counters", "gce_get_skipped_groups", "gce_get_index_counters", "gce_get_pairing_tiers", "gce_reset", "gce_last_error", "gce_status_message", "gce_abi_version",
     "gce_reserve", "gce_submit_async", "gce_submit_wait",
     "gce_bam_open", "gce_bam_close", "gce_bam_error", "gce_bam_get_info", "gce_bam_chunk", "gce_bam_write", "gce_bam_from_batch", "gce_sam_to_bam", "gce_bam_to_sam",
     "gce_fasta_load", "gce_fasta_get", "gce_fasta_free", "gce_run_bam", "gce_run_bam_hostcodec", "gce_run_bam_sharded", "gce_run_bam_sharded_hostcodec", "gce_raw_deflate_output", "gce_raw_read_deflated_async", "gce_bgzf_deflate", "gce_raw_deflate_output_codes", "gce_bgzf_deflate_codes", "gce_raw_attach_mirror", "gce_raw_select_shard", "gce_raw_merge_outputs", "gce_raw_begin", "gce_raw_push", "gce_raw_push_bgzf", "gce_bgzf_inflate", "gce_raw_finish", "gce_raw_build_output", "gce_raw_read_output_async", "gce_host_alloc", "gce_host_free", "gce_depth_stats", "gce_stats_payload_device", "gce_stats_payload_sum", "gce_stats_payload_read", "gce_run_bam_depth", "gce_depth_run_free", "gce_stats_device", "gce_stream_context", "gce_plan_shards", "gce_free", "gce_bed_load", "gce_bed_free",
@@ -212,6 +212,7 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
     lib.gce_get_timing.argtypes = [C.c_void_p, C.POINTER(GceTiming)]
     lib.gce_get_vote_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.gce_get_consensus_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.gce_get_skipped_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.gce_get_index_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.gce_get_pairing_tiers.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.gce_stats_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]

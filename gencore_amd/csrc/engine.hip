@@ -111,7 +111,7 @@ struct gce_engine {
     bool tab_clean = false; const void *tab_clean_ptr = nullptr; size_t tab_clean_cap = 0;   // the bucket table is all-zero (k_scatter wipes what a step used)
     DevBuf cl_ikey, cl_start, cl_n, cl_npairs, cl_ngroups, cl_gbase, cl_nresult, cl_hasumi, cl_tier;
     DevBuf members, sorted, pl, pr, pu, pg, gpl, gpr, grp_begin, grp_n, gl_cluster, g_begin, g_np;
-    DevBuf slow_args, deep_list, k64, slow_list, left_list, pf_flag, pf_list, pq_flag, pq_list, p16_flag, p16_list, pd_slab, gen_flag, gen_list, score_list, gw, g_wbase, vb_start, rp_left, rp_right, rp_merge, rp_rmerge, rp_umi, rp_umilen, rp_state, rp_supp, rp_nm, rp_qsl, rp_qsr, scan_part, si;
+    DevBuf slow_args, deep_list, k64, slow_list, left_list, pf_flag, pf_list, pq_flag, pq_list, p16_flag, p16_list, pd_slab, gen_flag, gen_list, score_list, gw, vlive, vb_start, rp_left, rp_right, rp_merge, rp_rmerge, rp_umi, rp_umilen, rp_state, rp_supp, rp_nm, rp_qsl, rp_qsr, scan_part, si;
     StreamInfo h_si{};
     void *si_pin = nullptr, *si_pin_dev = nullptr; unsigned long long si_seq = 0;      // read_si: the block in mapped host memory + its sequence word
     gce_timing timing{};
@@ -191,7 +191,7 @@ void gce_destroy(gce_engine *e) {
                      &e->o_key, &e->o_rec, &e->o_ksoff, &e->o_kqoff, &e->o_krow, &e->o_rank64, &e->o_part3, &e->o_soff, &e->o_qoff, &e->o_seq, &e->o_qual, &e->ref_ascii, &e->lrec, &e->lout, &e->bhdr,
                      &e->blk_base, &e->ev_tid, &e->ev_pos, &e->ev_read, &e->table, &e->toff, &e->cl_ikey, &e->cl_start, &e->cl_n,
                      &e->cl_npairs, &e->cl_ngroups, &e->cl_gbase, &e->cl_nresult, &e->cl_hasumi, &e->cl_tier, &e->members, &e->sorted, &e->pl, &e->pr, &e->pu,
-                     &e->pg, &e->gpl, &e->gpr, &e->grp_begin, &e->grp_n, &e->gl_cluster, &e->g_begin, &e->g_np, &e->deep_list, &e->k64, &e->slow_list, &e->pf_flag, &e->pf_list, &e->pq_flag, &e->pq_list, &e->left_list, &e->slow_args, &e->pd_slab, &e->gen_flag, &e->gen_list, &e->score_list, &e->gw, &e->g_wbase, &e->vb_start, &e->rp_left, &e->rp_right, &e->rp_merge, &e->rp_rmerge,
+                     &e->pg, &e->gpl, &e->gpr, &e->grp_begin, &e->grp_n, &e->gl_cluster, &e->g_begin, &e->g_np, &e->deep_list, &e->k64, &e->slow_list, &e->pf_flag, &e->pf_list, &e->pq_flag, &e->pq_list, &e->left_list, &e->slow_args, &e->pd_slab, &e->gen_flag, &e->gen_list, &e->score_list, &e->gw, &e->vlive, &e->vb_start, &e->rp_left, &e->rp_right, &e->rp_merge, &e->rp_rmerge,
                      &e->rp_umi, &e->rp_umilen, &e->rp_state, &e->rp_supp, &e->rp_nm, &e->rp_qsl, &e->rp_qsr, &e->scan_part, &e->si};
     for (auto *b : all) b->release();
     for (DevBuf *b : {&e->z_comp, &e->z_dir, &e->z_err, &e->raw, &e->rw_tmp, &e->rw_ncig, &e->rw_nmpos, &e->rw_rsize, &e->rw_roff, &e->rw_body, &e->sf_text}) b->release();
@@ -692,6 +692,10 @@ static int gce_process_impl(gce_engine *e) {
     memset(&e->timing, 0, sizeof e->timing);
     memset(&e->h_si, 0, sizeof e->h_si);
     if (N >= (int64_t)0xFFFFFC00ll) return fail(e, GCE_ERR_INVALID, "more than 2^32 reads in one engine");
+    // k_vote's batches come from ONE scan of packed words, weight prefix in the low half and live rank in the high half (k_group_fill, k_vote_batches): a weight sum of
+    // 2^32 would carry into the ranks.  The sum is at most (VB_MINW + 3) x reads (vb_start's bound below), so such a stream is refused here (it would need > 100 GB of
+    // descriptors and pair slots alone; the 32-bit weight prefixes of earlier versions wrapped at the same sum)
+    if ((uint64_t)(VB_MINW + 3) * (uint64_t)(N > 0 ? N : 0) >= (1ull << 32)) return fail(e, GCE_ERR_INVALID, "too many reads in one engine for the batch scan of k_vote (weight sum >= 2^32)");
     const size_t n1 = (size_t)(N > 0 ? N : 1);
 
     DevBatch b{}; b.n = N; b.core = hb.core; b.qname_off = hb.qname_off; b.qname = hb.qname; b.cigar_off = hb.cigar_off; b.cigar = hb.cigar;
@@ -952,15 +956,15 @@ static int gce_process_impl(gce_engine *e) {
         hipLaunchKernelGGL(k_u32_apply, dim3(nblk_C), dim3(256), 0, s, (const uint32_t *)w.cl_ngroups, w.cl_gbase, (uint64_t)C, (const uint64_t *)w.scan_part);
         // the compact group list and the batches of k_vote: sized by N (groups <= pairs <= reads) so that all of it runs before the one
         // host round trip that fetches the group count and the batch count together
-        ENS(gl_cluster, n1 * 4); ENS(g_begin, n1 * 4); ENS(g_np, n1 * 4); ENS(gw, n1 * 8); ENS(g_wbase, n1 * 4);
+        ENS(gl_cluster, n1 * 4); ENS(g_begin, n1 * 4); ENS(g_np, n1 * 4); ENS(gw, n1 * 8); ENS(vlive, n1 * 16);
         const size_t vb_cap = ((VB_MINW + 3) * n1) / VB_W + 8;     // sum of weights <= VB_MINW x groups + pairs + VB_W x deep groups (> 32 pairs each)
         ENS(vb_start, vb_cap * 4);
         w.gl_cluster = e->gl_cluster.as<uint32_t>(); w.g_begin = e->g_begin.as<uint32_t>(); w.g_np = e->g_np.as<uint32_t>();
-        w.gw = e->gw.as<uint64_t>(); w.g_wbase = e->g_wbase.as<uint32_t>(); w.vb_start = e->vb_start.as<uint32_t>();
+        w.gw = e->gw.as<uint64_t>(); w.vlive = e->vlive.as<uint4>(); w.vb_start = e->vb_start.as<uint32_t>();
         HIPCHK(hipMemsetAsync(e->vb_start.p, 0xFF, vb_cap * 4, s));
-        hipLaunchKernelGGL(k_group_fill, dim3(cdiv(C, 256)), dim3(256), 0, s, w, C, p.skip_low_complexity_thr, (uint32_t)VB_W, (uint32_t)VB_MINW);
+        hipLaunchKernelGGL(k_group_fill, dim3(cdiv(C, 256)), dim3(256), 0, s, p, w, C, (uint32_t)VB_W, (uint32_t)VB_MINW);
         hipLaunchKernelGGL(k_u64_reduce, dim3(nblk_N), dim3(256), 0, s, (const uint64_t *)w.gw, (const unsigned long long *)&w.si->n_groups, w.scan_part);
-        hipLaunchKernelGGL(k_u64_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (const unsigned long long *)&w.si->n_groups, &w.si->vote_weight);
+        hipLaunchKernelGGL(k_u64_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (const unsigned long long *)&w.si->n_groups, &w.si->vote_weight, &w.si->n_live);
         LAUNCH_EV(k_vote_batches, dim3(nblk_N), dim3(256), s, e->ev[EV_PAIRING], w, (const unsigned long long *)&w.si->n_groups, (const uint64_t *)w.scan_part);
         CANARY("EV_PAIRING");
         if ((rc = read_si(e)) != GCE_OK) return rc;
@@ -986,6 +990,7 @@ static int gce_process_impl(gce_engine *e) {
         fill_many(s, {FillSeg{e->gen_flag.p, g1 * 2, 0u, 0u},
                       FillSeg{e->rp_nm.p, g1 * 8, 0xFFu, 0u},                                  // -1: NM untouched
                       FillSeg{e->rp_left.p, g1 * 4, 0xFFu, 0u}, FillSeg{e->rp_right.p, g1 * 4, 0xFFu, 0u}});   // NONE: a group no kernel voted on emits nothing (instead of stale read indices)
+        const uint32_t n_live = (uint32_t)e->h_si.n_live;                                    // (with none, vb_start[0] stays NONE32: k_vote's one block returns at once and reads no list)
 #ifdef VB_XCD
         const unsigned nbatch = (((unsigned)(e->h_si.vote_weight / VB_W) + 1u) + 7u) & ~7u;      // (vb_start is 0xFF-filled up to vb_cap: the extra blocks find no batch)
 #else
@@ -994,12 +999,12 @@ static int gce_process_impl(gce_engine *e) {
 #ifdef VB_STOP
         {   // experiment builds (tools/vote_stop.sh): time the truncated k_vote alone and stop -- it leaves garbage behind
             hipEvent_t a_, b_; (void)hipEventCreate(&a_); (void)hipEventCreate(&b_);
-            (void)hipEventRecord(a_, s); hipLaunchKernelGGL(k_vote, dim3(nbatch), dim3(VB_T), 0, s, b, p, w, NG); (void)hipEventRecord(b_, s); (void)hipEventSynchronize(b_);
+            (void)hipEventRecord(a_, s); hipLaunchKernelGGL(k_vote, dim3(nbatch), dim3(VB_T), 0, s, b, p, w, n_live); (void)hipEventRecord(b_, s); (void)hipEventSynchronize(b_);
             float ms_ = 0; (void)hipEventElapsedTime(&ms_, a_, b_); fprintf(stderr, "k_vote up to tick %d: %.3f ms\n", VB_STOP, ms_);
             return fail(e, GCE_ERR_INVALID, "experiment build");
         }
 #endif
-        LAUNCH_EV(k_vote, dim3(nbatch), dim3(VB_T), s, e->ev[EV_SCORE], b, p, w, NG);
+        LAUNCH_EV(k_vote, dim3(nbatch), dim3(VB_T), s, e->ev[EV_SCORE], b, p, w, n_live);
         CANARY("EV_SCORE");
         // A stream of deep groups (mean depth beyond 24 pairs: the deep kernels carry the consensus phase, cfg5) runs Pair::computeScore for the
         // handed-on groups (k_score2: bandwidth) on a second HIP stream BESIDE the compaction, the hand-on of the deep sides and their template /
@@ -1308,11 +1313,22 @@ int gce_get_vote_counters(gce_engine *e, int64_t out[4]) {
 }
 
 // group sides FINISHED per consensus kernel in the last gce_process: [0] k_vote (every side of a group it did not hand on), [1] k_consensus_fast,
-// [2] k_deep_prepare (deep sides without a template: nothing to vote), [3] k_vote_deep, [4] k_consensus_slow.  The five add up to 2 x groups.
+// [2] k_deep_prepare (deep sides without a template: nothing to vote), [3] k_vote_deep, [4] k_consensus_slow.  The five add up to
+// 2 x (groups - skipped groups): a group d_group_skipped leaves out reaches none of them (gce_get_skipped_groups).
 int gce_get_consensus_counters(gce_engine *e, int64_t out[5]) {
     if (!e || !out || !e->processed) return GCE_ERR_INVALID;
-    out[0] = 2 * (int64_t)e->h_si.n_groups - (int64_t)(e->h_si.hand_on >> 32);
+    out[0] = 2 * (int64_t)(e->h_si.n_groups ? e->h_si.n_live : 0) - (int64_t)(e->h_si.hand_on >> 32);
     out[1] = (int64_t)e->h_si.cs_fast; out[2] = (int64_t)e->h_si.cs_prep; out[3] = (int64_t)e->h_si.cs_deep; out[4] = (int64_t)e->h_si.cs_slow;
+    return GCE_OK;
+}
+
+// groups of the last gce_process that were not evaluated because no setting of the run could write them (d_group_skipped, gce_kernels.hpp):
+// one-pair groups under --supporting_reads > 1 or --duplex_only in clusters that form no duplex.  0 with -s 1 and no --duplex_only.
+// out[1]: the batches k_vote formed over the live groups (vote_weight / VB_W + 1; 0 for a stream without groups).
+int gce_get_skipped_groups(gce_engine *e, int64_t out[2]) {
+    if (!e || !out || !e->processed) return GCE_ERR_INVALID;
+    out[0] = e->h_si.n_groups ? (int64_t)e->h_si.n_groups - (int64_t)e->h_si.n_live : 0;
+    out[1] = e->h_si.n_groups ? (int64_t)(e->h_si.vote_weight / VB_W) + 1 : 0;
     return GCE_OK;
 }
 

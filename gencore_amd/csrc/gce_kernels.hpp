@@ -52,7 +52,8 @@ struct Work {
     uint64_t *k64;                       // generic pairing scratch: 3 words per read (name window / UMI words)
     // groups (compact)
     uint32_t *gl_cluster, *g_begin, *g_np;   // per compact group: owning cluster, first pair slot, pair count
-    uint64_t *gw; uint32_t *g_wbase, *vb_start;   // k_vote batching: weight of every group, its exclusive prefix, first group of every batch
+    uint64_t *gw; uint4 *vlive; uint32_t *vb_start;   // k_vote batching: per group its weight | live << 32 (0: d_group_skipped); the LIVE groups as {group, first pair slot, pairs,
+                                         // weight prefix}, one 16-byte load in k_vote's P0; first live-list entry of every batch
     uint32_t *slow_list;                 // (group*2 + side) entries deferred to the generic consensus kernel
     uint8_t *pf_flag; uint32_t *pf_list;      // clusters the half-wave pairing kernel hands to the full-wave one (same scheme)
     uint8_t *pq_flag; uint32_t *pq_list;      // ... and the quarter-wave kernel to the half-wave one
@@ -532,20 +533,34 @@ __global__ __launch_bounds__(256) void k_pairing_fast(DevBatch b, DevParams p, W
     }
 }
 
-// exclusive scan helper over a uint32 array (small-ish n): element = v[i]; reuses the table-scan kernels via tab_elem's low word
-__global__ void k_group_fill(Work w, uint32_t n_clusters, int skip_thr, uint32_t deep_weight, uint32_t min_weight) {
+// A group whose result no setting of this run can write is not evaluated: ONE pair (mMergeReads = 1) under --supporting_reads > 1 or --duplex_only is deleted
+// unwritten (cluster.cpp:157-181) unless a duplex partner adds its reads -- and its Stats entry is known before a base is read: supporting reads 1, PE iff the
+// pair has both reads (group.cpp:73-77 for a mate-less pair; with one pair and --skip_low_complexity_cluster_threshold >= 1 consensusMergeBam returns that pair's
+// read, group.cpp:196-285; with a threshold of 0 it may return NULL, group.cpp:142-175, and the group keeps the full path).  It cannot find a partner when its
+// cluster forms no duplex at all: no UMI, --no_duplex, a single group (k_group_tail's rule).  A one-pair group of a cluster that does form duplexes keeps the
+// full path even where its own UMI could not match (looking at the UMI here cost what it saved), and so do groups of 2 .. cluster_size_req - 1
+// pairs: their PE flag needs the template choice.  k_group_fill leaves a skipped group out of k_vote's live list and k_group_tail takes its two
+// reads from the pair slot: both ask THIS function.
+__device__ __forceinline__ bool d_group_skipped(const DevParams &p, uint8_t cflags, uint32_t cl_groups, uint32_t np) {
+    if (np != 1u || p.skip_low_complexity_thr < 1 || !(p.duplex_only || p.cluster_size_req > 1)) return false;
+    return !(cflags & 1) || p.disable_duplex || cl_groups < 2u;
+}
+
+// the compact group list (one thread per cluster) and what k_vote_batches scans: weight | 1 << 32 of every live group, 0 for a skipped one
+__global__ void k_group_fill(DevParams p, Work w, uint32_t n_clusters, uint32_t deep_weight, uint32_t min_weight) {
     uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_clusters) return;
     uint32_t g0 = w.cl_gbase[c], ng = w.cl_ngroups[c];
     const uint32_t cs = w.cl_start[c];
+    const uint8_t cflags = ng ? w.cl_hasumi[c] : (uint8_t)0;
     for (uint32_t g = 0; g < ng; g++) {
-        const uint32_t np = w.grp_n[cs + g];
-        w.gl_cluster[g0 + g] = c; w.g_begin[g0 + g] = w.grp_begin[cs + g]; w.g_np[g0 + g] = np;
+        const uint32_t np = w.grp_n[cs + g], begin = w.grp_begin[cs + g];
+        w.gl_cluster[g0 + g] = c; w.g_begin[g0 + g] = begin; w.g_np[g0 + g] = np;
         // k_vote batches (gce_vote.hpp): a group weighs its pairs (at least VB_MINW: <= 16 groups per batch); a deep group is handed on by a batch of its own
         // (only a group of more than 32 pairs: P0's slot-flag loop is serial in its pairs.  A group that is "deep" by a small --skip_low_complexity
         //  threshold alone is handed on from a shared batch: with a batch of its own for every 2-pair group the batch count left the bound vb_start is sized by)
-        (void)skip_thr;
-        w.gw[g0 + g] = np > 32u ? (uint64_t)deep_weight : (uint64_t)(np < min_weight ? min_weight : np);
+        const uint64_t wt = np > 32u ? (uint64_t)deep_weight : (uint64_t)(np < min_weight ? min_weight : np);
+        w.gw[g0 + g] = d_group_skipped(p, cflags, ng, np) ? 0ull : (wt | (1ull << 32));
     }
 }
 // scan of cl_ngroups -> cl_gbase : same 3-phase scheme on the plain counts
@@ -1764,6 +1779,15 @@ __global__ __launch_bounds__(256) void k_group_tail(DevBatch b, DevParams p, Wor
     if (gi >= n_groups) return;
     const uint32_t c = w.gl_cluster[gi];
     const uint32_t begin = w.g_begin[gi], np = w.g_np[gi];
+    const uint8_t cflags = w.cl_hasumi[c];
+    const uint32_t G = w.cl_ngroups[c];
+    if (d_group_skipped(p, cflags, G, np)) {
+        // no kernel looked at this group (k_group_fill) and its cluster forms no duplex: its result records are the one pair's reads as they came in -- k_stats
+        // reads them for PE / SE --, one supporting read, never written (rp_nm is still -1: no NM patch was deferred)
+        w.rp_left[gi] = w.gpl[begin]; w.rp_right[gi] = w.gpr[begin];
+        w.rp_supp[gi] = 1; w.rp_state[gi] = RP_DROPPED;
+        return;
+    }
     uint32_t left = w.rp_left[gi], right = w.rp_right[gi];
     {   // the NM patches k_vote deferred (group.cpp:528-573): mismatchInc != 0 reads the template's NM tag -- absent: the reference crashes (quirk Q9);
         // mismatchInc > 5: the template was restored, NM stays; else NM + mismatchInc goes into the tag if it is stored as type 'C' and stays a byte
@@ -1780,8 +1804,6 @@ __global__ __launch_bounds__(256) void k_group_tail(DevBatch b, DevParams p, Wor
             *reinterpret_cast<int2 *>(w.rp_nm + 2 * (size_t)gi) = o;
         }
     }
-    const uint8_t cflags = w.cl_hasumi[c];
-    const uint32_t G = w.cl_ngroups[c];
     const bool single = np == 1 && w.gpr[begin] == NONE32;
     uint32_t qsl = left, qsr = right;                                     // BamUtil::copyQName sources (== the record itself if unchanged)
     // the two templates' name lengths and UMI places: one word each (round 5; core record + UMI pointer + UMI length + MI flag were four sectors per side)

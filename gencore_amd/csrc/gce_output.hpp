@@ -211,7 +211,8 @@ __global__ __launch_bounds__(256) void k_u64_reduce(const uint64_t *v, const uns
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
-__global__ __launch_bounds__(1024) void k_u64_partials(uint64_t *part, const unsigned long long *n_ptr, unsigned long long *total) {
+// (the total's halves go to *total_lo and *total_hi)
+__global__ __launch_bounds__(1024) void k_u64_partials(uint64_t *part, const unsigned long long *n_ptr, unsigned long long *total_lo, unsigned long long *total_hi) {
     __shared__ uint64_t s_w[16];
     __shared__ uint64_t s_carry;
     const uint64_t nparts = (*n_ptr + SCAN_TILE - 1) / SCAN_TILE;
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(1024) void k_u64_partials(uint64_t *part, const uns
         if (threadIdx.x == 1023) s_carry = carry + woff + x;
         __syncthreads();
     }
-    if (threadIdx.x == 0) *total = s_carry;
+    if (threadIdx.x == 0) { *total_lo = s_carry & 0xFFFFFFFFull; *total_hi = s_carry >> 32; }
 }
 // 16 bytes from an arbitrary byte address
 __device__ __forceinline__ uint4 ld16_unaligned(const uint8_t *p_) {

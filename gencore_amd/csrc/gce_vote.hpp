@@ -141,12 +141,14 @@ __device__ __forceinline__ int d_ref_nib_g(uint64_t ref, int64_t pos) {
     return (int)((0x42810u >> (4 * (code < 5 ? code : 5))) & 0xFu);
 }
 
-// weights + batch starts: exclusive scan of the group weights (k_u64_reduce / k_u64_partials in front), first group of every batch
+// live list + batch starts: exclusive scan of the packed group words of k_group_fill (weight | live << 32; k_u64_reduce / k_u64_partials in front).
+// A live group lands at its live rank in w.vlive as {group, first pair slot, pairs, weight prefix}; a skipped group (word 0) leaves no trace.
 __global__ __launch_bounds__(256) void k_vote_batches(Work w, const unsigned long long *n_ptr, const uint64_t *part) {
     __shared__ uint64_t s_w[4];
     __shared__ uint64_t s_carry;
     const uint64_t n = *n_ptr, base = (uint64_t)blockIdx.x * SCAN_TILE;
     if (base >= n) return;
+    const uint32_t n_live = (uint32_t)w.si->n_live;
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) s_carry = part[blockIdx.x];
     __syncthreads();
@@ -159,16 +161,17 @@ __global__ __launch_bounds__(256) void k_vote_batches(Work w, const unsigned lon
         uint64_t woff = 0;
         for (int q = 0; q < wv; q++) woff += s_w[q];
         const uint64_t carry = s_carry, ex = carry + woff + x - v;
-        if (i < n) {
-            w.g_wbase[i] = (uint32_t)ex;
-            // the first group of a batch writes the batch's start: group i opens batch ex / VB_W iff no earlier group lies in it, i.e. iff the
-            // group in front of it starts in an earlier batch (its start is ex - its weight, read from memory: NOT shuffled in from the
-            // neighbour lane -- this branch is divergent at the end of the list, and a shuffle in a divergent branch reads garbage, which
-            // is what a first version of this rule most likely did: a batch without start leaves its groups unvoted).  One store per batch
-            // instead of one device-scope atomicMin per group: 1.56 M atomics were 57 of this kernel's 67 us.  Equivalent to the minimum
-            // over the groups of the batch because the starts ascend with the index; groups of weight 0 do not exist (k_group_fill: >= 4).
-            const bool first = i == 0 || (ex - w.gw[i - 1]) / VB_W != ex / VB_W;
-            if (first) w.vb_start[ex / VB_W] = (uint32_t)i;
+        if (v != 0) {                                                                   // (a live group: i < n, weight >= VB_MINW)
+            const uint32_t li = (uint32_t)(ex >> 32), wex = (uint32_t)ex, wt = (uint32_t)v;
+            w.vlive[li] = make_uint4((uint32_t)i, w.g_begin[i], w.g_np[i], wex);
+            // The first live group of a batch is the batch's start.  Entry li opens batch wex / VB_W iff the live entry in front of it starts in an earlier
+            // batch -- and that entry is the one that knows: its start and its weight say where ITS SUCCESSOR starts, so every entry whose end lies in a later
+            // batch than its start writes the start of its successor's batch (entry 0 opens batch 0).  Nothing is read that another thread writes, nothing is
+            // shuffled in a divergent branch, and one store per batch instead of an atomicMin per group (1.56 M atomics were 57 of this kernel's 67 us).  A
+            // batch in which no entry starts (inside a deep group's weight) keeps NONE32; the last entry has no successor.
+            if (li == 0u) w.vb_start[0] = 0u;
+            const uint32_t nb = (wex + wt) / VB_W;
+            if (nb != wex / VB_W && li + 1u < n_live) w.vb_start[nb] = li + 1u;
         }
         __syncthreads();
         if (threadIdx.x == 255) s_carry = carry + woff + x;
@@ -236,7 +239,7 @@ __device__ __forceinline__ int vb_find_wave(const uint16_t *arr, int s0, int n, 
 #define VB_SUBTICK(k) do { } while (0)
 #endif
 #define gb_ gb_
-__global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8))) void k_vote(DevBatch b, DevParams p, Work w, uint32_t n_groups) {
+__global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8))) void k_vote(DevBatch b, DevParams p, Work w, uint32_t n_live) {      // n_live: entries of w.vlive (k_vote_batches)
     __shared__ VRead s_rd[2][VB_MAXP];
     __shared__ VOv s_ov[VB_MAXP];
     __shared__ VSide s_side[VB_SIDES];
@@ -281,9 +284,9 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
 #endif
     // ---------------------------------------------------------------- P0: the groups of this batch
     if (tid < 64) {
-        const uint32_t gi = g0 + (uint32_t)lane;
-        const bool maybe = lane < VB_MAXG && gi < n_groups;                            // (the three loads side by side: whether the group belongs to the batch only decides who uses them)
-        const uint32_t wb_ = maybe ? w.g_wbase[gi] : 0u, np_ = maybe ? w.g_np[gi] : 0u, gb_ = maybe ? w.g_begin[gi] : 0u;
+        const bool maybe = lane < VB_MAXG && g0 + (uint32_t)lane < n_live;             // (ONE 16-byte load per live-list entry: whether the group belongs to the batch only decides who uses it)
+        const uint4 lr_ = maybe ? w.vlive[g0 + (uint32_t)lane] : make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t gi = lr_.x, gb_ = lr_.y, np_ = lr_.z, wb_ = lr_.w;
         bool in = maybe && wb_ < (bid_ + 1u) * VB_W;
         uint32_t np = in ? np_ : 0u;
         const bool deep = in && (np > 32u || (int)np > p.skip_low_complexity_thr || !p.vote_ok);

@@ -111,6 +111,19 @@ class Engine:
         self._check(self.lib.gce_get_consensus_counters(self._h, v))
         return dict(zip(self.CONSENSUS_KERNELS, (int(x) for x in v)))
 
+    def skipped_groups(self):
+        """Groups of the last finish() that were not evaluated because no setting of the run could write them (gce_get_skipped_groups)."""
+        return self._skipped()[0]
+
+    def vote_batches(self):
+        """Batches k_vote formed over the evaluated groups of the last finish() (gce_get_skipped_groups)."""
+        return self._skipped()[1]
+
+    def _skipped(self):
+        v = (C.c_int64 * 2)()
+        self._check(self.lib.gce_get_skipped_groups(self._h, v))
+        return int(v[0]), int(v[1])
+
     def index_counters(self):
         """The record index of the last gce_raw_finish (gce_get_index_counters)."""
         return index_counters(self._h)

@@ -45,7 +45,7 @@ typedef enum gce_status {
      * EARLIEST read is reported (the reference stops at the first in stream order). */
     GCE_ERR_UNSORTED = -10,        /* src/gencore.cpp:233-241 "the input is unsorted" */
     GCE_ERR_UMI_MISMATCH = -11,    /* src/pair.cpp:201-212 "The UMI of a read pair should be identical" */
-    GCE_ERR_NM_MISSING = -12,      /* src/group.cpp:532-535: NM dereferenced although absent (segfault in the reference) */
+    GCE_ERR_NM_MISSING = -12,      /* src/group.cpp:532-535: NM dereferenced although absent (segfault in the reference); never for a group that is not evaluated (gce_batch) */
     GCE_ERR_UMI_PARSE = -13,       /* src/bamutil.cpp:47-62: substr(start) with start > length throws in the reference */
     GCE_ERR_QNAME_SHORT = -14,     /* src/bamutil.cpp:343-346 "copyQName ERROR: desitination qname is shorter" */
     GCE_ERR_REF_WINDOW = -15       /* a clustered read lies outside the reference window staged for its contig (gce_set_reference_window) */
@@ -112,7 +112,9 @@ typedef struct gce_params {
  * come from gce_core (l_qname, n_cigar, l_qseq).  seq is BAM 4-bit packed (high nibble = even base,
  * src/bamutil.cpp:133-147,167-189), qual is raw Phred.  seq/qual are MUTATED IN PLACE where the reference
  * mutates its bam1_t records (src/group.cpp:503-525,555-556, src/cluster.cpp:227-232; the quality rewrite of
- * src/pair.cpp:158-159 persists only in emitted records, see gce_result).
+ * src/pair.cpp:158-159 persists only in emitted records, see gce_result).  A group that no setting of the run can write -- one pair
+ * under --supporting_reads > 1 or --duplex_only in a cluster that forms no duplex (gce_get_skipped_groups) -- is not evaluated: its
+ * reads keep their input bytes, and it raises none of the consensus errors (GCE_ERR_NM_MISSING, GCE_ERR_QNAME_SHORT).
  * Device buffers (gce_submit_device): `core` must be 16-byte aligned and every blob readable 16 bytes past its end
  * (vector loads of the last read); gce_submit pads its own copies.  Reads longer than 65535 bases are rejected. */
 typedef struct gce_batch {
@@ -317,8 +319,14 @@ int gce_get_timing(gce_engine *e, gce_timing *out);
 int gce_get_vote_counters(gce_engine *e, int64_t out[4]);
 /* Group sides finished per consensus kernel in the last gce_process (ADDED under v3; for tests and diagnostics): out[0] k_vote (both sides of
  * every group it did not hand on), out[1] k_consensus_fast, out[2] k_deep_prepare (deep sides without a template), out[3] k_vote_deep,
- * out[4] k_consensus_slow.  After a gce_process without a device error the five add up to 2 x groups. */
+ * out[4] k_consensus_slow.  out[0] counts only sides k_vote really finished: after a gce_process without a device error the five add up to
+ * 2 x (groups - skipped groups). */
 int gce_get_consensus_counters(gce_engine *e, int64_t out[5]);
+/* Groups of the last gce_process that were not evaluated because their result could not be written (ADDED under v3; for tests and diagnostics):
+ * one-pair groups under --supporting_reads > 1 or --duplex_only, with --skip_low_complexity_cluster_threshold >= 1, whose cluster forms no
+ * duplex (no UMI, --no_duplex, or a single group).  Their Stats entries are those of the reference; no consensus kernel sees them.
+ * out[0]: their number, 0 with -s 1 and no --duplex_only.  out[1]: the batches k_vote formed over the other groups (a batch holds at most 16). */
+int gce_get_skipped_groups(gce_engine *e, int64_t out[2]);
 /* The GPU record index's counters (ADDED under v3; for tests and diagnostics): out[0] 16 KB segments, out[1] of those flagged by the first
  * check (a guessed record start off the chain), out[2] parallel repair rounds, out[3] serial repairs (0 or 1 per index).  e: its last
  * gce_raw_finish; e == NULL: summed over every window of the last pass runner of the process (gce_run_bam_passes, key pass and passes). */

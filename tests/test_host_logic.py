@@ -8,6 +8,7 @@ import pytest
 
 import fuzzgen
 from gencore_amd.batch import ReadBatch
+from outcases import rows_from_table
 from parity_helpers import diff_results
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -152,28 +153,6 @@ def test_oracle_matches_frozen_regression_vectors(oracle):
     for case in frozen["cases"]:
         got = make_golden.digest_case(case["seed"], case["kwargs"])
         assert got == case["digest"], case
-
-
-def rows_from_table(batch, t):
-    """The engine's table of emitted records (gce_result) rebuilt from a per-read ResultTable: rows in bamComp order
-    (gencore.h:19-47, input index as the last key), compact 16-byte aligned blobs."""
-    em = np.nonzero(t.out_flag)[0]
-    c = batch.core[em]
-    order = np.lexsort((em, c["isize"], c["mpos"], c["mtid"], c["pos"], c["tid"]))
-    src = em[order].astype(np.uint32)
-    row_of = np.full(batch.n, 0xFFFFFFFF, np.uint32); row_of[src] = np.arange(len(src), dtype=np.uint32)
-    lq = batch.core["l_qseq"].astype(np.int64)[src]
-    su, qu = ((lq + 1) // 2 + 15) // 16 * 16, (lq + 15) // 16 * 16
-    seq_off, qual_off = np.cumsum(su) - su, np.cumsum(qu) - qu
-    seq, qual = np.zeros(int(su.sum()), np.uint8), np.zeros(int(qu.sum()), np.uint8)
-    for k, i in enumerate(src):
-        i = int(i); L = int(lq[k])
-        seq[seq_off[k]:seq_off[k] + (L + 1) // 2] = t.seq[int(batch.seq_off[i]):int(batch.seq_off[i]) + (L + 1) // 2]
-        qual[qual_off[k]:qual_off[k] + L] = t.qual[int(batch.qual_off[i]):int(batch.qual_off[i]) + L]
-    m = t.mate[src]
-    mate = np.where(m == 0xFFFFFFFF, np.uint32(0xFFFFFFFF), row_of[np.where(m == 0xFFFFFFFF, 0, m).astype(np.int64)])
-    return dict(src=src, kind=t.out_flag[src], qname_src=t.qname_src[src], nm_new=t.nm_new[src], fr=t.fr[src], rr=t.rr[src],
-                mate=mate.astype(np.uint32), seq_off=seq_off.astype(np.uint64), qual_off=qual_off.astype(np.uint64), seq=seq, qual=qual)
 
 
 @pytest.mark.parametrize("seed", [3, 17, 604])

@@ -187,12 +187,14 @@ def sort_bam(bam, out, device=0, threads=0, level=-2, window_bytes=0, device_bud
 
 
 class CalmdRun:
-    """gce_calmd_run as an object: one attribute per field (counters and bytes as int, times as float)."""
+    """gce_calmd_run as an object: one attribute per field (counters and bytes as int, times as float); calmd_bam_stream adds the fields of
+    gce_calmd_stream_run (n_flushes, resident_cap_bytes, flushed_bytes)."""
 
-    def __init__(self, r):
-        for n, t in type(r)._fields_:
-            if n != "pad":
-                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+    def __init__(self, r, stream=None):
+        for s in (r,) if stream is None else (r, stream):
+            for n, t in type(s)._fields_:
+                if n != "pad":
+                    setattr(self, n, (float if t is C.c_double else int)(getattr(s, n)))
 
     def as_dict(self):
         return dict(vars(self))
@@ -214,6 +216,24 @@ def calmd_bam(in_path, out_path, fasta, device=0, threads=0, level=6, window_byt
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     return CalmdRun(r)
+
+
+def calmd_bam_stream(in_path, out_path, fasta, device=0, threads=0, level=6, window_bytes=0, device_budget_bytes=0, resident_bytes=0):
+    """gce_bam_calmd_stream: calmd_bam's file, byte for byte, for an input of any size: the rewritten records leave the device in whole BGZF
+    members as soon as the next window's output would take the resident ones past the cap, so the device holds the reference bases + one
+    window + 40 bytes per window record + one piece's deflate buffers + at least one window's output.  device_budget_bytes: 0 = auto (a
+    fraction of the free device memory, as sort_bam_passes); resident_bytes: 0 = the cap is what the budget leaves, otherwise the cap,
+    rounded up to a multiple of 0xff00 (forces flushes on a small file).  Returns calmd_bam's CalmdRun with n_flushes, resident_cap_bytes
+    and flushed_bytes added; raises GceError with the library's message (and leaves no output) on failure."""
+    from .capi import GceCalmdRun, GceCalmdStreamRun
+    lib = capi.load_library()
+    r, sr = GceCalmdRun(), GceCalmdStreamRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_calmd_stream(str(in_path).encode(), str(out_path).encode(), str(fasta).encode(), int(device), int(threads), int(level), int(window_bytes),
+                                  int(device_budget_bytes), int(resident_bytes), C.byref(r), C.byref(sr), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    return CalmdRun(r, sr)
 
 
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):

@@ -22,7 +22,8 @@ them into the temporary BAM that --sort would make, without a BAM written in bet
 --calmd (not the reference's) makes NM and MD of the BAM output true: a consensus record takes its optional fields from one read of its cluster,
 so its MD:Z describes that read and not the voted bases, and its NM is patched only where it was stored as type C.  After the output and the
 report are written the GPU recomputes both against -r (what `samtools calmd` does behind the reference) and the result replaces the output.
-The report is not changed by it.
+The report is not changed by it.  --device_memory bounds it (and --calmd_in) as it bounds the run: the rewritten records are written while the file
+is read, so neither the input nor the output has to fit the device (the reference bases do).
 --calmd_in (not the reference's) recomputes NM and MD of the input BAM the same way first, into a temporary BAM: an input whose records lack NM
 stops the run with GCE_ERR_NM_MISSING otherwise.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
@@ -82,7 +83,8 @@ def build_parser():
     a("--devices", default="0", help="[gencore_amd] HIP device ordinals, comma separated: one runs one engine, several run the sharded runner "
                                      "(an ordinal may repeat). Default 0.")
     a("--device_memory", default="auto", help="[gencore_amd] device memory budget in GB (2^30 bytes) for one device, or auto (a fraction of the free "
-                                               "memory): a file larger than the budget is processed in key-range passes, and sorted (--sort) in output-range passes. One device only. "
+                                               "memory): a file larger than the budget is processed in key-range passes, sorted (--sort) in output-range passes, and --calmd / --calmd_in "
+                                               "keep to the budget by writing their output as they go. One device only. "
                                                "Default auto.")
     a("--threads", type=int, default=0, help="[gencore_amd] host threads for the file codecs; 0 = all cores. Default 0.")
     a("--index", action="store_true", help="[gencore_amd] after the output and the report are written, index the BAM output on the GPU into "
@@ -92,11 +94,12 @@ def build_parser():
     a("--sort_sam", action="store_true", help="[gencore_amd] the input is SAM text that is not coordinate-sorted: parse and sort it on the GPU first (on the first of "
                                                "--devices, into a temporary BAM beside the output that is removed afterwards), then run on the sorted file. Off by default.")
     a("--calmd", action="store_true", help="[gencore_amd] after the output and the report are written (and before --index), recompute NM and MD of every record of "
-                                            "the BAM output against -r on the GPU (on the first of --devices, at --level, within --device_memory), through a temporary file beside "
-                                            "the output that is renamed over it. The report is not changed by it. Off by default.")
+                                            "the BAM output against -r on the GPU (on the first of --devices, at --level), through a temporary file beside "
+                                            "the output that is renamed over it. It honours the --device_memory budget: an output beyond it is written as it is "
+                                            "made. The report is not changed by it. Off by default.")
     a("--calmd_in", action="store_true", help="[gencore_amd] recompute NM and MD of the input BAM against -r on the GPU first (after --sort / --sort_sam; on the first of --devices, "
                                                "into a temporary BAM beside the output that is removed afterwards), then run on that file: an input without NM "
-                                               "becomes runnable. Off by default.")
+                                               "becomes runnable. It honours the --device_memory budget as --calmd does. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -214,7 +217,7 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import calmd_bam, index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam
+    from .bamio import calmd_bam_stream, index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = calmd_tmp = out_tmp = None
@@ -231,7 +234,7 @@ def main(argv=None):
             import tempfile
             fd, calmd_tmp = tempfile.mkstemp(suffix=".bam", prefix="gencore_calmd_", dir=tmp_dir)
             os.close(fd)
-            calmd_bam(o.input, calmd_tmp, o.ref, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
+            calmd_bam_stream(o.input, calmd_tmp, o.ref, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
             o.input = calmd_tmp
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
@@ -248,7 +251,7 @@ def main(argv=None):
         write_json(o.json, depth, names, o.coverage_sampling, command, region_names=region_names, has_bed=bool(o.bed))
         if o.calmd:
             out_tmp = o.output + ".calmd%d" % os.getpid()
-            r = calmd_bam(o.output, out_tmp, o.ref, device=devices[0], threads=o.threads, level=o.level, device_budget_bytes=o.device_memory_bytes)
+            r = calmd_bam_stream(o.output, out_tmp, o.ref, device=devices[0], threads=o.threads, level=o.level, device_budget_bytes=o.device_memory_bytes)
             os.replace(out_tmp, o.output)
             sys.stderr.write("calmd: %d records rewritten, NM changed in %d, MD changed in %d\n" % (r.n_rewritten, r.n_nm_changed, r.n_md_changed))
         if o.index:

@@ -246,6 +246,58 @@ static int calmd_counters_init(gce_sort *b) {
     return GCE_OK;
 }
 
+// ---- the output streamed (gce_bam_calmd_stream): the resident output is capped, whole members of 0xff00 bytes leave before the last window
+// flush(ctx, n): the caller writes the first n resident bytes (gce_sort_read) and lets them go (gce_sort_calmd_consume)
+typedef int (*calmd_flush_fn)(void *ctx, uint64_t n);
+
+// the deflate buffers of the largest piece of the first n resident bytes, before they are first needed (gce_sort_read makes none).  Buffers
+// that suffice stay; others are let go before the budget is asked, so that they are not counted beside their successors.  ahead: size them
+// for a piece of the cap as well, so that later flushes find them made.
+static int calmd_stream_zbufs(gce_sort *b, uint64_t n, bool ahead) {
+    if (b->cm_codes < 0 || !b->cm_piece || !n) return GCE_OK;
+    const uint64_t need = (std::min<uint64_t>(b->cm_piece, n) + 0xff00u - 1) / 0xff00u;
+    if (need * sort_slot() + 64 <= b->zs.cap && need * sort_slot() + 64 <= b->zo.cap && (need + 1) * 4 <= b->zz.cap && (need + 1) * 8 <= b->zf.cap) return GCE_OK;
+    for (DevBuf *x : {&b->zs, &b->zz, &b->zf, &b->zo}) x->release();
+    return sort_deflate_bufs(b, std::min<uint64_t>(b->cm_piece, ahead ? std::max<uint64_t>(n, b->cm_cap) : n));
+}
+// room for a window's wtotal output bytes behind the resident ones, `target` the size a new buffer should have: the cap R is derived from the
+// budget on first use; when the window would pass it (or the buffer cannot grow within the budget) the whole members resident so far are
+// flushed and the tail below 0xff00 bytes moves to the front.  One window's output always fits beside the tail, or GCE_ERR_OOM.
+static int calmd_stream_room(gce_sort *b, uint64_t wtotal, uint64_t target, calmd_flush_fn flush, void *ctx) {
+    const uint64_t M = 0xff00u, slack = 65536;                                        // (slack: the scans' scratch, allocator rounding)
+    hipStream_t s = b->s;
+    if (!b->cm_cap) {                                                                 // what the budget leaves now, beside the deflate buffers of one piece
+        // (held back: as much again as the window holds, for a later window that inflates to more and has to grow)
+        const uint64_t live = (uint64_t)std::max<long long>(__atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), 0) + sort_win_need(b->w, b->tmp) + slack;
+        const uint64_t avail = b->budget > live ? b->budget - live : 0;
+        uint64_t R = avail;
+        if (b->cm_codes >= 0 && b->cm_piece) { const uint64_t dp = sort_deflate_need(b->cm_piece / M); R = avail > dp + b->cm_piece ? avail - dp : avail / 18 * 5; }
+        b->cm_cap = b->budget ? std::max<uint64_t>(R / M * M, M) : ~0ull / M * M;
+    }
+    auto want_of = [&]() { return std::max<uint64_t>(b->out_n + wtotal + 64, std::min<uint64_t>(target, b->cm_cap + 64)) + 256; };
+    auto grows = [&]() { return !(b->out_n + wtotal + 64 <= b->out.cap && b->out.p); };
+    if (b->out_n >= M && flush && (b->out_n + wtotal > b->cm_cap || (grows() && !sort_room(b, want_of())))) {
+        const uint64_t n = b->out_n / M * M;
+        int rc;
+        if ((rc = calmd_stream_zbufs(b, n, true)) != GCE_OK || (rc = flush(ctx, n)) != GCE_OK) return rc;
+        if (b->out_n >= M) return sfail(b, GCE_ERR_INVALID, "calmd: the flushed bytes were not consumed");
+    }
+    if (!grows()) return GCE_OK;
+    const uint64_t want = want_of();
+    if (b->out.p && b->out_n < M && !sort_room(b, want)) {
+        // the old buffer and the new one do not fit side by side: the tail waits in host memory while the buffer is made anew
+        std::vector<uint8_t> tail((size_t)b->out_n);
+        if (b->out_n) { SCHK(hipMemcpyAsync(tail.data(), b->out.p, (size_t)b->out_n, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); }
+        b->out.release();
+        if (!sort_room(b, want)) return sort_oom(b, "one window's output record bytes", want);
+        const int rc = sort_grow(b, b->out, (size_t)(b->out_n + wtotal + 64), 0, (size_t)(want - 256), "one window's output record bytes");
+        if (rc != GCE_OK) return rc;
+        if (b->out_n) { SCHK(hipMemcpyAsync(b->out.p, tail.data(), (size_t)b->out_n, hipMemcpyHostToDevice, s)); SCHK(hipStreamSynchronize(s)); }
+        return GCE_OK;
+    }
+    return sort_grow(b, b->out, (size_t)(b->out_n + wtotal + 64), (size_t)b->out_n, (size_t)(want - 256), "the output record bytes");
+}
+
 }  // namespace
 
 extern "C" {
@@ -276,8 +328,8 @@ int gce_sort_calmd_ref(gce_sort *b, int32_t n_ref, const char *const *seq, const
 // the next piece of the file, as gce_sort_window takes it: its whole records are rewritten (rules E, W, T) behind the resident output.
 // est_bytes: the caller's estimate of the file's inflated bytes; *calmd_s: the seconds of the calmd kernels and their scan, added to.
 // GCE_ERR_INVALID names the lowest record whose optional fields do not tile its block_size, counting from 0 over the file.
-int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
-                          int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s) {
+static int calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, calmd_flush_fn flush, void *ctx) {
     if (!b || !b->calmd || !b->cm_tab.p || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
@@ -311,8 +363,15 @@ int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int3
             char m[256]; snprintf(m, sizeof m, "BAM record %llu (counting from 0): its optional fields do not tile its block_size, or its new MD would take it beyond 2^28 bytes", bad);
             return sfail(b, GCE_ERR_INVALID, m);
         }
-        const uint64_t start = std::min<uint64_t>(skip, total), in1 = b->cm_in + (end - start), have = b->out_n + wtotal;
-        const uint64_t eo = (uint64_t)((double)std::max<uint64_t>(est_bytes, in1) * ((double)have / (double)in1));    // the file's output bytes at the growth seen so far
+        const uint64_t start = std::min<uint64_t>(skip, total), in1 = b->cm_in + (end - start), seen = b->cm_flushed + b->out_n + wtotal;
+        const uint64_t eo = (uint64_t)((double)std::max<uint64_t>(est_bytes, in1) * ((double)seen / (double)in1));    // the file's output bytes at the growth seen so far
+        double fl = 0;
+        if (b->cm_stream) {                                                           // (a flush is the caller's write_s, not calmd_s)
+            const double f0 = mono_s();
+            if ((rc = calmd_stream_room(b, wtotal, eo + eo / 16 + 64, flush, ctx)) != GCE_OK) return rc;
+            fl = mono_s() - f0;
+        }
+        const uint64_t have = b->out_n + wtotal;
         if ((rc = sort_grow(b, b->out, (size_t)(have + 64), (size_t)b->out_n, (size_t)(eo + eo / 16 + 64), "the output record bytes")) != GCE_OK) return rc;
         uint8_t *out = b->out.as<uint8_t>() + b->out_n;
         hipLaunchKernelGGL(k_md_tags, dim3(nb), dim3(256), 0, s, u, off, n_rec, end, ref, (const uint32_t *)b->cm_size.p, (const calmd::Meta *)b->cm_meta.p, (const uint64_t *)b->cm_dst.p, out);
@@ -320,11 +379,51 @@ int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int3
                            (const uint64_t *)b->cm_dst.p, out);
         SCHK(hipGetLastError()); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
         b->out_n = have; b->n += n_rec; b->cm_in = in1;
-        if (calmd_s) *calmd_s += mono_s() - t0;
+        if (calmd_s) *calmd_s += mono_s() - t0 - fl;
     }
     rc = win_carry(b->w, s, total, end, b->err);
     b->win_need = std::max(b->win_need, sort_win_need(b->w, b->tmp));
     return rc;
+}
+int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                          int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s) {
+    if (b && b->cm_stream) return GCE_ERR_INVALID;
+    return calmd_window(b, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, est_bytes, calmd_s, nullptr, nullptr);
+}
+
+// ---- the output streamed (gce_bam_calmd_stream).  On a new object, before gce_sort_calmd_ref: the object caps its resident output
+// at resident_bytes (a multiple of 0xff00; 0: what the budget leaves beside the reference bases + one window + 40 bytes per window record +
+// one piece's deflate buffers, found when the first window's records are known).  codes / piece_bytes: as gce_sort_calmd_finish takes them.
+int gce_sort_calmd_stream_begin(gce_sort *b, int32_t codes, uint64_t piece_bytes, uint64_t resident_bytes) {
+    if (!b || b->calmd || b->cm_stream || b->passes || b->sam_text || b->n || b->out_n || codes > 1 || resident_bytes % 0xff00u || piece_bytes % 0xff00u) return GCE_ERR_INVALID;
+    b->cm_stream = true; b->cm_codes = codes; b->cm_piece = piece_bytes; b->cm_cap = resident_bytes;
+    return GCE_OK;
+}
+// gce_sort_calmd_window with the cap: when the window's output would pass it, flush(ctx, n) is called once, before the window's records are
+// emitted, with n = floor(resident bytes / 0xff00) * 0xff00 > 0: the caller reads [0, n) with gce_sort_read (the deflate buffers exist) and
+// then calls gce_sort_calmd_consume(b, n); what it returns other than GCE_OK ends the window.
+int gce_sort_calmd_stream_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                                 int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, int (*flush)(void *ctx, uint64_t n), void *ctx) {
+    if (!b || !b->cm_stream || !flush) return GCE_ERR_INVALID;
+    return calmd_window(b, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, est_bytes, calmd_s, flush, ctx);
+}
+// the first n bytes of the resident output are let go and the tail moves to the front.  n: a multiple of 0xff00 and at least the tail's
+// length, so that source and destination do not overlap: one device-to-device copy on the object's stream does it.
+int gce_sort_calmd_consume(gce_sort *b, uint64_t n) {
+    if (!b || !b->cm_stream || n % 0xff00u || n > b->out_n || (n && b->out_n - n > n)) return GCE_ERR_INVALID;
+    if (!n) return GCE_OK;
+    (void)hipSetDevice(b->device);
+    const uint64_t tail = b->out_n - n;
+    if (tail) SCHK(hipMemcpyAsync(b->out.p, b->out.as<uint8_t>() + n, (size_t)tail, hipMemcpyDeviceToDevice, b->s));
+    SCHK(hipStreamSynchronize(b->s)); SCHK(hipGetLastError());
+    b->out_n = tail; b->cm_flushes++; b->cm_flushed += n;
+    return GCE_OK;
+}
+// what a streamed run did so far: the flushes, the cap (0: no window had records yet and none was given), the bytes flushed
+int gce_sort_calmd_stream_stats(gce_sort *b, int32_t *n_flushes, uint64_t *resident_cap_bytes, uint64_t *flushed_bytes) {
+    if (!b || !b->cm_stream || !n_flushes || !resident_cap_bytes || !flushed_bytes) return GCE_ERR_INVALID;
+    *n_flushes = b->cm_flushes; *resident_cap_bytes = b->cm_cap; *flushed_bytes = b->cm_flushed;
+    return GCE_OK;
 }
 
 // after the last window: the window, the reference and the descriptions are let go; counts: records, rewritten, unchanged, contig missing,
@@ -345,6 +444,7 @@ int gce_sort_calmd_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int6
     counts[0] = (int64_t)b->n; counts[1] = (int64_t)h[1]; counts[2] = (int64_t)(b->n - h[1]); counts[3] = (int64_t)h[2]; counts[4] = (int64_t)h[3]; counts[5] = (int64_t)h[4];
     SCHK(hipMemsetAsync(b->out.as<uint8_t>() + b->out_n, 0, 64, s));                  // (the deflate kernels may look a few bytes ahead)
     SCHK(hipStreamSynchronize(s));
+    if (b->cm_stream) return calmd_stream_zbufs(b, b->out_n, false);                  // (the buffers of the flushes are live: not counted twice)
     if (codes >= 0 && piece_bytes) return sort_deflate_bufs(b, std::min<uint64_t>(piece_bytes, b->out_n));
     return GCE_OK;
 }

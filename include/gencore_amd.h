@@ -676,6 +676,33 @@ typedef struct gce_calmd_run {
 } gce_calmd_run;
 int gce_bam_calmd(const char *in_path, const char *out_path, const char *fasta_path, int32_t device, int threads, int level,
                   uint64_t window_bytes, size_t device_budget_bytes, gce_calmd_run *out, char err[256]);
+/* gce_bam_calmd for a file whose rewritten records do not fit the device: the same file, byte for byte, at every level, with the output
+ * streamed (addition under ABI v3; gencore_amd/csrc/gce_calmd.hpp).  calmd never reorders records, so the file is still read
+ * once; the temporary output is open before the first window, and whenever a window's output (known after k_md_size and its scan) would take
+ * the resident output record bytes past the cap R, the whole members resident so far -- floor(resident / 0xff00) * 0xff00 bytes -- are deflated
+ * and written as gce_bam_calmd writes its pieces, and the tail below 0xff00 bytes (which may begin inside a record) moves to the front of the
+ * buffer before the window's records are emitted behind it.  Rule F cuts the record stream into members of 0xff00 input bytes and every member
+ * is deflated on its own (host zlib, the host's fixed codes, one GPU lane per member at -2 and -3), so the file does not depend on where the
+ * stream was cut.  After the last window the rest is written with the last short member, then the EOF marker and the rename.
+ * device_budget_bytes: 0 = auto, GCE_PASS_BUDGET_FRACTION of the device's free memory when the call starts, as in gce_bam_sort_passes; it is
+ * checked before every growth and out->peak_device_bytes never exceeds an explicit budget.  resident_bytes: 0 = R is what the budget leaves
+ * beside the reference bases and their table, one window (and as much again held back for a larger window to come), 40 bytes per window
+ * record and the deflate buffers of one piece, found when the first window with records is known; otherwise R is resident_bytes rounded up
+ * to a multiple of 0xff00 (how a test forces flushes on a small file).  One window's output always fits beside the tail: the buffer grows
+ * to tail + that window's output when the budget allows.  Device memory: the reference bases + one window + 40 bytes per window record +
+ * one piece's deflate buffers + at least one window's output; the reference bases stay whole (3.1 GB at hg19).  GCE_ERR_OOM, with a
+ * message that states this footprint, when the budget cannot hold it.  A failed call leaves neither an output nor a temporary file and never
+ * touches the input, at any point: also for a malformed record found after several flushes were written.  The refusals, the counters in
+ * *out and rule C: gce_bam_calmd's, in its words, with gce_bam_calmd_stream where the entry point is named ("gce_bam_calmd_stream reads BAM,
+ * not SAM text").  out->write_s holds the flushes; out->inflate_index_s and out->calmd_s do not. */
+typedef struct gce_calmd_stream_run {
+    int32_t n_flushes, pad;          /* times resident output was written before the final one; 0: nothing left the device before the last window */
+    int64_t resident_cap_bytes;      /* the cap R on resident output record bytes that the call worked with (0: auto and no window had records) */
+    int64_t flushed_bytes;           /* record bytes written by those n_flushes flushes: a multiple of 0xff00 */
+} gce_calmd_stream_run;
+int gce_bam_calmd_stream(const char *in_path, const char *out_path, const char *fasta_path, int32_t device, int threads, int level,
+                         uint64_t window_bytes, size_t device_budget_bytes, uint64_t resident_bytes,
+                         gce_calmd_run *out, gce_calmd_stream_run *run, char err[256]);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

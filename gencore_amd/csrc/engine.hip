@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "gce_entry.h"
 #include "gce_kernels.hpp"
 #include "gce_pair2.hpp"
 #include "gce_vote.hpp"

@@ -1,0 +1,74 @@
+// gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
+// declare: the pass, index, sort and calmd objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp and gce_calmd.hpp.  They are exported, but
+// internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
+// file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
+// succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
+#ifndef GCE_ENTRY_H
+#define GCE_ENTRY_H
+#include <stddef.h>
+#include <stdint.h>
+#include "../../include/gencore_amd.h"
+
+extern "C" {
+
+struct gce_passes;
+struct gce_bai;
+struct gce_sort;
+
+int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
+
+// ---- one file in key-range passes on one device (gce_passes.hpp)
+int gce_passes_create(int32_t device, int32_t max_contig, int32_t flush_period, gce_passes **out);
+void gce_passes_destroy(gce_passes *p);
+const char *gce_passes_error(gce_passes *p);
+int gce_passes_window(gce_passes *p, gce_engine *e, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize,
+                      uint64_t skip, int32_t n_ref, int32_t last, int32_t *cut_reached);
+int gce_passes_plan(gce_passes *p, int32_t min_passes, uint64_t budget, uint64_t reserve, int32_t *P_out, uint64_t *total_w, uint64_t *per_pass, uint64_t *fixed_out);
+int gce_passes_info(gce_passes *p, int32_t k, uint64_t *weight, const uint64_t **cuts, int32_t *n_events, const int32_t **ev_tid, const int32_t **ev_pos);
+int gce_passes_begin(gce_passes *p, gce_engine *e, int32_t k);
+int gce_passes_end(gce_passes *p, gce_engine *e, uint64_t records_begin, int32_t n_ref, int64_t *n_records, int32_t *watermark_tid, int32_t *watermark_pos);
+int gce_passes_output(gce_passes *p, gce_engine *e, void *keys_host, void *body_host);
+int gce_passes_release(gce_passes *p, gce_engine *e);
+
+// ---- the BAI index of a coordinate-sorted BAM (gce_bai.hpp)
+int gce_bai_create(int32_t device, gce_bai **out);
+void gce_bai_destroy(gce_bai *b);
+const char *gce_bai_error(gce_bai *b);
+int gce_bai_window(gce_bai *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t file_base,
+                   uint64_t skip, int32_t n_ref, int32_t last);
+int gce_bai_finish(gce_bai *b, int32_t n_ref, uint64_t eod, int64_t counts[5], int64_t *bad_rec, int32_t *bad_kind);
+int gce_bai_serialise(gce_bai *b, int32_t n_ref, uint8_t **out, size_t *out_bytes);
+
+// ---- an unsorted BAM, or SAM text, into coordinate order (gce_sort.hpp)
+int gce_sort_create(int32_t device, size_t device_budget_bytes, gce_sort **out);
+void gce_sort_destroy(gce_sort *b);
+const char *gce_sort_error(gce_sort *b);
+int gce_sort_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                    int32_t n_ref, int32_t last, uint64_t est_bytes);
+int gce_sort_finish(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int64_t counts[3], int64_t *bad_rec, uint64_t *out_bytes, double times[2]);
+int gce_sort_read(gce_sort *b, uint64_t offset, size_t bytes, int32_t codes, void *host, size_t host_cap, size_t *got);
+int gce_sort_key_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, uint64_t est_bytes);
+int gce_sort_plan(gce_sort *b, int32_t n_ref, int32_t codes, uint64_t piece_bytes, int32_t min_passes, int64_t counts[3], int64_t *bad_rec, uint64_t *total_out, int32_t *n_passes,
+                  uint64_t *pass_bytes, uint64_t *resident, double *plan_s);
+int gce_sort_pass_begin(gce_sort *b, uint64_t lo, uint64_t hi);
+int gce_sort_pass_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                         int32_t n_ref, int32_t last);
+int gce_sort_pass_end(gce_sort *b, double *scatter_s);
+int gce_sort_sam_contigs(gce_sort *b, int32_t n_ref, const char *const *ref_name);
+int gce_sort_sam_window(gce_sort *b, const char *text, size_t n, int32_t n_ref, uint64_t est_bytes, int64_t *n_host_lines, int64_t *bad_line, uint64_t *bad_start, double *parse_s,
+                        uint64_t *resident_bytes);
+
+// ---- NM and MD recomputed against the reference, in core and with the output streamed (gce_calmd.hpp)
+int gce_sort_calmd_ref(gce_sort *b, int32_t n_ref, const char *const *seq, const int64_t *len);
+int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                          int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s);
+int gce_sort_calmd_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int64_t counts[6], uint64_t *in_bytes, uint64_t *out_bytes);
+int gce_sort_calmd_stream_begin(gce_sort *b, int32_t codes, uint64_t piece_bytes, uint64_t resident_bytes);
+int gce_sort_calmd_stream_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                                 int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, int (*flush)(void *ctx, uint64_t n), void *ctx);
+int gce_sort_calmd_consume(gce_sort *b, uint64_t n);
+int gce_sort_calmd_stream_stats(gce_sort *b, int32_t *n_flushes, uint64_t *resident_cap_bytes, uint64_t *flushed_bytes);
+
+}  // extern "C"
+#endif

@@ -357,7 +357,7 @@ def bgzf_members(blob):
 
 
 def pass_windows(blob, window_bytes, hdr_end, n_ref):
-    """One read of a BAM file by the pass runner (gce_run_bam_passes: PassReader::members_next pieces of `window_bytes` compressed bytes,
+    """One read of a BAM file by the pass runner (gce_run_bam_passes, bamio_passes.hpp: PassReader::members_next of bamio_reader.hpp, pieces of `window_bytes` compressed bytes,
     gce_passes_window on each): (the windows' indexes summed as counters, the record starts (offsets in the inflated stream), an error or
     None, the number of windows whose end cut a record)."""
     import zlib

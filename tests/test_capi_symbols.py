@@ -25,6 +25,38 @@ def test_header_symbols_exported(built):
     assert lib.gce_abi_version() == capi.GCE_ABI_VERSION
 
 
+def entry_functions():
+    txt = open(os.path.join(ROOT, "gencore_amd", "csrc", "gce_entry.h")).read()
+    txt = re.sub(r"//[^\n]*", "", txt)
+    return sorted(set(re.findall(r"\b(gce_[a-z_0-9]+)\s*\(", txt)))
+
+
+def test_internal_entry_points_declared_once(built):
+    """gce_entry.h declares the device entry points the file side calls beside the public header's: every one is exported, none is also in
+    the public header, and the file side (csrc/*.cpp and its bamio_*.hpp parts) holds no gce_ prototype of its own -- no file-scope
+    declaration of a gce_ function that ends in `;` -- so the definitions in engine.hip and the calls see one prototype each."""
+    import glob
+    from gencore_amd import capi
+    lib = capi.load_library()
+    names = entry_functions()
+    assert len(names) > 30 and "gce_sort_read" in names and "gce_passes_window" in names and "gce_bai_finish" in names and "gce_device_mem_info" in names
+    for n in names:
+        assert hasattr(lib, n), n
+    assert not set(names) & set(declared_functions())
+    csrc = os.path.join(ROOT, "gencore_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "bamio_*.hpp")))
+    assert [os.path.basename(f) for f in files if f.endswith(".cpp")] == ["bamio.cpp"] and len(files) >= 9
+    # a prototype: from the start of a line a return type, the name, a parameter list without braces or semicolons, then `;` -- a call
+    # starts indented or behind `=`, `(` or `return`, and a definition's parameter list is followed by `{`
+    proto = re.compile(r"^(?:extern\s+\"C\"\s+)?(?:static\s+|inline\s+)*(?:const\s+)?[A-Za-z_][A-Za-z_0-9]*[\s\*]+(gce_[a-z_0-9]+)\s*\([^;{}]*\)\s*;", re.M)
+    assert proto.search("int gce_sort_read(gce_sort *b, uint64_t offset,\n                  size_t bytes);").group(1) == "gce_sort_read"
+    assert proto.search("const char *gce_bai_error(gce_bai *b);") and proto.search("void gce_host_free(void *p);")
+    assert not proto.search("int gce_x(int a) { return a; }\n    if (gce_y(1)) return gce_z(2);\nint r = gce_w(3);")
+    for f in files:
+        txt = re.sub(r"//[^\n]*", "", open(f).read())
+        assert not proto.findall(txt), (os.path.basename(f), proto.findall(txt))
+
+
 def test_index_counters_symbol(built):
     """gce_get_index_counters (ABI v3) is exported, refuses a NULL output and, with no engine, reads the pass runner's window totals (no GPU
     call: this runs without a device)."""

@@ -1,8 +1,11 @@
-"""What each file-to-file runner says about a file whose BGZF framing or BAM header is damaged (gencore_amd/csrc/bamio.cpp: the member
-scanner and header parser of gce_bgzf.hpp under gce_run_bam, gce_run_bam_passes, gce_bam_index, gce_bam_sort and gce_bam_sort_passes).
+"""What each file-to-file runner says about a file whose BGZF framing or BAM header is damaged (the parts of gencore_amd/csrc/bamio.cpp: the
+member scanner and header parser of gce_bgzf.hpp and the reader of bamio_reader.hpp under gce_run_bam (bamio_run.hpp), gce_run_bam_passes
+(bamio_passes.hpp), gce_bam_index (bamio_index.hpp), gce_bam_sort and gce_bam_sort_passes (bamio_sort.hpp), gce_bam_calmd and
+gce_bam_calmd_stream (bamio_calmd.hpp)).
 Every damage here is one the host's framing check rejects before a damaged member reaches a kernel: where members do go to the GPU (a file
 cut inside its EOF member) they are whole and well-formed.  The table holds status and message of every (runner, damage) pair, read off
-each runner's own copy of the framing code as it stood before that code was shared; the messages are compared whole."""
+each runner's own copy of the framing code as it stood before that code was shared; the messages are compared whole.  The two calmd
+columns were recorded by running them against the library as it stood before bamio.cpp was split into its parts."""
 import struct
 
 import numpy as np
@@ -37,11 +40,30 @@ TABLE = {
                               (INVALID, "truncated BAM header")],
     "window_below_a_member": [None, (INVALID, WINDOW), (INVALID, WINDOW), (INVALID, WINDOW), (INVALID, WINDOW)],
 }
+# the same rows for the two calmd runners, which open their input as the sort runners do
+CALMD_RUNNERS = ("calmd", "calmd_stream")
+CALMD_TABLE = {
+    "cut_in_last_member": [(INVALID, CUT)] * 2,
+    "cut_in_header_member": [(INVALID, CUT)] * 2,
+    "magic_of_second_member": [(INVALID, NOT_BGZF)] * 2,
+    "bc_missing": [(INVALID, BAD)] * 2,
+    "isize_above_64k": [(INVALID, BAD_ISIZE)] * 2,
+    "not_bam": [(INVALID, NOT_BAM)] * 2,
+    "stream_ends_in_header": [(INVALID, "truncated BAM header")] * 2,
+    "window_below_a_member": [(INVALID, WINDOW)] * 2,
+}
+assert sorted(CALMD_TABLE) == sorted(TABLE)
+ALL_RUNNERS = RUNNERS + CALMD_RUNNERS
+
+
+def expected(runner, damage):
+    return TABLE[damage][RUNNERS.index(runner)] if runner in RUNNERS else CALMD_TABLE[damage][CALMD_RUNNERS.index(runner)]
 
 
 @pytest.fixture(scope="module")
-def parts():
-    """the members of a small sorted BAM: the header in a member of its own, a dozen records in two members, the EOF marker"""
+def parts(tmp_path_factory):
+    """the members of a small sorted BAM: the header in a member of its own, a dozen records in two members, the EOF marker; a FASTA of the
+    two contigs for the calmd runners"""
     from gencore_amd import synth
     from test_bamio import records_of
     d = synth.generate("cfg1s", n_pairs=7)
@@ -50,7 +72,14 @@ def parts():
     hdr = b"BAM\1" + struct.pack("<i", len(TEXT)) + TEXT.encode() + struct.pack("<i", len(TARGETS))
     for nm, ln in TARGETS:
         hdr += struct.pack("<i", len(nm) + 1) + nm.encode() + b"\0" + struct.pack("<i", ln)
-    return dict(d=d, hdr=hdr, members=[pybam.bgzf_block(hdr), pybam.bgzf_block(b"".join(recs[:6])), pybam.bgzf_block(b"".join(recs[6:])), pybam.EOF_BLOCK])
+    fasta = tmp_path_factory.mktemp("framing") / "ref.fa"
+    rng = np.random.default_rng(7)
+    with open(fasta, "w") as f:
+        for nm, ln in TARGETS:
+            f.write(">%s\n" % nm)
+            seq = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, ln)].tobytes().decode()
+            f.write("\n".join(seq[k:k + 60] for k in range(0, ln, 60)) + "\n")
+    return dict(d=d, hdr=hdr, fasta=str(fasta), members=[pybam.bgzf_block(hdr), pybam.bgzf_block(b"".join(recs[:6])), pybam.bgzf_block(b"".join(recs[6:])), pybam.EOF_BLOCK])
 
 
 def damaged(parts, damage):
@@ -91,7 +120,12 @@ def call(runner, parts, src, out, window):
         return bamio.index_bam(src, out, threads=2, window_bytes=window)
     if runner == "sort_bam":
         return bamio.sort_bam(src, out, threads=2, level=1, window_bytes=window)
-    return bamio.sort_bam_passes(src, out, threads=2, level=1, window_bytes=window, min_passes=2)
+    if runner == "sort_bam_passes":
+        return bamio.sort_bam_passes(src, out, threads=2, level=1, window_bytes=window, min_passes=2)
+    if runner == "calmd":
+        return bamio.calmd_bam(src, out, parts["fasta"], threads=2, level=1, window_bytes=window)
+    assert runner == "calmd_stream"
+    return bamio.calmd_bam_stream(src, out, parts["fasta"], threads=2, level=1, window_bytes=window)
 
 
 def test_the_damages_are_what_they_say(parts):
@@ -107,10 +141,10 @@ def test_the_damages_are_what_they_say(parts):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("runner,damage", [(r, d) for d in sorted(TABLE) for k, r in enumerate(RUNNERS) if TABLE[d][k] is not None])
+@pytest.mark.parametrize("runner,damage", [(r, d) for d in sorted(TABLE) for r in ALL_RUNNERS if expected(r, d) is not None])
 def test_runner_message(built, parts, tmp_path, runner, damage):
     from gencore_amd.capi import GceError
-    want = TABLE[damage][RUNNERS.index(runner)]
+    want = expected(runner, damage)
     blob, window = damaged(parts, damage)
     src, out = str(tmp_path / "in.bam"), str(tmp_path / ("out.bai" if runner == "bam_index" else "out.bam"))
     with open(src, "wb") as f:

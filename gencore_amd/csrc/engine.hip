@@ -13,6 +13,7 @@
 
 #include "gce_entry.h"
 #include "gce_kernels.hpp"
+#include "gce_params.hpp"
 #include "gce_pair2.hpp"
 #include "gce_vote.hpp"
 #include "gce_deep.hpp"
@@ -51,6 +52,8 @@ struct DevBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 struct ScopedBuf : DevBuf { ~ScopedBuf() { release(); } };                            // the device buffers of one call
+// ensure, then the typed pointer: one statement per buffer, so no pointer is taken in front of the ensure that may move it
+template <class T> inline hipError_t ensure_as(DevBuf &d, T *&dst, size_t bytes) { const hipError_t r = d.ensure(bytes); dst = d.as<T>(); return r; }
 
 enum { EV_START = 0, EV_CLUSTER, EV_CSR, EV_DESCRIBE, EV_PAIRING, EV_SCORE, EV_CONSENSUS, EV_FINISH, EV_OUTPUT, EV_COUNT };
 
@@ -660,264 +663,226 @@ int gce_process(gce_engine *e) {
             (double)(t_alloc_bytes - b0) / 1e9, e ? e->timing.total_ms : 0.0);
     return rc;
 }
-static int gce_process_impl(gce_engine *e) {
-    if (!e) return GCE_ERR_INVALID;
-    if (!e->host_mode && !e->device_mode) return fail(e, GCE_ERR_INVALID, "nothing submitted");
-    if (e->processed) return fail(e, GCE_ERR_INVALID, "gce_process called twice without a new submit (the stream was mutated in place)");
-    if (e->have_tick && !e->have_events) return fail(e, GCE_ERR_INVALID, "gce_batch.tick needs gce_set_flush_events");
-    (void)hipSetDevice(e->prm.device);
-    int rc;
-    if (e->host_mode && (rc = upload(e)) != GCE_OK) return rc;
-    const gce_batch &hb = e->dev_batch;
-    int64_t N = hb.n_reads;
+// One gce_process call: what its stages share.  gce_process_impl (below) is the list of the stages.
+// Every work buffer gets its Work / OutTable pointer where it is sized (TAKE): no pointer is taken in front of the ensure that may move the buffer.
+#define TAKE(buf, dst, bytes) HIPCHK(ensure_as(e->buf, dst, bytes))
+namespace {
+struct Step {
+    gce_engine *const e; const hipStream_t s; const gce_batch &hb;
+    DevBatch b{}; DevParams p{}; Work w{}; OutTable o{};
+    int64_t N = 0; size_t n1 = 1; uint32_t C = 0, NG = 0;
     PreExtra pre_extra{};
-    e->n_pre = N;
-    if (e->prm.max_contig > 0 && N > 0 && !e->shard_cut_done) {                    // src/gencore.cpp:243-246: the loop ends on the first read of contig >= maxContig
-        HIPCHK(e->si.ensure(sizeof(StreamInfo)));
-        unsigned int first = NONE32;
-        HIPCHK(hipMemcpyAsync(e->si.p, &first, 4, hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(k_first_contig_ge, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, hb.core, N, e->prm.max_contig, (unsigned int *)e->si.p);
-        HIPCHK(hipMemcpyAsync(&first, e->si.p, 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (first != NONE32) {
-            gce_core c2; int32_t nm = 0; uint8_t nmt = 0;                            // (the sorted check of :233-241 cannot fail on this read: every read in front has a smaller tid)
-            HIPCHK(hipMemcpy(&c2, hb.core + first, sizeof(gce_core), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(&nm, hb.nm + first, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nmt, hb.nm_type + first, 1, hipMemcpyDeviceToHost));
-            const int mism = nmt != 0 ? nm : 0;                                     // Stats::addRead (stats.cpp:101-121): the read is mapped (tid >= maxContig > 0)
-            pre_extra.v[0] = 1; pre_extra.v[1] = c2.l_qseq; pre_extra.v[4] = mism; pre_extra.v[5] = mism > 0;
-            N = (int64_t)first; e->n_pre = N + 1;
-        }
-    }
-    e->n = N; e->n_out = 0; e->out_seq_bytes = e->out_qual_bytes = 0; e->dev_error = 0; e->dev_error_read = 0;
-    e->processed = true;
-    memset(&e->timing, 0, sizeof e->timing);
-    memset(&e->h_si, 0, sizeof e->h_si);
-    if (N >= (int64_t)0xFFFFFC00ll) return fail(e, GCE_ERR_INVALID, "more than 2^32 reads in one engine");
-    // k_vote's batches come from ONE scan of packed words, weight prefix in the low half and live rank in the high half (k_group_fill, k_vote_batches): a weight sum of
-    // 2^32 would carry into the ranks.  The sum is at most (VB_MINW + 3) x reads (vb_start's bound below), so such a stream is refused here (it would need > 100 GB of
-    // descriptors and pair slots alone; the 32-bit weight prefixes of earlier versions wrapped at the same sum)
-    if ((uint64_t)(VB_MINW + 3) * (uint64_t)(N > 0 ? N : 0) >= (1ull << 32)) return fail(e, GCE_ERR_INVALID, "too many reads in one engine for the batch scan of k_vote (weight sum >= 2^32)");
-    const size_t n1 = (size_t)(N > 0 ? N : 1);
+    int64_t n_sblk = 0, max_events = 0; unsigned nblk_N = 0;
+    bool si_behind_describe = false;               // the host's copy of StreamInfo holds what k_describe found (read-length range)
+    explicit Step(gce_engine *e_) : e(e_), s(e_->stream), hb(e_->dev_batch) {}
 
-    DevBatch b{}; b.n = N; b.core = hb.core; b.qname_off = hb.qname_off; b.qname = hb.qname; b.cigar_off = hb.cigar_off; b.cigar = hb.cigar;
-    b.seq_off = hb.seq_off; b.seq = hb.seq; b.qual_off = hb.qual_off; b.qual = hb.qual; b.nm = hb.nm; b.nm_type = hb.nm_type;
-    b.mi_off = hb.mi_off; b.mi = hb.mi; b.tick = e->have_tick ? hb.tick : nullptr;
+    // ---- call order, the upload of a host batch, the --quit_after_contig cut, the stream's size
+    int check_and_cut() {
+        if (!e->host_mode && !e->device_mode) return fail(e, GCE_ERR_INVALID, "nothing submitted");
+        if (e->processed) return fail(e, GCE_ERR_INVALID, "gce_process called twice without a new submit (the stream was mutated in place)");
+        if (e->have_tick && !e->have_events) return fail(e, GCE_ERR_INVALID, "gce_batch.tick needs gce_set_flush_events");
+        (void)hipSetDevice(e->prm.device);
+        int rc;
+        if (e->host_mode && (rc = upload(e)) != GCE_OK) return rc;
+        N = hb.n_reads;
+        e->n_pre = N;
+        if (e->prm.max_contig > 0 && N > 0 && !e->shard_cut_done) {                    // src/gencore.cpp:243-246: the loop ends on the first read of contig >= maxContig
+            HIPCHK(e->si.ensure(sizeof(StreamInfo)));
+            unsigned int first = NONE32;
+            HIPCHK(hipMemcpyAsync(e->si.p, &first, 4, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_first_contig_ge, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, hb.core, N, e->prm.max_contig, (unsigned int *)e->si.p);
+            HIPCHK(hipMemcpyAsync(&first, e->si.p, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (first != NONE32) {
+                gce_core c2; int32_t nm = 0; uint8_t nmt = 0;                            // (the sorted check of :233-241 cannot fail on this read: every read in front has a smaller tid)
+                HIPCHK(hipMemcpy(&c2, hb.core + first, sizeof(gce_core), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(&nm, hb.nm + first, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&nmt, hb.nm_type + first, 1, hipMemcpyDeviceToHost));
+                const int mism = nmt != 0 ? nm : 0;                                     // Stats::addRead (stats.cpp:101-121): the read is mapped (tid >= maxContig > 0)
+                pre_extra.v[0] = 1; pre_extra.v[1] = c2.l_qseq; pre_extra.v[4] = mism; pre_extra.v[5] = mism > 0;
+                N = (int64_t)first; e->n_pre = N + 1;
+            }
+        }
+        e->n = N; e->n_out = 0; e->out_seq_bytes = e->out_qual_bytes = 0; e->dev_error = 0; e->dev_error_read = 0;
+        e->processed = true;
+        memset(&e->timing, 0, sizeof e->timing);
+        memset(&e->h_si, 0, sizeof e->h_si);
+        if (N >= (int64_t)0xFFFFFC00ll) return fail(e, GCE_ERR_INVALID, "more than 2^32 reads in one engine");
+        // k_vote's batches come from ONE scan of packed words, weight prefix in the low half and live rank in the high half (k_group_fill, k_vote_batches): a weight sum of
+        // 2^32 would carry into the ranks.  The sum is at most (VB_MINW + 3) x reads (vb_start's bound below), so such a stream is refused here (it would need > 100 GB of
+        // descriptors and pair slots alone; the 32-bit weight prefixes of earlier versions wrapped at the same sum)
+        if ((uint64_t)(VB_MINW + 3) * (uint64_t)(N > 0 ? N : 0) >= (1ull << 32)) return fail(e, GCE_ERR_INVALID, "too many reads in one engine for the batch scan of k_vote (weight sum >= 2^32)");
+        n1 = (size_t)(N > 0 ? N : 1);
+        b.n = N; b.core = hb.core; b.qname_off = hb.qname_off; b.qname = hb.qname; b.cigar_off = hb.cigar_off; b.cigar = hb.cigar;
+        b.seq_off = hb.seq_off; b.seq = hb.seq; b.qual_off = hb.qual_off; b.qual = hb.qual; b.nm = hb.nm; b.nm_type = hb.nm_type;
+        b.mi_off = hb.mi_off; b.mi = hb.mi; b.tick = e->have_tick ? hb.tick : nullptr;
+        return GCE_OK;
+    }
 
-    // reference + params to the device -- only when they changed since the last step (four small copies and two stream synchronisations per step otherwise:
-    // ~60 us of every 6 ms step in front of the first kernel)
-    const int nref = (int)e->ref_ptr.size();
-    HIPCHK(e->d_ref_ptr.ensure((size_t)(nref + 1) * 8)); HIPCHK(e->d_ref_len.ensure((size_t)(nref + 1) * 8));
-    HIPCHK(e->d_target_len.ensure(e->target_len.size() * 4 + 4));
-    HIPCHK(e->d_target_cum.ensure(e->target_len.size() * 8 + 8));
-    std::vector<int64_t> win;
-    if (e->have_win && nref) {                                                     // contigs staged whole: window = [0, length)
-        win.assign(2 * (size_t)nref, 0);
-        for (int t = 0; t < nref; t++) { const bool wd = 2 * (size_t)t + 1 < e->ref_win.size() && e->ref_win[2 * t + 1] > 0; win[2 * t] = wd ? e->ref_win[2 * t] : 0; win[2 * t + 1] = wd ? e->ref_win[2 * t + 1] : e->ref_len[t]; }
-        HIPCHK(e->d_ref_win.ensure(win.size() * 8));
-    }
-    const void *dev_now[5] = {e->d_ref_ptr.p, e->d_ref_len.p, e->d_target_len.p, e->d_target_cum.p, e->d_ref_win.p};
-    const bool same = e->up_valid && e->up_ref_ptr == e->ref_ptr && e->up_ref_len == e->ref_len && e->up_tl == e->target_len && e->up_win == win && memcmp(dev_now, e->up_dev, sizeof dev_now) == 0;
-    if (!same) {
-        e->up_valid = false;
-        if (nref) {
-            HIPCHK(hipMemcpyAsync(e->d_ref_ptr.p, e->ref_ptr.data(), (size_t)nref * 8, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipMemcpyAsync(e->d_ref_len.p, e->ref_len.data(), (size_t)nref * 8, hipMemcpyHostToDevice, e->stream));
+    // ---- reference + target arrays to the device -- only when they changed since the last step (four small copies and two stream synchronisations per step
+    // otherwise: ~60 us of every 6 ms step in front of the first kernel); their device pointers into p
+    int stage_constants() {
+        const int nref = (int)e->ref_ptr.size();
+        HIPCHK(e->d_ref_ptr.ensure((size_t)(nref + 1) * 8)); HIPCHK(e->d_ref_len.ensure((size_t)(nref + 1) * 8));
+        HIPCHK(e->d_target_len.ensure(e->target_len.size() * 4 + 4));
+        HIPCHK(e->d_target_cum.ensure(e->target_len.size() * 8 + 8));
+        std::vector<int64_t> win;
+        if (e->have_win && nref) {                                                     // contigs staged whole: window = [0, length)
+            win.assign(2 * (size_t)nref, 0);
+            for (int t = 0; t < nref; t++) { const bool wd = 2 * (size_t)t + 1 < e->ref_win.size() && e->ref_win[2 * t + 1] > 0; win[2 * t] = wd ? e->ref_win[2 * t] : 0; win[2 * t + 1] = wd ? e->ref_win[2 * t + 1] : e->ref_len[t]; }
+            HIPCHK(e->d_ref_win.ensure(win.size() * 8));
         }
-        std::vector<uint64_t> cum(e->target_len.size()); uint64_t acc = 0;
-        for (size_t i = 0; i < cum.size(); i++) { cum[i] = acc; acc += e->target_len[i]; }
-        if (!e->target_len.empty()) {
-            HIPCHK(hipMemcpyAsync(e->d_target_len.p, e->target_len.data(), e->target_len.size() * 4, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipMemcpyAsync(e->d_target_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, e->stream));
+        const void *dev_now[5] = {e->d_ref_ptr.p, e->d_ref_len.p, e->d_target_len.p, e->d_target_cum.p, e->d_ref_win.p};
+        const bool same = e->up_valid && e->up_ref_ptr == e->ref_ptr && e->up_ref_len == e->ref_len && e->up_tl == e->target_len && e->up_win == win && memcmp(dev_now, e->up_dev, sizeof dev_now) == 0;
+        if (!same) {
+            e->up_valid = false;
+            if (nref) {
+                HIPCHK(hipMemcpyAsync(e->d_ref_ptr.p, e->ref_ptr.data(), (size_t)nref * 8, hipMemcpyHostToDevice, s));
+                HIPCHK(hipMemcpyAsync(e->d_ref_len.p, e->ref_len.data(), (size_t)nref * 8, hipMemcpyHostToDevice, s));
+            }
+            std::vector<uint64_t> cum(e->target_len.size()); uint64_t acc = 0;
+            for (size_t i = 0; i < cum.size(); i++) { cum[i] = acc; acc += e->target_len[i]; }
+            if (!e->target_len.empty()) {
+                HIPCHK(hipMemcpyAsync(e->d_target_len.p, e->target_len.data(), e->target_len.size() * 4, hipMemcpyHostToDevice, s));
+                HIPCHK(hipMemcpyAsync(e->d_target_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, s));
+            }
+            if (!win.empty()) HIPCHK(hipMemcpyAsync(e->d_ref_win.p, win.data(), win.size() * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));                                               // (the sources are locals and vectors that may change)
+            e->up_ref_ptr = e->ref_ptr; e->up_ref_len = e->ref_len; e->up_tl = e->target_len; e->up_win = win; memcpy(e->up_dev, dev_now, sizeof dev_now);
+            e->up_valid = true;
         }
-        if (!win.empty()) HIPCHK(hipMemcpyAsync(e->d_ref_win.p, win.data(), win.size() * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));                                       // (the sources are locals and vectors that may change)
-        e->up_ref_ptr = e->ref_ptr; e->up_ref_len = e->ref_len; e->up_tl = e->target_len; e->up_win = win; memcpy(e->up_dev, dev_now, sizeof dev_now);
-        e->up_valid = true;
+        p.target_len = e->d_target_len.as<uint32_t>(); p.target_cum = e->target_len.empty() ? nullptr : e->d_target_cum.as<uint64_t>();
+        p.n_ref = nref; p.ref_data = e->d_ref_ptr.as<const uint8_t *>(); p.ref_len = e->d_ref_len.as<int64_t>(); p.ref_win = win.empty() ? nullptr : e->d_ref_win.as<int64_t>();
+        return GCE_OK;
     }
-    DevParams p{};
-    p.proper_thr = e->prm.proper_umi_diff_threshold; p.unproper_thr = e->prm.unproper_umi_diff_threshold;
-    p.duplex_mismatch_thr = e->prm.duplex_mismatch_threshold; p.cluster_size_req = e->prm.cluster_size_req; p.base_score_req = e->prm.base_score_req;
-    p.high_q = e->prm.high_quality; p.moderate_q = e->prm.moderate_quality; p.low_q = e->prm.low_quality;
-    p.s_high = e->prm.score_high; p.s_moderate = e->prm.score_moderate; p.s_low = e->prm.score_low; p.s_bad = e->prm.score_bad;
-    p.skip_low_complexity_thr = e->prm.skip_low_complexity_cluster_threshold; p.duplex_only = e->prm.duplex_only; p.disable_duplex = e->prm.disable_duplex;
-    p.period = e->prm.flush_period; p.score_percent_req = e->prm.score_percent_req;
-    {   // scores are qual2score(q) in {s_*}, +4 on overlap match, -3 on overlap mismatch, or 0 (pair.cpp:77-172)
-        int mn = std::min(std::min(p.s_high, p.s_moderate), std::min(p.s_low, p.s_bad)), mx = std::max(std::max(p.s_high, p.s_moderate), std::max(p.s_low, p.s_bad));
-        p.score_bias = std::max(0, 3 - mn); p.score_max = std::max(0, mx + 4);
-        if (p.score_max + p.score_bias > 255) return fail(e, GCE_ERR_INVALID, "score constants out of range");
-        auto by = [&](int sc) { return (uint32_t)((sc + p.score_bias) & 0xFF); };
-        p.q2s_lut = by(p.s_bad) | by(p.s_low) << 8 | by(p.s_moderate) << 16 | by(p.s_high) << 24;
-        p.thr_low4 = 0x01010101u * (uint32_t)(p.low_q & 0xFF); p.thr_mod4 = 0x01010101u * (uint32_t)(p.moderate_q & 0xFF); p.thr_high4 = 0x01010101u * (uint32_t)(p.high_q & 0xFF);
-        p.q2s_swar_ok = p.low_q >= 0 && p.low_q <= p.moderate_q && p.moderate_q <= p.high_q && p.high_q <= 127;
-        // k_vote (gce_vote.hpp): scores in a sane range (the packed tally keys of decide_column_packed), and whether a unanimous column whose
-        // top quality reaches `moderate` is bound to reach baseScoreReq too: that voter scores s_moderate or s_high (or >= min + 4 inside a
-        // matching mate overlap) and nobody scores below 0
-        p.s_min_lb = mn;
-        p.vote_ok = mn >= 0 && mx + 4 <= 120 && p.moderate_q >= 0 && p.moderate_q <= 127 && p.base_score_req <= 100 && p.q2s_swar_ok;   // (nested thresholds: k_vote's items index q2s_lut by the number of thresholds passed)
-        p.vote_accept_by_qual = std::min(std::min(p.s_moderate, p.s_high), mn + 4) >= std::max(p.base_score_req, 1);
-        if (!p.vote_ok && !e->vote_off_logged) {      // every group then goes to k_score2 and the per-side kernels: say why, once per engine
+
+    // ---- the scalars of p (gce_params.hpp), the allocations that only depend on N, StreamInfo and the bucket table ready, the step's clock started
+    int size_by_reads() {
+        // buckets: 1.25 x reads (worst case, every read its own cluster, still probes at load 0.8; typical load is a few percent).
+        const uint64_t T = ((uint64_t)n1 + (uint64_t)n1 / 4 + 2 * SCAN_TILE - 1) / SCAN_TILE * SCAN_TILE;
+        const char *vote_off_why = nullptr;
+        if (make_dev_params(e->prm, e->target_len, e->have_tick, N, T, &p, &vote_off_why) != GCE_OK) return fail(e, GCE_ERR_INVALID, "score constants out of range");
+        if (vote_off_why && !e->vote_off_logged) {      // every group then goes to k_score2 and the per-side kernels: say why, once per engine
             e->vote_off_logged = true;
-            const char *why = !p.q2s_swar_ok ? "quality thresholds not nested (low <= moderate <= high <= 127)" : mn < 0 ? "a score constant below 0"
-                            : mx + 4 > 120 ? "a score constant above 116" : (p.moderate_q < 0 || p.moderate_q > 127) ? "moderate quality outside 0..127" : "base_score_req above 100";
-            fprintf(stderr, "gencore_amd: k_vote off for this engine (%s): every group goes to the per-side kernels\n", why);
+            fprintf(stderr, "gencore_amd: k_vote off for this engine (%s): every group goes to the per-side kernels\n", vote_off_why);
         }
-    }
-    memcpy(p.prefix, e->prm.umi_prefix, 32); p.prefix[31] = 0; p.prefix_len = (int)strlen(p.prefix);
-    p.n_targets = (int)e->target_len.size(); p.target_len = e->d_target_len.as<uint32_t>(); p.target_cum = e->target_len.empty() ? nullptr : e->d_target_cum.as<uint64_t>();
-    p.tick_offset = e->have_tick ? 0 : e->prm.tick_offset; p.tick_epoch0 = p.tick_offset / p.period; p.tick_rem0 = (int32_t)(p.tick_offset % p.period); p.trailing_flush = e->have_tick ? 0 : e->prm.trailing_flush;
-    {   // packed cluster key of the bucket table: bits of the largest tid and of the longest contig
-        uint32_t mx = 1; for (uint32_t v : e->target_len) mx = std::max(mx, v);
-        int bt = 1; while (bt < 31 && (1ll << bt) < (long long)std::max<size_t>(e->target_len.size(), 1)) bt++;
-        int bl = 1; while (bl < 32 && (1ull << bl) <= (uint64_t)mx) bl++;
-        p.key_bt = bt; p.key_bl = bl;
-    }
-    p.n_ref = nref; p.ref_data = e->d_ref_ptr.as<const uint8_t *>(); p.ref_len = e->d_ref_len.as<int64_t>(); p.ref_win = win.empty() ? nullptr : e->d_ref_win.as<int64_t>();
+        n_sblk = (N + SB_READS - 1) / SB_READS;
+        w.n_sblk = n_sblk;
+        max_events = e->have_tick ? (int64_t)e->h_ev_tid.size() + 2 : (p.tick_offset % p.period + N) / p.period + 2;
+        w.max_events = (int)max_events;
+        w.tsize = T; w.tinv = 1.0 / (double)T;
+        const size_t qual_bytes = hb.qual_bytes ? hb.qual_bytes : 1;
+        const size_t nsb1 = (size_t)(n_sblk > 0 ? n_sblk : 1);
+        TAKE(uinfo, w.uinfo, n1 * 8); TAKE(rdesc, w.rdesc, n1 * sizeof(ReadDescP)); TAKE(spatch, w.spatch, n1 * 4); TAKE(slot, w.slot, n1 * 4 + 16); TAKE(score, w.score, qual_bytes + 64);
+        TAKE(out_flag, w.out_flag, n1 + 144);       /* (k_out_mate reads whole 64-byte blocks of flags) */ TAKE(nmx, w.nmx, n1 * 4); TAKE(orec, w.orec, n1 * sizeof(OutRec)); TAKE(out_index, w.out_index, n1 * 4);
+        TAKE(lrec, w.lrec, nsb1 * SB_READS * sizeof(LeadRec)); TAKE(lout, w.lout, nsb1 * SB_READS * sizeof(LeadOut));
+        TAKE(bhdr, w.bhdr, nsb1 * sizeof(BlkHdr)); TAKE(blk_base, w.blk_base, nsb1 * 4);
+        TAKE(ev_tid, w.ev_tid, (size_t)max_events * 4); TAKE(ev_pos, w.ev_pos, (size_t)max_events * 4); TAKE(ev_read, w.ev_read, (size_t)max_events * 4);
+        TAKE(table, w.tab, T * sizeof(TabEntry)); TAKE(toff, w.toff, T * 4);
+        TAKE(k64, w.k64, n1 * 24); TAKE(members, w.members, n1 * 4); TAKE(sorted, w.sorted, n1 * 4); TAKE(pl, w.pl, n1 * 4); TAKE(pr, w.pr, n1 * 4); TAKE(pu, w.pu, n1 * 4); TAKE(pg, w.pg, n1 * 4);
+        TAKE(gpl, w.gpl, n1 * 4); TAKE(gpr, w.gpr, n1 * 4); TAKE(grp_begin, w.grp_begin, n1 * 4); TAKE(grp_n, w.grp_n, n1 * 4); TAKE(slow_list, w.slow_list, n1 * 4 + 64);
+        TAKE(deep_list, w.deep_list, (n1 / 64 + 64) * 16);
+        nblk_N = cdiv(n1, SCAN_TILE);
+        TAKE(scan_part, w.scan_part, std::max<size_t>(2 * nsb1, (size_t)2 * nblk_N) * 8 + 16);    /* 2 x: the group-side flags (<= 2 per read); the scan blocks' totals behind those of k_num_reduce's blocks */
+        TAKE(si, w.si, sizeof(StreamInfo));
+        TAKE(cl_ikey, w.cl_ikey, n1 * 4); TAKE(cl_start, w.cl_start, n1 * 4); TAKE(cl_n, w.cl_n, n1 * 4);      // cl_* arrays are sized by N (a cluster has >= 1 read)
 
-    // ---- allocations that only depend on N
-    Work w{};
-    const int64_t n_sblk = (N + SB_READS - 1) / SB_READS;
-    w.n_sblk = n_sblk;
-    const int64_t max_events = e->have_tick ? (int64_t)e->h_ev_tid.size() + 2 : (p.tick_offset % p.period + N) / p.period + 2;
-    w.max_events = (int)max_events;
-    // buckets: 1.25 x reads (worst case, every read its own cluster, still probes at load 0.8; typical load is a few percent).
-    uint64_t T = ((uint64_t)n1 + (uint64_t)n1 / 4 + 2 * SCAN_TILE - 1) / SCAN_TILE * SCAN_TILE;
-    w.tsize = T; w.tinv = 1.0 / (double)T;
-    {   // normal bucket words: OCC | x div T | right - left + 1 | reads (gce_cluster.hpp, k_leaders)
-        uint64_t genome = 0; for (uint32_t v : e->target_len) genome += v;
-        const uint64_t qmax = (genome * TAB_WAYS + TAB_WAYS) / T + 1;
-        int cb = 1; while (cb < 33 && (1ull << cb) <= (uint64_t)N + 1024) cb++;
-        int qb = 1; while (qb < 52 && (1ull << qb) <= qmax) qb++;
-        p.nw_cb = cb; p.nw_bd = 62 - cb - qb; p.nw_ok = !e->target_len.empty() && p.nw_bd >= 1;
-        if (p.nw_bd > 40) p.nw_bd = 40;
+        StreamInfo init{}; init.first_unmapped = NONE32; init.err_key = ~0ull; init.lq_min = 0x7FFFFFFF; init.lq_max = -1;
+        if (e->have_tick) { init.n_events = init.n_events_a = (int)e->h_ev_tid.size(); }
+        HIPCHK(hipMemcpyAsync(e->si.p, &init, sizeof init, hipMemcpyHostToDevice, s));
+        if (e->have_tick && !e->h_ev_tid.empty()) {
+            HIPCHK(hipMemcpyAsync(e->ev_tid.p, e->h_ev_tid.data(), e->h_ev_tid.size() * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(e->ev_pos.p, e->h_ev_pos.data(), e->h_ev_pos.size() * 4, hipMemcpyHostToDevice, s));
+        }
+        // The bucket table is cleared by its users (k_scatter): a memset only for a new allocation or after a step that did not get that far.  A new
+        // allocation may come back at the address of the one it replaced, so the capacity tells it apart too (DevBuf::ensure only ever grows it).
+        if (!e->tab_clean || e->tab_clean_ptr != e->table.p || e->tab_clean_cap != e->table.cap) {
+            HIPCHK(hipMemsetAsync(e->table.p, 0, e->table.cap, s));
+            e->tab_clean_ptr = e->table.p; e->tab_clean_cap = e->table.cap;
+        }
+        e->tab_clean = false;
+        HIPCHK(hipEventRecord(e->ev[EV_START], s));
+        HIPCHK(hipMemsetAsync(e->out_flag.p, 0, n1, s));
+        return GCE_OK;
     }
-    const size_t qual_bytes = hb.qual_bytes ? hb.qual_bytes : 1;
-    const size_t nsb1 = (size_t)(n_sblk > 0 ? n_sblk : 1);
-#define ENS(buf, bytes) HIPCHK(e->buf.ensure(bytes))
-    ENS(uinfo, n1 * 8); ENS(rdesc, n1 * sizeof(ReadDescP)); ENS(spatch, n1 * 4); ENS(slot, n1 * 4 + 16); ENS(score, qual_bytes + 64);
-    ENS(out_flag, n1 + 144);       /* (k_out_mate reads whole 64-byte blocks of flags) */ ENS(nmx, n1 * 4); ENS(orec, n1 * sizeof(OutRec)); ENS(out_index, n1 * 4);
-    ENS(lrec, nsb1 * SB_READS * sizeof(LeadRec)); ENS(lout, nsb1 * SB_READS * sizeof(LeadOut));
-    ENS(bhdr, nsb1 * sizeof(BlkHdr)); ENS(blk_base, nsb1 * 4);
-    ENS(ev_tid, (size_t)max_events * 4); ENS(ev_pos, (size_t)max_events * 4); ENS(ev_read, (size_t)max_events * 4);
-    ENS(table, T * sizeof(TabEntry)); ENS(toff, T * 4);
-    ENS(k64, n1 * 24); ENS(members, n1 * 4); ENS(sorted, n1 * 4); ENS(pl, n1 * 4); ENS(pr, n1 * 4); ENS(pu, n1 * 4); ENS(pg, n1 * 4); ENS(gpl, n1 * 4); ENS(gpr, n1 * 4);
-    ENS(grp_begin, n1 * 4); ENS(grp_n, n1 * 4); ENS(slow_list, n1 * 4 + 64);
-    w.slow_list = e->slow_list.as<uint32_t>();
-    ENS(deep_list, (n1 / 64 + 64) * 16); w.deep_list = e->deep_list.p;
-    const unsigned nblk_N = cdiv(n1, SCAN_TILE);
-    ENS(scan_part, std::max<size_t>(2 * nsb1, (size_t)2 * nblk_N) * 8 + 16);    /* 2 x: the group-side flags (<= 2 per read); the scan blocks' totals behind those of k_num_reduce's blocks */ ENS(si, sizeof(StreamInfo));
-    w.uinfo = e->uinfo.as<uint64_t>(); w.rdesc = e->rdesc.as<ReadDescP>(); w.spatch = e->spatch.as<uint32_t>();
-    w.slot = e->slot.as<uint32_t>(); w.score = e->score.as<int8_t>();
-    w.out_flag = e->out_flag.as<uint8_t>(); w.nmx = e->nmx.as<uint32_t>(); w.orec = e->orec.as<OutRec>(); w.out_index = e->out_index.as<uint32_t>();
-    w.lrec = e->lrec.as<LeadRec>(); w.lout = e->lout.as<LeadOut>(); w.bhdr = e->bhdr.as<BlkHdr>(); w.blk_base = e->blk_base.as<uint32_t>();
-    w.ev_tid = e->ev_tid.as<int32_t>(); w.ev_pos = e->ev_pos.as<int32_t>(); w.ev_read = e->ev_read.as<uint32_t>();
-    w.tab = e->table.as<TabEntry>(); w.toff = e->toff.as<uint32_t>();
-    w.k64 = e->k64.as<uint64_t>(); w.members = e->members.as<uint32_t>(); w.sorted = e->sorted.as<uint32_t>(); w.pl = e->pl.as<uint32_t>(); w.pr = e->pr.as<uint32_t>();
-    w.pu = e->pu.as<uint32_t>(); w.pg = e->pg.as<uint32_t>(); w.gpl = e->gpl.as<uint32_t>(); w.gpr = e->gpr.as<uint32_t>();
-    w.grp_begin = e->grp_begin.as<uint32_t>(); w.grp_n = e->grp_n.as<uint32_t>();
-    w.scan_part = e->scan_part.as<uint64_t>(); w.si = e->si.as<StreamInfo>();
-    ENS(cl_ikey, n1 * 4); ENS(cl_start, n1 * 4); ENS(cl_n, n1 * 4);      // cl_* arrays are sized by N (a cluster has >= 1 read)
-    w.cl_ikey = e->cl_ikey.as<uint32_t>(); w.cl_start = e->cl_start.as<uint32_t>(); w.cl_n = e->cl_n.as<uint32_t>();
 
-    StreamInfo init{}; init.first_unmapped = NONE32; init.err_key = ~0ull; init.lq_min = 0x7FFFFFFF; init.lq_max = -1;
-    if (e->have_tick) { init.n_events = init.n_events_a = (int)e->h_ev_tid.size(); }
-    HIPCHK(hipMemcpyAsync(e->si.p, &init, sizeof init, hipMemcpyHostToDevice, e->stream));
-    if (e->have_tick && !e->h_ev_tid.empty()) {
-        HIPCHK(hipMemcpyAsync(e->ev_tid.p, e->h_ev_tid.data(), e->h_ev_tid.size() * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(e->ev_pos.p, e->h_ev_pos.data(), e->h_ev_pos.size() * 4, hipMemcpyHostToDevice, e->stream));
-    }
-    hipStream_t s = e->stream;
-    // The bucket table is cleared by its users (k_scatter): a memset only for a new allocation or after a step that did not get that far.  A new
-    // allocation may come back at the address of the one it replaced, so the capacity tells it apart too (DevBuf::ensure only ever grows it).
-    if (!e->tab_clean || e->tab_clean_ptr != e->table.p || e->tab_clean_cap != e->table.cap) {
-        HIPCHK(hipMemsetAsync(e->table.p, 0, e->table.cap, s));
-        e->tab_clean_ptr = e->table.p; e->tab_clean_cap = e->table.cap;
-    }
-    e->tab_clean = false;
-    HIPCHK(hipEventRecord(e->ev[EV_START], s));
-    HIPCHK(hipMemsetAsync(e->out_flag.p, 0, n1, s));
     // ---- cluster formation (gce_cluster.hpp): the scan, then the leaders (ticks + flush events come with the batch for key-range shards)
-    if (N > 0) LAUNCH_EV(k_cluster, dim3((unsigned)n_sblk), dim3(SB_T), s, e->ev[EV_CLUSTER], b, p, w);
+    int form_clusters() {
+        if (N > 0) LAUNCH_EV(k_cluster, dim3((unsigned)n_sblk), dim3(SB_T), s, e->ev[EV_CLUSTER], b, p, w);
 #ifdef CL_PROF
-    if (N > 0) {
-        StreamInfo hs; (void)hipStreamSynchronize(s); (void)hipMemcpy(&hs, e->si.p, sizeof hs, hipMemcpyDeviceToHost);
-        static const char *nm[3] = {"key records + keys", "LDS leaders", "stores"};
-        const double blocks = (double)hs.prof[15];
-        fprintf(stderr, "k_cluster phases, mean per block (us), %.0f blocks:", blocks);
-        for (int k = 0; k < 3; k++) fprintf(stderr, " %s %.2f;", nm[k], blocks ? hs.prof[k] / blocks / 100.0 : 0.0);
-        fprintf(stderr, "\n");
-    }
+        dump_cluster_prof();
 #endif
-    if (N <= 0) HIPCHK(hipEventRecord(e->ev[EV_CLUSTER], s));
-    CANARY("EV_CLUSTER");
-    if (N > 0) {
-        if (!e->have_tick) {
-            hipLaunchKernelGGL(k_blk_scan, dim3(1), dim3(1024), 0, s, w, p);
-            hipLaunchKernelGGL(k_events, dim3(cdiv(max_events, EV_T / 64)), dim3(EV_T), 0, s, b, p, w);
-        }
-        const unsigned nb4 = cdiv(n_sblk, 4);
-        hipLaunchKernelGGL(k_leaders, dim3(nb4), dim3(256), 0, s, b, p, w);
-        hipLaunchKernelGGL(k_num_reduce, dim3(nb4), dim3(256), 0, s, w, p.nw_cb);
-        hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nb4, &w.si->n_clusters, (unsigned long long *)nullptr);      // (one partial per k_num_reduce block)
-        hipLaunchKernelGGL(k_num_apply, dim3(nb4), dim3(256), 0, s, w);
-        LAUNCH_EV(k_scatter, dim3((unsigned)n_sblk), dim3(SB_T), s, e->ev[EV_CSR], N, w);
-    } else HIPCHK(hipEventRecord(e->ev[EV_CSR], s));
-    CANARY("EV_CSR");
+        if (N <= 0) HIPCHK(hipEventRecord(e->ev[EV_CLUSTER], s));
+        CANARY("EV_CLUSTER");
+        if (N > 0) {
+            if (!e->have_tick) {
+                hipLaunchKernelGGL(k_blk_scan, dim3(1), dim3(1024), 0, s, w, p);
+                hipLaunchKernelGGL(k_events, dim3(cdiv(max_events, EV_T / 64)), dim3(EV_T), 0, s, b, p, w);
+            }
+            const unsigned nb4 = cdiv(n_sblk, 4);
+            hipLaunchKernelGGL(k_leaders, dim3(nb4), dim3(256), 0, s, b, p, w);
+            hipLaunchKernelGGL(k_num_reduce, dim3(nb4), dim3(256), 0, s, w, p.nw_cb);
+            hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nb4, &w.si->n_clusters, (unsigned long long *)nullptr);      // (one partial per k_num_reduce block)
+            hipLaunchKernelGGL(k_num_apply, dim3(nb4), dim3(256), 0, s, w);
+            LAUNCH_EV(k_scatter, dim3((unsigned)n_sblk), dim3(SB_T), s, e->ev[EV_CSR], N, w);
+        } else HIPCHK(hipEventRecord(e->ev[EV_CSR], s));
+        CANARY("EV_CSR");
+        return GCE_OK;
+    }
+
     // ---- per-read descriptors, UMI slices, pre-Stats: independent of the clusters, consumed by pairing and the vote.
     // The host's look at the cluster count is asked for IN FRONT of it and awaited behind it: the word travels while k_describe runs (what k_describe adds to the
     // block -- pre-Stats, read-length range, its errors -- is read by the later looks; the pairing kernels do not mind a read k_describe refused)
-    unsigned long long si_seq1 = 0;
-    if ((rc = read_si_begin(e, &si_seq1)) != GCE_OK) return rc;
-    if (N > 0) {
+    int describe() {
+        int rc;
+        unsigned long long si_seq1 = 0;
+        if ((rc = read_si_begin(e, &si_seq1)) != GCE_OK) return rc;
+        if (N > 0) {
 #ifndef GCE_DESCRIBE_BLOCKS
 #define GCE_DESCRIBE_BLOCKS 32768        // at most this many blocks: their Stats partial sums end in six global atomics each
 #endif
-        const int64_t n_tiles = (N + 255) / 256;
-        int tpb = (int)((n_tiles + GCE_DESCRIBE_BLOCKS - 1) / GCE_DESCRIBE_BLOCKS); if (tpb < 1) tpb = 1;
-        LAUNCH_EV(k_describe, dim3(cdiv(n_tiles, tpb)), dim3(256), s, e->ev[EV_DESCRIBE], b, p, w, tpb);
-    } else HIPCHK(hipEventRecord(e->ev[EV_DESCRIBE], s));
-    CANARY("EV_DESCRIBE");
-    if ((rc = read_si_end(e, si_seq1)) != GCE_OK) return rc;
-    HIPCHK(hipGetLastError());
-    e->tab_clean = true;                          // k_scatter ran to the end
-    const uint32_t C = (uint32_t)e->h_si.n_clusters;
-    const size_t c1 = C ? C : 1;
-    ENS(cl_npairs, c1 * 4); ENS(cl_ngroups, c1 * 4); ENS(cl_gbase, c1 * 4); ENS(cl_nresult, c1 * 4); ENS(cl_hasumi, c1); ENS(cl_tier, c1);
-    w.cl_npairs = e->cl_npairs.as<uint32_t>(); w.cl_ngroups = e->cl_ngroups.as<uint32_t>(); w.cl_gbase = e->cl_gbase.as<uint32_t>();
-    w.cl_nresult = e->cl_nresult.as<uint32_t>(); w.cl_hasumi = e->cl_hasumi.as<uint8_t>(); w.cl_tier = e->cl_tier.as<uint8_t>();
-    uint32_t NG = 0;
-    bool si_behind_describe = false;               // the host's copy of StreamInfo holds what k_describe found (read-length range)
-    if (C > 0 && e->dev_error == 0) {
+            const int64_t n_tiles = (N + 255) / 256;
+            int tpb = (int)((n_tiles + GCE_DESCRIBE_BLOCKS - 1) / GCE_DESCRIBE_BLOCKS); if (tpb < 1) tpb = 1;
+            LAUNCH_EV(k_describe, dim3(cdiv(n_tiles, tpb)), dim3(256), s, e->ev[EV_DESCRIBE], b, p, w, tpb);
+        } else HIPCHK(hipEventRecord(e->ev[EV_DESCRIBE], s));
+        CANARY("EV_DESCRIBE");
+        if ((rc = read_si_end(e, si_seq1)) != GCE_OK) return rc;
+        HIPCHK(hipGetLastError());
+        e->tab_clean = true;                          // k_scatter ran to the end
+        C = (uint32_t)e->h_si.n_clusters;
+        const size_t c1 = C ? C : 1;
+        TAKE(cl_npairs, w.cl_npairs, c1 * 4); TAKE(cl_ngroups, w.cl_ngroups, c1 * 4); TAKE(cl_gbase, w.cl_gbase, c1 * 4); TAKE(cl_nresult, w.cl_nresult, c1 * 4);
+        TAKE(cl_hasumi, w.cl_hasumi, c1); TAKE(cl_tier, w.cl_tier, c1);
+        return GCE_OK;
+    }
+
+    // a flag per cluster -> the list of the flagged clusters and their count, by the scan kernels (never one shared append counter)
+    void compact_flags(uint8_t *flag, uint32_t *list, unsigned long long *count) {
+        const unsigned nbc = cdiv(C, SCAN_TILE);
+        hipLaunchKernelGGL(k_flag_reduce, dim3(nbc), dim3(256), 0, s, (const uint8_t *)flag, (uint64_t)C, w.scan_part);
+        hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nbc, count, (unsigned long long *)nullptr);
+        hipLaunchKernelGGL(k_flag_apply, dim3(nbc), dim3(256), 0, s, (const uint8_t *)flag, (uint64_t)C, (const uint64_t *)w.scan_part, list);
+    }
+
+    // ---- mate pairing + UMI grouping per cluster, the compact group list, the batches of k_vote; the host's second look: the group count
+    int pair_clusters() {
+        if (!(C > 0 && e->dev_error == 0)) { HIPCHK(hipEventRecord(e->ev[EV_PAIRING], s)); return GCE_OK; }
+        int rc;
+        const size_t c1 = C;
         // (gpl / gpr need no clearing: every reader -- k_vote, k_score2 behind the slot flags, the per-side kernels, k_group_tail -- looks at the pair slots
         //  [g_begin, g_begin + g_np) of a group only, and the pairing kernels write both words of every one of those)
         // three tiers: 16 lanes per cluster, then 32 for what that flags, then the full wave; each hand-over is a flag array
-        // compacted by the scan kernels (never one shared append counter)
-        ENS(left_list, c1 * 4 + 64); w.left_list = e->left_list.as<uint32_t>();
-        ENS(pf_flag, c1 + 64); ENS(pf_list, c1 * 4); ENS(pq_flag, c1 + 64); ENS(pq_list, c1 * 4); ENS(p16_flag, c1 + 64); ENS(p16_list, c1 * 4);
-        w.pf_flag = e->pf_flag.as<uint8_t>(); w.pf_list = e->pf_list.as<uint32_t>(); w.pq_flag = e->pq_flag.as<uint8_t>(); w.pq_list = e->pq_list.as<uint32_t>(); w.p16_flag = e->p16_flag.as<uint8_t>(); w.p16_list = e->p16_list.as<uint32_t>();
+        // compacted by the scan kernels (compact_flags)
+        TAKE(left_list, w.left_list, c1 * 4 + 64);
+        TAKE(pf_flag, w.pf_flag, c1 + 64); TAKE(pf_list, w.pf_list, c1 * 4); TAKE(pq_flag, w.pq_flag, c1 + 64); TAKE(pq_list, w.pq_list, c1 * 4); TAKE(p16_flag, w.p16_flag, c1 + 64); TAKE(p16_list, w.p16_list, c1 * 4);
         // size classes in front of the quarter-wave kernel (k_pair_classes) when a good share of the clusters is beyond it: mean cluster beyond 10 reads
         // (cfg3: 16 reads, 45 % of the clusters beyond 16 -- pairing 1.41 -> 1.26 ms; cfg2: 7 reads, nearly none -- the class pass would be 16 us for nothing)
         const bool pair_classes = (double)N > 10.0 * (double)C;
         if (!pair_classes) fill_many(s, {FillSeg{e->pf_flag.p, c1, 0u, 0u}, FillSeg{e->pq_flag.p, c1, 0u, 0u}});          // (with size classes every entry of the three flag arrays is written by k_pair_classes)
         const unsigned nbc = cdiv(C, SCAN_TILE);
-        auto compact = [&](uint8_t *flag, uint32_t *list, unsigned long long *count) {
-            hipLaunchKernelGGL(k_flag_reduce, dim3(nbc), dim3(256), 0, s, (const uint8_t *)flag, (uint64_t)C, w.scan_part);
-            hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nbc, count, (unsigned long long *)nullptr);
-            hipLaunchKernelGGL(k_flag_apply, dim3(nbc), dim3(256), 0, s, (const uint8_t *)flag, (uint64_t)C, (const uint64_t *)w.scan_part, list);
-        };
 #ifdef PS_STOP
-        {   // experiment builds (tools/pair_stop.sh): time the truncated k_pairing_sub<16> (all clusters) and <32> (all clusters as well: no list) alone and stop
-            hipEvent_t a_, b_, c_; (void)hipEventCreate(&a_); (void)hipEventCreate(&b_); (void)hipEventCreate(&c_);
-            (void)hipEventRecord(a_, s);
-            hipLaunchKernelGGL(k_pairing_sub<16>, dim3(cdiv(C, 4 * WAVES_PER_BLOCK)), dim3(256), 0, s, b, p, w, C, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, w.pq_flag, 0);
-            (void)hipEventRecord(b_, s);
-            hipLaunchKernelGGL(k_pairing_sub<32>, dim3(cdiv(C, 2 * WAVES_PER_BLOCK)), dim3(256), 0, s, b, p, w, C, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, w.pf_flag, 0);
-            (void)hipEventRecord(c_, s); (void)hipEventSynchronize(c_);
-            float m1 = 0, m2 = 0; (void)hipEventElapsedTime(&m1, a_, b_); (void)hipEventElapsedTime(&m2, b_, c_);
-            fprintf(stderr, "k_pairing_sub up to tick %d: <16> %.3f ms, <32> over ALL clusters %.3f ms\n", PS_STOP, m1, m2);
-            return fail(e, GCE_ERR_INVALID, "experiment build");
-        }
+        return time_pairing_sub_and_stop();
 #endif
-        ENS(pd_slab, PD_BIG_BLOCKS * PD_SLAB);
+        HIPCHK(e->pd_slab.ensure(PD_BIG_BLOCKS * PD_SLAB));
         if (pair_classes) {
             // the three register-resident tiers get their clusters BY SIZE beforehand (<= 16, <= 32, more) and run side by side: quarter- and half-wave kernels on the main
             // stream, the full-wave kernel and the LDS instantiation of k_pairing_deep -- the long, thin tail of the phase: 93 + 60 us with a few thousand waves -- on the second
@@ -941,9 +906,9 @@ static int gce_process_impl(gce_engine *e) {
             if (tiers_aux) HIPCHK(hipStreamWaitEvent(s, e->aux_ev[1], 0));
         } else {
             hipLaunchKernelGGL(k_pairing_sub<16>, dim3(cdiv(C, 4 * WAVES_PER_BLOCK)), dim3(256), 0, s, b, p, w, C, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, w.pq_flag, 0);
-            compact(w.pq_flag, w.pq_list, &w.si->n_pq_items);
+            compact_flags(w.pq_flag, w.pq_list, &w.si->n_pq_items);
             hipLaunchKernelGGL(k_pairing_sub<32>, dim3(cdiv(C, 2 * WAVES_PER_BLOCK)), dim3(256), 0, s, b, p, w, C, (const uint32_t *)w.pq_list, (const unsigned long long *)&w.si->n_pq_items, w.pf_flag, 0);
-            compact(w.pf_flag, w.pf_list, &w.si->n_pf_items);
+            compact_flags(w.pf_flag, w.pf_list, &w.si->n_pf_items);
             hipLaunchKernelGGL(k_pairing_fast, dim3(2048), dim3(256), 0, s, b, p, w, C, (const uint32_t *)w.pf_list);
             hipLaunchKernelGGL(k_pairing_deep<false>, dim3(256), dim3(PD_T), 0, s, b, p, w, (uint8_t *)nullptr);      // deep clusters in LDS; the rest -> left_list
         }
@@ -951,17 +916,14 @@ static int gce_process_impl(gce_engine *e) {
         hipLaunchKernelGGL(k_pairing_slow<0>, dim3(1024), dim3(256), 0, s, b, p, w);
         hipLaunchKernelGGL(k_pairing_slow<1>, dim3(1024, 16), dim3(256), 0, s, b, p, w);      // y: a cluster's 64-read blocks over 16 waves
         hipLaunchKernelGGL(k_pairing_slow<2>, dim3(1024), dim3(256), 0, s, b, p, w);
-        const unsigned nblk_C = cdiv(C, SCAN_TILE);
-        hipLaunchKernelGGL(k_scan_reduce, dim3(nblk_C), dim3(256), 0, s, (const uint32_t *)w.cl_ngroups, (uint64_t)C, w.scan_part);
-        hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nblk_C, &w.si->n_pairs /*scratch*/, &w.si->n_groups);
-        hipLaunchKernelGGL(k_u32_apply, dim3(nblk_C), dim3(256), 0, s, (const uint32_t *)w.cl_ngroups, w.cl_gbase, (uint64_t)C, (const uint64_t *)w.scan_part);
+        hipLaunchKernelGGL(k_scan_reduce, dim3(nbc), dim3(256), 0, s, (const uint32_t *)w.cl_ngroups, (uint64_t)C, w.scan_part);
+        hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nbc, &w.si->n_pairs /*scratch*/, &w.si->n_groups);
+        hipLaunchKernelGGL(k_u32_apply, dim3(nbc), dim3(256), 0, s, (const uint32_t *)w.cl_ngroups, w.cl_gbase, (uint64_t)C, (const uint64_t *)w.scan_part);
         // the compact group list and the batches of k_vote: sized by N (groups <= pairs <= reads) so that all of it runs before the one
         // host round trip that fetches the group count and the batch count together
-        ENS(gl_cluster, n1 * 4); ENS(g_begin, n1 * 4); ENS(g_np, n1 * 4); ENS(gw, n1 * 8); ENS(vlive, n1 * 16);
+        TAKE(gl_cluster, w.gl_cluster, n1 * 4); TAKE(g_begin, w.g_begin, n1 * 4); TAKE(g_np, w.g_np, n1 * 4); TAKE(gw, w.gw, n1 * 8); TAKE(vlive, w.vlive, n1 * 16);
         const size_t vb_cap = ((VB_MINW + 3) * n1) / VB_W + 8;     // sum of weights <= VB_MINW x groups + pairs + VB_W x deep groups (> 32 pairs each)
-        ENS(vb_start, vb_cap * 4);
-        w.gl_cluster = e->gl_cluster.as<uint32_t>(); w.g_begin = e->g_begin.as<uint32_t>(); w.g_np = e->g_np.as<uint32_t>();
-        w.gw = e->gw.as<uint64_t>(); w.vlive = e->vlive.as<uint4>(); w.vb_start = e->vb_start.as<uint32_t>();
+        TAKE(vb_start, w.vb_start, vb_cap * 4);
         HIPCHK(hipMemsetAsync(e->vb_start.p, 0xFF, vb_cap * 4, s));
         hipLaunchKernelGGL(k_group_fill, dim3(cdiv(C, 256)), dim3(256), 0, s, p, w, C, (uint32_t)VB_W, (uint32_t)VB_MINW);
         hipLaunchKernelGGL(k_u64_reduce, dim3(nblk_N), dim3(256), 0, s, (const uint64_t *)w.gw, (const unsigned long long *)&w.si->n_groups, w.scan_part);
@@ -972,79 +934,183 @@ static int gce_process_impl(gce_engine *e) {
         HIPCHK(hipGetLastError());
         si_behind_describe = true;
         NG = (uint32_t)e->h_si.n_groups;
-    } else HIPCHK(hipEventRecord(e->ev[EV_PAIRING], s));
-    const size_t g1 = NG ? NG : 1;
-    ENS(gen_list, g1 * 8); ENS(gen_flag, g1 * 2 + 64); ENS(score_list, n1 * 4 + 64);      /* one entry per pair SLOT: a pair may hold one read only (mate absent / far / on another contig), so slots <= N, not N / 2 */ ENS(rp_left, g1 * 4); ENS(rp_right, g1 * 4); ENS(rp_merge, g1 * 4); ENS(rp_rmerge, g1 * 4); ENS(rp_umi, g1 * 8);
-    ENS(rp_umilen, g1 * 2); ENS(rp_state, g1); ENS(rp_supp, g1 * 4); ENS(rp_nm, g1 * 8); ENS(rp_qsl, g1 * 4); ENS(rp_qsr, g1 * 4);
-    w.gen_list = e->gen_list.as<uint32_t>(); w.gen_flag = e->gen_flag.as<uint8_t>(); w.score_list = e->score_list.as<uint32_t>();
-    w.rp_left = e->rp_left.as<uint32_t>(); w.rp_right = e->rp_right.as<uint32_t>();
-    w.rp_merge = e->rp_merge.as<uint32_t>(); w.rp_rmerge = e->rp_rmerge.as<uint32_t>(); w.rp_umi = e->rp_umi.as<const char *>();
-    w.rp_umilen = e->rp_umilen.as<uint16_t>(); w.rp_state = e->rp_state.as<uint8_t>(); w.rp_supp = e->rp_supp.as<int32_t>();
-    w.rp_nm = e->rp_nm.as<int32_t>(); w.rp_qsl = e->rp_qsl.as<uint32_t>(); w.rp_qsr = e->rp_qsr.as<uint32_t>();
-    if (NG > 0 && e->dev_error == 0) {
-        {   // argument blocks of the generic consensus kernel in device memory (gce_kernels.hpp); here, where the host has just waited for the GPU anyway: `w` is complete
-            SlowArgs sa; sa.b = b; sa.p = p; sa.w = w;
-            HIPCHK(e->slow_args.ensure(sizeof sa));
-            HIPCHK(hipMemcpyAsync(e->slow_args.p, &sa, sizeof sa, hipMemcpyHostToDevice, s));      // (pageable source: staged before the call returns)
-        }
-        // one launch for the five clears (spatch needs none: k_score2 writes the patch word of both reads of every pair it scores, and only those are read)
-        fill_many(s, {FillSeg{e->gen_flag.p, g1 * 2, 0u, 0u},
-                      FillSeg{e->rp_nm.p, g1 * 8, 0xFFu, 0u},                                  // -1: NM untouched
-                      FillSeg{e->rp_left.p, g1 * 4, 0xFFu, 0u}, FillSeg{e->rp_right.p, g1 * 4, 0xFFu, 0u}});   // NONE: a group no kernel voted on emits nothing (instead of stale read indices)
-        const uint32_t n_live = (uint32_t)e->h_si.n_live;                                    // (with none, vb_start[0] stays NONE32: k_vote's one block returns at once and reads no list)
+        return GCE_OK;
+    }
+
+    // ---- Pair::computeScore, template pick and column vote per group (k_vote; what it hands on: k_score2 and the per-side kernels), qname reconciliation, the duplex stage
+    int consensus() {
+        int rc;
+        const size_t g1 = NG ? NG : 1;
+        TAKE(gen_list, w.gen_list, g1 * 8); TAKE(gen_flag, w.gen_flag, g1 * 2 + 64);
+        TAKE(score_list, w.score_list, n1 * 4 + 64);      // one entry per pair SLOT: a pair may hold one read only (mate absent / far / on another contig), so slots <= N, not N / 2
+        TAKE(rp_left, w.rp_left, g1 * 4); TAKE(rp_right, w.rp_right, g1 * 4); TAKE(rp_merge, w.rp_merge, g1 * 4); TAKE(rp_rmerge, w.rp_rmerge, g1 * 4); TAKE(rp_umi, w.rp_umi, g1 * 8);
+        TAKE(rp_umilen, w.rp_umilen, g1 * 2); TAKE(rp_state, w.rp_state, g1); TAKE(rp_supp, w.rp_supp, g1 * 4); TAKE(rp_nm, w.rp_nm, g1 * 8); TAKE(rp_qsl, w.rp_qsl, g1 * 4); TAKE(rp_qsr, w.rp_qsr, g1 * 4);
+        if (NG > 0 && e->dev_error == 0) {
+            {   // argument blocks of the generic consensus kernel in device memory (gce_kernels.hpp); here, where the host has just waited for the GPU anyway: `w` is complete
+                SlowArgs sa; sa.b = b; sa.p = p; sa.w = w;
+                HIPCHK(e->slow_args.ensure(sizeof sa));
+                HIPCHK(hipMemcpyAsync(e->slow_args.p, &sa, sizeof sa, hipMemcpyHostToDevice, s));      // (pageable source: staged before the call returns)
+            }
+            // one launch for the five clears (spatch needs none: k_score2 writes the patch word of both reads of every pair it scores, and only those are read)
+            fill_many(s, {FillSeg{e->gen_flag.p, g1 * 2, 0u, 0u},
+                          FillSeg{e->rp_nm.p, g1 * 8, 0xFFu, 0u},                                  // -1: NM untouched
+                          FillSeg{e->rp_left.p, g1 * 4, 0xFFu, 0u}, FillSeg{e->rp_right.p, g1 * 4, 0xFFu, 0u}});   // NONE: a group no kernel voted on emits nothing (instead of stale read indices)
+            const uint32_t n_live = (uint32_t)e->h_si.n_live;                                    // (with none, vb_start[0] stays NONE32: k_vote's one block returns at once and reads no list)
 #ifdef VB_XCD
-        const unsigned nbatch = (((unsigned)(e->h_si.vote_weight / VB_W) + 1u) + 7u) & ~7u;      // (vb_start is 0xFF-filled up to vb_cap: the extra blocks find no batch)
+            const unsigned nbatch = (((unsigned)(e->h_si.vote_weight / VB_W) + 1u) + 7u) & ~7u;      // (vb_start is 0xFF-filled up to vb_cap: the extra blocks find no batch)
 #else
-        const unsigned nbatch = (unsigned)(e->h_si.vote_weight / VB_W) + 1u;
+            const unsigned nbatch = (unsigned)(e->h_si.vote_weight / VB_W) + 1u;
 #endif
 #ifdef VB_STOP
-        {   // experiment builds (tools/vote_stop.sh): time the truncated k_vote alone and stop -- it leaves garbage behind
-            hipEvent_t a_, b_; (void)hipEventCreate(&a_); (void)hipEventCreate(&b_);
-            (void)hipEventRecord(a_, s); hipLaunchKernelGGL(k_vote, dim3(nbatch), dim3(VB_T), 0, s, b, p, w, n_live); (void)hipEventRecord(b_, s); (void)hipEventSynchronize(b_);
-            float ms_ = 0; (void)hipEventElapsedTime(&ms_, a_, b_); fprintf(stderr, "k_vote up to tick %d: %.3f ms\n", VB_STOP, ms_);
-            return fail(e, GCE_ERR_INVALID, "experiment build");
-        }
+            return time_vote_and_stop(nbatch, n_live);
 #endif
-        LAUNCH_EV(k_vote, dim3(nbatch), dim3(VB_T), s, e->ev[EV_SCORE], b, p, w, n_live);
-        CANARY("EV_SCORE");
-        // A stream of deep groups (mean depth beyond 24 pairs: the deep kernels carry the consensus phase, cfg5) runs Pair::computeScore for the
-        // handed-on groups (k_score2: bandwidth) on a second HIP stream BESIDE the compaction, the hand-on of the deep sides and their template /
-        // voter preparation (k_deep_prepare: a wave per side, latency) -- none of those reads a score or a quality; the votes wait for both.
-        const bool deep_stream = ((double)N > 48.0 * (double)NG || getenv("GCE_FORCE_AUX_STREAM")) && !getenv("GCE_NO_AUX_STREAM");          // (reads per group / 2 = mean pairs per group)
-        // both kernels stride over lists whose length only the device knows: on a stream of ordinary depth k_vote hands on a few percent of the groups, and a grid sized for
-        // "everything" spends its time starting empty blocks (k_consensus_fast: 32 k blocks for ~10 k sides were 20 of its 26 us at cfg3)
-        const unsigned cf_cap = deep_stream ? 32768u : 4096u, sc2_cap = deep_stream ? 16384u : 2048u;
-        const unsigned cf_grid = std::min<unsigned>(cdiv(2ull * NG, WAVES_PER_BLOCK), cf_cap);
-        const unsigned sc2_grid = std::min<unsigned>(cdiv(N, 2 * WAVES_PER_BLOCK * 64), sc2_cap);      // k_score2: waves stride over the list of handed-on pair slots (<= N)
-        if (deep_stream) {
-            if ((rc = aux_ready(e)) != GCE_OK) return rc;
-            HIPCHK(hipEventRecord(e->aux_ev[0], s));                                       // k_vote is done: its slot flags stand, the deep sides are on slow_list
-            HIPCHK(hipStreamWaitEvent(e->aux_stream, e->aux_ev[0], 0));
-            hipLaunchKernelGGL(k_score2, dim3(sc2_grid), dim3(256), 0, e->aux_stream, b, p, w);
-            HIPCHK(hipEventRecord(e->aux_ev[1], e->aux_stream));
-            hipLaunchKernelGGL(k_deep_prepare, dim3(1024), dim3(256), 0, s, b, p, w);      // (template + voter list of the deep sides: reads no score, no quality)
-            HIPCHK(hipStreamWaitEvent(s, e->aux_ev[1], 0));                                // the scores (and the rewritten qualities) stand
-            hipLaunchKernelGGL(k_consensus_fast, dim3(cf_grid), dim3(256), 0, s, b, p, w);           // everything else on gen_list
-        } else {
-            hipLaunchKernelGGL(k_score2, dim3(sc2_grid), dim3(256), 0, s, b, p, w);       // the handed-on groups only
-            hipLaunchKernelGGL(k_deep_prepare, dim3(1024), dim3(256), 0, s, b, p, w);      // (before k_consensus_fast appends the sides IT cannot take: those are not deep)
-            hipLaunchKernelGGL(k_consensus_fast, dim3(cf_grid), dim3(256), 0, s, b, p, w);
-        }
-        hipLaunchKernelGGL(k_vote_deep, dim3(1024), dim3(DV_T), 0, s, b, p, w);                 // deep sides, one block each; leaves what it cannot take
-        LAUNCH_EV(k_consensus_slow, dim3(512), dim3(256), s, e->ev[EV_CONSENSUS], (const SlowArgs *)e->slow_args.p);
-        CANARY("EV_CONSENSUS");
-        hipLaunchKernelGGL(k_group_tail, dim3(cdiv(NG, 256)), dim3(256), 0, s, b, p, w, NG);
-        if (!p.disable_duplex) {                                                                  // duplex stage: flagged clusters, compacted, a wave each
-            const unsigned nbc = cdiv(C, SCAN_TILE);
-            hipLaunchKernelGGL(k_finish_screen, dim3(cdiv(C, 256)), dim3(256), 0, s, w, C, w.pf_flag);
-            hipLaunchKernelGGL(k_flag_reduce, dim3(nbc), dim3(256), 0, s, (const uint8_t *)w.pf_flag, (uint64_t)C, w.scan_part);
-            hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (uint64_t)nbc, &w.si->n_pf_items, (unsigned long long *)nullptr);
-            hipLaunchKernelGGL(k_flag_apply, dim3(nbc), dim3(256), 0, s, (const uint8_t *)w.pf_flag, (uint64_t)C, (const uint64_t *)w.scan_part, w.pf_list);
-            hipLaunchKernelGGL(k_finish, dim3(4096), dim3(256), 0, s, b, p, w, (const uint32_t *)w.pf_list, (const unsigned long long *)&w.si->n_pf_items);
-        }
-    } else { HIPCHK(hipEventRecord(e->ev[EV_SCORE], s)); HIPCHK(hipEventRecord(e->ev[EV_CONSENSUS], s)); }
+            LAUNCH_EV(k_vote, dim3(nbatch), dim3(VB_T), s, e->ev[EV_SCORE], b, p, w, n_live);
+            CANARY("EV_SCORE");
+            // A stream of deep groups (mean depth beyond 24 pairs: the deep kernels carry the consensus phase, cfg5) runs Pair::computeScore for the
+            // handed-on groups (k_score2: bandwidth) on a second HIP stream BESIDE the compaction, the hand-on of the deep sides and their template /
+            // voter preparation (k_deep_prepare: a wave per side, latency) -- none of those reads a score or a quality; the votes wait for both.
+            const bool deep_stream = ((double)N > 48.0 * (double)NG || getenv("GCE_FORCE_AUX_STREAM")) && !getenv("GCE_NO_AUX_STREAM");          // (reads per group / 2 = mean pairs per group)
+            // both kernels stride over lists whose length only the device knows: on a stream of ordinary depth k_vote hands on a few percent of the groups, and a grid sized for
+            // "everything" spends its time starting empty blocks (k_consensus_fast: 32 k blocks for ~10 k sides were 20 of its 26 us at cfg3)
+            const unsigned cf_cap = deep_stream ? 32768u : 4096u, sc2_cap = deep_stream ? 16384u : 2048u;
+            const unsigned cf_grid = std::min<unsigned>(cdiv(2ull * NG, WAVES_PER_BLOCK), cf_cap);
+            const unsigned sc2_grid = std::min<unsigned>(cdiv(N, 2 * WAVES_PER_BLOCK * 64), sc2_cap);      // k_score2: waves stride over the list of handed-on pair slots (<= N)
+            if (deep_stream) {
+                if ((rc = aux_ready(e)) != GCE_OK) return rc;
+                HIPCHK(hipEventRecord(e->aux_ev[0], s));                                       // k_vote is done: its slot flags stand, the deep sides are on slow_list
+                HIPCHK(hipStreamWaitEvent(e->aux_stream, e->aux_ev[0], 0));
+                hipLaunchKernelGGL(k_score2, dim3(sc2_grid), dim3(256), 0, e->aux_stream, b, p, w);
+                HIPCHK(hipEventRecord(e->aux_ev[1], e->aux_stream));
+                hipLaunchKernelGGL(k_deep_prepare, dim3(1024), dim3(256), 0, s, b, p, w);      // (template + voter list of the deep sides: reads no score, no quality)
+                HIPCHK(hipStreamWaitEvent(s, e->aux_ev[1], 0));                                // the scores (and the rewritten qualities) stand
+                hipLaunchKernelGGL(k_consensus_fast, dim3(cf_grid), dim3(256), 0, s, b, p, w);           // everything else on gen_list
+            } else {
+                hipLaunchKernelGGL(k_score2, dim3(sc2_grid), dim3(256), 0, s, b, p, w);       // the handed-on groups only
+                hipLaunchKernelGGL(k_deep_prepare, dim3(1024), dim3(256), 0, s, b, p, w);      // (before k_consensus_fast appends the sides IT cannot take: those are not deep)
+                hipLaunchKernelGGL(k_consensus_fast, dim3(cf_grid), dim3(256), 0, s, b, p, w);
+            }
+            hipLaunchKernelGGL(k_vote_deep, dim3(1024), dim3(DV_T), 0, s, b, p, w);                 // deep sides, one block each; leaves what it cannot take
+            LAUNCH_EV(k_consensus_slow, dim3(512), dim3(256), s, e->ev[EV_CONSENSUS], (const SlowArgs *)e->slow_args.p);
+            CANARY("EV_CONSENSUS");
+            hipLaunchKernelGGL(k_group_tail, dim3(cdiv(NG, 256)), dim3(256), 0, s, b, p, w, NG);
+            if (!p.disable_duplex) {                                                                  // duplex stage: flagged clusters, compacted, a wave each
+                hipLaunchKernelGGL(k_finish_screen, dim3(cdiv(C, 256)), dim3(256), 0, s, w, C, w.pf_flag);
+                compact_flags(w.pf_flag, w.pf_list, &w.si->n_pf_items);
+                hipLaunchKernelGGL(k_finish, dim3(4096), dim3(256), 0, s, b, p, w, (const uint32_t *)w.pf_list, (const unsigned long long *)&w.si->n_pf_items);
+            }
+        } else { HIPCHK(hipEventRecord(e->ev[EV_SCORE], s)); HIPCHK(hipEventRecord(e->ev[EV_CONSENSUS], s)); }
 #ifdef VB_PROF
-    if (NG > 0) {
+        dump_vote_prof();
+#endif
+        return GCE_OK;
+    }
+
+    // ---- the output set: emitted reads in bamComp order (gencore.h:19-47) as one compact table.  Capacities are worst case
+    //      (every read emitted): nothing here needs a host round trip.
+    int output_table() {
+        HIPCHK(hipEventRecord(e->ev[EV_FINISH], s));
+        CANARY("EV_FINISH");
+        if (N > 0 && e->dev_error == 0) {
+            // worst case: every read emitted.  The sum of the reads' bytes is at most the blobs' size -- and at most reads x longest read (k_describe's lq_max, on the
+            // host since the first look at StreamInfo): on the raw-stream path the "blobs" are the whole inflated file (names, CIGARs and tags included, and the SAME
+            // 2.4 GB for bases and qualities), and sizing both outputs by it was 5 of the 9 GB an engine allocated for 8 M reads
+            size_t seq_cap = hb.seq_bytes + 16 * n1 + 64, qual_cap = hb.qual_bytes + 16 * n1 + 64;
+            if (e->h_si.lq_max >= 0) {
+                const size_t lqm = (size_t)e->h_si.lq_max;
+                seq_cap = std::min(seq_cap, n1 * ((lqm + 1) / 2 + 16) + 64); qual_cap = std::min(qual_cap, n1 * (lqm + 16) + 64);
+            }
+            TAKE(o_src, o.src, n1 * 4); TAKE(o_kind, o.kind, n1); TAKE(o_qsrc, o.qname_src, n1 * 4); TAKE(o_nm, o.nm_new, n1 * 4); TAKE(o_fr, o.fr, n1 * 2); TAKE(o_rr, o.rr, n1 * 2); TAKE(o_mate, o.mate, n1 * 4);
+            TAKE(o_soff, o.seq_off, n1 * 8); TAKE(o_qoff, o.qual_off, n1 * 8); TAKE(o_seq, o.seq, seq_cap); TAKE(o_qual, o.qual, qual_cap);
+            TAKE(o_key, o.key, n1 * sizeof(OutKey)); TAKE(o_rec, o.rec, n1 * sizeof(OutRec)); TAKE(o_ksoff, o.ksoff, n1 * 8); TAKE(o_kqoff, o.kqoff, n1 * 8); TAKE(o_krow, o.krow, n1 * 4); TAKE(o_rank64, o.rank64, (n1 / 64 + 2) * 4);
+            const unsigned nblk_O = cdiv(n1, OUT_TILE); TAKE(o_part3, o.part3, (size_t)nblk_O * 24 + 64);
+            if (e->h_si.n_raw > 0 && C > 0) hipLaunchKernelGGL(k_raw_emit, dim3(cdiv(C, 256)), dim3(256), 0, s, b, p, w, C);      // gencore.cpp:401-407 (malformed input only)
+            hipLaunchKernelGGL(k_stats, dim3(1024), dim3(256), 0, s, b, w, (NG > 0 ? C : 0u), NG);     // Stats: clusters, groups  (round 5: on the second stream beside the output kernels it hid its 50 us and stretched k_out_reduce / k_out_partials by as much: not kept)
+            CANARY("k_stats");
+            hipLaunchKernelGGL(k_out_reduce, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o);
+            CANARY("k_out_reduce");
+            hipLaunchKernelGGL(k_out_partials, dim3(1), dim3(1024), 0, s, o, (uint64_t)nblk_O, w);
+            CANARY("k_out_partials");
+            // every emitted read of one length (k_describe's range, final on the host once the look behind the pairing phase has happened): no offset lists in LDS
+            const bool lq_uniform = si_behind_describe && e->h_si.lq_max >= 0 && e->h_si.lq_min == e->h_si.lq_max;
+            if (lq_uniform) hipLaunchKernelGGL(k_out_meta<true>, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o, (int)e->h_si.lq_max);
+            else hipLaunchKernelGGL(k_out_meta<false>, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o, -1);
+            CANARY("k_out_meta");
+            const unsigned og = std::min<unsigned>(cdiv(n1, 256), 8192u);
+            hipLaunchKernelGGL(k_out_rows, dim3(og), dim3(256), 0, s, w, o);
+            CANARY("k_out_rows");
+            hipLaunchKernelGGL(k_out_mate, dim3(og), dim3(256), 0, s, w, o);
+            CANARY("k_out_mate");
+            hipLaunchKernelGGL(k_out_gather, dim3(std::min<unsigned>(cdiv(n1, 16), 16384u)), dim3(256), 0, s, b, w, o);
+            CANARY("k_out_gather");
+        }
+        HIPCHK(hipEventRecord(e->ev[EV_OUTPUT], s));
+        CANARY("EV_OUTPUT");
+        return GCE_OK;
+    }
+
+    // ---- the Stats blocks complete, the host's last look, the phase times, the device's error
+    int close_step() {
+        int rc;
+        hipLaunchKernelGGL(k_fold_stats, dim3(1), dim3(64), 0, s, w.si, pre_extra);          // (outside the timed step: a convenience of gce_stats_device)
+        if ((rc = read_si(e)) != GCE_OK) return rc;
+        HIPCHK(hipGetLastError());
+#ifdef GCE_SI_CHECK
+        si_check();
+#endif
+        e->h_si.n_groups = NG;
+        float ms = 0;
+        auto el = [&](int a, int c) { ms = 0; (void)hipEventElapsedTime(&ms, e->ev[a], e->ev[c]); return (double)ms; };
+        e->timing.total_ms = el(EV_START, EV_OUTPUT);
+        e->timing.cluster_ms = el(EV_START, EV_CLUSTER); e->timing.csr_ms = el(EV_CLUSTER, EV_CSR); e->timing.describe_ms = el(EV_CSR, EV_DESCRIBE);
+        e->timing.pairing_ms = el(EV_DESCRIBE, EV_PAIRING); e->timing.score_ms = el(EV_PAIRING, EV_SCORE); e->timing.consensus_ms = el(EV_SCORE, EV_CONSENSUS);
+        e->timing.finish_ms = el(EV_CONSENSUS, EV_FINISH); e->timing.output_ms = el(EV_FINISH, EV_OUTPUT);
+        e->timing.n_clusters = C; e->timing.n_groups = NG;
+        if (e->dev_error != 0) {
+            char buf[160]; snprintf(buf, sizeof buf, "%s (read %u)", gce_status_message(e->dev_error), e->dev_error_read);
+            return fail(e, e->dev_error, buf);
+        }
+        e->n_out = (int64_t)e->h_si.n_out;
+        e->out_seq_bytes = (size_t)(e->h_si.out_units >> 32) * 16; e->out_qual_bytes = (size_t)(e->h_si.out_units & 0xFFFFFFFFull) * 16;
+        e->timing.n_pairs = (int64_t)e->h_si.n_pairs_total; e->timing.n_leaders = (int64_t)e->h_si.n_leaders;
+        return GCE_OK;
+    }
+
+    // ---- experiment and debugging builds
+#ifdef CL_PROF
+    void dump_cluster_prof() {
+        if (N <= 0) return;
+        StreamInfo hs; (void)hipStreamSynchronize(s); (void)hipMemcpy(&hs, e->si.p, sizeof hs, hipMemcpyDeviceToHost);
+        static const char *nm[3] = {"key records + keys", "LDS leaders", "stores"};
+        const double blocks = (double)hs.prof[15];
+        fprintf(stderr, "k_cluster phases, mean per block (us), %.0f blocks:", blocks);
+        for (int k = 0; k < 3; k++) fprintf(stderr, " %s %.2f;", nm[k], blocks ? hs.prof[k] / blocks / 100.0 : 0.0);
+        fprintf(stderr, "\n");
+    }
+#endif
+#ifdef PS_STOP
+    int time_pairing_sub_and_stop() {   // tools/pair_stop.sh: time the truncated k_pairing_sub<16> (all clusters) and <32> (all clusters as well: no list) alone and stop
+        hipEvent_t a_, b_, c_; (void)hipEventCreate(&a_); (void)hipEventCreate(&b_); (void)hipEventCreate(&c_);
+        (void)hipEventRecord(a_, s);
+        hipLaunchKernelGGL(k_pairing_sub<16>, dim3(cdiv(C, 4 * WAVES_PER_BLOCK)), dim3(256), 0, s, b, p, w, C, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, w.pq_flag, 0);
+        (void)hipEventRecord(b_, s);
+        hipLaunchKernelGGL(k_pairing_sub<32>, dim3(cdiv(C, 2 * WAVES_PER_BLOCK)), dim3(256), 0, s, b, p, w, C, (const uint32_t *)nullptr, (const unsigned long long *)nullptr, w.pf_flag, 0);
+        (void)hipEventRecord(c_, s); (void)hipEventSynchronize(c_);
+        float m1 = 0, m2 = 0; (void)hipEventElapsedTime(&m1, a_, b_); (void)hipEventElapsedTime(&m2, b_, c_);
+        fprintf(stderr, "k_pairing_sub up to tick %d: <16> %.3f ms, <32> over ALL clusters %.3f ms\n", PS_STOP, m1, m2);
+        return fail(e, GCE_ERR_INVALID, "experiment build");
+    }
+#endif
+#ifdef VB_STOP
+    int time_vote_and_stop(unsigned nbatch, uint32_t n_live) {   // tools/vote_stop.sh: time the truncated k_vote alone and stop -- it leaves garbage behind
+        hipEvent_t a_, b_; (void)hipEventCreate(&a_); (void)hipEventCreate(&b_);
+        (void)hipEventRecord(a_, s); hipLaunchKernelGGL(k_vote, dim3(nbatch), dim3(VB_T), 0, s, b, p, w, n_live); (void)hipEventRecord(b_, s); (void)hipEventSynchronize(b_);
+        float ms_ = 0; (void)hipEventElapsedTime(&ms_, a_, b_); fprintf(stderr, "k_vote up to tick %d: %.3f ms\n", VB_STOP, ms_);
+        return fail(e, GCE_ERR_INVALID, "experiment build");
+    }
+#endif
+#ifdef VB_PROF
+    void dump_vote_prof() {
+        if (NG == 0) return;
         StreamInfo hs; (void)hipStreamSynchronize(s); (void)hipMemcpy(&hs, e->si.p, sizeof hs, hipMemcpyDeviceToHost);
         static const char *nm[11] = {"P0 groups", "P1 pairs", "P2 classes", "P3 overlap", "P4 pass A", "P5 lists", "P5 items", "P5 decide", "P5 tail", "P6 results", "P7 write"};
         const double blocks = (double)hs.prof[15];
@@ -1067,83 +1133,31 @@ static int gce_process_impl(gce_engine *e) {
         fprintf(stderr, "\n");
     }
 #endif
-    HIPCHK(hipEventRecord(e->ev[EV_FINISH], s));
-    CANARY("EV_FINISH");
-    // ---- the output set: emitted reads in bamComp order (gencore.h:19-47) as one compact table.  Capacities are worst case
-    //      (every read emitted): nothing here needs a host round trip.
-    OutTable o{};
-    if (N > 0 && e->dev_error == 0) {
-        // worst case: every read emitted.  The sum of the reads' bytes is at most the blobs' size -- and at most reads x longest read (k_describe's lq_max, on the
-        // host since the first look at StreamInfo): on the raw-stream path the "blobs" are the whole inflated file (names, CIGARs and tags included, and the SAME
-        // 2.4 GB for bases and qualities), and sizing both outputs by it was 5 of the 9 GB an engine allocated for 8 M reads
-        size_t seq_cap = hb.seq_bytes + 16 * n1 + 64, qual_cap = hb.qual_bytes + 16 * n1 + 64;
-        if (e->h_si.lq_max >= 0) {
-            const size_t lqm = (size_t)e->h_si.lq_max;
-            seq_cap = std::min(seq_cap, n1 * ((lqm + 1) / 2 + 16) + 64); qual_cap = std::min(qual_cap, n1 * (lqm + 16) + 64);
-        }
-        ENS(o_src, n1 * 4); ENS(o_kind, n1); ENS(o_qsrc, n1 * 4); ENS(o_nm, n1 * 4); ENS(o_fr, n1 * 2); ENS(o_rr, n1 * 2); ENS(o_mate, n1 * 4);
-        ENS(o_soff, n1 * 8); ENS(o_qoff, n1 * 8); ENS(o_seq, seq_cap); ENS(o_qual, qual_cap);
-        ENS(o_key, n1 * sizeof(OutKey)); ENS(o_rec, n1 * sizeof(OutRec)); ENS(o_ksoff, n1 * 8); ENS(o_kqoff, n1 * 8); ENS(o_krow, n1 * 4); ENS(o_rank64, (n1 / 64 + 2) * 4); const unsigned nblk_O = cdiv(n1, OUT_TILE); ENS(o_part3, (size_t)nblk_O * 24 + 64);
-        o.src = e->o_src.as<uint32_t>(); o.kind = e->o_kind.as<uint8_t>(); o.qname_src = e->o_qsrc.as<uint32_t>(); o.nm_new = e->o_nm.as<int32_t>();
-        o.fr = e->o_fr.as<int16_t>(); o.rr = e->o_rr.as<int16_t>(); o.mate = e->o_mate.as<uint32_t>();
-        o.seq_off = e->o_soff.as<uint64_t>(); o.qual_off = e->o_qoff.as<uint64_t>(); o.seq = e->o_seq.as<uint8_t>(); o.qual = e->o_qual.as<uint8_t>();
-        o.key = e->o_key.as<OutKey>(); o.rec = e->o_rec.as<OutRec>(); o.ksoff = e->o_ksoff.as<uint64_t>(); o.kqoff = e->o_kqoff.as<uint64_t>(); o.krow = e->o_krow.as<uint32_t>(); o.rank64 = e->o_rank64.as<uint32_t>(); o.part3 = e->o_part3.as<uint64_t>();
-        if (e->h_si.n_raw > 0 && C > 0) hipLaunchKernelGGL(k_raw_emit, dim3(cdiv(C, 256)), dim3(256), 0, s, b, p, w, C);      // gencore.cpp:401-407 (malformed input only)
-        hipLaunchKernelGGL(k_stats, dim3(1024), dim3(256), 0, s, b, w, (NG > 0 ? C : 0u), NG);     // Stats: clusters, groups  (round 5: on the second stream beside the output kernels it hid its 50 us and stretched k_out_reduce / k_out_partials by as much: not kept)
-        CANARY("k_stats");
-        hipLaunchKernelGGL(k_out_reduce, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o);
-        CANARY("k_out_reduce");
-        hipLaunchKernelGGL(k_out_partials, dim3(1), dim3(1024), 0, s, o, (uint64_t)nblk_O, w);
-        CANARY("k_out_partials");
-        // every emitted read of one length (k_describe's range, final on the host once the look behind the pairing phase has happened): no offset lists in LDS
-        const bool lq_uniform = si_behind_describe && e->h_si.lq_max >= 0 && e->h_si.lq_min == e->h_si.lq_max;
-        if (lq_uniform) hipLaunchKernelGGL(k_out_meta<true>, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o, (int)e->h_si.lq_max);
-        else hipLaunchKernelGGL(k_out_meta<false>, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o, -1);
-        CANARY("k_out_meta");
-        const unsigned og = std::min<unsigned>(cdiv(n1, 256), 8192u);
-        hipLaunchKernelGGL(k_out_rows, dim3(og), dim3(256), 0, s, w, o);
-        CANARY("k_out_rows");
-        hipLaunchKernelGGL(k_out_mate, dim3(og), dim3(256), 0, s, w, o);
-        CANARY("k_out_mate");
-        hipLaunchKernelGGL(k_out_gather, dim3(std::min<unsigned>(cdiv(n1, 16), 16384u)), dim3(256), 0, s, b, w, o);
-        CANARY("k_out_gather");
-    }
-    HIPCHK(hipEventRecord(e->ev[EV_OUTPUT], s));
-    CANARY("EV_OUTPUT");
-    hipLaunchKernelGGL(k_fold_stats, dim3(1), dim3(64), 0, s, w.si, pre_extra);          // (outside the timed step: a convenience of gce_stats_device)
-    if ((rc = read_si(e)) != GCE_OK) return rc;
-    HIPCHK(hipGetLastError());
-#ifdef GCE_SI_CHECK       // debugging build: the post block's histogram only ever has entry 1 (outputPair: addMolecule(1, PE)) -- anything else is a stray write
-    {
+#ifdef GCE_SI_CHECK
+    void si_check() {       // the post block's histogram only ever has entry 1 (outputPair: addMolecule(1, PE)) -- anything else is a stray write
         bool badw = false;
         for (int k = 14; k < GCE_STATS_WORDS; k++) if ((k != 15 && e->h_si.post[k] != 0) || e->h_si.pre[k] < 0) badw = true;
-        if (badw) {
-            StreamInfo again; (void)hipMemcpy(&again, e->si.p, sizeof again, hipMemcpyDeviceToHost);
-            fprintf(stderr, "SI_CHECK: N %lld NG %u C %u n_out %llu\n post:", (long long)N, NG, C, (unsigned long long)e->h_si.n_out);
-            for (int k = 0; k < 30; k++) fprintf(stderr, " %lld", e->h_si.post[k]);
-            fprintf(stderr, "\n post again:"); for (int k = 0; k < 30; k++) fprintf(stderr, " %lld", again.post[k]);
-            fprintf(stderr, "\n pre:"); for (int k = 0; k < 30; k++) fprintf(stderr, " %lld", e->h_si.pre[k]);
-            fprintf(stderr, "\n other nonzero post words:"); for (int k = 30; k < GCE_STATS_WORDS; k++) if (e->h_si.post[k]) fprintf(stderr, " [%d]=%lld", k, e->h_si.post[k]);
-            fprintf(stderr, "\n post_slot col 0..7 sums:"); for (int k = 0; k < 8; k++) { long long a = 0; for (int q = 0; q < GCE_PRE_SLOTS; q++) a += e->h_si.post_slot[q][k]; fprintf(stderr, " %lld", a); }
-            fprintf(stderr, "\n scalars: n_clustered %llu n_slow %u n_deep %u n_slow_pair %u n_gen %llu n_pf %llu n_pq %llu vote_weight %llu\n", e->h_si.n_clustered, e->h_si.n_slow, e->h_si.n_deep, e->h_si.n_slow_pair, (unsigned long long)(e->h_si.hand_on >> 32), e->h_si.n_pf_items, e->h_si.n_pq_items, e->h_si.vote_weight);
-        }
+        if (!badw) return;
+        StreamInfo again; (void)hipMemcpy(&again, e->si.p, sizeof again, hipMemcpyDeviceToHost);
+        fprintf(stderr, "SI_CHECK: N %lld NG %u C %u n_out %llu\n post:", (long long)N, NG, C, (unsigned long long)e->h_si.n_out);
+        for (int k = 0; k < 30; k++) fprintf(stderr, " %lld", e->h_si.post[k]);
+        fprintf(stderr, "\n post again:"); for (int k = 0; k < 30; k++) fprintf(stderr, " %lld", again.post[k]);
+        fprintf(stderr, "\n pre:"); for (int k = 0; k < 30; k++) fprintf(stderr, " %lld", e->h_si.pre[k]);
+        fprintf(stderr, "\n other nonzero post words:"); for (int k = 30; k < GCE_STATS_WORDS; k++) if (e->h_si.post[k]) fprintf(stderr, " [%d]=%lld", k, e->h_si.post[k]);
+        fprintf(stderr, "\n post_slot col 0..7 sums:"); for (int k = 0; k < 8; k++) { long long a = 0; for (int q = 0; q < GCE_PRE_SLOTS; q++) a += e->h_si.post_slot[q][k]; fprintf(stderr, " %lld", a); }
+        fprintf(stderr, "\n scalars: n_clustered %llu n_slow %u n_deep %u n_slow_pair %u n_gen %llu n_pf %llu n_pq %llu vote_weight %llu\n", e->h_si.n_clustered, e->h_si.n_slow, e->h_si.n_deep, e->h_si.n_slow_pair, (unsigned long long)(e->h_si.hand_on >> 32), e->h_si.n_pf_items, e->h_si.n_pq_items, e->h_si.vote_weight);
     }
 #endif
-    e->h_si.n_groups = NG;
-    float ms = 0;
-    auto el = [&](int a, int c) { ms = 0; (void)hipEventElapsedTime(&ms, e->ev[a], e->ev[c]); return (double)ms; };
-    e->timing.total_ms = el(EV_START, EV_OUTPUT);
-    e->timing.cluster_ms = el(EV_START, EV_CLUSTER); e->timing.csr_ms = el(EV_CLUSTER, EV_CSR); e->timing.describe_ms = el(EV_CSR, EV_DESCRIBE);
-    e->timing.pairing_ms = el(EV_DESCRIBE, EV_PAIRING); e->timing.score_ms = el(EV_PAIRING, EV_SCORE); e->timing.consensus_ms = el(EV_SCORE, EV_CONSENSUS);
-    e->timing.finish_ms = el(EV_CONSENSUS, EV_FINISH); e->timing.output_ms = el(EV_FINISH, EV_OUTPUT);
-    e->timing.n_clusters = C; e->timing.n_groups = NG;
-    if (e->dev_error != 0) {
-        char buf[160]; snprintf(buf, sizeof buf, "%s (read %u)", gce_status_message(e->dev_error), e->dev_error_read);
-        return fail(e, e->dev_error, buf);
-    }
-    e->n_out = (int64_t)e->h_si.n_out;
-    e->out_seq_bytes = (size_t)(e->h_si.out_units >> 32) * 16; e->out_qual_bytes = (size_t)(e->h_si.out_units & 0xFFFFFFFFull) * 16;
-    e->timing.n_pairs = (int64_t)e->h_si.n_pairs_total; e->timing.n_leaders = (int64_t)e->h_si.n_leaders;
+};
+}  // namespace
+#undef TAKE
+
+static int gce_process_impl(gce_engine *e) {
+    if (!e) return GCE_ERR_INVALID;
+    Step st(e);
+    int (Step::*const stages[])() = {&Step::check_and_cut, &Step::stage_constants, &Step::size_by_reads, &Step::form_clusters, &Step::describe,
+                                     &Step::pair_clusters, &Step::consensus, &Step::output_table, &Step::close_step};
+    for (auto stage : stages) { const int rc = (st.*stage)(); if (rc != GCE_OK) return rc; }
     return GCE_OK;
 }
 

@@ -1,6 +1,7 @@
 // gce_kernels.hpp — HIP kernels of the MI355X consensus engine (gfx950, wave64).
 //
-// Pipeline (one gce_process call, everything resident in HBM; engine.hip launches them in this order):
+// Pipeline (one gce_process call, everything resident in HBM; engine.hip launches them in this order, in the stages of its Step:
+// form_clusters, describe, pair_clusters, consensus, output_table):
 //   k_cluster        THE CLUSTERING SCAN (gce_cluster.hpp): class, key (tid,left,right), block-level leaders -> (leader, rank) per read
 //   k_blk_scan, k_events   ticks of the scan blocks; the reads on which the reference's periodic flush fires (gencore.cpp:319-322)
 //   k_leaders        one lane per leader: instance from the flush events, bucket table -> cluster of every leader run

@@ -22,6 +22,12 @@
 #define DV_DONE 2                // gen_flag value: side finished here
 
 struct DVoter { uint64_t so, qo; int rl, ld; uint32_t patch, pad; };
+// the packed tallies of k_vote_deep against their bounds.  A lane's register tally sees DV_CHUNK / 16 voters per chunk, each with a biased score and a
+// quality of one byte (make_dev_params: score_max + score_bias <= 255; qualities >= 128 back the side out): the 16-bit lanes of S02 / S13 / Q02 / Q13 hold them.
+static_assert((DV_CHUNK / 16) * 255 <= 0xFFFF, "16-bit score and quality lanes of k_vote_deep's register tallies");
+// The LDS tally is count (16) | biased score sum (24) | quality sum (24): k_deep_prepare hands over sides of nv < 65536 voters only, each adding at most 255
+static_assert(65535 * 255 < (1 << 24), "24-bit score and quality sums of k_vote_deep's LDS tallies");
+static_assert(DV_COLS == 16 * 32 && DV_CHUNK == DV_T, "dv_slot's 16 x 32 layout; one staged voter per thread");
 
 // column -> LDS slot: a lane owns 16 adjacent columns, so one atomic instruction of a wave touches columns 16 apart: column j of every
 // 16-column run goes to the j-th group of 32 slots (DV_COLS = 512 = 16 x 32), and the lanes land on consecutive slots

@@ -69,6 +69,9 @@ CASES = [
     # the score byte: max + bias = 250 + 4 + 1 = 255 fits (top byte of lut 251 = 0xFB), 251 + 4 + 1 = 256 does not
     ("score_high_250", dict(score_high=250), dict(max=254, lut=0xFB070503, vote_ok=0, why=ABOVE_116)),
     ("score_high_251", dict(score_high=251), None),
+    # the score byte at its limit with every score inside the reference's `char`: high 123 + 4 = 127, bad -125 - 3 = -128, bias = 3 + 125 = 128,
+    # max + bias = 255; lut = (-125, 4, 6, 123) + 128 = 03 84 86 FB; accept: min(6, 123, -125 + 4) < 6
+    ("score_byte_255", dict(score_high=123, score_bad=-125), dict(bias=128, max=127, lut=0xFB868403, min_lb=-125, vote_ok=0, accept=0, why=BELOW_0)),
     # ticks: 25000 = 2 x 10000 + 5000; a batch that brings its own ticks starts at 0 and has no trailing flush
     ("tick_25000", dict(tick_offset=25000, trailing_flush=1), dict(tick_offset=25000, tick_epoch0=2, tick_rem0=5000, trailing=1)),
     ("own_ticks", dict(tick_offset=25000, trailing_flush=1, have_tick=1), {}),

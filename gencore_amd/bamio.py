@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp and bamio_calmd.hpp:
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp and bamio_umi.hpp:
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -235,6 +235,37 @@ def calmd_bam_stream(in_path, out_path, fasta, device=0, threads=0, level=6, win
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     return CalmdRun(r, sr)
+
+
+class UmiRun:
+    """gce_umi_run as an object: one attribute per field (counters and bytes as int, times as float)."""
+
+    def __init__(self, r):
+        for n, t in type(r)._fields_:
+            setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+
+    def as_dict(self):
+        return dict(vars(self))
+
+
+def umi_to_mi(in_path, out_path, source="RX", device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0, resident_bytes=0):
+    """gce_bam_umi_to_mi: the UMI of every record of a BAM file, from the Z field tagged `source` (RX: fgbio, DRAGEN, `bwa mem -C`) or from the
+    last `:`-field of the read name (source="name": bcl-convert's ...:ACGT+TTGA), into an MI:Z field in the form the run reads
+    (src/bamutil.cpp:23-38): upper case, `-` and `+` as `_`, behind a `:`; MI fields the record had are dropped, everything else is kept.  A
+    record without such a field, or whose string is not a UMI (a byte other than ACGTNacgtn-+_, more than one separator, one at either end,
+    more than 250 bytes), is copied whole.  Streamed as calmd_bam_stream within device_budget_bytes (0 = auto); resident_bytes forces the
+    cap on resident output.  Returns a UmiRun (n_records, n_tagged, n_no_source, n_not_umi, n_mi_dropped, n_flushes, inflated_bytes,
+    out_record_bytes, out_bytes, peak_device_bytes, read_s, inflate_index_s, umi_s, write_s, total_s); raises GceError with the library's
+    message (and leaves no output) on failure."""
+    from .capi import GceUmiRun
+    lib = capi.load_library()
+    r = GceUmiRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_umi_to_mi(str(in_path).encode(), str(out_path).encode(), str(source).encode(), int(device), int(threads), int(level), int(window_bytes),
+                               int(device_budget_bytes), int(resident_bytes), C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    return UmiRun(r)
 
 
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):

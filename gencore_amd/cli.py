@@ -26,6 +26,11 @@ The report is not changed by it.  --device_memory bounds it (and --calmd_in) as 
 is read, so neither the input nor the output has to fit the device (the reference bases do).
 --calmd_in (not the reference's) recomputes NM and MD of the input BAM the same way first, into a temporary BAM: an input whose records lack NM
 stops the run with GCE_ERR_NM_MISSING otherwise.
+--umi_from (not the reference's) takes a file whose UMIs are not where the reference looks for them (the last `:`-field of an MI:Z value or of the
+read name, of A C G T with at most one `_`): --umi_from RX reads them from the RX:Z tag that fgbio, DRAGEN and `bwa mem -C` pipelines write
+(ACGT-TTGA for duplex), --umi_from name from an Illumina read name (...:ACGT+TTGA).  The GPU first writes a temporary BAM in which every such
+record carries its UMI as MI:Z (upper case, - and + as _), which the run then reads as the reference reads MI:Z; records without the tag, or
+whose value is not a UMI, are left as they are.  Without the flag such a file runs with every UMI empty: all reads of one position pair merge.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -100,6 +105,10 @@ def build_parser():
     a("--calmd_in", action="store_true", help="[gencore_amd] recompute NM and MD of the input BAM against -r on the GPU first (after --sort / --sort_sam; on the first of --devices, "
                                                "into a temporary BAM beside the output that is removed afterwards), then run on that file: an input without NM "
                                                "becomes runnable. It honours the --device_memory budget as --calmd does. Off by default.")
+    a("--umi_from", default=None, metavar="TAG|name",
+      help="[gencore_amd] where the UMIs are: a two-character tag whose Z value holds them (RX), or name for the last `:`-field of an Illumina read "
+           "name (ACGT+TTGA). The GPU first copies them into MI:Z fields (after --sort / --sort_sam and --calmd_in; on the first of --devices, into a "
+           "temporary BAM beside the output that is removed afterwards, within --device_memory), then runs on that file. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -128,7 +137,21 @@ def validate(o):
         err("--sort_sam needs an input file, not STDIN")
     if o.calmd_in and o.input == "-":
         err("--calmd_in needs an input file, not STDIN")
+    if o.umi_from is not None:
+        u = o.umi_from
+        if u != "name" and not (len(u) == 2 and u.isascii() and u[0].isalpha() and u[1].isalnum()):
+            err("--umi_from should be a two-character tag such as RX, or name, got '%s'" % u)
+        if u == "MI":
+            err("--umi_from MI is what the run reads without the flag")
+        if o.input == "-":
+            err("--umi_from needs an input file, not STDIN")
+        if o.umi_prefix != "auto":
+            err("--umi_from cannot be combined with --umi_prefix")
     check_file_valid(o.input)
+    if o.umi_from is not None and not o.sort_sam:
+        with open(o.input, "rb") as f:
+            if f.read(2) != b"\x1f\x8b":
+                err("--umi_from needs BAM input, not SAM text")
     if o.calmd_in and not o.sort_sam:
         with open(o.input, "rb") as f:
             if f.read(2) != b"\x1f\x8b":
@@ -202,7 +225,8 @@ def params_of(o):
     return default_params(cluster_size_req=o.supporting_reads, score_percent_req=o.ratio_threshold, base_score_req=o.score_threshold,
                           proper_umi_diff_threshold=o.umi_diff_threshold, duplex_mismatch_threshold=o.duplex_diff_threshold,
                           high_quality=o.high_qual, moderate_quality=o.moderate_qual, low_quality=o.low_qual,
-                          duplex_only=int(o.duplex_only), disable_duplex=int(o.no_duplex), max_contig=o.quit_after_contig, umi_prefix=o.umi_prefix)
+                          duplex_only=int(o.duplex_only), disable_duplex=int(o.no_duplex), max_contig=o.quit_after_contig,
+                          umi_prefix="" if o.umi_from is not None else o.umi_prefix)    # (--umi_from: the MI:Z the pass wrote; auto would look at names)
 
 
 def main(argv=None):
@@ -217,10 +241,10 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import calmd_bam_stream, index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam
+    from .bamio import calmd_bam_stream, index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
     from .capi import GceError
     from .report import read_header, summary, write_json
-    sorted_tmp = calmd_tmp = out_tmp = None
+    sorted_tmp = calmd_tmp = umi_tmp = out_tmp = None
     tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged
@@ -236,6 +260,13 @@ def main(argv=None):
             os.close(fd)
             calmd_bam_stream(o.input, calmd_tmp, o.ref, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
             o.input = calmd_tmp
+        if o.umi_from is not None:                                          # as --sort: the runners read the temporary file
+            import tempfile
+            fd, umi_tmp = tempfile.mkstemp(suffix=".bam", prefix="gencore_umi_", dir=tmp_dir)
+            os.close(fd)
+            r = umi_to_mi(o.input, umi_tmp, o.umi_from, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
+            sys.stderr.write("umi: %d records, MI written in %d, no source in %d, not a UMI in %d\n" % (r.n_records, r.n_tagged, r.n_no_source, r.n_not_umi))
+            o.input = umi_tmp
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
@@ -261,7 +292,7 @@ def main(argv=None):
         print("ERROR: %s%s" % (e, hint), file=sys.stderr)
         return 255
     finally:
-        for tmp in (sorted_tmp, calmd_tmp, out_tmp):
+        for tmp in (sorted_tmp, calmd_tmp, umi_tmp, out_tmp):
             if tmp is not None and os.path.exists(tmp):
                 os.remove(tmp)
     t2 = int(time.time())

@@ -30,6 +30,26 @@ int calmd_contigs(SortJob &j, const char *fasta_path, gce_fasta **fa, std::vecto
     return GCE_OK;
 }
 
+// the streamed runners (gce_bam_calmd_stream, gce_bam_umi_to_mi): the budget when the caller gives none, a fraction of the free device memory
+int stream_auto_budget(SortJob &j, int32_t device, uint64_t *budget) {
+    size_t fr = 0, tot = 0;
+    const int r0 = gce_device_mem_info(device, &fr, &tot);
+    if (r0 != GCE_OK) return j.fail(r0, "no HIP device");
+    *budget = std::max<uint64_t>((uint64_t)((double)fr * GCE_PASS_BUDGET_FRACTION), 1);
+    return GCE_OK;
+}
+// ... and their flush callback: the first n resident bytes are written as members and let go; s: the seconds flushes took
+struct StreamFlush { SortJob *j; double s; };
+int stream_flush(void *ctx, uint64_t n) {
+    StreamFlush &f = *(StreamFlush *)ctx;
+    const double f0 = now_s();
+    int r = f.j->host_room(n);
+    if (r == GCE_OK) r = f.j->write_range(n);
+    if (r == GCE_OK && (r = gce_sort_calmd_consume(f.j->b, n)) != GCE_OK) r = f.j->fail(r, gce_sort_error(f.j->b));
+    f.s += now_s() - f0;
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -94,12 +114,7 @@ int gce_bam_calmd_stream(const char *in_path, const char *out_path, const char *
     const int32_t n_ref = j.n_ref;
     out->n_ref = n_ref;
     uint64_t budget = device_budget_bytes;
-    if (!budget) {
-        size_t fr = 0, tot = 0;
-        const int r0 = gce_device_mem_info(device, &fr, &tot);
-        if (r0 != GCE_OK) return done(j.fail(r0, "no HIP device"));
-        budget = std::max<uint64_t>((uint64_t)((double)fr * GCE_PASS_BUDGET_FRACTION), 1);
-    }
+    if (!budget) { const int r0 = stream_auto_budget(j, device, &budget); if (r0 != GCE_OK) return done(r0); }
     // ---- rule R: the contigs by the header's names
     double t0 = now_s();
     std::vector<const char *> seq; std::vector<int64_t> len;
@@ -114,16 +129,8 @@ int gce_bam_calmd_stream(const char *in_path, const char *out_path, const char *
     gce_fasta_free(fa); fa = nullptr;
     // ---- rule F from the first window on: the header's members now, the record stream's as they are flushed
     if ((rc = j.begin_output(0)) != GCE_OK) return done(rc);
-    struct Flush { SortJob *j; double s; } fl = {&j, 0};
-    auto flush = [](void *ctx, uint64_t n) {
-        Flush &f = *(Flush *)ctx;
-        const double f0 = now_s();
-        int r = f.j->host_room(n);
-        if (r == GCE_OK) r = f.j->write_range(n);
-        if (r == GCE_OK && (r = gce_sort_calmd_consume(f.j->b, n)) != GCE_OK) r = f.j->fail(r, gce_sort_error(f.j->b));
-        f.s += now_s() - f0;
-        return r;
-    };
+    StreamFlush fl = {&j, 0};
+    auto flush = stream_flush;
     // ---- the file from its first byte, window by window: the GPU inflates, indexes and rewrites the records behind the resident output
     rc = j.stream(&out->read_s, &out->inflate_index_s, [&](PassReader &rd, uint64_t sk, uint64_t est) {
         return gce_sort_calmd_stream_window(j.b, rd.comp.data(), rd.used, (int32_t)rd.blocks.size(), rd.z_coff.data(), rd.z_csize.data(), rd.z_usize.data(), sk, n_ref, rd.last_piece() ? 1 : 0, est,

@@ -16,6 +16,8 @@
 // calmd::copy_body are __host__ __device__: tests/calmd_host_check.hip runs them on the host against tests/pycalmd.py, the model of the rules.
 // A record with more than two NM / MD fields has more than three kept stretches: its kept fields are copied by md_record<true> as it walks
 // them, and copy_body leaves them alone.
+// The window loop, the streamed output and the finish are written over "a record rewriter" (rewrite_window, rewrite_finish): calmd is one,
+// the UMI pass of gce_umi.hpp the other, which also uses field_bytes (rule T's step) and copy_body.
 #pragma once
 #include <cstdint>
 #include "gce_copy16.hpp"
@@ -45,6 +47,27 @@ CM_HD uint32_t code16(uint8_t b) {
     return (uint32_t)((k < 16 ? 0xFFF3FCFFB4FFD2E1ull >> (4 * k) : 0xFFFFFFFAF97F865Full >> (4 * (k - 16))) & 15u);
 }
 CM_HD uint8_t md_letter(uint8_t b) { return b >= 'A' && b <= 'Z' ? b : (uint8_t)'N'; }
+
+// rule T, one step: the optional field at p (tag, type, value) inside [p, end), p < end.  fs: the bytes of its value (the field takes 3 + fs).
+// false: fewer than 3 bytes are left, an unknown type or array subtype, a Z / H value without its NUL, or a value that passes `end`.
+CM_HD bool field_bytes(const uint8_t *p, const uint8_t *end, uint64_t &fs) {
+    if ((uint64_t)(end - p) < 3) return false;
+    const uint8_t type = p[2]; const uint8_t *v = p + 3; const uint64_t left = (uint64_t)(end - v);
+    if (type == 'A' || type == 'c' || type == 'C') fs = 1;
+    else if (type == 's' || type == 'S') fs = 2;
+    else if (type == 'i' || type == 'I' || type == 'f') fs = 4;
+    else if (type == 'd') fs = 8;
+    else if (type == 'Z' || type == 'H') { uint64_t n = 0; while (n < left && v[n]) n++; fs = n + 1; }               // (no NUL: n + 1 > left)
+    else if (type == 'B') {
+        if (left < 5) return false;
+        const uint8_t sub = v[0]; const uint64_t cnt = *(const cm_u32u *)(v + 1);
+        const uint32_t es = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : (sub == 'i' || sub == 'I' || sub == 'f') ? 4u : 0u;
+        if (!es) return false;
+        fs = 5 + es * cnt;
+    }
+    else return false;
+    return fs <= left;
+}
 
 // One record (r at its block_size, `avail` bytes from r to the end of the buffer).  EMIT == false: R is filled.  EMIT == true: R is the size
 // pass's; the NM field and the MD field are written at their place in the new record at `out` (and, R.many, the kept fields in front of
@@ -80,23 +103,9 @@ template <bool EMIT> CM_HD void md_record(const uint8_t *r, uint64_t avail, cons
     // ---- rule T: the optional fields tile [ax, end) exactly; every NM and MD is dropped
     uint32_t ndrop = 0, kept = 0; bool has_nm = false, nm_int = false, has_md = false; int64_t nm_old = 0; const uint8_t *md_old = nullptr; uint64_t md_old_len = 0;
     for (const uint8_t *p = ax; p < end;) {
-        if ((uint64_t)(end - p) < 3) { if (!EMIT) R.bad = 1; return; }
-        const uint8_t type = p[2]; const uint8_t *v = p + 3; const uint64_t left = (uint64_t)(end - v);
         uint64_t fs;
-        if (type == 'A' || type == 'c' || type == 'C') fs = 1;
-        else if (type == 's' || type == 'S') fs = 2;
-        else if (type == 'i' || type == 'I' || type == 'f') fs = 4;
-        else if (type == 'd') fs = 8;
-        else if (type == 'Z' || type == 'H') { uint64_t n = 0; while (n < left && v[n]) n++; fs = n + 1; }               // (no NUL: n + 1 > left)
-        else if (type == 'B') {
-            if (left < 5) { if (!EMIT) R.bad = 1; return; }
-            const uint8_t sub = v[0]; const uint64_t cnt = *(const cm_u32u *)(v + 1);
-            const uint32_t es = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : (sub == 'i' || sub == 'I' || sub == 'f') ? 4u : 0u;
-            if (!es) { if (!EMIT) R.bad = 1; return; }
-            fs = 5 + es * cnt;
-        }
-        else { if (!EMIT) R.bad = 1; return; }
-        if (fs > left) { if (!EMIT) R.bad = 1; return; }
+        if (!field_bytes(p, end, fs)) { if (!EMIT) R.bad = 1; return; }
+        const uint8_t type = p[2]; const uint8_t *v = p + 3;
         const bool is_nm = p[0] == 'N' && p[1] == 'M', is_md = p[0] == 'M' && p[1] == 'D';
         if (is_nm || is_md) {
             if (!EMIT) {
@@ -325,12 +334,19 @@ int gce_sort_calmd_ref(gce_sort *b, int32_t n_ref, const char *const *seq, const
     return GCE_OK;
 }
 
-// the next piece of the file, as gce_sort_window takes it: its whole records are rewritten (rules E, W, T) behind the resident output.
-// est_bytes: the caller's estimate of the file's inflated bytes; *calmd_s: the seconds of the calmd kernels and their scan, added to.
-// GCE_ERR_INVALID names the lowest record whose optional fields do not tile its block_size, counting from 0 over the file.
-static int calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
-                        int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, calmd_flush_fn flush, void *ctx) {
-    if (!b || !b->calmd || !b->cm_tab.p || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
+}  // extern "C"
+
+// A window of a gce_sort object in calmd mode under a record rewriter RW (calmd's own below, the UMI pass of gce_umi.hpp): the next piece of
+// the file, as gce_sort_window takes it; its whole records are rewritten behind the resident output.  RW gives
+//   meta_bytes          the bytes per record that its size pass leaves for its emit in cm_meta (cm_size and cm_dst are the window's)
+//   size(nb, ...)       launches the size pass: cm_size[i], cm_meta[i], misc[0] the lowest malformed record (atomicMin), misc[1..4] its counters
+//   emit(nb, ..., out)  launches what writes the new records at out + cm_dst[i]
+//   bad_fmt             the message for the lowest malformed record (one %llu)
+// est_bytes: the caller's estimate of the file's inflated bytes; *calmd_s: the seconds of the rewriter's kernels and their scan, added to.
+// GCE_ERR_INVALID names the lowest malformed record, counting from 0 over the file.
+template <class RW> static int rewrite_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                                              int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, calmd_flush_fn flush, void *ctx, const RW &rw) {
+    if (!b || !b->calmd || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
     int rc;
@@ -345,22 +361,21 @@ static int calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_
         {   // 40 bytes per window record: size, description, destination
             uint64_t add = 0;
             if (n_rec * 4 > b->cm_size.cap) add += DevBuf::padded(n_rec * 4);
-            if (n_rec * sizeof(calmd::Meta) > b->cm_meta.cap) add += DevBuf::padded(n_rec * sizeof(calmd::Meta));
+            if (n_rec * rw.meta_bytes > b->cm_meta.cap) add += DevBuf::padded(n_rec * rw.meta_bytes);
             if ((n_rec + 1) * 8 > b->cm_dst.cap) add += DevBuf::padded((n_rec + 1) * 8);
             if (add && !sort_room(b, add)) return sort_oom(b, "the sizes and destinations of a window's records", add);
-            SCHK(b->cm_size.ensure(n_rec * 4)); SCHK(b->cm_meta.ensure(n_rec * sizeof(calmd::Meta))); SCHK(b->cm_dst.ensure((n_rec + 1) * 8));
+            SCHK(b->cm_size.ensure(n_rec * 4)); SCHK(b->cm_meta.ensure(n_rec * rw.meta_bytes)); SCHK(b->cm_dst.ensure((n_rec + 1) * 8));
         }
-        const calmd::Ref ref = {b->cm_blob.as<uint8_t>(), b->cm_tab.as<int64_t>(), n_ref};
         const uint8_t *u = (const uint8_t *)b->w.win.p; const uint64_t *off = (const uint64_t *)b->w.idx.off.p;
         const unsigned nb = (unsigned)((n_rec + 255) / 256);
-        hipLaunchKernelGGL(k_md_size, dim3(nb), dim3(256), 0, s, u, off, n_rec, end, b->n, ref, b->cm_size.as<uint32_t>(), b->cm_meta.as<calmd::Meta>(), b->misc.as<unsigned long long>());
+        rw.size(nb, s, u, off, n_rec, end, b->n);
         SCHK(hipGetLastError());
         SCHK(dev_exclusive_sum((const uint32_t *)b->cm_size.p, n_rec, b->cm_dst.as<uint64_t>(), b->tmp, s));
         uint64_t wtotal = 0; unsigned long long bad = ~0ull;
         SCHK(hipMemcpyAsync(&wtotal, b->cm_dst.as<uint64_t>() + n_rec, 8, hipMemcpyDeviceToHost, s)); SCHK(hipMemcpyAsync(&bad, b->misc.p, 8, hipMemcpyDeviceToHost, s));
         SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
         if (bad != ~0ull) {
-            char m[256]; snprintf(m, sizeof m, "BAM record %llu (counting from 0): its optional fields do not tile its block_size, or its new MD would take it beyond 2^28 bytes", bad);
+            char m[256]; snprintf(m, sizeof m, rw.bad_fmt, bad);
             return sfail(b, GCE_ERR_INVALID, m);
         }
         const uint64_t start = std::min<uint64_t>(skip, total), in1 = b->cm_in + (end - start), seen = b->cm_flushed + b->out_n + wtotal;
@@ -374,9 +389,7 @@ static int calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_
         const uint64_t have = b->out_n + wtotal;
         if ((rc = sort_grow(b, b->out, (size_t)(have + 64), (size_t)b->out_n, (size_t)(eo + eo / 16 + 64), "the output record bytes")) != GCE_OK) return rc;
         uint8_t *out = b->out.as<uint8_t>() + b->out_n;
-        hipLaunchKernelGGL(k_md_tags, dim3(nb), dim3(256), 0, s, u, off, n_rec, end, ref, (const uint32_t *)b->cm_size.p, (const calmd::Meta *)b->cm_meta.p, (const uint64_t *)b->cm_dst.p, out);
-        hipLaunchKernelGGL(k_md_body, dim3((unsigned)std::min<uint64_t>((n_rec + 15) / 16, 65535u)), dim3(256), 0, s, u, off, n_rec, (const uint32_t *)b->cm_size.p, (const calmd::Meta *)b->cm_meta.p,
-                           (const uint64_t *)b->cm_dst.p, out);
+        rw.emit(nb, s, u, off, n_rec, end, out);
         SCHK(hipGetLastError()); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
         b->out_n = have; b->n += n_rec; b->cm_in = in1;
         if (calmd_s) *calmd_s += mono_s() - t0 - fl;
@@ -385,6 +398,30 @@ static int calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_
     b->win_need = std::max(b->win_need, sort_win_need(b->w, b->tmp));
     return rc;
 }
+
+// calmd's own rewriter (rules E, W, T): k_md_size, then k_md_tags and k_md_body
+struct CalmdRW {
+    gce_sort *b; calmd::Ref ref;
+    size_t meta_bytes = sizeof(calmd::Meta);
+    const char *bad_fmt = "BAM record %llu (counting from 0): its optional fields do not tile its block_size, or its new MD would take it beyond 2^28 bytes";
+    void size(unsigned nb, hipStream_t s, const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, uint64_t gbase) const {
+        hipLaunchKernelGGL(k_md_size, dim3(nb), dim3(256), 0, s, u, off, n_rec, end, gbase, ref, b->cm_size.as<uint32_t>(), b->cm_meta.as<calmd::Meta>(), b->misc.as<unsigned long long>());
+    }
+    void emit(unsigned nb, hipStream_t s, const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, uint8_t *out) const {
+        hipLaunchKernelGGL(k_md_tags, dim3(nb), dim3(256), 0, s, u, off, n_rec, end, ref, (const uint32_t *)b->cm_size.p, (const calmd::Meta *)b->cm_meta.p, (const uint64_t *)b->cm_dst.p, out);
+        hipLaunchKernelGGL(k_md_body, dim3((unsigned)std::min<uint64_t>((n_rec + 15) / 16, 65535u)), dim3(256), 0, s, u, off, n_rec, (const uint32_t *)b->cm_size.p, (const calmd::Meta *)b->cm_meta.p,
+                           (const uint64_t *)b->cm_dst.p, out);
+    }
+};
+static int calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, calmd_flush_fn flush, void *ctx) {
+    if (!b || !b->calmd || !b->cm_tab.p) return GCE_ERR_INVALID;
+    CalmdRW rw; rw.b = b; rw.ref = {b->cm_blob.as<uint8_t>(), b->cm_tab.as<int64_t>(), n_ref};
+    return rewrite_window(b, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, est_bytes, calmd_s, flush, ctx, rw);
+}
+
+extern "C" {
+
 int gce_sort_calmd_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                           int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s) {
     if (b && b->cm_stream) return GCE_ERR_INVALID;
@@ -429,24 +466,30 @@ int gce_sort_calmd_stream_stats(gce_sort *b, int32_t *n_flushes, uint64_t *resid
 // after the last window: the window, the reference and the descriptions are let go; counts: records, rewritten, unchanged, contig missing,
 // NM changed, MD changed; *out_bytes: the output stream's bytes, which gce_sort_read hands out.  codes >= 0: the buffers gce_sort_read
 // deflates pieces of up to piece_bytes with are made here, so that running out of device memory is known before the caller opens its output.
-int gce_sort_calmd_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int64_t counts[6], uint64_t *in_bytes, uint64_t *out_bytes) {
-    if (!b || !b->calmd || !counts || !in_bytes || !out_bytes || codes > 1) return GCE_ERR_INVALID;
+// h: the rewriter's misc[0..4] as its size pass left them (zeros for a file without records)
+static int rewrite_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, unsigned long long h[5], uint64_t *in_bytes, uint64_t *out_bytes) {
     (void)hipSetDevice(b->device);
     hipStream_t s = b->s;
     SCHK(hipStreamSynchronize(s));
     b->w.release();
     for (DevBuf *x : {&b->cm_blob, &b->cm_tab, &b->cm_size, &b->cm_meta, &b->cm_dst}) x->release();
-    for (int k = 0; k < 6; k++) counts[k] = 0;
+    for (int k = 0; k < 5; k++) h[k] = 0;
     *in_bytes = b->cm_in; *out_bytes = b->out_n;
     if (b->n == 0) return GCE_OK;
-    unsigned long long h[5];
-    SCHK(hipMemcpyAsync(h, b->misc.p, sizeof h, hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
-    counts[0] = (int64_t)b->n; counts[1] = (int64_t)h[1]; counts[2] = (int64_t)(b->n - h[1]); counts[3] = (int64_t)h[2]; counts[4] = (int64_t)h[3]; counts[5] = (int64_t)h[4];
+    SCHK(hipMemcpyAsync(h, b->misc.p, 5 * sizeof h[0], hipMemcpyDeviceToHost, s)); SCHK(hipStreamSynchronize(s)); SCHK(hipGetLastError());
     SCHK(hipMemsetAsync(b->out.as<uint8_t>() + b->out_n, 0, 64, s));                  // (the deflate kernels may look a few bytes ahead)
     SCHK(hipStreamSynchronize(s));
     if (b->cm_stream) return calmd_stream_zbufs(b, b->out_n, false);                  // (the buffers of the flushes are live: not counted twice)
     if (codes >= 0 && piece_bytes) return sort_deflate_bufs(b, std::min<uint64_t>(piece_bytes, b->out_n));
     return GCE_OK;
+}
+int gce_sort_calmd_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int64_t counts[6], uint64_t *in_bytes, uint64_t *out_bytes) {
+    if (!b || !b->calmd || !counts || !in_bytes || !out_bytes || codes > 1) return GCE_ERR_INVALID;
+    unsigned long long h[5];
+    for (int k = 0; k < 6; k++) counts[k] = 0;
+    const int rc = rewrite_finish(b, codes, piece_bytes, h, in_bytes, out_bytes);
+    if (b->n) { counts[0] = (int64_t)b->n; counts[1] = (int64_t)h[1]; counts[2] = (int64_t)(b->n - h[1]); counts[3] = (int64_t)h[2]; counts[4] = (int64_t)h[3]; counts[5] = (int64_t)h[4]; }
+    return rc;
 }
 
 }  // extern "C"

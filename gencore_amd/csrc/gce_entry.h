@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort and calmd objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp and gce_calmd.hpp.  They are exported, but
+// declare: the pass, index, sort, calmd and UMI objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp and gce_umi.hpp.  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -69,6 +69,12 @@ int gce_sort_calmd_stream_window(gce_sort *b, const void *comp, size_t comp_byte
                                  int32_t n_ref, int32_t last, uint64_t est_bytes, double *calmd_s, int (*flush)(void *ctx, uint64_t n), void *ctx);
 int gce_sort_calmd_consume(gce_sort *b, uint64_t n);
 int gce_sort_calmd_stream_stats(gce_sort *b, int32_t *n_flushes, uint64_t *resident_cap_bytes, uint64_t *flushed_bytes);
+
+// ---- the UMI of every record into an MI:Z field, on calmd's streamed output (gce_umi.hpp)
+int gce_sort_umi_begin(gce_sort *b, int32_t codes, uint64_t piece_bytes, uint64_t resident_bytes, const char *source);
+int gce_sort_umi_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, uint64_t est_bytes, double *umi_s, int (*flush)(void *ctx, uint64_t n), void *ctx);
+int gce_sort_umi_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int64_t counts[5], uint64_t *in_bytes, uint64_t *out_bytes);
 
 }  // extern "C"
 #endif

@@ -703,6 +703,29 @@ typedef struct gce_calmd_stream_run {
 int gce_bam_calmd_stream(const char *in_path, const char *out_path, const char *fasta_path, int32_t device, int threads, int level,
                          uint64_t window_bytes, size_t device_budget_bytes, uint64_t resident_bytes,
                          gce_calmd_run *out, gce_calmd_stream_run *run, char err[256]);
+/* The UMI of every record moved into an MI:Z field on ONE device, file to file (addition under ABI v3; gencore_amd/csrc/gce_umi.hpp,
+ * DESIGN.md 4h).  Replaces: nothing in the reference's source -- it feeds BamUtil::getUMI's MI:Z path (src/bamutil.cpp:23-38), which every
+ * runner here follows: a UMI is the last `:`-field of an MI:Z value or of the read name, of A C G T with at most one `_`.  A file whose UMIs are in
+ * an RX:Z tag (fgbio, DRAGEN, `bwa mem -C`: ACGT-TTGA) or in an Illumina name (...:ACGT+TTGA) runs with every UMI empty otherwise.  source: a
+ * two-character tag, or "name".  Per record: the source string s is the value of the first optional field with that tag if its type is Z, or
+ * what is behind the last `:` of the read name; a record without one (no field, no `:`, another type, s empty) is copied whole (n_no_source),
+ * and so is one whose s is not a UMI (n_not_umi): a byte other than ACGTNacgtn - + _, more than one of - + _, one of them first or last, or more
+ * than 250 bytes.  Every other record (n_tagged) loses its MI fields of any type (n_mi_dropped counts the records that had one) and gets
+ * MI:Z:":" + s, upper case and with - and + as _, behind its last kept field; block_size follows and nothing else changes.  An N is passed on:
+ * the run reads such a UMI as "", as the reference does.  The header is kept and the records stay in order.  The output is streamed as
+ * gce_bam_calmd_stream streams it, within device_budget_bytes (0: auto); resident_bytes forces the cap (0: what the budget leaves); level,
+ * window_bytes, the temporary file, the rename and an out_path that resolves to the input: as there.
+ * GCE_ERR_INVALID with a message, before a device is touched, for a NULL argument, a level outside -3..9, a source that is neither "name" nor
+ * [A-Za-z][A-Za-z0-9], source "MI" (the run reads that tag without this pass), an input that cannot be opened and SAM text; later for a
+ * record whose optional fields do not tile its block_size or whose new block_size would pass 2^28 (the message names the lowest such record,
+ * counting from 0).  A failed call leaves neither an output nor a temporary file. */
+typedef struct gce_umi_run {
+    int64_t n_records, n_tagged, n_no_source, n_not_umi, n_mi_dropped;   /* n_tagged + n_no_source + n_not_umi = n_records; n_mi_dropped of the tagged */
+    int64_t n_flushes, inflated_bytes, out_record_bytes, out_bytes, peak_device_bytes;   /* n_flushes: as gce_calmd_stream_run's */
+    double  read_s, inflate_index_s, umi_s, write_s, total_s;   /* umi_s: the k_umi_* kernels and their scan; write_s holds the flushes */
+} gce_umi_run;
+int gce_bam_umi_to_mi(const char *in_path, const char *out_path, const char *source, int32_t device, int threads, int level,
+                      uint64_t window_bytes, size_t device_budget_bytes, uint64_t resident_bytes, gce_umi_run *out, char err[256]);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp and bamio_umi.hpp:
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp and bamio_pileup.hpp:
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -266,6 +266,47 @@ def umi_to_mi(in_path, out_path, source="RX", device=0, threads=0, level=-2, win
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     return UmiRun(r)
+
+
+class PileupRun:
+    """gce_pileup_run as an object: the counters and bytes as int, the times as float, and the numpy arrays tid, pos ([n_sites], 0-based) and
+    counts ([n_sites, 2 strands, 8 classes]: A C G T N DEL INS LOWQ)."""
+    CLASSES = ("A", "C", "G", "T", "N", "DEL", "INS", "LOWQ")
+
+    def __init__(self, r):
+        for n, t in type(r)._fields_:
+            if n not in ("site_tid", "site_pos", "counts"):
+                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+        ns = self.n_sites
+        self.tid = np.ctypeslib.as_array(r.site_tid, (ns,)).copy() if ns else np.zeros(0, np.int32)
+        self.pos = np.ctypeslib.as_array(r.site_pos, (ns,)).copy() if ns else np.zeros(0, np.int32)
+        self.counts = (np.ctypeslib.as_array(r.counts, (ns * 16,)).copy() if ns else np.zeros(0, np.uint32)).reshape(ns, 2, 8)
+
+    def as_dict(self):
+        return {k: v for k, v in vars(self).items() if k not in ("tid", "pos", "counts")}
+
+
+def pileup_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_pileup: bases per strand at the sites of `bed` (the union of its regions, clamped to the contigs of the BAM's header), counted on
+    the GPU over every record with mapq >= min_mapq and no bit of exclude_flags, in any record order: per site and strand A C G T N DEL INS and
+    LOWQ (a base whose quality is below min_baseq).  tsv: the table's path (contig, 1-based pos, ref, depth, 16 counters; ref from `fasta`, N
+    without it), or None for no file.  direct=True makes every add a global atomic instead of meeting in the kernel's LDS tile: the same
+    counters.  Returns a PileupRun (n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar, n_sites,
+    n_intervals, peak_device_bytes, read_s, inflate_index_s, pileup_s, write_s, total_s, tid, pos, counts); raises GceError with the library's
+    message (and leaves no table) on failure."""
+    from .capi import GCE_PILEUP_DIRECT, GcePileupRun
+    lib = capi.load_library()
+    r = GcePileupRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_pileup(str(path).encode(), str(bed).encode(), None if fasta is None else str(fasta).encode(), None if tsv is None else str(tsv).encode(), int(device),
+                            int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), GCE_PILEUP_DIRECT if direct else 0, int(window_bytes), int(device_budget_bytes),
+                            C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return PileupRun(r)
+    finally:
+        lib.gce_pileup_free(C.byref(r))
 
 
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):

@@ -31,6 +31,12 @@ read name, of A C G T with at most one `_`): --umi_from RX reads them from the R
 (ACGT-TTGA for duplex), --umi_from name from an Illumina read name (...:ACGT+TTGA).  The GPU first writes a temporary BAM in which every such
 record carries its UMI as MI:Z (upper case, - and + as _), which the run then reads as the reference reads MI:Z; records without the tag, or
 whose value is not a UMI, are left as they are.  Without the flag such a file runs with every UMI empty: all reads of one position pair merge.
+--pileup FILE and --pileup_in FILE (not the reference's) count bases per strand at every position of the -b targets on the GPU (what
+`samtools mpileup` or `bam-readcount` are run for around a consensus step): --pileup_in over the input as the run reads it, --pileup over the
+BAM output (after --calmd), so the two tables show which mismatches consensus removed.  A table is tab-separated: contig, 1-based pos, ref (from
+-r), depth, then A C G T N DEL INS LOWQ of the forward and of the reverse strand; records with a flag bit of 0x704 (unmapped, secondary, QC
+fail, duplicate) are left out, as are those below --pileup_min_mapq, and a base below --pileup_min_baseq goes to LOWQ.  Overlapping mates are
+counted twice, there is no BAQ and no split by read group.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -109,6 +115,14 @@ def build_parser():
       help="[gencore_amd] where the UMIs are: a two-character tag whose Z value holds them (RX), or name for the last `:`-field of an Illumina read "
            "name (ACGT+TTGA). The GPU first copies them into MI:Z fields (after --sort / --sort_sam and --calmd_in; on the first of --devices, into a "
            "temporary BAM beside the output that is removed afterwards, within --device_memory), then runs on that file. Off by default.")
+    a("--pileup", default=None, metavar="FILE",
+      help="[gencore_amd] after the output is written (and after --calmd), count bases per strand at every position of the -b targets over the BAM output on the "
+           "GPU (on the first of --devices, within --device_memory) and write the table to FILE, with ref from -r. Off by default.")
+    a("--pileup_in", default=None, metavar="FILE",
+      help="[gencore_amd] the same table over the input as the run reads it (after --sort / --sort_sam, --calmd_in and --umi_from), written to FILE before the run. "
+           "Off by default.")
+    a("--pileup_min_mapq", type=int, default=0, help="[gencore_amd] --pileup / --pileup_in leave out records whose mapping quality is below this (0..255). Default 0.")
+    a("--pileup_min_baseq", type=int, default=0, help="[gencore_amd] --pileup / --pileup_in count a base whose quality is below this (0..255) as LOWQ. Default 0.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -137,6 +151,8 @@ def validate(o):
         err("--sort_sam needs an input file, not STDIN")
     if o.calmd_in and o.input == "-":
         err("--calmd_in needs an input file, not STDIN")
+    if o.pileup_in is not None and o.input == "-":
+        err("--pileup_in needs an input file, not STDIN")
     if o.umi_from is not None:
         u = o.umi_from
         if u != "name" and not (len(u) == 2 and u.isascii() and u[0].isalpha() and u[1].isalnum()):
@@ -217,6 +233,20 @@ def validate(o):
         err("--calmd needs an output file, not STDOUT")
     if o.calmd and o.output.endswith("sam"):
         err("--calmd needs BAM output, not SAM text")
+    for flag, given in (("--pileup", o.pileup), ("--pileup_in", o.pileup_in)):
+        if given is not None and not o.bed:
+            err("%s needs the targets of -b" % flag)
+    if o.pileup is not None and o.output == "-":
+        err("--pileup needs an output file, not STDOUT")
+    if o.pileup is not None and o.output.endswith("sam"):
+        err("--pileup needs BAM output, not SAM text")
+    if o.pileup_in is not None and not o.sort_sam:
+        with open(o.input, "rb") as f:
+            if f.read(2) != b"\x1f\x8b":
+                err("--pileup_in needs BAM input, not SAM text")
+    for name in ("pileup_min_mapq", "pileup_min_baseq"):
+        if not (0 <= getattr(o, name) <= 255):
+            err("%s should be 0..255" % name)
     return devices
 
 
@@ -241,10 +271,15 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import calmd_bam_stream, index_bam, load_bed, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
+    from .bamio import calmd_bam_stream, index_bam, load_bed, pileup_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = calmd_tmp = umi_tmp = out_tmp = None
+
+    def pileup(label, bam, tsv):
+        r = pileup_bam(bam, o.bed, fasta=o.ref, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.pileup_min_mapq, min_baseq=o.pileup_min_baseq,
+                       exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
+        sys.stderr.write("%s: %d records, %d eligible, %d sites\n" % (label, r.n_records, r.n_eligible, r.n_sites))
     tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged
@@ -267,6 +302,8 @@ def main(argv=None):
             r = umi_to_mi(o.input, umi_tmp, o.umi_from, device=devices[0], threads=o.threads, level=-2, device_budget_bytes=o.device_memory_bytes)
             sys.stderr.write("umi: %d records, MI written in %d, no source in %d, not a UMI in %d\n" % (r.n_records, r.n_tagged, r.n_no_source, r.n_not_umi))
             o.input = umi_tmp
+        if o.pileup_in is not None:
+            pileup("pileup_in", o.input, o.pileup_in)
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
@@ -285,6 +322,8 @@ def main(argv=None):
             r = calmd_bam_stream(o.output, out_tmp, o.ref, device=devices[0], threads=o.threads, level=o.level, device_budget_bytes=o.device_memory_bytes)
             os.replace(out_tmp, o.output)
             sys.stderr.write("calmd: %d records rewritten, NM changed in %d, MD changed in %d\n" % (r.n_rewritten, r.n_nm_changed, r.n_md_changed))
+        if o.pileup is not None:
+            pileup("pileup", o.output, o.pileup)
         if o.index:
             index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:

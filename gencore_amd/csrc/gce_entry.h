@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort, calmd and UMI objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp and gce_umi.hpp.  They are exported, but
+// declare: the pass, index, sort, calmd, UMI and pileup objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp and gce_pileup.hpp.  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -14,6 +14,7 @@ extern "C" {
 struct gce_passes;
 struct gce_bai;
 struct gce_sort;
+struct gce_pileup;
 
 int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
 
@@ -75,6 +76,15 @@ int gce_sort_umi_begin(gce_sort *b, int32_t codes, uint64_t piece_bytes, uint64_
 int gce_sort_umi_window(gce_sort *b, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                         int32_t n_ref, int32_t last, uint64_t est_bytes, double *umi_s, int (*flush)(void *ctx, uint64_t n), void *ctx);
 int gce_sort_umi_finish(gce_sort *b, int32_t codes, uint64_t piece_bytes, int64_t counts[5], uint64_t *in_bytes, uint64_t *out_bytes);
+
+// ---- bases per strand at BED targets (gce_pileup.hpp)
+int gce_pileup_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_pileup **out);
+void gce_pileup_destroy(gce_pileup *p);
+const char *gce_pileup_error(gce_pileup *p);
+int gce_pileup_set_sites(gce_pileup *p, int32_t n_ref, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, const uint32_t *site0);
+int gce_pileup_window(gce_pileup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                      int32_t n_ref, int32_t last, double *pileup_s);
+int gce_pileup_finish(gce_pileup *p, int64_t counters[8], uint32_t *counts_out);
 
 }  // extern "C"
 #endif

@@ -726,6 +726,40 @@ typedef struct gce_umi_run {
 } gce_umi_run;
 int gce_bam_umi_to_mi(const char *in_path, const char *out_path, const char *source, int32_t device, int threads, int level,
                       uint64_t window_bytes, size_t device_budget_bytes, uint64_t resident_bytes, gce_umi_run *out, char err[256]);
+/* Bases per strand at the sites of a BED file, counted on ONE device (addition under ABI v3; gencore_amd/csrc/gce_pileup.hpp).
+ * Replaces: nothing in the reference's source -- it stands in for the `samtools mpileup` / `bam-readcount` a panel's user runs on the input
+ * and on the consensus output to see which mismatches consensus removed; the reference's own report carries depth per bin and per region only
+ * (src/stats.cpp:57-84, src/bed.cpp:66-81).  Sites: the union of the BED's regions (gce_bed_load against the BAM header), each clamped to its
+ * contig, merged into intervals, in (tid, pos) order; a region on an unknown contig gives none; more than 2^28 sites is GCE_ERR_INVALID.  The
+ * file is streamed in windows of window_bytes compressed bytes (0 = 64 MB) as gce_bam_index streams it, in any record order.  A record is
+ * counted when 0 <= tid < n_ref and pos >= 0 (else n_unplaced), no bit of exclude_flags is set (n_flagged), mapq >= min_mapq (n_low_mapq),
+ * n_cigar_op > 0 (n_no_cigar), l_seq > 0 (n_no_seq), every CIGAR op is 0..8 and the CIGAR's query length is l_seq (n_bad_cigar): the first test
+ * that fails decides the counter.  Per site and strand (flag 0x10) eight uint32 counters: A C G T N DEL INS LOWQ.  An M / = / X column adds
+ * to its base's class (nibbles 1 2 4 8; every other nibble is N), or to LOWQ when the record has qualities and the base's is below min_baseq;
+ * a D column adds to DEL; an I op that follows an M / = / X / D op adds one to INS of the site in front of it; N skips; S, H, P add nothing.
+ * Overlapping mates are counted twice, there is no BAQ and no split by read group.  tsv_path (NULL: no file): a tab-separated table, a header
+ * line that begins with `#`, then one line per site: contig, 1-based pos, ref, depth (A + C + G + T + N of both strands), the forward
+ * strand's eight counters, the reverse strand's; ref is the upper-case byte of fasta_path's contig of that name, N where it has none or
+ * fasta_path is NULL (the reference never goes to the device).  The table is written to a temporary name beside tsv_path and renamed.
+ * options: GCE_PILEUP_DIRECT makes every add a global atomic (no LDS tile): the same counters, the A/B partner of the default.  Device memory:
+ * 64 bytes per site, the interval table, one window and 4 bytes per window record, within device_budget_bytes (0: no limit), else GCE_ERR_OOM
+ * with that footprint.  GCE_ERR_INVALID with a message, before a device is touched, for a NULL bam_path, bed_path or out, min_mapq or min_baseq
+ * outside 0..255, an unknown option bit, a BED or FASTA that does not exist and SAM text; later for a record whose fields overrun its
+ * block_size (the message names the lowest such record, counting from 0) and for a file whose eligible records hold 2^32 CIGAR operations or
+ * more.  A failed call leaves neither a table nor a temporary file.  site_tid, site_pos (0-based) and counts (16 per site) are malloc'ed:
+ * gce_pileup_free. */
+#define GCE_PILEUP_DIRECT 1u
+typedef struct gce_pileup_run {
+    int64_t n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar;   /* n_eligible + the six skips = n_records */
+    int64_t n_sites, n_intervals, peak_device_bytes;
+    double  read_s, inflate_index_s, pileup_s, write_s, total_s;   /* pileup_s: k_pile_scan and k_pile_count; write_s: the table */
+    int32_t *site_tid, *site_pos;   /* [n_sites] */
+    uint32_t *counts;               /* [n_sites][2 strands][8 classes] */
+} gce_pileup_run;
+int gce_bam_pileup(const char *bam_path, const char *bed_path, const char *fasta_path /* NULL: ref = N */, const char *tsv_path /* NULL: no file */,
+                   int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
+                   uint64_t window_bytes, size_t device_budget_bytes, gce_pileup_run *out, char err[256]);
+void gce_pileup_free(gce_pileup_run *out);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

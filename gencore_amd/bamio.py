@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp and bamio_pileup.hpp:
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp and bamio_errprof.hpp:
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -307,6 +307,46 @@ def pileup_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, min_mapq=0,
         return PileupRun(r)
     finally:
         lib.gce_pileup_free(C.byref(r))
+
+
+class ErrorProfileRun:
+    """gce_errprof_run as an object: the counters and bytes as int, the times as float, and the numpy array counts ([3 segments, 1024 cycles,
+    24 classes], uint64: classes 0..15 are 4 r + b over A C G T in sequencing orientation, then READ_N REF_OTHER LOWQ INS DEL and three zeros)."""
+    CLASSES = tuple("%s>%s" % (r, b) for r in "ACGT" for b in "ACGT") + ("READ_N", "REF_OTHER", "LOWQ", "INS", "DEL")
+
+    def __init__(self, r):
+        from .capi import GCE_ERRPROF_CLASSES, GCE_ERRPROF_MAX_CYCLE
+        for n, t in type(r)._fields_:
+            if n != "counts":
+                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+        self.counts = np.ctypeslib.as_array(r.counts, (3 * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES,)).copy().reshape(3, GCE_ERRPROF_MAX_CYCLE, GCE_ERRPROF_CLASSES)
+
+    def as_dict(self):
+        return {k: v for k, v in vars(self).items() if k != "counts"}
+
+
+def error_profile_bam(path, fasta, bed=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_error_profile: per segment of the pair (0: neither or both of 0x40 / 0x80, 1: first, 2: last) and sequencing cycle, the 4 x 4
+    table of reference base against read base in read orientation, and the read-N, unusable-reference, low-quality, inserted-base and deletion
+    counts, counted on the GPU over every record with mapq >= min_mapq and no bit of exclude_flags, in any record order, against the contigs of
+    `fasta` matched by name.  bed: restrict the events to the union of its regions.  tsv: the table's path (segment, cycle, bases, mismatches,
+    the 21 counters; integers, no rates), or None for no file.  direct=True makes every add a 64-bit global atomic instead of meeting in the
+    kernel's LDS planes: the same counters.  Returns an ErrorProfileRun (n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar,
+    n_no_seq, n_bad_cigar, n_no_ref, n_too_long, n_bases, n_mismatches, n_intervals (-1 without a BED), peak_device_bytes, read_s,
+    inflate_index_s, errprof_s, write_s, total_s, counts); raises GceError with the library's message (and leaves no table) on failure."""
+    from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun
+    lib = capi.load_library()
+    r = GceErrprofRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_error_profile(str(path).encode(), str(fasta).encode(), None if bed is None else str(bed).encode(), None if tsv is None else str(tsv).encode(), int(device),
+                                   int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), GCE_ERRPROF_DIRECT if direct else 0, int(window_bytes),
+                                   int(device_budget_bytes), C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return ErrorProfileRun(r)
+    finally:
+        lib.gce_errprof_free(C.byref(r))
 
 
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):

@@ -37,6 +37,14 @@ BAM output (after --calmd), so the two tables show which mismatches consensus re
 -r), depth, then A C G T N DEL INS LOWQ of the forward and of the reverse strand; records with a flag bit of 0x704 (unmapped, secondary, QC
 fail, duplicate) are left out, as are those below --pileup_min_mapq, and a base below --pileup_min_baseq goes to LOWQ.  Overlapping mates are
 counted twice, there is no BAQ and no split by read group.
+--error_profile FILE and --error_profile_in FILE (not the reference's) count, on the GPU, mismatches against -r by sequencing cycle (what `fgbio
+ErrorRateByReadPosition`, Picard's artifact metrics or the mismatches-per-cycle block of `samtools stats` are run for): --error_profile_in over
+the input as the run reads it, --error_profile over the BAM output (after --calmd), so the two tables show how far the error rate fell, by
+substitution and by read position.  A table is tab-separated: segment (1 first, 2 last of the pair, 0 otherwise), cycle, bases, mismatches, the
+sixteen counts A>A .. T>T of reference base against read base in read orientation (a reverse-strand read is complemented, so G>T stays apart
+from C>A), then READ_N REF_OTHER LOWQ INS DEL; integers only, no rates.  Records with a flag bit of 0x704 are left out, as are those below
+--error_profile_min_mapq, on a contig -r lacks or longer than 1024 bases; a base below --error_profile_min_baseq goes to LOWQ.  With -b only
+events on the targets count.  Hard clips do not count into the cycle, known variants are not masked, there is no split by read group.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -123,6 +131,16 @@ def build_parser():
            "Off by default.")
     a("--pileup_min_mapq", type=int, default=0, help="[gencore_amd] --pileup / --pileup_in leave out records whose mapping quality is below this (0..255). Default 0.")
     a("--pileup_min_baseq", type=int, default=0, help="[gencore_amd] --pileup / --pileup_in count a base whose quality is below this (0..255) as LOWQ. Default 0.")
+    a("--error_profile", default=None, metavar="FILE",
+      help="[gencore_amd] after the output is written (after --calmd, before --index), count mismatches against -r by sequencing cycle and substitution over the BAM "
+           "output on the GPU (on the first of --devices, within --device_memory) and write the table to FILE. Restricted to the -b targets when -b is given. Off by default.")
+    a("--error_profile_in", default=None, metavar="FILE",
+      help="[gencore_amd] the same table over the input as the run reads it (after --sort / --sort_sam, --calmd_in and --umi_from), written to FILE before the run. "
+           "Restricted to the -b targets when -b is given. Off by default.")
+    a("--error_profile_min_mapq", type=int, default=0,
+      help="[gencore_amd] --error_profile / --error_profile_in leave out records whose mapping quality is below this (0..255). Default 0.")
+    a("--error_profile_min_baseq", type=int, default=0,
+      help="[gencore_amd] --error_profile / --error_profile_in count a base whose quality is below this (0..255) as LOWQ. Default 0.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -153,6 +171,8 @@ def validate(o):
         err("--calmd_in needs an input file, not STDIN")
     if o.pileup_in is not None and o.input == "-":
         err("--pileup_in needs an input file, not STDIN")
+    if o.error_profile_in is not None and o.input == "-":
+        err("--error_profile_in needs an input file, not STDIN")
     if o.umi_from is not None:
         u = o.umi_from
         if u != "name" and not (len(u) == 2 and u.isascii() and u[0].isalpha() and u[1].isalnum()):
@@ -247,6 +267,17 @@ def validate(o):
     for name in ("pileup_min_mapq", "pileup_min_baseq"):
         if not (0 <= getattr(o, name) <= 255):
             err("%s should be 0..255" % name)
+    if o.error_profile is not None and o.output == "-":
+        err("--error_profile needs an output file, not STDOUT")
+    if o.error_profile is not None and o.output.endswith("sam"):
+        err("--error_profile needs BAM output, not SAM text")
+    if o.error_profile_in is not None and not o.sort_sam:
+        with open(o.input, "rb") as f:
+            if f.read(2) != b"\x1f\x8b":
+                err("--error_profile_in needs BAM input, not SAM text")
+    for name in ("error_profile_min_mapq", "error_profile_min_baseq"):
+        if not (0 <= getattr(o, name) <= 255):
+            err("%s should be 0..255" % name)
     return devices
 
 
@@ -271,7 +302,7 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import calmd_bam_stream, index_bam, load_bed, pileup_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
+    from .bamio import calmd_bam_stream, error_profile_bam, index_bam, load_bed, pileup_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = calmd_tmp = umi_tmp = out_tmp = None
@@ -280,6 +311,11 @@ def main(argv=None):
         r = pileup_bam(bam, o.bed, fasta=o.ref, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.pileup_min_mapq, min_baseq=o.pileup_min_baseq,
                        exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
         sys.stderr.write("%s: %d records, %d eligible, %d sites\n" % (label, r.n_records, r.n_eligible, r.n_sites))
+
+    def error_profile(label, bam, tsv):
+        r = error_profile_bam(bam, o.ref, bed=o.bed or None, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.error_profile_min_mapq,
+                              min_baseq=o.error_profile_min_baseq, exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
+        sys.stderr.write("%s: %d records, %d eligible, %d bases, %d mismatches\n" % (label, r.n_records, r.n_eligible, r.n_bases, r.n_mismatches))
     tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged
@@ -304,6 +340,8 @@ def main(argv=None):
             o.input = umi_tmp
         if o.pileup_in is not None:
             pileup("pileup_in", o.input, o.pileup_in)
+        if o.error_profile_in is not None:
+            error_profile("error_profile_in", o.input, o.error_profile_in)
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
@@ -324,6 +362,8 @@ def main(argv=None):
             sys.stderr.write("calmd: %d records rewritten, NM changed in %d, MD changed in %d\n" % (r.n_rewritten, r.n_nm_changed, r.n_md_changed))
         if o.pileup is not None:
             pileup("pileup", o.output, o.pileup)
+        if o.error_profile is not None:
+            error_profile("error_profile", o.output, o.error_profile)
         if o.index:
             index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:

@@ -307,6 +307,27 @@ static int calmd_stream_room(gce_sort *b, uint64_t wtotal, uint64_t target, calm
     return sort_grow(b, b->out, (size_t)(b->out_n + wtotal + 64), (size_t)b->out_n, (size_t)(want - 256), "the output record bytes");
 }
 
+// calmd::Ref on the host and its way to the device, shared with the error profile (gce_errprof.hpp).  tab: per contig the offset of its bases
+// in the blob and their length, -1 for a contig the FASTA lacks (seq[t] NULL or len[t] < 0); -> the blob's bytes
+static uint64_t calmd_ref_layout(int32_t n_ref, const char *const *seq, const int64_t *len, std::vector<int64_t> &tab) {
+    tab.assign((size_t)n_ref * 2 + 2, 0);
+    uint64_t total = 0;
+    for (int32_t t = 0; t < n_ref; t++) {
+        const bool have = seq[t] && len[t] >= 0;
+        tab[2 * (size_t)t] = (int64_t)total; tab[2 * (size_t)t + 1] = have ? len[t] : -1;
+        if (have) total += (uint64_t)len[t];
+    }
+    return total;
+}
+static hipError_t calmd_ref_upload(DevBuf &blob, DevBuf &dtab, int32_t n_ref, const char *const *seq, const int64_t *len, const std::vector<int64_t> &tab, uint64_t total, hipStream_t s) {
+    hipError_t e;
+    if ((e = blob.ensure(total + 64)) != hipSuccess || (e = dtab.ensure(tab.size() * 8)) != hipSuccess) return e;
+    for (int32_t t = 0; t < n_ref; t++)
+        if (tab[2 * (size_t)t + 1] > 0 && (e = hipMemcpyAsync(blob.as<uint8_t>() + tab[2 * (size_t)t], seq[t], (size_t)len[t], hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    return hipStreamSynchronize(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -317,20 +338,11 @@ int gce_sort_calmd_ref(gce_sort *b, int32_t n_ref, const char *const *seq, const
     if (!b || n_ref < 0 || (n_ref && (!seq || !len)) || b->n || b->passes || b->sam_text || b->cm_tab.p) return GCE_ERR_INVALID;
     (void)hipSetDevice(b->device);
     b->calmd = true;
-    std::vector<int64_t> tab((size_t)n_ref * 2 + 2, 0);
-    uint64_t total = 0;
-    for (int32_t t = 0; t < n_ref; t++) {
-        const bool have = seq[t] && len[t] >= 0;
-        tab[2 * (size_t)t] = (int64_t)total; tab[2 * (size_t)t + 1] = have ? len[t] : -1;
-        if (have) total += (uint64_t)len[t];
-    }
+    std::vector<int64_t> tab;
+    const uint64_t total = calmd_ref_layout(n_ref, seq, len, tab);
     const uint64_t want = DevBuf::padded(total + 64) + DevBuf::padded(tab.size() * 8);
     if (!sort_room(b, want)) return sort_oom(b, "the reference bases", want);
-    SCHK(b->cm_blob.ensure(total + 64)); SCHK(b->cm_tab.ensure(tab.size() * 8));
-    for (int32_t t = 0; t < n_ref; t++)
-        if (tab[2 * (size_t)t + 1] > 0) SCHK(hipMemcpyAsync(b->cm_blob.as<uint8_t>() + tab[2 * (size_t)t], seq[t], (size_t)len[t], hipMemcpyHostToDevice, b->s));
-    SCHK(hipMemcpyAsync(b->cm_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, b->s));
-    SCHK(hipStreamSynchronize(b->s));
+    SCHK(calmd_ref_upload(b->cm_blob, b->cm_tab, n_ref, seq, len, tab, total, b->s));
     return GCE_OK;
 }
 

@@ -760,6 +760,41 @@ int gce_bam_pileup(const char *bam_path, const char *bed_path, const char *fasta
                    int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
                    uint64_t window_bytes, size_t device_budget_bytes, gce_pileup_run *out, char err[256]);
 void gce_pileup_free(gce_pileup_run *out);
+/* Mismatches by read cycle against the reference, counted on ONE device (addition under ABI v3; gencore_amd/csrc/gce_errprof.hpp).
+ * Replaces: nothing in the reference's source -- it stands in for the `fgbio ErrorRateByReadPosition`, Picard artifact metrics or `samtools
+ * stats` mismatches-per-cycle a user runs on the input and on the consensus output to see how far the error rate fell; the reference's own
+ * report carries one mismatch total from NM (src/stats.cpp:103-108).  One streaming pass over bam_path in any record order.  Eligible records:
+ * gce_bam_pileup's tests in its order (n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar), then n_no_ref (fasta_path lacks
+ * the contig, matched by name as gce_bam_calmd matches it) and n_too_long (l_seq > GCE_ERRPROF_MAX_CYCLE).  Segment: 1 for flag 0x40 without
+ * 0x80, 2 for 0x80 without 0x40, else 0.  Cycle of query index y: y + 1, on the reverse strand l_seq - y (hard clips are not counted).
+ * counts[(segment * 1024 + cycle - 1) * 24 + class]; classes 0..15: 4 r + b, reference base r against read base b over A C G T in sequencing
+ * orientation (both complemented on the reverse strand); 16 READ_N, 17 REF_OTHER, 18 LOWQ, 19 INS, 20 DEL, 21..23 zero.  An M / = / X column:
+ * LOWQ when QUAL[0] != 0xFF and its quality < min_baseq, else REF_OTHER when it lies at or beyond the contig's FASTA length or the upper-cased
+ * reference byte is not A C G T, else READ_N when the read nibble is not 1, 2, 4 or 8, else 4 r + b.  Every inserted base adds INS at its own
+ * cycle; a D adds one DEL at the cycle of the query base in front of it (the first, when there is none).  bed_path (NULL: none) restricts the
+ * events to the union of its regions (clamped, merged and matched against the header as gce_bam_pileup does): a column by its own position, an
+ * inserted base by the position in front of it (its own when no M = X D came earlier), a deletion by its first position.  tsv_path (NULL: no
+ * file): a header line that begins with `#`, then per segment with a counter one line per cycle from 1 to the last with a counter: segment,
+ * cycle, bases (classes 0..15), mismatches (the off-diagonal ones), the sixteen A>A .. T>T, READ_N REF_OTHER LOWQ INS DEL; written to a
+ * temporary name and renamed.  options: GCE_ERRPROF_DIRECT makes every add a 64-bit global atomic (no LDS planes): the same counters, the A/B
+ * partner of the default.  Device memory: the reference bases, 576 KiB of counters, the interval table, one window and 4 bytes per window
+ * record, within device_budget_bytes (0: no limit), else GCE_ERR_OOM with that footprint.  GCE_ERR_INVALID with a message, before a device is
+ * touched, for a NULL bam_path, fasta_path or out, min_mapq or min_baseq outside 0..255, an unknown option bit, a FASTA or BED that does not
+ * exist and SAM text; later for a record whose fields overrun its block_size (the message names the lowest such record, counting from 0).  A
+ * failed call leaves neither a table nor a temporary file.  counts (3 x 1024 x 24) is malloc'ed: gce_errprof_free. */
+#define GCE_ERRPROF_DIRECT 1u
+#define GCE_ERRPROF_MAX_CYCLE 1024
+#define GCE_ERRPROF_CLASSES 24
+typedef struct gce_errprof_run {
+    int64_t n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar, n_no_ref, n_too_long;   /* n_eligible + the eight skips = n_records */
+    int64_t n_bases, n_mismatches, n_intervals /* -1: no BED */, peak_device_bytes;
+    double  read_s, inflate_index_s, errprof_s, write_s, total_s;   /* errprof_s: k_err_scan and k_err_count; write_s: the table */
+    uint64_t *counts;               /* [3 segments][1024 cycles][24 classes] */
+} gce_errprof_run;
+int gce_bam_error_profile(const char *bam_path, const char *fasta_path, const char *bed_path /* NULL: no BED */, const char *tsv_path /* NULL: no file */,
+                          int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
+                          uint64_t window_bytes, size_t device_budget_bytes, gce_errprof_run *out, char err[256]);
+void gce_errprof_free(gce_errprof_run *out);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

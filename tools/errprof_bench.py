@@ -1,0 +1,166 @@
+#!/usr/bin/env python
+"""gce_bam_error_profile with its LDS planes beside the same pass with direct atomics (GCE_ERRPROF_DIRECT) and beside gce_bam_index, the
+streaming floor over the same file: the cfg3 stream of tools/bam_bench.py as a BAM file, without a BED and with its panel as BED.
+    python tools/errprof_bench.py [--workload cfg3] [--pairs 4000000] [--reps 3] [--direct_limit 900] [--out profiles/errprof.json]
+The variants are interleaved; every run is a fresh child process under its own time limit (--limit; the direct variant, whose every add is a
+global atomic on a few thousand addresses, has --direct_limit, and the file is never truncated for it); one warm-up round, then --reps timed
+rounds, reported as medians with all values.  The question is which variant has the lower median errprof_s (k_err_scan + k_err_count, host
+clocks around work that ends in a device synchronise): the planes stay the default only if their median beats direct's by more than the
+spread of the values.  gce_bam_index's gpu_s (inflate, record index and the index's kernels) stands beside errprof_s + inflate_index_s so
+that the cost of the count kernels above read, inflate and index is visible.  One rocprofv3 --kernel-trace --stats run per variant, each in a
+process of its own, gives the kernel times.  There is no pass mark."""
+import argparse
+import csv
+import glob
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+MODES = ("planes", "direct", "planes_bed", "direct_bed", "index")
+
+
+def child(args):
+    import zlib
+    from gencore_amd import bamio
+    src, bed, fa = (os.path.join(args.child, n) for n in ("in.bam", "panel.bed", "ref.fa"))
+    for p in (src, fa):                                           # the inputs in the page cache
+        with open(p, "rb") as f:
+            while f.read(1 << 26):
+                pass
+    t0 = time.perf_counter()
+    if args.mode == "index":
+        d = bamio.index_bam(src, os.path.join(args.child, "in.bam.bai"), threads=args.threads)
+        d = {k: v for k, v in (d if isinstance(d, dict) else vars(d)).items() if isinstance(v, (int, float))}
+    else:
+        r = bamio.error_profile_bam(src, fa, bed=bed if args.mode.endswith("_bed") else None, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads,
+                                    direct=args.mode.startswith("direct"))
+        d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())))
+    print(json.dumps(dict(d, wall_s=time.perf_counter() - t0)), flush=True)
+
+
+def child_make(args):
+    """in.bam (the stream), ref.fa (its reference) and panel.bed (its panel) under args.child"""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("errprof_bench: no GPU; nothing is measured without one")
+    from gencore_amd import synth
+    from gencore_amd.bamio import write_batch_as_bam
+    d = synth.generate(args.workload, n_pairs=args.pairs, device=torch.device("cuda:0"))
+    batch = d.to_batch()
+    tl = np.asarray(d.target_len, np.uint32)
+    names = ["chr%d" % (i + 1) for i in range(len(tl))]
+    write_batch_as_bam(os.path.join(args.child, "in.bam"), batch, tl, names, threads=args.threads, level=1)
+    code = np.frombuffer(b"NATCG" + b"N" * 11, np.uint8)          # FastaReader's nibbles -> ASCII bases
+    ref_bytes = 0
+    with open(os.path.join(args.child, "ref.fa"), "wb") as f:
+        for nm, (nib, ln) in zip(names, d.reference_host()):
+            if nib is None:
+                continue
+            both = np.empty(len(nib) * 2, np.uint8)
+            both[0::2] = nib & 0xF
+            both[1::2] = nib >> 4
+            lines = np.concatenate([code[both[:ln]], np.zeros((-ln) % 60, np.uint8)]).reshape(-1, 60)
+            body = np.concatenate([lines, np.full((len(lines), 1), 10, np.uint8)], 1).reshape(-1)
+            f.write(b">" + nm.encode() + b" synthetic\n" + body.tobytes().replace(b"\0", b""))
+            ref_bytes += int(ln)
+    bed = np.asarray(d.info["bed"])[:, :3]
+    with open(os.path.join(args.child, "panel.bed"), "w") as f:
+        for t, a, z in bed:
+            f.write("%s\t%d\t%d\n" % (names[int(t)], int(a), int(z)))
+    print(json.dumps(dict(reads=int(batch.n), bed_regions=int(len(bed)), reference_bases=ref_bytes)), flush=True)
+
+
+def run_child(args, tmp, mode, prefix=(), limit=None):
+    limit = limit or (args.direct_limit if mode.startswith("direct") else args.limit)
+    p = subprocess.run(["timeout", "-k", "10", str(limit)] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--mode", mode, "--threads", str(args.threads),
+                                                                           "--workload", args.workload, "--pairs", str(args.pairs)], stdout=subprocess.PIPE, universal_newlines=True)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    if p.returncode != 0 or not lines:
+        raise SystemExit("errprof_bench: a child run (%s) failed (exit %d, limit %d s)" % (mode, p.returncode, limit))
+    return json.loads(lines[-1])
+
+
+def kernel_times(args, tmp, mode):
+    prof = os.path.join(tmp, "prof_" + mode)
+    run_child(args, tmp, mode, prefix=["rocprofv3", "--kernel-trace", "--stats", "-d", prof, "-o", "errprof", "--output-format", "csv", "--"])
+    kern = {}
+    for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            m = re.search(r"k_err_\w+", r["Name"])                 # (the CSV holds the demangled name)
+            if m:
+                k = kern.setdefault(m.group(0), dict(calls=0, seconds=0.0))
+                k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9
+    if not kern:
+        raise SystemExit("errprof_bench: no k_err_ row in rocprofv3's *kernel_stats.csv under %s" % prof)
+    return {n: dict(calls=k["calls"], seconds=round(k["seconds"], 6)) for n, k in sorted(kern.items())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="cfg3")
+    ap.add_argument("--pairs", type=int, default=4_000_000)
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--dir", default=None)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--limit", type=int, default=300)
+    ap.add_argument("--direct_limit", type=int, default=900)
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--mode", default="planes", choices=("make",) + MODES)
+    args = ap.parse_args()
+    if args.child is not None:
+        return child_make(args) if args.mode == "make" else child(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "errprof.json")
+    tmp = args.dir or tempfile.mkdtemp(prefix="gce_errprof_")
+    made = run_child(args, tmp, "make", limit=900)
+    per = {m: [] for m in MODES}
+    for rep in range(args.reps + 1):                               # interleaved; the first round is the warm-up
+        for m in MODES:
+            r = run_child(args, tmp, m)
+            if rep:
+                per[m].append(r)
+        print("errprof_bench: round %d done" % rep, flush=True)
+    med = lambda rs, k: sorted(r[k] for r in rs)[len(rs) // 2]
+    spread = lambda rs, k: max(r[k] for r in rs) - min(r[k] for r in rs)
+    res = dict(workload=args.workload, pairs=int(args.pairs), reps=args.reps, **made, input_bytes=os.path.getsize(os.path.join(tmp, "in.bam")),
+               clocks="the library's stage times: host clocks around work that ends in a device synchronise",
+               limits=dict(planes_s=args.limit, direct_s=args.direct_limit, direct_file="the whole file, not truncated"), variants={})
+    for m in MODES[:4]:
+        rs = per[m]
+        res["variants"][m] = dict(stages={k: round(med(rs, k), 5) for k in ("read_s", "inflate_index_s", "errprof_s", "write_s", "total_s", "wall_s")},
+                                  errprof_s_all=[round(r["errprof_s"], 5) for r in rs], total_s_all=[round(r["total_s"], 4) for r in rs], peak_device_bytes=int(rs[0]["peak_device_bytes"]),
+                                  counters={c: int(rs[0][c]) for c in rs[0] if c.startswith("n_")}, counts_sum=rs[0]["counts_sum"], counts_crc=rs[0]["counts_crc"])
+    rs = per["index"]
+    res["index"] = dict(what="gce_bam_index on the same file, interleaved: the streaming floor; not a gate",
+                        stages={k: round(med(rs, k), 5) for k in ("read_s", "gpu_s", "write_s", "total_s", "wall_s")}, gpu_s_all=[round(r["gpu_s"], 5) for r in rs],
+                        total_s_all=[round(r["total_s"], 4) for r in rs])
+    res["decision"] = {}
+    for suffix in ("", "_bed"):
+        t, d = res["variants"]["planes" + suffix], res["variants"]["direct" + suffix]
+        gap = d["stages"]["errprof_s"] - t["stages"]["errprof_s"]
+        noise = max(spread(per["planes" + suffix], "errprof_s"), spread(per["direct" + suffix], "errprof_s"))
+        res["decision"]["bed" if suffix else "no_bed"] = dict(
+            rule="the planes stay the default only if their median errprof_s beats direct's by more than the spread of the values",
+            counters_identical=t["counts_crc"] == d["counts_crc"] and t["counters"] == d["counters"], counts_sum=t["counts_sum"],
+            direct_minus_planes_s=round(gap, 5), spread_s=round(noise, 5), default="planes" if gap > noise else "direct")
+    for m in MODES[:4]:
+        v = res["variants"][m]
+        v["gpu_s_beside_index"] = dict(errprof_s=v["stages"]["errprof_s"], inflate_index_s=v["stages"]["inflate_index_s"], index_gpu_s=res["index"]["stages"]["gpu_s"])
+    for m in ("planes", "direct"):
+        res["variants"][m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -292,6 +292,18 @@ int gce_set_flush_events(gce_engine *e, int32_t n_events, const int32_t *ev_tid,
 
 // the six addRead counters of either Stats block are spread over GCE_PRE_SLOTS words each (k_describe, k_out_meta): summed into the
 // blocks themselves, the slots cleared, so that the device copy is complete (the host adds the slots of ITS copy: zeros after this)
+// where a TS_* sum goes in the two Stats blocks (one writer per target word: k_fold_stats gives every TS word its own thread).  Every pair k_group_tail
+// writes is an SSCS: addSSCS + outputPair's addMolecule(1, PE), so one count feeds post sscs, molecules and histogram entry 1.
+__host__ __device__ inline void si_add_tail(StreamInfo *si, int k, long long a) {
+    switch (k) {
+    case TS_PRE_CLUSTERS: si->pre[6] += a; break;   case TS_PRE_MULTI: si->pre[7] += a; break;   case TS_PRE_MOLECULES: si->pre[8] += a; break;
+    case TS_PRE_SE: si->pre[9] += a; break;         case TS_PRE_PE: si->pre[10] += a; break;     case TS_PRE_UNCOUNTED: si->pre[13] += a; break;
+    case TS_NPAIRS: si->n_pairs_total += (unsigned long long)a; break;
+    case TS_POST_CLUSTERS: si->post[6] += a; break; case TS_POST_MULTI: si->post[7] += a; break;
+    case TS_POST_SSCS: si->post[11] += a; si->post[8] += a; si->post[14 + 1] += a; break;
+    case TS_POST_SE: si->post[9] += a; break;       case TS_POST_PE: si->post[10] += a; break;
+    }
+}
 struct PreExtra { long long v[6]; };      // addRead of the read on which --quit_after_contig ended the loop (counted, then ignored)
 __global__ void k_fold_stats(StreamInfo *si, PreExtra x) {
     const int k = threadIdx.x;
@@ -299,6 +311,17 @@ __global__ void k_fold_stats(StreamInfo *si, PreExtra x) {
         long long a = 0, c = 0;
         for (int q = 0; q < GCE_PRE_SLOTS; q++) { a += si->pre_slot[q][k]; c += si->post_slot[q][k]; si->pre_slot[q][k] = 0; si->post_slot[q][k] = 0; }
         si->pre[k] += a + x.v[k]; si->post[k] += c;
+    }
+    // k_group_tail's share (gce_device.hpp, TS_*): one thread per scalar, then the histogram
+    if (k < TS_WORDS) {
+        long long a = 0;
+        for (int q = 0; q < GCE_TAIL_SLOTS; q++) { a += si->tail_slot[q][k]; si->tail_slot[q][k] = 0; }
+        si_add_tail(si, k, a);
+    }
+    for (int h = k; h < GCE_MAX_SUPPORTING_READS; h += blockDim.x) {
+        long long a = 0;
+        for (int q = 0; q < GCE_TAIL_HSLOTS; q++) { a += si->tail_hist[q][h]; si->tail_hist[q][h] = 0; }
+        si->pre[14 + h] += a;
     }
 }
 // --quit_after_contig: the first read whose tid >= max_contig (the stream is sorted, unmapped reads -- tid -1 -- never match)
@@ -545,18 +568,20 @@ static int upload(gce_engine *e) {
 // the interrupt-driven wake-up of the waiting thread).  Instead a one-block kernel writes the block into mapped, coherent host memory and
 // then a sequence number (system-scope fences, release store); the host spins on that word (acquire loads), looking at the stream's state
 // now and then so that a failed launch cannot hang it.  GCE_SYNC_COPY=1 takes the copy + synchronize path.
-__global__ __launch_bounds__(256) void k_publish_si(const StreamInfo *si, StreamInfo *host, unsigned long long *flag, unsigned long long seq) {
+__global__ __launch_bounds__(256) void k_publish_si(const StreamInfo *si, StreamInfo *host, unsigned long long *flag, unsigned long long seq, unsigned n_words) {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(si);
     uint32_t *dst = reinterpret_cast<uint32_t *>(host);
-    for (unsigned i = threadIdx.x; i < sizeof(StreamInfo) / 4; i += 256) dst[i] = src[i];
+    for (unsigned i = threadIdx.x; i < n_words; i += 256) dst[i] = src[i];
     __threadfence_system();                                   // my words have left for host memory ...
     __syncthreads();                                          // ... and so have everybody's
     if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-static_assert(sizeof(StreamInfo) % 4 == 0, "k_publish_si copies words");
+static_assert(sizeof(StreamInfo) % 4 == 0 && GCE_SI_HEAD_BYTES % 4 == 0, "k_publish_si copies words");
 // In two halves: the first enqueues the publishing kernel, the second waits for its word -- work that does not need the answer can be enqueued in between
 // and keeps the GPU busy while the word travels (gce_process: k_describe behind the cluster count).
-static int read_si_begin(gce_engine *e, unsigned long long *seq_out) {
+// head_only: a look inside the step, which needs none of k_group_tail's Stats slots at the block's end (they are all zero until that kernel has run, and so is
+// their place in the pinned copy: only the look behind k_fold_stats, which clears them, ever carries them)
+static int read_si_begin(gce_engine *e, unsigned long long *seq_out, bool head_only = false) {
     *seq_out = 0;
     static const bool sync_copy = getenv("GCE_SYNC_COPY") != nullptr;
     if (!sync_copy && !e->si_pin) {
@@ -571,7 +596,7 @@ static int read_si_begin(gce_engine *e, unsigned long long *seq_out) {
     if (!sync_copy && e->si_pin) {
         unsigned long long *dflag = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(e->si_pin_dev) + ((sizeof(StreamInfo) + 7) & ~size_t(7)));
         const unsigned long long seq = ++e->si_seq;
-        hipLaunchKernelGGL(k_publish_si, dim3(1), dim3(256), 0, e->stream, (const StreamInfo *)e->si.p, reinterpret_cast<StreamInfo *>(e->si_pin_dev), dflag, seq);
+        hipLaunchKernelGGL(k_publish_si, dim3(1), dim3(256), 0, e->stream, (const StreamInfo *)e->si.p, reinterpret_cast<StreamInfo *>(e->si_pin_dev), dflag, seq, (unsigned)((head_only ? GCE_SI_HEAD_BYTES : sizeof(StreamInfo)) / 4));
         HIPCHK(hipGetLastError());
         *seq_out = seq;
     }
@@ -598,12 +623,14 @@ static int read_si_end(gce_engine *e, unsigned long long seq) {
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     for (int k = 0; k < 6; k++) for (int q = 0; q < GCE_PRE_SLOTS; q++) { e->h_si.pre[k] += e->h_si.pre_slot[q][k]; e->h_si.post[k] += e->h_si.post_slot[q][k]; }    // k_describe's spread counters
+    for (int k = 0; k < TS_WORDS; k++) { long long a = 0; for (int q = 0; q < GCE_TAIL_SLOTS; q++) a += e->h_si.tail_slot[q][k]; si_add_tail(&e->h_si, k, a); }      // k_group_tail's share
+    for (int h = 0; h < GCE_MAX_SUPPORTING_READS; h++) for (int q = 0; q < GCE_TAIL_HSLOTS; q++) e->h_si.pre[14 + h] += e->h_si.tail_hist[q][h];
     if (e->h_si.err_key != ~0ull) { e->dev_error = -(int)(e->h_si.err_key & 0xFF); e->dev_error_read = (uint32_t)(e->h_si.err_key >> 8); }
     return GCE_OK;
 }
-static int read_si(gce_engine *e) {
+static int read_si(gce_engine *e, bool head_only = false) {
     unsigned long long seq = 0;
-    const int rc = read_si_begin(e, &seq);
+    const int rc = read_si_begin(e, &seq, head_only);
     return rc != GCE_OK ? rc : read_si_end(e, seq);
 }
 
@@ -673,7 +700,8 @@ struct Step {
     int64_t N = 0; size_t n1 = 1; uint32_t C = 0, NG = 0;
     PreExtra pre_extra{};
     int64_t n_sblk = 0, max_events = 0; unsigned nblk_N = 0;
-    bool si_behind_describe = false;               // the host's copy of StreamInfo holds what k_describe found (read-length range)
+    bool si_behind_describe = false;               // the host's copy of StreamInfo holds what k_describe found (read-length range, umi_us)
+    bool duplex_ran = false;                       // the duplex stage ran (k_finish): k_stats counts its clusters
     explicit Step(gce_engine *e_) : e(e_), s(e_->stream), hb(e_->dev_batch) {}
 
     // ---- call order, the upload of a host batch, the --quit_after_contig cut, the stream's size
@@ -835,7 +863,7 @@ struct Step {
     int describe() {
         int rc;
         unsigned long long si_seq1 = 0;
-        if ((rc = read_si_begin(e, &si_seq1)) != GCE_OK) return rc;
+        if ((rc = read_si_begin(e, &si_seq1, true)) != GCE_OK) return rc;
         if (N > 0) {
 #ifndef GCE_DESCRIBE_BLOCKS
 #define GCE_DESCRIBE_BLOCKS 32768        // at most this many blocks: their Stats partial sums end in six global atomics each
@@ -930,7 +958,7 @@ struct Step {
         hipLaunchKernelGGL(k_u64_partials, dim3(1), dim3(1024), 0, s, w.scan_part, (const unsigned long long *)&w.si->n_groups, &w.si->vote_weight, &w.si->n_live);
         LAUNCH_EV(k_vote_batches, dim3(nblk_N), dim3(256), s, e->ev[EV_PAIRING], w, (const unsigned long long *)&w.si->n_groups, (const uint64_t *)w.scan_part);
         CANARY("EV_PAIRING");
-        if ((rc = read_si(e)) != GCE_OK) return rc;
+        if ((rc = read_si(e, true)) != GCE_OK) return rc;
         HIPCHK(hipGetLastError());
         si_behind_describe = true;
         NG = (uint32_t)e->h_si.n_groups;
@@ -992,8 +1020,12 @@ struct Step {
             hipLaunchKernelGGL(k_vote_deep, dim3(1024), dim3(DV_T), 0, s, b, p, w);                 // deep sides, one block each; leaves what it cannot take
             LAUNCH_EV(k_consensus_slow, dim3(512), dim3(256), s, e->ev[EV_CONSENSUS], (const SlowArgs *)e->slow_args.p);
             CANARY("EV_CONSENSUS");
-            hipLaunchKernelGGL(k_group_tail, dim3(cdiv(NG, 256)), dim3(256), 0, s, b, p, w, NG);
-            if (!p.disable_duplex) {                                                                  // duplex stage: flagged clusters, compacted, a wave each
+            // Cluster::isDuplex (cluster.cpp:246-258) wants two '_'-separated tokens in both UMIs: a stream whose UMIs hold no '_' (k_describe, umi_us -- every
+            // single-UMI library) forms no duplex, every group is final in k_group_tail, and neither the duplex stage nor k_stats has anything to do
+            const bool duplex_on = !p.disable_duplex && !(si_behind_describe && e->h_si.umi_us == 0u);
+            hipLaunchKernelGGL(k_group_tail, dim3(cdiv(NG, 256)), dim3(256), 0, s, b, p, w, NG, (int)duplex_on);
+            duplex_ran = duplex_on;
+            if (duplex_on) {                                                                          // duplex stage: flagged clusters, compacted, a wave each
                 hipLaunchKernelGGL(k_finish_screen, dim3(cdiv(C, 256)), dim3(256), 0, s, w, C, w.pf_flag);
                 compact_flags(w.pf_flag, w.pf_list, &w.si->n_pf_items);
                 hipLaunchKernelGGL(k_finish, dim3(4096), dim3(256), 0, s, b, p, w, (const uint32_t *)w.pf_list, (const unsigned long long *)&w.si->n_pf_items);
@@ -1024,7 +1056,7 @@ struct Step {
             TAKE(o_key, o.key, n1 * sizeof(OutKey)); TAKE(o_rec, o.rec, n1 * sizeof(OutRec)); TAKE(o_ksoff, o.ksoff, n1 * 8); TAKE(o_kqoff, o.kqoff, n1 * 8); TAKE(o_krow, o.krow, n1 * 4); TAKE(o_rank64, o.rank64, (n1 / 64 + 2) * 4);
             const unsigned nblk_O = cdiv(n1, OUT_TILE); TAKE(o_part3, o.part3, (size_t)nblk_O * 24 + 64);
             if (e->h_si.n_raw > 0 && C > 0) hipLaunchKernelGGL(k_raw_emit, dim3(cdiv(C, 256)), dim3(256), 0, s, b, p, w, C);      // gencore.cpp:401-407 (malformed input only)
-            hipLaunchKernelGGL(k_stats, dim3(1024), dim3(256), 0, s, b, w, (NG > 0 ? C : 0u), NG);     // Stats: clusters, groups  (round 5: on the second stream beside the output kernels it hid its 50 us and stretched k_out_reduce / k_out_partials by as much: not kept)
+            if (duplex_ran) hipLaunchKernelGGL(k_stats, dim3(1024), dim3(256), 0, s, b, w, NG);     // Stats of the duplex stage's clusters (the rest: k_group_tail)  (round 5: on the second stream beside the output kernels it hid its 50 us and stretched k_out_reduce / k_out_partials by as much: not kept)
             CANARY("k_stats");
             hipLaunchKernelGGL(k_out_reduce, dim3(nblk_O), dim3(OUT_T), 0, s, b, w, o);
             CANARY("k_out_reduce");

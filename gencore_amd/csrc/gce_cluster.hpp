@@ -582,6 +582,7 @@ __global__ __launch_bounds__(256, DESC_WPE) void k_describe(DevBatch b, DevParam
     __shared__ long long s_stat[WAVES_PER_BLOCK][6];
     long long st[6] = {0, 0, 0, 0, 0, 0};       // reads, bases, reads_unmapped, bases_unmapped, base_mismatches, reads_with_mismatches
     int lqmin = 0x7FFFFFFF, lqmax = -1;
+    bool any_us = false;                        // a UMI of mine holds a '_' (or comes from an MI tag): the stream may form duplexes (StreamInfo::umi_us)
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     for (int cb = 0; cb < tiles_per_block; cb++) {
         const int64_t i = ((int64_t)blockIdx.x * tiles_per_block + cb) * 256 + threadIdx.x;
@@ -616,10 +617,11 @@ __global__ __launch_bounds__(256, DESC_WPE) void k_describe(DevBatch b, DevParam
                 const char *src2; uint8_t hm = 0;
                 if (b.mi && b.mi_off[i] != 0xFFFFFFFFFFFFFFFFull) { src2 = b.mi + b.mi_off[i]; hm = 1; }
                 else src2 = b.qname + b.qname_off[i];
-                int s0, l0;
-                if (!d_umi_slice(src2, p, s0, l0, hm ? -1 : (int)k.l_qname - 1)) { raise_error(w.si, GCE_ERR_UMI_PARSE, (uint32_t)i); s0 = 0; l0 = 0; }
+                int s0, l0; bool us;
+                if (!d_umi_slice(src2, p, s0, l0, hm ? -1 : (int)k.l_qname - 1, us)) { raise_error(w.si, GCE_ERR_UMI_PARSE, (uint32_t)i); s0 = 0; l0 = 0; }
                 if (l0 > UINFO_MAXLEN) { raise_error(w.si, GCE_ERR_UMI_PARSE, (uint32_t)i); l0 = 0; }
                 w.uinfo[i] = uinfo_pack((hm ? b.mi_off[i] : b.qname_off[i]) + (uint64_t)s0, hm != 0, k.l_qname, l0);
+                any_us |= us || hm;             // (a tagged read's mate may still give its NAME's slice to the pair, k_group_tail: such streams keep the duplex stage)
             }
         }
     }
@@ -629,6 +631,7 @@ __global__ __launch_bounds__(256, DESC_WPE) void k_describe(DevBatch b, DevParam
         if (lqmin < *(volatile int *)&w.si->lq_min) atomicMin(&w.si->lq_min, lqmin);
         if (lqmax > *(volatile int *)&w.si->lq_max) atomicMax(&w.si->lq_max, lqmax);
     }
+    if (__any(any_us) && lane == 0 && *(volatile unsigned int *)&w.si->umi_us == 0u) atomicOr(&w.si->umi_us, 1u);
     __syncthreads();
     if (threadIdx.x < 6) {
         long long v = s_stat[0][threadIdx.x] + s_stat[1][threadIdx.x] + s_stat[2][threadIdx.x] + s_stat[3][threadIdx.x];

@@ -57,6 +57,8 @@ struct DevParams {
 
 // stream-level scalars produced by the prescan (device resident)
 #define GCE_PRE_SLOTS 64
+#define GCE_TAIL_SLOTS 16
+#define GCE_TAIL_HSLOTS 8
 struct StreamInfo {
     unsigned long long n_clustered;      // number of clustered reads (ticks)
     unsigned int first_unmapped;         // index of the first unmapped read (U) or NONE32
@@ -91,7 +93,14 @@ struct StreamInfo {
     long long post_slot[GCE_PRE_SLOTS][8];  // k_out_meta's six addRead counters of the emitted records, spread the same way
     long long pre_slot[GCE_PRE_SLOTS][8];   // k_prescan's six addRead counters, spread over GCE_PRE_SLOTS address sets (block & mask) and added
                                            // up by the host: tens of thousands of blocks adding to SIX words queued behind each other
+    unsigned int umi_us;                 // k_describe: some clustered read's UMI holds a '_' (or comes from an MI tag): only then can Cluster::isDuplex be true and the duplex stage run
+    unsigned int pad_us;
+    // ---- k_group_tail's share of the Stats (the groups that are final there), spread the same way; the early looks of the host do not carry them (GCE_SI_HEAD_BYTES)
+    long long tail_slot[GCE_TAIL_SLOTS][16];   // TS_* below
+    long long tail_hist[GCE_TAIL_HSLOTS][GCE_MAX_SUPPORTING_READS];   // pre supporting-reads histogram
 };
+#define GCE_SI_HEAD_BYTES offsetof(StreamInfo, tail_slot)
+enum { TS_PRE_CLUSTERS = 0, TS_PRE_MULTI, TS_PRE_MOLECULES, TS_PRE_SE, TS_PRE_PE, TS_PRE_UNCOUNTED, TS_NPAIRS, TS_POST_CLUSTERS, TS_POST_MULTI, TS_POST_SSCS, TS_POST_SE, TS_POST_PE, TS_WORDS };
 
 // Fatal conditions of the path: the reference exits on the first one it meets; the engine reports the one on the EARLIEST read
 // (deterministic whatever the scheduling: one 64-bit atomicMin on read index << 8 | code).
@@ -283,14 +292,16 @@ __device__ __forceinline__ uint64_t d_range_bytes(int lo, int hi, int k) {
     return upto_z & ~upto_a;
 }
 
-__device__ inline bool d_umi_slice_bytes(const char *s, const DevParams &p, int &start, int &len, int n);
+__device__ inline bool d_umi_slice_bytes(const char *s, const DevParams &p, int &start, int &len, int n, bool &has_us);
 
 // BamUtil::getUMI(string, prefix) on the LAST 32 BYTES of a name held in four registers (bamutil.cpp:40-112): the prefix
 // character / ':' that anchors the UMI is practically always inside that window, and the scans become a handful of packed
 // compares instead of two divergent byte loops per read.  Anything the window cannot answer takes the byte walk.
 // Reads up to 7 bytes past s[n-1]: device blobs are readable 16 bytes past their end (include/gencore_amd.h).
-__device__ inline bool d_umi_slice(const char *s, const DevParams &p, int &start, int &len, int n = -1) {
-    if (n < 0 || p.prefix_len > 4) return d_umi_slice_bytes(s, p, start, len, n);
+// has_us: the slice [start, start + len) holds a '_' (what Cluster::isDuplex needs of both UMIs of a duplex).
+__device__ inline bool d_umi_slice(const char *s, const DevParams &p, int &start, int &len, int n, bool &has_us) {
+    has_us = false;
+    if (n < 0 || p.prefix_len > 4) return d_umi_slice_bytes(s, p, start, len, n, has_us);
     const int base = n > 32 ? n - 32 : 0, nwin = n - base;
     uint64_t w[4];
 #pragma unroll
@@ -311,21 +322,24 @@ __device__ inline bool d_umi_slice(const char *s, const DevParams &p, int &start
     }
     if (wpos < 0) {
         if (base == 0) return true;                                        // no anchor anywhere: no UMI
-        return d_umi_slice_bytes(s, p, start, len, n);                     // anchor (if any) in front of the window
+        return d_umi_slice_bytes(s, p, start, len, n, has_us);             // anchor (if any) in front of the window
     }
     if (p.prefix_len > 0) {
         const int wst = wpos + 2;                                          // find_last_of + 2 (bamutil.cpp:47-50)
         if (base + wst > n) return false;                                  // substr(start) with start > size() throws
         int l = nwin - wst;                                                // run of [ATCG_] from wst, ended by the first other byte
         bool open = true;                                                  // (forward from the word that holds wst; stop at the first hit)
+        uint64_t us = 0;                                                   // '_' bytes of the run: the compare is d_umi_bytes' own, the masks are the stop's
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if (open && 8 * k + 8 > wst && 8 * k < nwin) {
-                const uint64_t stop = ~d_umi_bytes(w[k]) & 0x8080808080808080ull & d_range_bytes(wst, nwin, k);
+                const uint64_t rng = d_range_bytes(wst, nwin, k), e_us = d_eq_bytes(w[k], '_');
+                const uint64_t stop = ~(d_eq_bytes(w[k], 'A') | d_eq_bytes(w[k], 'T') | d_eq_bytes(w[k], 'C') | d_eq_bytes(w[k], 'G') | e_us) & 0x8080808080808080ull & rng;
+                us |= e_us & rng & (stop ? (stop & (0ull - stop)) - 1ull : ~0ull);         // (below the first stop byte)
                 if (stop) { l = 8 * k + ((__ffsll((long long)stop) - 1) >> 3) - wst; open = false; }
             }
         }
-        start = base + wst; len = l;
+        start = base + wst; len = l; has_us = us != 0;
         return true;
     }
     // no prefix: text after the last ':' if it is all [ATCG_] with at most one '_' (bamutil.cpp:65-111)
@@ -341,13 +355,14 @@ __device__ inline bool d_umi_slice(const char *s, const DevParams &p, int &start
     int st = sep + 1;
     { const int j = wpos + 1; const char c = (char)(w[j >> 3] >> (8 * (j & 7))); if (st < n - 1 && c == '_') { st++; us--; } }
     if (!ok || us > 1) return true;
-    start = st; len = n - st;
+    start = st; len = n - st; has_us = us > 0;
     return true;
 }
+__device__ inline bool d_umi_slice(const char *s, const DevParams &p, int &start, int &len, int n = -1) { bool u; return d_umi_slice(s, p, start, len, n, u); }
 
-__device__ inline bool d_umi_slice_bytes(const char *s, const DevParams &p, int &start, int &len, int n) {
+__device__ inline bool d_umi_slice_bytes(const char *s, const DevParams &p, int &start, int &len, int n, bool &has_us) {
     if (n < 0) { n = 0; while (s[n]) n++; }
-    start = 0; len = 0;
+    start = 0; len = 0; has_us = false;
     if (p.prefix_len > 0) {
         int pos = -1;
         for (int i = n - 1; i >= 0; i--) {
@@ -362,7 +377,7 @@ __device__ inline bool d_umi_slice_bytes(const char *s, const DevParams &p, int 
         // every character after the last prefix character up to the end was examined by the backward scan; of those only a
         // run of [ATCG_] right after st counts
         int l = 0;
-        while (st + l < n && d_is_umi_char(s[st + l])) l++;
+        while (st + l < n && d_is_umi_char(s[st + l])) { has_us |= s[st + l] == '_'; l++; }
         start = st; len = l;
         return true;
     }
@@ -378,7 +393,7 @@ __device__ inline bool d_umi_slice_bytes(const char *s, const DevParams &p, int 
     int st = sep + 1;
     if (st < n - 1 && s[st] == '_') { st++; us--; }      // one leading underscore is skipped, and not counted
     if (!ok || us > 1) return true;
-    start = st; len = n - st;
+    start = st; len = n - st; has_us = us > 0;
     return true;
 }
 

@@ -6,16 +6,18 @@
 //   k_blk_scan, k_events   ticks of the scan blocks; the reads on which the reference's periodic flush fires (gencore.cpp:319-322)
 //   k_leaders        one lane per leader: instance from the flush events, bucket table -> cluster of every leader run
 //   k_num_* k_scatter  cluster list (one claiming leader per cluster) + CSR fill: members[] per cluster
-//   k_describe       per read: the 32-byte ReadDesc, UMI slice, pre-Stats
+//   k_describe       per read: the 32-byte ReadDesc, UMI slice (and whether any holds a '_'), pre-Stats
 //   k_pairing_sub<16|32> (gce_pair2.hpp), k_pairing_fast, k_pairing_deep (gce_deep.hpp), k_pairing_slow
 //                    per cluster: qname order, mate pairing (cluster.cpp:260-273), greedy UMI grouping (cluster.cpp:55-100)
 //   k_group_fill, k_vote_batches   compact (cluster, group) list, batches of groups
 //   k_vote (gce_vote.hpp)   per batch of groups: Pair::computeScore (pair.cpp:88-172) + template pick (group.cpp:136-318) + column
 //                    vote (group.cpp:320-579), both sides; groups outside its scope go on through
 //   k_score2, k_consensus_fast, k_deep_prepare + k_vote_deep (gce_deep.hpp), k_consensus_slow
-//   k_group_tail, k_finish_screen, k_finish   qname reconciliation; duplex merge / filter / FR,RR tags (cluster.cpp:116-188, pair.cpp:43-68)
-//   k_out_* (gce_output.hpp)   emitted records in bamComp order as one compact table
-//   k_stats          Stats reductions (stats.cpp:101-139)
+//   k_group_tail     qname reconciliation; filter / FR tag and the Stats events (stats.cpp:123-139) of every group that is final there: all of them
+//                    unless some UMI of the stream holds a '_' (k_describe: StreamInfo::umi_us), else those of clusters that cannot form a duplex
+//   k_finish_screen, k_finish   only when a UMI holds a '_': duplex merge / filter / FR,RR tags (cluster.cpp:116-188, pair.cpp:43-68)
+//   k_stats          only then: Stats events of the duplex stage's clusters
+//   k_out_* (gce_output.hpp)   emitted records in bamComp order as one compact table, Stats::addRead of the emitted records
 //   k_depth (gce_depth.hpp)   depth / BED statistics on request
 #pragma once
 #include "gce_device.hpp"
@@ -1763,52 +1765,69 @@ __device__ inline int d_duplex_merge_bam(const DevBatch &b, uint32_t r1, uint32_
     return wave_sum(diff) + (l1 > l2 ? l1 - l2 : l2 - l1);
 }
 
-__device__ inline void d_emit_pair(const Work &w, uint32_t gi, bool duplex) {      // Pair::writeSscsDcsTag + Gencore::outputPair
-    uint32_t l = w.rp_left[gi], r = w.rp_right[gi];
-    int fr = (int)min(w.rp_merge[gi], 65535u) & 0xFF;                               // low byte of an unsigned short (quirk Q8)
-    int rr = (int)min(w.rp_rmerge[gi], 65535u) & 0xFF;
+// Pair::writeSscsDcsTag + Gencore::outputPair of one result pair.  Everything comes as arguments: k_group_tail has it in registers, the duplex stage loads what
+// k_group_tail stored for its clusters (d_emit_group).
+__device__ inline void d_emit_pair(const Work &w, uint32_t l, uint32_t r, uint32_t merge, uint32_t rmerge, uint32_t qsl, uint32_t qsr, int nml, int nmr, bool duplex) {
+    int fr = (int)min(merge, 65535u) & 0xFF;                                        // low byte of an unsigned short (quirk Q8)
+    int rr = (int)min(rmerge, 65535u) & 0xFF;
     OutRec o; o.fr = (int16_t)fr; o.rr = duplex ? (int16_t)rr : (int16_t)-1; o.pad = 0;
-    if (l != NONE32) { w.out_flag[l] = 1; o.qname_src = w.rp_qsl[gi]; o.mate = r; o.nm_new = (int16_t)w.rp_nm[gi * 2]; w.orec[l] = o; }
-    if (r != NONE32) { w.out_flag[r] = 1; o.qname_src = w.rp_qsr[gi]; o.mate = l; o.nm_new = (int16_t)w.rp_nm[gi * 2 + 1]; w.orec[r] = o; }
+    if (l != NONE32) { w.out_flag[l] = 1; o.qname_src = qsl; o.mate = r; o.nm_new = (int16_t)nml; w.orec[l] = o; }
+    if (r != NONE32) { w.out_flag[r] = 1; o.qname_src = qsr; o.mate = l; o.nm_new = (int16_t)nmr; w.orec[r] = o; }
+}
+__device__ inline void d_emit_group(const Work &w, uint32_t gi, uint32_t l, uint32_t r, uint32_t merge, uint32_t rmerge, bool duplex) {      // a group of the duplex stage
+    const int2 nv = *reinterpret_cast<const int2 *>(w.rp_nm + 2 * (size_t)gi);
+    d_emit_pair(w, l, r, merge, rmerge, w.rp_qsl[gi], w.rp_qsr[gi], nv.x, nv.y, duplex);
 }
 
 // The tail of Group::consensusMerge (group.cpp:104-132) — mMergeReads, qname reconciliation, the new Pair's UMI — one
-// THREAD per group; groups of clusters that cannot form a duplex (no UMI, --no_duplex, or a single group) are also
-// filtered, tagged and emitted here (cluster.cpp:169-183; with one group the duplex loop finds no partner, :157-166).
-__global__ __launch_bounds__(256) void k_group_tail(DevBatch b, DevParams p, Work w, uint32_t n_groups) {
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= n_groups) return;
-    const uint32_t c = w.gl_cluster[gi];
+// THREAD per group; groups of clusters that cannot form a duplex (no UMI, --no_duplex, a single group, or a stream none of whose UMIs
+// holds a '_': duplex_on == 0, StreamInfo::umi_us) are FINAL here: filtered, tagged and emitted (cluster.cpp:169-183; with one group or
+// one-token UMIs the duplex loop finds no partner, :157-166), and their Stats events (addMolecule, addSSCS, outputPair's addMolecule(1, PE),
+// addCluster before and after: cluster.cpp:102,185-187) are counted from the registers -- nothing of such a group is stored for a later
+// kernel.  Groups of the other clusters are left pending for k_finish, with everything it needs in the rp_* arrays; k_stats counts those.
+enum { TF_FINAL = 1, TF_PE = 2, TF_OUT = 4, TF_CFIRST = 8, TF_CMULTI = 16, TF_POSTC = 32, TF_POSTM = 64 };
+__device__ __forceinline__ uint32_t d_group_tail(const DevBatch &b, const DevParams &p, const Work &w, uint32_t gi, bool duplex_on, uint32_t &supp, uint32_t &cl_pairs) {
+    // everything the group index alone addresses is asked for first, then what hangs on the cluster and on the result reads: two round trips in a row, not four
+    // (a skipped group's rp_left / rp_right are still NONE32, its rp_nm -1: the clears of the step)
+    const uint32_t c = w.gl_cluster[gi], c_prev = gi ? w.gl_cluster[gi - 1] : NONE32;
     const uint32_t begin = w.g_begin[gi], np = w.g_np[gi];
+    const uint32_t left = w.rp_left[gi], right = w.rp_right[gi];
+    int2 nmv = *reinterpret_cast<const int2 *>(w.rp_nm + 2 * (size_t)gi);
     const uint8_t cflags = w.cl_hasumi[c];
     const uint32_t G = w.cl_ngroups[c];
-    if (d_group_skipped(p, cflags, G, np)) {
-        // no kernel looked at this group (k_group_fill) and its cluster forms no duplex: its result records are the one pair's reads as they came in -- k_stats
-        // reads them for PE / SE --, one supporting read, never written (rp_nm is still -1: no NM patch was deferred)
-        w.rp_left[gi] = w.gpl[begin]; w.rp_right[gi] = w.gpr[begin];
-        w.rp_supp[gi] = 1; w.rp_state[gi] = RP_DROPPED;
-        return;
+    // the two templates' name lengths and UMI places: one word each (round 5; core record + UMI pointer + UMI length + MI flag were four sectors per side)
+    const uint64_t uL = left != NONE32 ? w.uinfo[left] : 0ull, uR = right != NONE32 ? w.uinfo[right] : 0ull;
+    const bool duplex_cluster = duplex_on && (cflags & 1) && !p.disable_duplex && G >= 2;
+    uint32_t tf = 0;
+    if (!duplex_cluster && c_prev != c) {                 // the cluster's first group: Stats::addCluster before and after, the pairs behind timing.n_pairs
+        tf |= TF_CFIRST | (G > 1 ? TF_CMULTI : 0);
+        cl_pairs = w.cl_npairs[c];
+        if (G > 1 && !p.duplex_only) {                                                // written groups among the siblings: merge == pairs of the group (below), a skipped group has one pair
+            uint32_t nr = 0;
+            for (uint32_t g = 0; g < G && nr < 2; g++) nr += (int)w.g_np[gi + g] >= p.cluster_size_req;
+            tf |= (nr > 0 ? TF_POSTC : 0) | (nr > 1 ? TF_POSTM : 0);
+        }
     }
-    uint32_t left = w.rp_left[gi], right = w.rp_right[gi];
+    if (d_group_skipped(p, cflags, G, np)) {
+        // no kernel looked at this group (k_group_fill) and its cluster forms no duplex: one supporting read, never written
+        supp = 1;
+        return tf | TF_FINAL | ((w.gpl[begin] != NONE32 && w.gpr[begin] != NONE32) ? TF_PE : 0);
+    }
     {   // the NM patches k_vote deferred (group.cpp:528-573): mismatchInc != 0 reads the template's NM tag -- absent: the reference crashes (quirk Q9);
         // mismatchInc > 5: the template was restored, NM stays; else NM + mismatchInc goes into the tag if it is stored as type 'C' and stays a byte
-        const int2 nv = *reinterpret_cast<const int2 *>(w.rp_nm + 2 * (size_t)gi);
-        if (NM_IS_DEFERRED(nv.x) || NM_IS_DEFERRED(nv.y)) {
-            int2 o = nv;
+        if (NM_IS_DEFERRED(nmv.x) || NM_IS_DEFERRED(nmv.y)) {
             auto resolve = [&](int v, uint32_t out) -> int {
                 if (!NM_IS_DEFERRED(v)) return v;
                 const int minc = v - NM_DEFER, ty = b.nm_type[out], nn = b.nm[out] + minc;
                 if (ty == 0) { raise_error(w.si, GCE_ERR_NM_MISSING, out); return -1; }
                 return (minc <= 5 && ty == 'C' && nn >= 0 && nn <= 255) ? nn : -1;
             };
-            o.x = resolve(nv.x, left); o.y = resolve(nv.y, right);
-            *reinterpret_cast<int2 *>(w.rp_nm + 2 * (size_t)gi) = o;
+            nmv.x = resolve(nmv.x, left); nmv.y = resolve(nmv.y, right);
+            if (duplex_cluster) *reinterpret_cast<int2 *>(w.rp_nm + 2 * (size_t)gi) = nmv;
         }
     }
     const bool single = np == 1 && w.gpr[begin] == NONE32;
     uint32_t qsl = left, qsr = right;                                     // BamUtil::copyQName sources (== the record itself if unchanged)
-    // the two templates' name lengths and UMI places: one word each (round 5; core record + UMI pointer + UMI length + MI flag were four sectors per side)
-    const uint64_t uL = left != NONE32 ? w.uinfo[left] : 0ull, uR = right != NONE32 ? w.uinfo[right] : 0ull;
     if (!single) {
         if (cflags & 2) {                                                 // cross-contig cluster: group.cpp:79-99,109-112
             uint32_t ntc = NONE32; int bl = 0;
@@ -1826,9 +1845,7 @@ __global__ __launch_bounds__(256) void k_group_tail(DevBatch b, DevParams p, Wor
             else qsl = right;
         }
     }
-    w.rp_qsl[gi] = qsl; w.rp_qsr[gi] = qsr;
-    const uint32_t merge = single ? 1 : np;
-    const bool duplex_cluster = (cflags & 1) && !p.disable_duplex && G >= 2;
+    const uint32_t merge = single ? 1 : np;                               // (== np: a single has one pair)
     const char *u = nullptr; int ul = 0;                                  // Pair::setLeft / setRight (pair.cpp:188-216)
     if ((cflags & 1) || b.mi) {
         auto rec_umi = [&](uint64_t vrec, uint32_t src, const char *&uo, int &ulo) {       // d_record_umi on the words already here
@@ -1853,11 +1870,48 @@ __global__ __launch_bounds__(256) void k_group_tail(DevBatch b, DevParams p, Wor
             u = u2; ul = ul2;
         }
     }
-    w.rp_merge[gi] = merge; w.rp_rmerge[gi] = 0; w.rp_umi[gi] = u; w.rp_umilen[gi] = (uint16_t)ul;
-    if (duplex_cluster) { w.rp_state[gi] = RP_PENDING; w.rp_supp[gi] = -1; return; }
+    if (duplex_cluster) {                                                 // -> k_finish, k_stats
+        w.rp_qsl[gi] = qsl; w.rp_qsr[gi] = qsr;
+        w.rp_merge[gi] = merge; w.rp_rmerge[gi] = 0; w.rp_umi[gi] = u; w.rp_umilen[gi] = (uint16_t)ul;
+        w.rp_state[gi] = RP_PENDING; w.rp_supp[gi] = -1;
+        return tf;
+    }
     const bool outp = !p.duplex_only && (int)merge >= p.cluster_size_req;
-    w.rp_supp[gi] = (int)merge; w.rp_state[gi] = outp ? RP_OUT_SSCS : RP_DROPPED;
-    if (outp) d_emit_pair(w, gi, false);
+    if (outp) d_emit_pair(w, left, right, merge, 0u, qsl, qsr, nmv.x, nmv.y, false);
+    if (G == 1 && outp) tf |= TF_POSTC;
+    supp = merge;
+    return tf | TF_FINAL | ((left != NONE32 && right != NONE32) ? TF_PE : 0) | (outp ? TF_OUT : 0);
+}
+__global__ __launch_bounds__(256) void k_group_tail(DevBatch b, DevParams p, Work w, uint32_t n_groups, int duplex_on) {
+    __shared__ unsigned int s_hist[GCE_MAX_SUPPORTING_READS];
+    __shared__ unsigned long long s_ts[TS_WORDS];
+    if (threadIdx.x < GCE_MAX_SUPPORTING_READS) s_hist[threadIdx.x] = 0;
+    if (threadIdx.x < TS_WORDS) s_ts[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t tf = 0, supp = 0, cl_pairs = 0;
+    if (gi < n_groups) tf = d_group_tail(b, p, w, gi, duplex_on != 0, supp, cl_pairs);
+    // Stats: every counter but the pair count is a predicate of the thread -- a ballot per counter and wave, the histogram through LDS, then one
+    // set of atomics per block on one of GCE_TAIL_SLOTS address sets (the host and k_fold_stats add them up)
+    const bool fin = tf & TF_FINAL, out = tf & TF_OUT, pe = tf & TF_PE;
+    const bool uncounted = fin && supp >= (uint32_t)GCE_MAX_SUPPORTING_READS;
+    if (fin && !uncounted) atomicAdd(&s_hist[supp], 1u);
+    unsigned int cnt[TS_WORDS];
+    cnt[TS_PRE_CLUSTERS] = __popcll(__ballot(tf & TF_CFIRST)); cnt[TS_PRE_MULTI] = __popcll(__ballot(tf & TF_CMULTI));
+    cnt[TS_PRE_MOLECULES] = __popcll(__ballot(fin)); cnt[TS_PRE_SE] = __popcll(__ballot(fin && !pe)); cnt[TS_PRE_PE] = __popcll(__ballot(fin && pe));
+    cnt[TS_PRE_UNCOUNTED] = __popcll(__ballot(uncounted));
+    cnt[TS_NPAIRS] = 0;
+    cnt[TS_POST_CLUSTERS] = __popcll(__ballot(tf & TF_POSTC)); cnt[TS_POST_MULTI] = __popcll(__ballot(tf & TF_POSTM));
+    cnt[TS_POST_SSCS] = __popcll(__ballot(out)); cnt[TS_POST_SE] = __popcll(__ballot(out && !pe)); cnt[TS_POST_PE] = __popcll(__ballot(out && pe));
+    const long long npw = wave_sum64((long long)cl_pairs);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int k = 0; k < TS_WORDS; k++) if (cnt[k]) atomicAdd(&s_ts[k], (unsigned long long)cnt[k]);
+        if (npw) atomicAdd(&s_ts[TS_NPAIRS], (unsigned long long)npw);
+    }
+    __syncthreads();
+    if (threadIdx.x < TS_WORDS && s_ts[threadIdx.x]) atomicAdd((unsigned long long *)&w.si->tail_slot[blockIdx.x & (GCE_TAIL_SLOTS - 1)][threadIdx.x], s_ts[threadIdx.x]);
+    if (threadIdx.x < GCE_MAX_SUPPORTING_READS && s_hist[threadIdx.x]) atomicAdd((unsigned long long *)&w.si->tail_hist[(blockIdx.x >> 4) & (GCE_TAIL_HSLOTS - 1)][threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
 }
 
 // Duplex matching (cluster.cpp:119-168), one wave per cluster that has UMIs and at least two groups.
@@ -1904,13 +1958,13 @@ __device__ bool finish_cluster_lanes(const DevBatch &b, const DevParams &p, cons
                 w.rp_rmerge[gi] = m2;
                 w.rp_state[gi] = outp ? RP_OUT_DCS : RP_DROPPED;
                 w.rp_state[g2] = RP_CONSUMED;
-                if (outp) d_emit_pair(w, gi, true);
+                if (outp) d_emit_group(w, gi, l1, r1, m1, m2, true);
             }
             WAVE_SYNC();                                     // (the merged bases / qualities of this pair before anybody reads them again)
         } else {
             const bool outp = !p.duplex_only && (int)m1 >= p.cluster_size_req;
             if (lane == idx) st = outp ? RP_OUT_SSCS : RP_DROPPED;
-            if (lane == 0) { w.rp_supp[gi] = (int)m1; w.rp_state[gi] = outp ? RP_OUT_SSCS : RP_DROPPED; if (outp) d_emit_pair(w, gi, false); }
+            if (lane == 0) { w.rp_supp[gi] = (int)m1; w.rp_state[gi] = outp ? RP_OUT_SSCS : RP_DROPPED; if (outp) d_emit_group(w, gi, l1, r1, m1, 0u, false); }
         }
     }
     return true;
@@ -1943,11 +1997,11 @@ __device__ void finish_cluster(const DevBatch &b, const DevParams &p, const Work
                 w.rp_rmerge[gi] = m2;
                 w.rp_state[gi] = outp ? RP_OUT_DCS : RP_DROPPED;
                 w.rp_state[g2] = RP_CONSUMED;
-                if (outp) d_emit_pair(w, gi, true);
+                if (outp) d_emit_group(w, gi, l1, r1, m1, m2, true);
             }
         } else {
             bool outp = !p.duplex_only && (int)m1 >= p.cluster_size_req;
-            if (lane == 0) { w.rp_supp[gi] = (int)m1; w.rp_state[gi] = outp ? RP_OUT_SSCS : RP_DROPPED; if (outp) d_emit_pair(w, gi, false); }
+            if (lane == 0) { w.rp_supp[gi] = (int)m1; w.rp_state[gi] = outp ? RP_OUT_SSCS : RP_DROPPED; if (outp) d_emit_group(w, gi, l1, r1, m1, 0u, false); }
         }
         WAVE_SYNC();
     }
@@ -2007,7 +2061,9 @@ __global__ __launch_bounds__(256) void k_raw_emit(DevBatch b, DevParams p, Work 
 // ===================================================================================================== Stats
 // All counters are additive (stats.h:47-65).  Block-local accumulation in LDS, one global atomic per non-zero counter.
 // (Stats::addRead of the emitted records: k_out_meta, gce_output.hpp)
-__global__ __launch_bounds__(256) void k_stats(DevBatch b, Work w, uint32_t n_clusters, uint32_t n_groups) {
+// Only the clusters that went through the duplex stage (UMIs and two or more groups; launched when that stage ran): every other group was final in k_group_tail
+// and is counted there.  A group's thread looks at its cluster's flags; the cluster's first group counts the cluster.
+__global__ __launch_bounds__(256) void k_stats(DevBatch b, Work w, uint32_t n_groups) {
     __shared__ unsigned long long s_pre[GCE_STATS_WORDS], s_post[GCE_STATS_WORDS], s_np;
     for (int k = threadIdx.x; k < GCE_STATS_WORDS; k += blockDim.x) { s_pre[k] = 0; s_post[k] = 0; }
     if (threadIdx.x == 0) s_np = 0;
@@ -2018,15 +2074,16 @@ __global__ __launch_bounds__(256) void k_stats(DevBatch b, Work w, uint32_t n_cl
     // The scalar counters are summed in registers and reduced per wave at the end (64 lanes adding to one LDS word serialise);
     // only the histogram goes through LDS atomics.
     long long pre[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, post[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, np = 0, post_h1 = 0;
-    for (uint64_t c = tid0; c < n_clusters; c += stride) {
-        uint32_t G = w.cl_ngroups[c];
-        if (G == 0) continue;
-        pre[6] += 1; if (G > 1) pre[7] += 1;                                             // cluster.cpp:102
-        np += w.cl_npairs[c];
-        uint32_t nr = 0; { const uint32_t g0 = w.cl_gbase[c]; for (uint32_t g = 0; g < G; g++) { uint8_t st = w.rp_state[g0 + g]; nr += (st == RP_OUT_SSCS || st == RP_OUT_DCS); } }
-        if (nr > 0) { post[6] += 1; if (nr > 1) post[7] += 1; }                         // cluster.cpp:185-187
-    }
     for (uint64_t g = tid0; g < n_groups; g += stride) {
+        const uint32_t c = w.gl_cluster[g];
+        const uint32_t G = w.cl_ngroups[c];
+        if (!(w.cl_hasumi[c] & 1) || G < 2) continue;                                    // final in k_group_tail
+        if (g == 0 || w.gl_cluster[g - 1] != c) {
+            pre[6] += 1; pre[7] += 1;                                                    // cluster.cpp:102
+            np += w.cl_npairs[c];
+            uint32_t nr = 0; for (uint32_t k = 0; k < G; k++) { uint8_t st = w.rp_state[g + k]; nr += (st == RP_OUT_SSCS || st == RP_OUT_DCS); }
+            if (nr > 0) { post[6] += 1; if (nr > 1) post[7] += 1; }                     // cluster.cpp:185-187
+        }
         int supp = w.rp_supp[g];
         if (supp < 0) continue;                                                          // consumed as the reverse strand: no event
         bool pe = w.rp_left[g] != NONE32 && w.rp_right[g] != NONE32;

@@ -16,6 +16,7 @@
 //   bamio_sort.hpp    gce_bam_sort, gce_bam_sort_passes, gce_sam_sort
 //   bamio_calmd.hpp   gce_bam_calmd, gce_bam_calmd_stream
 //   bamio_umi.hpp     gce_bam_umi_to_mi
+//   bamio_reduce.hpp  reduce_run, the runner of the two reduce passes
 //   bamio_pileup.hpp  gce_bam_pileup
 //   bamio_errprof.hpp gce_bam_error_profile
 // No part launches a kernel itself: the runners read the file, find its BGZF members and hand them, window by window, to the engine's entry
@@ -24,7 +25,9 @@
 //
 // One copy of each shared piece: member framing, the BAM header, the member codec, the EOF member and the file helpers are in gce_bgzf.hpp;
 // the output file in gce_fileout.hpp; the clock, the input file, pinned buffers and the engine set-up in bamio_common.hpp; PassReader (a
-// file's members, piece by piece), read_bam_header and for_each_window (the window loop of the index and sort runners) in bamio_reader.hpp;
+// file's members, piece by piece), read_bam_header, read_stream_header and for_each_window (the window loop of the index, sort and reduce
+// runners) in bamio_reader.hpp; the FASTA's contigs matched by name (match_contigs) in bamio_common.hpp; the runner of the pileup and the error
+// profile (reduce_run) in bamio_reduce.hpp;
 // PassWriter (a record stream in rounds of 0xff00-byte members deflated on all host threads, or by the GPU) in bamio_writer.hpp.  Each part
 // is an anonymous-namespace helper section, then one extern "C" block of entry points.
 // Everything that scales with the file is spread over `threads` host threads: inflate per BGZF block, the struct-of-arrays fill

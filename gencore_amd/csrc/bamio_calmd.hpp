@@ -1,7 +1,6 @@
 // bamio_calmd.hpp -- NM and MD recomputed against the reference: gce_bam_calmd and gce_bam_calmd_stream (gce_calmd.hpp).  A
 // part of bamio.cpp.
 #pragma once
-#include <unordered_map>
 #include "bamio_sort.hpp"
 
 namespace {
@@ -18,15 +17,7 @@ int calmd_check(int level, const char *fasta_path, char err[256]) {
 int calmd_contigs(SortJob &j, const char *fasta_path, gce_fasta **fa, std::vector<const char *> &seq, std::vector<int64_t> &len) {
     const int rc = gce_fasta_load(fasta_path, j.T, fa);
     if (rc != GCE_OK) return j.fail(rc, "cannot read the reference FASTA");
-    seq.assign((size_t)j.n_ref, nullptr); len.assign((size_t)j.n_ref, -1);
-    int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr;
-    gce_fasta_get(*fa, &nc, &ids, &seqs, &flen);
-    std::unordered_map<std::string, int32_t> where;
-    for (int32_t c = 0; c < nc; c++) where.emplace(ids[c], c);
-    for (int32_t t = 0; t < j.n_ref; t++) {
-        auto it = where.find(j.names[(size_t)t].c_str());                              // (the name up to its first NUL)
-        if (it != where.end()) { seq[(size_t)t] = seqs[it->second]; len[(size_t)t] = flen[it->second]; }
-    }
+    match_contigs(j.names, *fa, seq, len);
     return GCE_OK;
 }
 

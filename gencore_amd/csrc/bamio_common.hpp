@@ -14,6 +14,7 @@
 #include <ctime>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 #include "../../include/gencore_amd.h"
 #include "gce_bgzf.hpp"
@@ -87,6 +88,19 @@ template <class Name> int set_reference(gce_engine *e, const gce_fasta *fa, cons
         for (int32_t c = 0; c < nc; c++)
             if (same_name(names[t], ids[c]) && (rc = gce_set_reference_ascii(e, (int32_t)t, seqs[c], flen[c])) != GCE_OK) return rc;
     return GCE_OK;
+}
+// the contigs of names[] the loaded FASTA has, matched by name (a name counts up to its first NUL): seq[t] / len[t] are contig t's bases and
+// their length as gce_sort_calmd_ref takes them, NULL / -1 for a contig the FASTA lacks
+inline void match_contigs(const std::vector<std::string> &names, const gce_fasta *fa, std::vector<const char *> &seq, std::vector<int64_t> &len) {
+    seq.assign(names.size(), nullptr); len.assign(names.size(), -1);
+    int32_t nc = 0; const char *const *ids = nullptr; const char *const *seqs = nullptr; const int64_t *flen = nullptr;
+    gce_fasta_get(fa, &nc, &ids, &seqs, &flen);
+    std::unordered_map<std::string, int32_t> where;
+    for (int32_t c = 0; c < nc; c++) where.emplace(ids[c], c);
+    for (size_t t = 0; t < names.size(); t++) {
+        auto it = where.find(names[t].c_str());
+        if (it != where.end()) { seq[t] = seqs[it->second]; len[t] = flen[it->second]; }
+    }
 }
 // the depth report's arrays (freed by gce_depth_run_free), n_regions being set: bins of coverage_step per contig, contigs back to back.  false: out of host memory
 inline bool depth_alloc(gce_depth_run *depth, const std::vector<uint32_t> &lens, int32_t coverage_step) {

@@ -27,14 +27,8 @@ int gce_bam_index(const char *bam_path, const char *bai_path, int32_t device, in
     // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
     uint64_t hdr_end = 0; int32_t n_ref = 0;
     {
-        PassReader rh; rh.fd = fd; rh.fsz = fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
-        BamHeader bh;
-        switch (read_bam_header(rh, Contigs::Skip, false, bh)) {
-        case HeaderRead::Failed: return done(GCE_ERR_INVALID, rh.msg.c_str());
-        case HeaderRead::NotBam: return done(GCE_ERR_INVALID, "not a BAM stream");
-        case HeaderRead::Ended: case HeaderRead::Empty: return done(GCE_ERR_INVALID, "truncated BAM header");
-        case HeaderRead::Complete: break;
-        }
+        PassReader rh; BamHeader bh; const char *why = "";
+        if (read_stream_header(rh, in, T, window_bytes, bh, &why) != HeaderRead::Complete) return done(GCE_ERR_INVALID, why);
         hdr_end = bh.hdr_end; n_ref = (int32_t)bh.n_ref;
     }
     out->n_ref = n_ref;

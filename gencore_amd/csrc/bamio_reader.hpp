@@ -1,5 +1,6 @@
 // bamio_reader.hpp -- a BGZF file read piece by piece on the host: PassReader (the members of each piece, inflated on request), read_bam_header
-// (the one loop that host-inflates a file's first members until its BAM header is whole) and for_each_window (the window loop of the index,
+// (the one loop that host-inflates a file's first members until its BAM header is whole), read_stream_header (the same with the streaming
+// runners' pieces and words) and for_each_window (the window loop of the index,
 // sort and calmd runners).  Needs no device: beside gce_bgzf.hpp and parallel_for, its pinned window comes from gce_host_alloc / gce_host_free,
 // which a program without HIP supplies over malloc (tests/reader_host_check.cpp).
 #pragma once
@@ -90,6 +91,20 @@ inline HeaderRead read_bam_header(PassReader &rd, Contigs dialect, bool first_na
         if (g == 0) break;
     }
     return HeaderRead::Complete;
+}
+// ... for a runner that then streams the file from its first byte: rh reads `in` with T threads in pieces of 1 MB (of a window, where that is
+// smaller), the contigs passed over.  *why: the words for what is returned, the reader's own (rh.msg) when it failed.
+inline HeaderRead read_stream_header(PassReader &rh, const InputFile &in, int T, uint64_t window_bytes, BamHeader &bh, const char **why, std::vector<std::string> *names = nullptr,
+                                     std::vector<uint32_t> *lens = nullptr) {
+    rh.fd = in.fd; rh.fsz = in.fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
+    const HeaderRead h = read_bam_header(rh, Contigs::Skip, false, bh, names, lens);
+    switch (h) {
+    case HeaderRead::Failed: *why = rh.msg.c_str(); break;
+    case HeaderRead::NotBam: *why = "not a BAM stream"; break;
+    case HeaderRead::Ended: case HeaderRead::Empty: *why = "truncated BAM header"; break;
+    case HeaderRead::Complete: *why = ""; break;
+    }
+    return h;
 }
 
 // A BGZF file from its first byte, window by window, for the index and sort runners: the host reads a piece and finds its members, the

@@ -57,14 +57,8 @@ struct SortJob {
         if (!in.is_bgzf()) return fail(GCE_ERR_INVALID, "not a BGZF file");
         T = threads > 0 ? threads : default_threads();
         // ---- the header: the host inflates the first members (1 MB pieces) until it is whole
-        PassReader rh; rh.fd = in.fd; rh.fsz = in.fsz; rh.T = T; rh.piece = window_bytes > 0 ? (size_t)std::min<uint64_t>(window_bytes, (uint64_t)1 << 20) : ((size_t)1 << 20);
-        BamHeader bh;
-        switch (read_bam_header(rh, Contigs::Skip, false, bh, keep_header ? &names : nullptr)) {
-        case HeaderRead::Failed: return fail(GCE_ERR_INVALID, rh.msg);
-        case HeaderRead::NotBam: return fail(GCE_ERR_INVALID, "not a BAM stream");
-        case HeaderRead::Ended: case HeaderRead::Empty: return fail(GCE_ERR_INVALID, "truncated BAM header");
-        case HeaderRead::Complete: break;
-        }
+        PassReader rh; BamHeader bh; const char *why = "";
+        if (read_stream_header(rh, in, T, window_bytes, bh, &why, keep_header ? &names : nullptr) != HeaderRead::Complete) return fail(GCE_ERR_INVALID, why);
         const uint8_t *u = rh.win.p;
         hdr_end = bh.hdr_end; n_ref = (int32_t)bh.n_ref;
         if (keep_header) { hdr.assign(u, u + bh.hdr_end); return GCE_OK; }

@@ -1424,5 +1424,6 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_sort.hpp"
 #include "gce_calmd.hpp"
 #include "gce_umi.hpp"
+#include "gce_reduce.hpp"
 #include "gce_pileup.hpp"
 #include "gce_errprof.hpp"

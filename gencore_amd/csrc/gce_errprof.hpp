@@ -3,12 +3,13 @@
 // Stands in for `fgbio ErrorRateByReadPosition`, Picard's artifact metrics or the mismatches-per-cycle block of `samtools stats` around a
 // consensus step.  The file is streamed window by window as gce_bam_pileup streams it (win_inflate_index / win_carry, gce_passes.hpp); the
 // reference bases are resident in calmd's layout (calmd::Ref, gce_calmd.hpp); an optional BED restricts the events to the union of its
-// regions (pileup::Sites, pileup::seek, gce_pileup.hpp).  The reduction is the opposite corner from pileup's: 3 segments x 1024 cycles x 24
+// regions (reduce::Sites, reduce::seek, gce_reduce.hpp).  The reduction is the opposite corner from pileup's: 3 segments x 1024 cycles x 24
 // classes of 64-bit totals (576 KiB) stay on the device, and every base of every read lands on the few thousand of them its cycle can reach.
 // Per window:
-//   k_err_scan     one thread per record: eligibility (rule E), the first interval the record can touch; the skip counters by ballot and one
-//                  atomic per wave, the lowest malformed record (atomicMin), 4 bytes of meta per record (the first interval, 0 without a BED,
-//                  or EP_NONE for a record that is skipped or can touch no interval: the count kernel drops it on one load)
+//   the scan       (k_reduce_scan over ErrScan, gce_reduce.hpp) one thread per record: eligibility (rule E), the first interval the record can
+//                  touch; the skip counters by ballot and one atomic per wave, the lowest malformed record (atomicMin), 4 bytes of meta per
+//                  record (the first interval, 0 without a BED, or EP_NONE for a record that is skipped or can touch no interval: the count
+//                  kernel drops it on one load)
 //   k_err_count    16 lanes per record, 32 records per step of a block of 512 threads, a fixed grid whose blocks stride over the window's
 //                  records.  Adds of the first EP_CYC cycles meet in LDS: two planes of 32-bit counters per block, a record slot's parity
 //                  choosing the plane, so that the two records of a 32-lane LDS lane group, which walk the same cycles at the same time,
@@ -16,9 +17,11 @@
 //                  planes goes to memory, one 64-bit global atomic per non-zero counter.  k_err_count<true> (GCE_ERRPROF_DIRECT) has no
 //                  planes: every add is a 64-bit global atomic.
 // errprof::scan_record and errprof::count_record are __host__ __device__: tests/errprof_host_check.hip runs them on the host against
-// tests/pyerrprof.py, the model of the rules.
+// tests/pyerrprof.py, the model of the rules.  What the pass shares with gce_bam_pileup -- rule E, the interval table, the scan kernel and the
+// device object -- is gce_reduce.hpp's.
 #pragma once
 #include <cstdint>
+#include "gce_reduce.hpp"
 
 namespace errprof {
 
@@ -27,58 +30,36 @@ namespace errprof {
 typedef uint32_t __attribute__((aligned(1), may_alias)) ep_u32u;
 typedef uint16_t __attribute__((aligned(1), may_alias)) ep_u16u;
 
-#define EP_NONE 0xFFFFFFFFu
+#define EP_NONE RD_NONE
 #define EP_MAX_CYCLE 1024u
 #define EP_ROW 24u                                                                    // counters per (segment, cycle): 21 classes, 3 zeros
 #define EP_COUNTERS (3u * EP_MAX_CYCLE * EP_ROW)
 enum { EP_READ_N = 16, EP_REF_OTHER, EP_LOWQ, EP_INS, EP_DEL, EP_NCLASS };
-enum { EP_SKIP_UNPLACED = 1, EP_SKIP_FLAGGED, EP_SKIP_LOW_MAPQ, EP_SKIP_NO_CIGAR, EP_SKIP_NO_SEQ, EP_SKIP_BAD_CIGAR, EP_SKIP_NO_REF, EP_SKIP_TOO_LONG };
+enum { EP_SKIP_NO_REF = reduce::N_SKIP + 1, EP_SKIP_TOO_LONG, EP_N_SKIP = EP_SKIP_TOO_LONG };            // behind rule E's six (gce_reduce.hpp)
 
 // bed: rule B is on (S holds the intervals); off, S is not read
 struct Params { int32_t n_ref, min_mapq, min_baseq; uint32_t exclude, bed; };
-// what the scan learns about a record.  bad: block_size < 32 or beyond the buffer, or fields that overrun block_size; skip: 0, or the one
-// counter of rule E the record goes to; first: the first interval it can touch (0 without a BED; EP_NONE: none, or not eligible)
+// what the scan learns about a record.  bad: reduce::rule_e's BAD; skip: 0, or the one counter of rule E the record goes to; first: the first interval it can touch (0 without a BED; EP_NONE: none, or not eligible)
 struct Rec { uint32_t first; uint8_t bad, skip; };
 
 // One record (r at its block_size, `avail` bytes from r to the end of the buffer): rule E, the first interval.  No byte is read outside
 // r[0, min(avail, 4 + block_size)).
-EP_HD void scan_record(const uint8_t *r, uint64_t avail, const Params &P, const calmd::Ref &ref, const pileup::Sites &S, Rec &R) {
+EP_HD void scan_record(const uint8_t *r, uint64_t avail, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, Rec &R) {
     R.first = EP_NONE; R.bad = 0; R.skip = 0;
-    if (avail < 4) { R.bad = 1; return; }
-    const uint64_t bs = *(const ep_u32u *)r;
-    if (bs < 32 || 4 + bs > avail) { R.bad = 1; return; }
-    const uint8_t *c = r + 4;
-    const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
-    const uint32_t lq = c[8], mapq = c[9], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
-    if (lseq < 0 || 32ull + lq + 4ull * nc + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > bs) { R.bad = 1; return; }
-    // ---- rule E, in its order
-    if (tid < 0 || tid >= P.n_ref || pos < 0) { R.skip = EP_SKIP_UNPLACED; return; }
-    if (flag & P.exclude) { R.skip = EP_SKIP_FLAGGED; return; }
-    if ((int32_t)mapq < P.min_mapq) { R.skip = EP_SKIP_LOW_MAPQ; return; }
-    if (nc == 0) { R.skip = EP_SKIP_NO_CIGAR; return; }
-    if (lseq == 0) { R.skip = EP_SKIP_NO_SEQ; return; }
-    const uint8_t *cg = c + 32 + lq;
-    uint64_t qn = 0; int64_t rlen = 0;
-    for (uint32_t k = 0; k < nc; k++) {
-        const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u;
-        if (op > 8) { R.skip = EP_SKIP_BAD_CIGAR; return; }
-        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qn += w >> 4;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += w >> 4;
-    }
-    if (qn != (uint64_t)lseq) { R.skip = EP_SKIP_BAD_CIGAR; return; }
-    if (ref.tab[2 * tid + 1] < 0) { R.skip = EP_SKIP_NO_REF; return; }
-    if ((uint32_t)lseq > EP_MAX_CYCLE) { R.skip = EP_SKIP_TOO_LONG; return; }
+    reduce::Core c;
+    const int e = reduce::rule_e(r, avail, P.n_ref, P.min_mapq, P.exclude, c);
+    if (e != reduce::ELIGIBLE) { if (e == reduce::BAD) R.bad = 1; else R.skip = (uint8_t)e; return; }
+    if (ref.tab[2 * c.tid + 1] < 0) { R.skip = EP_SKIP_NO_REF; return; }
+    if ((uint32_t)c.l_seq > EP_MAX_CYCLE) { R.skip = EP_SKIP_TOO_LONG; return; }
     if (!P.bed) { R.first = 0; return; }
     // ---- rule B's anchors lie in [pos - 1, pos + rlen] (pos - 1: an insertion behind a zero-length M; pos + rlen: a leading insertion of a
     //      record without reference bases): the first interval that ends behind pos - 1, if it starts at or in front of pos + rlen
-    uint32_t lo = S.tfirst[tid]; const uint32_t tend = S.tfirst[tid + 1]; uint32_t hi = tend;
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (S.iv[mid].end < pos) lo = mid + 1; else hi = mid; }
-    if (lo < tend && (int64_t)S.iv[lo].start <= (int64_t)pos + rlen) R.first = lo;
+    R.first = reduce::first_interval(S, c.tid, c.pos, (int64_t)c.pos + c.rlen + 1);
 }
 
-// rule B for one anchor a, which is x or x - 1, with cur = pileup::seek(S, ., tend, x): the intervals in front of cur end at or in front of
+// rule B for one anchor a, which is x or x - 1, with cur = reduce::seek(S, ., tend, x): the intervals in front of cur end at or in front of
 // x - 1 and hold neither; cur itself may end at x
-EP_HD bool in_sites(const pileup::Sites &S, uint32_t cur, uint32_t tend, int64_t a) {
+EP_HD bool in_sites(const reduce::Sites &S, uint32_t cur, uint32_t tend, int64_t a) {
     if (cur < tend && (int64_t)S.iv[cur].end <= a) cur++;
     return cur < tend && (int64_t)S.iv[cur].start <= a;
 }
@@ -87,7 +68,7 @@ EP_HD bool in_sites(const pileup::Sites &S, uint32_t cur, uint32_t tend, int64_t
 // M / = / X op and over the bases of each I op, lane 0 takes the deletions.  add(row, cls): counter row * 24 + cls += 1, row = segment * 1024
 // + cycle - 1 < 3072, cls < 21.  Reads stay inside the record (the scan checked its fields against block_size, the CIGAR's query length
 // against l_seq and l_seq against 1024) and inside the contig's [0, length).
-template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const pileup::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
+template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
     const uint8_t *c = r + 4;
     const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
     const uint32_t lq = c[8], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
@@ -102,12 +83,12 @@ template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, 
         const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
         if (op == 0 || op == 7 || op == 8) {
             const int64_t xe = x + len;
-            if (P.bed) cur = pileup::seek(S, cur, tend, x);
+            if (P.bed) cur = reduce::seek(S, cur, tend, x);
             for (uint32_t j = cur;; j++) {                                            // the op's columns, or with a BED their part in every interval
                 int64_t a = x, z = xe;
                 if (P.bed) {
                     if (j >= tend || (int64_t)S.iv[j].start >= xe) break;
-                    const pileup::Ivl v = S.iv[j];
+                    const reduce::Ivl v = S.iv[j];
                     a = x > v.start ? x : (int64_t)v.start; z = xe < v.end ? xe : (int64_t)v.end;
                 }
                 for (int64_t col = a + lane; col < z; col += nlanes) {
@@ -126,12 +107,12 @@ template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, 
             }
             x = xe; q += len; seen = true;
         } else if (op == 2) {
-            if (P.bed) cur = pileup::seek(S, cur, tend, x);
+            if (P.bed) cur = reduce::seek(S, cur, tend, x);
             if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), (uint32_t)EP_DEL);
             x += len; seen = true;
         } else if (op == 3) x += len;
         else if (op == 1) {
-            if (P.bed) cur = pileup::seek(S, cur, tend, x);
+            if (P.bed) cur = reduce::seek(S, cur, tend, x);
             if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x))
                 for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), (uint32_t)EP_INS);
             q += len;
@@ -169,29 +150,13 @@ static_assert(EP_CLS == (unsigned)errprof::EP_NCLASS && (EP_CLS & 1u) && EP_CYC 
 
 namespace {
 
-// misc: [0] the lowest malformed record (atomicMin), [1..8] the skip counters of rule E in its order, [9] eligible records
-__global__ __launch_bounds__(256) void k_err_scan(const uint8_t *u, const uint64_t *off, uint64_t n, uint64_t end, uint64_t gbase, errprof::Params P, calmd::Ref ref, pileup::Sites S,
-                                                  uint32_t *meta, unsigned long long *misc) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    errprof::Rec R; R.first = EP_NONE; R.bad = 0; R.skip = 0;
-    const bool live = i < n;
-    if (live) {
-        const uint64_t a = off[i];
-        errprof::scan_record(u + a, a < end ? end - a : 0, P, ref, S, R);
-        meta[i] = R.bad ? EP_NONE : R.first;
-        if (R.bad) atomicMin(misc, (unsigned long long)(gbase + i));
-    }
-    const bool elig = live && !R.bad && !R.skip;
-    unsigned long long b[9];
-#pragma unroll
-    for (int k = 1; k <= 8; k++) b[k] = __ballot(R.skip == k);
-    b[0] = __ballot(elig);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int k = 1; k <= 8; k++) if (b[k]) atomicAdd(misc + k, (unsigned long long)__popcll(b[k]));
-        if (b[0]) atomicAdd(misc + 9, (unsigned long long)__popcll(b[0]));
-    }
-}
+// the scan of k_reduce_scan.  misc: [0] the lowest malformed record, [1..8] the skip counters of rule E in its order, [9] eligible records
+struct ErrScan {
+    typedef errprof::Rec Rec;
+    static constexpr int NSKIP = errprof::EP_N_SKIP; static constexpr bool OPS = false;
+    errprof::Params P; calmd::Ref ref; reduce::Sites S;
+    __device__ void operator()(const uint8_t *r, uint64_t avail, Rec &R) const { errprof::scan_record(r, avail, P, ref, S, R); }
+};
 
 // an add of k_err_count: into the record slot's plane when the cycle lies in it, else to memory
 template <bool DIRECT> struct ErrAdd {
@@ -203,7 +168,7 @@ template <bool DIRECT> struct ErrAdd {
     }
 };
 // 16 lanes per record, 32 records per step; block b takes the records [32 (b + k gridDim.x), + 32) of the window, k = 0, 1, ...
-template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_err_count(const uint8_t *u, const uint64_t *off, uint64_t n, errprof::Params P, calmd::Ref ref, pileup::Sites S,
+template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_err_count(const uint8_t *u, const uint64_t *off, uint64_t n, errprof::Params P, calmd::Ref ref, reduce::Sites S,
                                                                                  const uint32_t *meta, unsigned long long *counts) {
     __shared__ uint32_t s_tab[DIRECT ? 1 : EP_PLANES * EP_PLANE];
     const uint32_t slot = threadIdx.x >> 4, sub = threadIdx.x & 15u;
@@ -230,56 +195,19 @@ template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_err_count
 
 }  // namespace
 
-struct gce_errprof {
-    int32_t device = 0;
-    hipStream_t s = nullptr;
-    std::string err;
-    uint64_t budget = 0;                                                              // device bytes the process may hold (0: no limit beyond the device)
+struct gce_errprof : ReduceSession {
     errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
-    WinIdx w; DevBuf tmp, misc, meta;                                                 // the window; the counters of k_err_scan; 4 bytes per window record
     DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
-    DevBuf iv, tfirst; bool sites_set = false;                                        // rule B's table
     DevBuf counts;                                                                    // EP_COUNTERS 64-bit totals
-    uint64_t n = 0;                                                                   // records so far
+    std::string needs() const override { return "gce_bam_error_profile needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 576 KiB of counters"; }
 };
-
-static int errp_fail(gce_errprof *p, int code, const std::string &m) { if (p) p->err = m; return code; }
-static int errp_oom(gce_errprof *p, const char *what, uint64_t add) {
-    char m[256];
-    snprintf(m, sizeof m, "out of device memory: gce_bam_error_profile needs the reference bases (%llu bytes) + 576 KiB of counters + 16 bytes per interval + one window + 4 bytes per "
-                          "window record (%lld bytes live, budget %llu, %llu more for %s)", (unsigned long long)p->ref_bytes, __atomic_load_n(&g_dev_live, __ATOMIC_RELAXED),
-             (unsigned long long)p->budget, (unsigned long long)add, what);
-    return errp_fail(p, GCE_ERR_OOM, m);
-}
-static bool errp_room(const gce_errprof *p, uint64_t add) {
-    return !p->budget || (uint64_t)std::max<long long>(__atomic_load_n(&g_dev_live, __ATOMIC_RELAXED), 0) + add <= p->budget;
-}
-#define EPCHK(call) do { hipError_t _e = (call); if (_e == hipErrorOutOfMemory) return errp_oom(p, #call, 0); if (_e != hipSuccess) return errp_fail(p, GCE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); } while (0)
 
 extern "C" {
 
-// options: GCE_ERRPROF_DIRECT or 0.  The thresholds are the runner's, checked there.
 int gce_errprof_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errprof **out) {
-    if (!out) return GCE_ERR_INVALID;
-    *out = nullptr;
-    if (options & ~(uint32_t)GCE_ERRPROF_DIRECT) return GCE_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return GCE_ERR_NO_DEVICE;
-    gce_errprof *p = new gce_errprof();
-    p->device = device; p->budget = (uint64_t)device_budget_bytes;
-    p->P.min_mapq = min_mapq; p->P.min_baseq = min_baseq; p->P.exclude = exclude_flags; p->direct = (options & GCE_ERRPROF_DIRECT) != 0;
-    if (hipStreamCreate(&p->s) != hipSuccess) { delete p; return GCE_ERR_HIP; }
-    *out = p;
-    return GCE_OK;
+    return rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, (uint32_t)GCE_ERRPROF_DIRECT, out);
 }
-void gce_errprof_destroy(gce_errprof *p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    (void)hipStreamSynchronize(p->s);
-    p->w.release();
-    for (DevBuf *x : {&p->tmp, &p->misc, &p->meta, &p->blob, &p->tab, &p->iv, &p->tfirst, &p->counts}) x->release();
-    (void)hipStreamDestroy(p->s);
-    delete p;
-}
+void gce_errprof_destroy(gce_errprof *p) { if (p) rd_destroy(p, {&p->blob, &p->tab, &p->counts}); }
 const char *gce_errprof_error(gce_errprof *p) { return p ? p->err.c_str() : ""; }
 
 // the reference, once, first of all: seq[t] / len[t] as gce_sort_calmd_ref takes them, laid out as it lays them out (calmd_ref_layout)
@@ -290,8 +218,8 @@ int gce_errprof_set_ref(gce_errprof *p, int32_t n_ref, const char *const *seq, c
     const uint64_t total = calmd_ref_layout(n_ref, seq, len, tab);
     p->ref_bytes = total; p->P.n_ref = n_ref;
     const uint64_t want = DevBuf::padded(total + 64) + DevBuf::padded(tab.size() * 8);
-    if (!errp_room(p, want)) return errp_oom(p, "the reference bases", want);
-    EPCHK(calmd_ref_upload(p->blob, p->tab, n_ref, seq, len, tab, total, p->s));
+    if (!p->room(want)) return p->oom("the reference bases", want);
+    RDCHK(calmd_ref_upload(p->blob, p->tab, n_ref, seq, len, tab, total, p->s));
     p->ref_set = true;
     return GCE_OK;
 }
@@ -301,78 +229,27 @@ int gce_errprof_set_ref(gce_errprof *p, int32_t n_ref, const char *const *seq, c
 int gce_errprof_set_sites(gce_errprof *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end) {
     if (!p || !p->ref_set || p->sites_set || (n_intervals > 0 && (!tid || !start || !end))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
-    hipStream_t s = p->s;
-    const int32_t n_ref = p->P.n_ref;
     p->P.bed = n_intervals >= 0;
-    const size_t ni = (size_t)std::max<int64_t>(n_intervals, 0);
-    std::vector<pileup::Ivl> iv(ni);
-    std::vector<uint32_t> tf((size_t)n_ref + 1, 0);
-    uint64_t sites = 0;
-    for (size_t j = 0; j < ni; j++) {
-        const bool ordered = j == 0 || tid[j - 1] < tid[j] || (tid[j - 1] == tid[j] && end[j - 1] < start[j]);
-        if (tid[j] < 0 || tid[j] >= n_ref || start[j] < 0 || end[j] <= start[j] || !ordered) return errp_fail(p, GCE_ERR_INVALID, "gce_errprof_set_sites: intervals out of rule S's order");
-        iv[j] = {tid[j], start[j], end[j], (uint32_t)sites};
-        sites += (uint64_t)(end[j] - start[j]);
-        tf[(size_t)tid[j] + 1]++;
-    }
-    for (int32_t t = 0; t < n_ref; t++) tf[(size_t)t + 1] += tf[(size_t)t];
-    const uint64_t need = DevBuf::padded(EP_COUNTERS * 8ull) + DevBuf::padded(iv.size() * sizeof(pileup::Ivl) + 64) + DevBuf::padded(tf.size() * 4) + DevBuf::padded(128);
-    if (!errp_room(p, need)) return errp_oom(p, "the counters and the interval table", need);
-    EPCHK(p->counts.ensure(EP_COUNTERS * 8ull)); EPCHK(p->iv.ensure(iv.size() * sizeof(pileup::Ivl) + 64)); EPCHK(p->tfirst.ensure(tf.size() * 4)); EPCHK(p->misc.ensure(128));
-    EPCHK(hipMemsetAsync(p->counts.p, 0, EP_COUNTERS * 8ull, s));
-    if (!iv.empty()) EPCHK(hipMemcpyAsync(p->iv.p, iv.data(), iv.size() * sizeof(pileup::Ivl), hipMemcpyHostToDevice, s));
-    EPCHK(hipMemcpyAsync(p->tfirst.p, tf.data(), tf.size() * 4, hipMemcpyHostToDevice, s));
-    const unsigned long long init[10] = {~0ull, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    EPCHK(hipMemcpyAsync(p->misc.p, init, sizeof init, hipMemcpyHostToDevice, s));
-    EPCHK(hipStreamSynchronize(s));
-    p->sites_set = true;
-    return GCE_OK;
+    RdTable t;
+    const int rc = rd_intervals(p, "gce_errprof_set_sites", p->P.n_ref, std::max<int64_t>(n_intervals, 0), tid, start, end, t);
+    if (rc != GCE_OK) return rc;
+    return rd_set_sites(p, t, p->counts, EP_COUNTERS * 8ull, 10);
 }
 
-// the next piece of the file, as gce_pileup_window takes it; *errprof_s: the seconds of k_err_scan and k_err_count, added to.  GCE_ERR_INVALID
+// the next piece of the file, as gce_pileup_window takes it; *errprof_s: the seconds of the scan and k_err_count, added to.  GCE_ERR_INVALID
 // names the lowest malformed record, counting from 0 over the file.
 int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s) {
-    if (!p || !p->sites_set || n_ref != p->P.n_ref || n_members < 0 || (n_members && (!comp || !coff || !csize || !usize))) return GCE_ERR_INVALID;
-    (void)hipSetDevice(p->device);
-    hipStream_t s = p->s;
-    {
-        uint64_t u_all = p->w.carry_n; for (int32_t k = 0; k < n_members; k++) u_all += usize[k];
-        const uint64_t add = win_room(p->w, comp_bytes, u_all);
-        if (add && !errp_room(p, add)) return errp_oom(p, "a window of the file", add);
-    }
-    uint64_t total = 0, n_rec = 0, end = 0;
-    int rc = win_inflate_index(p->w, p->tmp, s, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, nullptr, &total, &n_rec, &end, p->err);
-    if (rc == GCE_ERR_OOM) return errp_oom(p, "a window of the file", 0);
-    if (rc != GCE_OK) return rc;
-    if (n_rec) {
-        const double t0 = mono_s();
-        if (n_rec * 4 > p->meta.cap) {
-            const uint64_t add = DevBuf::padded(n_rec * 4);
-            if (!errp_room(p, add)) return errp_oom(p, "the meta of a window's records", add);
-            EPCHK(p->meta.ensure(n_rec * 4));
-        }
-        const uint8_t *u = (const uint8_t *)p->w.win.p; const uint64_t *off = (const uint64_t *)p->w.idx.off.p;
-        const calmd::Ref ref{p->blob.as<uint8_t>(), p->tab.as<int64_t>(), p->P.n_ref};
-        const pileup::Sites S{p->iv.as<pileup::Ivl>(), p->tfirst.as<uint32_t>()};
-        unsigned long long *misc = p->misc.as<unsigned long long>();
-        hipLaunchKernelGGL(k_err_scan, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, u, off, n_rec, end, p->n, p->P, ref, S, p->meta.as<uint32_t>(), misc);
-        EPCHK(hipGetLastError());
-        unsigned long long bad = ~0ull;
-        EPCHK(hipMemcpyAsync(&bad, misc, 8, hipMemcpyDeviceToHost, s)); EPCHK(hipStreamSynchronize(s)); EPCHK(hipGetLastError());
-        if (bad != ~0ull) {
-            char m[160]; snprintf(m, sizeof m, "BAM record %llu (counting from 0): its fields overrun its block_size", bad);
-            return errp_fail(p, GCE_ERR_INVALID, m);
-        }
+    if (!p) return GCE_ERR_INVALID;
+    const calmd::Ref ref{p->blob.as<uint8_t>(), p->tab.as<int64_t>(), p->P.n_ref};
+    const reduce::Sites S = p->sites();
+    return rd_window(p, ErrScan{p->P, ref, S}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, errprof_s, [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end) {
         const unsigned nb = (unsigned)std::min<uint64_t>((n_rec + EP_STEP_RECS - 1) / EP_STEP_RECS, EP_GRID);
         unsigned long long *counts = p->counts.as<unsigned long long>();
-        if (p->direct || (end >> 32)) hipLaunchKernelGGL(k_err_count<true>, dim3(nb), dim3(EP_THREADS), 0, s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
-        else hipLaunchKernelGGL(k_err_count<false>, dim3(nb), dim3(EP_THREADS), 0, s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
-        EPCHK(hipGetLastError()); EPCHK(hipStreamSynchronize(s)); EPCHK(hipGetLastError());
-        p->n += n_rec;
-        if (errprof_s) *errprof_s += mono_s() - t0;
-    }
-    return win_carry(p->w, s, total, end, p->err);
+        if (p->direct || (end >> 32)) hipLaunchKernelGGL(k_err_count<true>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
+        else hipLaunchKernelGGL(k_err_count<false>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
+        return true;
+    });
 }
 
 // after the last window: counters[0] records, [1..8] the skip counters of rule E in its order, [9] eligible; counts_out: room for
@@ -381,17 +258,13 @@ int gce_errprof_finish(gce_errprof *p, int64_t counters[10], uint64_t *counts_ou
     if (!p || !p->sites_set || !counters || !counts_out) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     hipStream_t s = p->s;
-    EPCHK(hipStreamSynchronize(s));
-    p->w.release(); p->meta.release();
     unsigned long long h[10];
-    EPCHK(hipMemcpyAsync(h, p->misc.p, sizeof h, hipMemcpyDeviceToHost, s)); EPCHK(hipStreamSynchronize(s));
-    counters[0] = (int64_t)p->n;
-    for (int k = 1; k <= 9; k++) counters[k] = (int64_t)h[k];
-    EPCHK(hipMemcpyAsync(counts_out, p->counts.p, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s)); EPCHK(hipStreamSynchronize(s));
-    EPCHK(hipGetLastError());
+    const int rc = rd_finish(p, ErrScan::NSKIP, counters, h, 10);
+    if (rc != GCE_OK) return rc;
+    RDCHK(hipMemcpyAsync(counts_out, p->counts.p, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
+    RDCHK(hipGetLastError());
     return GCE_OK;
 }
 
 }  // extern "C"
-#undef EPCHK
 #endif  // GCE_ERRPROF_HOST_CHECK

@@ -1,4 +1,4 @@
-// errprof::scan_record and errprof::count_record of gencore_amd/csrc/gce_errprof.hpp -- what each thread of k_err_scan and each 16-lane group of
+// errprof::scan_record and errprof::count_record of gencore_amd/csrc/gce_errprof.hpp -- what each thread of the scan kernel and each 16-lane group of
 // k_err_count runs -- compiled for the HOST (tests/test_errprof_model.py builds this with the host's address and undefined-behaviour
 // sanitizers and compares what it prints and writes with tests/pyerrprof.py).  Every record, the reference bases and the interval table are
 // handed over in heap blocks of exactly their size, so the sanitizer sees a read past them; the walk runs once with one lane and once with

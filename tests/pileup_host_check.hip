@@ -1,4 +1,4 @@
-// pileup::scan_record and pileup::count_record of gencore_amd/csrc/gce_pileup.hpp -- what each thread of k_pile_scan and each 16-lane group of
+// pileup::scan_record and pileup::count_record of gencore_amd/csrc/gce_pileup.hpp -- what each thread of the scan kernel and each 16-lane group of
 // k_pile_count runs -- compiled for the HOST (tests/test_pileup_model.py builds this with the host's address and undefined-behaviour
 // sanitizers and compares what it prints and writes with tests/pypileup.py).  Every record is handed over in a heap block of exactly its
 // size, so the sanitizer sees a read past it; the walk runs once with one lane and once with 16 lanes standing in for the group, one after

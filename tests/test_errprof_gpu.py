@@ -1,7 +1,7 @@
-"""gce_bam_error_profile on the GPU: k_err_scan and k_err_count, with the LDS planes and with direct atomics (direct=True), against
+"""gce_bam_error_profile on the GPU: the scan (k_reduce_scan) and k_err_count, with the LDS planes and with direct atomics (direct=True), against
 the model (tests/pyerrprof.py) and the hand-written counters (tests/errprofcases.py): every integer equal, so the two variants equal each
 other.  The cases are the smallest at which the kernels can go wrong: every hand case, the cycles at the planes' last index and past it, the
-32-record steps and the grid's stride, 300 identical reads, file order, records cut between windows, the budget, malformed records, the
+32-record steps and the grid's stride, 300 identical reads, file order, records cut between windows, the scan's counter slots, the budget, malformed records, the
 table's text and the command line."""
 import os
 import re
@@ -140,6 +140,30 @@ def test_records_cut_between_windows(built, tmp_path, direct):
 
 @pytest.mark.gpu
 @VARIANTS
+def test_scan_counter_slots(built, tmp_path, direct):
+    """65 records, one wave of the scan and one record: a record for each of rule E's eight skips (the skip_order case's, under min_mapq 1) among
+    eligible ones, so every counter slot of the scan is added to by a wave's ballot and the tail wave runs; in one window, and in windows of half
+    the file, where the slots are added to twice.  Every n_* counter equals the model's"""
+    skips = [c for c in ec.all_cases() if c["label"] == "skip_order"][0]["records"]
+    assert len(skips) == 8
+    good = [ec.rec(0, k % 9, "3M", "ACG", flag=(0, 0x10, 0x40, 0x90)[k & 3]) for k in range(57)]
+    recs = [r for k in range(8) for r in good[7 * k:7 * k + 7] + [skips[k]]] + good[56:]
+    assert len(recs) == 65
+    one, res = run_files(tmp_path, recs, ec.NAMES, ec.LENS, ec.FASTA, direct, block=300, min_mapq=1)
+    assert [res[k] for k in pyerrprof.SKIPS] == [1] * 8 and res["n_eligible"] == 57 and res["n_records"] == 65
+    same(one, res)
+    size = os.path.getsize(str(tmp_path / "x.bam"))
+    assert size // 2 >= 400                                                                # (a member of 300 inflated bytes takes some 330 at the most: half the file holds whole ones)
+    two, _ = run_files(tmp_path, recs, ec.NAMES, ec.LENS, ec.FASTA, direct, block=300, min_mapq=1, window_bytes=size // 2)
+    same(two, res)
+
+
+OOM = re.compile(r"out of device memory: gce_bam_error_profile needs the reference bases \((\d+) bytes\) \+ 576 KiB of counters \+ 16 bytes per interval \+ one window \+ 4 bytes per "
+                 r"window record \(\d+ bytes live, budget (\d+), (\d+) more for the reference bases\)")
+
+
+@pytest.mark.gpu
+@VARIANTS
 def test_budget(built, tmp_path, direct):
     """a budget that cannot hold the reference is GCE_ERR_OOM naming the reference bases, with the footprint in its message; no file is left"""
     from gencore_amd.bamio import error_profile_bam
@@ -149,7 +173,9 @@ def test_budget(built, tmp_path, direct):
     fa.write_text(">c0\n" + "ACGT" * (3 << 18) + "\n")
     with pytest.raises(GceError) as ei:
         error_profile_bam(bam, fa, tsv=tmp_path / "out.tsv", direct=direct, device_budget_bytes=1 << 20)
-    assert ei.value.status == -4 and "the reference bases (%d bytes)" % (3 << 20) in str(ei.value) and "more for the reference bases" in str(ei.value)
+    m = OOM.search(str(ei.value))
+    assert ei.value.status == -4 and m and str(ei.value).endswith(m.group(0)), str(ei.value)
+    assert [int(x) for x in m.groups()[:2]] == [3 << 20, 1 << 20] and int(m.group(3)) > 3 << 20
     assert sorted(p.name for p in tmp_path.iterdir()) == ["in.bam", "ref.fa"]
     run = error_profile_bam(bam, fa, tsv=tmp_path / "out.tsv", direct=direct, device_budget_bytes=64 << 20)
     assert run.n_eligible == 1 and run.n_bases == 2 and 3 << 20 < run.peak_device_bytes <= 64 << 20

@@ -1,7 +1,7 @@
 """gce_bam_error_profile without a GPU: the model of the rules (tests/pyerrprof.py) against records whose counters are written out
 by hand (tests/errprofcases.py) and against tests/pycalmd.py's NM as an arbiter of its own, the symbol, its prototype and its argument checks,
 the flags of the command line, and the per-record functions of the kernels (gce_errprof.hpp) compiled for the host under the address and
-undefined-behaviour sanitizers and compared with the model."""
+undefined-behaviour sanitizers and compared with the model, and its scan beside gce_bam_pileup's: one rule E."""
 import ctypes as C
 import inspect
 import os
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import errprofcases as ec
+import pileupcases as pc
 import pycalmd
 import pyerrprof
 import pypileup
@@ -313,3 +314,41 @@ def test_one_long_stream_on_the_host(host_check):
             res = pyerrprof.profile(recs, ec.refs(), ec.LENS, reg, mq, bq, 0x704)
             assert counts == res["counts"] and res["n_bases"] >= 100
             assert sum(1 for r in rows if r[2] == 0) == res["n_eligible"]
+
+
+@pytest.fixture(scope="module")
+def pileup_host_check(tmp_path_factory):
+    """pileup_host_check, as tests/test_pileup_model.py builds it"""
+    d = tmp_path_factory.mktemp("pileuphost")
+    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
+    exe = str(d / "pileup_host_check")
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "pileup_host_check.hip"), "-o", exe])
+    return d, exe
+
+
+def test_both_scans_apply_one_rule_e(host_check, pileup_host_check):
+    """pileup::scan_record and errprof::scan_record on the same records with the same thresholds: the same bad flag and the same skip code 1..6
+    for every record.  The records are every one of pileupcases' and errprofcases' cases and both malformed() lists, of at most 1024 bases, on
+    a reference that has every contig, so that the error profile's own skips (7 and 8) stay out of it.  Both go through reduce::rule_e
+    (gce_reduce.hpp): this holds by construction, and pins that it stays so."""
+    d, exe = host_check
+    pd, pexe = pileup_host_check
+    recs = [r for cs in pc.all_cases() + ec.all_cases() for r in cs["records"]] + [b for _, b in pc.malformed() + ec.malformed()]
+    recs = [r for r in recs if len(r) < 24 or int.from_bytes(r[20:24], "little", signed=True) <= pyerrprof.MAX_CYCLE]
+    refs = [ec.FASTA.get(nm, "ACGT" * 8) for nm in ec.NAMES]
+    assert all(refs) and len(recs) > 100
+    seen = set()
+    for mq, excl in ((0, 0x704), (10, 0x704), (1, 0x10)):
+        rows, _ = host_run(d, exe, recs, refs, ec.LENS, None, mq, 0, excl)
+        (pd / "intervals").write_text("".join("%d %d %d %d\n" % x for x in pypileup.intervals([(0, 10, 12)], ec.LENS)[0]))
+        (pd / "frames").write_bytes(pc.frames(recs))
+        r = subprocess.run(["timeout", "-k", "10", "300", pexe, str(len(ec.LENS)), str(mq), "0", str(excl), str(pd / "intervals"), str(pd / "frames"), str(pd / "out")],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+        assert r.returncode == 0 and "FAIL" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
+        prows = [[int(x) for x in l.split()] for l in r.stdout.splitlines()]
+        assert len(rows) == len(prows) == len(recs)
+        for k in range(len(recs)):
+            assert rows[k][1:3] == prows[k][1:3] and 0 <= rows[k][2] <= 6 and rows[k][1] in (0, 1), (mq, excl, k, rows[k], prows[k])
+        seen |= {(r[1], r[2]) for r in rows}
+    assert seen == {(1, 0)} | {(0, k) for k in range(7)}                              # malformed, eligible and each of rule E's six skips occur

@@ -1,7 +1,7 @@
-"""gce_bam_pileup on the GPU: k_pile_scan and k_pile_count, with the LDS tile and with direct atomics (direct=True), against the
+"""gce_bam_pileup on the GPU: the scan (k_reduce_scan) and k_pile_count, with the LDS tile and with direct atomics (direct=True), against the
 model (tests/pypileup.py) and the hand-written counters (tests/pileupcases.py): every integer equal, so the two variants equal each other.
 The cases are the smallest at which the kernels can go wrong: every op at an interval's edges, the regions' clamping and merging, the
-nibbles and qualities, every skip, the tile's edges and the 16-record blocks, records cut between windows, the budget, malformed records,
+nibbles and qualities, every skip, the tile's edges and the 16-record blocks, records cut between windows, the scan's counter slots, the budget, malformed records,
 one generated stream, the table's text and the command line."""
 import os
 import re
@@ -129,6 +129,31 @@ def test_records_cut_between_windows(built, tmp_path, direct):
 
 @pytest.mark.gpu
 @VARIANTS
+def test_scan_counter_slots(built, tmp_path, direct):
+    """65 records, one wave of the scan and one record: a record for each of rule E's six skips (the skip_order case's, under min_mapq 1) among
+    eligible ones, so every counter slot of the scan is added to by a wave's ballot and the tail wave runs; in one window, and in windows of half
+    the file, where the slots are added to twice.  Every n_* counter equals the model's"""
+    skips = [c for c in pc.all_cases() if c["label"] == "skip_order"][0]["records"] + [pc.rec(0, 10, [(9, 1)], "A")]
+    assert len(skips) == 6
+    good = [pc.rec(0, 5 + k % 9, "3M", "ACG", flag=16 * (k & 1)) for k in range(59)]
+    recs = [r for k in range(6) for r in good[9 * k:9 * k + 9] + [skips[k]]] + good[54:]
+    assert len(recs) == 65
+    bed = [("c0", 8, 14)]
+    one, res = run_files(tmp_path, recs, bed, pc.NAMES, pc.LENS, direct, block=300, min_mapq=1)
+    assert [res[k] for k in pypileup.SKIPS] == [1] * 6 and res["n_eligible"] == 59 and res["n_records"] == 65
+    same(one, res)
+    size = os.path.getsize(str(tmp_path / "x.bam"))
+    assert size // 2 >= 400                                                                # (a member of 300 inflated bytes takes some 330 at the most: half the file holds whole ones)
+    two, _ = run_files(tmp_path, recs, bed, pc.NAMES, pc.LENS, direct, block=300, min_mapq=1, window_bytes=size // 2)
+    same(two, res)
+
+
+OOM = re.compile(r"out of device memory: gce_bam_pileup needs 64 bytes per site \((\d+) sites: (\d+) bytes\) \+ 16 bytes per interval \+ one window \+ 4 bytes per window record "
+                 r"\(\d+ bytes live, budget (\d+), (\d+) more for the counters and the interval table\)")
+
+
+@pytest.mark.gpu
+@VARIANTS
 def test_budget_and_site_limit(built, tmp_path, direct):
     """a budget that cannot hold the counters is GCE_ERR_OOM with the footprint in its message; more than 2^28 sites is GCE_ERR_INVALID;
     neither leaves a file"""
@@ -139,7 +164,9 @@ def test_budget_and_site_limit(built, tmp_path, direct):
     bed.write_text("c0\t0\t%d\n" % (1 << 20))
     with pytest.raises(GceError) as ei:
         pileup_bam(bam, bed, tsv=tmp_path / "out.tsv", direct=direct, device_budget_bytes=1 << 20)
-    assert ei.value.status == -4 and "64 bytes per site (%d sites: %d bytes)" % (1 << 20, 64 << 20) in str(ei.value) and "one window" in str(ei.value)
+    m = OOM.search(str(ei.value))
+    assert ei.value.status == -4 and m and str(ei.value).endswith(m.group(0)), str(ei.value)
+    assert [int(x) for x in m.groups()[:3]] == [1 << 20, 64 << 20, 1 << 20] and int(m.group(4)) > 64 << 20
     bed.write_text("c0\t0\t%d\n" % ((1 << 28) + 1))
     with pytest.raises(GceError) as ei:
         pileup_bam(bam, bed, tsv=tmp_path / "out.tsv", direct=direct)

@@ -4,7 +4,7 @@ streaming floor over the same file: the cfg3 stream of tools/bam_
     python tools/errprof_bench.py [--workload cfg3] [--pairs 4000000] [--reps 3] [--direct_limit 900] [--out profiles/errprof.json]
 The variants are interleaved; every run is a fresh child process under its own time limit (--limit; the direct variant, whose every add is a
 global atomic on a few thousand addresses, has --direct_limit, and the file is never truncated for it); one warm-up round, then --reps timed
-rounds, reported as medians with all values.  The question is which variant has the lower median errprof_s (k_err_scan + k_err_count, host
+rounds, reported as medians with all values.  The question is which variant has the lower median errprof_s (the scan + k_err_count, host
 clocks around work that ends in a device synchronise): the planes stay the default only if their median beats direct's by more than the
 spread of the values.  gce_bam_index's gpu_s (inflate, record index and the index's kernels) stands beside errprof_s + inflate_index_s so
 that the cost of the count kernels above read, inflate and index is visible.  One rocprofv3 --kernel-trace --stats run per variant, each in a
@@ -93,7 +93,7 @@ def kernel_times(args, tmp, mode):
     kern = {}
     for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"k_err_\w+", r["Name"])                 # (the CSV holds the demangled name)
+            m = re.search(r"k_err_\w+|k_reduce_scan", r["Name"])   # (the CSV holds the demangled name)
             if m:
                 k = kern.setdefault(m.group(0), dict(calls=0, seconds=0.0))
                 k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9

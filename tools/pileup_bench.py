@@ -3,7 +3,7 @@
 pass over the same file this pass was built on: the cfg3 stream of tools/bam_bench.py as a BAM file, with its panel as the BED.
     python tools/pileup_bench.py [--workload cfg3] [--pairs 4000000] [--reps 3] [--out profiles/pileup.json]
 The variants are interleaved; every run is a fresh child process under its own time limit; one warm-up round, then --reps timed rounds,
-reported as medians with all values.  The question is which variant has the lower median pileup_s (k_pile_scan + k_pile_count, host clocks
+reported as medians with all values.  The question is which variant has the lower median pileup_s (the scan + k_pile_count, host clocks
 around work that ends in a device synchronise): if the two differ by less than the spread of their values the default is direct, the simpler
 path.  gce_bam_index's gpu_s (inflate, record index, facts and the index's kernels) stands beside pileup_s + inflate_index_s so that the cost
 of the count kernels above read, inflate and index is visible.  One rocprofv3 --kernel-trace --stats run per variant, each in a process of its
@@ -75,7 +75,7 @@ def kernel_times(args, tmp, mode):
     kern = {}
     for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"k_pile_\w+", r["Name"])                # (the CSV holds the demangled name)
+            m = re.search(r"k_pile_\w+|k_reduce_scan", r["Name"])  # (the CSV holds the demangled name)
             if m:
                 k = kern.setdefault(m.group(0), dict(calls=0, seconds=0.0))
                 k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9

@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp and bamio_errprof.hpp (the last two over bamio_reduce.hpp):
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp and bamio_errprof.hpp (the last three over bamio_reduce.hpp):
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -269,7 +269,7 @@ def umi_to_mi(in_path, out_path, source="RX", device=0, threads=0, level=-2, win
 
 
 class PileupRun:
-    """gce_pileup_run as an object: the counters and bytes as int, the times as float, and the numpy arrays tid, pos ([n_sites], 0-based) and
+    """gce_pileup_run or gce_fragpile_run as an object: the counters and bytes as int, the times as float, and the numpy arrays tid, pos ([n_sites], 0-based) and
     counts ([n_sites, 2 strands, 8 classes]: A C G T N DEL INS LOWQ)."""
     CLASSES = ("A", "C", "G", "T", "N", "DEL", "INS", "LOWQ")
 
@@ -307,6 +307,30 @@ def pileup_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, min_mapq=0,
         return PileupRun(r)
     finally:
         lib.gce_pileup_free(C.byref(r))
+
+
+def pileup_fragments_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, weak_hash=False, window_bytes=0,
+                         device_budget_bytes=0):
+    """gce_bam_pileup_fragments: pileup_bam's table over a coordinate-sorted BAM with every fragment counted once where its mates overlap (as
+    `samtools mpileup` resolves the overlap, in outline): at a site that both mates of a pair cover, one of them is counted -- the earlier in
+    the file where they agree (its quality the sum, at most 200), the one of higher quality where they differ (its quality times 4 / 5).  A
+    record without a partner is counted as pileup_bam counts it.  weak_hash=True keeps 4 bits of the join's hash: the same counters, for
+    tests.  Returns a PileupRun with pileup_bam's fields plus n_pairs, n_shared_columns, n_disagree_columns, n_ambiguous and n_deferred (the
+    records carried across a window boundary: the one counter that depends on window_bytes); raises GceError with the library's message (and
+    leaves no table) on failure, a record that lies in front of its predecessor among them."""
+    from .capi import GCE_FRAGPILE_DIRECT, GCE_FRAGPILE_WEAK_HASH, GceFragpileRun
+    lib = capi.load_library()
+    r = GceFragpileRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_pileup_fragments(str(path).encode(), str(bed).encode(), None if fasta is None else str(fasta).encode(), None if tsv is None else str(tsv).encode(), int(device),
+                                      int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), (GCE_FRAGPILE_DIRECT if direct else 0) | (GCE_FRAGPILE_WEAK_HASH if weak_hash else 0),
+                                      int(window_bytes), int(device_budget_bytes), C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return PileupRun(r)
+    finally:
+        lib.gce_fragpile_free(C.byref(r))
 
 
 class ErrorProfileRun:

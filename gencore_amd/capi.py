@@ -106,10 +106,12 @@ EXPORTED_SYMBOLS = [
     "gce_fasta_load", "gce_fasta_get", "gce_fasta_free", "gce_run_bam", "gce_run_bam_hostcodec", "gce_run_bam_sharded", "gce_run_bam_sharded_hostcodec", "gce_raw_deflate_output", "gce_raw_read_deflated_async", "gce_bgzf_deflate", "gce_raw_deflate_output_codes", "gce_bgzf_deflate_codes", "gce_raw_attach_mirror", "gce_raw_select_shard", "gce_raw_merge_outputs", "gce_raw_begin", "gce_raw_push", "gce_raw_push_bgzf", "gce_bgzf_inflate", "gce_raw_finish", "gce_raw_build_output", "gce_raw_read_output_async", "gce_host_alloc", "gce_host_free", "gce_depth_stats", "gce_stats_payload_device", "gce_stats_payload_sum", "gce_stats_payload_read", "gce_run_bam_depth", "gce_depth_run_free", "gce_stats_device", "gce_stream_context", "gce_plan_shards", "gce_free", "gce_bed_load", "gce_bed_free",
     "gce_report_json", "gce_report_summary", "gce_bam_read_header", "gce_bam_header_free", "gce_run_bam_passes", "gce_device_bytes", "gce_bam_index", "gce_bam_sort", "gce_bam_sort_passes", "gce_sam_parse", "gce_sam_sort",
     "gce_sam_format", "gce_raw_format_output", "gce_raw_read_text_async", "gce_get_sam_format_counters",
-    "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free",
+    "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free", "gce_bam_pileup_fragments", "gce_fragpile_free",
     "gce_bam_error_profile", "gce_errprof_free"]
 
 GCE_PILEUP_DIRECT = 1
+GCE_FRAGPILE_DIRECT = 1
+GCE_FRAGPILE_WEAK_HASH = 2
 GCE_ERRPROF_DIRECT = 1
 GCE_ERRPROF_MAX_CYCLE = 1024
 GCE_ERRPROF_CLASSES = 24
@@ -179,6 +181,12 @@ class GcePileupRun(C.Structure):
                 ("n_no_seq", C.c_int64), ("n_bad_cigar", C.c_int64), ("n_sites", C.c_int64), ("n_intervals", C.c_int64), ("peak_device_bytes", C.c_int64),
                 ("read_s", C.c_double), ("inflate_index_s", C.c_double), ("pileup_s", C.c_double), ("write_s", C.c_double), ("total_s", C.c_double),
                 ("site_tid", C.POINTER(C.c_int32)), ("site_pos", C.POINTER(C.c_int32)), ("counts", C.POINTER(C.c_uint32))]
+
+
+class GceFragpileRun(C.Structure):
+    """gce_fragpile_run (gce_bam_pileup_fragments): gce_pileup_run's fields, then rule M's and rule V's counters."""
+    _fields_ = GcePileupRun._fields_ + [("n_pairs", C.c_int64), ("n_shared_columns", C.c_int64), ("n_disagree_columns", C.c_int64), ("n_ambiguous", C.c_int64),
+                                        ("n_deferred", C.c_int64)]
 
 
 class GceErrprofRun(C.Structure):
@@ -317,6 +325,11 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
                                        C.POINTER(GcePileupRun), C.c_char_p]
         lib.gce_pileup_free.argtypes = [C.POINTER(GcePileupRun)]
         lib.gce_pileup_free.restype = None
+    if hasattr(lib, "gce_bam_pileup_fragments"):
+        lib.gce_bam_pileup_fragments.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_size_t,
+                                                 C.POINTER(GceFragpileRun), C.c_char_p]
+        lib.gce_fragpile_free.argtypes = [C.POINTER(GceFragpileRun)]
+        lib.gce_fragpile_free.restype = None
     if hasattr(lib, "gce_bam_error_profile"):
         lib.gce_bam_error_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_size_t,
                                               C.POINTER(GceErrprofRun), C.c_char_p]

@@ -36,7 +36,10 @@ whose value is not a UMI, are left as they are.  Without the flag such a file ru
 BAM output (after --calmd), so the two tables show which mismatches consensus removed.  A table is tab-separated: contig, 1-based pos, ref (from
 -r), depth, then A C G T N DEL INS LOWQ of the forward and of the reverse strand; records with a flag bit of 0x704 (unmapped, secondary, QC
 fail, duplicate) are left out, as are those below --pileup_min_mapq, and a base below --pileup_min_baseq goes to LOWQ.  Overlapping mates are
-counted twice, there is no BAQ and no split by read group.
+counted twice, there is no BAQ and no split by read group.  With --pileup_fragments (for coordinate-sorted files) both tables count every
+fragment once where its mates overlap, as `samtools mpileup` does in outline: where the mates agree the first in the file is counted with the
+sum of the two qualities (at most 200), where they differ the one of higher quality with 4 / 5 of its quality; a second line on STDERR gives
+the pairs, the shared columns and those that disagree.
 --error_profile FILE and --error_profile_in FILE (not the reference's) count, on the GPU, mismatches against -r by sequencing cycle (what `fgbio
 ErrorRateByReadPosition`, Picard's artifact metrics or the mismatches-per-cycle block of `samtools stats` are run for): --error_profile_in over
 the input as the run reads it, --error_profile over the BAM output (after --calmd), so the two tables show how far the error rate fell, by
@@ -129,6 +132,8 @@ def build_parser():
     a("--pileup_in", default=None, metavar="FILE",
       help="[gencore_amd] the same table over the input as the run reads it (after --sort / --sort_sam, --calmd_in and --umi_from), written to FILE before the run. "
            "Off by default.")
+    a("--pileup_fragments", action="store_true",
+      help="[gencore_amd] --pileup / --pileup_in count each fragment once where its mates overlap (the file must be coordinate-sorted). Off by default.")
     a("--pileup_min_mapq", type=int, default=0, help="[gencore_amd] --pileup / --pileup_in leave out records whose mapping quality is below this (0..255). Default 0.")
     a("--pileup_min_baseq", type=int, default=0, help="[gencore_amd] --pileup / --pileup_in count a base whose quality is below this (0..255) as LOWQ. Default 0.")
     a("--error_profile", default=None, metavar="FILE",
@@ -256,6 +261,8 @@ def validate(o):
     for flag, given in (("--pileup", o.pileup), ("--pileup_in", o.pileup_in)):
         if given is not None and not o.bed:
             err("%s needs the targets of -b" % flag)
+    if o.pileup_fragments and o.pileup is None and o.pileup_in is None:
+        err("--pileup_fragments needs --pileup or --pileup_in")
     if o.pileup is not None and o.output == "-":
         err("--pileup needs an output file, not STDOUT")
     if o.pileup is not None and o.output.endswith("sam"):
@@ -302,15 +309,17 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import calmd_bam_stream, error_profile_bam, index_bam, load_bed, pileup_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
+    from .bamio import calmd_bam_stream, error_profile_bam, index_bam, load_bed, pileup_bam, pileup_fragments_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = calmd_tmp = umi_tmp = out_tmp = None
 
     def pileup(label, bam, tsv):
-        r = pileup_bam(bam, o.bed, fasta=o.ref, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.pileup_min_mapq, min_baseq=o.pileup_min_baseq,
-                       exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
+        r = (pileup_fragments_bam if o.pileup_fragments else pileup_bam)(bam, o.bed, fasta=o.ref, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.pileup_min_mapq,
+                                                                         min_baseq=o.pileup_min_baseq, exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
         sys.stderr.write("%s: %d records, %d eligible, %d sites\n" % (label, r.n_records, r.n_eligible, r.n_sites))
+        if o.pileup_fragments:
+            sys.stderr.write("%s: %d pairs, %d shared columns, %d disagreeing\n" % (label, r.n_pairs, r.n_shared_columns, r.n_disagree_columns))
 
     def error_profile(label, bam, tsv):
         r = error_profile_bam(bam, o.ref, bed=o.bed or None, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.error_profile_min_mapq,

@@ -16,7 +16,7 @@ void gce_errprof_free(gce_errprof_run *out) {
 namespace {
 
 struct ErrprofPass {
-    static constexpr const char *who = "gce_bam_error_profile", *option_name = "GCE_ERRPROF_DIRECT";
+    static constexpr const char *who = "gce_bam_error_profile", *options_known = "GCE_ERRPROF_DIRECT is the only one";
     static constexpr uint32_t option = GCE_ERRPROF_DIRECT;
     static constexpr bool bed_first = false;
     static constexpr auto create = gce_errprof_create; static constexpr auto window = gce_errprof_window; static constexpr auto error = gce_errprof_error;

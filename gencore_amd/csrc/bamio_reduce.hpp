@@ -42,7 +42,7 @@ struct ReduceInput {
 };
 
 // One run of a reduce pass over a BAM file.  PASS is the entry point's own part:
-//   who, option_name, option   the entry point's name, and its one option bit with its name
+//   who, option, options_known the entry point's name, its option bits, and what the refusal of any other says of them
 //   bed_first                  the BED is the required file and checked first, the FASTA optional (else the other way round)
 //   out                        its gce_*_run: read_s, inflate_index_s, write_s, total_s and peak_device_bytes are the frame's to fill
 //   zero(), sites(in)          out as a call starts; what out says of the BED
@@ -58,7 +58,7 @@ template <class PASS> int reduce_run(PASS &ps, const char *bam_path, const char 
     auto *out = ps.out;
     if (min_mapq < 0 || min_mapq > 255) { set_err(err, "min_mapq should be 0..255"); return GCE_ERR_INVALID; }
     if (min_baseq < 0 || min_baseq > 255) { set_err(err, "min_baseq should be 0..255"); return GCE_ERR_INVALID; }
-    if (options & ~PASS::option) { set_err(err, (std::string("unknown option bit (") + PASS::option_name + " is the only one)").c_str()); return GCE_ERR_INVALID; }
+    if (options & ~PASS::option) { set_err(err, (std::string("unknown option bit (") + PASS::options_known + ")").c_str()); return GCE_ERR_INVALID; }
     for (const bool bed : {PASS::bed_first, !PASS::bed_first}) {
         const char *path = bed ? bed_path : fasta_path;
         struct stat sf;

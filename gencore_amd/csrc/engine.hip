@@ -1426,4 +1426,5 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_umi.hpp"
 #include "gce_reduce.hpp"
 #include "gce_pileup.hpp"
+#include "gce_fragpile.hpp"
 #include "gce_errprof.hpp"

@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort, calmd, UMI, pileup and error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp and gce_errprof.hpp (the last two over gce_reduce.hpp).  They are exported, but
+// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup and error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp and gce_errprof.hpp (the last three over gce_reduce.hpp).  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -15,6 +15,7 @@ struct gce_passes;
 struct gce_bai;
 struct gce_sort;
 struct gce_pileup;
+struct gce_fragpile;
 struct gce_errprof;
 
 int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
@@ -86,6 +87,15 @@ int gce_pileup_set_sites(gce_pileup *p, int32_t n_ref, int64_t n_intervals, cons
 int gce_pileup_window(gce_pileup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                       int32_t n_ref, int32_t last, double *pileup_s);
 int gce_pileup_finish(gce_pileup *p, int64_t counters[8], uint32_t *counts_out);
+
+// ---- the same table with every fragment counted once where its mates overlap (gce_fragpile.hpp)
+int gce_fragpile_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_fragpile **out);
+void gce_fragpile_destroy(gce_fragpile *p);
+const char *gce_fragpile_error(gce_fragpile *p);
+int gce_fragpile_set_sites(gce_fragpile *p, int32_t n_ref, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, const uint32_t *site0);
+int gce_fragpile_window(gce_fragpile *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                        int32_t n_ref, int32_t last, double *pileup_s);
+int gce_fragpile_finish(gce_fragpile *p, int64_t counters[13], uint32_t *counts_out);
 
 // ---- mismatches by read cycle against the reference (gce_errprof.hpp)
 int gce_errprof_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errprof **out);

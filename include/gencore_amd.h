@@ -760,6 +760,43 @@ int gce_bam_pileup(const char *bam_path, const char *bed_path, const char *fasta
                    int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
                    uint64_t window_bytes, size_t device_budget_bytes, gce_pileup_run *out, char err[256]);
 void gce_pileup_free(gce_pileup_run *out);
+/* gce_bam_pileup's table with every fragment counted once where its mates overlap, on ONE device (addition under ABI v3;
+ * gencore_amd/csrc/gce_fragpile.hpp).  Replaces: nothing in the reference's source -- it is the overlap handling of the
+ * `samtools mpileup` / `bam-readcount` that gce_bam_pileup stands in for, in outline.  The arguments, sites, record tests, walk, table and
+ * gce_pileup_run's counters are gce_bam_pileup's; a record without a partner is counted exactly as gce_bam_pileup counts it.  Rule P: the
+ * file is coordinate-sorted -- placed records (tid >= 0) in non-decreasing (tid, pos), every record with tid < 0 behind them; the first
+ * record that breaks this ends the run with GCE_ERR_INVALID ("BAM record N (counting from 0) lies in front of its predecessor: ..."),
+ * whether or not a site is near, across windows too; within a window the malformed-record refusal comes first.  Rule M: a counted record
+ * that can touch a site is a candidate when its flag has 0x1, none of 0x4 0x8 0x100 0x800 and exactly one of 0x40 / 0x80, next_refID ==
+ * refID, and next_pos < pos + its reference span when next_pos >= pos.  Two candidates are a pair when their names are byte-equal
+ * (with l_read_name), their refIDs equal, one has 0x40 and the other 0x80, and each lies at the other's next_pos; a, the earlier in the
+ * file.  More than two candidates of one name, refID and unordered {pos, next_pos}: none pairs, each adds to n_ambiguous (defined for
+ * groups inside one window).  A candidate with next_pos >= pos and no partner yet waits (carried across windows on the device, n_deferred)
+ * until a placed record beyond (refID, next_pos), a record with tid < 0 or the end of the file shows that none can come; then it is
+ * counted alone.  The result does not depend on window_bytes.  Rule V, for a pair, at every site column that an M / = / X / D op of both
+ * mates covers (n_shared_columns): each mate has a raw class (A C G T N, DEL for a D column) and a quality (its QUAL byte; 0 for a D column
+ * or without qualities).  Same class: a is counted, with quality min(qa + qb, 200) for the LOWQ test, b adds nothing.  Different classes
+ * (n_disagree_columns): the winner is a when qa >= qb, else b, counted with quality (4 q) / 5; the loser adds nothing.  The winner adds,
+ * on its own strand, to DEL for a DEL, else to LOWQ when it has qualities and the adjusted quality is below min_baseq, else to its class.
+ * Columns one mate alone covers, and every I op of both mates, are counted as gce_bam_pileup counts them.  No BAQ, no split by read group.
+ * options: GCE_FRAGPILE_DIRECT as GCE_PILEUP_DIRECT; GCE_FRAGPILE_WEAK_HASH keeps 4 bits of the join's 64-bit hash: the same counters, a
+ * test's handle on long probe runs.  Device memory: gce_bam_pileup's, 16 bytes per window record, a join table of 4 bytes per slot (at
+ * least twice the records) and two arenas of deferred records, within device_budget_bytes, else GCE_ERR_OOM with that footprint.  The
+ * refusals are gce_bam_pileup's, and rule P's.  site_tid, site_pos and counts are malloc'ed: gce_fragpile_free. */
+#define GCE_FRAGPILE_DIRECT 1u
+#define GCE_FRAGPILE_WEAK_HASH 2u
+typedef struct gce_fragpile_run {
+    int64_t n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar;   /* n_eligible + the six skips = n_records */
+    int64_t n_sites, n_intervals, peak_device_bytes;
+    double  read_s, inflate_index_s, pileup_s, write_s, total_s;   /* pileup_s: the scan, the join, k_frag_count and the carry; write_s: the table */
+    int32_t *site_tid, *site_pos;   /* [n_sites] */
+    uint32_t *counts;               /* [n_sites][2 strands][8 classes] */
+    int64_t n_pairs, n_shared_columns, n_disagree_columns, n_ambiguous, n_deferred;   /* n_deferred alone depends on window_bytes */
+} gce_fragpile_run;
+int gce_bam_pileup_fragments(const char *bam_path, const char *bed_path, const char *fasta_path /* NULL: ref = N */, const char *tsv_path /* NULL: no file */,
+                             int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
+                             uint64_t window_bytes, size_t device_budget_bytes, gce_fragpile_run *out, char err[256]);
+void gce_fragpile_free(gce_fragpile_run *out);
 /* Mismatches by read cycle against the reference, counted on ONE device (addition under ABI v3; gencore_amd/csrc/gce_errprof.hpp).
  * Replaces: nothing in the reference's source -- it stands in for the `fgbio ErrorRateByReadPosition`, Picard artifact metrics or `samtools
  * stats` mismatches-per-cycle a user runs on the input and on the consensus output to see how far the error rate fell; the reference's own

@@ -7,7 +7,11 @@ reported as medians with all values.  The question is which variant has the lowe
 around work that ends in a device synchronise): if the two differ by less than the spread of their values the default is direct, the simpler
 path.  gce_bam_index's gpu_s (inflate, record index, facts and the index's kernels) stands beside pileup_s + inflate_index_s so that the cost
 of the count kernels above read, inflate and index is visible.  One rocprofv3 --kernel-trace --stats run per variant, each in a process of its
-own, gives the kernel times.  There is no pass mark."""
+own, gives the kernel times.  There is no pass mark.
+    python tools/pileup_bench.py --fragments [--out profiles/pileup_fragments.json]
+runs gce_bam_pileup_fragments (frag_tile, frag_direct) beside gce_bam_pileup (tile, direct) on the same file in the same
+interleaved rounds: both passes' pileup_s with all values and the median, the new pass's share of its total_s, tile against direct, and one
+kernel trace per variant.  No time is fixed for the join or the paired walk; the pass is opt-in and no default rides on the outcome."""
 import argparse
 import csv
 import glob
@@ -37,7 +41,8 @@ def child(args):
         d = bamio.index_bam(src, os.path.join(args.child, "in.bam.bai"), threads=args.threads)
         d = {k: v for k, v in (d if isinstance(d, dict) else vars(d)).items() if isinstance(v, (int, float))}
     else:
-        r = bamio.pileup_bam(src, bed, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads, direct=args.mode == "direct")
+        run = bamio.pileup_fragments_bam if args.mode.startswith("frag_") else bamio.pileup_bam
+        r = run(src, bed, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads, direct=args.mode.endswith("direct"))
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(__import__("zlib").crc32(r.counts.tobytes())))
     print(json.dumps(dict(d, wall_s=time.perf_counter() - t0)), flush=True)
 
@@ -75,12 +80,12 @@ def kernel_times(args, tmp, mode):
     kern = {}
     for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"k_pile_\w+|k_reduce_scan", r["Name"])  # (the CSV holds the demangled name)
+            m = re.search(r"k_pile_\w+|k_frag_\w+|k_reduce_scan", r["Name"])  # (the CSV holds the demangled name)
             if m:
                 k = kern.setdefault(m.group(0), dict(calls=0, seconds=0.0))
                 k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9
     if not kern:
-        raise SystemExit("pileup_bench: no k_pile_ row in rocprofv3's *kernel_stats.csv under %s" % prof)
+        raise SystemExit("pileup_bench: no k_pile_ or k_frag_ row in rocprofv3's *kernel_stats.csv under %s" % prof)
     return {n: dict(calls=k["calls"], seconds=round(k["seconds"], 6)) for n, k in sorted(kern.items())}
 
 
@@ -93,10 +98,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--child", default=None)
-    ap.add_argument("--mode", default="tile", choices=("make", "tile", "direct", "index"))
+    ap.add_argument("--mode", default="tile", choices=("make", "tile", "direct", "index", "frag_tile", "frag_direct"))
+    ap.add_argument("--fragments", action="store_true", help="gce_bam_pileup_fragments beside gce_bam_pileup; writes profiles/pileup_fragments.json")
     args = ap.parse_args()
     if args.child is not None:
         return child_make(args) if args.mode == "make" else child(args)
+    if args.fragments:
+        return main_fragments(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "pileup.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_pileup_")
     made = run_child(args, tmp, "make", limit=600)
@@ -132,6 +140,43 @@ def main():
         v = res["variants"][m]
         v["gpu_s_beside_index"] = dict(pileup_s=v["stages"]["pileup_s"], inflate_index_s=v["stages"]["inflate_index_s"], index_gpu_s=res["index"]["stages"]["gpu_s"])
         v["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+def main_fragments(args):
+    args.out = args.out or os.path.join(ROOT, "profiles", "pileup_fragments.json")
+    tmp = args.dir or tempfile.mkdtemp(prefix="gce_fragpile_")
+    made = run_child(args, tmp, "make", limit=600)
+    modes = ("tile", "frag_tile", "direct", "frag_direct")
+    per = {m: [] for m in modes}
+    for rep in range(args.reps + 1):                               # interleaved; the first round is the warm-up
+        for m in modes:
+            r = run_child(args, tmp, m)
+            if rep:
+                per[m].append(r)
+        print("pileup_bench: round %d done" % rep, flush=True)
+    med = lambda rs, k: sorted(r[k] for r in rs)[len(rs) // 2]
+    res = dict(workload=args.workload, pairs=int(args.pairs), reps=args.reps, **made, input_bytes=os.path.getsize(os.path.join(tmp, "in.bam")),
+               clocks="the library's stage times: host clocks around work that ends in a device synchronise",
+               what="gce_bam_pileup_fragments (frag_*) beside gce_bam_pileup on the same file, interleaved; no pass mark", variants={})
+    for m in modes:
+        rs = per[m]
+        res["variants"][m] = dict(stages={k: round(med(rs, k), 5) for k in ("read_s", "inflate_index_s", "pileup_s", "write_s", "total_s", "wall_s")},
+                                  pileup_s_all=[round(r["pileup_s"], 5) for r in rs], total_s_all=[round(r["total_s"], 4) for r in rs], peak_device_bytes=int(rs[0]["peak_device_bytes"]),
+                                  pileup_share_of_total=round(med(rs, "pileup_s") / med(rs, "total_s"), 4),
+                                  counters={c: int(rs[0][c]) for c in rs[0] if c.startswith("n_")}, counts_sum=rs[0]["counts_sum"], counts_crc=rs[0]["counts_crc"])
+    v = res["variants"]
+    res["counters_identical"] = dict(pileup=v["tile"]["counts_crc"] == v["direct"]["counts_crc"], fragments=v["frag_tile"]["counts_crc"] == v["frag_direct"]["counts_crc"] and
+                                     {k: c for k, c in v["frag_tile"]["counters"].items() if k != "n_deferred"} == {k: c for k, c in v["frag_direct"]["counters"].items() if k != "n_deferred"})
+    res["pileup_s_ratio"] = dict(frag_tile_over_tile=round(v["frag_tile"]["stages"]["pileup_s"] / v["tile"]["stages"]["pileup_s"], 3),
+                                 frag_direct_over_direct=round(v["frag_direct"]["stages"]["pileup_s"] / v["direct"]["stages"]["pileup_s"], 3),
+                                 frag_tile_over_frag_direct=round(v["frag_tile"]["stages"]["pileup_s"] / v["frag_direct"]["stages"]["pileup_s"], 3))
+    for m in modes:
+        v[m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

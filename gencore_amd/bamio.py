@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp and bamio_errprof.hpp (the last three over bamio_reduce.hpp):
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp and bamio_fragerr.hpp (the last four over bamio_reduce.hpp):
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -341,12 +341,15 @@ class ErrorProfileRun:
     def __init__(self, r):
         from .capi import GCE_ERRPROF_CLASSES, GCE_ERRPROF_MAX_CYCLE
         for n, t in type(r)._fields_:
-            if n != "counts":
+            if n not in ("counts", "overlap"):
                 setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
-        self.counts = np.ctypeslib.as_array(r.counts, (3 * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES,)).copy().reshape(3, GCE_ERRPROF_MAX_CYCLE, GCE_ERRPROF_CLASSES)
+        table = lambda p: np.ctypeslib.as_array(p, (3 * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES,)).copy().reshape(3, GCE_ERRPROF_MAX_CYCLE, GCE_ERRPROF_CLASSES)
+        self.counts = table(r.counts)
+        if hasattr(r, "overlap"):
+            self.overlap = table(r.overlap)
 
     def as_dict(self):
-        return {k: v for k, v in vars(self).items() if k != "counts"}
+        return {k: v for k, v in vars(self).items() if k not in ("counts", "overlap")}
 
 
 def error_profile_bam(path, fasta, bed=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, window_bytes=0, device_budget_bytes=0):
@@ -371,6 +374,37 @@ def error_profile_bam(path, fasta, bed=None, tsv=None, device=0, threads=0, min_
         return ErrorProfileRun(r)
     finally:
         lib.gce_errprof_free(C.byref(r))
+
+
+OVERLAP_CLASSES = ErrorProfileRun.CLASSES[:16] + ("AGREE_REF", "AGREE_ALT", "DIFF_OTHER", "UNUSABLE", "LOWQ")
+
+
+def error_profile_fragments_bam(path, fasta, bed=None, tsv=None, overlap_tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, weak_hash=False,
+                                window_bytes=0, device_budget_bytes=0):
+    """gce_bam_error_profile_fragments: error_profile_bam's table over a coordinate-sorted BAM with every fragment counted once where its mates
+    overlap -- at a reference position that an M / = / X op of both mates of a pair covers, one of them is counted, chosen as
+    pileup_fragments_bam chooses it -- and a second table, `overlap` (classes OVERLAP_CLASSES), to which both mates add there, each at its
+    own segment and cycle: AGREE_REF, AGREE_ALT (both read the same base and it is not the reference's: older than the sequencer, or a
+    variant), r>b with r != b (this mate's sequencing error: the partner reads the reference base), r>r (this mate read it right, the partner
+    did not), DIFF_OTHER, UNUSABLE (an N, or no usable reference base) and LOWQ (a raw quality below min_baseq).  overlap.sum() is twice
+    n_shared_columns.  tsv, overlap_tsv: the tables' paths, or None.  direct, weak_hash as pileup_fragments_bam takes them.  Returns an
+    ErrorProfileRun with error_profile_bam's fields plus n_pairs, n_shared_columns, n_disagree_columns, n_ambiguous, n_deferred and overlap
+    ([3, 1024, 24], uint64); raises GceError with the library's message (and leaves no table) on failure, a record that lies in front of its
+    predecessor among them."""
+    from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun
+    lib = capi.load_library()
+    r = GceFragerrRun()
+    err = (C.c_char * 256)()
+    enc = lambda x: None if x is None else str(x).encode()
+    rc = lib.gce_bam_error_profile_fragments(str(path).encode(), str(fasta).encode(), enc(bed), enc(tsv), enc(overlap_tsv), int(device), int(threads), int(min_mapq), int(min_baseq),
+                                             int(exclude_flags), (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), int(window_bytes),
+                                             int(device_budget_bytes), C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return ErrorProfileRun(r)
+    finally:
+        lib.gce_fragerr_free(C.byref(r))
 
 
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):

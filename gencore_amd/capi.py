@@ -107,7 +107,7 @@ EXPORTED_SYMBOLS = [
     "gce_report_json", "gce_report_summary", "gce_bam_read_header", "gce_bam_header_free", "gce_run_bam_passes", "gce_device_bytes", "gce_bam_index", "gce_bam_sort", "gce_bam_sort_passes", "gce_sam_parse", "gce_sam_sort",
     "gce_sam_format", "gce_raw_format_output", "gce_raw_read_text_async", "gce_get_sam_format_counters",
     "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free", "gce_bam_pileup_fragments", "gce_fragpile_free",
-    "gce_bam_error_profile", "gce_errprof_free"]
+    "gce_bam_error_profile", "gce_errprof_free", "gce_bam_error_profile_fragments", "gce_fragerr_free"]
 
 GCE_PILEUP_DIRECT = 1
 GCE_FRAGPILE_DIRECT = 1
@@ -115,6 +115,8 @@ GCE_FRAGPILE_WEAK_HASH = 2
 GCE_ERRPROF_DIRECT = 1
 GCE_ERRPROF_MAX_CYCLE = 1024
 GCE_ERRPROF_CLASSES = 24
+GCE_FRAGERR_DIRECT = 1
+GCE_FRAGERR_WEAK_HASH = 2
 
 
 class GceBamInfo(C.Structure):
@@ -196,6 +198,12 @@ class GceErrprofRun(C.Structure):
                 ("n_intervals", C.c_int64), ("peak_device_bytes", C.c_int64),
                 ("read_s", C.c_double), ("inflate_index_s", C.c_double), ("errprof_s", C.c_double), ("write_s", C.c_double), ("total_s", C.c_double),
                 ("counts", C.POINTER(C.c_uint64))]
+
+
+class GceFragerrRun(C.Structure):
+    """gce_fragerr_run (gce_bam_error_profile_fragments): gce_errprof_run's counters and times, rule M's and rule V's counters, the two tables."""
+    _fields_ = GceErrprofRun._fields_[:-1] + [("n_pairs", C.c_int64), ("n_shared_columns", C.c_int64), ("n_disagree_columns", C.c_int64), ("n_ambiguous", C.c_int64),
+                                              ("n_deferred", C.c_int64), ("counts", C.POINTER(C.c_uint64)), ("overlap", C.POINTER(C.c_uint64))]
 
 
 class GceCalmdStreamRun(C.Structure):
@@ -335,6 +343,11 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
                                               C.POINTER(GceErrprofRun), C.c_char_p]
         lib.gce_errprof_free.argtypes = [C.POINTER(GceErrprofRun)]
         lib.gce_errprof_free.restype = None
+    if hasattr(lib, "gce_bam_error_profile_fragments"):
+        lib.gce_bam_error_profile_fragments.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                                                        C.c_uint64, C.c_size_t, C.POINTER(GceFragerrRun), C.c_char_p]
+        lib.gce_fragerr_free.argtypes = [C.POINTER(GceFragerrRun)]
+        lib.gce_fragerr_free.restype = None
     lib.gce_depth_run_free.argtypes = [C.POINTER(GceDepthRun)]
     lib.gce_depth_run_free.restype = None
     lib.gce_bed_load.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

@@ -48,6 +48,12 @@ sixteen counts A>A .. T>T of reference base against read base in read orientatio
 from C>A), then READ_N REF_OTHER LOWQ INS DEL; integers only, no rates.  Records with a flag bit of 0x704 are left out, as are those below
 --error_profile_min_mapq, on a contig -r lacks or longer than 1024 bases; a base below --error_profile_min_baseq goes to LOWQ.  With -b only
 events on the targets count.  Hard clips do not count into the cycle, known variants are not masked, there is no split by read group.
+Overlapping mates are counted twice.  With --error_profile_fragments (for coordinate-sorted files) both tables count every fragment once
+where its mates overlap, choosing the mate as --pileup_fragments does, and a second table, FILE.overlap.tsv, says what the two mates of a pair
+show about each other at the positions both cover: segment, cycle, shared, errors, the sixteen A>A .. T>T (off the diagonal this mate's
+sequencing error, its partner reading the reference base; on it the partner's), then AGREE_REF, AGREE_ALT (both read the same base that is
+not the reference's: older than the sequencer, or a variant), DIFF_OTHER, UNUSABLE and LOWQ; a second line on STDERR gives the pairs, the
+shared columns and those that disagree.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -146,6 +152,9 @@ def build_parser():
       help="[gencore_amd] --error_profile / --error_profile_in leave out records whose mapping quality is below this (0..255). Default 0.")
     a("--error_profile_min_baseq", type=int, default=0,
       help="[gencore_amd] --error_profile / --error_profile_in count a base whose quality is below this (0..255) as LOWQ. Default 0.")
+    a("--error_profile_fragments", action="store_true",
+      help="[gencore_amd] --error_profile / --error_profile_in count each fragment once where its mates overlap (the file must be coordinate-sorted) and write the mates' "
+           "agreement by cycle to FILE.overlap.tsv beside each. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -282,6 +291,8 @@ def validate(o):
         with open(o.input, "rb") as f:
             if f.read(2) != b"\x1f\x8b":
                 err("--error_profile_in needs BAM input, not SAM text")
+    if o.error_profile_fragments and o.error_profile is None and o.error_profile_in is None:
+        err("--error_profile_fragments needs --error_profile or --error_profile_in")
     for name in ("error_profile_min_mapq", "error_profile_min_baseq"):
         if not (0 <= getattr(o, name) <= 255):
             err("%s should be 0..255" % name)
@@ -309,7 +320,7 @@ def main(argv=None):
     command = "".join(a + " " for a in ["gencore"] + argv)           # main.cpp:101-104
     if o.html is not None:
         print("NOTE: gencore_amd does not write the HTML report; --html %s is ignored" % o.html, file=sys.stderr)
-    from .bamio import calmd_bam_stream, error_profile_bam, index_bam, load_bed, pileup_bam, pileup_fragments_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
+    from .bamio import calmd_bam_stream, error_profile_bam, error_profile_fragments_bam, index_bam, load_bed, pileup_bam, pileup_fragments_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
     from .capi import GceError
     from .report import read_header, summary, write_json
     sorted_tmp = calmd_tmp = umi_tmp = out_tmp = None
@@ -322,9 +333,12 @@ def main(argv=None):
             sys.stderr.write("%s: %d pairs, %d shared columns, %d disagreeing\n" % (label, r.n_pairs, r.n_shared_columns, r.n_disagree_columns))
 
     def error_profile(label, bam, tsv):
-        r = error_profile_bam(bam, o.ref, bed=o.bed or None, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.error_profile_min_mapq,
-                              min_baseq=o.error_profile_min_baseq, exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
+        kw = dict(bed=o.bed or None, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.error_profile_min_mapq, min_baseq=o.error_profile_min_baseq, exclude_flags=0x704,
+                  device_budget_bytes=o.device_memory_bytes)
+        r = error_profile_fragments_bam(bam, o.ref, overlap_tsv=tsv + ".overlap.tsv", **kw) if o.error_profile_fragments else error_profile_bam(bam, o.ref, **kw)
         sys.stderr.write("%s: %d records, %d eligible, %d bases, %d mismatches\n" % (label, r.n_records, r.n_eligible, r.n_bases, r.n_mismatches))
+        if o.error_profile_fragments:
+            sys.stderr.write("%s: %d pairs, %d shared columns, %d disagreeing\n" % (label, r.n_pairs, r.n_shared_columns, r.n_disagree_columns))
     tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged

@@ -20,8 +20,9 @@
 //   bamio_pileup.hpp  gce_bam_pileup
 //   bamio_fragpile.hpp gce_bam_pileup_fragments
 //   bamio_errprof.hpp gce_bam_error_profile
+//   bamio_fragerr.hpp gce_bam_error_profile_fragments
 // No part launches a kernel itself: the runners read the file, find its BGZF members and hand them, window by window, to the engine's entry
-// points in engine.hip (gce_raw_* of the public header; gce_passes_*, gce_bai_*, gce_sort_*, gce_pileup_*, gce_fragpile_*, gce_errprof_* of gce_entry.h, the one place they are declared),
+// points in engine.hip (gce_raw_* of the public header; gce_passes_*, gce_bai_*, gce_sort_*, gce_pileup_*, gce_fragpile_*, gce_errprof_*, gce_fragerr_* of gce_entry.h, the one place they are declared),
 // which inflate, index, process, sort and deflate in HBM; the output comes back in pieces and is written on the host.
 //
 // One copy of each shared piece: member framing, the BAM header, the member codec, the EOF member and the file helpers are in gce_bgzf.hpp;
@@ -811,3 +812,4 @@ void gce_bed_free(int32_t n_regions, int32_t *tid, int32_t *start, int32_t *end,
 #include "bamio_pileup.hpp"
 #include "bamio_fragpile.hpp"
 #include "bamio_errprof.hpp"
+#include "bamio_fragerr.hpp"

@@ -15,6 +15,31 @@ void gce_errprof_free(gce_errprof_run *out) {
 
 namespace {
 
+// rule O's table of one block of counters: the header line (its third and fourth column and the five behind the sixteen are the caller's),
+// then per segment one row per cycle up to the last with a counter: segment, cycle, the sum of the classes below n_sum, the off-diagonal
+// ones of the sixteen, the 21 counters.  total, offdiag: those two sums over the table, added to
+inline void errprof_table(const uint64_t *counts, const char *col3, const char *col4, const char *tail, int n_sum, int64_t &total, int64_t &offdiag, std::string &buf) {
+    buf += "#segment\tcycle\t"; buf += col3; buf += '\t'; buf += col4;
+    for (const char *r : {"A", "C", "G", "T"}) for (const char *b : {"A", "C", "G", "T"}) { buf += '\t'; buf += r; buf += '>'; buf += b; }
+    buf += tail;
+    for (int g = 0; g < 3; g++) {
+        const uint64_t *seg = counts + (size_t)g * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES;
+        int last = 0;                                                                 // the last cycle with a counter
+        for (int cy = 1; cy <= GCE_ERRPROF_MAX_CYCLE; cy++) for (int k = 0; k < 21; k++) if (seg[(size_t)(cy - 1) * GCE_ERRPROF_CLASSES + k]) last = cy;
+        for (int cy = 1; cy <= last; cy++) {
+            const uint64_t *k = seg + (size_t)(cy - 1) * GCE_ERRPROF_CLASSES;
+            uint64_t bases = 0, mism = 0;
+            for (int q = 0; q < n_sum; q++) { bases += k[q]; if (q < 16 && (q >> 2) != (q & 3)) mism += k[q]; }
+            total += (int64_t)bases; offdiag += (int64_t)mism;
+            char line[26 * 21], *w = line;
+            w = pile_num(w, (uint64_t)g); *w++ = '\t'; w = pile_num(w, (uint64_t)cy); *w++ = '\t'; w = pile_num(w, bases); *w++ = '\t'; w = pile_num(w, mism);
+            for (int q = 0; q < 21; q++) { *w++ = '\t'; w = pile_num(w, k[q]); }
+            *w++ = '\n';
+            buf.append(line, (size_t)(w - line));
+        }
+    }
+}
+
 struct ErrprofPass {
     static constexpr const char *who = "gce_bam_error_profile", *options_known = "GCE_ERRPROF_DIRECT is the only one";
     static constexpr uint32_t option = GCE_ERRPROF_DIRECT;
@@ -46,25 +71,8 @@ struct ErrprofPass {
     }
     // rule O: the totals, with or without a file, and one row per cycle up to the last with a counter
     template <class EMIT> bool table(const ReduceInput &, bool, EMIT &&emit) {
-        std::string buf = "#segment\tcycle\tbases\tmismatches";
-        for (const char *r : {"A", "C", "G", "T"}) for (const char *b : {"A", "C", "G", "T"}) { buf += '\t'; buf += r; buf += '>'; buf += b; }
-        buf += "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\n";
-        for (int g = 0; g < 3; g++) {
-            const uint64_t *seg = out->counts + (size_t)g * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES;
-            int last = 0;                                                             // the last cycle with a counter
-            for (int cy = 1; cy <= GCE_ERRPROF_MAX_CYCLE; cy++) for (int k = 0; k < 21; k++) if (seg[(size_t)(cy - 1) * GCE_ERRPROF_CLASSES + k]) last = cy;
-            for (int cy = 1; cy <= last; cy++) {
-                const uint64_t *k = seg + (size_t)(cy - 1) * GCE_ERRPROF_CLASSES;
-                uint64_t bases = 0, mism = 0;
-                for (int q = 0; q < 16; q++) { bases += k[q]; if ((q >> 2) != (q & 3)) mism += k[q]; }
-                out->n_bases += (int64_t)bases; out->n_mismatches += (int64_t)mism;
-                char line[26 * 21], *w = line;
-                w = pile_num(w, (uint64_t)g); *w++ = '\t'; w = pile_num(w, (uint64_t)cy); *w++ = '\t'; w = pile_num(w, bases); *w++ = '\t'; w = pile_num(w, mism);
-                for (int q = 0; q < 21; q++) { *w++ = '\t'; w = pile_num(w, k[q]); }
-                *w++ = '\n';
-                buf.append(line, (size_t)(w - line));
-            }
-        }
+        std::string buf;
+        errprof_table(out->counts, "bases", "mismatches", "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\n", 16, out->n_bases, out->n_mismatches, buf);
         return emit(buf);
     }
 };

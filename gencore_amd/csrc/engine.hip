@@ -1428,3 +1428,4 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_pileup.hpp"
 #include "gce_fragpile.hpp"
 #include "gce_errprof.hpp"
+#include "gce_fragerr.hpp"

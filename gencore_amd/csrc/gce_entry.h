@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup and error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp and gce_errprof.hpp (the last three over gce_reduce.hpp).  They are exported, but
+// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp (the last four over gce_reduce.hpp).  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -17,6 +17,7 @@ struct gce_sort;
 struct gce_pileup;
 struct gce_fragpile;
 struct gce_errprof;
+struct gce_fragerr;
 
 int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
 
@@ -106,6 +107,16 @@ int gce_errprof_set_sites(gce_errprof *p, int64_t n_intervals, const int32_t *ti
 int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s);
 int gce_errprof_finish(gce_errprof *p, int64_t counters[10], uint64_t *counts_out);
+
+// ---- the same table with every fragment counted once where its mates overlap, and the overlap table (gce_fragerr.hpp)
+int gce_fragerr_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_fragerr **out);
+void gce_fragerr_destroy(gce_fragerr *p);
+const char *gce_fragerr_error(gce_fragerr *p);
+int gce_fragerr_set_ref(gce_fragerr *p, int32_t n_ref, const char *const *seq, const int64_t *len);
+int gce_fragerr_set_sites(gce_fragerr *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_fragerr_window(gce_fragerr *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                       int32_t n_ref, int32_t last, double *errprof_s);
+int gce_fragerr_finish(gce_fragerr *p, int64_t counters[15], uint64_t *counts_out, uint64_t *overlap_out);
 
 }  // extern "C"
 #endif

@@ -202,16 +202,9 @@ struct gce_errprof : ReduceSession {
     std::string needs() const override { return "gce_bam_error_profile needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 576 KiB of counters"; }
 };
 
-extern "C" {
-
-int gce_errprof_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errprof **out) {
-    return rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, (uint32_t)GCE_ERRPROF_DIRECT, out);
-}
-void gce_errprof_destroy(gce_errprof *p) { if (p) rd_destroy(p, {&p->blob, &p->tab, &p->counts}); }
-const char *gce_errprof_error(gce_errprof *p) { return p ? p->err.c_str() : ""; }
-
-// the reference, once, first of all: seq[t] / len[t] as gce_sort_calmd_ref takes them, laid out as it lays them out (calmd_ref_layout)
-int gce_errprof_set_ref(gce_errprof *p, int32_t n_ref, const char *const *seq, const int64_t *len) {
+// The reference and rule B's intervals of a pass whose object T has gce_errprof's members (P, blob, tab, ref_bytes, ref_set, counts):
+// gce_errprof_set_ref / gce_errprof_set_sites and gce_fragerr.hpp's.  counts_bytes: the pass's counters
+template <class T> static int ep_set_ref(T *p, int32_t n_ref, const char *const *seq, const int64_t *len) {
     if (!p || p->ref_set || n_ref < 0 || (n_ref && (!seq || !len))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     std::vector<int64_t> tab;
@@ -223,17 +216,31 @@ int gce_errprof_set_ref(gce_errprof *p, int32_t n_ref, const char *const *seq, c
     p->ref_set = true;
     return GCE_OK;
 }
-
-// rule B's intervals, once, behind the reference and in front of the first window, as gce_pileup_set_sites takes them; n_intervals < 0: no BED.
-// The counters are made and zeroed.
-int gce_errprof_set_sites(gce_errprof *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end) {
+template <class T> static int ep_set_sites(T *p, const char *entry, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, uint64_t counts_bytes) {
     if (!p || !p->ref_set || p->sites_set || (n_intervals > 0 && (!tid || !start || !end))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     p->P.bed = n_intervals >= 0;
     RdTable t;
-    const int rc = rd_intervals(p, "gce_errprof_set_sites", p->P.n_ref, std::max<int64_t>(n_intervals, 0), tid, start, end, t);
+    const int rc = rd_intervals(p, entry, p->P.n_ref, std::max<int64_t>(n_intervals, 0), tid, start, end, t);
     if (rc != GCE_OK) return rc;
-    return rd_set_sites(p, t, p->counts, EP_COUNTERS * 8ull, 10);
+    return rd_set_sites(p, t, p->counts, counts_bytes, 10);
+}
+
+extern "C" {
+
+int gce_errprof_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errprof **out) {
+    return rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, (uint32_t)GCE_ERRPROF_DIRECT, out);
+}
+void gce_errprof_destroy(gce_errprof *p) { if (p) rd_destroy(p, {&p->blob, &p->tab, &p->counts}); }
+const char *gce_errprof_error(gce_errprof *p) { return p ? p->err.c_str() : ""; }
+
+// the reference, once, first of all: seq[t] / len[t] as gce_sort_calmd_ref takes them, laid out as it lays them out (calmd_ref_layout)
+int gce_errprof_set_ref(gce_errprof *p, int32_t n_ref, const char *const *seq, const int64_t *len) { return ep_set_ref(p, n_ref, seq, len); }
+
+// rule B's intervals, once, behind the reference and in front of the first window, as gce_pileup_set_sites takes them; n_intervals < 0: no BED.
+// The counters are made and zeroed.
+int gce_errprof_set_sites(gce_errprof *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end) {
+    return ep_set_sites(p, "gce_errprof_set_sites", n_intervals, tid, start, end, EP_COUNTERS * 8ull);
 }
 
 // the next piece of the file, as gce_pileup_window takes it; *errprof_s: the seconds of the scan and k_err_count, added to.  GCE_ERR_INVALID

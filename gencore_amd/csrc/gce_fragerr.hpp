@@ -1,0 +1,294 @@
+// gce_fragerr.hpp — gce_bam_error_profile's table with every fragment counted once where its mates overlap, and a second table of what the two
+// mates say about each other there (gce_bam_error_profile_fragments).
+//
+// Rules E, G, C, B, W and O are gce_errprof.hpp's, rules P and M and the join that carries them across windows gce_matejoin.hpp's.  New here:
+// rule V' (at a column that an M / = / X op of both mates covers, one of the two is counted in the primary table, as gce_fragpile.hpp's rule V
+// chooses it) and rule X (both mates add to the overlap table there: agreement with the reference, agreement against it, or which of the two
+// made a sequencing error at which cycle).  Per window, behind the scan (k_reduce_scan over ErrScan) and the join:
+//   k_fragerr_count  k_err_count's shape: 16 lanes per entry, 32 entries per step of a block of 512 threads, a fixed grid whose blocks stride
+//                    over the entries.  errprof::count_record for an entry without partner, nothing for a deferred one,
+//                    errprof::paired_walk for a mate: it walks its own columns with an errprof::Cursor over the partner's CIGAR, which only
+//                    moves forward, so a lane reads every op of the partner once per record, not once per column.  One LDS plane for the
+//                    primary table and one for the overlap table; cycles past EP_CYC are 64-bit global atomics.  k_fragerr_count<true>
+//                    (GCE_FRAGERR_DIRECT): global atomics only.
+// errprof::Cursor and errprof::paired_walk are __host__ __device__: tests/fragerr_host_check.hip runs them on the host against
+// tests/pyfragerr.py, the model of the rules.
+#pragma once
+#include <cstdint>
+#include "gce_errprof.hpp"
+#include "gce_matejoin.hpp"
+
+namespace errprof {
+
+#define EP_HD __host__ __device__ inline
+
+enum { OVL_AGREE_REF = 16, OVL_AGREE_ALT, OVL_DIFF_OTHER, OVL_UNUSABLE, OVL_LOWQ, OVL_NCLASS };
+static_assert((unsigned)OVL_NCLASS == EP_CLS, "the overlap table has the primary table's row");
+
+// A forward-only cursor over the CIGAR of an eligible record o: op k starts at reference x0 and query q0.  at(x, cls, q): the raw class
+// (0..3 = A C G T, 4 = N) and the quality (0 for a record without qualities) of o's base at reference column x; false: no M / = / X op of o
+// covers x.  The x of successive calls must not decrease: every op is read once however many columns are asked for.
+struct Cursor {
+    const uint8_t *cg, *sq, *ql; uint32_t nc, k, q0; int64_t x0; bool has_q;
+    EP_HD explicit Cursor(const uint8_t *o) {
+        const uint8_t *c = o + 4;
+        const int32_t lseq = (int32_t) * (const ep_u32u *)(c + 16);
+        const uint32_t lq = c[8];
+        nc = *(const ep_u16u *)(c + 12);
+        cg = c + 32 + lq; sq = cg + 4 * nc; ql = sq + ((uint32_t)lseq + 1) / 2;
+        has_q = ql[0] != 0xFF;
+        k = 0; q0 = 0; x0 = (int32_t) * (const ep_u32u *)(c + 4);
+    }
+    EP_HD bool at(int64_t x, uint32_t &cls, uint32_t &q) {
+        if (x < x0) return false;                                                     // (in front of pos: x0 never passes an x that was asked for)
+        for (; k < nc; k++) {
+            const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
+            if (op == 0 || op == 7 || op == 8) {
+                if (x < x0 + len) {
+                    const uint32_t yi = q0 + (uint32_t)(x - x0), nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
+                    cls = nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
+                    q = has_q ? ql[yi] : 0u;
+                    return true;
+                }
+                x0 += len; q0 += len;
+            } else if (op == 2 || op == 3) {
+                if (x < x0 + len) return false;
+                x0 += len;
+            } else if (op == 1 || op == 4) q0 += len;
+        }
+        return false;
+    }
+};
+
+// Rules W, V' and X for a mate r of a pair whose other mate is o, by lane `lane` of the record's `nlanes`, as count_record walks a record
+// alone.  is_b: r is the later of the two in the file.  A column that an M / = / X op of o covers is shared: add2(row, cls) takes r's count
+// of rule X, and add(row, cls) r's count of rule V' if r is the one rule V' counts.  Every other column, every insertion and every deletion is
+// rule W's.  shared, differ: rule V's counters, added to by the later mate's walk alone.
+template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first,
+                                                        uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ) {
+    const uint8_t *c = r + 4;
+    const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
+    const uint32_t lq = c[8], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
+    const uint8_t *cg = c + 32 + lq, *sq = cg + 4 * nc, *ql = sq + ((uint32_t)lseq + 1) / 2;
+    const bool rev = (flag & 16u) != 0, has_q = ql[0] != 0xFF;
+    const uint32_t seg = (flag & 0xC0u) == 0x40u ? 1u : (flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
+    const uint32_t tend = P.bed ? S.tfirst[tid + 1] : 0u;
+    const uint8_t *rb = ref.blob + ref.tab[2 * tid]; const int64_t rlen = ref.tab[2 * tid + 1];
+    Cursor oc(o);
+    uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
+#define EP_CYC0(y) (rev ? (uint32_t)lseq - 1u - (y) : (y))                             // rule C, less one
+    for (uint32_t k = 0; k < nc; k++) {
+        const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
+        if (op == 0 || op == 7 || op == 8) {
+            const int64_t xe = x + len;
+            if (P.bed) cur = reduce::seek(S, cur, tend, x);
+            for (uint32_t j = cur;; j++) {                                            // the op's columns, or with a BED their part in every interval
+                int64_t a = x, z = xe;
+                if (P.bed) {
+                    if (j >= tend || (int64_t)S.iv[j].start >= xe) break;
+                    const reduce::Ivl v = S.iv[j];
+                    a = x > v.start ? x : (int64_t)v.start; z = xe < v.end ? xe : (int64_t)v.end;
+                }
+                for (int64_t col = a + lane; col < z; col += nlanes) {
+                    const uint32_t yi = q + (uint32_t)(col - x), row = row0 + EP_CYC0(yi);
+                    const uint32_t mq = has_q ? ql[yi] : 0u;
+                    uint32_t rc = 4;
+                    if (col < rlen) { const uint8_t b = rb[col] & 0xDFu; rc = b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; }
+                    const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u, bc = nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
+                    uint32_t ob = 0, oq = 0, adj = mq;
+                    if (oc.at(col, ob, oq)) {
+                        // ---- rule X: this mate's count in the overlap table
+                        uint32_t xc;
+                        if ((has_q && (int32_t)mq < P.min_baseq) || (oc.has_q && (int32_t)oq < P.min_baseq)) xc = OVL_LOWQ;
+                        else if (bc > 3 || ob > 3 || rc > 3) xc = OVL_UNUSABLE;
+                        else if (bc == ob) xc = bc == rc ? (uint32_t)OVL_AGREE_REF : (uint32_t)OVL_AGREE_ALT;
+                        else if (ob == rc || bc == rc) xc = rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
+                        else xc = OVL_DIFF_OTHER;
+                        add2(row, xc);
+                        // ---- rule V': which of the two the primary table counts, and at which quality
+                        const uint32_t qa = is_b ? oq : mq, qb = is_b ? mq : oq;
+                        bool mine;
+                        if (bc == ob) { mine = !is_b; adj = qa + qb < FP_Q_CAP ? qa + qb : FP_Q_CAP; }
+                        else { mine = is_b ? qa < qb : qa >= qb; adj = (4u * mq) / 5u; }
+                        if (is_b) { shared++; differ += bc != ob; }
+                        if (!mine) continue;
+                    }
+                    const uint32_t cls = has_q && (int32_t)adj < P.min_baseq ? (uint32_t)EP_LOWQ
+                                         : rc > 3 ? (uint32_t)EP_REF_OTHER : bc > 3 ? (uint32_t)EP_READ_N : rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
+                    add(row, cls);
+                }
+                if (!P.bed) break;
+            }
+            x = xe; q += len; seen = true;
+        } else if (op == 2) {
+            if (P.bed) cur = reduce::seek(S, cur, tend, x);
+            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), (uint32_t)EP_DEL);
+            x += len; seen = true;
+        } else if (op == 3) x += len;
+        else if (op == 1) {
+            if (P.bed) cur = reduce::seek(S, cur, tend, x);
+            if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x))
+                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), (uint32_t)EP_INS);
+            q += len;
+        } else if (op == 4) q += len;
+    }
+#undef EP_CYC0
+}
+
+#undef EP_HD
+
+}  // namespace errprof
+
+// k_fragerr_count's LDS is k_err_count's: two planes of EP_PLANE 32-bit counters, 80 640 bytes, 2 blocks of 8 waves a CU.  Here one plane
+// belongs to the primary table and one to the overlap table, so the two entries of a 32-lane LDS lane group share a plane (DESIGN.md 4j
+// measured one plane as fast as two).  Row stride EP_CLS 21 for both: the 16 lanes of an entry, on 16 consecutive cycles, fall on 16
+// different banks.
+// The 32-bit counters cannot wrap within one launch.  Per table, every add reads a byte of the entries no other add to that table reads: in
+// the primary table the quality byte of the counted base (at a shared column the one mate that rule V' counts adds, at its own base) or the
+// low byte of the CIGAR word of a D; in the overlap table each mate adds once per base of its own, that base's quality byte.  So a launch
+// adds fewer than 2^32 times to either table while the window and the pending records together are shorter than 2^32 bytes;
+// gce_fragerr::process launches the direct kernel otherwise.
+static_assert(2u * EP_PLANE * 4u <= EP_LDS_PER_CU / EP_BLOCKS_PER_CU, "k_fragerr_count's planes must leave the CU its 2 blocks of 8 waves");
+
+#ifndef GCE_FRAGERR_HOST_CHECK
+
+namespace {
+
+// what k_reduce_scan over ErrScan left in meta: the first interval (0 without a BED), or EP_NONE for a record that is skipped or touches none
+struct FragerrRead {
+    errprof::Params P;
+    __device__ bool operator()(const uint8_t *r, uint32_t m, uint32_t &first, reduce::Core &C) const {
+        first = m;
+        return m != EP_NONE && reduce::rule_e(r, 4ull + rb32(r), P.n_ref, P.min_mapq, P.exclude, C) == reduce::ELIGIBLE;
+    }
+};
+
+// 16 lanes per entry, 32 entries per step; block b takes the entries [32 (b + k gridDim.x), + 32) of the join, k = 0, 1, ...
+template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_fragerr_count(FragView V, errprof::Params P, calmd::Ref ref, reduce::Sites S, const uint32_t *first, const uint32_t *partner,
+                                                                                     unsigned long long *counts, unsigned long long *ovl, unsigned long long *fm) {
+    __shared__ uint32_t s_tab[DIRECT ? 1 : 2 * EP_PLANE];
+    const uint32_t slot = threadIdx.x >> 4, sub = threadIdx.x & 15u;
+    if (!DIRECT) {
+        for (uint32_t i = threadIdx.x; i < 2 * EP_PLANE; i += EP_THREADS) s_tab[i] = 0u;
+        __syncthreads();
+    }
+    ErrAdd<DIRECT> add{s_tab, counts}, add2{s_tab + (DIRECT ? 0u : EP_PLANE), ovl};
+    uint32_t shared = 0, differ = 0;
+    for (uint64_t e = (uint64_t)blockIdx.x * EP_STEP_RECS + slot; e < V.n; e += (uint64_t)gridDim.x * EP_STEP_RECS) {
+        const uint32_t pc = partner[e];
+        if (pc == FP_SKIP || pc == FP_DEFER) continue;
+        const uint32_t f = first[e];
+        if (f == EP_NONE) continue;
+        const uint8_t *r = V.rec(e);
+        if (pc == FP_ALONE) errprof::count_record(r, P, ref, S, f, sub, 16u, add);
+        else errprof::paired_walk(r, V.rec(pc & ~FP_IS_B), (pc & FP_IS_B) != 0, P, ref, S, f, sub, 16u, add, add2, shared, differ);
+    }
+    if (!DIRECT) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < 2 * EP_PLANE; i += EP_THREADS) {
+            const uint32_t v = s_tab[i];
+            if (v) {
+                const uint32_t t = i >= EP_PLANE ? 1u : 0u, ii = i - t * EP_PLANE, prow = ii / EP_CLS, cls = ii - prow * EP_CLS, seg = prow / EP_CYC, c0 = prow - seg * EP_CYC;
+                atomicAdd((t ? ovl : counts) + (seg * EP_MAX_CYCLE + c0) * EP_ROW + cls, (unsigned long long)v);
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { shared += __shfl_xor(shared, d); differ += __shfl_xor(differ, d); }
+    if (lane_id() == 0) {
+        if (shared) atomicAdd(fm + FM_SHARED, (unsigned long long)shared);
+        if (differ) atomicAdd(fm + FM_DIFFER, (unsigned long long)differ);
+    }
+}
+
+}  // namespace
+
+struct gce_fragerr : ReduceSession {
+    errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
+    DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
+    DevBuf counts;                                                                    // two blocks of EP_COUNTERS 64-bit totals: the primary table, the overlap table
+    MateJoin J; int cb_rc = GCE_OK;
+    std::string needs() const override {
+        return "gce_bam_error_profile_fragments needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 1152 KiB of counters, a join table (" + std::to_string(J.table_bytes()) +
+               " bytes) and an arena (" + std::to_string(J.arena_bytes()) + " bytes)";
+    }
+    calmd::Ref ref() const { return calmd::Ref{blob.as<uint8_t>(), tab.as<int64_t>(), P.n_ref}; }
+    int process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, bool final);
+};
+
+// One join (MateJoin::run) with k_fragerr_count between join and carry.  end: the bytes of the window
+int gce_fragerr::process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, bool final) {
+    const bool wide = ((end + J.arena[J.cur].cap) >> 32) != 0;                        // (the no-wrap argument of the planes does not hold)
+    return J.run(this, "gce_bam_error_profile_fragments", FragerrRead{P}, u, off, n_rec, final, [&](const FragView &V, uint64_t N, const uint32_t *first, const uint32_t *partner, unsigned long long *m) {
+        const unsigned nb = (unsigned)std::min<uint64_t>((N + EP_STEP_RECS - 1) / EP_STEP_RECS, EP_GRID);
+        unsigned long long *c = counts.as<unsigned long long>();
+        if (direct || wide) hipLaunchKernelGGL(k_fragerr_count<true>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
+        else hipLaunchKernelGGL(k_fragerr_count<false>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
+        return true;
+    });
+}
+
+extern "C" {
+
+int gce_fragerr_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_fragerr **out) {
+    if (out) *out = nullptr;
+    if (options & ~(uint32_t)(GCE_FRAGERR_DIRECT | GCE_FRAGERR_WEAK_HASH)) return GCE_ERR_INVALID;
+    const int rc = rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options & (uint32_t)GCE_FRAGERR_DIRECT, (uint32_t)GCE_FRAGERR_DIRECT, out);
+    if (rc == GCE_OK) (*out)->J.weak = (options & GCE_FRAGERR_WEAK_HASH) != 0;
+    return rc;
+}
+void gce_fragerr_destroy(gce_fragerr *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device); (void)hipStreamSynchronize(p->s);
+    p->J.release();
+    rd_destroy(p, {&p->blob, &p->tab, &p->counts});
+}
+const char *gce_fragerr_error(gce_fragerr *p) { return p ? p->err.c_str() : ""; }
+
+// the reference, once, first of all, as gce_errprof_set_ref takes it
+int gce_fragerr_set_ref(gce_fragerr *p, int32_t n_ref, const char *const *seq, const int64_t *len) { return ep_set_ref(p, n_ref, seq, len); }
+
+// rule B's intervals, once, behind the reference and in front of the first window, as gce_errprof_set_sites takes them.  Both counter blocks
+// and the join's device words are made and zeroed.
+int gce_fragerr_set_sites(gce_fragerr *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end) {
+    int rc = ep_set_sites(p, "gce_fragerr_set_sites", n_intervals, tid, start, end, 2ull * EP_COUNTERS * 8ull);
+    if (rc != GCE_OK) return rc;
+    p->sites_set = false;
+    if ((rc = p->J.init(p)) != GCE_OK) return rc;
+    p->sites_set = true;
+    return GCE_OK;
+}
+
+// the next piece of the file, as gce_errprof_window takes it; *errprof_s: the seconds of the scan, the join and the count, added to.
+// GCE_ERR_INVALID names the lowest malformed record, else the first record that lies in front of its predecessor, counting from 0 over the file.
+int gce_fragerr_window(gce_fragerr *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                       int32_t n_ref, int32_t last, double *errprof_s) {
+    if (!p) return GCE_ERR_INVALID;
+    p->cb_rc = GCE_OK;
+    const int rc = rd_window(p, ErrScan{p->P, p->ref(), p->sites()}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, errprof_s,
+                             [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end) { p->cb_rc = p->process(u, off, n_rec, end, last != 0); return p->cb_rc == GCE_OK; });
+    return rc != GCE_OK ? rc : p->cb_rc;
+}
+
+// after the last window: what is still pending is counted alone; counters[0..9] as gce_errprof_finish gives them, [10] pairs, [11] shared
+// columns, [12] those whose classes differ, [13] ambiguous candidates, [14] records carried across a window boundary; counts_out,
+// overlap_out: room for 3 x 1024 x 24 uint64 each
+int gce_fragerr_finish(gce_fragerr *p, int64_t counters[15], uint64_t *counts_out, uint64_t *overlap_out) {
+    if (!p || !p->sites_set || !counters || !counts_out || !overlap_out) return GCE_ERR_INVALID;
+    (void)hipSetDevice(p->device);
+    hipStream_t s = p->s;
+    int rc = p->process(nullptr, nullptr, 0, 0, true);
+    if (rc != GCE_OK) return rc;
+    unsigned long long h[10], f[FM_WORDS];
+    if ((rc = rd_finish(p, ErrScan::NSKIP, counters, h, 10)) != GCE_OK) return rc;
+    RDCHK(hipMemcpyAsync(f, p->J.fm.p, sizeof f, hipMemcpyDeviceToHost, s));
+    RDCHK(hipMemcpyAsync(counts_out, p->counts.p, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s));
+    RDCHK(hipMemcpyAsync(overlap_out, p->counts.as<uint8_t>() + EP_COUNTERS * 8ull, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s));
+    RDCHK(hipStreamSynchronize(s));
+    counters[10] = (int64_t)f[FM_PAIRS]; counters[11] = (int64_t)f[FM_SHARED]; counters[12] = (int64_t)f[FM_DIFFER]; counters[13] = (int64_t)f[FM_AMBIG]; counters[14] = (int64_t)f[FM_DEFER];
+    RDCHK(hipGetLastError());
+    return GCE_OK;
+}
+
+}  // extern "C"
+#endif  // GCE_FRAGERR_HOST_CHECK

@@ -2,7 +2,9 @@
 //
 // The same sites (rule S), record filters (rule E), walk (rule W) and table (rule O) as gce_pileup.hpp, over the same windowed reduce frame
 // (gce_reduce.hpp), for a coordinate-sorted file (rule P).  What is new is a mate join that survives window boundaries (rule M) and a count
-// kernel that walks two records at once (rule V).  Per window, behind the scan (k_reduce_scan over PileScan):
+// kernel that walks two records at once (rule V).  The join -- k_frag_prep, k_frag_join, k_frag_carry, the arenas and their host half -- is
+// gce_matejoin.hpp's, shared with gce_fragerr.hpp; this file gives it FragpileRead and k_frag_count.  Per window, behind the scan
+// (k_reduce_scan over PileScan):
 //   k_frag_prep    one thread per entry -- the pending records of the arena, then the window's records.  Rule P against the predecessor (for
 //                  the window's first record a device word that holds the previous window's last key), the lowest offender by atomicMin; rule
 //                  M's candidate test; every candidate goes into an open-addressing table (slot = hash & mask, linear probing, atomicCAS on a
@@ -22,66 +24,14 @@
 #pragma once
 #include <cstdint>
 #include "gce_pileup.hpp"
+#include "gce_matejoin.hpp"
 
 namespace fragpile {
 
 #define FP_HD __host__ __device__ inline
 
-typedef uint32_t __attribute__((aligned(1), may_alias)) fp_u32u;
-typedef uint16_t __attribute__((aligned(1), may_alias)) fp_u16u;
-
-// what the join leaves per entry: the partner's entry index (FP_IS_B: this entry is the later of the two in the file), or one of
-#define FP_ALONE 0xFFFFFFFFu          // counted by rule W alone
-#define FP_DEFER 0xFFFFFFFEu          // not counted yet: carried to the next window
-#define FP_SKIP  0xFFFFFFFDu          // touches no site, or is not eligible
-#define FP_IS_B  0x80000000u
-#define FP_Q_CAP 200u
-
 using pileup::Ivl; using pileup::Params; using pileup::Sites; using reduce::seek;
 using pileup::PU_A; using pileup::PU_C; using pileup::PU_G; using pileup::PU_T; using pileup::PU_N; using pileup::PU_DEL; using pileup::PU_INS; using pileup::PU_LOWQ;
-
-FP_HD int32_t rd_i32(const uint8_t *p) { return (int32_t) * (const fp_u32u *)p; }
-
-// rule P's key of a record: placed records by (tid, pos), every record with tid < 0 behind them
-FP_HD uint64_t order_key(int32_t tid, int32_t pos) { return tid < 0 ? ~0ull : ((uint64_t)(uint32_t)tid << 32) | ((uint32_t)pos ^ 0x80000000u); }
-FP_HD uint64_t order_key(const uint8_t *r) { return order_key(rd_i32(r + 4), rd_i32(r + 8)); }
-
-// rule M's candidate test for an eligible record: C as reduce::rule_e left it, first as the scan did
-FP_HD bool candidate(const uint8_t *r, const reduce::Core &C, uint32_t first) {
-    if (first == RD_NONE) return false;
-    const uint32_t fl = C.flag;
-    if (!(fl & 0x1u) || (fl & (0x4u | 0x8u | 0x100u | 0x800u)) || !(((fl >> 6) ^ (fl >> 7)) & 1u)) return false;
-    const int32_t ntid = rd_i32(r + 24), npos = rd_i32(r + 28);
-    if (ntid != C.tid) return false;
-    return !(npos >= C.pos && (int64_t)npos >= (int64_t)C.pos + C.rlen);
-}
-
-// the join's key: a 64-bit hash of (name bytes, refID, min(pos, next_pos), max(pos, next_pos)); weak: its low 4 bits alone
-FP_HD uint64_t key(const uint8_t *r, bool weak) {
-    const uint32_t lq = r[12];
-    const int32_t pos = rd_i32(r + 8), npos = rd_i32(r + 28);
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (uint32_t k = 0; k < lq; k++) h = (h ^ r[36 + k]) * 0x100000001b3ull;
-    const uint32_t w[3] = {(uint32_t)rd_i32(r + 4), (uint32_t)(pos < npos ? pos : npos), (uint32_t)(pos < npos ? npos : pos)};
-    for (int k = 0; k < 3; k++) { h = (h ^ w[k]) * 0x100000001b3ull; h ^= h >> 29; }
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33;
-    return weak ? (h & 15u) : h;
-}
-
-// two candidates of one group: the same l_read_name and name bytes, refID and unordered {pos, next_pos}
-FP_HD bool same_group(const uint8_t *a, const uint8_t *b) {
-    const uint32_t lq = a[12];
-    if (lq != b[12] || rd_i32(a + 4) != rd_i32(b + 4)) return false;
-    const int32_t pa = rd_i32(a + 8), na = rd_i32(a + 28), pb = rd_i32(b + 8), nb = rd_i32(b + 28);
-    if ((pa < na ? pa : na) != (pb < nb ? pb : nb) || (pa < na ? na : pa) != (pb < nb ? nb : pb)) return false;
-    for (uint32_t k = 0; k < lq; k++) if (a[36 + k] != b[36 + k]) return false;
-    return true;
-}
-// ... that are a pair: one first, one last, each where the other says its mate is
-FP_HD bool is_pair(const uint8_t *a, const uint8_t *b) {
-    const uint32_t fa = *(const fp_u16u *)(a + 18), fb = *(const fp_u16u *)(b + 18);
-    return ((fa ^ fb) & 0x40u) && rd_i32(a + 28) == rd_i32(b + 8) && rd_i32(b + 28) == rd_i32(a + 8);
-}
 
 // Rule V's lookup: the raw class (A C G T N, DEL for a D column) and the quality (0 for a D column or a record without qualities) of eligible
 // record r at reference column x; false: no M / = / X / D op of it covers x
@@ -174,83 +124,14 @@ namespace {
 #define FP_TILE PU_TILE
 static_assert(FP_TILE * 64u + 64u <= PU_LDS_PER_CU / PU_BLOCKS_PER_CU, "k_frag_count's tile must leave the CU its 8 blocks of 4 waves");
 
-// the pass's device words
-enum { FM_BAD = 0, FM_NCARRY, FM_CBYTES, FM_BUMP, FM_PAIRS, FM_SHARED, FM_DIFFER, FM_AMBIG, FM_DEFER, FM_KEY0, FM_KEY1, FM_WORDS = 12 };
-// a slot of the arena: the file-wide record index (8 bytes), the scan's first interval (4), the slot's bytes (4), the record, padded to 8
-#define FP_AHDR 16u
-#define FP_EMPTY 0xFFFFFFFFu
-#define FP_BUMP_SHIFT 40
-
-// the entries of a window's join: [0, n_pend) the pending records of the arena, [n_pend, n) the window's records
-struct FragView {
-    const uint8_t *u; const uint64_t *off; const uint8_t *arena; const uint64_t *aoff; uint64_t n_pend, n, gbase;
-    __device__ const uint8_t *rec(uint64_t e) const { return e < n_pend ? arena + aoff[e] + FP_AHDR : u + off[e - n_pend]; }
-    __device__ uint64_t gidx(uint64_t e) const { return e < n_pend ? *(const uint64_t *)(arena + aoff[e]) : gbase + (e - n_pend); }
+// what k_reduce_scan over PileScan left in meta: the first interval, or PU_NONE for a record that is skipped or touches none
+struct FragpileRead {
+    pileup::Params P;
+    __device__ bool operator()(const uint8_t *r, uint32_t m, uint32_t &first, reduce::Core &C) const {
+        first = m;
+        return m != RD_NONE && reduce::rule_e(r, 4ull + rb32(r), P.n_ref, P.min_mapq, P.exclude, C) == reduce::ELIGIBLE;
+    }
 };
-__device__ __forceinline__ uint32_t fp_slot_bytes(const uint8_t *r) { return (FP_AHDR + 4u + rb32(r) + 7u) & ~7u; }
-
-__global__ __launch_bounds__(256) void k_frag_prep(FragView V, pileup::Params P, const uint32_t *meta, uint32_t par, uint32_t weak, uint64_t *hkey, uint32_t *first, uint32_t *partner,
-                                                   uint32_t *table, uint32_t mask, unsigned long long *fm) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= V.n) return;
-    const uint8_t *r = V.rec(e);
-    uint32_t f; bool cand;
-    if (e < V.n_pend) { f = *(const uint32_t *)(V.arena + V.aoff[e] + 8); cand = true; }
-    else {
-        const uint64_t i = e - V.n_pend;
-        const uint64_t k = fragpile::order_key(r), prev = i ? fragpile::order_key(V.u + V.off[i - 1]) : (uint64_t)fm[FM_KEY0 + par];
-        if (k < prev) atomicMin(fm + FM_BAD, (unsigned long long)(V.gbase + i));
-        if (e + 1 == V.n) fm[FM_KEY0 + (par ^ 1u)] = k;
-        f = meta[i]; cand = false;
-        if (f != RD_NONE) {
-            reduce::Core C;
-            cand = reduce::rule_e(r, 4ull + rb32(r), P.n_ref, P.min_mapq, P.exclude, C) == reduce::ELIGIBLE && fragpile::candidate(r, C, f);
-        }
-    }
-    first[e] = f;
-    partner[e] = cand ? 0u : f == RD_NONE ? FP_SKIP : FP_ALONE;
-    if (!cand) return;
-    const uint64_t h = fragpile::key(r, weak != 0);
-    hkey[e] = h;
-    for (uint32_t slot = (uint32_t)h & mask;; slot = (slot + 1u) & mask)
-        if (atomicCAS(table + slot, FP_EMPTY, (uint32_t)e) == FP_EMPTY) break;
-}
-
-__global__ __launch_bounds__(256) void k_frag_join(FragView V, const uint64_t *hkey, uint32_t *partner, const uint32_t *table, uint32_t mask, uint32_t par, uint32_t final, unsigned long long *fm) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool cand = e < V.n && partner[e] == 0u;
-    bool pair_b = false, ambig = false, defer = false, fresh = false;
-    uint32_t cbytes = 0;
-    if (cand) {
-        const uint8_t *r = V.rec(e);
-        const uint64_t h = hkey[e];
-        uint32_t cnt = 0, other = 0, res = FP_ALONE;
-        for (uint32_t slot = (uint32_t)h & mask;; slot = (slot + 1u) & mask) {
-            const uint32_t o = table[slot];
-            if (o == FP_EMPTY) break;
-            if (o != (uint32_t)e && hkey[o] == h && fragpile::same_group(r, V.rec(o))) { cnt++; other = o; }
-        }
-        if (cnt >= 2) ambig = true;
-        else if (cnt == 1 && fragpile::is_pair(r, V.rec(other))) {
-            pair_b = V.gidx(e) > V.gidx(other);
-            res = other | (pair_b ? FP_IS_B : 0u);
-        } else {
-            const int32_t pos = fragpile::rd_i32(r + 8), npos = fragpile::rd_i32(r + 28);
-            const bool expired = final || (uint64_t)fm[FM_KEY0 + (par ^ 1u)] > fragpile::order_key(fragpile::rd_i32(r + 4), npos);
-            if (npos >= pos && !expired) { res = FP_DEFER; defer = true; fresh = e >= V.n_pend; cbytes = fp_slot_bytes(r); }
-        }
-        partner[e] = res;
-    }
-    const unsigned long long bp = __ballot(pair_b), ba = __ballot(ambig), bd = __ballot(defer), bf = __ballot(fresh);
-#pragma unroll
-    for (int d = 32; d; d >>= 1) cbytes += __shfl_xor(cbytes, d);
-    if (lane_id() == 0) {
-        if (bp) atomicAdd(fm + FM_PAIRS, (unsigned long long)__popcll(bp));
-        if (ba) atomicAdd(fm + FM_AMBIG, (unsigned long long)__popcll(ba));
-        if (bf) atomicAdd(fm + FM_DEFER, (unsigned long long)__popcll(bf));
-        if (bd) { atomicAdd(fm + FM_NCARRY, (unsigned long long)__popcll(bd)); atomicAdd(fm + FM_CBYTES, (unsigned long long)cbytes); }
-    }
-}
 
 // 16 lanes per entry, 16 entries per block (block b: entries [16 b, 16 b + 16)); n_counts: 16 x the number of sites
 template <bool DIRECT> __global__ __launch_bounds__(256) void k_frag_count(FragView V, pileup::Params P, pileup::Sites S, const uint32_t *first, const uint32_t *partner, uint32_t *counts,
@@ -302,97 +183,28 @@ template <bool DIRECT> __global__ __launch_bounds__(256) void k_frag_count(FragV
     }
 }
 
-// the deferred entries into the other arena: one atomic per record takes its slot number (the high bits) and its bytes (the low 40)
-__global__ __launch_bounds__(256) void k_frag_carry(FragView V, const uint32_t *first, const uint32_t *partner, uint8_t *arena_out, uint64_t *aoff_out, uint64_t n_out, uint64_t bytes_out,
-                                                    unsigned long long *fm) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= V.n || partner[e] != FP_DEFER) return;
-    const uint8_t *r = V.rec(e);
-    const uint32_t sz = fp_slot_bytes(r), body = 4u + rb32(r);
-    const unsigned long long old = atomicAdd(fm + FM_BUMP, (1ull << FP_BUMP_SHIFT) | sz);
-    const uint64_t k = old >> FP_BUMP_SHIFT, o = old & ((1ull << FP_BUMP_SHIFT) - 1);
-    if (k >= n_out || o + sz > bytes_out) return;                                     // (the join counted exactly these: cannot be)
-    aoff_out[k] = o;
-    uint8_t *w = arena_out + o;
-    *(uint64_t *)w = V.gidx(e); *(uint32_t *)(w + 8) = first[e]; *(uint32_t *)(w + 12) = sz;
-    for (uint32_t b = 0; b < body; b++) w[FP_AHDR + b] = r[b];
-}
-
 }  // namespace
 
 struct gce_fragpile : ReduceSession {
-    pileup::Params P{0, 0, 0, 0}; bool direct = false, weak = false;
+    pileup::Params P{0, 0, 0, 0}; bool direct = false;
     DevBuf counts; uint64_t n_sites = 0;                                              // 64 bytes per site
-    DevBuf fm, hkey, first, partner, table;                                           // the device words; 16 bytes per entry; the join's table
-    DevBuf arena[2], aoff[2]; int cur = 0; uint64_t n_pend = 0;                        // the pending records: arena[cur] is joined against, the other is written
-    uint32_t par = 0; int cb_rc = GCE_OK;
+    MateJoin J; int cb_rc = GCE_OK;
     std::string needs() const override {
-        return "gce_bam_pileup_fragments needs 64 bytes per site (" + std::to_string(n_sites) + " sites), a join table (" + std::to_string(hkey.cap + first.cap + partner.cap + table.cap) +
-               " bytes) and an arena (" + std::to_string(arena[0].cap + arena[1].cap + aoff[0].cap + aoff[1].cap) + " bytes)";
-    }
-    int oom_own(const char *what, uint64_t add) {
-        char m[256];
-        snprintf(m, sizeof m, "out of device memory: %s (%lld bytes live, budget %llu, %llu more for %s)", needs().c_str(), __atomic_load_n(&g_dev_live, __ATOMIC_RELAXED),
-                 (unsigned long long)budget, (unsigned long long)add, what);
-        return fail(GCE_ERR_OOM, m);
-    }
-    int grow(DevBuf &b, uint64_t bytes, const char *what) {
-        if (bytes <= b.cap && b.p) return GCE_OK;
-        const uint64_t add = DevBuf::padded(bytes);
-        if (!room(add > b.cap ? add - b.cap : 0)) return oom_own(what, add);
-        const hipError_t e = b.ensure(bytes);
-        if (e == hipErrorOutOfMemory) return oom_own(what, add);
-        return e == hipSuccess ? GCE_OK : fail(GCE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        return "gce_bam_pileup_fragments needs 64 bytes per site (" + std::to_string(n_sites) + " sites), a join table (" + std::to_string(J.table_bytes()) + " bytes) and an arena (" +
+               std::to_string(J.arena_bytes()) + " bytes)";
     }
     int process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, bool final);
 };
 
-// One join: the pending records and the window's n_rec records (none: the flush behind the last window).  final: nothing more can come.
+// One join (MateJoin::run) with k_frag_count between join and carry
 int gce_fragpile::process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, bool final) {
-    gce_fragpile *p = this;
-    const uint64_t N = n_pend + n_rec;
-    if (!N) return GCE_OK;
-    if (N >= 0x7FFFFFF0ull) return fail(GCE_ERR_INVALID, "2^31 records or more in one window");
-    uint64_t cap = 16; while (cap < 2 * N) cap <<= 1;
-    int rc;
-    if ((rc = grow(hkey, N * 8, "the join table")) != GCE_OK || (rc = grow(first, N * 4, "the join table")) != GCE_OK || (rc = grow(partner, N * 4, "the join table")) != GCE_OK ||
-        (rc = grow(table, cap * 4, "the join table")) != GCE_OK) return rc;
-    unsigned long long *m = fm.as<unsigned long long>();
-    RDCHK(hipMemsetAsync(table.p, 0xFF, cap * 4, s));
-    RDCHK(hipMemsetAsync(m + FM_NCARRY, 0, 3 * 8, s));
-    const FragView V{u, off, arena[cur].as<uint8_t>(), aoff[cur].as<uint64_t>(), n_pend, N, n};
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(k_frag_prep, dim3(nb), dim3(256), 0, s, V, P, (const uint32_t *)meta.p, par, weak ? 1u : 0u, hkey.as<uint64_t>(), first.as<uint32_t>(), partner.as<uint32_t>(),
-                       table.as<uint32_t>(), (uint32_t)(cap - 1), m);
-    RDCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_frag_join, dim3(nb), dim3(256), 0, s, V, (const uint64_t *)hkey.p, partner.as<uint32_t>(), (const uint32_t *)table.p, (uint32_t)(cap - 1), par, final ? 1u : 0u, m);
-    RDCHK(hipGetLastError());
-    unsigned long long h[3] = {~0ull, 0, 0};
-    RDCHK(hipMemcpyAsync(h, m, sizeof h, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s)); RDCHK(hipGetLastError());
-    if (h[FM_BAD] != ~0ull) {
-        char msg[200]; snprintf(msg, sizeof msg, "BAM record %llu (counting from 0) lies in front of its predecessor: gce_bam_pileup_fragments needs a coordinate-sorted file", h[FM_BAD]);
-        return fail(GCE_ERR_INVALID, msg);
-    }
-    const uint64_t n_carry = h[FM_NCARRY], cbytes = h[FM_CBYTES];
-    if (n_carry) {
-        if (cbytes >> FP_BUMP_SHIFT) return fail(GCE_ERR_INVALID, "2^40 bytes of deferred records or more");
-        if ((rc = grow(arena[cur ^ 1], cbytes, "the arena")) != GCE_OK || (rc = grow(aoff[cur ^ 1], n_carry * 8, "the arena")) != GCE_OK) return rc;
-    }
-    if (n_sites) {
+    return J.run(this, "gce_bam_pileup_fragments", FragpileRead{P}, u, off, n_rec, final, [&](const FragView &V, uint64_t N, const uint32_t *first, const uint32_t *partner, unsigned long long *m) {
+        if (!n_sites) return false;
         const unsigned cb = (unsigned)((N + 15) / 16);
-        if (direct) hipLaunchKernelGGL(k_frag_count<true>, dim3(cb), dim3(256), 0, s, V, P, sites(), (const uint32_t *)first.p, (const uint32_t *)partner.p, counts.as<uint32_t>(), n_sites * 16, m);
-        else hipLaunchKernelGGL(k_frag_count<false>, dim3(cb), dim3(256), 0, s, V, P, sites(), (const uint32_t *)first.p, (const uint32_t *)partner.p, counts.as<uint32_t>(), n_sites * 16, m);
-        RDCHK(hipGetLastError());
-    }
-    if (n_carry) {
-        hipLaunchKernelGGL(k_frag_carry, dim3(nb), dim3(256), 0, s, V, (const uint32_t *)first.p, (const uint32_t *)partner.p, arena[cur ^ 1].as<uint8_t>(), aoff[cur ^ 1].as<uint64_t>(), n_carry,
-                           cbytes, m);
-        RDCHK(hipGetLastError());
-    }
-    RDCHK(hipStreamSynchronize(s)); RDCHK(hipGetLastError());
-    cur ^= 1; n_pend = n_carry;
-    if (n_rec) par ^= 1u;
-    return GCE_OK;
+        if (direct) hipLaunchKernelGGL(k_frag_count<true>, dim3(cb), dim3(256), 0, s, V, P, sites(), first, partner, counts.as<uint32_t>(), n_sites * 16, m);
+        else hipLaunchKernelGGL(k_frag_count<false>, dim3(cb), dim3(256), 0, s, V, P, sites(), first, partner, counts.as<uint32_t>(), n_sites * 16, m);
+        return true;
+    });
 }
 
 extern "C" {
@@ -401,11 +213,14 @@ int gce_fragpile_create(int32_t device, size_t device_budget_bytes, int32_t min_
     if (out) *out = nullptr;
     if (options & ~(uint32_t)(GCE_FRAGPILE_DIRECT | GCE_FRAGPILE_WEAK_HASH)) return GCE_ERR_INVALID;
     const int rc = rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options & (uint32_t)GCE_FRAGPILE_DIRECT, (uint32_t)GCE_FRAGPILE_DIRECT, out);
-    if (rc == GCE_OK) (*out)->weak = (options & GCE_FRAGPILE_WEAK_HASH) != 0;
+    if (rc == GCE_OK) (*out)->J.weak = (options & GCE_FRAGPILE_WEAK_HASH) != 0;
     return rc;
 }
 void gce_fragpile_destroy(gce_fragpile *p) {
-    if (p) rd_destroy(p, {&p->counts, &p->fm, &p->hkey, &p->first, &p->partner, &p->table, &p->arena[0], &p->arena[1], &p->aoff[0], &p->aoff[1]});
+    if (!p) return;
+    (void)hipSetDevice(p->device); (void)hipStreamSynchronize(p->s);
+    p->J.release();
+    rd_destroy(p, {&p->counts});
 }
 const char *gce_fragpile_error(gce_fragpile *p) { return p ? p->err.c_str() : ""; }
 
@@ -421,9 +236,7 @@ int gce_fragpile_set_sites(gce_fragpile *p, int32_t n_ref, int64_t n_intervals, 
     p->n_sites = t.sites; p->P.n_ref = n_ref;
     if ((rc = rd_set_sites(p, t, p->counts, t.sites * 64 + 64, 9)) != GCE_OK) return rc;
     p->sites_set = false;
-    if ((rc = p->grow(p->fm, FM_WORDS * 8, "the pass's device words")) != GCE_OK) return rc;
-    const unsigned long long init[FM_WORDS] = {~0ull};
-    RDCHK(hipMemcpyAsync(p->fm.p, init, sizeof init, hipMemcpyHostToDevice, p->s)); RDCHK(hipStreamSynchronize(p->s));
+    if ((rc = p->J.init(p)) != GCE_OK) return rc;
     p->sites_set = true;
     return GCE_OK;
 }
@@ -450,7 +263,7 @@ int gce_fragpile_finish(gce_fragpile *p, int64_t counters[13], uint32_t *counts_
     unsigned long long h[9], f[FM_WORDS];
     if ((rc = rd_finish(p, PileScan::NSKIP, counters, h, 9)) != GCE_OK) return rc;
     if (h[8] >> 32) return p->fail(GCE_ERR_INVALID, "the eligible records hold 2^32 CIGAR operations or more: the 32-bit counters cannot be shown to hold");
-    RDCHK(hipMemcpyAsync(f, p->fm.p, sizeof f, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
+    RDCHK(hipMemcpyAsync(f, p->J.fm.p, sizeof f, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
     counters[8] = (int64_t)f[FM_PAIRS]; counters[9] = (int64_t)f[FM_SHARED]; counters[10] = (int64_t)f[FM_DIFFER]; counters[11] = (int64_t)f[FM_AMBIG]; counters[12] = (int64_t)f[FM_DEFER];
     if (counts_out && p->n_sites) { RDCHK(hipMemcpyAsync(counts_out, p->counts.p, p->n_sites * 64, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s)); }
     RDCHK(hipGetLastError());

@@ -832,6 +832,47 @@ int gce_bam_error_profile(const char *bam_path, const char *fasta_path, const ch
                           int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
                           uint64_t window_bytes, size_t device_budget_bytes, gce_errprof_run *out, char err[256]);
 void gce_errprof_free(gce_errprof_run *out);
+/* gce_bam_error_profile's table with every fragment counted once where its mates overlap, and a second table of what the two mates say of
+ * each other there, on ONE device (addition under ABI v3; gencore_amd/csrc/gce_fragerr.hpp).
+ * Replaces: nothing in the reference's source -- it stands in for the `fgbio ErrorRateByReadPosition` / Picard artifact metrics that
+ * gce_bam_error_profile stands in for, which count overlapping mates twice and cannot tell a sequencing error from an older one without a
+ * variant mask.  The arguments, eligible records, segment, cycle, classes, BED and primary table are gce_bam_error_profile's; a record
+ * without a partner is counted exactly as gce_bam_error_profile counts it.  Rule P (the file is coordinate-sorted;
+ * "BAM record N (counting from 0) lies in front of its predecessor: ...") and Rule M (candidates, pairs, n_ambiguous, waiting across
+ * windows, n_deferred) are gce_bam_pileup_fragments', with
+ * "can touch a site" read as: every eligible record without a BED, with one a record whose reference span touches a region.  Rule V': for a
+ * pair (a, the earlier in the file), a shared column (n_shared_columns) is a reference position that an M / = / X op of both mates covers
+ * and, with a BED, lies in its regions; a D or N of either mate there: not shared.  Each mate has a base class over A C G T N and a quality
+ * (its QUAL byte; 0 without qualities).  In counts: same class, a is counted at its own segment and cycle with quality min(qa + qb, 200)
+ * for the LOWQ test, b adds nothing; different classes (n_disagree_columns), the winner is a when qa >= qb, else b, counted with quality
+ * (4 q) / 5, the loser adds nothing; the winner's class is then LOWQ (when it has qualities), REF_OTHER, READ_N or 4 r + b as in
+ * gce_bam_error_profile.  Insertions and deletions of both mates and all other columns are counted as gce_bam_error_profile counts them.
+ * Rule X: overlap[(segment * 1024 + cycle - 1) * 24 + class], where BOTH mates add one at every shared column, each at its own segment and
+ * cycle, the first class that applies (m this mate, o the other, r the reference base): 20 OVL_LOWQ when a mate with qualities has a raw
+ * quality < min_baseq; 19 OVL_UNUSABLE when either base is N or r is REF_OTHER; 16 OVL_AGREE_REF when bm == bo == r; 17 OVL_AGREE_ALT when
+ * bm == bo != r (older than the sequencer, or a variant); bm != bo: 4 r + bm when bo == r (m's sequencing error) or bm == r (the diagonal: m
+ * read it right, o did not), both complemented on m's reverse strand; 18 OVL_DIFF_OTHER when neither is r; 21..23 zero.  The sum of overlap
+ * is 2 n_shared_columns.  tsv_path as gce_bam_error_profile's; overlap_tsv_path (NULL: no file): a header line that begins with `#`, then
+ * per segment one line per cycle up to the last with a counter: segment, cycle, shared (classes 0..18), errors (the off-diagonal ones), the
+ * sixteen A>A .. T>T, AGREE_REF AGREE_ALT DIFF_OTHER UNUSABLE LOWQ; each written to a temporary name and renamed.  The result does not
+ * depend on window_bytes (n_deferred alone does).  options: GCE_FRAGERR_DIRECT as GCE_ERRPROF_DIRECT; GCE_FRAGERR_WEAK_HASH as
+ * GCE_FRAGPILE_WEAK_HASH.  Device memory: gce_bam_error_profile's with 1152 KiB of counters, 16 bytes per window record, a join table of 4
+ * bytes per slot and two arenas of deferred records, within device_budget_bytes, else GCE_ERR_OOM with that footprint.  The refusals are
+ * gce_bam_error_profile's, and rule P's.  No BAQ, no split by read group.  counts and overlap (3 x 1024 x 24 each) are malloc'ed:
+ * gce_fragerr_free. */
+#define GCE_FRAGERR_DIRECT 1u
+#define GCE_FRAGERR_WEAK_HASH 2u
+typedef struct gce_fragerr_run {
+    int64_t n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar, n_no_ref, n_too_long;   /* n_eligible + the eight skips = n_records */
+    int64_t n_bases, n_mismatches, n_intervals /* -1: no BED */, peak_device_bytes;
+    double  read_s, inflate_index_s, errprof_s, write_s, total_s;   /* errprof_s: the scan, the join, k_fragerr_count and the carry; write_s: the tables */
+    int64_t n_pairs, n_shared_columns, n_disagree_columns, n_ambiguous, n_deferred;   /* n_deferred alone depends on window_bytes */
+    uint64_t *counts, *overlap;     /* [3 segments][1024 cycles][24 classes] each */
+} gce_fragerr_run;
+int gce_bam_error_profile_fragments(const char *bam_path, const char *fasta_path, const char *bed_path /* NULL: no BED */, const char *tsv_path /* NULL: no file */,
+                                    const char *overlap_tsv_path /* NULL: no file */, int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags,
+                                    uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_fragerr_run *out, char err[256]);
+void gce_fragerr_free(gce_fragerr_run *out);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

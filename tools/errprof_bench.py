@@ -8,7 +8,13 @@ rounds, reported as medians with all values.  The question is which variant has 
 clocks around work that ends in a device synchronise): the planes stay the default only if their median beats direct's by more than the
 spread of the values.  gce_bam_index's gpu_s (inflate, record index and the index's kernels) stands beside errprof_s + inflate_index_s so
 that the cost of the count kernels above read, inflate and index is visible.  One rocprofv3 --kernel-trace --stats run per variant, each in a
-process of its own, gives the kernel times.  There is no pass mark."""
+process of its own, gives the kernel times.  There is no pass mark.
+    python tools/errprof_bench.py --fragments [--parent_lib PATH] [--out profiles/errprof_fragments.json]
+runs gce_bam_error_profile_fragments (frag_planes, frag_direct) beside gce_bam_error_profile (planes, direct) on the same file,
+without a BED, in the same interleaved way.  With --parent_lib, the library built from the parent commit (loaded through GCE_LIB) runs in the
+same rounds: its gce_bam_error_profile (parent_planes) is the comparison partner, and its gce_bam_pileup_fragments (parent_pileup_fragments)
+stands beside this tree's (pileup_fragments), whose join moved into gce_matejoin.hpp: pileup_s is unchanged when the two medians differ by
+less than the spread of the values."""
 import argparse
 import csv
 import glob
@@ -23,6 +29,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 MODES = ("planes", "direct", "planes_bed", "direct_bed", "index")
+FRAG_MODES = ("planes", "frag_planes", "direct", "frag_direct")
+PARENT_MODES = ("parent_planes", "pileup_fragments", "parent_pileup_fragments")
 
 
 def child(args):
@@ -37,9 +45,17 @@ def child(args):
     if args.mode == "index":
         d = bamio.index_bam(src, os.path.join(args.child, "in.bam.bai"), threads=args.threads)
         d = {k: v for k, v in (d if isinstance(d, dict) else vars(d)).items() if isinstance(v, (int, float))}
+    elif args.mode.endswith("pileup_fragments"):
+        r = bamio.pileup_fragments_bam(src, bed, threads=args.threads)
+        d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())))
+    elif args.mode.startswith("frag_"):
+        r = bamio.error_profile_fragments_bam(src, fa, tsv=os.path.join(args.child, "%s.tsv" % args.mode), overlap_tsv=os.path.join(args.child, "%s.overlap.tsv" % args.mode),
+                                              threads=args.threads, direct=args.mode.endswith("direct"))
+        d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())), overlap_sum=int(r.overlap.sum()),
+                 overlap_crc=int(zlib.crc32(r.overlap.tobytes())))
     else:
         r = bamio.error_profile_bam(src, fa, bed=bed if args.mode.endswith("_bed") else None, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads,
-                                    direct=args.mode.startswith("direct"))
+                                    direct="direct" in args.mode)
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())))
     print(json.dumps(dict(d, wall_s=time.perf_counter() - t0)), flush=True)
 
@@ -78,9 +94,10 @@ def child_make(args):
 
 
 def run_child(args, tmp, mode, prefix=(), limit=None):
-    limit = limit or (args.direct_limit if mode.startswith("direct") else args.limit)
+    limit = limit or (args.direct_limit if "direct" in mode else args.limit)
+    env = dict(os.environ, GCE_LIB=os.path.abspath(args.parent_lib)) if mode.startswith("parent_") else None
     p = subprocess.run(["timeout", "-k", "10", str(limit)] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--mode", mode, "--threads", str(args.threads),
-                                                                           "--workload", args.workload, "--pairs", str(args.pairs)], stdout=subprocess.PIPE, universal_newlines=True)
+                                                                           "--workload", args.workload, "--pairs", str(args.pairs)], stdout=subprocess.PIPE, universal_newlines=True, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:
         raise SystemExit("errprof_bench: a child run (%s) failed (exit %d, limit %d s)" % (mode, p.returncode, limit))
@@ -93,7 +110,7 @@ def kernel_times(args, tmp, mode):
     kern = {}
     for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"k_err_\w+|k_reduce_scan", r["Name"])   # (the CSV holds the demangled name)
+            m = re.search(r"k_err_\w+|k_fragerr_\w+|k_frag_\w+|k_reduce_scan", r["Name"])   # (the CSV holds the demangled name)
             if m:
                 k = kern.setdefault(m.group(0), dict(calls=0, seconds=0.0))
                 k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9
@@ -113,10 +130,14 @@ def main():
     ap.add_argument("--limit", type=int, default=300)
     ap.add_argument("--direct_limit", type=int, default=900)
     ap.add_argument("--child", default=None)
-    ap.add_argument("--mode", default="planes", choices=("make",) + MODES)
+    ap.add_argument("--mode", default="planes", choices=("make",) + MODES + FRAG_MODES[1::2] + PARENT_MODES)
+    ap.add_argument("--fragments", action="store_true", help="gce_bam_error_profile_fragments beside gce_bam_error_profile; writes profiles/errprof_fragments.json")
+    ap.add_argument("--parent_lib", default=None, help="with --fragments: the parent commit's libgencore_amd.so, run in the same rounds through GCE_LIB")
     args = ap.parse_args()
     if args.child is not None:
         return child_make(args) if args.mode == "make" else child(args)
+    if args.fragments:
+        return main_fragments(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "errprof.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_errprof_")
     made = run_child(args, tmp, "make", limit=900)
@@ -155,6 +176,53 @@ def main():
         v["gpu_s_beside_index"] = dict(errprof_s=v["stages"]["errprof_s"], inflate_index_s=v["stages"]["inflate_index_s"], index_gpu_s=res["index"]["stages"]["gpu_s"])
     for m in ("planes", "direct"):
         res["variants"][m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+def main_fragments(args):
+    args.out = args.out or os.path.join(ROOT, "profiles", "errprof_fragments.json")
+    tmp = args.dir or tempfile.mkdtemp(prefix="gce_fragerr_")
+    made = run_child(args, tmp, "make", limit=900)
+    modes = FRAG_MODES + (PARENT_MODES if args.parent_lib else ())
+    per = {m: [] for m in modes}
+    for rep in range(args.reps + 1):                               # interleaved; the first round is the warm-up
+        for m in modes:
+            r = run_child(args, tmp, m)
+            if rep:
+                per[m].append(r)
+        print("errprof_bench: round %d done" % rep, flush=True)
+    med = lambda rs, k: sorted(r[k] for r in rs)[len(rs) // 2]
+    spread = lambda rs, k: max(r[k] for r in rs) - min(r[k] for r in rs)
+    res = dict(workload=args.workload, pairs=int(args.pairs), reps=args.reps, **made, input_bytes=os.path.getsize(os.path.join(tmp, "in.bam")),
+               clocks="the library's stage times: host clocks around work that ends in a device synchronise",
+               what="gce_bam_error_profile_fragments (frag_*) beside gce_bam_error_profile on the same file, without a BED, interleaved; no pass mark", variants={})
+    for m in modes:
+        rs = per[m]
+        key = "pileup_s" if m.endswith("pileup_fragments") else "errprof_s"
+        res["variants"][m] = dict(stages={k: round(med(rs, k), 5) for k in ("read_s", "inflate_index_s", key, "write_s", "total_s", "wall_s")},
+                                  **{key + "_all": [round(r[key], 5) for r in rs]}, total_s_all=[round(r["total_s"], 4) for r in rs], peak_device_bytes=int(rs[0]["peak_device_bytes"]),
+                                  share_of_total=round(med(rs, key) / med(rs, "total_s"), 4), counters={c: int(rs[0][c]) for c in rs[0] if c.startswith("n_")},
+                                  sums={c: rs[0][c] for c in ("counts_sum", "counts_crc", "overlap_sum", "overlap_crc") if c in rs[0]})
+    v = res["variants"]
+    same = lambda a, b: v[a]["sums"] == v[b]["sums"] and {k: c for k, c in v[a]["counters"].items() if k != "n_deferred"} == {k: c for k, c in v[b]["counters"].items() if k != "n_deferred"}
+    res["counters_identical"] = dict(error_profile=same("planes", "direct"), fragments=same("frag_planes", "frag_direct"),
+                                     overlap_sum_is_twice_shared=v["frag_planes"]["sums"]["overlap_sum"] == 2 * v["frag_planes"]["counters"]["n_shared_columns"])
+    e = lambda m: v[m]["stages"]["errprof_s"]
+    res["errprof_s_ratio"] = dict(frag_planes_over_planes=round(e("frag_planes") / e("planes"), 3), frag_direct_over_direct=round(e("frag_direct") / e("direct"), 3),
+                                  frag_planes_over_frag_direct=round(e("frag_planes") / e("frag_direct"), 3))
+    if args.parent_lib:
+        res["errprof_s_ratio"]["frag_planes_over_parent_planes"] = round(e("frag_planes") / e("parent_planes"), 3)
+        a, b = v["pileup_fragments"], v["parent_pileup_fragments"]
+        gap = a["stages"]["pileup_s"] - b["stages"]["pileup_s"]
+        noise = max(spread(per["pileup_fragments"], "pileup_s"), spread(per["parent_pileup_fragments"], "pileup_s"))
+        res["pileup_fragments_after_the_move"] = dict(rule="pileup_s is unchanged when the medians differ by less than the spread of the values", this_minus_parent_s=round(gap, 5),
+                                                      spread_s=round(noise, 5), unchanged=abs(gap) <= noise, counters_identical=same("pileup_fragments", "parent_pileup_fragments"))
+    for m in FRAG_MODES:
+        v[m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

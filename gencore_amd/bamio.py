@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp and bamio_fragerr.hpp (the last four over bamio_reduce.hpp):
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp and bamio_fragerr.hpp (the last four over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -338,11 +338,14 @@ class ErrorProfileRun:
     24 classes], uint64: classes 0..15 are 4 r + b over A C G T in sequencing orientation, then READ_N REF_OTHER LOWQ INS DEL and three zeros)."""
     CLASSES = tuple("%s>%s" % (r, b) for r in "ACGT" for b in "ACGT") + ("READ_N", "REF_OTHER", "LOWQ", "INS", "DEL")
 
-    def __init__(self, r):
+    def __init__(self, r, mask=None):
         from .capi import GCE_ERRPROF_CLASSES, GCE_ERRPROF_MAX_CYCLE
         for n, t in type(r)._fields_:
             if n not in ("counts", "overlap"):
                 setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+        if mask is not None:                                                 # gce_mask_run's fields; n_records and n_intervals are the BAM's and the BED's: the mask's are n_mask_*
+            for n, t in type(mask)._fields_:
+                setattr(self, {"n_intervals": "n_mask_intervals", "n_records": "n_mask_records"}.get(n, n), (float if t is C.c_double else int)(getattr(mask, n)))
         table = lambda p: np.ctypeslib.as_array(p, (3 * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES,)).copy().reshape(3, GCE_ERRPROF_MAX_CYCLE, GCE_ERRPROF_CLASSES)
         self.counts = table(r.counts)
         if hasattr(r, "overlap"):
@@ -376,6 +379,28 @@ def error_profile_bam(path, fasta, bed=None, tsv=None, device=0, threads=0, min_
         lib.gce_errprof_free(C.byref(r))
 
 
+def error_profile_masked_bam(path, fasta, mask, bed=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_error_profile_masked: error_profile_bam with the known variant sites of `mask` (a .vcf, .vcf.gz or .bed, read as load_mask reads
+    it) taken out of every class: an event whose anchor -- a column's own position, the position in front of an inserted base, a deletion's
+    first position -- is masked goes to class 21, MASKED, at its segment and cycle, and the table gets a trailing MASKED column.  n_bases and
+    n_mismatches are then the sequencer's and the polymerase's, not the sample's genotype.  Returns an ErrorProfileRun with error_profile_bam's
+    fields plus gce_mask_run's: n_lines, n_mask_records, n_unknown_contig, n_no_alt, n_mask_intervals, n_masked_bases, n_masked_events, load_s and
+    fill_s."""
+    from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun, GceMaskRun
+    lib = capi.load_library()
+    r, m = GceErrprofRun(), GceMaskRun()
+    err = (C.c_char * 256)()
+    enc = lambda x: None if x is None else str(x).encode()
+    rc = lib.gce_bam_error_profile_masked(str(path).encode(), str(fasta).encode(), enc(bed), enc(mask), enc(tsv), int(device), int(threads), int(min_mapq), int(min_baseq),
+                                          int(exclude_flags), GCE_ERRPROF_DIRECT if direct else 0, int(window_bytes), int(device_budget_bytes), C.byref(r), C.byref(m), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return ErrorProfileRun(r, m)
+    finally:
+        lib.gce_errprof_free(C.byref(r))
+
+
 OVERLAP_CLASSES = ErrorProfileRun.CLASSES[:16] + ("AGREE_REF", "AGREE_ALT", "DIFF_OTHER", "UNUSABLE", "LOWQ")
 
 
@@ -405,6 +430,51 @@ def error_profile_fragments_bam(path, fasta, bed=None, tsv=None, overlap_tsv=Non
         return ErrorProfileRun(r)
     finally:
         lib.gce_fragerr_free(C.byref(r))
+
+
+def error_profile_fragments_masked_bam(path, fasta, mask, bed=None, tsv=None, overlap_tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False,
+                                       weak_hash=False, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_error_profile_fragments_masked: error_profile_fragments_bam under error_profile_masked_bam's mask.  At a shared masked column the
+    one mate that is counted adds MASKED to counts and both add class 21, OVL_MASKED, to overlap; overlap.sum() is still twice
+    n_shared_columns.  Both tables get the trailing MASKED column.  Returns error_profile_fragments_bam's ErrorProfileRun with
+    error_profile_masked_bam's mask fields."""
+    from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun, GceMaskRun
+    lib = capi.load_library()
+    r, m = GceFragerrRun(), GceMaskRun()
+    err = (C.c_char * 256)()
+    enc = lambda x: None if x is None else str(x).encode()
+    rc = lib.gce_bam_error_profile_fragments_masked(str(path).encode(), str(fasta).encode(), enc(bed), enc(mask), enc(tsv), enc(overlap_tsv), int(device), int(threads), int(min_mapq),
+                                                    int(min_baseq), int(exclude_flags), (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0),
+                                                    int(window_bytes), int(device_budget_bytes), C.byref(r), C.byref(m), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return ErrorProfileRun(r, m)
+    finally:
+        lib.gce_fragerr_free(C.byref(r))
+
+
+def load_mask(path, names, lens, threads=0):
+    """gce_mask_load: the variant mask `path` (.vcf, .vcf.gz as gzip or BGZF, or .bed) against the contig names, clamped to lens (per contig
+    min(header length, FASTA length); <= 0: no reference bases, its intervals are dropped), sorted and merged.  No device is touched.
+    -> dict(n_lines, n_records, n_unknown_contig, n_no_alt, n_intervals, n_masked_bases, intervals=[(tid, start, end)]); raises GceError with
+    `variant mask line N: ...` for a malformed line."""
+    from .capi import GceMask
+    lib = capi.load_library()
+    m = GceMask()
+    err = (C.c_char * 256)()
+    n = len(names)
+    cn = (C.c_char_p * max(n, 1))(*[x.encode() if isinstance(x, str) else x for x in names])
+    cl = (C.c_int64 * max(n, 1))(*[int(x) for x in lens])
+    rc = lib.gce_mask_load(str(path).encode(), n, cn, cl, int(threads), C.byref(m), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        d = {k: int(getattr(m, k)) for k, _ in GceMask._fields_[:6]}
+        d["intervals"] = [(int(m.tid[k]), int(m.start[k]), int(m.end[k])) for k in range(d["n_intervals"])]
+        return d
+    finally:
+        lib.gce_mask_free(C.byref(m))
 
 
 def sort_sam(sam, out, device=0, threads=0, level=-2, window_bytes=0, device_budget_bytes=0):

@@ -107,7 +107,8 @@ EXPORTED_SYMBOLS = [
     "gce_report_json", "gce_report_summary", "gce_bam_read_header", "gce_bam_header_free", "gce_run_bam_passes", "gce_device_bytes", "gce_bam_index", "gce_bam_sort", "gce_bam_sort_passes", "gce_sam_parse", "gce_sam_sort",
     "gce_sam_format", "gce_raw_format_output", "gce_raw_read_text_async", "gce_get_sam_format_counters",
     "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free", "gce_bam_pileup_fragments", "gce_fragpile_free",
-    "gce_bam_error_profile", "gce_errprof_free", "gce_bam_error_profile_fragments", "gce_fragerr_free"]
+    "gce_bam_error_profile", "gce_errprof_free", "gce_bam_error_profile_fragments", "gce_fragerr_free",
+    "gce_mask_load", "gce_mask_free", "gce_bam_error_profile_masked", "gce_bam_error_profile_fragments_masked"]
 
 GCE_PILEUP_DIRECT = 1
 GCE_FRAGPILE_DIRECT = 1
@@ -204,6 +205,18 @@ class GceFragerrRun(C.Structure):
     """gce_fragerr_run (gce_bam_error_profile_fragments): gce_errprof_run's counters and times, rule M's and rule V's counters, the two tables."""
     _fields_ = GceErrprofRun._fields_[:-1] + [("n_pairs", C.c_int64), ("n_shared_columns", C.c_int64), ("n_disagree_columns", C.c_int64), ("n_ambiguous", C.c_int64),
                                               ("n_deferred", C.c_int64), ("counts", C.POINTER(C.c_uint64)), ("overlap", C.POINTER(C.c_uint64))]
+
+
+class GceMask(C.Structure):
+    """gce_mask (gce_mask_load): rule K's counters and the merged intervals."""
+    _fields_ = [("n_lines", C.c_int64), ("n_records", C.c_int64), ("n_unknown_contig", C.c_int64), ("n_no_alt", C.c_int64), ("n_intervals", C.c_int64),
+                ("n_masked_bases", C.c_int64), ("tid", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32))]
+
+
+class GceMaskRun(C.Structure):
+    """gce_mask_run (gce_bam_error_profile_masked, gce_bam_error_profile_fragments_masked)."""
+    _fields_ = [("n_lines", C.c_int64), ("n_records", C.c_int64), ("n_unknown_contig", C.c_int64), ("n_no_alt", C.c_int64), ("n_intervals", C.c_int64),
+                ("n_masked_bases", C.c_int64), ("n_masked_events", C.c_int64), ("load_s", C.c_double), ("fill_s", C.c_double)]
 
 
 class GceCalmdStreamRun(C.Structure):
@@ -348,6 +361,14 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
                                                         C.c_uint64, C.c_size_t, C.POINTER(GceFragerrRun), C.c_char_p]
         lib.gce_fragerr_free.argtypes = [C.POINTER(GceFragerrRun)]
         lib.gce_fragerr_free.restype = None
+    if hasattr(lib, "gce_mask_load"):                                               # (the parent's build, loaded for an A/B run, lacks the mask)
+        lib.gce_mask_load.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(GceMask), C.c_char_p]
+        lib.gce_mask_free.argtypes = [C.POINTER(GceMask)]
+        lib.gce_mask_free.restype = None
+        lib.gce_bam_error_profile_masked.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                                                     C.c_uint64, C.c_size_t, C.POINTER(GceErrprofRun), C.POINTER(GceMaskRun), C.c_char_p]
+        lib.gce_bam_error_profile_fragments_masked.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                                               C.c_uint32, C.c_uint32, C.c_uint64, C.c_size_t, C.POINTER(GceFragerrRun), C.POINTER(GceMaskRun), C.c_char_p]
     lib.gce_depth_run_free.argtypes = [C.POINTER(GceDepthRun)]
     lib.gce_depth_run_free.restype = None
     lib.gce_bed_load.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

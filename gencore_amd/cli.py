@@ -47,7 +47,9 @@ substitution and by read position.  A table is tab-separated: segment (1 first, 
 sixteen counts A>A .. T>T of reference base against read base in read orientation (a reverse-strand read is complemented, so G>T stays apart
 from C>A), then READ_N REF_OTHER LOWQ INS DEL; integers only, no rates.  Records with a flag bit of 0x704 are left out, as are those below
 --error_profile_min_mapq, on a contig -r lacks or longer than 1024 bases; a base below --error_profile_min_baseq goes to LOWQ.  With -b only
-events on the targets count.  Hard clips do not count into the cycle, known variants are not masked, there is no split by read group.
+events on the targets count.  Hard clips do not count into the cycle, there is no split by read group.  --error_profile_mask FILE (.vcf, .vcf.gz or .bed of known variant
+sites) takes the events at those positions out of every class and counts them in a trailing MASKED column (one more line on STDERR gives the
+mask's intervals, its bases and the events masked): without it the mismatches of a consensus output are the sample's genotype.
 Overlapping mates are counted twice.  With --error_profile_fragments (for coordinate-sorted files) both tables count every fragment once
 where its mates overlap, choosing the mate as --pileup_fragments does, and a second table, FILE.overlap.tsv, says what the two mates of a pair
 show about each other at the positions both cover: segment, cycle, shared, errors, the sixteen A>A .. T>T (off the diagonal this mate's
@@ -152,6 +154,9 @@ def build_parser():
       help="[gencore_amd] --error_profile / --error_profile_in leave out records whose mapping quality is below this (0..255). Default 0.")
     a("--error_profile_min_baseq", type=int, default=0,
       help="[gencore_amd] --error_profile / --error_profile_in count a base whose quality is below this (0..255) as LOWQ. Default 0.")
+    a("--error_profile_mask", default=None, metavar="FILE",
+      help="[gencore_amd] --error_profile / --error_profile_in take the known variant sites of FILE (.vcf, .vcf.gz or .bed) out of every class: an event at a masked position "
+           "is counted in a trailing MASKED column instead, so that the mismatches are errors, not the sample's genotype. Applies to both tables and to --error_profile_fragments.")
     a("--error_profile_fragments", action="store_true",
       help="[gencore_amd] --error_profile / --error_profile_in count each fragment once where its mates overlap (the file must be coordinate-sorted) and write the mates' "
            "agreement by cycle to FILE.overlap.tsv beside each. Off by default.")
@@ -293,6 +298,12 @@ def validate(o):
                 err("--error_profile_in needs BAM input, not SAM text")
     if o.error_profile_fragments and o.error_profile is None and o.error_profile_in is None:
         err("--error_profile_fragments needs --error_profile or --error_profile_in")
+    if o.error_profile_mask is not None:
+        if o.error_profile is None and o.error_profile_in is None:
+            err("--error_profile_mask needs --error_profile or --error_profile_in")
+        check_file_valid(o.error_profile_mask)
+        if not o.error_profile_mask.endswith((".vcf", ".vcf.gz", ".bed")):
+            err("--error_profile_mask needs a .vcf, .vcf.gz or .bed file")
     for name in ("error_profile_min_mapq", "error_profile_min_baseq"):
         if not (0 <= getattr(o, name) <= 255):
             err("%s should be 0..255" % name)
@@ -335,10 +346,17 @@ def main(argv=None):
     def error_profile(label, bam, tsv):
         kw = dict(bed=o.bed or None, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.error_profile_min_mapq, min_baseq=o.error_profile_min_baseq, exclude_flags=0x704,
                   device_budget_bytes=o.device_memory_bytes)
-        r = error_profile_fragments_bam(bam, o.ref, overlap_tsv=tsv + ".overlap.tsv", **kw) if o.error_profile_fragments else error_profile_bam(bam, o.ref, **kw)
+        if o.error_profile_mask is not None:
+            from .bamio import error_profile_fragments_masked_bam, error_profile_masked_bam
+            r = (error_profile_fragments_masked_bam(bam, o.ref, o.error_profile_mask, overlap_tsv=tsv + ".overlap.tsv", **kw) if o.error_profile_fragments
+                 else error_profile_masked_bam(bam, o.ref, o.error_profile_mask, **kw))
+        else:
+            r = error_profile_fragments_bam(bam, o.ref, overlap_tsv=tsv + ".overlap.tsv", **kw) if o.error_profile_fragments else error_profile_bam(bam, o.ref, **kw)
         sys.stderr.write("%s: %d records, %d eligible, %d bases, %d mismatches\n" % (label, r.n_records, r.n_eligible, r.n_bases, r.n_mismatches))
         if o.error_profile_fragments:
             sys.stderr.write("%s: %d pairs, %d shared columns, %d disagreeing\n" % (label, r.n_pairs, r.n_shared_columns, r.n_disagree_columns))
+        if o.error_profile_mask is not None:
+            sys.stderr.write("%s: mask %d intervals, %d bases, %d events masked\n" % (label, r.n_mask_intervals, r.n_masked_bases, r.n_masked_events))
     tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged

@@ -16,6 +16,7 @@
 //   bamio_sort.hpp    gce_bam_sort, gce_bam_sort_passes, gce_sam_sort
 //   bamio_calmd.hpp   gce_bam_calmd, gce_bam_calmd_stream
 //   bamio_umi.hpp     gce_bam_umi_to_mi
+//   bamio_varmask.hpp gce_mask_load, the variant mask of the error profile (host only)
 //   bamio_reduce.hpp  reduce_run, the runner of the reduce passes
 //   bamio_pileup.hpp  gce_bam_pileup
 //   bamio_fragpile.hpp gce_bam_pileup_fragments
@@ -809,6 +810,7 @@ void gce_bed_free(int32_t n_regions, int32_t *tid, int32_t *start, int32_t *end,
 #include "bamio_sort.hpp"
 #include "bamio_calmd.hpp"
 #include "bamio_umi.hpp"
+#include "bamio_varmask.hpp"
 #include "bamio_pileup.hpp"
 #include "bamio_fragpile.hpp"
 #include "bamio_errprof.hpp"

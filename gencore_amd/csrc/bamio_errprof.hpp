@@ -18,22 +18,23 @@ namespace {
 // rule O's table of one block of counters: the header line (its third and fourth column and the five behind the sixteen are the caller's),
 // then per segment one row per cycle up to the last with a counter: segment, cycle, the sum of the classes below n_sum, the off-diagonal
 // ones of the sixteen, the 21 counters.  total, offdiag: those two sums over the table, added to
-inline void errprof_table(const uint64_t *counts, const char *col3, const char *col4, const char *tail, int n_sum, int64_t &total, int64_t &offdiag, std::string &buf) {
+// n_cls: 21, or 22 with a variant mask, whose MASKED column the caller's tail names
+inline void errprof_table(const uint64_t *counts, const char *col3, const char *col4, const char *tail, int n_sum, int64_t &total, int64_t &offdiag, std::string &buf, int n_cls = 21) {
     buf += "#segment\tcycle\t"; buf += col3; buf += '\t'; buf += col4;
     for (const char *r : {"A", "C", "G", "T"}) for (const char *b : {"A", "C", "G", "T"}) { buf += '\t'; buf += r; buf += '>'; buf += b; }
     buf += tail;
     for (int g = 0; g < 3; g++) {
         const uint64_t *seg = counts + (size_t)g * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES;
         int last = 0;                                                                 // the last cycle with a counter
-        for (int cy = 1; cy <= GCE_ERRPROF_MAX_CYCLE; cy++) for (int k = 0; k < 21; k++) if (seg[(size_t)(cy - 1) * GCE_ERRPROF_CLASSES + k]) last = cy;
+        for (int cy = 1; cy <= GCE_ERRPROF_MAX_CYCLE; cy++) for (int k = 0; k < n_cls; k++) if (seg[(size_t)(cy - 1) * GCE_ERRPROF_CLASSES + k]) last = cy;
         for (int cy = 1; cy <= last; cy++) {
             const uint64_t *k = seg + (size_t)(cy - 1) * GCE_ERRPROF_CLASSES;
             uint64_t bases = 0, mism = 0;
             for (int q = 0; q < n_sum; q++) { bases += k[q]; if (q < 16 && (q >> 2) != (q & 3)) mism += k[q]; }
             total += (int64_t)bases; offdiag += (int64_t)mism;
-            char line[26 * 21], *w = line;
+            char line[27 * 21], *w = line;
             w = pile_num(w, (uint64_t)g); *w++ = '\t'; w = pile_num(w, (uint64_t)cy); *w++ = '\t'; w = pile_num(w, bases); *w++ = '\t'; w = pile_num(w, mism);
-            for (int q = 0; q < 21; q++) { *w++ = '\t'; w = pile_num(w, k[q]); }
+            for (int q = 0; q < n_cls; q++) { *w++ = '\t'; w = pile_num(w, k[q]); }
             *w++ = '\n';
             buf.append(line, (size_t)(w - line));
         }
@@ -46,7 +47,7 @@ struct ErrprofPass {
     static constexpr bool bed_first = false;
     static constexpr auto create = gce_errprof_create; static constexpr auto window = gce_errprof_window; static constexpr auto error = gce_errprof_error;
     static constexpr auto destroy = gce_errprof_destroy; static constexpr auto free_out = gce_errprof_free;
-    gce_errprof_run *out; gce_errprof *p = nullptr;
+    gce_errprof_run *out; MaskJob mk{}; gce_errprof *p = nullptr;
     void zero() { memset(out, 0, sizeof *out); out->n_intervals = -1; }
     void sites(const ReduceInput &in) { out->n_intervals = (int64_t)in.ps.tid.size(); }
     // the reference bases go to the device and the host's copy is let go; then rule B's intervals
@@ -54,6 +55,7 @@ struct ErrprofPass {
         const int rc = gce_errprof_set_ref(p, in.n_ref, in.seq.data(), in.slen.data());
         if (rc != GCE_OK) return rc;
         gce_fasta_free(in.fa); in.fa = nullptr;
+        if (mk.on) { const int mrc = mk.fill([&](int64_t n, const int32_t *t, const int32_t *a, const int32_t *z) { return gce_errprof_set_mask(p, n, t, a, z); }); if (mrc != GCE_OK) return mrc; }
         return gce_errprof_set_sites(p, in.has_bed ? (int64_t)in.ps.tid.size() : -1, in.ps.tid.data(), in.ps.start.data(), in.ps.end.data());
     }
     double *pass_s() { return &out->errprof_s; }
@@ -67,12 +69,14 @@ struct ErrprofPass {
         if (rc != GCE_OK) return rc;
         out->n_records = c[0]; out->n_unplaced = c[1]; out->n_flagged = c[2]; out->n_low_mapq = c[3]; out->n_no_cigar = c[4]; out->n_no_seq = c[5]; out->n_bad_cigar = c[6];
         out->n_no_ref = c[7]; out->n_too_long = c[8]; out->n_eligible = c[9];
+        if (mk.on) mk.out->n_masked_events = MaskJob::events(out->counts);
         return GCE_OK;
     }
     // rule O: the totals, with or without a file, and one row per cycle up to the last with a counter
     template <class EMIT> bool table(const ReduceInput &, bool, EMIT &&emit) {
         std::string buf;
-        errprof_table(out->counts, "bases", "mismatches", "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\n", 16, out->n_bases, out->n_mismatches, buf);
+        errprof_table(out->counts, "bases", "mismatches", mk.on ? "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\tMASKED\n" : "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\n", 16, out->n_bases, out->n_mismatches, buf,
+                      mk.on ? 22 : 21);
         return emit(buf);
     }
 };
@@ -84,6 +88,14 @@ extern "C" {
 int gce_bam_error_profile(const char *bam_path, const char *fasta_path, const char *bed_path, const char *tsv_path, int32_t device, int threads, int32_t min_mapq, int32_t min_baseq,
                           uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_errprof_run *out, char err[256]) {
     ErrprofPass ps{out};
+    return reduce_run(ps, bam_path, bed_path, fasta_path, tsv_path, device, threads, min_mapq, min_baseq, exclude_flags, options, window_bytes, device_budget_bytes, err);
+}
+
+int gce_bam_error_profile_masked(const char *bam_path, const char *fasta_path, const char *bed_path, const char *mask_path, const char *tsv_path, int32_t device, int threads, int32_t min_mapq,
+                                 int32_t min_baseq, uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_errprof_run *out, gce_mask_run *mask,
+                                 char err[256]) {
+    ErrprofPass ps{out};
+    ps.mk.on = true; ps.mk.path = mask_path; ps.mk.out = mask;
     return reduce_run(ps, bam_path, bed_path, fasta_path, tsv_path, device, threads, min_mapq, min_baseq, exclude_flags, options, window_bytes, device_budget_bytes, err);
 }
 

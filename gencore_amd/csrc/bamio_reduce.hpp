@@ -4,6 +4,7 @@
 #pragma once
 #include "gce_entry.h"
 #include "bamio_reader.hpp"
+#include "bamio_varmask.hpp"
 
 namespace {
 
@@ -41,6 +42,28 @@ struct ReduceInput {
     gce_fasta *fa = nullptr; std::vector<const char *> seq; std::vector<int64_t> slen;
 };
 
+// The variant mask of a run (rule K and rule Y of DESIGN.md 4m), for the passes that take one: a pass with a member `MaskJob mk` has it loaded
+// behind the header and the FASTA (on: the entry point is a masked one; path and out are then its arguments) and sets it in its set()
+struct MaskJob {
+    bool on = false; const char *path = nullptr; gce_mask_run *out = nullptr;
+    gce_mask m{};
+    // the intervals through the pass's set_mask, at least once, so that an empty mask is a mask; fill_s: the seconds of it
+    template <class SET> int fill(SET &&set_mask) {
+        const double t0 = now_s();
+        const int rc = set_mask(m.n_intervals, m.tid, m.start, m.end);
+        out->fill_s += now_s() - t0;
+        return rc;
+    }
+    // class 21 of a block of counters, summed
+    static int64_t events(const uint64_t *counts) {
+        int64_t n = 0;
+        for (size_t r = 0; r < (size_t)3 * GCE_ERRPROF_MAX_CYCLE; r++) n += (int64_t)counts[r * GCE_ERRPROF_CLASSES + 21];
+        return n;
+    }
+};
+template <class P> auto mask_job(P &ps, int) -> decltype(&ps.mk) { return &ps.mk; }
+template <class P> MaskJob *mask_job(P &, long) { return nullptr; }
+
 // One run of a reduce pass over a BAM file.  PASS is the entry point's own part:
 //   who, option, options_known the entry point's name, its option bits, and what the refusal of any other says of them
 //   bed_first                  the BED is the required file and checked first, the FASTA optional (else the other way round)
@@ -50,11 +73,15 @@ struct ReduceInput {
 //   set(in), pass_s()          p set up in front of the first window; where out keeps the seconds of the pass's kernels
 //   alloc(in), finish()         out's arrays; the counters into out
 //   table(in, to_file, emit)   rule O: the table through emit(buf), a piece or all at once; to_file: there is a file to write
+//   mk (optional)              a MaskJob: with mk.on the mask file is checked with the other files, loaded behind the FASTA and freed by the frame
 template <class PASS> int reduce_run(PASS &ps, const char *bam_path, const char *bed_path, const char *fasta_path, const char *tsv_path, int32_t device, int threads, int32_t min_mapq,
                                      int32_t min_baseq, uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, char err[256]) {
     set_err(err, "");
-    if (!bam_path || !(PASS::bed_first ? bed_path : fasta_path) || !ps.out) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
+    MaskJob *mj = mask_job(ps, 0);
+    if (mj && !mj->on) mj = nullptr;
+    if (!bam_path || !(PASS::bed_first ? bed_path : fasta_path) || !ps.out || (mj && (!mj->path || !mj->out))) { set_err(err, "bad argument"); return GCE_ERR_INVALID; }
     ps.zero();
+    if (mj) memset(mj->out, 0, sizeof *mj->out);
     auto *out = ps.out;
     if (min_mapq < 0 || min_mapq > 255) { set_err(err, "min_mapq should be 0..255"); return GCE_ERR_INVALID; }
     if (min_baseq < 0 || min_baseq > 255) { set_err(err, "min_baseq should be 0..255"); return GCE_ERR_INVALID; }
@@ -63,6 +90,11 @@ template <class PASS> int reduce_run(PASS &ps, const char *bam_path, const char 
         const char *path = bed ? bed_path : fasta_path;
         struct stat sf;
         if (path && (stat(path, &sf) != 0 || S_ISDIR(sf.st_mode))) { set_err(err, bed ? "cannot open the BED file" : "cannot open the reference FASTA"); return GCE_ERR_INVALID; }
+    }
+    if (mj) {
+        struct stat sf;
+        if (stat(mj->path, &sf) != 0 || S_ISDIR(sf.st_mode)) { set_err(err, "cannot open the variant mask"); return GCE_ERR_INVALID; }
+        if (!mask_kind(mj->path)) { set_err(err, GCE_MASK_NAME_REFUSAL); return GCE_ERR_INVALID; }
     }
     const double t_start = now_s();
     InputFile in;
@@ -73,6 +105,7 @@ template <class PASS> int reduce_run(PASS &ps, const char *bam_path, const char 
         set_err(err, m);                                                              // (m may be the device object's: copied before it goes)
         if (ps.p) PASS::destroy(ps.p);
         if (ri.fa) gce_fasta_free(ri.fa);
+        if (mj) gce_mask_free(&mj->m);
         if (fo) { fclose(fo); fo = nullptr; }
         if (code != GCE_OK) { if (tsv_path) unlink(tmp.c_str()); PASS::free_out(out); }
         return code;
@@ -107,6 +140,20 @@ template <class PASS> int reduce_run(PASS &ps, const char *bam_path, const char 
         match_contigs(ri.names, ri.fa, ri.seq, ri.slen);
     }
     out->read_s += now_s() - t0;
+    // ---- rule K: the mask against the header's names, clamped to min(header length, FASTA length)
+    if (mj) {
+        t0 = now_s();
+        std::vector<const char *> np; for (const std::string &s : ri.names) np.push_back(s.c_str());
+        std::vector<int64_t> ml((size_t)n_ref);
+        for (int32_t t = 0; t < n_ref; t++) ml[(size_t)t] = std::min<int64_t>(ri.slen[(size_t)t], (int64_t)ri.lens[(size_t)t]);
+        char why[256];
+        const int mrc = gce_mask_load(mj->path, n_ref, np.data(), ml.data(), T, &mj->m, why);
+        if (mrc != GCE_OK) return done(mrc, why);
+        gce_mask_run *mo = mj->out;
+        mo->n_lines = mj->m.n_lines; mo->n_records = mj->m.n_records; mo->n_unknown_contig = mj->m.n_unknown_contig; mo->n_no_alt = mj->m.n_no_alt;
+        mo->n_intervals = mj->m.n_intervals; mo->n_masked_bases = mj->m.n_masked_bases;
+        mo->load_s = now_s() - t0;
+    }
     (void)gce_device_bytes(nullptr, nullptr, 1);
     int rc = PASS::create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, &ps.p);
     if (rc != GCE_OK) return done(rc, "no HIP device");

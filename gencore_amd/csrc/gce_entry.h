@@ -104,6 +104,7 @@ void gce_errprof_destroy(gce_errprof *p);
 const char *gce_errprof_error(gce_errprof *p);
 int gce_errprof_set_ref(gce_errprof *p, int32_t n_ref, const char *const *seq, const int64_t *len);
 int gce_errprof_set_sites(gce_errprof *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_errprof_set_mask(gce_errprof *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end);   /* gce_varmask.hpp; DESIGN.md 4m */
 int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s);
 int gce_errprof_finish(gce_errprof *p, int64_t counters[10], uint64_t *counts_out);
@@ -114,6 +115,7 @@ void gce_fragerr_destroy(gce_fragerr *p);
 const char *gce_fragerr_error(gce_fragerr *p);
 int gce_fragerr_set_ref(gce_fragerr *p, int32_t n_ref, const char *const *seq, const int64_t *len);
 int gce_fragerr_set_sites(gce_fragerr *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_fragerr_set_mask(gce_fragerr *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end);
 int gce_fragerr_window(gce_fragerr *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s);
 int gce_fragerr_finish(gce_fragerr *p, int64_t counters[15], uint64_t *counts_out, uint64_t *overlap_out);

@@ -16,6 +16,8 @@
 //                  never add to one address in one instruction.  Later cycles are 64-bit global atomics.  At the end the sum of the two
 //                  planes goes to memory, one 64-bit global atomic per non-zero counter.  k_err_count<true> (GCE_ERRPROF_DIRECT) has no
 //                  planes: every add is a 64-bit global atomic.
+// With a variant mask (gce_errprof_set_mask; gce_varmask.hpp) an event whose anchor has its bit set goes to class 21, MASKED
+// (rule Y): k_err_count<DIRECT, errprof::Mask>, the same walk with one bit test per event.
 // errprof::scan_record and errprof::count_record are __host__ __device__: tests/errprof_host_check.hip runs them on the host against
 // tests/pyerrprof.py, the model of the rules.  What the pass shares with gce_bam_pileup -- rule E, the interval table, the scan kernel and the
 // device object -- is gce_reduce.hpp's.
@@ -32,13 +34,16 @@ typedef uint16_t __attribute__((aligned(1), may_alias)) ep_u16u;
 
 #define EP_NONE RD_NONE
 #define EP_MAX_CYCLE 1024u
-#define EP_ROW 24u                                                                    // counters per (segment, cycle): 21 classes, 3 zeros
+#define EP_ROW 24u                                                                    // counters per (segment, cycle): 21 classes, MASKED, 2 zeros
 #define EP_COUNTERS (3u * EP_MAX_CYCLE * EP_ROW)
 enum { EP_READ_N = 16, EP_REF_OTHER, EP_LOWQ, EP_INS, EP_DEL, EP_NCLASS };
+#define EP_MASKED 21u                                                                 // rule Y's class, counted with a variant mask alone (gce_varmask.hpp); 22, 23: zero
 enum { EP_SKIP_NO_REF = reduce::N_SKIP + 1, EP_SKIP_TOO_LONG, EP_N_SKIP = EP_SKIP_TOO_LONG };            // behind rule E's six (gce_reduce.hpp)
 
 // bed: rule B is on (S holds the intervals); off, S is not read
 struct Params { int32_t n_ref, min_mapq, min_baseq; uint32_t exclude, bed; };
+// rule Y's bitmap (gce_varmask.hpp): one bit per byte of ref.blob, bit i of byte i / 8, so the bit of (tid, x) is ref.tab[2 tid] + x
+struct Mask { const uint8_t *bits; };
 // what the scan learns about a record.  bad: reduce::rule_e's BAD; skip: 0, or the one counter of rule E the record goes to; first: the first interval it can touch (0 without a BED; EP_NONE: none, or not eligible)
 struct Rec { uint32_t first; uint8_t bad, skip; };
 
@@ -64,11 +69,21 @@ EP_HD bool in_sites(const reduce::Sites &S, uint32_t cur, uint32_t tend, int64_t
     return cur < tend && (int64_t)S.iv[cur].start <= a;
 }
 
+// rule Y for the anchor a of an event on a contig whose bases start at byte `base` of the blob and whose FASTA has rlen of them: an anchor
+// outside [0, rlen) is not masked (there is no bit where there is no reference base)
+EP_HD bool mask_at(const Mask &M, int64_t base, int64_t rlen, int64_t a) {
+    if (a < 0 || a >= rlen) return false;
+    const uint64_t i = (uint64_t)(base + a);
+    return (M.bits[i >> 3] >> (i & 7u)) & 1u;
+}
+
 // Rule W for an eligible record whose scan gave `first`, by lane `lane` of the record's `nlanes`: the lanes stride over the columns of each
 // M / = / X op and over the bases of each I op, lane 0 takes the deletions.  add(row, cls): counter row * 24 + cls += 1, row = segment * 1024
 // + cycle - 1 < 3072, cls < 21.  Reads stay inside the record (the scan checked its fields against block_size, the CIGAR's query length
-// against l_seq and l_seq against 1024) and inside the contig's [0, length).
-template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
+// against l_seq and l_seq against 1024) and inside the contig's [0, length).  MASK: rule Y is on and M holds the bitmap (cls is then < 22);
+// off, M is not read and the code is the walk without a mask: count_record below gives both their names.
+template <bool MASK, class ADD> EP_HD void walk_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add,
+                                                       const Mask &M) {
     const uint8_t *c = r + 4;
     const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
     const uint32_t lq = c[8], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
@@ -76,7 +91,8 @@ template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, 
     const bool rev = (flag & 16u) != 0, has_q = ql[0] != 0xFF;
     const uint32_t seg = (flag & 0xC0u) == 0x40u ? 1u : (flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
     const uint32_t tend = P.bed ? S.tfirst[tid + 1] : 0u;
-    const uint8_t *rb = ref.blob + ref.tab[2 * tid]; const int64_t rlen = ref.tab[2 * tid + 1];
+    const int64_t rbase = ref.tab[2 * tid];
+    const uint8_t *rb = ref.blob + rbase; const int64_t rlen = ref.tab[2 * tid + 1];
     uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
 #define EP_CYC0(y) (rev ? (uint32_t)lseq - 1u - (y) : (y))                             // rule C, less one
     for (uint32_t k = 0; k < nc; k++) {
@@ -94,7 +110,8 @@ template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, 
                 for (int64_t col = a + lane; col < z; col += nlanes) {
                     const uint32_t yi = q + (uint32_t)(col - x);
                     uint32_t cls;
-                    if (has_q && (int32_t)ql[yi] < P.min_baseq) cls = EP_LOWQ;
+                    if (MASK && mask_at(M, rbase, rlen, col)) cls = EP_MASKED;        // (in front of LOWQ: the position's property, not the read's)
+                    else if (has_q && (int32_t)ql[yi] < P.min_baseq) cls = EP_LOWQ;
                     else {
                         uint32_t rc = 4;
                         if (col < rlen) { const uint8_t b = rb[col] & 0xDFu; rc = b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; }
@@ -108,17 +125,27 @@ template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, 
             x = xe; q += len; seen = true;
         } else if (op == 2) {
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), (uint32_t)EP_DEL);
+            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), MASK && mask_at(M, rbase, rlen, x) ? EP_MASKED : (uint32_t)EP_DEL);
             x += len; seen = true;
         } else if (op == 3) x += len;
         else if (op == 1) {
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x))
-                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), (uint32_t)EP_INS);
+            if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x)) {
+                const uint32_t cls = MASK && mask_at(M, rbase, rlen, seen ? x - 1 : x) ? EP_MASKED : (uint32_t)EP_INS;
+                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), cls);
+            }
             q += len;
         } else if (op == 4) q += len;
     }
 #undef EP_CYC0
+}
+// rule W alone, and rules W and Y under the bitmap M
+template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
+    walk_record<false>(r, P, ref, S, first, lane, nlanes, add, Mask{nullptr});
+}
+template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add,
+                                             const Mask &M) {
+    walk_record<true>(r, P, ref, S, first, lane, nlanes, add, M);
 }
 
 #undef EP_HD
@@ -134,6 +161,11 @@ template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, 
 // The 32-bit counters cannot wrap within one launch: every add reads a byte of the window no other add reads (a quality byte for a base of
 // M = X I, the low byte of the CIGAR word for a D), so a launch adds fewer than 2^32 times in all while the window is shorter than 2^32
 // bytes; gce_errprof_window launches the direct kernel for a longer one.
+// MASKED (class 21, rule Y) has no slot in a plane's row: a 22nd slot makes the stride even, so the 16 lanes of a record fall on 8 banks two
+// by two, and 23 slots make two planes 88 320 bytes, more than half a CU's LDS.  A masked event is a 64-bit global atomic, as an add past
+// EP_CYC is: under a sample's VCF about one base in a thousand, and the kernels without a mask (k_err_count<DIRECT>, no Mask argument) are
+// the instantiations they were, so a run without a mask pays nothing.  A mask that covers a large share of the targets (a BED of repeats)
+// pays an atomic per masked base; a per-block plane of 3 x EP_CYC MASKED counters is the next step if DESIGN.md 4m's measurement asks for it.
 #define EP_CYC 160u
 #define EP_CLS 21u
 #define EP_PLANES 2u
@@ -147,6 +179,7 @@ static_assert(EP_PLANES * EP_PLANE * 4u <= EP_LDS_PER_CU / EP_BLOCKS_PER_CU, "k_
 static_assert(EP_CLS == (unsigned)errprof::EP_NCLASS && (EP_CLS & 1u) && EP_CYC <= EP_MAX_CYCLE && EP_STEP_RECS * 16u == EP_THREADS, "k_err_count's layout");
 
 #ifndef GCE_ERRPROF_HOST_CHECK
+#include "gce_varmask.hpp"
 
 namespace {
 
@@ -167,19 +200,31 @@ template <bool DIRECT> struct ErrAdd {
         else atomicAdd(counts + row * EP_ROW + cls, 1ull);
     }
 };
+// ... with a variant mask: MASKED goes to memory, whatever its cycle
+template <bool DIRECT> struct ErrAddMasked {
+    uint32_t *plane; unsigned long long *counts;
+    __device__ __forceinline__ void operator()(uint32_t row, uint32_t cls) {
+        const uint32_t c0 = row & (EP_MAX_CYCLE - 1u);
+        if (!DIRECT && c0 < EP_CYC && cls != EP_MASKED) atomicAdd(plane + ((row >> 10) * EP_CYC + c0) * EP_CLS + cls, 1u);
+        else atomicAdd(counts + row * EP_ROW + cls, 1ull);
+    }
+};
+template <bool DIRECT, bool MASK> struct ErrAddOf { typedef ErrAdd<DIRECT> type; };
+template <bool DIRECT> struct ErrAddOf<DIRECT, true> { typedef ErrAddMasked<DIRECT> type; };
 // 16 lanes per record, 32 records per step; block b takes the records [32 (b + k gridDim.x), + 32) of the window, k = 0, 1, ...
-template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_err_count(const uint8_t *u, const uint64_t *off, uint64_t n, errprof::Params P, calmd::Ref ref, reduce::Sites S,
-                                                                                 const uint32_t *meta, unsigned long long *counts) {
+// MASK: none, or one errprof::Mask for rule Y
+template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) void k_err_count(const uint8_t *u, const uint64_t *off, uint64_t n, errprof::Params P, calmd::Ref ref, reduce::Sites S,
+                                                                                                const uint32_t *meta, unsigned long long *counts, MASK... mask) {
     __shared__ uint32_t s_tab[DIRECT ? 1 : EP_PLANES * EP_PLANE];
     const uint32_t slot = threadIdx.x >> 4, sub = threadIdx.x & 15u;
     if (!DIRECT) {
         for (uint32_t i = threadIdx.x; i < EP_PLANES * EP_PLANE; i += EP_THREADS) s_tab[i] = 0u;
         __syncthreads();
     }
-    ErrAdd<DIRECT> add{s_tab + (DIRECT ? 0u : (slot & (EP_PLANES - 1u)) * EP_PLANE), counts};
+    typename ErrAddOf<DIRECT, sizeof...(MASK) != 0>::type add{s_tab + (DIRECT ? 0u : (slot & (EP_PLANES - 1u)) * EP_PLANE), counts};
     for (uint64_t j = (uint64_t)blockIdx.x * EP_STEP_RECS + slot; j < n; j += (uint64_t)gridDim.x * EP_STEP_RECS) {
         const uint32_t first = meta[j];
-        if (first != EP_NONE) errprof::count_record(u + off[j], P, ref, S, first, sub, 16u, add);
+        if (first != EP_NONE) errprof::count_record(u + off[j], P, ref, S, first, sub, 16u, add, mask...);
     }
     if (!DIRECT) {
         __syncthreads();
@@ -199,7 +244,10 @@ struct gce_errprof : ReduceSession {
     errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
     DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
     DevBuf counts;                                                                    // EP_COUNTERS 64-bit totals
-    std::string needs() const override { return "gce_bam_error_profile needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 576 KiB of counters"; }
+    DevBuf mask; uint64_t mask_bytes = 0;                                             // rule Y's bitmap (gce_varmask.hpp); 0 bytes: no mask
+    std::string needs() const override {
+        return "gce_bam_error_profile needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 576 KiB of counters" + varmask_needs(mask_bytes);
+    }
 };
 
 // The reference and rule B's intervals of a pass whose object T has gce_errprof's members (P, blob, tab, ref_bytes, ref_set, counts):
@@ -231,7 +279,7 @@ extern "C" {
 int gce_errprof_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errprof **out) {
     return rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, (uint32_t)GCE_ERRPROF_DIRECT, out);
 }
-void gce_errprof_destroy(gce_errprof *p) { if (p) rd_destroy(p, {&p->blob, &p->tab, &p->counts}); }
+void gce_errprof_destroy(gce_errprof *p) { if (p) rd_destroy(p, {&p->blob, &p->tab, &p->counts, &p->mask}); }
 const char *gce_errprof_error(gce_errprof *p) { return p ? p->err.c_str() : ""; }
 
 // the reference, once, first of all: seq[t] / len[t] as gce_sort_calmd_ref takes them, laid out as it lays them out (calmd_ref_layout)
@@ -243,6 +291,10 @@ int gce_errprof_set_sites(gce_errprof *p, int64_t n_intervals, const int32_t *ti
     return ep_set_sites(p, "gce_errprof_set_sites", n_intervals, tid, start, end, EP_COUNTERS * 8ull);
 }
 
+// rule Y's mask, a chunk of it: the bits of [start[j], end[j]) of contig tid[j], clamped to the contig's FASTA length, are set.  Any number
+// of times, behind the reference and in front of the first window; chunks may repeat or overlap.  Class 21 is MASKED from the first call on.
+int gce_errprof_set_mask(gce_errprof *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end) { return ep_set_mask(p, n, tid, start, end); }
+
 // the next piece of the file, as gce_pileup_window takes it; *errprof_s: the seconds of the scan and k_err_count, added to.  GCE_ERR_INVALID
 // names the lowest malformed record, counting from 0 over the file.
 int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
@@ -253,7 +305,12 @@ int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int3
     return rd_window(p, ErrScan{p->P, ref, S}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, errprof_s, [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end) {
         const unsigned nb = (unsigned)std::min<uint64_t>((n_rec + EP_STEP_RECS - 1) / EP_STEP_RECS, EP_GRID);
         unsigned long long *counts = p->counts.as<unsigned long long>();
-        if (p->direct || (end >> 32)) hipLaunchKernelGGL(k_err_count<true>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
+        const bool direct = p->direct || (end >> 32);
+        if (p->mask_bytes) {
+            const errprof::Mask M{p->mask.as<uint8_t>()};
+            if (direct) hipLaunchKernelGGL((k_err_count<true, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts, M);
+            else hipLaunchKernelGGL((k_err_count<false, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts, M);
+        } else if (direct) hipLaunchKernelGGL(k_err_count<true>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
         else hipLaunchKernelGGL(k_err_count<false>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
         return true;
     });

@@ -23,6 +23,7 @@ namespace errprof {
 #define EP_HD __host__ __device__ inline
 
 enum { OVL_AGREE_REF = 16, OVL_AGREE_ALT, OVL_DIFF_OTHER, OVL_UNUSABLE, OVL_LOWQ, OVL_NCLASS };
+#define OVL_MASKED EP_MASKED                                                          // rule Y in the overlap table: class 21, with a variant mask alone
 static_assert((unsigned)OVL_NCLASS == EP_CLS, "the overlap table has the primary table's row");
 
 // A forward-only cursor over the CIGAR of an eligible record o: op k starts at reference x0 and query q0.  at(x, cls, q): the raw class
@@ -63,9 +64,11 @@ struct Cursor {
 // Rules W, V' and X for a mate r of a pair whose other mate is o, by lane `lane` of the record's `nlanes`, as count_record walks a record
 // alone.  is_b: r is the later of the two in the file.  A column that an M / = / X op of o covers is shared: add2(row, cls) takes r's count
 // of rule X, and add(row, cls) r's count of rule V' if r is the one rule V' counts.  Every other column, every insertion and every deletion is
-// rule W's.  shared, differ: rule V's counters, added to by the later mate's walk alone.
-template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first,
-                                                        uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ) {
+// rule W's.  shared, differ: rule V's counters, added to by the later mate's walk alone.  MASK: rule Y is on and M holds the bitmap: at a
+// masked shared column both mates add OVL_MASKED to the overlap table and the mate rule V' counts adds MASKED to the primary one, so the
+// fragment is still counted once and shared / differ are what they are without a mask.  Off, M is not read: paired_walk below names both.
+template <bool MASK, class ADD, class ADD2> EP_HD void paired_walk_record(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S,
+                                                                          uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ, const Mask &M) {
     const uint8_t *c = r + 4;
     const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
     const uint32_t lq = c[8], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
@@ -73,7 +76,8 @@ template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const 
     const bool rev = (flag & 16u) != 0, has_q = ql[0] != 0xFF;
     const uint32_t seg = (flag & 0xC0u) == 0x40u ? 1u : (flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
     const uint32_t tend = P.bed ? S.tfirst[tid + 1] : 0u;
-    const uint8_t *rb = ref.blob + ref.tab[2 * tid]; const int64_t rlen = ref.tab[2 * tid + 1];
+    const int64_t rbase = ref.tab[2 * tid];
+    const uint8_t *rb = ref.blob + rbase; const int64_t rlen = ref.tab[2 * tid + 1];
     Cursor oc(o);
     uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
 #define EP_CYC0(y) (rev ? (uint32_t)lseq - 1u - (y) : (y))                             // rule C, less one
@@ -96,6 +100,7 @@ template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const 
                     if (col < rlen) { const uint8_t b = rb[col] & 0xDFu; rc = b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; }
                     const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u, bc = nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
                     uint32_t ob = 0, oq = 0, adj = mq;
+                    const bool mk = MASK && mask_at(M, rbase, rlen, col);
                     if (oc.at(col, ob, oq)) {
                         // ---- rule X: this mate's count in the overlap table
                         uint32_t xc;
@@ -104,7 +109,7 @@ template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const 
                         else if (bc == ob) xc = bc == rc ? (uint32_t)OVL_AGREE_REF : (uint32_t)OVL_AGREE_ALT;
                         else if (ob == rc || bc == rc) xc = rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
                         else xc = OVL_DIFF_OTHER;
-                        add2(row, xc);
+                        add2(row, mk ? OVL_MASKED : xc);
                         // ---- rule V': which of the two the primary table counts, and at which quality
                         const uint32_t qa = is_b ? oq : mq, qb = is_b ? mq : oq;
                         bool mine;
@@ -113,7 +118,7 @@ template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const 
                         if (is_b) { shared++; differ += bc != ob; }
                         if (!mine) continue;
                     }
-                    const uint32_t cls = has_q && (int32_t)adj < P.min_baseq ? (uint32_t)EP_LOWQ
+                    const uint32_t cls = mk ? EP_MASKED : has_q && (int32_t)adj < P.min_baseq ? (uint32_t)EP_LOWQ
                                          : rc > 3 ? (uint32_t)EP_REF_OTHER : bc > 3 ? (uint32_t)EP_READ_N : rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
                     add(row, cls);
                 }
@@ -122,17 +127,27 @@ template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const 
             x = xe; q += len; seen = true;
         } else if (op == 2) {
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), (uint32_t)EP_DEL);
+            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), MASK && mask_at(M, rbase, rlen, x) ? EP_MASKED : (uint32_t)EP_DEL);
             x += len; seen = true;
         } else if (op == 3) x += len;
         else if (op == 1) {
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x))
-                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), (uint32_t)EP_INS);
+            if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x)) {
+                const uint32_t cls = MASK && mask_at(M, rbase, rlen, seen ? x - 1 : x) ? EP_MASKED : (uint32_t)EP_INS;
+                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), cls);
+            }
             q += len;
         } else if (op == 4) q += len;
     }
 #undef EP_CYC0
+}
+template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first,
+                                                        uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ) {
+    paired_walk_record<false>(r, o, is_b, P, ref, S, first, lane, nlanes, add, add2, shared, differ, Mask{nullptr});
+}
+template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first,
+                                                        uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ, const Mask &M) {
+    paired_walk_record<true>(r, o, is_b, P, ref, S, first, lane, nlanes, add, add2, shared, differ, M);
 }
 
 #undef EP_HD
@@ -164,15 +179,17 @@ struct FragerrRead {
 };
 
 // 16 lanes per entry, 32 entries per step; block b takes the entries [32 (b + k gridDim.x), + 32) of the join, k = 0, 1, ...
-template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_fragerr_count(FragView V, errprof::Params P, calmd::Ref ref, reduce::Sites S, const uint32_t *first, const uint32_t *partner,
-                                                                                     unsigned long long *counts, unsigned long long *ovl, unsigned long long *fm) {
+// MASK: none, or one errprof::Mask for rule Y (MASKED and OVL_MASKED go to memory, as in k_err_count)
+template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) void k_fragerr_count(FragView V, errprof::Params P, calmd::Ref ref, reduce::Sites S, const uint32_t *first,
+                                                                                                    const uint32_t *partner, unsigned long long *counts, unsigned long long *ovl,
+                                                                                                    unsigned long long *fm, MASK... mask) {
     __shared__ uint32_t s_tab[DIRECT ? 1 : 2 * EP_PLANE];
     const uint32_t slot = threadIdx.x >> 4, sub = threadIdx.x & 15u;
     if (!DIRECT) {
         for (uint32_t i = threadIdx.x; i < 2 * EP_PLANE; i += EP_THREADS) s_tab[i] = 0u;
         __syncthreads();
     }
-    ErrAdd<DIRECT> add{s_tab, counts}, add2{s_tab + (DIRECT ? 0u : EP_PLANE), ovl};
+    typename ErrAddOf<DIRECT, sizeof...(MASK) != 0>::type add{s_tab, counts}, add2{s_tab + (DIRECT ? 0u : EP_PLANE), ovl};
     uint32_t shared = 0, differ = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * EP_STEP_RECS + slot; e < V.n; e += (uint64_t)gridDim.x * EP_STEP_RECS) {
         const uint32_t pc = partner[e];
@@ -180,8 +197,8 @@ template <bool DIRECT> __global__ __launch_bounds__(EP_THREADS) void k_fragerr_c
         const uint32_t f = first[e];
         if (f == EP_NONE) continue;
         const uint8_t *r = V.rec(e);
-        if (pc == FP_ALONE) errprof::count_record(r, P, ref, S, f, sub, 16u, add);
-        else errprof::paired_walk(r, V.rec(pc & ~FP_IS_B), (pc & FP_IS_B) != 0, P, ref, S, f, sub, 16u, add, add2, shared, differ);
+        if (pc == FP_ALONE) errprof::count_record(r, P, ref, S, f, sub, 16u, add, mask...);
+        else errprof::paired_walk(r, V.rec(pc & ~FP_IS_B), (pc & FP_IS_B) != 0, P, ref, S, f, sub, 16u, add, add2, shared, differ, mask...);
     }
     if (!DIRECT) {
         __syncthreads();
@@ -207,10 +224,11 @@ struct gce_fragerr : ReduceSession {
     errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
     DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
     DevBuf counts;                                                                    // two blocks of EP_COUNTERS 64-bit totals: the primary table, the overlap table
+    DevBuf mask; uint64_t mask_bytes = 0;                                             // rule Y's bitmap (gce_varmask.hpp); 0 bytes: no mask
     MateJoin J; int cb_rc = GCE_OK;
     std::string needs() const override {
         return "gce_bam_error_profile_fragments needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 1152 KiB of counters, a join table (" + std::to_string(J.table_bytes()) +
-               " bytes) and an arena (" + std::to_string(J.arena_bytes()) + " bytes)";
+               " bytes) and an arena (" + std::to_string(J.arena_bytes()) + " bytes)" + varmask_needs(mask_bytes);
     }
     calmd::Ref ref() const { return calmd::Ref{blob.as<uint8_t>(), tab.as<int64_t>(), P.n_ref}; }
     int process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, bool final);
@@ -222,7 +240,11 @@ int gce_fragerr::process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, 
     return J.run(this, "gce_bam_error_profile_fragments", FragerrRead{P}, u, off, n_rec, final, [&](const FragView &V, uint64_t N, const uint32_t *first, const uint32_t *partner, unsigned long long *m) {
         const unsigned nb = (unsigned)std::min<uint64_t>((N + EP_STEP_RECS - 1) / EP_STEP_RECS, EP_GRID);
         unsigned long long *c = counts.as<unsigned long long>();
-        if (direct || wide) hipLaunchKernelGGL(k_fragerr_count<true>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
+        if (mask_bytes) {
+            const errprof::Mask M{mask.as<uint8_t>()};
+            if (direct || wide) hipLaunchKernelGGL((k_fragerr_count<true, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m, M);
+            else hipLaunchKernelGGL((k_fragerr_count<false, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m, M);
+        } else if (direct || wide) hipLaunchKernelGGL(k_fragerr_count<true>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
         else hipLaunchKernelGGL(k_fragerr_count<false>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
         return true;
     });
@@ -241,7 +263,7 @@ void gce_fragerr_destroy(gce_fragerr *p) {
     if (!p) return;
     (void)hipSetDevice(p->device); (void)hipStreamSynchronize(p->s);
     p->J.release();
-    rd_destroy(p, {&p->blob, &p->tab, &p->counts});
+    rd_destroy(p, {&p->blob, &p->tab, &p->counts, &p->mask});
 }
 const char *gce_fragerr_error(gce_fragerr *p) { return p ? p->err.c_str() : ""; }
 
@@ -258,6 +280,9 @@ int gce_fragerr_set_sites(gce_fragerr *p, int64_t n_intervals, const int32_t *ti
     p->sites_set = true;
     return GCE_OK;
 }
+
+// rule Y's mask, a chunk of it, as gce_errprof_set_mask takes it: class 21 of the primary table is MASKED, of the overlap table OVL_MASKED
+int gce_fragerr_set_mask(gce_fragerr *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end) { return ep_set_mask(p, n, tid, start, end); }
 
 // the next piece of the file, as gce_errprof_window takes it; *errprof_s: the seconds of the scan, the join and the count, added to.
 // GCE_ERR_INVALID names the lowest malformed record, else the first record that lies in front of its predecessor, counting from 0 over the file.

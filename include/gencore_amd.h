@@ -443,6 +443,27 @@ int gce_bed_load(const char *path, int32_t n_targets, const char *const *target_
                  int32_t **end, char ***name);
 void gce_bed_free(int32_t n_regions, int32_t *tid, int32_t *start, int32_t *end, char **name);
 
+/* The variant mask of the error profile, read on the host (addition under ABI v3; gencore_amd/csrc/bamio_varmask.hpp, DESIGN.md 4m rule K).
+ * Replaces: nothing in the reference's source -- it is the `--variants` of `fgbio ErrorRateByReadPosition` and the DB_SNP of Picard's
+ * metrics.  path ends in `.vcf` or `.vcf.gz` (plain gzip or BGZF, any number of members; inflated and parsed as a stream, so no line is too
+ * long) or in `.bed` (read with gce_bed_load, unchanged); any other name is refused.  VCF: lines end in LF or CR LF, the last may lack it;
+ * empty lines and lines that begin with `#` are no records; every other line needs five tab-separated fields CHROM POS ID REF ALT with POS a
+ * decimal integer >= 1 and REF not empty, else GCE_ERR_INVALID with "variant mask line N: ..." (N from 1 over all lines).  A record (n_records)
+ * gives the 0-based interval [POS - 1, POS - 1 + strlen(REF)) of the contig names[t] == CHROM: the SNP base, an insertion's anchor base, a
+ * deletion's anchor and its deleted bases.  Not used: a record of an unknown CHROM (n_unknown_contig), else one whose ALT is `.`, `<NON_REF>`
+ * or `<*>` alone (n_no_alt: the reference blocks of a gVCF).  FILTER, INFO (END= too) and the genotypes are not read: a symbolic SV allele
+ * masks its one REF base.  BED: every region is a record, one of an unknown contig n_unknown_contig.  The intervals are clamped to
+ * [0, lens[t]) -- the caller gives min(header length, FASTA length), <= 0 for a contig without reference bases, whose intervals are dropped
+ * --, sorted by (tid, start) and merged where they overlap or abut (n_intervals of them, n_masked_bases positions; no cap on either).
+ * threads is accepted for symmetry with gce_fasta_load; inflate and parse are one pass on one thread.  No device is touched.  The arrays are
+ * malloc'ed: gce_mask_free.  A failed call leaves *out zeroed. */
+typedef struct gce_mask {
+    int64_t n_lines, n_records, n_unknown_contig, n_no_alt, n_intervals, n_masked_bases;   /* n_lines: 0 for a BED */
+    int32_t *tid, *start, *end;     /* n_intervals each */
+} gce_mask;
+int gce_mask_load(const char *path, int32_t n_ref, const char *const *names, const int64_t *lens, int threads, gce_mask *out, char err[256]);
+void gce_mask_free(gce_mask *m);
+
 typedef struct gce_bam_run {
     int64_t n_reads, n_out;
     double  open_s;          /* gce_bam_open: read + inflate + index */
@@ -805,7 +826,7 @@ void gce_fragpile_free(gce_fragpile_run *out);
  * the contig, matched by name as gce_bam_calmd matches it) and n_too_long (l_seq > GCE_ERRPROF_MAX_CYCLE).  Segment: 1 for flag 0x40 without
  * 0x80, 2 for 0x80 without 0x40, else 0.  Cycle of query index y: y + 1, on the reverse strand l_seq - y (hard clips are not counted).
  * counts[(segment * 1024 + cycle - 1) * 24 + class]; classes 0..15: 4 r + b, reference base r against read base b over A C G T in sequencing
- * orientation (both complemented on the reverse strand); 16 READ_N, 17 REF_OTHER, 18 LOWQ, 19 INS, 20 DEL, 21..23 zero.  An M / = / X column:
+ * orientation (both complemented on the reverse strand); 16 READ_N, 17 REF_OTHER, 18 LOWQ, 19 INS, 20 DEL, 21..23 zero (21 is MASKED under gce_bam_error_profile_masked).  An M / = / X column:
  * LOWQ when QUAL[0] != 0xFF and its quality < min_baseq, else REF_OTHER when it lies at or beyond the contig's FASTA length or the upper-cased
  * reference byte is not A C G T, else READ_N when the read nibble is not 1, 2, 4 or 8, else 4 r + b.  Every inserted base adds INS at its own
  * cycle; a D adds one DEL at the cycle of the query base in front of it (the first, when there is none).  bed_path (NULL: none) restricts the
@@ -835,8 +856,8 @@ void gce_errprof_free(gce_errprof_run *out);
 /* gce_bam_error_profile's table with every fragment counted once where its mates overlap, and a second table of what the two mates say of
  * each other there, on ONE device (addition under ABI v3; gencore_amd/csrc/gce_fragerr.hpp).
  * Replaces: nothing in the reference's source -- it stands in for the `fgbio ErrorRateByReadPosition` / Picard artifact metrics that
- * gce_bam_error_profile stands in for, which count overlapping mates twice and cannot tell a sequencing error from an older one without a
- * variant mask.  The arguments, eligible records, segment, cycle, classes, BED and primary table are gce_bam_error_profile's; a record
+ * gce_bam_error_profile stands in for, which count overlapping mates twice and cannot tell a sequencing error from an older one at a site
+ * no variant mask names (gce_bam_error_profile_fragments_masked takes one).  The arguments, eligible records, segment, cycle, classes, BED and primary table are gce_bam_error_profile's; a record
  * without a partner is counted exactly as gce_bam_error_profile counts it.  Rule P (the file is coordinate-sorted;
  * "BAM record N (counting from 0) lies in front of its predecessor: ...") and Rule M (candidates, pairs, n_ambiguous, waiting across
  * windows, n_deferred) are gce_bam_pileup_fragments', with
@@ -873,6 +894,33 @@ int gce_bam_error_profile_fragments(const char *bam_path, const char *fasta_path
                                     const char *overlap_tsv_path /* NULL: no file */, int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags,
                                     uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_fragerr_run *out, char err[256]);
 void gce_fragerr_free(gce_fragerr_run *out);
+/* gce_bam_error_profile and gce_bam_error_profile_fragments with known variant sites masked (addition under ABI v3;
+ * gencore_amd/csrc/gce_varmask.hpp).  Replaces: nothing in the reference's source -- `fgbio ErrorRateByReadPosition --variants`,
+ * Picard's DB_SNP.  mask_path is read with gce_mask_load against the header's names, clamped to min(header length, FASTA length), behind the
+ * header and the FASTA; a NULL or missing mask_path or a NULL mask is refused before a device is touched, like the FASTA, a name with
+ * another ending and a malformed line (gce_mask_load's message) before a window is read.  On the device the mask is one bit per reference
+ * base (ref bytes / 8 more device memory, inside device_budget_bytes; GCE_ERR_OOM names `the variant mask`).  Rule Y: class 21 of every
+ * (segment, cycle) row is MASKED, in the overlap table OVL_MASKED.  An event whose anchor is masked goes there, at the segment and cycle it
+ * would have had, instead of to any other class: an M / = / X column by its own position (tested in front of LOWQ), every inserted base by
+ * the position in front of it (its own when no M = X D came earlier), a deletion by its first position; an anchor outside [0, FASTA length)
+ * is not masked; with a BED its test comes first, so an event off the targets is still not counted.  At a shared masked column of a pair the
+ * one mate rule V' counts adds MASKED to counts, both add OVL_MASKED to overlap; n_shared_columns, n_disagree_columns and the sum of overlap
+ * stay what they are.  So per (segment, cycle) the sum of classes 0..21 equals the sum of 0..20 without a mask, and n_bases, n_mismatches,
+ * shared and errors (classes 0..15 and 0..18) lose the masked sites.  The tables get one more trailing column, MASKED, in the header line
+ * and every row.  Everything else is the unmasked entry point's, whose counters, tables and structs do not change.  *mask: what
+ * gce_mask_load counted, n_masked_events (the sum of class 21 of counts), load_s (the file read and parsed on the host) and fill_s (a host clock around the set_mask calls: the bitmap's allocation and zeroing, the
+ * staging copies, k_mask_fill and a synchronise per 65 536 intervals). */
+typedef struct gce_mask_run {
+    int64_t n_lines, n_records, n_unknown_contig, n_no_alt, n_intervals, n_masked_bases, n_masked_events;
+    double  load_s, fill_s;
+} gce_mask_run;
+int gce_bam_error_profile_masked(const char *bam_path, const char *fasta_path, const char *bed_path /* NULL: no BED */, const char *mask_path, const char *tsv_path /* NULL: no file */,
+                                 int32_t device, int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options,
+                                 uint64_t window_bytes, size_t device_budget_bytes, gce_errprof_run *out, gce_mask_run *mask, char err[256]);
+int gce_bam_error_profile_fragments_masked(const char *bam_path, const char *fasta_path, const char *bed_path /* NULL: no BED */, const char *mask_path,
+                                           const char *tsv_path /* NULL: no file */, const char *overlap_tsv_path /* NULL: no file */, int32_t device, int threads, int32_t min_mapq,
+                                           int32_t min_baseq, uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_fragerr_run *out,
+                                           gce_mask_run *mask, char err[256]);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

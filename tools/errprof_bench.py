@@ -14,7 +14,14 @@ runs gce_bam_error_profile_fragments (frag_planes, frag_direct) be
 without a BED, in the same interleaved way.  With --parent_lib, the library built from the parent commit (loaded through GCE_LIB) runs in the
 same rounds: its gce_bam_error_profile (parent_planes) is the comparison partner, and its gce_bam_pileup_fragments (parent_pileup_fragments)
 stands beside this tree's (pileup_fragments), whose join moved into gce_matejoin.hpp: pileup_s is unchanged when the two medians differ by
-less than the spread of the values."""
+less than the spread of the values.
+    python tools/errprof_bench.py --mask [--parent_lib PATH] [--out profiles/errprof_mask.json]
+runs gce_bam_error_profile_masked beside gce_bam_error_profile on the same file, without a BED, in the same interleaved way:
+planes (the unmasked entry point of this build), parent_planes (with --parent_lib: the unmasked entry point of the parent commit's library,
+through GCE_LIB), mask_vcf (a synthetic VCF of one SNP per 1000 reference bases) and mask_bed (a BED mask of about 10 % of the reference in
+1 kb blocks).  It reports errprof_s, fill_s, load_s and peak_device_bytes, whether planes differs from parent_planes by more than the spread
+of the values (a run without a mask is to pay nothing), and what the two masks cost over planes; one rocprofv3 --kernel-trace --stats run per masked variant, each in a process of
+its own, gives k_mask_fill's own time beside fill_s, the host clock around set_mask."""
 import argparse
 import csv
 import glob
@@ -31,6 +38,7 @@ sys.path.insert(0, ROOT)
 MODES = ("planes", "direct", "planes_bed", "direct_bed", "index")
 FRAG_MODES = ("planes", "frag_planes", "direct", "frag_direct")
 PARENT_MODES = ("parent_planes", "pileup_fragments", "parent_pileup_fragments")
+MASK_MODES = ("planes", "mask_vcf", "mask_bed")
 
 
 def child(args):
@@ -48,6 +56,10 @@ def child(args):
     elif args.mode.endswith("pileup_fragments"):
         r = bamio.pileup_fragments_bam(src, bed, threads=args.threads)
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())))
+    elif args.mode.startswith("mask_"):
+        r = bamio.error_profile_masked_bam(src, fa, os.path.join(args.child, "mask.vcf" if args.mode == "mask_vcf" else "mask.bed"), tsv=os.path.join(args.child, "%s.tsv" % args.mode),
+                                           threads=args.threads)
+        d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())), rows_sum_crc=int(zlib.crc32(r.counts.sum(axis=2).tobytes())))
     elif args.mode.startswith("frag_"):
         r = bamio.error_profile_fragments_bam(src, fa, tsv=os.path.join(args.child, "%s.tsv" % args.mode), overlap_tsv=os.path.join(args.child, "%s.overlap.tsv" % args.mode),
                                               threads=args.threads, direct=args.mode.endswith("direct"))
@@ -56,7 +68,7 @@ def child(args):
     else:
         r = bamio.error_profile_bam(src, fa, bed=bed if args.mode.endswith("_bed") else None, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads,
                                     direct="direct" in args.mode)
-        d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())))
+        d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())), rows_sum_crc=int(zlib.crc32(r.counts.sum(axis=2).tobytes())))
     print(json.dumps(dict(d, wall_s=time.perf_counter() - t0)), flush=True)
 
 
@@ -90,6 +102,19 @@ def child_make(args):
     with open(os.path.join(args.child, "panel.bed"), "w") as f:
         for t, a, z in bed:
             f.write("%s\t%d\t%d\n" % (names[int(t)], int(a), int(z)))
+    if not args.mask:
+        print(json.dumps(dict(reads=int(batch.n), bed_regions=int(len(bed)), reference_bases=ref_bytes)), flush=True)
+        return
+    # ---- the masks of --mask: one SNP per 1000 reference bases as VCF, and about 10 % of the reference in 1 kb blocks as BED
+    with open(os.path.join(args.child, "mask.vcf"), "w") as fv, open(os.path.join(args.child, "mask.bed"), "w") as fb:
+        fv.write("##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\n")
+        for nm, (nib, ln) in zip(names, d.reference_host()):
+            if nib is None:
+                continue
+            for x in range(500, int(ln), 1000):
+                fv.write("%s\t%d\t.\tN\t<X>\n" % (nm, x + 1))
+            for x in range(2000, int(ln) - 1000, 10000):
+                fb.write("%s\t%d\t%d\n" % (nm, x, x + 1000))
     print(json.dumps(dict(reads=int(batch.n), bed_regions=int(len(bed)), reference_bases=ref_bytes)), flush=True)
 
 
@@ -97,7 +122,7 @@ def run_child(args, tmp, mode, prefix=(), limit=None):
     limit = limit or (args.direct_limit if "direct" in mode else args.limit)
     env = dict(os.environ, GCE_LIB=os.path.abspath(args.parent_lib)) if mode.startswith("parent_") else None
     p = subprocess.run(["timeout", "-k", "10", str(limit)] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--mode", mode, "--threads", str(args.threads),
-                                                                           "--workload", args.workload, "--pairs", str(args.pairs)], stdout=subprocess.PIPE, universal_newlines=True, env=env)
+                                                                           "--workload", args.workload, "--pairs", str(args.pairs)] + (["--mask"] if args.mask else []), stdout=subprocess.PIPE, universal_newlines=True, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:
         raise SystemExit("errprof_bench: a child run (%s) failed (exit %d, limit %d s)" % (mode, p.returncode, limit))
@@ -110,7 +135,7 @@ def kernel_times(args, tmp, mode):
     kern = {}
     for f in glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"k_err_\w+|k_fragerr_\w+|k_frag_\w+|k_reduce_scan", r["Name"])   # (the CSV holds the demangled name)
+            m = re.search(r"k_err_\w+|k_fragerr_\w+|k_frag_\w+|k_reduce_scan|k_mask_fill", r["Name"])   # (the CSV holds the demangled name)
             if m:
                 k = kern.setdefault(m.group(0), dict(calls=0, seconds=0.0))
                 k["calls"] += int(r["Calls"]); k["seconds"] += float(r["TotalDurationNs"]) * 1e-9
@@ -130,14 +155,17 @@ def main():
     ap.add_argument("--limit", type=int, default=300)
     ap.add_argument("--direct_limit", type=int, default=900)
     ap.add_argument("--child", default=None)
-    ap.add_argument("--mode", default="planes", choices=("make",) + MODES + FRAG_MODES[1::2] + PARENT_MODES)
+    ap.add_argument("--mode", default="planes", choices=("make",) + MODES + FRAG_MODES[1::2] + PARENT_MODES + MASK_MODES[1:])
+    ap.add_argument("--mask", action="store_true", help="gce_bam_error_profile_masked beside gce_bam_error_profile; writes profiles/errprof_mask.json")
     ap.add_argument("--fragments", action="store_true", help="gce_bam_error_profile_fragments beside gce_bam_error_profile; writes profiles/errprof_fragments.json")
-    ap.add_argument("--parent_lib", default=None, help="with --fragments: the parent commit's libgencore_amd.so, run in the same rounds through GCE_LIB")
+    ap.add_argument("--parent_lib", default=None, help="with --fragments or --mask: the parent commit's libgencore_amd.so, run in the same rounds through GCE_LIB")
     args = ap.parse_args()
     if args.child is not None:
         return child_make(args) if args.mode == "make" else child(args)
     if args.fragments:
         return main_fragments(args)
+    if args.mask:
+        return main_mask(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "errprof.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_errprof_")
     made = run_child(args, tmp, "make", limit=900)
@@ -223,6 +251,56 @@ def main_fragments(args):
                                                       spread_s=round(noise, 5), unchanged=abs(gap) <= noise, counters_identical=same("pileup_fragments", "parent_pileup_fragments"))
     for m in FRAG_MODES:
         v[m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+def main_mask(args):
+    args.out = args.out or os.path.join(ROOT, "profiles", "errprof_mask.json")
+    tmp = args.dir or tempfile.mkdtemp(prefix="gce_errmask_")
+    made = run_child(args, tmp, "make", limit=900)
+    modes = MASK_MODES[:1] + (("parent_planes",) if args.parent_lib else ()) + MASK_MODES[1:]
+    per = {m: [] for m in modes}
+    for rep in range(args.reps + 1):                               # interleaved; the first round is the warm-up
+        for m in modes:
+            r = run_child(args, tmp, m)
+            if rep:
+                per[m].append(r)
+        print("errprof_bench: round %d done" % rep, flush=True)
+    med = lambda rs, k: sorted(r[k] for r in rs)[len(rs) // 2]
+    spread = lambda rs, k: max(r[k] for r in rs) - min(r[k] for r in rs)
+    res = dict(workload=args.workload, pairs=int(args.pairs), reps=args.reps, **made, input_bytes=os.path.getsize(os.path.join(tmp, "in.bam")),
+               clocks="the library's stage times: host clocks around work that ends in a device synchronise",
+               what="gce_bam_error_profile_masked (mask_vcf: one SNP per 1000 reference bases; mask_bed: about 10 % of the reference in 1 kb blocks) beside gce_bam_error_profile "
+                    "(planes; parent_planes: the parent commit's library) on the same file, without a BED, interleaved; no pass mark", variants={})
+    for m in modes:
+        rs = per[m]
+        keys = ("read_s", "inflate_index_s", "errprof_s", "write_s", "total_s", "wall_s") + (("load_s", "fill_s") if m.startswith("mask_") else ())
+        res["variants"][m] = dict(stages={k: round(med(rs, k), 5) for k in keys}, errprof_s_all=[round(r["errprof_s"], 5) for r in rs], total_s_all=[round(r["total_s"], 4) for r in rs],
+                                  peak_device_bytes=int(rs[0]["peak_device_bytes"]), counters={c: int(rs[0][c]) for c in rs[0] if c.startswith("n_")},
+                                  sums={c: rs[0][c] for c in ("counts_sum", "counts_crc", "rows_sum_crc") if c in rs[0]})
+        if m.startswith("mask_"):
+            res["variants"][m].update(fill_s_all=[round(r["fill_s"], 5) for r in rs], load_s_all=[round(r["load_s"], 5) for r in rs])
+    v = res["variants"]
+    e = lambda m: v[m]["stages"]["errprof_s"]
+    res["rows_keep_their_sums"] = all(v[m]["sums"]["rows_sum_crc"] == v["planes"]["sums"]["rows_sum_crc"] for m in MASK_MODES[1:])
+    res["cost_over_planes"] = {m: dict(errprof_s=round(e(m) - e("planes"), 5), errprof_s_ratio=round(e(m) / e("planes"), 3), fill_s=v[m]["stages"]["fill_s"], load_s=v[m]["stages"]["load_s"],
+                                       peak_device_bytes=v[m]["peak_device_bytes"] - v["planes"]["peak_device_bytes"], spread_s=round(max(spread(per[m], "errprof_s"), spread(per["planes"], "errprof_s")), 5),
+                                       masked_share_of_events=round(v[m]["counters"]["n_masked_events"] / max(v["planes"]["sums"]["counts_sum"], 1), 5)) for m in MASK_MODES[1:]}
+    if args.parent_lib:
+        gap = e("planes") - e("parent_planes")
+        noise = max(spread(per["planes"], "errprof_s"), spread(per["parent_planes"], "errprof_s"))
+        res["unmasked_against_the_parent"] = dict(rule="a run without a mask pays nothing when the medians differ by less than the spread of the values", this_minus_parent_s=round(gap, 5),
+                                                  spread_s=round(noise, 5), unchanged=abs(gap) <= noise,
+                                                  counters_identical=v["planes"]["sums"]["counts_crc"] == v["parent_planes"]["sums"]["counts_crc"] and v["planes"]["counters"] == v["parent_planes"]["counters"])
+    for m in MASK_MODES[1:]:                                      # where fill_s goes: k_mask_fill's own time beside the host clock around set_mask
+        try:
+            v[m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
+        except SystemExit as e:                                   # (the timed rounds stand without the trace)
+            v[m]["kernels"] = dict(source="no kernel trace: %s" % e)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

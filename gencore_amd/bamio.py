@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp and bamio_fragerr.hpp (the last four over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp, bamio_fragerr.hpp and bamio_errsup.hpp (the last five over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -452,6 +452,57 @@ def error_profile_fragments_masked_bam(path, fasta, mask, bed=None, tsv=None, ov
         return ErrorProfileRun(r, m)
     finally:
         lib.gce_fragerr_free(C.byref(r))
+
+
+class ErrorProfileSupportRun:
+    """gce_errsup_run as an object: the counters and bytes as int, the times as float, and the numpy array counts ([3 segments, 33 forward
+    buckets, 33 reverse buckets, 24 classes], uint64: bucket 0 is an absent tag, 1..31 the value, 32 every other value; classes 0..20 are
+    ErrorProfileRun.CLASSES, 21 MASKED, 22 RECORDS, 23 zero).  With a mask, gce_mask_run's fields as ErrorProfileRun names them."""
+    CLASSES = ErrorProfileRun.CLASSES + ("MASKED", "RECORDS")
+
+    def __init__(self, r, mask=None):
+        from .capi import GCE_ERRPROF_CLASSES, GCE_ERRSUP_BUCKETS
+        for n, t in type(r)._fields_:
+            if n != "counts":
+                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+        if mask is not None:
+            for n, t in type(mask)._fields_:
+                setattr(self, {"n_intervals": "n_mask_intervals", "n_records": "n_mask_records"}.get(n, n), (float if t is C.c_double else int)(getattr(mask, n)))
+        shape = (3, GCE_ERRSUP_BUCKETS, GCE_ERRSUP_BUCKETS, GCE_ERRPROF_CLASSES)
+        self.counts = np.ctypeslib.as_array(r.counts, (int(np.prod(shape)),)).copy().reshape(shape)
+
+    def as_dict(self):
+        return {k: v for k, v in vars(self).items() if k != "counts"}
+
+
+def error_profile_support_bam(path, fasta, mask=None, bed=None, tsv=None, tags=("FR", "RR"), direct=False, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704,
+                              window_bytes=0, device_budget_bytes=0):
+    """gce_bam_error_profile_support: error_profile_bam's classes, walk, BED and (with `mask`, as error_profile_masked_bam takes it) variant
+    mask, tabulated not by cycle but by the support of each consensus record: f, the value of its first `tags[0]` field (FR, the forward-strand
+    reads merged into it), and r, that of its first `tags[1]` field (RR, written on duplex records alone), each as a bucket: 0 absent (or not
+    of an integer type), 1..31 the value, 32 every other value.  A run at -s 1 profiled this way shows the residual error of FR = 1 (no
+    consensus), 2, 3, ... and of duplex against single-strand records from one file: the choice of -s and of duplex-only.  Any BAM is taken;
+    tags=("aD", "bD") reads fgbio's duplex depths.  A record whose optional fields cannot be walked is counted in n_bad_aux and left out.
+    tsv: the table's path (segment, forward, reverse, records, bases, mismatches, the 21 counters, MASKED with a mask; one row per (segment,
+    forward, reverse) with a counter), or None.  direct=True makes every add a 64-bit global atomic instead of collecting a record's adds on
+    chip: the same counters.  Returns an ErrorProfileSupportRun (error_profile_bam's totals plus n_bad_aux, n_with_forward, n_with_reverse and
+    counts [3, 33, 33, 24]); raises GceError with the library's message (and leaves no table) on failure."""
+    from .capi import GCE_ERRSUP_DIRECT, GceErrsupRun, GceMaskRun
+    lib = capi.load_library()
+    r, m = GceErrsupRun(), GceMaskRun()
+    err = (C.c_char * 256)()
+    enc = lambda x: None if x is None else str(x).encode()
+    if isinstance(tags, (str, bytes)) or len(tags) != 2 or any(not isinstance(t, str) or len(t.encode("latin-1", "replace")) != 2 for t in tags):
+        raise ValueError("tags should be two two-character tags")
+    rc = lib.gce_bam_error_profile_support(str(path).encode(), str(fasta).encode(), enc(bed), enc(mask), enc(tsv), (tags[0] + tags[1]).encode("latin-1", "replace"), int(device), int(threads),
+                                           int(min_mapq), int(min_baseq), int(exclude_flags), GCE_ERRSUP_DIRECT if direct else 0, int(window_bytes), int(device_budget_bytes), C.byref(r),
+                                           None if mask is None else C.byref(m), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return ErrorProfileSupportRun(r, None if mask is None else m)
+    finally:
+        lib.gce_errsup_free(C.byref(r))
 
 
 def load_mask(path, names, lens, threads=0):

@@ -108,7 +108,8 @@ EXPORTED_SYMBOLS = [
     "gce_sam_format", "gce_raw_format_output", "gce_raw_read_text_async", "gce_get_sam_format_counters",
     "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free", "gce_bam_pileup_fragments", "gce_fragpile_free",
     "gce_bam_error_profile", "gce_errprof_free", "gce_bam_error_profile_fragments", "gce_fragerr_free",
-    "gce_mask_load", "gce_mask_free", "gce_bam_error_profile_masked", "gce_bam_error_profile_fragments_masked"]
+    "gce_mask_load", "gce_mask_free", "gce_bam_error_profile_masked", "gce_bam_error_profile_fragments_masked",
+    "gce_bam_error_profile_support", "gce_errsup_free"]
 
 GCE_PILEUP_DIRECT = 1
 GCE_FRAGPILE_DIRECT = 1
@@ -118,6 +119,8 @@ GCE_ERRPROF_MAX_CYCLE = 1024
 GCE_ERRPROF_CLASSES = 24
 GCE_FRAGERR_DIRECT = 1
 GCE_FRAGERR_WEAK_HASH = 2
+GCE_ERRSUP_DIRECT = 1
+GCE_ERRSUP_BUCKETS = 33
 
 
 class GceBamInfo(C.Structure):
@@ -205,6 +208,11 @@ class GceFragerrRun(C.Structure):
     """gce_fragerr_run (gce_bam_error_profile_fragments): gce_errprof_run's counters and times, rule M's and rule V's counters, the two tables."""
     _fields_ = GceErrprofRun._fields_[:-1] + [("n_pairs", C.c_int64), ("n_shared_columns", C.c_int64), ("n_disagree_columns", C.c_int64), ("n_ambiguous", C.c_int64),
                                               ("n_deferred", C.c_int64), ("counts", C.POINTER(C.c_uint64)), ("overlap", C.POINTER(C.c_uint64))]
+
+
+class GceErrsupRun(C.Structure):
+    """gce_errsup_run (gce_bam_error_profile_support): gce_errprof_run's fields with n_bad_aux behind the eight skips and the records that carry each tag."""
+    _fields_ = GceErrprofRun._fields_[:10] + [("n_bad_aux", C.c_int64), ("n_with_forward", C.c_int64), ("n_with_reverse", C.c_int64)] + GceErrprofRun._fields_[10:]
 
 
 class GceMask(C.Structure):
@@ -369,6 +377,11 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
                                                      C.c_uint64, C.c_size_t, C.POINTER(GceErrprofRun), C.POINTER(GceMaskRun), C.c_char_p]
         lib.gce_bam_error_profile_fragments_masked.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32,
                                                                C.c_uint32, C.c_uint32, C.c_uint64, C.c_size_t, C.POINTER(GceFragerrRun), C.POINTER(GceMaskRun), C.c_char_p]
+    if hasattr(lib, "gce_bam_error_profile_support"):                               # (the parent's build, loaded for an A/B run, lacks the pass)
+        lib.gce_bam_error_profile_support.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_uint32,
+                                                      C.c_uint32, C.c_uint64, C.c_size_t, C.POINTER(GceErrsupRun), C.POINTER(GceMaskRun), C.c_char_p]
+        lib.gce_errsup_free.argtypes = [C.POINTER(GceErrsupRun)]
+        lib.gce_errsup_free.restype = None
     lib.gce_depth_run_free.argtypes = [C.POINTER(GceDepthRun)]
     lib.gce_depth_run_free.restype = None
     lib.gce_bed_load.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

@@ -6,6 +6,7 @@ Stats summaries go to stderr and the JSON report is written (src/gencore.cpp:284
 Every check happens before the library is loaded, so a bad command line never touches a GPU."""
 import argparse
 import os
+import re
 import sys
 import time
 
@@ -56,6 +57,14 @@ show about each other at the positions both cover: segment, cycle, shared, error
 sequencing error, its partner reading the reference base; on it the partner's), then AGREE_REF, AGREE_ALT (both read the same base that is
 not the reference's: older than the sequencer, or a variant), DIFF_OTHER, UNUSABLE and LOWQ; a second line on STDERR gives the pairs, the
 shared columns and those that disagree.
+--error_profile_support FILE (not the reference's) answers how -s and --duplex_only should be set, from ONE run at -s 1: over the BAM output,
+on the GPU, it tabulates the same classes not by cycle but by the support of each consensus record, the FR tag (forward-strand reads merged
+into it) and the RR tag (reverse-strand reads; duplex records alone carry it).  A row: segment, forward, reverse (`.` for an absent tag, 1 ..
+31, `32+`), records, bases, mismatches, the sixteen A>A .. T>T, READ_N REF_OTHER LOWQ INS DEL, and MASKED with --error_profile_mask; the
+mismatches over the bases of the rows forward = 1, 2, 3, ... are the residual error a family of that size leaves, and the rows with a
+reverse count against those with `.` are duplex against single-strand.  It honours -b, --error_profile_mask, --error_profile_min_mapq and
+--error_profile_min_baseq; --error_profile_support_tags A,B reads two other integer tags (aD,bD: fgbio's duplex depths).  Every record is
+counted (overlapping mates twice), there is no cycle column and no split by read group.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -160,6 +169,14 @@ def build_parser():
     a("--error_profile_fragments", action="store_true",
       help="[gencore_amd] --error_profile / --error_profile_in count each fragment once where its mates overlap (the file must be coordinate-sorted) and write the mates' "
            "agreement by cycle to FILE.overlap.tsv beside each. Off by default.")
+    a("--error_profile_support", default=None, metavar="FILE",
+      help="[gencore_amd] after the output is written (after --calmd, beside --error_profile, before --index), count mismatches against -r over the BAM output by the support of "
+           "each consensus record -- its FR tag (forward-strand reads) and its RR tag (reverse-strand reads, on duplex records) -- on the GPU (on the first of --devices, within "
+           "--device_memory) and write the table to FILE: for choosing -s and --duplex_only from one run at -s 1. Honours -b, --error_profile_mask, --error_profile_min_mapq and "
+           "--error_profile_min_baseq. Off by default.")
+    a("--error_profile_support_tags", default="FR,RR", metavar="A,B",
+      help="[gencore_amd] --error_profile_support reads the forward count from tag A and the reverse count from tag B, two two-character tags of an integer type "
+           "(aD,bD: fgbio's duplex depths). Default FR,RR.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -298,8 +315,17 @@ def validate(o):
                 err("--error_profile_in needs BAM input, not SAM text")
     if o.error_profile_fragments and o.error_profile is None and o.error_profile_in is None:
         err("--error_profile_fragments needs --error_profile or --error_profile_in")
+    if o.error_profile_support is not None:
+        if o.output == "-":
+            err("--error_profile_support needs an output file, not STDOUT")
+        if o.output.endswith("sam"):
+            err("--error_profile_support needs BAM output, not SAM text")
+    if not re.fullmatch(r"[A-Za-z][A-Za-z0-9],[A-Za-z][A-Za-z0-9]", o.error_profile_support_tags):
+        err("--error_profile_support_tags needs two two-character tags, as in FR,RR")
+    if o.error_profile_support_tags != "FR,RR" and o.error_profile_support is None:
+        err("--error_profile_support_tags needs --error_profile_support")
     if o.error_profile_mask is not None:
-        if o.error_profile is None and o.error_profile_in is None:
+        if o.error_profile is None and o.error_profile_in is None and o.error_profile_support is None:
             err("--error_profile_mask needs --error_profile or --error_profile_in")
         check_file_valid(o.error_profile_mask)
         if not o.error_profile_mask.endswith((".vcf", ".vcf.gz", ".bed")):
@@ -405,6 +431,15 @@ def main(argv=None):
             pileup("pileup", o.output, o.pileup)
         if o.error_profile is not None:
             error_profile("error_profile", o.output, o.error_profile)
+        if o.error_profile_support is not None:
+            from .bamio import error_profile_support_bam
+            ft, rt = o.error_profile_support_tags.split(",")
+            r = error_profile_support_bam(o.output, o.ref, mask=o.error_profile_mask, bed=o.bed or None, tsv=o.error_profile_support, tags=(ft, rt), device=devices[0], threads=o.threads,
+                                          min_mapq=o.error_profile_min_mapq, min_baseq=o.error_profile_min_baseq, exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
+            sys.stderr.write("error_profile_support: %d records, %d eligible, %d bases, %d mismatches, %d with %s, %d with %s\n"
+                             % (r.n_records, r.n_eligible, r.n_bases, r.n_mismatches, r.n_with_forward, ft, r.n_with_reverse, rt))
+            if o.error_profile_mask is not None:
+                sys.stderr.write("error_profile_support: mask %d intervals, %d bases, %d events masked\n" % (r.n_mask_intervals, r.n_masked_bases, r.n_masked_events))
         if o.index:
             index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:

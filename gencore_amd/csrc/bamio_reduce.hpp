@@ -69,7 +69,8 @@ template <class P> MaskJob *mask_job(P &, long) { return nullptr; }
 //   bed_first                  the BED is the required file and checked first, the FASTA optional (else the other way round)
 //   out                        its gce_*_run: read_s, inflate_index_s, write_s, total_s and peak_device_bytes are the frame's to fill
 //   zero(), sites(in)          out as a call starts; what out says of the BED
-//   create, window, error, destroy, free_out   the entry points of its device object p (gce_entry.h) and the free of its gce_*_run
+//   create, window, error, destroy, free_out   the entry points of its device object p (gce_entry.h) and the free of its gce_*_run; create is called on
+//                              the pass, so one whose object takes more than the common arguments (gce_errsup's tags) has a member function
 //   set(in), pass_s()          p set up in front of the first window; where out keeps the seconds of the pass's kernels
 //   alloc(in), finish()         out's arrays; the counters into out
 //   table(in, to_file, emit)   rule O: the table through emit(buf), a piece or all at once; to_file: there is a file to write
@@ -155,7 +156,7 @@ template <class PASS> int reduce_run(PASS &ps, const char *bam_path, const char 
         mo->load_s = now_s() - t0;
     }
     (void)gce_device_bytes(nullptr, nullptr, 1);
-    int rc = PASS::create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, &ps.p);
+    int rc = ps.create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, &ps.p);
     if (rc != GCE_OK) return done(rc, "no HIP device");
     if ((rc = ps.set(ri)) != GCE_OK) return done(rc, PASS::error(ps.p));
     // ---- the file from its first byte, window by window: the host reads and finds the members, the GPU inflates, indexes and counts them

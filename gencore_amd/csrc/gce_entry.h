@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp (the last four over gce_reduce.hpp).  They are exported, but
+// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp, and the support-profile object of gce_errsup.hpp (the last five over gce_reduce.hpp).  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -18,6 +18,7 @@ struct gce_pileup;
 struct gce_fragpile;
 struct gce_errprof;
 struct gce_fragerr;
+struct gce_errsup;
 
 int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
 
@@ -119,6 +120,17 @@ int gce_fragerr_set_mask(gce_fragerr *p, int64_t n, const int32_t *tid, const in
 int gce_fragerr_window(gce_fragerr *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s);
 int gce_fragerr_finish(gce_fragerr *p, int64_t counters[15], uint64_t *counts_out, uint64_t *overlap_out);
+
+// ---- the error profile by consensus support, the FR / RR tags (gce_errsup.hpp)
+int gce_errsup_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, const char *tags, gce_errsup **out);
+void gce_errsup_destroy(gce_errsup *p);
+const char *gce_errsup_error(gce_errsup *p);
+int gce_errsup_set_ref(gce_errsup *p, int32_t n_ref, const char *const *seq, const int64_t *len);
+int gce_errsup_set_mask(gce_errsup *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_errsup_set_sites(gce_errsup *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_errsup_window(gce_errsup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                      int32_t n_ref, int32_t last, double *errprof_s);
+int gce_errsup_finish(gce_errsup *p, int64_t counters[11], uint64_t *counts_out);
 
 }  // extern "C"
 #endif

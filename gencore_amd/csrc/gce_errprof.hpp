@@ -251,7 +251,8 @@ struct gce_errprof : ReduceSession {
 };
 
 // The reference and rule B's intervals of a pass whose object T has gce_errprof's members (P, blob, tab, ref_bytes, ref_set, counts):
-// gce_errprof_set_ref / gce_errprof_set_sites and gce_fragerr.hpp's.  counts_bytes: the pass's counters
+// gce_errprof_set_ref / gce_errprof_set_sites, gce_fragerr.hpp's and gce_errsup.hpp's.  counts_bytes: the pass's counters; misc_words: the
+// scan's counters to start from zero, its NSKIP + 2
 template <class T> static int ep_set_ref(T *p, int32_t n_ref, const char *const *seq, const int64_t *len) {
     if (!p || p->ref_set || n_ref < 0 || (n_ref && (!seq || !len))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
@@ -264,14 +265,15 @@ template <class T> static int ep_set_ref(T *p, int32_t n_ref, const char *const 
     p->ref_set = true;
     return GCE_OK;
 }
-template <class T> static int ep_set_sites(T *p, const char *entry, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, uint64_t counts_bytes) {
+template <class T> static int ep_set_sites(T *p, const char *entry, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, uint64_t counts_bytes,
+                                           int misc_words = 10) {
     if (!p || !p->ref_set || p->sites_set || (n_intervals > 0 && (!tid || !start || !end))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     p->P.bed = n_intervals >= 0;
     RdTable t;
     const int rc = rd_intervals(p, entry, p->P.n_ref, std::max<int64_t>(n_intervals, 0), tid, start, end, t);
     if (rc != GCE_OK) return rc;
-    return rd_set_sites(p, t, p->counts, counts_bytes, 10);
+    return rd_set_sites(p, t, p->counts, counts_bytes, misc_words);
 }
 
 extern "C" {

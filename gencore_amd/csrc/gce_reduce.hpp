@@ -1,5 +1,5 @@
 // gce_reduce.hpp — what a windowed reduce pass is: the part gce_bam_pileup (gce_pileup.hpp) and gce_bam_error_profile
-// (gce_errprof.hpp) share, and what a third pass of their kind starts from.  Such a pass streams the file window by window
+// (gce_errprof.hpp) share, and what a third pass of their kind starts from (gce_errsup.hpp, DESIGN.md 4n, is one).  Such a pass streams the file window by window
 // (win_inflate_index / win_carry, gce_passes.hpp) and keeps nothing of a window but what it added to counters that stay on the device: per window
 // k_reduce_scan runs one thread per record over the pass's scan functor and leaves 4 bytes of meta per record, then the pass's own count kernels
 // walk the records the meta keeps.  reduce::rule_e (the malformed-record test and rule E) and rule S's interval table with its searches are

@@ -921,6 +921,42 @@ int gce_bam_error_profile_fragments_masked(const char *bam_path, const char *fas
                                            const char *tsv_path /* NULL: no file */, const char *overlap_tsv_path /* NULL: no file */, int32_t device, int threads, int32_t min_mapq,
                                            int32_t min_baseq, uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_fragerr_run *out,
                                            gce_mask_run *mask, char err[256]);
+/* The error profile by consensus support: residual error against the reference per (segment, forward reads, reverse reads), counted on ONE
+ * device (addition under ABI v3; gencore_amd/csrc/gce_errsup.hpp).  Replaces: nothing in the reference's source -- it reads
+ * back the FR:C and RR:C fields the reference writes on every consensus record (Pair::writeSscsDcsTagBam), which a user otherwise tabulates
+ * with a host script to choose -s and duplex-only: one run at -s 1, then this table.  One streaming pass over bam_path in any record order.
+ * Eligible records: gce_bam_error_profile's eight tests in its order, then n_bad_aux: the optional fields, from the end of QUAL to the end of
+ * the block, do not tile it (fewer than three bytes left, an unknown type or B subtype, a Z / H without its NUL, a value that passes the
+ * block's end); such a record is skipped, not refused.  Support: f from the first optional field whose tag is tags[0..1], r from the first
+ * whose tag is tags[2..3] (tags NULL: "FRRR"; "aDbD" reads fgbio's duplex depths).  A field of type c C s S i I has the value v its type's
+ * sign gives; the bucket is v for 1 <= v <= 31 and 32 for every other v (0 among them: the reference writes the low byte of the count, so 0
+ * stands for a multiple of 256 reads); no such field, or a first field of that tag with another type: bucket 0, absent.
+ * counts[((segment * 33 + f) * 33 + r) * 24 + class]: classes 0..20 and the walk, the BED and the mask exactly as gce_bam_error_profile and
+ * gce_bam_error_profile_masked have them, 21 MASKED (zero without mask_path), 22 RECORDS (one per eligible record; with a BED one per eligible
+ * record whose reference span, widened by one position at both ends, touches a region), 23 zero.  mask_path (NULL: no mask; else *mask is
+ * filled as gce_bam_error_profile_masked fills it and must not be NULL).  tsv_path (NULL: no file): a header line that begins with `#`, then
+ * one line per (segment, forward, reverse) with a counter that is not zero, in ascending order: segment, forward, reverse (`.` absent, 1..31,
+ * `32+`), records, bases (classes 0..15), mismatches (the off-diagonal ones), the sixteen A>A .. T>T, READ_N REF_OTHER LOWQ INS DEL, and
+ * MASKED with a mask; integers, no rates; written to a temporary name and renamed.  n_with_forward / n_with_reverse: RECORDS summed over
+ * f != 0 / r != 0.  options: GCE_ERRSUP_DIRECT makes every add a 64-bit global atomic instead of collecting a record's adds on chip: the same
+ * counters, the A/B partner of the default.  Device memory: the reference bases, 627 264 bytes of counters, the mask's bit per base, the
+ * interval table, one window and 4 bytes per window record, within device_budget_bytes (0: no limit), else GCE_ERR_OOM with that footprint.
+ * The refusals are gce_bam_error_profile's, and tags that are not four characters.  Not here: the once-per-fragment rule of
+ * gce_bam_error_profile_fragments, a cycle dimension, read groups, SAM text, several devices.  counts is malloc'ed: gce_errsup_free. */
+#define GCE_ERRSUP_DIRECT 1u
+#define GCE_ERRSUP_BUCKETS 33
+typedef struct gce_errsup_run {
+    int64_t n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar, n_no_ref, n_too_long, n_bad_aux;   /* n_eligible + the nine skips = n_records */
+    int64_t n_with_forward, n_with_reverse;
+    int64_t n_bases, n_mismatches, n_intervals /* -1: no BED */, peak_device_bytes;
+    double  read_s, inflate_index_s, errprof_s, write_s, total_s;   /* errprof_s: the scan and k_sup_count; write_s: the table */
+    uint64_t *counts;               /* [3 segments][33 forward][33 reverse][24 classes] */
+} gce_errsup_run;
+int gce_bam_error_profile_support(const char *bam_path, const char *fasta_path, const char *bed_path /* NULL: no BED */, const char *mask_path /* NULL: no mask */,
+                                  const char *tsv_path /* NULL: no file */, const char *tags /* NULL: "FRRR" */, int32_t device, int threads, int32_t min_mapq, int32_t min_baseq,
+                                  uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_errsup_run *out,
+                                  gce_mask_run *mask /* NULL without mask_path */, char err[256]);
+void gce_errsup_free(gce_errsup_run *out);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

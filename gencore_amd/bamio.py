@@ -333,6 +333,35 @@ def pileup_fragments_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, m
         lib.gce_fragpile_free(C.byref(r))
 
 
+def _copy_run_fields(obj, r, mask=None):
+    """The scalar fields of a gce_*_run onto obj, the counters and bytes as int, the times as float; with `mask`, gce_mask_run's fields too:
+    n_records and n_intervals are the BAM's and the BED's, so the mask's are n_mask_records and n_mask_intervals."""
+    for n, t in type(r)._fields_:
+        if n not in ("counts", "overlap"):
+            setattr(obj, n, (float if t is C.c_double else int)(getattr(r, n)))
+    if mask is not None:
+        for n, t in type(mask)._fields_:
+            setattr(obj, {"n_intervals": "n_mask_intervals", "n_records": "n_mask_records"}.get(n, n), (float if t is C.c_double else int)(getattr(mask, n)))
+
+
+def _error_profile_call(entry, run_type, wrap, free, paths, options, device, threads, min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes, masked=False):
+    """One error-profile entry point of the library: `paths` are its leading arguments (None for an optional path that is absent), behind
+    them the common ones, its gce_*_run, with `masked` a gce_mask_run, and err.  Returns wrap(run[, mask run]); the run's arrays
+    are freed with `free` either way."""
+    from .capi import GceMaskRun
+    lib = capi.load_library()
+    r, m = run_type(), GceMaskRun() if masked else None
+    err = (C.c_char * 256)()
+    rc = getattr(lib, entry)(*[None if x is None else str(x).encode() for x in paths], int(device), int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), int(options), int(window_bytes), int(device_budget_bytes),
+                             C.byref(r), *([C.byref(m)] if masked else []), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return wrap(r, m)
+    finally:
+        getattr(lib, free)(C.byref(r))
+
+
 class ErrorProfileRun:
     """gce_errprof_run as an object: the counters and bytes as int, the times as float, and the numpy array counts ([3 segments, 1024 cycles,
     24 classes], uint64: classes 0..15 are 4 r + b over A C G T in sequencing orientation, then READ_N REF_OTHER LOWQ INS DEL and three zeros)."""
@@ -340,12 +369,7 @@ class ErrorProfileRun:
 
     def __init__(self, r, mask=None):
         from .capi import GCE_ERRPROF_CLASSES, GCE_ERRPROF_MAX_CYCLE
-        for n, t in type(r)._fields_:
-            if n not in ("counts", "overlap"):
-                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
-        if mask is not None:                                                 # gce_mask_run's fields; n_records and n_intervals are the BAM's and the BED's: the mask's are n_mask_*
-            for n, t in type(mask)._fields_:
-                setattr(self, {"n_intervals": "n_mask_intervals", "n_records": "n_mask_records"}.get(n, n), (float if t is C.c_double else int)(getattr(mask, n)))
+        _copy_run_fields(self, r, mask)
         table = lambda p: np.ctypeslib.as_array(p, (3 * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES,)).copy().reshape(3, GCE_ERRPROF_MAX_CYCLE, GCE_ERRPROF_CLASSES)
         self.counts = table(r.counts)
         if hasattr(r, "overlap"):
@@ -365,18 +389,8 @@ def error_profile_bam(path, fasta, bed=None, tsv=None, device=0, threads=0, min_
     n_no_seq, n_bad_cigar, n_no_ref, n_too_long, n_bases, n_mismatches, n_intervals (-1 without a BED), peak_device_bytes, read_s,
     inflate_index_s, errprof_s, write_s, total_s, counts); raises GceError with the library's message (and leaves no table) on failure."""
     from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun
-    lib = capi.load_library()
-    r = GceErrprofRun()
-    err = (C.c_char * 256)()
-    rc = lib.gce_bam_error_profile(str(path).encode(), str(fasta).encode(), None if bed is None else str(bed).encode(), None if tsv is None else str(tsv).encode(), int(device),
-                                   int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), GCE_ERRPROF_DIRECT if direct else 0, int(window_bytes),
-                                   int(device_budget_bytes), C.byref(r), err)
-    if rc != 0:
-        raise GceError(rc, err.value.decode(errors="replace"))
-    try:
-        return ErrorProfileRun(r)
-    finally:
-        lib.gce_errprof_free(C.byref(r))
+    return _error_profile_call("gce_bam_error_profile", GceErrprofRun, ErrorProfileRun, "gce_errprof_free", (str(path), str(fasta), bed, tsv), GCE_ERRPROF_DIRECT if direct else 0, device, threads,
+                               min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes)
 
 
 def error_profile_masked_bam(path, fasta, mask, bed=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, window_bytes=0, device_budget_bytes=0):
@@ -386,19 +400,9 @@ def error_profile_masked_bam(path, fasta, mask, bed=None, tsv=None, device=0, th
     n_mismatches are then the sequencer's and the polymerase's, not the sample's genotype.  Returns an ErrorProfileRun with error_profile_bam's
     fields plus gce_mask_run's: n_lines, n_mask_records, n_unknown_contig, n_no_alt, n_mask_intervals, n_masked_bases, n_masked_events, load_s and
     fill_s."""
-    from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun, GceMaskRun
-    lib = capi.load_library()
-    r, m = GceErrprofRun(), GceMaskRun()
-    err = (C.c_char * 256)()
-    enc = lambda x: None if x is None else str(x).encode()
-    rc = lib.gce_bam_error_profile_masked(str(path).encode(), str(fasta).encode(), enc(bed), enc(mask), enc(tsv), int(device), int(threads), int(min_mapq), int(min_baseq),
-                                          int(exclude_flags), GCE_ERRPROF_DIRECT if direct else 0, int(window_bytes), int(device_budget_bytes), C.byref(r), C.byref(m), err)
-    if rc != 0:
-        raise GceError(rc, err.value.decode(errors="replace"))
-    try:
-        return ErrorProfileRun(r, m)
-    finally:
-        lib.gce_errprof_free(C.byref(r))
+    from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun
+    return _error_profile_call("gce_bam_error_profile_masked", GceErrprofRun, ErrorProfileRun, "gce_errprof_free", (str(path), str(fasta), bed, str(mask), tsv), GCE_ERRPROF_DIRECT if direct else 0, device,
+                               threads, min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes, masked=True)
 
 
 OVERLAP_CLASSES = ErrorProfileRun.CLASSES[:16] + ("AGREE_REF", "AGREE_ALT", "DIFF_OTHER", "UNUSABLE", "LOWQ")
@@ -417,19 +421,9 @@ def error_profile_fragments_bam(path, fasta, bed=None, tsv=None, overlap_tsv=Non
     ([3, 1024, 24], uint64); raises GceError with the library's message (and leaves no table) on failure, a record that lies in front of its
     predecessor among them."""
     from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun
-    lib = capi.load_library()
-    r = GceFragerrRun()
-    err = (C.c_char * 256)()
-    enc = lambda x: None if x is None else str(x).encode()
-    rc = lib.gce_bam_error_profile_fragments(str(path).encode(), str(fasta).encode(), enc(bed), enc(tsv), enc(overlap_tsv), int(device), int(threads), int(min_mapq), int(min_baseq),
-                                             int(exclude_flags), (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), int(window_bytes),
-                                             int(device_budget_bytes), C.byref(r), err)
-    if rc != 0:
-        raise GceError(rc, err.value.decode(errors="replace"))
-    try:
-        return ErrorProfileRun(r)
-    finally:
-        lib.gce_fragerr_free(C.byref(r))
+    return _error_profile_call("gce_bam_error_profile_fragments", GceFragerrRun, ErrorProfileRun, "gce_fragerr_free", (str(path), str(fasta), bed, tsv, overlap_tsv),
+                               (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
+                               device_budget_bytes)
 
 
 def error_profile_fragments_masked_bam(path, fasta, mask, bed=None, tsv=None, overlap_tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False,
@@ -438,20 +432,10 @@ def error_profile_fragments_masked_bam(path, fasta, mask, bed=None, tsv=None, ov
     one mate that is counted adds MASKED to counts and both add class 21, OVL_MASKED, to overlap; overlap.sum() is still twice
     n_shared_columns.  Both tables get the trailing MASKED column.  Returns error_profile_fragments_bam's ErrorProfileRun with
     error_profile_masked_bam's mask fields."""
-    from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun, GceMaskRun
-    lib = capi.load_library()
-    r, m = GceFragerrRun(), GceMaskRun()
-    err = (C.c_char * 256)()
-    enc = lambda x: None if x is None else str(x).encode()
-    rc = lib.gce_bam_error_profile_fragments_masked(str(path).encode(), str(fasta).encode(), enc(bed), enc(mask), enc(tsv), enc(overlap_tsv), int(device), int(threads), int(min_mapq),
-                                                    int(min_baseq), int(exclude_flags), (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0),
-                                                    int(window_bytes), int(device_budget_bytes), C.byref(r), C.byref(m), err)
-    if rc != 0:
-        raise GceError(rc, err.value.decode(errors="replace"))
-    try:
-        return ErrorProfileRun(r, m)
-    finally:
-        lib.gce_fragerr_free(C.byref(r))
+    from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun
+    return _error_profile_call("gce_bam_error_profile_fragments_masked", GceFragerrRun, ErrorProfileRun, "gce_fragerr_free", (str(path), str(fasta), bed, str(mask), tsv, overlap_tsv),
+                               (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
+                               device_budget_bytes, masked=True)
 
 
 class ErrorProfileSupportRun:
@@ -462,12 +446,7 @@ class ErrorProfileSupportRun:
 
     def __init__(self, r, mask=None):
         from .capi import GCE_ERRPROF_CLASSES, GCE_ERRSUP_BUCKETS
-        for n, t in type(r)._fields_:
-            if n != "counts":
-                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
-        if mask is not None:
-            for n, t in type(mask)._fields_:
-                setattr(self, {"n_intervals": "n_mask_intervals", "n_records": "n_mask_records"}.get(n, n), (float if t is C.c_double else int)(getattr(mask, n)))
+        _copy_run_fields(self, r, mask)
         shape = (3, GCE_ERRSUP_BUCKETS, GCE_ERRSUP_BUCKETS, GCE_ERRPROF_CLASSES)
         self.counts = np.ctypeslib.as_array(r.counts, (int(np.prod(shape)),)).copy().reshape(shape)
 

@@ -1,7 +1,7 @@
 // bamio_errsup.hpp -- the error profile by consensus support, the FR / RR tags: gce_bam_error_profile_support (gce_errsup.hpp).
-// A part of bamio.cpp: the pass's own part of reduce_run (bamio_reduce.hpp), which runs it.
+// A part of bamio.cpp: the pass's own part of reduce_run (bamio_reduce.hpp), which runs it, over bamio_errprof.hpp's ErrPass.
 #pragma once
-#include "bamio_reduce.hpp"
+#include "bamio_errprof.hpp"
 
 extern "C" {
 
@@ -23,27 +23,16 @@ inline bool errsup_tag_ok(const char *t) {
     return alpha(t[0]) && (alpha(t[1]) || (t[1] >= '0' && t[1] <= '9'));
 }
 
-struct ErrsupPass {
+struct ErrsupPass : ErrPass<ErrsupPass, gce_errsup_run, gce_errsup> {
     static constexpr const char *who = "gce_bam_error_profile_support", *options_known = "GCE_ERRSUP_DIRECT is the only one";
     static constexpr uint32_t option = GCE_ERRSUP_DIRECT;
-    static constexpr bool bed_first = false;
     static constexpr auto window = gce_errsup_window; static constexpr auto error = gce_errsup_error;
     static constexpr auto destroy = gce_errsup_destroy; static constexpr auto free_out = gce_errsup_free;
-    gce_errsup_run *out; const char *tags = nullptr; MaskJob mk{}; gce_errsup *p = nullptr;
+    static constexpr auto set_ref = gce_errsup_set_ref; static constexpr auto set_mask = gce_errsup_set_mask; static constexpr auto set_sites = gce_errsup_set_sites;
+    const char *tags = nullptr;
     int create(int32_t device, size_t budget, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errsup **o) const {
         return gce_errsup_create(device, budget, min_mapq, min_baseq, exclude_flags, options, tags, o);
     }
-    void zero() { memset(out, 0, sizeof *out); out->n_intervals = -1; }
-    void sites(const ReduceInput &in) { out->n_intervals = (int64_t)in.ps.tid.size(); }
-    // the reference bases go to the device and the host's copy is let go; then the mask and rule B's intervals
-    int set(ReduceInput &in) {
-        const int rc = gce_errsup_set_ref(p, in.n_ref, in.seq.data(), in.slen.data());
-        if (rc != GCE_OK) return rc;
-        gce_fasta_free(in.fa); in.fa = nullptr;
-        if (mk.on) { const int mrc = mk.fill([&](int64_t n, const int32_t *t, const int32_t *a, const int32_t *z) { return gce_errsup_set_mask(p, n, t, a, z); }); if (mrc != GCE_OK) return mrc; }
-        return gce_errsup_set_sites(p, in.has_bed ? (int64_t)in.ps.tid.size() : -1, in.ps.tid.data(), in.ps.start.data(), in.ps.end.data());
-    }
-    double *pass_s() { return &out->errprof_s; }
     bool alloc(const ReduceInput &) {
         out->counts = (uint64_t *)malloc((size_t)ERRSUP_ROWS * GCE_ERRPROF_CLASSES * 8);
         return out->counts != nullptr;
@@ -52,8 +41,7 @@ struct ErrsupPass {
         int64_t c[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         const int rc = gce_errsup_finish(p, c, out->counts);
         if (rc != GCE_OK) return rc;
-        out->n_records = c[0]; out->n_unplaced = c[1]; out->n_flagged = c[2]; out->n_low_mapq = c[3]; out->n_no_cigar = c[4]; out->n_no_seq = c[5]; out->n_bad_cigar = c[6];
-        out->n_no_ref = c[7]; out->n_too_long = c[8]; out->n_bad_aux = c[9]; out->n_eligible = c[10];
+        counters(c, 10); out->n_bad_aux = c[9];
         int64_t masked = 0;
         for (int row = 0; row < ERRSUP_ROWS; row++) {
             const uint64_t *k = out->counts + (size_t)row * GCE_ERRPROF_CLASSES;
@@ -69,8 +57,8 @@ struct ErrsupPass {
     template <class EMIT> bool table(const ReduceInput &, bool, EMIT &&emit) {
         std::string buf = "#segment\tforward\treverse\trecords\tbases\tmismatches";
         for (const char *r : {"A", "C", "G", "T"}) for (const char *b : {"A", "C", "G", "T"}) { buf += '\t'; buf += r; buf += '>'; buf += b; }
-        buf += mk.on ? "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\tMASKED\n" : "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\n";
-        const int n_cls = mk.on ? 22 : 21;
+        buf += tail();
+        const int n_cls = this->n_cls();
         auto bucket = [](char *w, int b) {
             if (b == 0) { *w++ = '.'; return w; }
             w = pile_num(w, (uint64_t)b);
@@ -105,7 +93,7 @@ int gce_bam_error_profile_support(const char *bam_path, const char *fasta_path, 
                                   int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_errsup_run *out,
                                   gce_mask_run *mask, char err[256]) {
     if (tags && (strlen(tags) != 4 || !errsup_tag_ok(tags) || !errsup_tag_ok(tags + 2))) { set_err(err, "tags should be two two-character tags, four characters"); return GCE_ERR_INVALID; }
-    ErrsupPass ps{out};
+    ErrsupPass ps{{out}};
     ps.tags = tags;
     if (mask_path) { ps.mk.on = true; ps.mk.path = mask_path; ps.mk.out = mask; }
     return reduce_run(ps, bam_path, bed_path, fasta_path, tsv_path, device, threads, min_mapq, min_baseq, exclude_flags, options, window_bytes, device_budget_bytes, err);

@@ -1,6 +1,7 @@
 // bamio_fragerr.hpp -- gce_bam_error_profile's table with every fragment counted once where its mates overlap, and the overlap table:
 // gce_bam_error_profile_fragments (gce_fragerr.hpp).  A part of bamio.cpp: the pass's own part of reduce_run
-// (bamio_reduce.hpp), which runs it and writes the primary table; the rows of both tables are bamio_errprof.hpp's.
+// (bamio_reduce.hpp), which runs it and writes the primary table; the rows of both tables and the runner's base (ErrPass) are
+// bamio_errprof.hpp's.
 #pragma once
 #include "bamio_errprof.hpp"
 
@@ -16,23 +17,13 @@ void gce_fragerr_free(gce_fragerr_run *out) {
 
 namespace {
 
-struct FragerrPass {
+struct FragerrPass : ErrPass<FragerrPass, gce_fragerr_run, gce_fragerr> {
     static constexpr const char *who = "gce_bam_error_profile_fragments", *options_known = "GCE_FRAGERR_DIRECT and GCE_FRAGERR_WEAK_HASH are the only ones";
     static constexpr uint32_t option = GCE_FRAGERR_DIRECT | GCE_FRAGERR_WEAK_HASH;
-    static constexpr bool bed_first = false;
     static constexpr auto create = gce_fragerr_create; static constexpr auto window = gce_fragerr_window; static constexpr auto error = gce_fragerr_error;
     static constexpr auto destroy = gce_fragerr_destroy; static constexpr auto free_out = gce_fragerr_free;
-    gce_fragerr_run *out; std::string ovl_tmp; MaskJob mk{}; gce_fragerr *p = nullptr;               // ovl_tmp: the overlap table's temporary name, empty for no file
-    void zero() { memset(out, 0, sizeof *out); out->n_intervals = -1; }
-    void sites(const ReduceInput &in) { out->n_intervals = (int64_t)in.ps.tid.size(); }
-    int set(ReduceInput &in) {
-        const int rc = gce_fragerr_set_ref(p, in.n_ref, in.seq.data(), in.slen.data());
-        if (rc != GCE_OK) return rc;
-        gce_fasta_free(in.fa); in.fa = nullptr;
-        if (mk.on) { const int mrc = mk.fill([&](int64_t n, const int32_t *t, const int32_t *a, const int32_t *z) { return gce_fragerr_set_mask(p, n, t, a, z); }); if (mrc != GCE_OK) return mrc; }
-        return gce_fragerr_set_sites(p, in.has_bed ? (int64_t)in.ps.tid.size() : -1, in.ps.tid.data(), in.ps.start.data(), in.ps.end.data());
-    }
-    double *pass_s() { return &out->errprof_s; }
+    static constexpr auto set_ref = gce_fragerr_set_ref; static constexpr auto set_mask = gce_fragerr_set_mask; static constexpr auto set_sites = gce_fragerr_set_sites;
+    std::string ovl_tmp;                                                              // the overlap table's temporary name, empty for no file
     bool alloc(const ReduceInput &) {
         const size_t bytes = (size_t)3 * GCE_ERRPROF_MAX_CYCLE * GCE_ERRPROF_CLASSES * 8;
         out->counts = (uint64_t *)malloc(bytes); out->overlap = (uint64_t *)malloc(bytes);
@@ -42,8 +33,7 @@ struct FragerrPass {
         int64_t c[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         const int rc = gce_fragerr_finish(p, c, out->counts, out->overlap);
         if (rc != GCE_OK) return rc;
-        out->n_records = c[0]; out->n_unplaced = c[1]; out->n_flagged = c[2]; out->n_low_mapq = c[3]; out->n_no_cigar = c[4]; out->n_no_seq = c[5]; out->n_bad_cigar = c[6];
-        out->n_no_ref = c[7]; out->n_too_long = c[8]; out->n_eligible = c[9];
+        counters(c, 9);
         out->n_pairs = c[10]; out->n_shared_columns = c[11]; out->n_disagree_columns = c[12]; out->n_ambiguous = c[13]; out->n_deferred = c[14];
         if (mk.on) mk.out->n_masked_events = MaskJob::events(out->counts);
         return GCE_OK;
@@ -51,14 +41,12 @@ struct FragerrPass {
     // rule O for the primary table through the frame; the overlap table to its temporary name, which the entry point renames
     template <class EMIT> bool table(const ReduceInput &, bool, EMIT &&emit) {
         std::string buf;
-        errprof_table(out->counts, "bases", "mismatches", mk.on ? "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\tMASKED\n" : "\tREAD_N\tREF_OTHER\tLOWQ\tINS\tDEL\n", 16, out->n_bases, out->n_mismatches, buf,
-                      mk.on ? 22 : 21);
+        errprof_table(out->counts, "bases", "mismatches", tail(), 16, out->n_bases, out->n_mismatches, buf, n_cls());
         if (!emit(buf)) return false;
         if (ovl_tmp.empty()) return true;
         int64_t shared = 0, errors = 0;
         buf.clear();
-        errprof_table(out->overlap, "shared", "errors", mk.on ? "\tAGREE_REF\tAGREE_ALT\tDIFF_OTHER\tUNUSABLE\tLOWQ\tMASKED\n" : "\tAGREE_REF\tAGREE_ALT\tDIFF_OTHER\tUNUSABLE\tLOWQ\n", 19, shared, errors,
-                      buf, mk.on ? 22 : 21);
+        errprof_table(out->overlap, "shared", "errors", tail(true), 19, shared, errors, buf, n_cls());
         FILE *fo = fopen(ovl_tmp.c_str(), "wb");
         if (!fo) return false;
         const bool wrote = fwrite(buf.data(), 1, buf.size(), fo) == buf.size();
@@ -74,7 +62,7 @@ namespace {
 int fragerr_run(const char *bam_path, const char *fasta_path, const char *bed_path, bool masked, const char *mask_path, const char *tsv_path, const char *overlap_tsv_path, int32_t device,
                 int threads, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_fragerr_run *out,
                 gce_mask_run *mask, char err[256]) {
-    FragerrPass ps{out, overlap_tsv_path ? std::string(overlap_tsv_path) + ".tmp" + std::to_string((long long)getpid()) : std::string()};
+    FragerrPass ps{{out}, overlap_tsv_path ? std::string(overlap_tsv_path) + ".tmp" + std::to_string((long long)getpid()) : std::string()};
     ps.mk.on = masked; ps.mk.path = mask_path; ps.mk.out = mask;
     int rc = reduce_run(ps, bam_path, bed_path, fasta_path, tsv_path, device, threads, min_mapq, min_baseq, exclude_flags, options, window_bytes, device_budget_bytes, err);
     if (!overlap_tsv_path) return rc;

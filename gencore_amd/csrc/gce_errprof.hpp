@@ -20,7 +20,10 @@
 // (rule Y): k_err_count<DIRECT, errprof::Mask>, the same walk with one bit test per event.
 // errprof::scan_record and errprof::count_record are __host__ __device__: tests/errprof_host_check.hip runs them on the host against
 // tests/pyerrprof.py, the model of the rules.  What the pass shares with gce_bam_pileup -- rule E, the interval table, the scan kernel and the
-// device object -- is gce_reduce.hpp's.
+// device object -- is gce_reduce.hpp's.  What it shares with gce_fragerr.hpp (4l) and gce_errsup.hpp (4n) is here, once: the CIGAR walk
+// (errprof::walk_record, which calls a functor at every column of an M / = / X op; count_record is the walk under rule W's functor), the
+// classes of a reference base, a read base and a counted base, the device object's base (ErrSession, with the one choice of a count kernel's
+// instantiation), the add of the planes (ErrAdd) and ep_set_ref / ep_set_sites / ep_finish; ep_set_mask is gce_varmask.hpp's.
 #pragma once
 #include <cstdint>
 #include "gce_reduce.hpp"
@@ -77,26 +80,65 @@ EP_HD bool mask_at(const Mask &M, int64_t base, int64_t rlen, int64_t a) {
     return (M.bits[i >> 3] >> (i & 7u)) & 1u;
 }
 
-// Rule W for an eligible record whose scan gave `first`, by lane `lane` of the record's `nlanes`: the lanes stride over the columns of each
-// M / = / X op and over the bases of each I op, lane 0 takes the deletions.  add(row, cls): counter row * 24 + cls += 1, row = segment * 1024
-// + cycle - 1 < 3072, cls < 21.  Reads stay inside the record (the scan checked its fields against block_size, the CIGAR's query length
-// against l_seq and l_seq against 1024) and inside the contig's [0, length).  MASK: rule Y is on and M holds the bitmap (cls is then < 22);
-// off, M is not read and the code is the walk without a mask: count_record below gives both their names.
-template <bool MASK, class ADD> EP_HD void walk_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add,
-                                                       const Mask &M) {
-    const uint8_t *c = r + 4;
-    const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
-    const uint32_t lq = c[8], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
-    const uint8_t *cg = c + 32 + lq, *sq = cg + 4 * nc, *ql = sq + ((uint32_t)lseq + 1) / 2;
-    const bool rev = (flag & 16u) != 0, has_q = ql[0] != 0xFF;
-    const uint32_t seg = (flag & 0xC0u) == 0x40u ? 1u : (flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
-    const uint32_t tend = P.bed ? S.tfirst[tid + 1] : 0u;
-    const int64_t rbase = ref.tab[2 * tid];
-    const uint8_t *rb = ref.blob + rbase; const int64_t rlen = ref.tab[2 * tid + 1];
-    uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
-#define EP_CYC0(y) (rev ? (uint32_t)lseq - 1u - (y) : (y))                             // rule C, less one
-    for (uint32_t k = 0; k < nc; k++) {
-        const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
+// The fields of a record (r at its block_size) that the walks read, decoded once: walk_record for the record it walks, Cursor
+// (gce_fragerr.hpp) for the partner
+struct Head {
+    const uint8_t *cg, *sq, *ql; int32_t tid, pos, lseq; uint32_t nc, flag; bool has_q;
+    EP_HD explicit Head(const uint8_t *r) {
+        const uint8_t *c = r + 4;
+        tid = (int32_t) * (const ep_u32u *)(c + 0); pos = (int32_t) * (const ep_u32u *)(c + 4); lseq = (int32_t) * (const ep_u32u *)(c + 16);
+        nc = *(const ep_u16u *)(c + 12); flag = *(const ep_u16u *)(c + 14);
+        cg = c + 32 + c[8]; sq = cg + 4 * nc; ql = sq + ((uint32_t)lseq + 1) / 2;
+        has_q = ql[0] != 0xFF;
+    }
+};
+// the class of a reference base (rb: the contig's bases, rlen of them) and of a read's 4-bit base: 0..3 = A C G T, 4 = anything else
+EP_HD uint32_t ref_class(const uint8_t *rb, int64_t rlen, int64_t col) {
+    if (col >= rlen) return 4u;
+    const uint8_t b = rb[col] & 0xDFu;
+    return b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u;
+}
+EP_HD uint32_t read_class(const uint8_t *sq, uint32_t yi) {
+    const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
+    return nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
+}
+// the class of a reference base rc against a read's base bc in sequencing orientation: 4 r + b for two usable bases, cls < 18
+EP_HD uint32_t base_class(uint32_t rc, uint32_t bc, bool rev) {
+    return rc > 3 ? (uint32_t)EP_REF_OTHER : bc > 3 ? (uint32_t)EP_READ_N : rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
+}
+// One column of an M / = / X op as the walk hands it to its functor: the reference position x, the query index yi, the counter row (segment *
+// 1024 + cycle - 1) and rule Y's bit (false without a mask).  Nothing of the read or the reference is loaded until a functor asks: q() the
+// base's quality (0 for a record without qualities), rc() and bc() the classes of the reference base and the read's.
+// EP_PRIMARY(c, P, at_q, rc, bc): the class in the primary table of column c's base when it counts at quality at_q.  MASKED stands in front
+// of LOWQ (the position's property, not the read's) and both in front of the bases; a macro, so that rc and bc may be the calls c.rc() and
+// c.bc(), evaluated for a base that is neither
+struct Column {
+    const uint8_t *rb, *sq, *ql; int64_t rlen, x; uint32_t yi, row; bool has_q, rev, masked;
+    EP_HD uint32_t q() const { return has_q ? ql[yi] : 0u; }
+    EP_HD uint32_t rc() const { return ref_class(rb, rlen, x); }
+    EP_HD uint32_t bc() const { return read_class(sq, yi); }
+    EP_HD bool lowq(const Params &P, uint32_t at_q) const { return has_q && (int32_t)at_q < P.min_baseq; }
+};
+#define EP_PRIMARY(c, P, at_q, rc, bc) ((c).masked ? EP_MASKED : (c).lowq(P, at_q) ? (uint32_t)EP_LOWQ : base_class(rc, bc, (c).rev))
+
+// The one CIGAR walk of the error profile, for an eligible record whose scan gave `first`, by lane `lane` of the record's `nlanes`: the lanes
+// stride over the columns of each M / = / X op and over the bases of each I op, lane 0 takes the deletions.  at(P, column) is what happens at
+// one column of an M / = / X op: rule W's ColumnW below, rules X and V' in gce_fragerr.hpp's MateColumn.  at.add(row, cls): counter
+// row * 24 + cls += 1 for an insertion or a deletion, row < 3072.  Reads stay inside the record (the scan checked its fields against
+// block_size, the CIGAR's query length against l_seq and l_seq against 1024) and inside the contig's [0, length).  MASK: rule Y is on and M
+// holds the bitmap (cls is then < 22); off, M is not read and the code is the walk without a mask.
+template <bool MASK, class AT> EP_HD void walk_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, AT &at,
+                                                      const Mask &M) {
+    const Head h(r);
+    const bool rev = (h.flag & 16u) != 0;
+    const uint32_t seg = (h.flag & 0xC0u) == 0x40u ? 1u : (h.flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
+    const uint32_t tend = P.bed ? S.tfirst[h.tid + 1] : 0u;
+    const int64_t rbase = ref.tab[2 * h.tid];
+    const uint8_t *rb = ref.blob + rbase; const int64_t rlen = ref.tab[2 * h.tid + 1];
+    uint32_t cur = first, q = 0; int64_t x = h.pos; bool seen = false;
+#define EP_CYC0(y) (rev ? (uint32_t)h.lseq - 1u - (y) : (y))                           // rule C, less one
+    for (uint32_t k = 0; k < h.nc; k++) {
+        const uint32_t w = *(const ep_u32u *)(h.cg + 4 * k), op = w & 15u, len = w >> 4;
         if (op == 0 || op == 7 || op == 8) {
             const int64_t xe = x + len;
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
@@ -109,43 +151,41 @@ template <bool MASK, class ADD> EP_HD void walk_record(const uint8_t *r, const P
                 }
                 for (int64_t col = a + lane; col < z; col += nlanes) {
                     const uint32_t yi = q + (uint32_t)(col - x);
-                    uint32_t cls;
-                    if (MASK && mask_at(M, rbase, rlen, col)) cls = EP_MASKED;        // (in front of LOWQ: the position's property, not the read's)
-                    else if (has_q && (int32_t)ql[yi] < P.min_baseq) cls = EP_LOWQ;
-                    else {
-                        uint32_t rc = 4;
-                        if (col < rlen) { const uint8_t b = rb[col] & 0xDFu; rc = b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; }
-                        const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u, bc = nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
-                        cls = rc > 3 ? (uint32_t)EP_REF_OTHER : bc > 3 ? (uint32_t)EP_READ_N : rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
-                    }
-                    add(row0 + EP_CYC0(yi), cls);
+                    at(P, Column{rb, h.sq, h.ql, rlen, col, yi, row0 + EP_CYC0(yi), h.has_q, rev, MASK && mask_at(M, rbase, rlen, col)});
                 }
                 if (!P.bed) break;
             }
             x = xe; q += len; seen = true;
         } else if (op == 2) {
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), MASK && mask_at(M, rbase, rlen, x) ? EP_MASKED : (uint32_t)EP_DEL);
+            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) at.add(row0 + EP_CYC0(q ? q - 1u : 0u), MASK && mask_at(M, rbase, rlen, x) ? EP_MASKED : (uint32_t)EP_DEL);
             x += len; seen = true;
         } else if (op == 3) x += len;
         else if (op == 1) {
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
             if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x)) {
                 const uint32_t cls = MASK && mask_at(M, rbase, rlen, seen ? x - 1 : x) ? EP_MASKED : (uint32_t)EP_INS;
-                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), cls);
+                for (uint32_t j = lane; j < len; j += nlanes) at.add(row0 + EP_CYC0(q + j), cls);
             }
             q += len;
         } else if (op == 4) q += len;
     }
 #undef EP_CYC0
 }
+// rule W at one column: the base's class, cls < 21 (< 22 with a mask)
+template <class ADD> struct ColumnW {
+    ADD &add;
+    EP_HD void operator()(const Params &P, const Column &c) { add(c.row, EP_PRIMARY(c, P, c.q(), c.rc(), c.bc())); }
+};
 // rule W alone, and rules W and Y under the bitmap M
 template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
-    walk_record<false>(r, P, ref, S, first, lane, nlanes, add, Mask{nullptr});
+    ColumnW<ADD> at{add};
+    walk_record<false>(r, P, ref, S, first, lane, nlanes, at, Mask{nullptr});
 }
 template <class ADD> EP_HD void count_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add,
                                              const Mask &M) {
-    walk_record<true>(r, P, ref, S, first, lane, nlanes, add, M);
+    ColumnW<ADD> at{add};
+    walk_record<true>(r, P, ref, S, first, lane, nlanes, at, M);
 }
 
 #undef EP_HD
@@ -179,6 +219,24 @@ static_assert(EP_PLANES * EP_PLANE * 4u <= EP_LDS_PER_CU / EP_BLOCKS_PER_CU, "k_
 static_assert(EP_CLS == (unsigned)errprof::EP_NCLASS && (EP_CLS & 1u) && EP_CYC <= EP_MAX_CYCLE && EP_STEP_RECS * 16u == EP_THREADS, "k_err_count's layout");
 
 #ifndef GCE_ERRPROF_HOST_CHECK
+
+// The device object of an error-profile pass: what gce_errprof, gce_fragerr (gce_fragerr.hpp) and gce_errsup (gce_errsup.hpp) hold alike.
+// needs() stays the pass's own.
+struct ErrSession : ReduceSession {
+    errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
+    DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
+    DevBuf counts;                                                                    // the pass's 64-bit totals
+    DevBuf mask; uint64_t mask_bytes = 0;                                             // rule Y's bitmap (gce_varmask.hpp); 0 bytes: no mask
+    calmd::Ref ref() const { return calmd::Ref{blob.as<uint8_t>(), tab.as<int64_t>(), P.n_ref}; }
+    // The instantiation of a count kernel k<DIRECT, MASK...> for (direct_now, a mask or none): launch(std::bool_constant<DIRECT>, the
+    // errprof::Mask or nothing) names the kernel as k<decltype(D)::value, decltype(m)...> and hands it m... behind its other arguments
+    template <class LAUNCH> void dispatch(bool direct_now, LAUNCH &&launch) const {
+        const errprof::Mask M{mask.as<uint8_t>()};
+        if (mask_bytes) { if (direct_now) launch(std::true_type{}, M); else launch(std::false_type{}, M); }
+        else if (direct_now) launch(std::true_type{});
+        else launch(std::false_type{});
+    }
+};
 #include "gce_varmask.hpp"
 
 namespace {
@@ -191,26 +249,16 @@ struct ErrScan {
     __device__ void operator()(const uint8_t *r, uint64_t avail, Rec &R) const { errprof::scan_record(r, avail, P, ref, S, R); }
 };
 
-// an add of k_err_count: into the record slot's plane when the cycle lies in it, else to memory
-template <bool DIRECT> struct ErrAdd {
+// an add of k_err_count and k_fragerr_count: into the plane when the cycle lies in it, else to memory.  MASK: MASKED goes to memory, whatever
+// its cycle
+template <bool DIRECT, bool MASK> struct ErrAdd {
     uint32_t *plane; unsigned long long *counts;
     __device__ __forceinline__ void operator()(uint32_t row, uint32_t cls) {
         const uint32_t c0 = row & (EP_MAX_CYCLE - 1u);
-        if (!DIRECT && c0 < EP_CYC) atomicAdd(plane + ((row >> 10) * EP_CYC + c0) * EP_CLS + cls, 1u);
+        if (!DIRECT && c0 < EP_CYC && (!MASK || cls != EP_MASKED)) atomicAdd(plane + ((row >> 10) * EP_CYC + c0) * EP_CLS + cls, 1u);
         else atomicAdd(counts + row * EP_ROW + cls, 1ull);
     }
 };
-// ... with a variant mask: MASKED goes to memory, whatever its cycle
-template <bool DIRECT> struct ErrAddMasked {
-    uint32_t *plane; unsigned long long *counts;
-    __device__ __forceinline__ void operator()(uint32_t row, uint32_t cls) {
-        const uint32_t c0 = row & (EP_MAX_CYCLE - 1u);
-        if (!DIRECT && c0 < EP_CYC && cls != EP_MASKED) atomicAdd(plane + ((row >> 10) * EP_CYC + c0) * EP_CLS + cls, 1u);
-        else atomicAdd(counts + row * EP_ROW + cls, 1ull);
-    }
-};
-template <bool DIRECT, bool MASK> struct ErrAddOf { typedef ErrAdd<DIRECT> type; };
-template <bool DIRECT> struct ErrAddOf<DIRECT, true> { typedef ErrAddMasked<DIRECT> type; };
 // 16 lanes per record, 32 records per step; block b takes the records [32 (b + k gridDim.x), + 32) of the window, k = 0, 1, ...
 // MASK: none, or one errprof::Mask for rule Y
 template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) void k_err_count(const uint8_t *u, const uint64_t *off, uint64_t n, errprof::Params P, calmd::Ref ref, reduce::Sites S,
@@ -221,7 +269,7 @@ template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) v
         for (uint32_t i = threadIdx.x; i < EP_PLANES * EP_PLANE; i += EP_THREADS) s_tab[i] = 0u;
         __syncthreads();
     }
-    typename ErrAddOf<DIRECT, sizeof...(MASK) != 0>::type add{s_tab + (DIRECT ? 0u : (slot & (EP_PLANES - 1u)) * EP_PLANE), counts};
+    ErrAdd<DIRECT, sizeof...(MASK) != 0> add{s_tab + (DIRECT ? 0u : (slot & (EP_PLANES - 1u)) * EP_PLANE), counts};
     for (uint64_t j = (uint64_t)blockIdx.x * EP_STEP_RECS + slot; j < n; j += (uint64_t)gridDim.x * EP_STEP_RECS) {
         const uint32_t first = meta[j];
         if (first != EP_NONE) errprof::count_record(u + off[j], P, ref, S, first, sub, 16u, add, mask...);
@@ -240,20 +288,15 @@ template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) v
 
 }  // namespace
 
-struct gce_errprof : ReduceSession {
-    errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
-    DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
-    DevBuf counts;                                                                    // EP_COUNTERS 64-bit totals
-    DevBuf mask; uint64_t mask_bytes = 0;                                             // rule Y's bitmap (gce_varmask.hpp); 0 bytes: no mask
+struct gce_errprof : ErrSession {
     std::string needs() const override {
         return "gce_bam_error_profile needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 576 KiB of counters" + varmask_needs(mask_bytes);
     }
 };
 
-// The reference and rule B's intervals of a pass whose object T has gce_errprof's members (P, blob, tab, ref_bytes, ref_set, counts):
-// gce_errprof_set_ref / gce_errprof_set_sites, gce_fragerr.hpp's and gce_errsup.hpp's.  counts_bytes: the pass's counters; misc_words: the
-// scan's counters to start from zero, its NSKIP + 2
-template <class T> static int ep_set_ref(T *p, int32_t n_ref, const char *const *seq, const int64_t *len) {
+// The reference and rule B's intervals of an error-profile pass: gce_errprof_set_ref / gce_errprof_set_sites, gce_fragerr.hpp's and
+// gce_errsup.hpp's.  counts_bytes: the pass's counters; misc_words: the scan's counters to start from zero, its NSKIP + 2
+static int ep_set_ref(ErrSession *p, int32_t n_ref, const char *const *seq, const int64_t *len) {
     if (!p || p->ref_set || n_ref < 0 || (n_ref && (!seq || !len))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     std::vector<int64_t> tab;
@@ -265,8 +308,7 @@ template <class T> static int ep_set_ref(T *p, int32_t n_ref, const char *const 
     p->ref_set = true;
     return GCE_OK;
 }
-template <class T> static int ep_set_sites(T *p, const char *entry, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, uint64_t counts_bytes,
-                                           int misc_words = 10) {
+static int ep_set_sites(ErrSession *p, const char *entry, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, uint64_t counts_bytes, int misc_words = 10) {
     if (!p || !p->ref_set || p->sites_set || (n_intervals > 0 && (!tid || !start || !end))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     p->P.bed = n_intervals >= 0;
@@ -274,6 +316,20 @@ template <class T> static int ep_set_sites(T *p, const char *entry, int64_t n_in
     const int rc = rd_intervals(p, entry, p->P.n_ref, std::max<int64_t>(n_intervals, 0), tid, start, end, t);
     if (rc != GCE_OK) return rc;
     return rd_set_sites(p, t, p->counts, counts_bytes, misc_words);
+}
+// After the last window, behind rd_finish: counters[0] records, [1..nskip] the skip counters in the pass's order, [nskip + 1] eligible; then
+// the pass's tables, `bytes` each, one behind the other in p->counts
+static int ep_finish(ErrSession *p, int nskip, int64_t *counters, std::initializer_list<uint64_t *> tables, uint64_t bytes) {
+    (void)hipSetDevice(p->device);
+    hipStream_t s = p->s;
+    unsigned long long h[RD_MISC_WORDS];
+    const int rc = rd_finish(p, nskip, counters, h, nskip + 2);
+    if (rc != GCE_OK) return rc;
+    const uint8_t *src = p->counts.as<uint8_t>();
+    for (uint64_t *t : tables) { RDCHK(hipMemcpyAsync(t, src, bytes, hipMemcpyDeviceToHost, s)); src += bytes; }
+    RDCHK(hipStreamSynchronize(s));
+    RDCHK(hipGetLastError());
+    return GCE_OK;
 }
 
 extern "C" {
@@ -302,18 +358,14 @@ int gce_errprof_set_mask(gce_errprof *p, int64_t n, const int32_t *tid, const in
 int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s) {
     if (!p) return GCE_ERR_INVALID;
-    const calmd::Ref ref{p->blob.as<uint8_t>(), p->tab.as<int64_t>(), p->P.n_ref};
+    const calmd::Ref ref = p->ref();
     const reduce::Sites S = p->sites();
     return rd_window(p, ErrScan{p->P, ref, S}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, errprof_s, [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end) {
         const unsigned nb = (unsigned)std::min<uint64_t>((n_rec + EP_STEP_RECS - 1) / EP_STEP_RECS, EP_GRID);
-        unsigned long long *counts = p->counts.as<unsigned long long>();
-        const bool direct = p->direct || (end >> 32);
-        if (p->mask_bytes) {
-            const errprof::Mask M{p->mask.as<uint8_t>()};
-            if (direct) hipLaunchKernelGGL((k_err_count<true, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts, M);
-            else hipLaunchKernelGGL((k_err_count<false, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts, M);
-        } else if (direct) hipLaunchKernelGGL(k_err_count<true>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
-        else hipLaunchKernelGGL(k_err_count<false>, dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p, counts);
+        p->dispatch(p->direct || (end >> 32), [&](auto D, auto... m) {
+            hipLaunchKernelGGL((k_err_count<decltype(D)::value, decltype(m)...>), dim3(nb), dim3(EP_THREADS), 0, p->s, u, off, n_rec, p->P, ref, S, (const uint32_t *)p->meta.p,
+                               p->counts.as<unsigned long long>(), m...);
+        });
         return true;
     });
 }
@@ -322,14 +374,7 @@ int gce_errprof_window(gce_errprof *p, const void *comp, size_t comp_bytes, int3
 // 3 x 1024 x 24 uint64
 int gce_errprof_finish(gce_errprof *p, int64_t counters[10], uint64_t *counts_out) {
     if (!p || !p->sites_set || !counters || !counts_out) return GCE_ERR_INVALID;
-    (void)hipSetDevice(p->device);
-    hipStream_t s = p->s;
-    unsigned long long h[10];
-    const int rc = rd_finish(p, ErrScan::NSKIP, counters, h, 10);
-    if (rc != GCE_OK) return rc;
-    RDCHK(hipMemcpyAsync(counts_out, p->counts.p, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
-    RDCHK(hipGetLastError());
-    return GCE_OK;
+    return ep_finish(p, ErrScan::NSKIP, counters, {counts_out}, EP_COUNTERS * 8ull);
 }
 
 }  // extern "C"

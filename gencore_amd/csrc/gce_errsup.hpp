@@ -3,7 +3,7 @@
 // Every consensus record this library writes carries FR:C, the forward-strand reads merged into it, and a duplex record RR:C as well (quirk
 // A11).  A run at -s 1 followed by this pass gives the residual error of every (FR, RR) from one file: how many reads a family needs, and
 // whether both strands are needed.  The pass is gce_bam_error_profile's (gce_errprof.hpp) with another row: rule E with a
-// ninth skip, rules W, B and Y (the walk, the BED, the variant mask) unchanged -- errprof::walk_record as it is -- and the counter
+// ninth skip, rules W, B and Y (the walk, the BED, the variant mask) unchanged -- errprof::count_record as it is -- and the counter
 //   counts[((segment * 33 + f) * 33 + r) * 24 + class]        3 x 33 x 33 x 24 64-bit totals, 627 264 bytes
 // where f and r are rule U's buckets of the forward and the reverse tag: 0 absent, 1..31 the value, 32 anything else.  Class 21 is MASKED as
 // in 4m, class 22 RECORDS (one per eligible record the scan keeps), class 23 zero.
@@ -94,7 +94,7 @@ ES_HD uint32_t segment(const uint8_t *r) {
 // the row of an eligible record, < ES_ROWS
 ES_HD uint32_t row_of(const uint8_t *r, const Support &s) { return (segment(r) * ES_BUCKETS + s.f) * ES_BUCKETS + s.r; }
 
-// Rule W (and Y, with a mask) for a record the scan kept, by lane `lane` of `nlanes`: errprof::walk_record with its row dropped, since every
+// Rule W (and Y, with a mask) for a record the scan kept, by lane `lane` of `nlanes`: errprof::count_record with its row dropped, since every
 // add of the record goes to the record's own row.  add(cls): the record's counter of class cls += 1, cls < 22; lane 0 adds RECORDS.
 template <class ADD> struct RowAdd {
     ADD &add;
@@ -219,12 +219,8 @@ template <bool DIRECT, class... MASK> __global__ __launch_bounds__(ES_THREADS) v
 
 }  // namespace
 
-struct gce_errsup : ReduceSession {
-    errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
+struct gce_errsup : ErrSession {                                                      // counts: ES_COUNTERS totals
     errsup::Tags T{0, 0};
-    DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
-    DevBuf counts;                                                                    // ES_COUNTERS 64-bit totals
-    DevBuf mask; uint64_t mask_bytes = 0;                                             // rule Y's bitmap (gce_varmask.hpp); 0 bytes: no mask
     std::string needs() const override {
         return "gce_bam_error_profile_support needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + " + std::to_string(ES_COUNTERS * 8ull) + " bytes of counters" +
                varmask_needs(mask_bytes);
@@ -258,19 +254,14 @@ int gce_errsup_set_sites(gce_errsup *p, int64_t n_intervals, const int32_t *tid,
 int gce_errsup_window(gce_errsup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                       int32_t n_ref, int32_t last, double *errprof_s) {
     if (!p) return GCE_ERR_INVALID;
-    const calmd::Ref ref{p->blob.as<uint8_t>(), p->tab.as<int64_t>(), p->P.n_ref};
+    const calmd::Ref ref = p->ref();
     const reduce::Sites S = p->sites();
     return rd_window(p, SupScan{p->P, p->T, ref, S}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, errprof_s, [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end) {
         const unsigned nb = (unsigned)std::min<uint64_t>((n_rec + ES_STEP_RECS - 1) / ES_STEP_RECS, ES_GRID);
-        unsigned long long *counts = p->counts.as<unsigned long long>();
-        const uint32_t *meta = (const uint32_t *)p->meta.p;
-        const bool direct = p->direct || (end >> 32);
-        if (p->mask_bytes) {
-            const errprof::Mask M{p->mask.as<uint8_t>()};
-            if (direct) hipLaunchKernelGGL((k_sup_count<true, errprof::Mask>), dim3(nb), dim3(ES_THREADS), 0, p->s, u, off, n_rec, p->P, p->T, ref, S, meta, counts, M);
-            else hipLaunchKernelGGL((k_sup_count<false, errprof::Mask>), dim3(nb), dim3(ES_THREADS), 0, p->s, u, off, n_rec, p->P, p->T, ref, S, meta, counts, M);
-        } else if (direct) hipLaunchKernelGGL(k_sup_count<true>, dim3(nb), dim3(ES_THREADS), 0, p->s, u, off, n_rec, p->P, p->T, ref, S, meta, counts);
-        else hipLaunchKernelGGL(k_sup_count<false>, dim3(nb), dim3(ES_THREADS), 0, p->s, u, off, n_rec, p->P, p->T, ref, S, meta, counts);
+        p->dispatch(p->direct || (end >> 32), [&](auto D, auto... m) {
+            hipLaunchKernelGGL((k_sup_count<decltype(D)::value, decltype(m)...>), dim3(nb), dim3(ES_THREADS), 0, p->s, u, off, n_rec, p->P, p->T, ref, S, (const uint32_t *)p->meta.p,
+                               p->counts.as<unsigned long long>(), m...);
+        });
         return true;
     });
 }
@@ -279,14 +270,7 @@ int gce_errsup_window(gce_errsup *p, const void *comp, size_t comp_bytes, int32_
 // 3 x 33 x 33 x 24 uint64
 int gce_errsup_finish(gce_errsup *p, int64_t counters[11], uint64_t *counts_out) {
     if (!p || !p->sites_set || !counters || !counts_out) return GCE_ERR_INVALID;
-    (void)hipSetDevice(p->device);
-    hipStream_t s = p->s;
-    unsigned long long h[SupScan::NSKIP + 2];
-    const int rc = rd_finish(p, SupScan::NSKIP, counters, h, SupScan::NSKIP + 2);
-    if (rc != GCE_OK) return rc;
-    RDCHK(hipMemcpyAsync(counts_out, p->counts.p, ES_COUNTERS * 8ull, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
-    RDCHK(hipGetLastError());
-    return GCE_OK;
+    return ep_finish(p, SupScan::NSKIP, counters, {counts_out}, ES_COUNTERS * 8ull);
 }
 
 }  // extern "C"

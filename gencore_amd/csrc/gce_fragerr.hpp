@@ -7,8 +7,9 @@
 // made a sequencing error at which cycle).  Per window, behind the scan (k_reduce_scan over ErrScan) and the join:
 //   k_fragerr_count  k_err_count's shape: 16 lanes per entry, 32 entries per step of a block of 512 threads, a fixed grid whose blocks stride
 //                    over the entries.  errprof::count_record for an entry without partner, nothing for a deferred one,
-//                    errprof::paired_walk for a mate: it walks its own columns with an errprof::Cursor over the partner's CIGAR, which only
-//                    moves forward, so a lane reads every op of the partner once per record, not once per column.  One LDS plane for the
+//                    errprof::paired_walk for a mate: gce_errprof.hpp's walk_record under the functor MateColumn, which at every column of
+//                    the mate's own asks an errprof::Cursor over the partner's CIGAR; the cursor only moves forward, so a lane reads every
+//                    op of the partner once per record, not once per column.  One LDS plane for the
 //                    primary table and one for the overlap table; cycles past EP_CYC are 64-bit global atomics.  k_fragerr_count<true>
 //                    (GCE_FRAGERR_DIRECT): global atomics only.
 // errprof::Cursor and errprof::paired_walk are __host__ __device__: tests/fragerr_host_check.hip runs them on the host against
@@ -32,13 +33,9 @@ static_assert((unsigned)OVL_NCLASS == EP_CLS, "the overlap table has the primary
 struct Cursor {
     const uint8_t *cg, *sq, *ql; uint32_t nc, k, q0; int64_t x0; bool has_q;
     EP_HD explicit Cursor(const uint8_t *o) {
-        const uint8_t *c = o + 4;
-        const int32_t lseq = (int32_t) * (const ep_u32u *)(c + 16);
-        const uint32_t lq = c[8];
-        nc = *(const ep_u16u *)(c + 12);
-        cg = c + 32 + lq; sq = cg + 4 * nc; ql = sq + ((uint32_t)lseq + 1) / 2;
-        has_q = ql[0] != 0xFF;
-        k = 0; q0 = 0; x0 = (int32_t) * (const ep_u32u *)(c + 4);
+        const Head h(o);
+        cg = h.cg; sq = h.sq; ql = h.ql; nc = h.nc; has_q = h.has_q;
+        k = 0; q0 = 0; x0 = h.pos;
     }
     EP_HD bool at(int64_t x, uint32_t &cls, uint32_t &q) {
         if (x < x0) return false;                                                     // (in front of pos: x0 never passes an x that was asked for)
@@ -46,8 +43,8 @@ struct Cursor {
             const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
             if (op == 0 || op == 7 || op == 8) {
                 if (x < x0 + len) {
-                    const uint32_t yi = q0 + (uint32_t)(x - x0), nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
-                    cls = nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
+                    const uint32_t yi = q0 + (uint32_t)(x - x0);
+                    cls = read_class(sq, yi);
                     q = has_q ? ql[yi] : 0u;
                     return true;
                 }
@@ -61,93 +58,49 @@ struct Cursor {
     }
 };
 
-// Rules W, V' and X for a mate r of a pair whose other mate is o, by lane `lane` of the record's `nlanes`, as count_record walks a record
-// alone.  is_b: r is the later of the two in the file.  A column that an M / = / X op of o covers is shared: add2(row, cls) takes r's count
-// of rule X, and add(row, cls) r's count of rule V' if r is the one rule V' counts.  Every other column, every insertion and every deletion is
-// rule W's.  shared, differ: rule V's counters, added to by the later mate's walk alone.  MASK: rule Y is on and M holds the bitmap: at a
-// masked shared column both mates add OVL_MASKED to the overlap table and the mate rule V' counts adds MASKED to the primary one, so the
-// fragment is still counted once and shared / differ are what they are without a mask.  Off, M is not read: paired_walk below names both.
-template <bool MASK, class ADD, class ADD2> EP_HD void paired_walk_record(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S,
-                                                                          uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ, const Mask &M) {
-    const uint8_t *c = r + 4;
-    const int32_t tid = (int32_t) * (const ep_u32u *)(c + 0), pos = (int32_t) * (const ep_u32u *)(c + 4), lseq = (int32_t) * (const ep_u32u *)(c + 16);
-    const uint32_t lq = c[8], nc = *(const ep_u16u *)(c + 12), flag = *(const ep_u16u *)(c + 14);
-    const uint8_t *cg = c + 32 + lq, *sq = cg + 4 * nc, *ql = sq + ((uint32_t)lseq + 1) / 2;
-    const bool rev = (flag & 16u) != 0, has_q = ql[0] != 0xFF;
-    const uint32_t seg = (flag & 0xC0u) == 0x40u ? 1u : (flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
-    const uint32_t tend = P.bed ? S.tfirst[tid + 1] : 0u;
-    const int64_t rbase = ref.tab[2 * tid];
-    const uint8_t *rb = ref.blob + rbase; const int64_t rlen = ref.tab[2 * tid + 1];
-    Cursor oc(o);
-    uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
-#define EP_CYC0(y) (rev ? (uint32_t)lseq - 1u - (y) : (y))                             // rule C, less one
-    for (uint32_t k = 0; k < nc; k++) {
-        const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
-        if (op == 0 || op == 7 || op == 8) {
-            const int64_t xe = x + len;
-            if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            for (uint32_t j = cur;; j++) {                                            // the op's columns, or with a BED their part in every interval
-                int64_t a = x, z = xe;
-                if (P.bed) {
-                    if (j >= tend || (int64_t)S.iv[j].start >= xe) break;
-                    const reduce::Ivl v = S.iv[j];
-                    a = x > v.start ? x : (int64_t)v.start; z = xe < v.end ? xe : (int64_t)v.end;
-                }
-                for (int64_t col = a + lane; col < z; col += nlanes) {
-                    const uint32_t yi = q + (uint32_t)(col - x), row = row0 + EP_CYC0(yi);
-                    const uint32_t mq = has_q ? ql[yi] : 0u;
-                    uint32_t rc = 4;
-                    if (col < rlen) { const uint8_t b = rb[col] & 0xDFu; rc = b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; }
-                    const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u, bc = nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
-                    uint32_t ob = 0, oq = 0, adj = mq;
-                    const bool mk = MASK && mask_at(M, rbase, rlen, col);
-                    if (oc.at(col, ob, oq)) {
-                        // ---- rule X: this mate's count in the overlap table
-                        uint32_t xc;
-                        if ((has_q && (int32_t)mq < P.min_baseq) || (oc.has_q && (int32_t)oq < P.min_baseq)) xc = OVL_LOWQ;
-                        else if (bc > 3 || ob > 3 || rc > 3) xc = OVL_UNUSABLE;
-                        else if (bc == ob) xc = bc == rc ? (uint32_t)OVL_AGREE_REF : (uint32_t)OVL_AGREE_ALT;
-                        else if (ob == rc || bc == rc) xc = rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
-                        else xc = OVL_DIFF_OTHER;
-                        add2(row, mk ? OVL_MASKED : xc);
-                        // ---- rule V': which of the two the primary table counts, and at which quality
-                        const uint32_t qa = is_b ? oq : mq, qb = is_b ? mq : oq;
-                        bool mine;
-                        if (bc == ob) { mine = !is_b; adj = qa + qb < FP_Q_CAP ? qa + qb : FP_Q_CAP; }
-                        else { mine = is_b ? qa < qb : qa >= qb; adj = (4u * mq) / 5u; }
-                        if (is_b) { shared++; differ += bc != ob; }
-                        if (!mine) continue;
-                    }
-                    const uint32_t cls = mk ? EP_MASKED : has_q && (int32_t)adj < P.min_baseq ? (uint32_t)EP_LOWQ
-                                         : rc > 3 ? (uint32_t)EP_REF_OTHER : bc > 3 ? (uint32_t)EP_READ_N : rev ? 4u * (3u - rc) + (3u - bc) : 4u * rc + bc;
-                    add(row, cls);
-                }
-                if (!P.bed) break;
-            }
-            x = xe; q += len; seen = true;
-        } else if (op == 2) {
-            if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (lane == 0 && (!P.bed || in_sites(S, cur, tend, x))) add(row0 + EP_CYC0(q ? q - 1u : 0u), MASK && mask_at(M, rbase, rlen, x) ? EP_MASKED : (uint32_t)EP_DEL);
-            x += len; seen = true;
-        } else if (op == 3) x += len;
-        else if (op == 1) {
-            if (P.bed) cur = reduce::seek(S, cur, tend, x);
-            if (!P.bed || in_sites(S, cur, tend, seen ? x - 1 : x)) {
-                const uint32_t cls = MASK && mask_at(M, rbase, rlen, seen ? x - 1 : x) ? EP_MASKED : (uint32_t)EP_INS;
-                for (uint32_t j = lane; j < len; j += nlanes) add(row0 + EP_CYC0(q + j), cls);
-            }
-            q += len;
-        } else if (op == 4) q += len;
+// Rules W, V' and X at one column of a mate r of a pair whose other mate is o: walk_record's functor (gce_errprof.hpp), so that r is walked
+// as count_record walks a record alone.  is_b: r is the later of the two in the file.  A column that an M / = / X op of o covers is shared:
+// add2(row, cls) takes r's count of rule X, and add(row, cls) r's count of rule V' if r is the one rule V' counts.  Every other column, every
+// insertion and every deletion is rule W's.  shared, differ: rule V's counters, added to by the later mate's walk alone.  Under a mask (rule
+// Y, the column's `masked`) both mates add OVL_MASKED to the overlap table at a masked shared column and the mate rule V' counts adds MASKED
+// to the primary one, so the fragment is still counted once and shared / differ are what they are without a mask.
+template <class ADD, class ADD2> struct MateColumn {
+    ADD &add; ADD2 &add2; Cursor oc; bool is_b; uint32_t &shared, &differ;
+    EP_HD void operator()(const Params &P, const Column &c) {
+        uint32_t ob = 0, oq = 0;
+        const bool both = oc.at(c.x, ob, oq);                                         // (in front of this mate's loads: its base is not live across the cursor's loop)
+        const uint32_t mq = c.q(), rc = c.rc(), bc = c.bc();
+        uint32_t adj = mq;
+        if (both) {
+            // ---- rule X: this mate's count in the overlap table
+            uint32_t xc;
+            if (c.lowq(P, mq) || (oc.has_q && (int32_t)oq < P.min_baseq)) xc = OVL_LOWQ;
+            else if (bc > 3 || ob > 3 || rc > 3) xc = OVL_UNUSABLE;
+            else if (bc == ob) xc = bc == rc ? (uint32_t)OVL_AGREE_REF : (uint32_t)OVL_AGREE_ALT;
+            else if (ob == rc || bc == rc) xc = base_class(rc, bc, c.rev);
+            else xc = OVL_DIFF_OTHER;
+            add2(c.row, c.masked ? OVL_MASKED : xc);
+            // ---- rule V': which of the two the primary table counts, and at which quality
+            const uint32_t qa = is_b ? oq : mq, qb = is_b ? mq : oq;
+            bool mine;
+            if (bc == ob) { mine = !is_b; adj = qa + qb < FP_Q_CAP ? qa + qb : FP_Q_CAP; }
+            else { mine = is_b ? qa < qb : qa >= qb; adj = (4u * mq) / 5u; }
+            if (is_b) { shared++; differ += bc != ob; }
+            if (!mine) return;
+        }
+        add(c.row, EP_PRIMARY(c, P, adj, rc, bc));
     }
-#undef EP_CYC0
-}
+};
+// without a mask (M is not read), and under the bitmap M
 template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first,
                                                         uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ) {
-    paired_walk_record<false>(r, o, is_b, P, ref, S, first, lane, nlanes, add, add2, shared, differ, Mask{nullptr});
+    MateColumn<ADD, ADD2> at{add, add2, Cursor(o), is_b, shared, differ};
+    walk_record<false>(r, P, ref, S, first, lane, nlanes, at, Mask{nullptr});
 }
 template <class ADD, class ADD2> EP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first,
                                                         uint32_t lane, uint32_t nlanes, ADD &add, ADD2 &add2, uint32_t &shared, uint32_t &differ, const Mask &M) {
-    paired_walk_record<true>(r, o, is_b, P, ref, S, first, lane, nlanes, add, add2, shared, differ, M);
+    MateColumn<ADD, ADD2> at{add, add2, Cursor(o), is_b, shared, differ};
+    walk_record<true>(r, P, ref, S, first, lane, nlanes, at, M);
 }
 
 #undef EP_HD
@@ -189,7 +142,7 @@ template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) v
         for (uint32_t i = threadIdx.x; i < 2 * EP_PLANE; i += EP_THREADS) s_tab[i] = 0u;
         __syncthreads();
     }
-    typename ErrAddOf<DIRECT, sizeof...(MASK) != 0>::type add{s_tab, counts}, add2{s_tab + (DIRECT ? 0u : EP_PLANE), ovl};
+    ErrAdd<DIRECT, sizeof...(MASK) != 0> add{s_tab, counts}, add2{s_tab + (DIRECT ? 0u : EP_PLANE), ovl};
     uint32_t shared = 0, differ = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * EP_STEP_RECS + slot; e < V.n; e += (uint64_t)gridDim.x * EP_STEP_RECS) {
         const uint32_t pc = partner[e];
@@ -220,32 +173,24 @@ template <bool DIRECT, class... MASK> __global__ __launch_bounds__(EP_THREADS) v
 
 }  // namespace
 
-struct gce_fragerr : ReduceSession {
-    errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;
-    DevBuf blob, tab; uint64_t ref_bytes = 0; bool ref_set = false;                   // calmd::Ref
-    DevBuf counts;                                                                    // two blocks of EP_COUNTERS 64-bit totals: the primary table, the overlap table
-    DevBuf mask; uint64_t mask_bytes = 0;                                             // rule Y's bitmap (gce_varmask.hpp); 0 bytes: no mask
+struct gce_fragerr : ErrSession {                                                     // counts: two blocks of EP_COUNTERS totals, the primary table and the overlap table
     MateJoin J; int cb_rc = GCE_OK;
     std::string needs() const override {
         return "gce_bam_error_profile_fragments needs the reference bases (" + std::to_string(ref_bytes) + " bytes) + 1152 KiB of counters, a join table (" + std::to_string(J.table_bytes()) +
                " bytes) and an arena (" + std::to_string(J.arena_bytes()) + " bytes)" + varmask_needs(mask_bytes);
     }
-    calmd::Ref ref() const { return calmd::Ref{blob.as<uint8_t>(), tab.as<int64_t>(), P.n_ref}; }
     int process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, bool final);
 };
 
 // One join (MateJoin::run) with k_fragerr_count between join and carry.  end: the bytes of the window
 int gce_fragerr::process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t end, bool final) {
     const bool wide = ((end + J.arena[J.cur].cap) >> 32) != 0;                        // (the no-wrap argument of the planes does not hold)
-    return J.run(this, "gce_bam_error_profile_fragments", FragerrRead{P}, u, off, n_rec, final, [&](const FragView &V, uint64_t N, const uint32_t *first, const uint32_t *partner, unsigned long long *m) {
+    return J.run(this, "gce_bam_error_profile_fragments", FragerrRead{P}, u, off, n_rec, final, [&](const FragView &V, uint64_t N, const uint32_t *first, const uint32_t *partner, unsigned long long *fm) {
         const unsigned nb = (unsigned)std::min<uint64_t>((N + EP_STEP_RECS - 1) / EP_STEP_RECS, EP_GRID);
         unsigned long long *c = counts.as<unsigned long long>();
-        if (mask_bytes) {
-            const errprof::Mask M{mask.as<uint8_t>()};
-            if (direct || wide) hipLaunchKernelGGL((k_fragerr_count<true, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m, M);
-            else hipLaunchKernelGGL((k_fragerr_count<false, errprof::Mask>), dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m, M);
-        } else if (direct || wide) hipLaunchKernelGGL(k_fragerr_count<true>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
-        else hipLaunchKernelGGL(k_fragerr_count<false>, dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, m);
+        dispatch(direct || wide, [&](auto D, auto... m) {
+            hipLaunchKernelGGL((k_fragerr_count<decltype(D)::value, decltype(m)...>), dim3(nb), dim3(EP_THREADS), 0, s, V, P, ref(), sites(), first, partner, c, c + EP_COUNTERS, fm, m...);
+        });
         return true;
     });
 }
@@ -304,14 +249,10 @@ int gce_fragerr_finish(gce_fragerr *p, int64_t counters[15], uint64_t *counts_ou
     hipStream_t s = p->s;
     int rc = p->process(nullptr, nullptr, 0, 0, true);
     if (rc != GCE_OK) return rc;
-    unsigned long long h[10], f[FM_WORDS];
-    if ((rc = rd_finish(p, ErrScan::NSKIP, counters, h, 10)) != GCE_OK) return rc;
-    RDCHK(hipMemcpyAsync(f, p->J.fm.p, sizeof f, hipMemcpyDeviceToHost, s));
-    RDCHK(hipMemcpyAsync(counts_out, p->counts.p, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s));
-    RDCHK(hipMemcpyAsync(overlap_out, p->counts.as<uint8_t>() + EP_COUNTERS * 8ull, EP_COUNTERS * 8ull, hipMemcpyDeviceToHost, s));
-    RDCHK(hipStreamSynchronize(s));
+    if ((rc = ep_finish(p, ErrScan::NSKIP, counters, {counts_out, overlap_out}, EP_COUNTERS * 8ull)) != GCE_OK) return rc;
+    unsigned long long f[FM_WORDS];
+    RDCHK(hipMemcpyAsync(f, p->J.fm.p, sizeof f, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
     counters[10] = (int64_t)f[FM_PAIRS]; counters[11] = (int64_t)f[FM_SHARED]; counters[12] = (int64_t)f[FM_DIFFER]; counters[13] = (int64_t)f[FM_AMBIG]; counters[14] = (int64_t)f[FM_DEFER];
-    RDCHK(hipGetLastError());
     return GCE_OK;
 }
 

@@ -1,4 +1,4 @@
-// gce_varmask.hpp — the variant mask of the error profile on the device (gce_errprof_set_mask, gce_fragerr_set_mask).
+// gce_varmask.hpp — the variant mask of the error profile on the device (gce_errprof_set_mask, gce_fragerr_set_mask, gce_errsup_set_mask).
 //
 // After consensus the residual error rate is 1e-5 to 1e-6 per base and a germline SNP comes once in a thousand bases, so without a mask the
 // off-diagonal counters of gce_bam_error_profile are the sample's genotype.  The mask is one bit per byte of calmd::Ref's blob: the bit of
@@ -64,9 +64,9 @@ __global__ __launch_bounds__(VM_THREADS) void k_mask_fill(const int32_t *tid, co
 
 }  // namespace
 
-// gce_errprof_set_mask / gce_fragerr_set_mask for a pass whose object T has gce_errprof's members (ref_set, ref_bytes, tab, P, mask,
-// mask_bytes): the first call makes and zeroes the bitmap, every call ORs its intervals in, VM_CHUNK of them per launch
-template <class T> static int ep_set_mask(T *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end) {
+// gce_errprof_set_mask / gce_fragerr_set_mask / gce_errsup_set_mask over the passes' ErrSession (gce_errprof.hpp, which includes this file
+// behind it): the first call makes and zeroes the bitmap, every call ORs its intervals in, VM_CHUNK of them per launch
+static int ep_set_mask(ErrSession *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end) {
     if (!p || !p->ref_set || p->n || n < 0 || (n > 0 && (!tid || !start || !end))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     hipStream_t s = p->s;
@@ -93,7 +93,7 @@ template <class T> static int ep_set_mask(T *p, int64_t n, const int32_t *tid, c
             const uint32_t m = (uint32_t)std::min<int64_t>(n - k, (int64_t)cap);
             RDCHK(hipMemcpyAsync(dt, tid + k, (size_t)m * 4, hipMemcpyHostToDevice, s)); RDCHK(hipMemcpyAsync(da, start + k, (size_t)m * 4, hipMemcpyHostToDevice, s));
             RDCHK(hipMemcpyAsync(dz, end + k, (size_t)m * 4, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_mask_fill, dim3((m + VM_BLOCK_IVS - 1) / VM_BLOCK_IVS), dim3(VM_THREADS), 0, s, dt, da, dz, m, p->tab.template as<int64_t>(), p->P.n_ref, p->mask.template as<uint32_t>(),
+            hipLaunchKernelGGL(k_mask_fill, dim3((m + VM_BLOCK_IVS - 1) / VM_BLOCK_IVS), dim3(VM_THREADS), 0, s, dt, da, dz, m, p->tab.as<int64_t>(), p->P.n_ref, p->mask.as<uint32_t>(),
                                p->ref_bytes);
             RDCHK(hipGetLastError()); RDCHK(hipStreamSynchronize(s));
         }

@@ -12,12 +12,12 @@ process of its own, gives the kernel times.  There is no pass mark.
     python tools/errprof_bench.py --fragments [--parent_lib PATH] [--out profiles/errprof_fragments.json]
 runs gce_bam_error_profile_fragments (frag_planes, frag_direct) beside gce_bam_error_profile (planes, direct) on the same file,
 without a BED, in the same interleaved way.  With --parent_lib, the library built from the parent commit (loaded through GCE_LIB) runs in the
-same rounds: its gce_bam_error_profile (parent_planes) is the comparison partner, and its gce_bam_pileup_fragments (parent_pileup_fragments)
-stands beside this tree's (pileup_fragments), whose join moved into gce_matejoin.hpp: pileup_s is unchanged when the two medians differ by
-less than the spread of the values.
+same rounds: its gce_bam_error_profile (parent_planes) is the comparison partner, its gce_bam_error_profile_fragments (parent_frag_planes)
+stands beside this tree's frag_planes, and its gce_bam_pileup_fragments (parent_pileup_fragments) beside this tree's (pileup_fragments),
+whose join is gce_matejoin.hpp's: errprof_s and pileup_s are unchanged when the two medians differ by less than the spread of the values.
     python tools/errprof_bench.py --mask [--parent_lib PATH] [--out profiles/errprof_mask.json]
 runs gce_bam_error_profile_masked beside gce_bam_error_profile on the same file, without a BED, in the same interleaved way:
-planes (the unmasked entry point of this build), parent_planes (with --parent_lib: the unmasked entry point of the parent commit's library,
+planes (the unmasked entry point of this build), parent_planes and parent_mask_vcf (with --parent_lib: the parent commit's library,
 through GCE_LIB), mask_vcf (a synthetic VCF of one SNP per 1000 reference bases) and mask_bed (a BED mask of about 10 % of the reference in
 1 kb blocks).  It reports errprof_s, fill_s, load_s and peak_device_bytes, whether planes differs from parent_planes by more than the spread
 of the values (a run without a mask is to pay nothing), and what the two masks cost over planes; one rocprofv3 --kernel-trace --stats run per masked variant, each in a process of
@@ -37,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 MODES = ("planes", "direct", "planes_bed", "direct_bed", "index")
 FRAG_MODES = ("planes", "frag_planes", "direct", "frag_direct")
-PARENT_MODES = ("parent_planes", "pileup_fragments", "parent_pileup_fragments")
+PARENT_MODES = ("parent_planes", "parent_frag_planes", "pileup_fragments", "parent_pileup_fragments")
 MASK_MODES = ("planes", "mask_vcf", "mask_bed")
 
 
@@ -49,25 +49,26 @@ def child(args):
         with open(p, "rb") as f:
             while f.read(1 << 26):
                 pass
+    mode = args.mode[len("parent_"):] if args.mode.startswith("parent_") else args.mode   # (the parent's library is GCE_LIB's doing, run_child)
     t0 = time.perf_counter()
-    if args.mode == "index":
+    if mode == "index":
         d = bamio.index_bam(src, os.path.join(args.child, "in.bam.bai"), threads=args.threads)
         d = {k: v for k, v in (d if isinstance(d, dict) else vars(d)).items() if isinstance(v, (int, float))}
-    elif args.mode.endswith("pileup_fragments"):
+    elif mode.endswith("pileup_fragments"):
         r = bamio.pileup_fragments_bam(src, bed, threads=args.threads)
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())))
-    elif args.mode.startswith("mask_"):
-        r = bamio.error_profile_masked_bam(src, fa, os.path.join(args.child, "mask.vcf" if args.mode == "mask_vcf" else "mask.bed"), tsv=os.path.join(args.child, "%s.tsv" % args.mode),
+    elif mode.startswith("mask_"):
+        r = bamio.error_profile_masked_bam(src, fa, os.path.join(args.child, "mask.vcf" if mode == "mask_vcf" else "mask.bed"), tsv=os.path.join(args.child, "%s.tsv" % args.mode),
                                            threads=args.threads)
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())), rows_sum_crc=int(zlib.crc32(r.counts.sum(axis=2).tobytes())))
-    elif args.mode.startswith("frag_"):
+    elif mode.startswith("frag_"):
         r = bamio.error_profile_fragments_bam(src, fa, tsv=os.path.join(args.child, "%s.tsv" % args.mode), overlap_tsv=os.path.join(args.child, "%s.overlap.tsv" % args.mode),
-                                              threads=args.threads, direct=args.mode.endswith("direct"))
+                                              threads=args.threads, direct=mode.endswith("direct"))
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())), overlap_sum=int(r.overlap.sum()),
                  overlap_crc=int(zlib.crc32(r.overlap.tobytes())))
     else:
-        r = bamio.error_profile_bam(src, fa, bed=bed if args.mode.endswith("_bed") else None, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads,
-                                    direct="direct" in args.mode)
+        r = bamio.error_profile_bam(src, fa, bed=bed if mode.endswith("_bed") else None, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads,
+                                    direct="direct" in mode)
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(zlib.crc32(r.counts.tobytes())), rows_sum_crc=int(zlib.crc32(r.counts.sum(axis=2).tobytes())))
     print(json.dumps(dict(d, wall_s=time.perf_counter() - t0)), flush=True)
 
@@ -155,7 +156,7 @@ def main():
     ap.add_argument("--limit", type=int, default=300)
     ap.add_argument("--direct_limit", type=int, default=900)
     ap.add_argument("--child", default=None)
-    ap.add_argument("--mode", default="planes", choices=("make",) + MODES + FRAG_MODES[1::2] + PARENT_MODES + MASK_MODES[1:])
+    ap.add_argument("--mode", default="planes", choices=("make",) + MODES + FRAG_MODES[1::2] + PARENT_MODES + MASK_MODES[1:] + ("parent_mask_vcf",))
     ap.add_argument("--mask", action="store_true", help="gce_bam_error_profile_masked beside gce_bam_error_profile; writes profiles/errprof_mask.json")
     ap.add_argument("--fragments", action="store_true", help="gce_bam_error_profile_fragments beside gce_bam_error_profile; writes profiles/errprof_fragments.json")
     ap.add_argument("--parent_lib", default=None, help="with --fragments or --mask: the parent commit's libgencore_amd.so, run in the same rounds through GCE_LIB")
@@ -211,6 +212,14 @@ def main():
     print(json.dumps(res))
 
 
+def against_parent(per, v, m, identical):
+    """errprof_s of mode m beside the parent library's run of it, by the rule of every A/B here"""
+    spread = lambda rs: max(r["errprof_s"] for r in rs) - min(r["errprof_s"] for r in rs)
+    gap, noise = v[m]["stages"]["errprof_s"] - v["parent_" + m]["stages"]["errprof_s"], max(spread(per[m]), spread(per["parent_" + m]))
+    return dict(rule="errprof_s is unchanged when the medians differ by less than the spread of the values", this_minus_parent_s=round(gap, 5), spread_s=round(noise, 5),
+                unchanged=abs(gap) <= noise, counters_identical=identical)
+
+
 def main_fragments(args):
     args.out = args.out or os.path.join(ROOT, "profiles", "errprof_fragments.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_fragerr_")
@@ -244,6 +253,7 @@ def main_fragments(args):
                                   frag_planes_over_frag_direct=round(e("frag_planes") / e("frag_direct"), 3))
     if args.parent_lib:
         res["errprof_s_ratio"]["frag_planes_over_parent_planes"] = round(e("frag_planes") / e("parent_planes"), 3)
+        res["against_the_parent"] = {m: against_parent(per, v, m, same(m, "parent_" + m)) for m in ("planes", "frag_planes")}
         a, b = v["pileup_fragments"], v["parent_pileup_fragments"]
         gap = a["stages"]["pileup_s"] - b["stages"]["pileup_s"]
         noise = max(spread(per["pileup_fragments"], "pileup_s"), spread(per["parent_pileup_fragments"], "pileup_s"))
@@ -262,7 +272,7 @@ def main_mask(args):
     args.out = args.out or os.path.join(ROOT, "profiles", "errprof_mask.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_errmask_")
     made = run_child(args, tmp, "make", limit=900)
-    modes = MASK_MODES[:1] + (("parent_planes",) if args.parent_lib else ()) + MASK_MODES[1:]
+    modes = MASK_MODES[:1] + (("parent_planes",) if args.parent_lib else ()) + MASK_MODES[1:2] + (("parent_mask_vcf",) if args.parent_lib else ()) + MASK_MODES[2:]
     per = {m: [] for m in modes}
     for rep in range(args.reps + 1):                               # interleaved; the first round is the warm-up
         for m in modes:
@@ -278,11 +288,11 @@ def main_mask(args):
                     "(planes; parent_planes: the parent commit's library) on the same file, without a BED, interleaved; no pass mark", variants={})
     for m in modes:
         rs = per[m]
-        keys = ("read_s", "inflate_index_s", "errprof_s", "write_s", "total_s", "wall_s") + (("load_s", "fill_s") if m.startswith("mask_") else ())
+        keys = ("read_s", "inflate_index_s", "errprof_s", "write_s", "total_s", "wall_s") + (("load_s", "fill_s") if "mask_" in m else ())
         res["variants"][m] = dict(stages={k: round(med(rs, k), 5) for k in keys}, errprof_s_all=[round(r["errprof_s"], 5) for r in rs], total_s_all=[round(r["total_s"], 4) for r in rs],
                                   peak_device_bytes=int(rs[0]["peak_device_bytes"]), counters={c: int(rs[0][c]) for c in rs[0] if c.startswith("n_")},
                                   sums={c: rs[0][c] for c in ("counts_sum", "counts_crc", "rows_sum_crc") if c in rs[0]})
-        if m.startswith("mask_"):
+        if "mask_" in m:
             res["variants"][m].update(fill_s_all=[round(r["fill_s"], 5) for r in rs], load_s_all=[round(r["load_s"], 5) for r in rs])
     v = res["variants"]
     e = lambda m: v[m]["stages"]["errprof_s"]
@@ -296,6 +306,7 @@ def main_mask(args):
         res["unmasked_against_the_parent"] = dict(rule="a run without a mask pays nothing when the medians differ by less than the spread of the values", this_minus_parent_s=round(gap, 5),
                                                   spread_s=round(noise, 5), unchanged=abs(gap) <= noise,
                                                   counters_identical=v["planes"]["sums"]["counts_crc"] == v["parent_planes"]["sums"]["counts_crc"] and v["planes"]["counters"] == v["parent_planes"]["counters"])
+        res["masked_against_the_parent"] = against_parent(per, v, "mask_vcf", v["mask_vcf"]["sums"] == v["parent_mask_vcf"]["sums"] and v["mask_vcf"]["counters"] == v["parent_mask_vcf"]["counters"])
     for m in MASK_MODES[1:]:                                      # where fill_s goes: k_mask_fill's own time beside the host clock around set_mask
         try:
             v[m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))

@@ -274,9 +274,7 @@ class PileupRun:
     CLASSES = ("A", "C", "G", "T", "N", "DEL", "INS", "LOWQ")
 
     def __init__(self, r):
-        for n, t in type(r)._fields_:
-            if n not in ("site_tid", "site_pos", "counts"):
-                setattr(self, n, (float if t is C.c_double else int)(getattr(r, n)))
+        _copy_run_fields(self, r)
         ns = self.n_sites
         self.tid = np.ctypeslib.as_array(r.site_tid, (ns,)).copy() if ns else np.zeros(0, np.int32)
         self.pos = np.ctypeslib.as_array(r.site_pos, (ns,)).copy() if ns else np.zeros(0, np.int32)
@@ -295,18 +293,8 @@ def pileup_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, min_mapq=0,
     n_intervals, peak_device_bytes, read_s, inflate_index_s, pileup_s, write_s, total_s, tid, pos, counts); raises GceError with the library's
     message (and leaves no table) on failure."""
     from .capi import GCE_PILEUP_DIRECT, GcePileupRun
-    lib = capi.load_library()
-    r = GcePileupRun()
-    err = (C.c_char * 256)()
-    rc = lib.gce_bam_pileup(str(path).encode(), str(bed).encode(), None if fasta is None else str(fasta).encode(), None if tsv is None else str(tsv).encode(), int(device),
-                            int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), GCE_PILEUP_DIRECT if direct else 0, int(window_bytes), int(device_budget_bytes),
-                            C.byref(r), err)
-    if rc != 0:
-        raise GceError(rc, err.value.decode(errors="replace"))
-    try:
-        return PileupRun(r)
-    finally:
-        lib.gce_pileup_free(C.byref(r))
+    return _reduce_call("gce_bam_pileup", GcePileupRun, PileupRun, "gce_pileup_free", (str(path), str(bed), fasta, tsv), GCE_PILEUP_DIRECT if direct else 0, device, threads, min_mapq, min_baseq,
+                        exclude_flags, window_bytes, device_budget_bytes)
 
 
 def pileup_fragments_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, weak_hash=False, window_bytes=0,
@@ -319,34 +307,25 @@ def pileup_fragments_bam(path, bed, fasta=None, tsv=None, device=0, threads=0, m
     records carried across a window boundary: the one counter that depends on window_bytes); raises GceError with the library's message (and
     leaves no table) on failure, a record that lies in front of its predecessor among them."""
     from .capi import GCE_FRAGPILE_DIRECT, GCE_FRAGPILE_WEAK_HASH, GceFragpileRun
-    lib = capi.load_library()
-    r = GceFragpileRun()
-    err = (C.c_char * 256)()
-    rc = lib.gce_bam_pileup_fragments(str(path).encode(), str(bed).encode(), None if fasta is None else str(fasta).encode(), None if tsv is None else str(tsv).encode(), int(device),
-                                      int(threads), int(min_mapq), int(min_baseq), int(exclude_flags), (GCE_FRAGPILE_DIRECT if direct else 0) | (GCE_FRAGPILE_WEAK_HASH if weak_hash else 0),
-                                      int(window_bytes), int(device_budget_bytes), C.byref(r), err)
-    if rc != 0:
-        raise GceError(rc, err.value.decode(errors="replace"))
-    try:
-        return PileupRun(r)
-    finally:
-        lib.gce_fragpile_free(C.byref(r))
+    return _reduce_call("gce_bam_pileup_fragments", GceFragpileRun, PileupRun, "gce_fragpile_free", (str(path), str(bed), fasta, tsv),
+                        (GCE_FRAGPILE_DIRECT if direct else 0) | (GCE_FRAGPILE_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
+                        device_budget_bytes)
 
 
 def _copy_run_fields(obj, r, mask=None):
     """The scalar fields of a gce_*_run onto obj, the counters and bytes as int, the times as float; with `mask`, gce_mask_run's fields too:
     n_records and n_intervals are the BAM's and the BED's, so the mask's are n_mask_records and n_mask_intervals."""
     for n, t in type(r)._fields_:
-        if n not in ("counts", "overlap"):
+        if n not in ("site_tid", "site_pos", "counts", "overlap"):
             setattr(obj, n, (float if t is C.c_double else int)(getattr(r, n)))
     if mask is not None:
         for n, t in type(mask)._fields_:
             setattr(obj, {"n_intervals": "n_mask_intervals", "n_records": "n_mask_records"}.get(n, n), (float if t is C.c_double else int)(getattr(mask, n)))
 
 
-def _error_profile_call(entry, run_type, wrap, free, paths, options, device, threads, min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes, masked=False):
-    """One error-profile entry point of the library: `paths` are its leading arguments (None for an optional path that is absent), behind
-    them the common ones, its gce_*_run, with `masked` a gce_mask_run, and err.  Returns wrap(run[, mask run]); the run's arrays
+def _reduce_call(entry, run_type, wrap, free, paths, options, device, threads, min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes, masked=False):
+    """One pileup or error-profile entry point of the library: `paths` are its leading arguments (None for an optional path that is absent),
+    behind them the common ones, its gce_*_run, with `masked` a gce_mask_run, and err.  Returns wrap(run[, mask run]); the run's arrays
     are freed with `free` either way."""
     from .capi import GceMaskRun
     lib = capi.load_library()
@@ -357,7 +336,7 @@ def _error_profile_call(entry, run_type, wrap, free, paths, options, device, thr
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     try:
-        return wrap(r, m)
+        return wrap(r, m) if masked else wrap(r)
     finally:
         getattr(lib, free)(C.byref(r))
 
@@ -389,8 +368,8 @@ def error_profile_bam(path, fasta, bed=None, tsv=None, device=0, threads=0, min_
     n_no_seq, n_bad_cigar, n_no_ref, n_too_long, n_bases, n_mismatches, n_intervals (-1 without a BED), peak_device_bytes, read_s,
     inflate_index_s, errprof_s, write_s, total_s, counts); raises GceError with the library's message (and leaves no table) on failure."""
     from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun
-    return _error_profile_call("gce_bam_error_profile", GceErrprofRun, ErrorProfileRun, "gce_errprof_free", (str(path), str(fasta), bed, tsv), GCE_ERRPROF_DIRECT if direct else 0, device, threads,
-                               min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes)
+    return _reduce_call("gce_bam_error_profile", GceErrprofRun, ErrorProfileRun, "gce_errprof_free", (str(path), str(fasta), bed, tsv), GCE_ERRPROF_DIRECT if direct else 0, device, threads,
+                        min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes)
 
 
 def error_profile_masked_bam(path, fasta, mask, bed=None, tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False, window_bytes=0, device_budget_bytes=0):
@@ -401,8 +380,8 @@ def error_profile_masked_bam(path, fasta, mask, bed=None, tsv=None, device=0, th
     fields plus gce_mask_run's: n_lines, n_mask_records, n_unknown_contig, n_no_alt, n_mask_intervals, n_masked_bases, n_masked_events, load_s and
     fill_s."""
     from .capi import GCE_ERRPROF_DIRECT, GceErrprofRun
-    return _error_profile_call("gce_bam_error_profile_masked", GceErrprofRun, ErrorProfileRun, "gce_errprof_free", (str(path), str(fasta), bed, str(mask), tsv), GCE_ERRPROF_DIRECT if direct else 0, device,
-                               threads, min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes, masked=True)
+    return _reduce_call("gce_bam_error_profile_masked", GceErrprofRun, ErrorProfileRun, "gce_errprof_free", (str(path), str(fasta), bed, str(mask), tsv), GCE_ERRPROF_DIRECT if direct else 0, device,
+                        threads, min_mapq, min_baseq, exclude_flags, window_bytes, device_budget_bytes, masked=True)
 
 
 OVERLAP_CLASSES = ErrorProfileRun.CLASSES[:16] + ("AGREE_REF", "AGREE_ALT", "DIFF_OTHER", "UNUSABLE", "LOWQ")
@@ -421,9 +400,9 @@ def error_profile_fragments_bam(path, fasta, bed=None, tsv=None, overlap_tsv=Non
     ([3, 1024, 24], uint64); raises GceError with the library's message (and leaves no table) on failure, a record that lies in front of its
     predecessor among them."""
     from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun
-    return _error_profile_call("gce_bam_error_profile_fragments", GceFragerrRun, ErrorProfileRun, "gce_fragerr_free", (str(path), str(fasta), bed, tsv, overlap_tsv),
-                               (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
-                               device_budget_bytes)
+    return _reduce_call("gce_bam_error_profile_fragments", GceFragerrRun, ErrorProfileRun, "gce_fragerr_free", (str(path), str(fasta), bed, tsv, overlap_tsv),
+                        (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
+                        device_budget_bytes)
 
 
 def error_profile_fragments_masked_bam(path, fasta, mask, bed=None, tsv=None, overlap_tsv=None, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, direct=False,
@@ -433,9 +412,9 @@ def error_profile_fragments_masked_bam(path, fasta, mask, bed=None, tsv=None, ov
     n_shared_columns.  Both tables get the trailing MASKED column.  Returns error_profile_fragments_bam's ErrorProfileRun with
     error_profile_masked_bam's mask fields."""
     from .capi import GCE_FRAGERR_DIRECT, GCE_FRAGERR_WEAK_HASH, GceFragerrRun
-    return _error_profile_call("gce_bam_error_profile_fragments_masked", GceFragerrRun, ErrorProfileRun, "gce_fragerr_free", (str(path), str(fasta), bed, str(mask), tsv, overlap_tsv),
-                               (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
-                               device_budget_bytes, masked=True)
+    return _reduce_call("gce_bam_error_profile_fragments_masked", GceFragerrRun, ErrorProfileRun, "gce_fragerr_free", (str(path), str(fasta), bed, str(mask), tsv, overlap_tsv),
+                        (GCE_FRAGERR_DIRECT if direct else 0) | (GCE_FRAGERR_WEAK_HASH if weak_hash else 0), device, threads, min_mapq, min_baseq, exclude_flags, window_bytes,
+                        device_budget_bytes, masked=True)
 
 
 class ErrorProfileSupportRun:

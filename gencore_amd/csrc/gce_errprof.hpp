@@ -32,9 +32,6 @@ namespace errprof {
 
 #define EP_HD __host__ __device__ inline
 
-typedef uint32_t __attribute__((aligned(1), may_alias)) ep_u32u;
-typedef uint16_t __attribute__((aligned(1), may_alias)) ep_u16u;
-
 #define EP_NONE RD_NONE
 #define EP_MAX_CYCLE 1024u
 #define EP_ROW 24u                                                                    // counters per (segment, cycle): 21 classes, MASKED, 2 zeros
@@ -80,27 +77,12 @@ EP_HD bool mask_at(const Mask &M, int64_t base, int64_t rlen, int64_t a) {
     return (M.bits[i >> 3] >> (i & 7u)) & 1u;
 }
 
-// The fields of a record (r at its block_size) that the walks read, decoded once: walk_record for the record it walks, Cursor
-// (gce_fragerr.hpp) for the partner
-struct Head {
-    const uint8_t *cg, *sq, *ql; int32_t tid, pos, lseq; uint32_t nc, flag; bool has_q;
-    EP_HD explicit Head(const uint8_t *r) {
-        const uint8_t *c = r + 4;
-        tid = (int32_t) * (const ep_u32u *)(c + 0); pos = (int32_t) * (const ep_u32u *)(c + 4); lseq = (int32_t) * (const ep_u32u *)(c + 16);
-        nc = *(const ep_u16u *)(c + 12); flag = *(const ep_u16u *)(c + 14);
-        cg = c + 32 + c[8]; sq = cg + 4 * nc; ql = sq + ((uint32_t)lseq + 1) / 2;
-        has_q = ql[0] != 0xFF;
-    }
-};
-// the class of a reference base (rb: the contig's bases, rlen of them) and of a read's 4-bit base: 0..3 = A C G T, 4 = anything else
+using reduce::Head; using reduce::read_class;                                         // the record header and the class of a read base, gce_reduce.hpp's
+// the class of a reference base (rb: the contig's bases, rlen of them): 0..3 = A C G T, 4 = anything else, as reduce::read_class has a read's
 EP_HD uint32_t ref_class(const uint8_t *rb, int64_t rlen, int64_t col) {
     if (col >= rlen) return 4u;
     const uint8_t b = rb[col] & 0xDFu;
     return b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u;
-}
-EP_HD uint32_t read_class(const uint8_t *sq, uint32_t yi) {
-    const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
-    return nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
 }
 // the class of a reference base rc against a read's base bc in sequencing orientation: 4 r + b for two usable bases, cls < 18
 EP_HD uint32_t base_class(uint32_t rc, uint32_t bc, bool rev) {
@@ -130,7 +112,7 @@ struct Column {
 template <bool MASK, class AT> EP_HD void walk_record(const uint8_t *r, const Params &P, const calmd::Ref &ref, const reduce::Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, AT &at,
                                                       const Mask &M) {
     const Head h(r);
-    const bool rev = (h.flag & 16u) != 0;
+    const bool has_q = h.has_q(), rev = (h.flag & 16u) != 0;
     const uint32_t seg = (h.flag & 0xC0u) == 0x40u ? 1u : (h.flag & 0xC0u) == 0x80u ? 2u : 0u, row0 = seg * EP_MAX_CYCLE;
     const uint32_t tend = P.bed ? S.tfirst[h.tid + 1] : 0u;
     const int64_t rbase = ref.tab[2 * h.tid];
@@ -138,7 +120,7 @@ template <bool MASK, class AT> EP_HD void walk_record(const uint8_t *r, const Pa
     uint32_t cur = first, q = 0; int64_t x = h.pos; bool seen = false;
 #define EP_CYC0(y) (rev ? (uint32_t)h.lseq - 1u - (y) : (y))                           // rule C, less one
     for (uint32_t k = 0; k < h.nc; k++) {
-        const uint32_t w = *(const ep_u32u *)(h.cg + 4 * k), op = w & 15u, len = w >> 4;
+        const uint32_t w = *(const reduce::rd_u32u *)(h.cg + 4 * k), op = w & 15u, len = w >> 4;
         if (op == 0 || op == 7 || op == 8) {
             const int64_t xe = x + len;
             if (P.bed) cur = reduce::seek(S, cur, tend, x);
@@ -151,7 +133,7 @@ template <bool MASK, class AT> EP_HD void walk_record(const uint8_t *r, const Pa
                 }
                 for (int64_t col = a + lane; col < z; col += nlanes) {
                     const uint32_t yi = q + (uint32_t)(col - x);
-                    at(P, Column{rb, h.sq, h.ql, rlen, col, yi, row0 + EP_CYC0(yi), h.has_q, rev, MASK && mask_at(M, rbase, rlen, col)});
+                    at(P, Column{rb, h.sq, h.ql, rlen, col, yi, row0 + EP_CYC0(yi), has_q, rev, MASK && mask_at(M, rbase, rlen, col)});
                 }
                 if (!P.bed) break;
             }

@@ -55,20 +55,20 @@ ES_HD uint32_t bucket(int64_t v) { return v >= 1 && v <= 31 ? (uint32_t)v : ES_T
 ES_HD Support support(const uint8_t *r, const Tags &T) {
     Support s{0u, 0u, false};
     const uint8_t *c = r + 4;
-    const uint32_t bs = *(const errprof::ep_u32u *)r, lq = c[8], nc = *(const errprof::ep_u16u *)(c + 12), lseq = *(const errprof::ep_u32u *)(c + 16);
+    const uint32_t bs = *(const reduce::rd_u32u *)r, lq = c[8], nc = *(const reduce::rd_u16u *)(c + 12), lseq = *(const reduce::rd_u32u *)(c + 16);
     const uint8_t *end = c + bs, *p = c + 32 + lq + 4 * nc + (lseq + 1) / 2 + lseq;
     bool seen_f = false, seen_r = false;
     while (p < end) {
         uint64_t fs;
         if (!calmd::field_bytes(p, end, fs)) { s.bad = true; return s; }
-        const uint32_t tag = *(const errprof::ep_u16u *)p;
+        const uint32_t tag = *(const reduce::rd_u16u *)p;
         const bool is_f = !seen_f && tag == T.fwd, is_r = !seen_r && tag == T.rev;
         if (is_f || is_r) {
             const uint8_t type = p[2]; const uint8_t *v = p + 3;
             bool num = true; int64_t val = 0;
             if (type == 'c') val = (int8_t)v[0]; else if (type == 'C') val = v[0];
-            else if (type == 's') val = (int16_t) * (const errprof::ep_u16u *)v; else if (type == 'S') val = *(const errprof::ep_u16u *)v;
-            else if (type == 'i') val = (int32_t) * (const errprof::ep_u32u *)v; else if (type == 'I') val = *(const errprof::ep_u32u *)v;
+            else if (type == 's') val = (int16_t) * (const reduce::rd_u16u *)v; else if (type == 'S') val = *(const reduce::rd_u16u *)v;
+            else if (type == 'i') val = (int32_t) * (const reduce::rd_u32u *)v; else if (type == 'I') val = *(const reduce::rd_u32u *)v;
             else num = false;
             const uint32_t b = num ? bucket(val) : 0u;
             if (is_f) { seen_f = true; s.f = b; }
@@ -88,7 +88,7 @@ ES_HD void scan_record(const uint8_t *r, uint64_t avail, const errprof::Params &
 }
 
 ES_HD uint32_t segment(const uint8_t *r) {
-    const uint32_t flag = *(const errprof::ep_u16u *)(r + 4 + 14);
+    const uint32_t flag = *(const reduce::rd_u16u *)(r + 4 + 14);
     return (flag & 0xC0u) == 0x40u ? 1u : (flag & 0xC0u) == 0x80u ? 2u : 0u;
 }
 // the row of an eligible record, < ES_ROWS

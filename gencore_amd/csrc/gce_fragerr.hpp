@@ -34,13 +34,13 @@ struct Cursor {
     const uint8_t *cg, *sq, *ql; uint32_t nc, k, q0; int64_t x0; bool has_q;
     EP_HD explicit Cursor(const uint8_t *o) {
         const Head h(o);
-        cg = h.cg; sq = h.sq; ql = h.ql; nc = h.nc; has_q = h.has_q;
+        cg = h.cg; sq = h.sq; ql = h.ql; nc = h.nc; has_q = h.has_q();
         k = 0; q0 = 0; x0 = h.pos;
     }
     EP_HD bool at(int64_t x, uint32_t &cls, uint32_t &q) {
         if (x < x0) return false;                                                     // (in front of pos: x0 never passes an x that was asked for)
         for (; k < nc; k++) {
-            const uint32_t w = *(const ep_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
+            const uint32_t w = *(const reduce::rd_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
             if (op == 0 || op == 7 || op == 8) {
                 if (x < x0 + len) {
                     const uint32_t yi = q0 + (uint32_t)(x - x0);

@@ -13,9 +13,9 @@
 //                  partner, none, or ambiguity, whatever the insertion order.  A candidate without partner whose next_pos >= pos and whose
 //                  partner may still come (the window's last key is not beyond (refID, next_pos), the file has not ended) is deferred
 //   k_frag_count   16 lanes per entry, 16 entries per block, the LDS tile and PileAdd of k_pile_count: pileup::count_record for an entry
-//                  without partner, nothing for a deferred one, fragpile::paired_walk for a mate: it walks its own columns, looks the
-//                  partner's (class, quality) up from the partner's CIGAR and decides its own add by rule V; no order between the mates is
-//                  needed.  The later mate's walk alone adds to rule V's counters, reduced per wave.  k_frag_count<true>
+//                  without partner, nothing for a deferred one, fragpile::paired_walk for a mate: pileup::walk_record (gce_pileup.hpp)
+//                  under the functor ColumnV, which at each of the mate's own columns looks the partner's (class, quality) up from the
+//                  partner's CIGAR (fragpile::column) and decides the mate's add by rule V; no order between the mates is needed.  The later mate's walk alone adds to rule V's counters, reduced per wave.  k_frag_count<true>
 //                  (GCE_FRAGPILE_DIRECT): global atomics only
 //   k_frag_carry   the deferred entries, whole and with their file-wide record index, into the other of two arenas, bump-allocated with one
 //                  atomic per record; the next window joins against it
@@ -30,27 +30,23 @@ namespace fragpile {
 
 #define FP_HD __host__ __device__ inline
 
-using pileup::Ivl; using pileup::Params; using pileup::Sites; using reduce::seek;
-using pileup::PU_A; using pileup::PU_C; using pileup::PU_G; using pileup::PU_T; using pileup::PU_N; using pileup::PU_DEL; using pileup::PU_INS; using pileup::PU_LOWQ;
+using pileup::Params; using pileup::Sites; using pileup::PU_DEL; using pileup::PU_LOWQ;
 
 // Rule V's lookup: the raw class (A C G T N, DEL for a D column) and the quality (0 for a D column or a record without qualities) of eligible
 // record r at reference column x; false: no M / = / X / D op of it covers x
 FP_HD bool column(const uint8_t *r, int64_t x, uint32_t &cls, uint32_t &q) {
-    const uint8_t *c = r + 4;
-    const int32_t pos = rd_i32(c + 4), lseq = rd_i32(c + 16);
-    const uint32_t lq = c[8], nc = *(const fp_u16u *)(c + 12);
-    const uint8_t *cg = c + 32 + lq, *sq = cg + 4 * nc, *ql = sq + ((uint32_t)lseq + 1) / 2;
-    int64_t x0 = pos; uint32_t q0 = 0;
+    const reduce::Head h(r);
+    int64_t x0 = h.pos; uint32_t q0 = 0;
     if (x < x0) return false;
-    for (uint32_t k = 0; k < nc; k++) {
-        const uint32_t w = *(const fp_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
+    for (uint32_t k = 0; k < h.nc; k++) {
+        const uint32_t w = *(const reduce::rd_u32u *)(h.cg + 4 * k), op = w & 15u, len = w >> 4;
         if (op == 0 || op == 7 || op == 8 || op == 2 || op == 3) {
             if (x < x0 + len) {
                 if (op == 3) return false;
                 if (op == 2) { cls = PU_DEL; q = 0; return true; }
-                const uint32_t yi = q0 + (uint32_t)(x - x0), nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
-                cls = nib == 1 ? PU_A : nib == 2 ? PU_C : nib == 4 ? PU_G : nib == 8 ? PU_T : PU_N;
-                q = ql[0] != 0xFF ? ql[yi] : 0u;
+                const uint32_t yi = q0 + (uint32_t)(x - x0);
+                cls = reduce::read_class(h.sq, yi);
+                q = h.has_q() ? h.ql[yi] : 0u;
                 return true;
             }
             x0 += len; if (op != 2 && op != 3) q0 += len;
@@ -59,57 +55,33 @@ FP_HD bool column(const uint8_t *r, int64_t x, uint32_t &cls, uint32_t &q) {
     return false;
 }
 
-// Rules W and V for a mate r of a pair whose other mate is o, by lane `lane` of the record's `nlanes`, as pileup::count_record walks a record
-// alone.  is_b: r is the later of the two in the file.  A column that o covers is decided by rule V and r adds only what r has won; every
-// other column and every insertion is rule W's.  shared, differ: rule V's counters, added to by the later mate's walk alone.
+// Rule V at one column of a mate of a pair whose other mate is o: pileup::walk_record's functor, so that the mate is walked as
+// pileup::count_record walks a record alone.  is_b: the mate is the later of the two in the file.  A column that o covers is decided by rule V
+// and the mate adds only what it has won; every other column is rule W's.  shared, differ: rule V's counters, added to by the later mate's
+// walk alone.
+struct ColumnV {
+    const uint8_t *o; bool is_b; uint32_t &shared, &differ;
+    FP_HD bool operator()(const Params &P, const pileup::Column &c, uint32_t &cls) {
+        uint32_t mq;
+        c.load(cls, mq);
+        uint32_t oc = 0, oq = 0, adj = mq;
+        if (column(o, c.x, oc, oq)) {
+            const uint32_t qa = is_b ? oq : mq, qb = is_b ? mq : oq;
+            bool mine;
+            if (cls == oc) { mine = !is_b; adj = qa + qb < FP_Q_CAP ? qa + qb : FP_Q_CAP; }
+            else { mine = is_b ? qa < qb : qa >= qb; adj = (4u * mq) / 5u; }
+            if (is_b) { shared++; differ += cls != oc; }
+            if (!mine) return false;
+        }
+        if (c.lowq(P, adj)) cls = PU_LOWQ;
+        return true;
+    }
+};
+// Rules W and V for a mate r of a pair whose other mate is o, by lane `lane` of the record's `nlanes`; the insertions are rule W's
 template <class ADD> FP_HD void paired_walk(const uint8_t *r, const uint8_t *o, bool is_b, const Params &P, const Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add,
                                             uint32_t &shared, uint32_t &differ) {
-    const uint8_t *c = r + 4;
-    const int32_t tid = rd_i32(c + 0), pos = rd_i32(c + 4), lseq = rd_i32(c + 16);
-    const uint32_t lq = c[8], nc = *(const fp_u16u *)(c + 12), flag = *(const fp_u16u *)(c + 14);
-    const uint8_t *cg = c + 32 + lq, *sq = cg + 4 * nc, *ql = sq + ((uint32_t)lseq + 1) / 2;
-    const uint32_t sbase = ((flag >> 4) & 1u) * 8u, tend = S.tfirst[tid + 1];
-    const bool has_q = ql[0] != 0xFF;
-    uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
-    for (uint32_t k = 0; k < nc; k++) {
-        const uint32_t w = *(const fp_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
-        if (op == 0 || op == 7 || op == 8 || op == 2) {
-            cur = seek(S, cur, tend, x);
-            const int64_t xe = x + len;
-            for (uint32_t j = cur; j < tend && (int64_t)S.iv[j].start < xe; j++) {
-                const Ivl v = S.iv[j];
-                const int64_t a = x > v.start ? x : (int64_t)v.start, z = xe < v.end ? xe : (int64_t)v.end;
-                for (int64_t col = a + lane; col < z; col += nlanes) {
-                    uint32_t cls = PU_DEL, mq = 0;
-                    if (op != 2) {
-                        const uint32_t yi = q + (uint32_t)(col - x), nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
-                        cls = nib == 1 ? PU_A : nib == 2 ? PU_C : nib == 4 ? PU_G : nib == 8 ? PU_T : PU_N;
-                        mq = has_q ? ql[yi] : 0u;
-                    }
-                    uint32_t oc = 0, oq = 0, adj = mq;
-                    bool mine = true;
-                    if (column(o, col, oc, oq)) {
-                        const uint32_t qa = is_b ? oq : mq, qb = is_b ? mq : oq;
-                        if (cls == oc) { mine = !is_b; adj = qa + qb < FP_Q_CAP ? qa + qb : FP_Q_CAP; }
-                        else { mine = is_b ? qa < qb : qa >= qb; adj = (4u * mq) / 5u; }
-                        if (is_b) { shared++; differ += cls != oc; }
-                    }
-                    if (!mine) continue;
-                    if (cls != PU_DEL && has_q && (int32_t)adj < P.min_baseq) cls = PU_LOWQ;
-                    add((v.site0 + (uint32_t)(col - v.start)) * 16u + sbase + cls);
-                }
-            }
-            x = xe; if (op != 2) q += len;
-            seen = true;
-        } else if (op == 3) x += len;
-        else if (op == 1) {
-            if (seen && x >= 1) {
-                cur = seek(S, cur, tend, x);
-                if (cur < tend && (int64_t)S.iv[cur].start <= x - 1 && lane == 0) add((S.iv[cur].site0 + (uint32_t)(x - 1 - S.iv[cur].start)) * 16u + sbase + PU_INS);
-            }
-            q += len;
-        } else if (op == 4) q += len;
-    }
+    ColumnV at{o, is_b, shared, differ};
+    pileup::walk_record(r, P, S, first, lane, nlanes, at, add);
 }
 
 #undef FP_HD
@@ -120,10 +92,6 @@ template <class ADD> FP_HD void paired_walk(const uint8_t *r, const uint8_t *o, 
 
 namespace {
 
-// k_frag_count's tile is k_pile_count's: 8 blocks of 4 waves a CU, 20 KiB of LDS each
-#define FP_TILE PU_TILE
-static_assert(FP_TILE * 64u + 64u <= PU_LDS_PER_CU / PU_BLOCKS_PER_CU, "k_frag_count's tile must leave the CU its 8 blocks of 4 waves");
-
 // what k_reduce_scan over PileScan left in meta: the first interval, or PU_NONE for a record that is skipped or touches none
 struct FragpileRead {
     pileup::Params P;
@@ -133,48 +101,23 @@ struct FragpileRead {
     }
 };
 
-// 16 lanes per entry, 16 entries per block (block b: entries [16 b, 16 b + 16)); n_counts: 16 x the number of sites
+// 16 lanes per entry, 16 entries per block (block b: entries [16 b, 16 b + 16)), the tile and the adds of k_pile_count (PileAdd,
+// gce_pileup.hpp); n_counts: 16 x the number of sites
 template <bool DIRECT> __global__ __launch_bounds__(256) void k_frag_count(FragView V, pileup::Params P, pileup::Sites S, const uint32_t *first, const uint32_t *partner, uint32_t *counts,
                                                                            uint64_t n_counts, unsigned long long *fm) {
-    __shared__ uint32_t s_tile[DIRECT ? 1 : FP_TILE * 16u];
-    __shared__ uint32_t s_base[16];
-    const uint32_t g = threadIdx.x >> 4, sub = threadIdx.x & 15u;
-    const uint64_t e = (uint64_t)blockIdx.x * 16u + g;
+    const uint32_t sub = threadIdx.x & 15u;
+    const uint64_t e = (uint64_t)blockIdx.x * 16u + (threadIdx.x >> 4);
     uint32_t f = PU_NONE, pc = FP_SKIP;
     if (e < V.n) { pc = partner[e]; if (pc != FP_SKIP && pc != FP_DEFER) f = first[e]; }
     const uint8_t *r = f != PU_NONE ? V.rec(e) : nullptr;
-    uint32_t base = 0;
-    if (!DIRECT) {
-        for (uint32_t i = threadIdx.x; i < FP_TILE * 16u; i += 256u) s_tile[i] = 0u;
-        if (sub == 0) {                                                               // the first site this record can touch, as k_pile_count takes it
-            uint32_t b = PU_NONE;
-            if (f != PU_NONE) {
-                const int32_t pos = (int32_t)rb32(r + 8);
-                const pileup::Ivl v = S.iv[f];
-                b = v.site0 + (uint32_t)(max(pos - 1, v.start) - v.start);
-            }
-            s_base[g] = b;
-        }
-        __syncthreads();
-        base = PU_NONE;
-#pragma unroll
-        for (int k = 15; k >= 0; k--) if (s_base[k] != PU_NONE) base = s_base[k];
-        if (base == PU_NONE) return;
-    }
-    PileAdd<DIRECT> add{s_tile, counts, base * 16u};
+    PileAdd<DIRECT> add;
+    if (!add.open(f, S, counts, [&] { return r; })) return;
     uint32_t shared = 0, differ = 0;
     if (f != PU_NONE) {
         if (pc == FP_ALONE) pileup::count_record(r, P, S, f, sub, 16u, add);
         else fragpile::paired_walk(r, V.rec(pc & ~FP_IS_B), (pc & FP_IS_B) != 0, P, S, f, sub, 16u, add, shared, differ);
     }
-    if (!DIRECT) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < FP_TILE * 16u; i += 256u) {
-            const uint32_t v = s_tile[i];
-            const uint64_t at = (uint64_t)base * 16u + i;
-            if (v && at < n_counts) atomicAdd(counts + at, v);
-        }
-    }
+    add.flush(n_counts);
 #pragma unroll
     for (int d = 32; d; d >>= 1) { shared += __shfl_xor(shared, d); differ += __shfl_xor(differ, d); }
     if (lane_id() == 0) {
@@ -185,9 +128,7 @@ template <bool DIRECT> __global__ __launch_bounds__(256) void k_frag_count(FragV
 
 }  // namespace
 
-struct gce_fragpile : ReduceSession {
-    pileup::Params P{0, 0, 0, 0}; bool direct = false;
-    DevBuf counts; uint64_t n_sites = 0;                                              // 64 bytes per site
+struct gce_fragpile : PileSession {
     MateJoin J; int cb_rc = GCE_OK;
     std::string needs() const override {
         return "gce_bam_pileup_fragments needs 64 bytes per site (" + std::to_string(n_sites) + " sites), a join table (" + std::to_string(J.table_bytes()) + " bytes) and an arena (" +
@@ -200,9 +141,9 @@ struct gce_fragpile : ReduceSession {
 int gce_fragpile::process(const uint8_t *u, const uint64_t *off, uint64_t n_rec, bool final) {
     return J.run(this, "gce_bam_pileup_fragments", FragpileRead{P}, u, off, n_rec, final, [&](const FragView &V, uint64_t N, const uint32_t *first, const uint32_t *partner, unsigned long long *m) {
         if (!n_sites) return false;
-        const unsigned cb = (unsigned)((N + 15) / 16);
-        if (direct) hipLaunchKernelGGL(k_frag_count<true>, dim3(cb), dim3(256), 0, s, V, P, sites(), first, partner, counts.as<uint32_t>(), n_sites * 16, m);
-        else hipLaunchKernelGGL(k_frag_count<false>, dim3(cb), dim3(256), 0, s, V, P, sites(), first, partner, counts.as<uint32_t>(), n_sites * 16, m);
+        dispatch([&](auto D) {
+            hipLaunchKernelGGL(k_frag_count<decltype(D)::value>, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, V, P, sites(), first, partner, counts.as<uint32_t>(), n_sites * 16, m);
+        });
         return true;
     });
 }
@@ -226,15 +167,8 @@ const char *gce_fragpile_error(gce_fragpile *p) { return p ? p->err.c_str() : ""
 
 // rule S's intervals, as gce_pileup_set_sites takes them; the counters and the pass's device words are made and zeroed
 int gce_fragpile_set_sites(gce_fragpile *p, int32_t n_ref, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, const uint32_t *site0) {
-    if (!p || p->sites_set || n_ref < 0 || n_intervals < 0 || (n_intervals && (!tid || !start || !end || !site0))) return GCE_ERR_INVALID;
-    (void)hipSetDevice(p->device);
-    RdTable t;
-    int rc = rd_intervals(p, "gce_fragpile_set_sites", n_ref, n_intervals, tid, start, end, t);
+    int rc = pu_set_sites(p, "gce_fragpile_set_sites", n_ref, n_intervals, tid, start, end, site0);
     if (rc != GCE_OK) return rc;
-    for (int64_t j = 0; j < n_intervals; j++) if (site0[j] != t.iv[(size_t)j].site0) return p->out_of_order("gce_fragpile_set_sites");
-    if (t.sites > PU_MAX_SITES) return p->fail(GCE_ERR_INVALID, "more than 2^28 sites");
-    p->n_sites = t.sites; p->P.n_ref = n_ref;
-    if ((rc = rd_set_sites(p, t, p->counts, t.sites * 64 + 64, 9)) != GCE_OK) return rc;
     p->sites_set = false;
     if ((rc = p->J.init(p)) != GCE_OK) return rc;
     p->sites_set = true;
@@ -260,13 +194,10 @@ int gce_fragpile_finish(gce_fragpile *p, int64_t counters[13], uint32_t *counts_
     hipStream_t s = p->s;
     int rc = p->process(nullptr, nullptr, 0, true);
     if (rc != GCE_OK) return rc;
-    unsigned long long h[9], f[FM_WORDS];
-    if ((rc = rd_finish(p, PileScan::NSKIP, counters, h, 9)) != GCE_OK) return rc;
-    if (h[8] >> 32) return p->fail(GCE_ERR_INVALID, "the eligible records hold 2^32 CIGAR operations or more: the 32-bit counters cannot be shown to hold");
+    if ((rc = pu_finish(p, counters, counts_out)) != GCE_OK) return rc;
+    unsigned long long f[FM_WORDS];
     RDCHK(hipMemcpyAsync(f, p->J.fm.p, sizeof f, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s));
     counters[8] = (int64_t)f[FM_PAIRS]; counters[9] = (int64_t)f[FM_SHARED]; counters[10] = (int64_t)f[FM_DIFFER]; counters[11] = (int64_t)f[FM_AMBIG]; counters[12] = (int64_t)f[FM_DEFER];
-    if (counts_out && p->n_sites) { RDCHK(hipMemcpyAsync(counts_out, p->counts.p, p->n_sites * 64, hipMemcpyDeviceToHost, s)); RDCHK(hipStreamSynchronize(s)); }
-    RDCHK(hipGetLastError());
     return GCE_OK;
 }
 

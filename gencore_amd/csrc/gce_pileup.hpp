@@ -15,8 +15,11 @@
 //                  Sortedness decides only how many adds the tile catches.  k_pile_count<true> (GCE_PILEUP_DIRECT) has no tile: every add is a
 //                  global atomic.
 // pileup::scan_record and pileup::count_record are __host__ __device__: tests/pileup_host_check.hip runs them on the host against
-// tests/pypileup.py, the model of the rules.  What the pass shares with gce_bam_error_profile -- rule E, the interval table, the scan kernel and
-// the device object -- is gce_reduce.hpp's.
+// tests/pypileup.py, the model of the rules.  What the pass shares with gce_bam_error_profile -- rule E, the interval table, the scan kernel,
+// the device object, the decode of a record's header (reduce::Head) and the class of a 4-bit base (reduce::read_class) -- is
+// gce_reduce.hpp's.  What it shares with gce_fragpile.hpp (4k) is here, once: the CIGAR walk (pileup::walk_record, which asks a functor at
+// every column of an M / = / X / D op; count_record is the walk under rule W's functor), the LDS tile and its adds (PileAdd), the device
+// object's base (PileSession, with the one choice of a count kernel's instantiation) and pu_set_sites / pu_finish.
 #pragma once
 #include <cstdint>
 #include "gce_reduce.hpp"
@@ -25,12 +28,10 @@ namespace pileup {
 
 #define PU_HD __host__ __device__ inline
 
-typedef uint32_t __attribute__((aligned(1), may_alias)) pu_u32u;
-typedef uint16_t __attribute__((aligned(1), may_alias)) pu_u16u;
-
 #define PU_NONE RD_NONE
 #define PU_MAX_SITES (1u << 28)
 enum { PU_A = 0, PU_C, PU_G, PU_T, PU_N, PU_DEL, PU_INS, PU_LOWQ };
+static_assert(PU_A == 0 && PU_C == 1 && PU_G == 2 && PU_T == 3 && PU_N == 4, "the classes of a base are reduce::read_class's 0..4");
 
 using reduce::Ivl; using reduce::Sites; using reduce::seek;                           // rule S on the device
 struct Params { int32_t n_ref, min_mapq, min_baseq; uint32_t exclude; };
@@ -51,19 +52,31 @@ PU_HD void scan_record(const uint8_t *r, uint64_t avail, const Params &P, const 
     R.first = reduce::first_interval(S, c.tid, c.pos, (int64_t)c.pos + c.rlen);
 }
 
-// Rule W for an eligible record whose scan gave `first`, by lane `lane` of the record's `nlanes`: the lanes stride over the columns of each
-// M / = / X / D op, lane 0 takes the insertions.  add(i): counter i (site * 16 + strand * 8 + class) += 1.  Reads stay inside the record (the
-// scan checked its fields against block_size and the CIGAR's query length against l_seq); i < 16 * the number of sites.
-template <class ADD> PU_HD void count_record(const uint8_t *r, const Params &P, const Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
-    const uint8_t *c = r + 4;
-    const int32_t tid = (int32_t) * (const pu_u32u *)(c + 0), pos = (int32_t) * (const pu_u32u *)(c + 4), lseq = (int32_t) * (const pu_u32u *)(c + 16);
-    const uint32_t lq = c[8], nc = *(const pu_u16u *)(c + 12), flag = *(const pu_u16u *)(c + 14);
-    const uint8_t *cg = c + 32 + lq, *sq = cg + 4 * nc, *ql = sq + ((uint32_t)lseq + 1) / 2;
-    const uint32_t sbase = ((flag >> 4) & 1u) * 8u, tend = S.tfirst[tid + 1];
-    const bool has_q = ql[0] != 0xFF;
-    uint32_t cur = first, q = 0; int64_t x = pos; bool seen = false;
-    for (uint32_t k = 0; k < nc; k++) {
-        const uint32_t w = *(const pu_u32u *)(cg + 4 * k), op = w & 15u, len = w >> 4;
+// One column of an M / = / X / D op as walk_record hands it to its functor: the reference position x, the query index yi (of the op's first
+// base at a D column, and not to be used), whether a D op covers it.  Nothing of the read is loaded until a functor asks: load(cls, q) gives
+// the raw class (A C G T N, DEL at a D column) and the base's quality (0 at a D column or for a record without qualities), under one test of
+// `del`, so that a column costs one branch; lowq(P, at_q): the column counts as LOWQ at quality at_q
+struct Column {
+    const uint8_t *sq, *ql; int64_t x; uint32_t yi; bool has_q, del;
+    PU_HD void load(uint32_t &cls, uint32_t &q) const {
+        cls = PU_DEL; q = 0;
+        if (!del) { cls = reduce::read_class(sq, yi); if (has_q) q = ql[yi]; }
+    }
+    PU_HD bool lowq(const Params &P, uint32_t at_q) const { return !del && has_q && (int32_t)at_q < P.min_baseq; }
+};
+
+// The one CIGAR walk of the pileup pair, for an eligible record whose scan gave `first`, by lane `lane` of the record's `nlanes`: the lanes
+// stride over the columns of each M / = / X / D op, clipped to every interval the op meets, lane 0 takes the insertions.  at(P, column, cls)
+// is what happens at one column: the class the record adds there, or false, not mine -- rule W's ColumnW below, rule V's fragpile::ColumnV
+// (gce_fragpile.hpp).  add(i): counter i (site * 16 + strand * 8 + class) += 1.  Reads stay inside the record (the scan checked its fields
+// against block_size and the CIGAR's query length against l_seq); i < 16 * the number of sites.
+template <class AT, class ADD> PU_HD void walk_record(const uint8_t *r, const Params &P, const Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, AT &at, ADD &add) {
+    const reduce::Head h(r);
+    const uint32_t sbase = ((h.flag >> 4) & 1u) * 8u, tend = S.tfirst[h.tid + 1];
+    const bool has_q = h.has_q();
+    uint32_t cur = first, q = 0; int64_t x = h.pos; bool seen = false;
+    for (uint32_t k = 0; k < h.nc; k++) {
+        const uint32_t w = *(const reduce::rd_u32u *)(h.cg + 4 * k), op = w & 15u, len = w >> 4;
         if (op == 0 || op == 7 || op == 8 || op == 2) {
             cur = seek(S, cur, tend, x);
             const int64_t xe = x + len;
@@ -71,13 +84,8 @@ template <class ADD> PU_HD void count_record(const uint8_t *r, const Params &P, 
                 const Ivl v = S.iv[j];
                 const int64_t a = x > v.start ? x : (int64_t)v.start, z = xe < v.end ? xe : (int64_t)v.end;
                 for (int64_t col = a + lane; col < z; col += nlanes) {
-                    uint32_t cls = PU_DEL;
-                    if (op != 2) {
-                        const uint32_t yi = q + (uint32_t)(col - x), nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
-                        cls = nib == 1 ? PU_A : nib == 2 ? PU_C : nib == 4 ? PU_G : nib == 8 ? PU_T : PU_N;
-                        if (has_q && (int32_t)ql[yi] < P.min_baseq) cls = PU_LOWQ;
-                    }
-                    add((v.site0 + (uint32_t)(col - v.start)) * 16u + sbase + cls);
+                    uint32_t cls;
+                    if (at(P, Column{h.sq, h.ql, col, q + (uint32_t)(col - x), has_q, op == 2}, cls)) add((v.site0 + (uint32_t)(col - v.start)) * 16u + sbase + cls);
                 }
             }
             x = xe; if (op != 2) q += len;
@@ -92,6 +100,20 @@ template <class ADD> PU_HD void count_record(const uint8_t *r, const Params &P, 
         } else if (op == 4) q += len;
     }
 }
+// rule W at one column: the raw class, LOWQ for a base under min_baseq
+struct ColumnW {
+    PU_HD bool operator()(const Params &P, const Column &c, uint32_t &cls) const {
+        uint32_t q;
+        c.load(cls, q);
+        if (c.lowq(P, q)) cls = PU_LOWQ;
+        return true;
+    }
+};
+// rule W for a record alone
+template <class ADD> PU_HD void count_record(const uint8_t *r, const Params &P, const Sites &S, uint32_t first, uint32_t lane, uint32_t nlanes, ADD &add) {
+    ColumnW at;
+    walk_record(r, P, S, first, lane, nlanes, at, add);
+}
 
 #undef PU_HD
 
@@ -101,7 +123,7 @@ template <class ADD> PU_HD void count_record(const uint8_t *r, const Params &P, 
 
 namespace {
 
-// The LDS tile of k_pile_count: PU_TILE sites x 16 counters x 4 bytes.  A CU of the MI355X has 160 KiB of LDS and holds 32 waves; a block of
+// The LDS tile of k_pile_count and k_frag_count (PileAdd below): PU_TILE sites x 16 counters x 4 bytes.  A CU of the MI355X has 160 KiB of LDS and holds 32 waves; a block of
 // 256 threads is 4 waves, so 8 blocks fill a CU and each may hold 160 KiB / 8 = 20 KiB.  256 sites are 16 KiB (+ 64 bytes of tile starts): a
 // block's 16 reads of a sorted panel span a read length and a little.
 #define PU_TILE 256u
@@ -119,7 +141,9 @@ struct PileScan {
     __device__ uint32_t ops(const Rec &R) const { return R.nc; }
 };
 
-// an add of k_pile_count: into the block's tile when the counter lies in it, else to memory
+// The adds of k_pile_count and k_frag_count (gce_fragpile.hpp), 16 lanes per record and 16 records per block of 256: into the block's tile
+// when the counter lies in it, else to memory.  The tile starts at the first site the block's first overlapping record can touch.  DIRECT: no
+// tile, every add is a global atomic
 template <bool DIRECT> struct PileAdd {
     uint32_t *tile, *counts; uint32_t base16;
     __device__ __forceinline__ void operator()(uint32_t idx) {
@@ -127,93 +151,84 @@ template <bool DIRECT> struct PileAdd {
         if (!DIRECT && d < PU_TILE * 16u) atomicAdd(tile + d, 1u);
         else atomicAdd(counts + idx, 1u);
     }
-};
-// 16 lanes per record, 16 records per block (block b: records [16 b, 16 b + 16) of the window); n_counts: 16 x the number of sites
-template <bool DIRECT> __global__ __launch_bounds__(256) void k_pile_count(const uint8_t *u, const uint64_t *off, uint64_t n, pileup::Params P, pileup::Sites S, const uint32_t *meta,
-                                                                           uint32_t *counts, uint64_t n_counts) {
-    __shared__ uint32_t s_tile[DIRECT ? 1 : PU_TILE * 16u];
-    __shared__ uint32_t s_base[16];
-    const uint32_t g = threadIdx.x >> 4, sub = threadIdx.x & 15u;
-    const uint64_t j = (uint64_t)blockIdx.x * 16u + g;
-    const uint32_t first = j < n ? meta[j] : PU_NONE;
-    uint32_t base = 0;
-    if (!DIRECT) {
+    // The tile zeroed and placed, by the whole block.  rec(): the record of this thread's slot (threadIdx.x >> 4) whose scan gave `first`, asked
+    // for by the slot's first lane, and not when first is PU_NONE: the record is skipped or touches no site.  false, for the whole block: no
+    // record of it touches a site, and no barrier may follow
+    template <class REC> __device__ __forceinline__ bool open(uint32_t first, const pileup::Sites &S, uint32_t *counts_, REC &&rec) {
+        __shared__ uint32_t s_tile[DIRECT ? 1 : PU_TILE * 16u];
+        __shared__ uint32_t s_base[16];
+        tile = s_tile; counts = counts_; base16 = 0;
+        if (DIRECT) return true;
         for (uint32_t i = threadIdx.x; i < PU_TILE * 16u; i += 256u) s_tile[i] = 0u;
-        if (sub == 0) {                                                               // the first site this record can touch: that of max(pos - 1, the interval's start)
+        if ((threadIdx.x & 15u) == 0) {                                               // the first site this record can touch: that of max(pos - 1, the interval's start)
             uint32_t b = PU_NONE;
             if (first != PU_NONE) {
-                const int32_t pos = (int32_t)rb32(u + off[j] + 8);
+                const int32_t pos = (int32_t)rb32(rec() + 8);
                 const pileup::Ivl v = S.iv[first];
                 b = v.site0 + (uint32_t)(max(pos - 1, v.start) - v.start);
             }
-            s_base[g] = b;
+            s_base[threadIdx.x >> 4] = b;
         }
         __syncthreads();
-        base = PU_NONE;
+        uint32_t base = PU_NONE;
 #pragma unroll
         for (int k = 15; k >= 0; k--) if (s_base[k] != PU_NONE) base = s_base[k];       // the block's first overlapping record's
-        if (base == PU_NONE) return;                                                  // (the whole block: no record of it touches a site)
+        base16 = base * 16u;
+        return base != PU_NONE;
     }
-    PileAdd<DIRECT> add{s_tile, counts, base * 16u};
-    if (first != PU_NONE) pileup::count_record(u + off[j], P, S, first, sub, 16u, add);
-    if (!DIRECT) {
+    // the tile's non-zero counters to memory, one global atomic each, by the whole block; n_counts: 16 x the number of sites
+    __device__ __forceinline__ void flush(uint64_t n_counts) {
+        if (DIRECT) return;
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < PU_TILE * 16u; i += 256u) {
-            const uint32_t v = s_tile[i];
-            const uint64_t at = (uint64_t)base * 16u + i;
+            const uint32_t v = tile[i];
+            const uint64_t at = (uint64_t)base16 + i;
             if (v && at < n_counts) atomicAdd(counts + at, v);
         }
     }
+};
+// block b: records [16 b, 16 b + 16) of the window
+template <bool DIRECT> __global__ __launch_bounds__(256) void k_pile_count(const uint8_t *u, const uint64_t *off, uint64_t n, pileup::Params P, pileup::Sites S, const uint32_t *meta,
+                                                                           uint32_t *counts, uint64_t n_counts) {
+    const uint64_t j = (uint64_t)blockIdx.x * 16u + (threadIdx.x >> 4);
+    const uint32_t first = j < n ? meta[j] : PU_NONE;
+    PileAdd<DIRECT> add;
+    if (!add.open(first, S, counts, [&] { return u + off[j]; })) return;
+    if (first != PU_NONE) pileup::count_record(u + off[j], P, S, first, threadIdx.x & 15u, 16u, add);
+    add.flush(n_counts);
 }
 
 }  // namespace
 
-struct gce_pileup : ReduceSession {
+// The device object of a pileup pass: what gce_pileup and gce_fragpile (gce_fragpile.hpp) hold alike.  needs() stays the pass's own.
+struct PileSession : ReduceSession {
     pileup::Params P{0, 0, 0, 0}; bool direct = false;
     DevBuf counts; uint64_t n_sites = 0;                                              // 64 bytes per site
+    // The instantiation of a count kernel k<DIRECT>: launch(std::bool_constant<DIRECT>) names the kernel as k<decltype(D)::value>
+    template <class LAUNCH> void dispatch(LAUNCH &&launch) const { if (direct) launch(std::true_type{}); else launch(std::false_type{}); }
+};
+struct gce_pileup : PileSession {
     std::string needs() const override { return "gce_bam_pileup needs 64 bytes per site (" + std::to_string(n_sites) + " sites: " + std::to_string(n_sites * 64) + " bytes)"; }
 };
 
-extern "C" {
-
-int gce_pileup_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_pileup **out) {
-    return rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, (uint32_t)GCE_PILEUP_DIRECT, out);
-}
-void gce_pileup_destroy(gce_pileup *p) { if (p) rd_destroy(p, {&p->counts}); }
-const char *gce_pileup_error(gce_pileup *p) { return p ? p->err.c_str() : ""; }
-
-// rule S's intervals, once, in front of the first window: interval j = [start[j], end[j]) of contig tid[j], in (tid, start) order, disjoint and
-// not abutting, inside the contig; site0[j]: the site index of start[j] (the sum of the lengths in front of it).  The counters are made and zeroed.
-int gce_pileup_set_sites(gce_pileup *p, int32_t n_ref, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, const uint32_t *site0) {
+// gce_pileup_set_sites and gce_fragpile_set_sites: rule S's intervals, once, in front of the first window: interval j = [start[j], end[j]) of
+// contig tid[j], in (tid, start) order, disjoint and not abutting, inside the contig; site0[j]: the site index of start[j] (the sum of the
+// lengths in front of it).  The counters are made and zeroed.  entry: the entry point that names itself in the refusal
+static int pu_set_sites(PileSession *p, const char *entry, int32_t n_ref, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, const uint32_t *site0) {
     if (!p || p->sites_set || n_ref < 0 || n_intervals < 0 || (n_intervals && (!tid || !start || !end || !site0))) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     RdTable t;
-    const int rc = rd_intervals(p, "gce_pileup_set_sites", n_ref, n_intervals, tid, start, end, t);
+    const int rc = rd_intervals(p, entry, n_ref, n_intervals, tid, start, end, t);
     if (rc != GCE_OK) return rc;
-    for (int64_t j = 0; j < n_intervals; j++) if (site0[j] != t.iv[(size_t)j].site0) return p->out_of_order("gce_pileup_set_sites");
+    for (int64_t j = 0; j < n_intervals; j++) if (site0[j] != t.iv[(size_t)j].site0) return p->out_of_order(entry);
     if (t.sites > PU_MAX_SITES) return p->fail(GCE_ERR_INVALID, "more than 2^28 sites");
     p->n_sites = t.sites; p->P.n_ref = n_ref;
     return rd_set_sites(p, t, p->counts, t.sites * 64 + 64, 9);
 }
-
-// the next piece of the file, as gce_bai_window takes it; *pileup_s: the seconds of the scan and k_pile_count, added to.  GCE_ERR_INVALID
-// names the lowest malformed record, counting from 0 over the file.
-int gce_pileup_window(gce_pileup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
-                      int32_t n_ref, int32_t last, double *pileup_s) {
-    if (!p) return GCE_ERR_INVALID;
-    const pileup::Sites S = p->sites();
-    return rd_window(p, PileScan{p->P, S}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, pileup_s, [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t) {
-        if (!p->n_sites) return false;
-        const unsigned nb = (unsigned)((n_rec + 15) / 16);
-        if (p->direct) hipLaunchKernelGGL(k_pile_count<true>, dim3(nb), dim3(256), 0, p->s, u, off, n_rec, p->P, S, (const uint32_t *)p->meta.p, p->counts.as<uint32_t>(), p->n_sites * 16);
-        else hipLaunchKernelGGL(k_pile_count<false>, dim3(nb), dim3(256), 0, p->s, u, off, n_rec, p->P, S, (const uint32_t *)p->meta.p, p->counts.as<uint32_t>(), p->n_sites * 16);
-        return true;
-    });
-}
-
-// after the last window: counters[0] records, [1..6] the skip counters of rule E in its order, [7] eligible; counts_out (NULL, or room for
-// 16 uint32 per site): the counters.  GCE_ERR_INVALID when the eligible records' n_cigar_op sum to 2^32 or more.
-int gce_pileup_finish(gce_pileup *p, int64_t counters[8], uint32_t *counts_out) {
+// gce_pileup_finish and the first part of gce_fragpile_finish, after the last window: counters[0] records, [1..6] the skip counters of rule E
+// in its order, [7] eligible; counts_out (NULL, or room for 16 uint32 per site): the counters.  GCE_ERR_INVALID when the eligible records'
+// n_cigar_op sum to 2^32 or more.
+static int pu_finish(PileSession *p, int64_t *counters, uint32_t *counts_out) {
     if (!p || !p->sites_set || !counters) return GCE_ERR_INVALID;
     (void)hipSetDevice(p->device);
     hipStream_t s = p->s;
@@ -225,6 +240,36 @@ int gce_pileup_finish(gce_pileup *p, int64_t counters[8], uint32_t *counts_out) 
     RDCHK(hipGetLastError());
     return GCE_OK;
 }
+
+extern "C" {
+
+int gce_pileup_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_pileup **out) {
+    return rd_create(device, device_budget_bytes, min_mapq, min_baseq, exclude_flags, options, (uint32_t)GCE_PILEUP_DIRECT, out);
+}
+void gce_pileup_destroy(gce_pileup *p) { if (p) rd_destroy(p, {&p->counts}); }
+const char *gce_pileup_error(gce_pileup *p) { return p ? p->err.c_str() : ""; }
+
+int gce_pileup_set_sites(gce_pileup *p, int32_t n_ref, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end, const uint32_t *site0) {
+    return pu_set_sites(p, "gce_pileup_set_sites", n_ref, n_intervals, tid, start, end, site0);
+}
+
+// the next piece of the file, as gce_bai_window takes it; *pileup_s: the seconds of the scan and k_pile_count, added to.  GCE_ERR_INVALID
+// names the lowest malformed record, counting from 0 over the file.
+int gce_pileup_window(gce_pileup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                      int32_t n_ref, int32_t last, double *pileup_s) {
+    if (!p) return GCE_ERR_INVALID;
+    const pileup::Sites S = p->sites();
+    return rd_window(p, PileScan{p->P, S}, p->P.n_ref, comp, comp_bytes, n_members, coff, csize, usize, skip, n_ref, last, pileup_s, [&](const uint8_t *u, const uint64_t *off, uint64_t n_rec, uint64_t) {
+        if (!p->n_sites) return false;
+        p->dispatch([&](auto D) {
+            hipLaunchKernelGGL(k_pile_count<decltype(D)::value>, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, p->s, u, off, n_rec, p->P, S, (const uint32_t *)p->meta.p, p->counts.as<uint32_t>(),
+                               p->n_sites * 16);
+        });
+        return true;
+    });
+}
+
+int gce_pileup_finish(gce_pileup *p, int64_t counters[8], uint32_t *counts_out) { return pu_finish(p, counters, counts_out); }
 
 }  // extern "C"
 #endif  // GCE_PILEUP_HOST_CHECK

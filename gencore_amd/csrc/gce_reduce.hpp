@@ -2,8 +2,9 @@
 // (gce_errprof.hpp) share, and what a third pass of their kind starts from (gce_errsup.hpp, DESIGN.md 4n, is one).  Such a pass streams the file window by window
 // (win_inflate_index / win_carry, gce_passes.hpp) and keeps nothing of a window but what it added to counters that stay on the device: per window
 // k_reduce_scan runs one thread per record over the pass's scan functor and leaves 4 bytes of meta per record, then the pass's own count kernels
-// walk the records the meta keeps.  reduce::rule_e (the malformed-record test and rule E) and rule S's interval table with its searches are
-// __host__ __device__: the passes' host checks (tests/pileup_host_check.hip, tests/errprof_host_check.hip) compile that half alone.
+// walk the records the meta keeps.  reduce::rule_e (the malformed-record test and rule E), rule S's interval table with its searches, the
+// decode of a record's header (reduce::Head) and the class of a 4-bit base (reduce::read_class) are __host__ __device__: the passes' host
+// checks (tests/pileup_host_check.hip, tests/errprof_host_check.hip) compile that half alone.
 // ReduceSession is the device object: the out-of-memory message, the interval upload, the window sequence and the counter read-back, once.
 #pragma once
 #include <cstdint>
@@ -68,6 +69,25 @@ RD_HD uint32_t seek(const Sites &S, uint32_t cur, uint32_t tend, int64_t x) {
     uint32_t lo = cur + 1, hi = tend;
     while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((int64_t)S.iv[mid].end < x) lo = mid + 1; else hi = mid; }
     return lo;
+}
+
+// The fields of a record (r at its block_size) that the CIGAR walks read, decoded once: the passes' walks for the record they walk,
+// fragpile::column and errprof::Cursor for the partner.  The constructor reads the record's fixed part alone; has_q() reads the first quality
+// byte, which lies behind the sequence: a walk asks once and keeps the answer, fragpile::column asks only at a column it has found
+struct Head {
+    const uint8_t *cg, *sq, *ql; int32_t tid, pos, lseq; uint32_t nc, flag;
+    RD_HD explicit Head(const uint8_t *r) {
+        const uint8_t *c = r + 4;
+        tid = (int32_t) * (const rd_u32u *)(c + 0); pos = (int32_t) * (const rd_u32u *)(c + 4); lseq = (int32_t) * (const rd_u32u *)(c + 16);
+        nc = *(const rd_u16u *)(c + 12); flag = *(const rd_u16u *)(c + 14);
+        cg = c + 32 + c[8]; sq = cg + 4 * nc; ql = sq + ((uint32_t)lseq + 1) / 2;
+    }
+    RD_HD bool has_q() const { return ql[0] != 0xFF; }
+};
+// the class of a read's 4-bit base: 0..3 = A C G T, 4 = anything else
+RD_HD uint32_t read_class(const uint8_t *sq, uint32_t yi) {
+    const uint32_t nib = (sq[yi >> 1] >> ((~yi & 1u) << 2)) & 15u;
+    return nib == 1 ? 0u : nib == 2 ? 1u : nib == 4 ? 2u : nib == 8 ? 3u : 4u;
 }
 
 #undef RD_HD

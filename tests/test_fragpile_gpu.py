@@ -1,7 +1,7 @@
 """gce_bam_pileup_fragments on the GPU: the order check and the join (k_frag_prep, k_frag_join), k_frag_count with the LDS tile and
 with direct atomics, with the full and the weak hash where the join is the subject, and the carry across windows, against the model
 (tests/pyfragpile.py) and the hand-written counters (tests/fragcases.py): every integer equal.  The cases are the smallest at which the
-kernels can go wrong: rule V column by column, the overlap's geometry, every way not to be a pair, a pair across a 16-record block, 300
+kernels can go wrong: rule V column by column, the overlap's geometry, every way not to be a pair, a pair across a 16-record block, mates on a tile's edge, 300
 pairs at one locus, mates in different windows and every way a waiting record expires, rule P inside a window and on a window's first
 record, the budget, one generated paired stream, the table's bytes and the command line."""
 import os
@@ -16,6 +16,7 @@ import pyfragpile
 import pypileup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TILE = int(re.search(r"#define PU_TILE (\d+)u", open(os.path.join(ROOT, "gencore_amd", "csrc", "gce_pileup.hpp")).read()).group(1))
 VARIANTS = pytest.mark.parametrize("direct", [False, True], ids=["tile", "direct"])
 HASHES = pytest.mark.parametrize("weak", [False, True], ids=["hash", "weak_hash"])
 BIG = (["c0", "c1"], [20000, 3000])
@@ -85,6 +86,42 @@ def test_300_pairs_at_one_locus(built, tmp_path, direct, weak):
     run, res = run_files(tmp_path, a + b[::-1], fc.T, pc.NAMES, pc.LENS, direct, weak, min_baseq=13)
     assert res["n_pairs"] == 300 == res["n_shared_columns"] and 150 < res["n_disagree_columns"] < 300 and res["n_ambiguous"] == 0
     same(run, res, deferred=0)
+
+
+def tile_edge_records():
+    """one sorted block of 6 entries on one interval [0, 3 TILE) of c0 of BIG.  The first record lies at pos 100, so the block's tile holds
+    the sites [99, 99 + TILE).  Pair `edge` shares the four columns e - 2 .. e + 1 around the tile's end e = 99 + TILE: they agree at e - 2
+    and e (a is counted, inside and behind the tile), differ at e - 1 (b is of higher quality: the later mate adds to the tile's last site)
+    and at e + 1 (a is: the earlier mate adds behind the tile).  Pair `far` shares two columns behind an N skip of 2 TILE, one agreeing and
+    one not.  A single read ends exactly on the tile's last site."""
+    e = 99 + TILE
+    return [pc.rec(0, 100, "3M", "ACG", name="first"),
+            fc.ma("ACGT", pos=101, cigar="1M%dN3M" % (2 * TILE), next_pos=103 + 2 * TILE, name="far"),
+            fc.ma("ACGTAC", [30] * 6, pos=e - 4, cigar="6M", next_pos=e - 2, name="edge"),
+            pc.rec(0, e - 3, "3M", "CCC", name="single"),
+            fc.mb("GAAGTT", [40, 40, 30, 20, 30, 30], pos=e - 2, cigar="6M", next_pos=e - 4, name="edge"),
+            fc.mb("GAT", pos=103 + 2 * TILE, cigar="3M", next_pos=101, name="far")]
+
+
+@pytest.mark.gpu
+@VARIANTS
+def test_paired_mates_at_the_tile_edges(built, tmp_path, direct):
+    """rule V's adds on the last site of a block's tile, on the first site behind it and far behind it over an N skip, by either mate: the
+    model's counters, and the tile and the direct kernel agree"""
+    e = 99 + TILE
+    bed = [("c0", 0, 3 * TILE)]
+    recs = tile_edge_records()
+    assert len(recs) <= 16
+    run, res = run_files(tmp_path, recs, bed, *BIG, direct)
+    assert (res["n_pairs"], res["n_shared_columns"], res["n_disagree_columns"]) == (2, 6, 3)
+    same(run, res, deferred=0)
+    assert run.n_shared_columns == res["n_shared_columns"] and run.n_disagree_columns == res["n_disagree_columns"]
+    c = run.counts.reshape(-1, 16)
+    assert c[e - 1].sum() > 0 and c[e].sum() > 0 and c[103 + 2 * TILE].sum() > 0
+    assert c[e - 1].tolist() == [0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0]      # the single read's C; b's A, reverse, over a's T
+    assert c[e].tolist() == [1] + [0] * 15 and c[e + 1].tolist() == [0, 1] + [0] * 14   # a's A where they agree; a's C over b's G
+    other, _ = run_files(tmp_path, recs, bed, *BIG, not direct)
+    assert (other.counts == run.counts).all() and other.n_shared_columns == run.n_shared_columns and other.n_disagree_columns == run.n_disagree_columns
 
 
 def window_stream(tail):

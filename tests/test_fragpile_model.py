@@ -122,8 +122,11 @@ def test_symbol_prototype_and_argument_checks(built, tmp_path):
 
 
 def test_tile_is_checked_and_pileup_untouched():
+    # k_frag_count's tile is k_pile_count's, PileAdd: its size is checked where it is declared, and gce_fragpile.hpp declares none of its own
     src = open(os.path.join(ROOT, "gencore_amd", "csrc", "gce_fragpile.hpp")).read()
-    assert "static_assert(FP_TILE * 64u + 64u <= PU_LDS_PER_CU / PU_BLOCKS_PER_CU" in src and "#define FP_TILE PU_TILE" in src
+    pile = open(os.path.join(ROOT, "gencore_amd", "csrc", "gce_pileup.hpp")).read()
+    assert "static_assert(PU_TILE * 64u + 64u <= PU_LDS_PER_CU / PU_BLOCKS_PER_CU" in pile and pile.count("__shared__ uint32_t s_tile[DIRECT ? 1 : PU_TILE * 16u]") == 1
+    assert "PileAdd<DIRECT> add;" in src and "add.open(" in src and "add.flush(" in src and "__shared__" not in src and "_TILE" not in src
     head = open(os.path.join(ROOT, "include", "gencore_amd.h")).read()
     assert "Overlapping mates are counted twice, there is no BAQ and no split by read group." in re.sub(r"\s*\n \* ", " ", head)
 

@@ -11,7 +11,11 @@ own, gives the kernel times.  There is no pass mark.
     python tools/pileup_bench.py --fragments [--out profiles/pileup_fragments.json]
 runs gce_bam_pileup_fragments (frag_tile, frag_direct) beside gce_bam_pileup (tile, direct) on the same file in the same
 interleaved rounds: both passes' pileup_s with all values and the median, the new pass's share of its total_s, tile against direct, and one
-kernel trace per variant.  No time is fixed for the join or the paired walk; the pass is opt-in and no default rides on the outcome."""
+kernel trace per variant.  No time is fixed for the join or the paired walk; the pass is opt-in and no default rides on the outcome.
+    python tools/pileup_bench.py --fragments --parent_lib PATH [--out ...]
+runs the library built from the parent commit (loaded through GCE_LIB) in the same rounds as tools/errprof_bench.py does: parent_tile,
+parent_direct, parent_frag_tile and parent_frag_direct.  Per pair it reports this_minus_parent_s, the spread, `unchanged` (the medians of
+pileup_s differ by less than the spread of the values) and counters_identical (the CRC of the counts and the n_* counters but n_deferred)."""
 import argparse
 import csv
 import glob
@@ -25,6 +29,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+FRAG_MODES = ("tile", "frag_tile", "direct", "frag_direct")
+PARENT_MODES = tuple("parent_" + m for m in FRAG_MODES)
 
 
 def child(args):
@@ -36,13 +42,14 @@ def child(args):
     with open(src, "rb") as f:                                    # the input in the page cache
         while f.read(1 << 26):
             pass
+    mode = args.mode[len("parent_"):] if args.mode.startswith("parent_") else args.mode   # (the parent's library is GCE_LIB's doing, run_child)
     t0 = time.perf_counter()
-    if args.mode == "index":
+    if mode == "index":
         d = bamio.index_bam(src, os.path.join(args.child, "in.bam.bai"), threads=args.threads)
         d = {k: v for k, v in (d if isinstance(d, dict) else vars(d)).items() if isinstance(v, (int, float))}
     else:
-        run = bamio.pileup_fragments_bam if args.mode.startswith("frag_") else bamio.pileup_bam
-        r = run(src, bed, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads, direct=args.mode.endswith("direct"))
+        run = bamio.pileup_fragments_bam if mode.startswith("frag_") else bamio.pileup_bam
+        r = run(src, bed, tsv=os.path.join(args.child, "%s.tsv" % args.mode), threads=args.threads, direct=mode.endswith("direct"))
         d = dict(r.as_dict(), counts_sum=int(r.counts.sum()), counts_crc=int(__import__("zlib").crc32(r.counts.tobytes())))
     print(json.dumps(dict(d, wall_s=time.perf_counter() - t0)), flush=True)
 
@@ -66,8 +73,9 @@ def child_make(args):
 
 
 def run_child(args, tmp, mode, prefix=(), limit=300):
+    env = dict(os.environ, GCE_LIB=os.path.abspath(args.parent_lib)) if mode.startswith("parent_") else None
     p = subprocess.run(["timeout", "-k", "10", str(limit)] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", tmp, "--mode", mode, "--threads", str(args.threads),
-                                                                           "--workload", args.workload, "--pairs", str(args.pairs)], stdout=subprocess.PIPE, universal_newlines=True)
+                                                                           "--workload", args.workload, "--pairs", str(args.pairs)], stdout=subprocess.PIPE, universal_newlines=True, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:
         raise SystemExit("pileup_bench: a child run (%s) failed (exit %d)" % (mode, p.returncode))
@@ -98,8 +106,9 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--child", default=None)
-    ap.add_argument("--mode", default="tile", choices=("make", "tile", "direct", "index", "frag_tile", "frag_direct"))
+    ap.add_argument("--mode", default="tile", choices=("make", "index") + FRAG_MODES + PARENT_MODES)
     ap.add_argument("--fragments", action="store_true", help="gce_bam_pileup_fragments beside gce_bam_pileup; writes profiles/pileup_fragments.json")
+    ap.add_argument("--parent_lib", default=None, help="with --fragments: the parent commit's libgencore_amd.so, run in the same rounds through GCE_LIB")
     args = ap.parse_args()
     if args.child is not None:
         return child_make(args) if args.mode == "make" else child(args)
@@ -151,7 +160,7 @@ def main_fragments(args):
     args.out = args.out or os.path.join(ROOT, "profiles", "pileup_fragments.json")
     tmp = args.dir or tempfile.mkdtemp(prefix="gce_fragpile_")
     made = run_child(args, tmp, "make", limit=600)
-    modes = ("tile", "frag_tile", "direct", "frag_direct")
+    modes = FRAG_MODES + (PARENT_MODES if args.parent_lib else ())
     per = {m: [] for m in modes}
     for rep in range(args.reps + 1):                               # interleaved; the first round is the warm-up
         for m in modes:
@@ -175,7 +184,15 @@ def main_fragments(args):
     res["pileup_s_ratio"] = dict(frag_tile_over_tile=round(v["frag_tile"]["stages"]["pileup_s"] / v["tile"]["stages"]["pileup_s"], 3),
                                  frag_direct_over_direct=round(v["frag_direct"]["stages"]["pileup_s"] / v["direct"]["stages"]["pileup_s"], 3),
                                  frag_tile_over_frag_direct=round(v["frag_tile"]["stages"]["pileup_s"] / v["frag_direct"]["stages"]["pileup_s"], 3))
-    for m in modes:
+    if args.parent_lib:
+        spread = lambda rs: max(r["pileup_s"] for r in rs) - min(r["pileup_s"] for r in rs)
+        same = lambda a, b: v[a]["counts_crc"] == v[b]["counts_crc"] and {k: c for k, c in v[a]["counters"].items() if k != "n_deferred"} == {k: c for k, c in v[b]["counters"].items() if k != "n_deferred"}
+        res["against_the_parent"] = {}
+        for m in FRAG_MODES:
+            gap, noise = v[m]["stages"]["pileup_s"] - v["parent_" + m]["stages"]["pileup_s"], max(spread(per[m]), spread(per["parent_" + m]))
+            res["against_the_parent"][m] = dict(rule="pileup_s is unchanged when the medians differ by less than the spread of the values", this_minus_parent_s=round(gap, 5),
+                                                spread_s=round(noise, 5), unchanged=abs(gap) <= noise, counters_identical=same(m, "parent_" + m))
+    for m in FRAG_MODES:
         v[m]["kernels"] = dict(source="rocprofv3 --kernel-trace --stats, one run of this variant in a process of its own", **kernel_times(args, tmp, m))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp, bamio_fragerr.hpp and bamio_errsup.hpp (the last five over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp, bamio_fragerr.hpp, bamio_errsup.hpp and bamio_errqual.hpp (the last six over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -461,6 +461,49 @@ def error_profile_support_bam(path, fasta, mask=None, bed=None, tsv=None, tags=(
         return ErrorProfileSupportRun(r, None if mask is None else m)
     finally:
         lib.gce_errsup_free(C.byref(r))
+
+
+class ErrorProfileQualityRun:
+    """gce_errqual_run as an object: the counters and bytes as int, the times as float, and the numpy array counts ([3 segments, 96 quality
+    buckets, 24 classes], uint64: bucket 0..93 is the QUAL byte, 94 every other byte, 95 a record without qualities; classes 0..20 are
+    ErrorProfileRun.CLASSES, 21 MASKED, 22 and 23 zero).  With a mask, gce_mask_run's fields as ErrorProfileRun names them."""
+    CLASSES = ErrorProfileRun.CLASSES + ("MASKED",)
+
+    def __init__(self, r, mask=None):
+        from .capi import GCE_ERRPROF_CLASSES, GCE_ERRQUAL_BUCKETS
+        _copy_run_fields(self, r, mask)
+        shape = (3, GCE_ERRQUAL_BUCKETS, GCE_ERRPROF_CLASSES)
+        self.counts = np.ctypeslib.as_array(r.counts, (int(np.prod(shape)),)).copy().reshape(shape)
+
+    def as_dict(self):
+        return {k: v for k, v in vars(self).items() if k != "counts"}
+
+
+def error_profile_quality_bam(path, fasta, mask=None, bed=None, tsv=None, direct=False, device=0, threads=0, min_mapq=0, min_baseq=0, exclude_flags=0x704, window_bytes=0,
+                              device_budget_bytes=0):
+    """gce_bam_error_profile_quality: error_profile_bam's classes, walk, BED and (with `mask`, as error_profile_masked_bam takes it) variant
+    mask, tabulated not by cycle but by the base quality the file reports: of the bases at quality q, how many differ from the reference.
+    Over the input it holds the sequencer's qualities against an error rate, over the consensus output the qualities the consensus step
+    wrote.  The bucket of an event is the QUAL byte of its query base (an inserted base's own, a deletion's the base in front of it):
+    0..93 as it is, 94 every other byte, 95 for a record without qualities.  Summed over the buckets the table is error_profile_bam's summed
+    over the cycles.  tsv: the table's path (segment, quality (the number, `94+` or `.`), bases, mismatches, the 21 counters, MASKED with a
+    mask; one row per (segment, quality) with a counter), or None.  direct=True makes every add a 64-bit global atomic instead of meeting
+    in the kernel's table on chip: the same counters.  Returns an ErrorProfileQualityRun (error_profile_bam's totals and counts [3, 96,
+    24]); raises GceError with the library's message (and leaves no table) on failure."""
+    from .capi import GCE_ERRQUAL_DIRECT, GceErrqualRun, GceMaskRun
+    lib = capi.load_library()
+    r, m = GceErrqualRun(), GceMaskRun()
+    err = (C.c_char * 256)()
+    enc = lambda x: None if x is None else str(x).encode()
+    rc = lib.gce_bam_error_profile_quality(str(path).encode(), str(fasta).encode(), enc(bed), enc(mask), enc(tsv), int(device), int(threads), int(min_mapq), int(min_baseq),
+                                           int(exclude_flags), GCE_ERRQUAL_DIRECT if direct else 0, int(window_bytes), int(device_budget_bytes), C.byref(r),
+                                           None if mask is None else C.byref(m), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    try:
+        return ErrorProfileQualityRun(r, None if mask is None else m)
+    finally:
+        lib.gce_errqual_free(C.byref(r))
 
 
 def load_mask(path, names, lens, threads=0):

@@ -109,7 +109,7 @@ EXPORTED_SYMBOLS = [
     "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free", "gce_bam_pileup_fragments", "gce_fragpile_free",
     "gce_bam_error_profile", "gce_errprof_free", "gce_bam_error_profile_fragments", "gce_fragerr_free",
     "gce_mask_load", "gce_mask_free", "gce_bam_error_profile_masked", "gce_bam_error_profile_fragments_masked",
-    "gce_bam_error_profile_support", "gce_errsup_free"]
+    "gce_bam_error_profile_support", "gce_errsup_free", "gce_bam_error_profile_quality", "gce_errqual_free"]
 
 GCE_PILEUP_DIRECT = 1
 GCE_FRAGPILE_DIRECT = 1
@@ -121,6 +121,8 @@ GCE_FRAGERR_DIRECT = 1
 GCE_FRAGERR_WEAK_HASH = 2
 GCE_ERRSUP_DIRECT = 1
 GCE_ERRSUP_BUCKETS = 33
+GCE_ERRQUAL_DIRECT = 1
+GCE_ERRQUAL_BUCKETS = 96
 
 
 class GceBamInfo(C.Structure):
@@ -213,6 +215,11 @@ class GceFragerrRun(C.Structure):
 class GceErrsupRun(C.Structure):
     """gce_errsup_run (gce_bam_error_profile_support): gce_errprof_run's fields with n_bad_aux behind the eight skips and the records that carry each tag."""
     _fields_ = GceErrprofRun._fields_[:10] + [("n_bad_aux", C.c_int64), ("n_with_forward", C.c_int64), ("n_with_reverse", C.c_int64)] + GceErrprofRun._fields_[10:]
+
+
+class GceErrqualRun(C.Structure):
+    """gce_errqual_run (gce_bam_error_profile_quality): gce_errprof_run's fields; counts is [3][96][24]."""
+    _fields_ = list(GceErrprofRun._fields_)
 
 
 class GceMask(C.Structure):
@@ -382,6 +389,11 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
                                                       C.c_uint32, C.c_uint64, C.c_size_t, C.POINTER(GceErrsupRun), C.POINTER(GceMaskRun), C.c_char_p]
         lib.gce_errsup_free.argtypes = [C.POINTER(GceErrsupRun)]
         lib.gce_errsup_free.restype = None
+    if hasattr(lib, "gce_bam_error_profile_quality"):                               # (the parent's build, loaded for an A/B run, lacks the pass)
+        lib.gce_bam_error_profile_quality.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_uint32,
+                                                      C.c_uint32, C.c_uint64, C.c_size_t, C.POINTER(GceErrqualRun), C.POINTER(GceMaskRun), C.c_char_p]
+        lib.gce_errqual_free.argtypes = [C.POINTER(GceErrqualRun)]
+        lib.gce_errqual_free.restype = None
     lib.gce_depth_run_free.argtypes = [C.POINTER(GceDepthRun)]
     lib.gce_depth_run_free.restype = None
     lib.gce_bed_load.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

@@ -65,6 +65,15 @@ mismatches over the bases of the rows forward = 1, 2, 3, ... are the residual er
 reverse count against those with `.` are duplex against single-strand.  It honours -b, --error_profile_mask, --error_profile_min_mapq and
 --error_profile_min_baseq; --error_profile_support_tags A,B reads two other integer tags (aD,bD: fgbio's duplex depths).  Every record is
 counted (overlapping mates twice), there is no cycle column and no split by read group.
+--error_profile_quality FILE and --error_profile_quality_in FILE (not the reference's) tabulate the same classes, on the GPU, by the base
+quality the records report (what GATK's recalibration table or Picard QualityScoreDistribution beside the artifact metrics are run for): of
+the bases at quality q, how many differ from -r.  --error_profile_quality_in reads the input as the run reads it, the sequencer's qualities;
+--error_profile_quality the BAM output (after --calmd), the qualities the consensus step wrote itself, which a caller that weights by QUAL
+trusts.  A row: segment, quality (the number, `94+` for a byte above 93, `.` for a record without qualities), bases, mismatches, the sixteen
+A>A .. T>T, READ_N REF_OTHER LOWQ INS DEL, and MASKED with --error_profile_mask; an inserted base counts at its own quality, a deletion at
+that of the base in front of it.  Both honour -b, --error_profile_mask, --error_profile_min_mapq and --error_profile_min_baseq (a base below
+it is LOWQ in its own quality's row).  --error_profile_fragments does not apply to them: every record is counted (overlapping mates twice),
+there is no cycle column and no split by read group.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -177,6 +186,14 @@ def build_parser():
     a("--error_profile_support_tags", default="FR,RR", metavar="A,B",
       help="[gencore_amd] --error_profile_support reads the forward count from tag A and the reverse count from tag B, two two-character tags of an integer type "
            "(aD,bD: fgbio's duplex depths). Default FR,RR.")
+    a("--error_profile_quality", default=None, metavar="FILE",
+      help="[gencore_amd] after the output is written (after --calmd, beside --error_profile, before --index), count mismatches against -r over the BAM output by the base "
+           "quality each record reports -- the qualities the consensus step wrote -- on the GPU (on the first of --devices, within --device_memory) and write the table to FILE: "
+           "one row per (segment, quality). Honours -b, --error_profile_mask, --error_profile_min_mapq and --error_profile_min_baseq; --error_profile_fragments does not apply "
+           "to it. Off by default.")
+    a("--error_profile_quality_in", default=None, metavar="FILE",
+      help="[gencore_amd] the same table over the input as the run reads it (after --sort / --sort_sam, --calmd_in and --umi_from), the sequencer's qualities, written to FILE "
+           "before the run. --error_profile_fragments does not apply to it. Off by default.")
     a("--level", type=int, default=6, help="[gencore_amd] BGZF compression level of a BAM output: 0..9 (zlib), -1 (fixed Huffman on the host), "
                                            "-2 (fixed Huffman on the GPU), -3 (the smallest of dynamic Huffman, fixed Huffman and stored per block, on the GPU). "
                                            "With an output name that ends in sam, -2 and -3 make the GPU write the SAM text; every other level leaves it to the host. Default 6.")
@@ -209,6 +226,8 @@ def validate(o):
         err("--pileup_in needs an input file, not STDIN")
     if o.error_profile_in is not None and o.input == "-":
         err("--error_profile_in needs an input file, not STDIN")
+    if o.error_profile_quality_in is not None and o.input == "-":
+        err("--error_profile_quality_in needs an input file, not STDIN")
     if o.umi_from is not None:
         u = o.umi_from
         if u != "name" and not (len(u) == 2 and u.isascii() and u[0].isalpha() and u[1].isalnum()):
@@ -324,8 +343,17 @@ def validate(o):
         err("--error_profile_support_tags needs two two-character tags, as in FR,RR")
     if o.error_profile_support_tags != "FR,RR" and o.error_profile_support is None:
         err("--error_profile_support_tags needs --error_profile_support")
+    if o.error_profile_quality is not None:
+        if o.output == "-":
+            err("--error_profile_quality needs an output file, not STDOUT")
+        if o.output.endswith("sam"):
+            err("--error_profile_quality needs BAM output, not SAM text")
+    if o.error_profile_quality_in is not None and not o.sort_sam:
+        with open(o.input, "rb") as f:
+            if f.read(2) != b"\x1f\x8b":
+                err("--error_profile_quality_in needs BAM input, not SAM text")
     if o.error_profile_mask is not None:
-        if o.error_profile is None and o.error_profile_in is None and o.error_profile_support is None:
+        if o.error_profile is None and o.error_profile_in is None and o.error_profile_support is None and o.error_profile_quality is None and o.error_profile_quality_in is None:
             err("--error_profile_mask needs --error_profile or --error_profile_in")
         check_file_valid(o.error_profile_mask)
         if not o.error_profile_mask.endswith((".vcf", ".vcf.gz", ".bed")):
@@ -383,6 +411,15 @@ def main(argv=None):
             sys.stderr.write("%s: %d pairs, %d shared columns, %d disagreeing\n" % (label, r.n_pairs, r.n_shared_columns, r.n_disagree_columns))
         if o.error_profile_mask is not None:
             sys.stderr.write("%s: mask %d intervals, %d bases, %d events masked\n" % (label, r.n_mask_intervals, r.n_masked_bases, r.n_masked_events))
+
+    def error_profile_quality(label, bam, tsv):
+        from .bamio import error_profile_quality_bam
+        r = error_profile_quality_bam(bam, o.ref, mask=o.error_profile_mask, bed=o.bed or None, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.error_profile_min_mapq,
+                                      min_baseq=o.error_profile_min_baseq, exclude_flags=0x704, device_budget_bytes=o.device_memory_bytes)
+        sys.stderr.write("%s: %d records, %d eligible, %d bases, %d mismatches, %d qualities\n"
+                         % (label, r.n_records, r.n_eligible, r.n_bases, r.n_mismatches, int((r.counts[:, :, :22].sum(axis=(0, 2)) != 0).sum())))
+        if o.error_profile_mask is not None:
+            sys.stderr.write("%s: mask %d intervals, %d bases, %d events masked\n" % (label, r.n_mask_intervals, r.n_masked_bases, r.n_masked_events))
     tmp_dir = None if o.output == "-" else os.path.dirname(os.path.abspath(o.output))
     try:
         if o.sort or o.sort_sam:                                            # the runners below read the sorted temporary file, unchanged
@@ -409,6 +446,8 @@ def main(argv=None):
             pileup("pileup_in", o.input, o.pileup_in)
         if o.error_profile_in is not None:
             error_profile("error_profile_in", o.input, o.error_profile_in)
+        if o.error_profile_quality_in is not None:
+            error_profile_quality("error_profile_quality_in", o.input, o.error_profile_quality_in)
         names, _ = read_header(o.input)
         region_names = [r[3] for r in load_bed(o.bed, names)] if o.bed else None
         out = "/dev/stdout" if o.output == "-" else o.output              # the runner only ever appends to its output: a pipe works
@@ -440,6 +479,8 @@ def main(argv=None):
                              % (r.n_records, r.n_eligible, r.n_bases, r.n_mismatches, r.n_with_forward, ft, r.n_with_reverse, rt))
             if o.error_profile_mask is not None:
                 sys.stderr.write("error_profile_support: mask %d intervals, %d bases, %d events masked\n" % (r.n_mask_intervals, r.n_masked_bases, r.n_masked_events))
+        if o.error_profile_quality is not None:
+            error_profile_quality("error_profile_quality", o.output, o.error_profile_quality)
         if o.index:
             index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:

@@ -23,6 +23,7 @@
 //   bamio_errprof.hpp gce_bam_error_profile
 //   bamio_fragerr.hpp gce_bam_error_profile_fragments
 //   bamio_errsup.hpp  gce_bam_error_profile_support
+//   bamio_errqual.hpp gce_bam_error_profile_quality
 // No part launches a kernel itself: the runners read the file, find its BGZF members and hand them, window by window, to the engine's entry
 // points in engine.hip (gce_raw_* of the public header; gce_passes_*, gce_bai_*, gce_sort_*, gce_pileup_*, gce_fragpile_*, gce_errprof_*, gce_fragerr_* of gce_entry.h, the one place they are declared),
 // which inflate, index, process, sort and deflate in HBM; the output comes back in pieces and is written on the host.
@@ -817,3 +818,4 @@ void gce_bed_free(int32_t n_regions, int32_t *tid, int32_t *start, int32_t *end,
 #include "bamio_errprof.hpp"
 #include "bamio_fragerr.hpp"
 #include "bamio_errsup.hpp"
+#include "bamio_errqual.hpp"

@@ -42,8 +42,8 @@ inline void errprof_table(const uint64_t *counts, const char *col3, const char *
     }
 }
 
-// What the three error-profile passes do alike around their device objects: ErrprofPass, FragerrPass (bamio_fragerr.hpp) and ErrsupPass
-// (bamio_errsup.hpp) derive from it and name their set_ref / set_mask / set_sites beside create / window / ... (bamio_reduce.hpp)
+// What the error-profile passes do alike around their device objects: ErrprofPass, FragerrPass (bamio_fragerr.hpp), ErrsupPass
+// (bamio_errsup.hpp) and ErrqualPass (bamio_errqual.hpp) derive from it and name their set_ref / set_mask / set_sites beside create / window / ... (bamio_reduce.hpp)
 template <class PASS, class RUN, class OBJ> struct ErrPass {
     static constexpr bool bed_first = false;
     RUN *out; MaskJob mk{}; OBJ *p = nullptr;

@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp, and the support-profile object of gce_errsup.hpp (the last five over gce_reduce.hpp).  They are exported, but
+// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp, and the support-profile and quality-profile objects of gce_errsup.hpp and gce_errqual.hpp (the last six over gce_reduce.hpp).  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -19,6 +19,7 @@ struct gce_fragpile;
 struct gce_errprof;
 struct gce_fragerr;
 struct gce_errsup;
+struct gce_errqual;
 
 int gce_device_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes);
 
@@ -131,6 +132,17 @@ int gce_errsup_set_sites(gce_errsup *p, int64_t n_intervals, const int32_t *tid,
 int gce_errsup_window(gce_errsup *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                       int32_t n_ref, int32_t last, double *errprof_s);
 int gce_errsup_finish(gce_errsup *p, int64_t counters[11], uint64_t *counts_out);
+
+// ---- the error profile by reported base quality (gce_errqual.hpp)
+int gce_errqual_create(int32_t device, size_t device_budget_bytes, int32_t min_mapq, int32_t min_baseq, uint32_t exclude_flags, uint32_t options, gce_errqual **out);
+void gce_errqual_destroy(gce_errqual *p);
+const char *gce_errqual_error(gce_errqual *p);
+int gce_errqual_set_ref(gce_errqual *p, int32_t n_ref, const char *const *seq, const int64_t *len);
+int gce_errqual_set_mask(gce_errqual *p, int64_t n, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_errqual_set_sites(gce_errqual *p, int64_t n_intervals, const int32_t *tid, const int32_t *start, const int32_t *end);
+int gce_errqual_window(gce_errqual *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
+                       int32_t n_ref, int32_t last, double *errprof_s);
+int gce_errqual_finish(gce_errqual *p, int64_t counters[10], uint64_t *counts_out);
 
 }  // extern "C"
 #endif

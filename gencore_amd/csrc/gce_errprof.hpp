@@ -20,7 +20,7 @@
 // (rule Y): k_err_count<DIRECT, errprof::Mask>, the same walk with one bit test per event.
 // errprof::scan_record and errprof::count_record are __host__ __device__: tests/errprof_host_check.hip runs them on the host against
 // tests/pyerrprof.py, the model of the rules.  What the pass shares with gce_bam_pileup -- rule E, the interval table, the scan kernel and the
-// device object -- is gce_reduce.hpp's.  What it shares with gce_fragerr.hpp (4l) and gce_errsup.hpp (4n) is here, once: the CIGAR walk
+// device object -- is gce_reduce.hpp's.  What it shares with gce_fragerr.hpp (4l), gce_errsup.hpp (4n) and gce_errqual.hpp (4o) is here, once: the CIGAR walk
 // (errprof::walk_record, which calls a functor at every column of an M / = / X op; count_record is the walk under rule W's functor), the
 // classes of a reference base, a read base and a counted base, the device object's base (ErrSession, with the one choice of a count kernel's
 // instantiation), the add of the planes (ErrAdd) and ep_set_ref / ep_set_sites / ep_finish; ep_set_mask is gce_varmask.hpp's.
@@ -202,7 +202,8 @@ static_assert(EP_CLS == (unsigned)errprof::EP_NCLASS && (EP_CLS & 1u) && EP_CYC 
 
 #ifndef GCE_ERRPROF_HOST_CHECK
 
-// The device object of an error-profile pass: what gce_errprof, gce_fragerr (gce_fragerr.hpp) and gce_errsup (gce_errsup.hpp) hold alike.
+// The device object of an error-profile pass: what gce_errprof, gce_fragerr (gce_fragerr.hpp), gce_errsup (gce_errsup.hpp) and gce_errqual
+// (gce_errqual.hpp) hold alike.
 // needs() stays the pass's own.
 struct ErrSession : ReduceSession {
     errprof::Params P{0, 0, 0, 0, 0}; bool direct = false;

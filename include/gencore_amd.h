@@ -957,6 +957,40 @@ int gce_bam_error_profile_support(const char *bam_path, const char *fasta_path, 
                                   uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_errsup_run *out,
                                   gce_mask_run *mask /* NULL without mask_path */, char err[256]);
 void gce_errsup_free(gce_errsup_run *out);
+/* The error profile by reported base quality: of the bases a file reports at quality q, how many differ from the reference, per (segment,
+ * quality), counted on ONE device (addition under ABI v3; gencore_amd/csrc/gce_errqual.hpp).  Replaces: nothing in the
+ * reference's source -- it stands in for GATK BaseRecalibrator's table by reported quality, Picard QualityScoreDistribution read beside its
+ * artifact metrics, or `fgbio ErrorRateByReadPosition` split by quality, which a user runs on the input and on the consensus output: the
+ * consensus step writes qualities of its own, from the voters' scores and the reference's thresholds, and a caller that weights evidence by
+ * QUAL trusts them.  One streaming pass over bam_path in any record order.  Eligible records, segment, classes 0..20, the walk, the BED and
+ * the mask are exactly gce_bam_error_profile's and gce_bam_error_profile_masked's; the cycle is replaced by the quality bucket of the event:
+ * an M / = / X column's own QUAL byte (a column below min_baseq adds LOWQ in its own quality's row), an inserted base's own byte, a
+ * deletion's byte of the query base in front of it (the first, when there is none); QUAL is read in the stored, reference orientation.
+ * The bucket of a byte b is b for b <= 93 and 94 for every other byte; every event of a record without qualities (QUAL[0] == 0xFF) has
+ * bucket 95.  counts[((segment * 96 + bucket) * 24) + class]: 21 MASKED (zero without mask_path), 22 and 23 zero.  For every (segment,
+ * class) the sum over the buckets equals gce_bam_error_profile's sum over the cycles on the same file and arguments.  mask_path (NULL: no
+ * mask; else *mask is filled as gce_bam_error_profile_masked fills it and must not be NULL).  tsv_path (NULL: no file): a header line that
+ * begins with `#`, then one line per (segment, quality) with a counter that is not zero, in ascending order: segment, quality (the number,
+ * `94+`, or `.` for bucket 95), bases (classes 0..15), mismatches (the off-diagonal ones), the sixteen A>A .. T>T, READ_N REF_OTHER LOWQ INS
+ * DEL, and MASKED with a mask; integers, no rates; written to a temporary name and renamed.  options: GCE_ERRQUAL_DIRECT makes every add a
+ * 64-bit global atomic instead of meeting in the block's table on chip: the same counters, the A/B partner of the default.  Device memory:
+ * the reference bases, 55 296 bytes of counters, the mask's bit per base, the interval table, one window and 4 bytes per window record,
+ * within device_budget_bytes (0: no limit), else GCE_ERR_OOM with that footprint.  The refusals are gce_bam_error_profile's.  Not here: the
+ * once-per-fragment rule of gce_bam_error_profile_fragments, a cycle or support dimension beside quality, the overlap table by quality, read
+ * groups, SAM text, several devices.  counts is malloc'ed: gce_errqual_free. */
+#define GCE_ERRQUAL_DIRECT 1u
+#define GCE_ERRQUAL_BUCKETS 96
+typedef struct gce_errqual_run {
+    int64_t n_records, n_eligible, n_unplaced, n_flagged, n_low_mapq, n_no_cigar, n_no_seq, n_bad_cigar, n_no_ref, n_too_long;   /* n_eligible + the eight skips = n_records */
+    int64_t n_bases, n_mismatches, n_intervals /* -1: no BED */, peak_device_bytes;
+    double  read_s, inflate_index_s, errprof_s, write_s, total_s;   /* errprof_s: the scan and k_qual_count; write_s: the table */
+    uint64_t *counts;               /* [3 segments][96 quality buckets][24 classes] */
+} gce_errqual_run;
+int gce_bam_error_profile_quality(const char *bam_path, const char *fasta_path, const char *bed_path /* NULL: no BED */, const char *mask_path /* NULL: no mask */,
+                                  const char *tsv_path /* NULL: no file */, int32_t device, int threads, int32_t min_mapq, int32_t min_baseq,
+                                  uint32_t exclude_flags, uint32_t options, uint64_t window_bytes, size_t device_budget_bytes, gce_errqual_run *out,
+                                  gce_mask_run *mask /* NULL without mask_path */, char err[256]);
+void gce_errqual_free(gce_errqual_run *out);
 /* One window of SAM text through the GPU's line parser (addition under ABI v3; gencore_amd/csrc/gce_samdev.hpp).
  * Replaces: htslib's sam_read1 / sam_parse1 under the reference when its input is SAM text (src/gencore.cpp:164,205), which this library had
  * on host threads only (gce_sam_to_bam, gce_run_bam's SAM input).  text[0, n): alignment lines only (no `@` lines), whole lines, n < 2^32 - 256;

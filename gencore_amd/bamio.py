@@ -1,5 +1,5 @@
 """Host-side file formats around the hot path, thin ctypes wrappers over gencore_amd/csrc/bamio.cpp (the
-host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp, bamio_fragerr.hpp, bamio_errsup.hpp and bamio_errqual.hpp (the last six over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
+host-only formats) and the runners in its parts, csrc/bamio_run.hpp, bamio_passes.hpp, bamio_index.hpp, bamio_sort.hpp, bamio_calmd.hpp, bamio_overlap.hpp, bamio_umi.hpp, bamio_pileup.hpp, bamio_fragpile.hpp, bamio_errprof.hpp, bamio_fragerr.hpp, bamio_errsup.hpp and bamio_errqual.hpp (the last six over bamio_reduce.hpp) and bamio_varmask.hpp (load_mask, host only):
 BamFile (gce_bam_open / gce_bam_chunk: a sorted BAM -> ReadBatch), write_bam (gce_bam_write), load_fasta (gce_fasta_load) and
 run_bam (gce_run_bam: BAM in -> engine -> BAM out, with the wall time of every stage).  No htslib."""
 import ctypes as C
@@ -235,6 +235,26 @@ def calmd_bam_stream(in_path, out_path, fasta, device=0, threads=0, level=6, win
     if rc != 0:
         raise GceError(rc, err.value.decode(errors="replace"))
     return CalmdRun(r, sr)
+
+
+def merge_overlap_bam(in_path, out_path, device=0, threads=0, level=-2, min_mapq=0, exclude_flags=0x704, weak_hash=False, window_bytes=0, device_budget_bytes=0):
+    """gce_bam_merge_overlap: the QUAL bytes of overlapping mates of a coordinate-sorted BAM rewritten on the GPU so that a plain pileup of
+    `out_path` counts every fragment once: where the mates agree the earlier one carries min(qa + qb, 93) and the later one 0,
+    where they disagree the better base keeps (4 q) / 5 and the other gets 0.  Nothing but QUAL bytes changes; the header and the record order
+    stay.  level as run_bam; weak_hash: the join keeps 4 bits of its hash (a test's switch); window_bytes: compressed bytes per window,
+    0 = 64 MB; device_budget_bytes: 0 = no limit beyond the device (the pass is in-core).  Returns a CalmdRun-like object (n_records, n_pairs,
+    n_pairs_no_qual, n_ambiguous, n_shared_columns, n_disagree_columns, n_columns_skipped, n_records_changed, inflated_bytes, out_bytes,
+    peak_device_bytes, n_ref, read_s, inflate_index_s, merge_s, write_s, total_s); raises GceError with the library's message (and leaves no
+    output) on failure."""
+    from .capi import GCE_OVERLAP_WEAK_HASH, GceOverlapRun
+    lib = capi.load_library()
+    r = GceOverlapRun()
+    err = (C.c_char * 256)()
+    rc = lib.gce_bam_merge_overlap(str(in_path).encode(), str(out_path).encode(), int(device), int(threads), int(level), int(window_bytes), int(device_budget_bytes), int(min_mapq),
+                                   int(exclude_flags), GCE_OVERLAP_WEAK_HASH if weak_hash else 0, C.byref(r), err)
+    if rc != 0:
+        raise GceError(rc, err.value.decode(errors="replace"))
+    return CalmdRun(r)
 
 
 class UmiRun:

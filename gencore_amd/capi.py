@@ -109,7 +109,8 @@ EXPORTED_SYMBOLS = [
     "gce_bam_calmd", "gce_bam_calmd_stream", "gce_bam_umi_to_mi", "gce_bam_pileup", "gce_pileup_free", "gce_bam_pileup_fragments", "gce_fragpile_free",
     "gce_bam_error_profile", "gce_errprof_free", "gce_bam_error_profile_fragments", "gce_fragerr_free",
     "gce_mask_load", "gce_mask_free", "gce_bam_error_profile_masked", "gce_bam_error_profile_fragments_masked",
-    "gce_bam_error_profile_support", "gce_errsup_free", "gce_bam_error_profile_quality", "gce_errqual_free"]
+    "gce_bam_error_profile_support", "gce_errsup_free", "gce_bam_error_profile_quality", "gce_errqual_free",
+    "gce_bam_merge_overlap"]
 
 GCE_PILEUP_DIRECT = 1
 GCE_FRAGPILE_DIRECT = 1
@@ -123,6 +124,7 @@ GCE_ERRSUP_DIRECT = 1
 GCE_ERRSUP_BUCKETS = 33
 GCE_ERRQUAL_DIRECT = 1
 GCE_ERRQUAL_BUCKETS = 96
+GCE_OVERLAP_WEAK_HASH = 1
 
 
 class GceBamInfo(C.Structure):
@@ -174,6 +176,14 @@ class GceCalmdRun(C.Structure):
                 ("n_md_changed", C.c_int64), ("inflated_bytes", C.c_int64), ("out_record_bytes", C.c_int64), ("out_bytes", C.c_int64), ("peak_device_bytes", C.c_int64),
                 ("n_ref", C.c_int32), ("pad", C.c_int32), ("read_s", C.c_double), ("inflate_index_s", C.c_double), ("calmd_s", C.c_double), ("write_s", C.c_double),
                 ("total_s", C.c_double)]
+
+
+class GceOverlapRun(C.Structure):
+    """gce_overlap_run (gce_bam_merge_overlap)."""
+    _fields_ = [("n_records", C.c_int64), ("n_pairs", C.c_int64), ("n_pairs_no_qual", C.c_int64), ("n_ambiguous", C.c_int64), ("n_shared_columns", C.c_int64),
+                ("n_disagree_columns", C.c_int64), ("n_columns_skipped", C.c_int64), ("n_records_changed", C.c_int64), ("inflated_bytes", C.c_int64), ("out_bytes", C.c_int64),
+                ("peak_device_bytes", C.c_int64), ("n_ref", C.c_int32), ("pad", C.c_int32), ("read_s", C.c_double), ("inflate_index_s", C.c_double), ("merge_s", C.c_double),
+                ("write_s", C.c_double), ("total_s", C.c_double)]
 
 
 class GceUmiRun(C.Structure):
@@ -351,6 +361,9 @@ def load_library(path=None, mode=C.RTLD_GLOBAL):
         lib.gce_get_sam_format_counters.argtypes = [C.POINTER(C.c_int64)]
     if hasattr(lib, "gce_bam_calmd"):
         lib.gce_bam_calmd.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int, C.c_uint64, C.c_size_t, C.POINTER(GceCalmdRun), C.c_char_p]
+    if hasattr(lib, "gce_bam_merge_overlap"):                                       # (the parent's build, loaded for an A/B run, lacks the pass)
+        lib.gce_bam_merge_overlap.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int, C.c_uint64, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(GceOverlapRun),
+                                              C.c_char_p]
     if hasattr(lib, "gce_bam_calmd_stream"):
         lib.gce_bam_calmd_stream.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int, C.c_uint64, C.c_size_t, C.c_uint64, C.POINTER(GceCalmdRun),
                                              C.POINTER(GceCalmdStreamRun), C.c_char_p]

@@ -74,6 +74,16 @@ A>A .. T>T, READ_N REF_OTHER LOWQ INS DEL, and MASKED with --error_profile_mask;
 that of the base in front of it.  Both honour -b, --error_profile_mask, --error_profile_min_mapq and --error_profile_min_baseq (a base below
 it is LOWQ in its own quality's row).  --error_profile_fragments does not apply to them: every record is counted (overlapping mates twice),
 there is no cycle column and no split by read group.
+--merge_overlap (not the reference's) resolves overlapping mates in the BAM output itself, on the GPU, so that whatever reads the file next
+(a pileup-based caller, `bam-readcount`, a script that counts alleles) counts every fragment once without a tool of its own in between (`fgbio
+ClipBam --clip-overlapping-reads`, `bamUtil clipOverlap`): mpileup's overlap tweak made durable.  At every reference column that both mates of
+a pair cover with a base, where they agree the first in the file carries min(qa + qb, 93) and the other quality 0, where they differ the
+better base keeps 4 / 5 of its quality and the other gets 0; a column where either quality is already 0 (or above 93) is left alone, so a
+second run changes nothing.  Nothing but QUAL bytes changes: no soft clipping, so sizes, positions, CIGARs, NM / MD and the order stay.  It
+runs after the output, the report, --calmd and the tables of --pileup and --error_profile* are written (they stay what they are without the
+flag) and before --index, replaces the output through a temporary file beside it at --level, in-core within --device_memory, and prints the
+pairs, the shared columns, those that disagree and the records changed on STDERR.  Records with a flag bit of 0x704 take no part; a name with
+more than two candidate records is left alone.
 -h is --html as in the reference, so help is --help only.  The HTML report is not written (--html is accepted with a notice), --debug is accepted
 and does nothing.
 
@@ -145,6 +155,11 @@ def build_parser():
                                             "the BAM output against -r on the GPU (on the first of --devices, at --level), through a temporary file beside "
                                             "the output that is renamed over it. It honours the --device_memory budget: an output beyond it is written as it is "
                                             "made. The report is not changed by it. Off by default.")
+    a("--merge_overlap", action="store_true", help="[gencore_amd] after the output, the report, --calmd and the --pileup / --error_profile* tables are written (and before --index), "
+                                                    "rewrite the base qualities of overlapping mates in the BAM output on the GPU so that a pileup of the file counts every fragment once: "
+                                                    "where the mates agree the first carries the summed quality (at most 93) and the other 0, where they differ the better base keeps 4 / 5 "
+                                                    "of its quality and the other gets 0. Only QUAL bytes change (no clipping). Needs a coordinate-sorted BAM output file; in-core within "
+                                                    "--device_memory. Off by default.")
     a("--calmd_in", action="store_true", help="[gencore_amd] recompute NM and MD of the input BAM against -r on the GPU first (after --sort / --sort_sam; on the first of --devices, "
                                                "into a temporary BAM beside the output that is removed afterwards), then run on that file: an input without NM "
                                                "becomes runnable. It honours the --device_memory budget as --calmd does. Off by default.")
@@ -308,6 +323,10 @@ def validate(o):
         err("--calmd needs an output file, not STDOUT")
     if o.calmd and o.output.endswith("sam"):
         err("--calmd needs BAM output, not SAM text")
+    if o.merge_overlap and o.output == "-":
+        err("--merge_overlap needs an output file, not STDOUT")
+    if o.merge_overlap and o.output.endswith("sam"):
+        err("--merge_overlap needs BAM output, not SAM text")
     for flag, given in (("--pileup", o.pileup), ("--pileup_in", o.pileup_in)):
         if given is not None and not o.bed:
             err("%s needs the targets of -b" % flag)
@@ -388,7 +407,7 @@ def main(argv=None):
     from .bamio import calmd_bam_stream, error_profile_bam, error_profile_fragments_bam, index_bam, load_bed, pileup_bam, pileup_fragments_bam, run_bam_depth, run_bam_passes, sort_bam_passes, sort_sam, umi_to_mi
     from .capi import GceError
     from .report import read_header, summary, write_json
-    sorted_tmp = calmd_tmp = umi_tmp = out_tmp = None
+    sorted_tmp = calmd_tmp = umi_tmp = out_tmp = merge_tmp = None
 
     def pileup(label, bam, tsv):
         r = (pileup_fragments_bam if o.pileup_fragments else pileup_bam)(bam, o.bed, fasta=o.ref, tsv=tsv, device=devices[0], threads=o.threads, min_mapq=o.pileup_min_mapq,
@@ -481,6 +500,12 @@ def main(argv=None):
                 sys.stderr.write("error_profile_support: mask %d intervals, %d bases, %d events masked\n" % (r.n_mask_intervals, r.n_masked_bases, r.n_masked_events))
         if o.error_profile_quality is not None:
             error_profile_quality("error_profile_quality", o.output, o.error_profile_quality)
+        if o.merge_overlap:                                                 # (behind every output-side table: they stay what they are without the flag)
+            from .bamio import merge_overlap_bam
+            merge_tmp = o.output + ".overlap%d" % os.getpid()
+            r = merge_overlap_bam(o.output, merge_tmp, device=devices[0], threads=o.threads, level=o.level, device_budget_bytes=o.device_memory_bytes)
+            os.replace(merge_tmp, o.output)
+            sys.stderr.write("merge_overlap: %d pairs, %d shared columns, %d disagreeing, %d records changed\n" % (r.n_pairs, r.n_shared_columns, r.n_disagree_columns, r.n_records_changed))
         if o.index:
             index_bam(o.output, o.output + ".bai", device=devices[0], threads=o.threads)
     except (GceError, OSError) as e:
@@ -488,7 +513,7 @@ def main(argv=None):
         print("ERROR: %s%s" % (e, hint), file=sys.stderr)
         return 255
     finally:
-        for tmp in (sorted_tmp, calmd_tmp, umi_tmp, out_tmp):
+        for tmp in (sorted_tmp, calmd_tmp, umi_tmp, out_tmp, merge_tmp):
             if tmp is not None and os.path.exists(tmp):
                 os.remove(tmp)
     t2 = int(time.time())

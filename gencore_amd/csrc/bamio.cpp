@@ -15,6 +15,7 @@
 //   bamio_index.hpp   gce_bam_index
 //   bamio_sort.hpp    gce_bam_sort, gce_bam_sort_passes, gce_sam_sort
 //   bamio_calmd.hpp   gce_bam_calmd, gce_bam_calmd_stream
+//   bamio_overlap.hpp gce_bam_merge_overlap
 //   bamio_umi.hpp     gce_bam_umi_to_mi
 //   bamio_varmask.hpp gce_mask_load, the variant mask of the error profile (host only)
 //   bamio_reduce.hpp  reduce_run, the runner of the reduce passes
@@ -811,6 +812,7 @@ void gce_bed_free(int32_t n_regions, int32_t *tid, int32_t *start, int32_t *end,
 #include "bamio_index.hpp"
 #include "bamio_sort.hpp"
 #include "bamio_calmd.hpp"
+#include "bamio_overlap.hpp"
 #include "bamio_umi.hpp"
 #include "bamio_varmask.hpp"
 #include "bamio_pileup.hpp"

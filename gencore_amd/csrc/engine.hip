@@ -1431,3 +1431,4 @@ int gce_get_pairing_tiers(gce_engine *e, int64_t cap, uint8_t *tier, uint32_t *r
 #include "gce_fragerr.hpp"
 #include "gce_errsup.hpp"
 #include "gce_errqual.hpp"
+#include "gce_ovlmerge.hpp"

@@ -1,5 +1,5 @@
 // gce_entry.h — the device entry points the file side (bamio.cpp and its bamio_*.hpp parts) calls that include/gencore_amd.h does not
-// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp, and the support-profile and quality-profile objects of gce_errsup.hpp and gce_errqual.hpp (the last six over gce_reduce.hpp).  They are exported, but
+// declare: the pass, index, sort, calmd, UMI, pileup, fragment-pileup, error-profile and fragment-error-profile objects of gce_passes.hpp, gce_bai.hpp, gce_sort.hpp, gce_calmd.hpp, gce_umi.hpp, gce_pileup.hpp, gce_fragpile.hpp, gce_errprof.hpp and gce_fragerr.hpp, and the support-profile and quality-profile objects of gce_errsup.hpp and gce_errqual.hpp (the last six over gce_reduce.hpp), and the overlap merge of gce_ovlmerge.hpp over the sort object.  They are exported, but
 // internal: their signatures may change with the library.  engine.hip includes this file in front of the headers that define them and the
 // file side includes it to call them, so a definition and a call that drift apart are a build error (conflicting types), not a link that
 // succeeds and breaks at run time.  Every gce_ prototype lives here or in the public header, nowhere else.
@@ -143,6 +143,11 @@ int gce_errqual_set_sites(gce_errqual *p, int64_t n_intervals, const int32_t *ti
 int gce_errqual_window(gce_errqual *p, const void *comp, size_t comp_bytes, int32_t n_members, const uint64_t *coff, const uint32_t *csize, const uint32_t *usize, uint64_t skip,
                        int32_t n_ref, int32_t last, double *errprof_s);
 int gce_errqual_finish(gce_errqual *p, int64_t counters[10], uint64_t *counts_out);
+
+// ---- the QUAL bytes of overlapping mates rewritten in the resident records of gce_sort_window (gce_ovlmerge.hpp)
+int gce_sort_overlap_begin(gce_sort *b);
+int gce_sort_overlap_finish(gce_sort *b, int32_t min_mapq, uint32_t exclude_flags, uint32_t options, int32_t codes, uint64_t piece_bytes, int64_t counts[8], int64_t *bad_rec,
+                            uint64_t *out_bytes);
 
 }  // extern "C"
 #endif

@@ -97,7 +97,7 @@ struct FragView {
 };
 __device__ __forceinline__ uint32_t fp_slot_bytes(const uint8_t *r) { return (FP_AHDR + 4u + rb32(r) + 7u) & ~7u; }
 
-// READ: read(r, meta[i], first, C) -> the record is eligible; first: the first interval it can touch, or RD_NONE; C: its core fields, set for
+// READ: read(r, meta[i], first, C) (meta NULL, for a pass without a scan: 0) -> the record is eligible; first: the first interval it can touch, or RD_NONE; C: its core fields, set for
 // an eligible record whose first is not RD_NONE
 template <class READ> __global__ __launch_bounds__(256) void k_frag_prep(FragView V, READ read, const uint32_t *meta, uint32_t par, uint32_t weak, uint64_t *hkey, uint32_t *first,
                                                                          uint32_t *partner, uint32_t *table, uint32_t mask, unsigned long long *fm) {
@@ -112,7 +112,7 @@ template <class READ> __global__ __launch_bounds__(256) void k_frag_prep(FragVie
         if (k < prev) atomicMin(fm + FM_BAD, (unsigned long long)(V.gbase + i));
         if (e + 1 == V.n) fm[FM_KEY0 + (par ^ 1u)] = k;
         reduce::Core C;
-        cand = read(r, meta[i], f, C) && f != RD_NONE && fragpile::candidate(r, C, f);
+        cand = read(r, meta ? meta[i] : 0u, f, C) && f != RD_NONE && fragpile::candidate(r, C, f);
     }
     first[e] = f;
     partner[e] = cand ? 0u : f == RD_NONE ? FP_SKIP : FP_ALONE;

@@ -139,12 +139,15 @@ struct gce_sort {
     bool cm_stream = false; int32_t cm_codes = -1, cm_flushes = 0; uint64_t cm_piece = 0, cm_cap = 0, cm_flushed = 0;
     // the UMI pass (gce_bam_umi_to_mi, gce_umi.hpp): calmd mode, streamed, under another record rewriter; um_src: 0 the read name, else the tag's two bytes
     bool umi = false; uint32_t um_src = 0;
+    // overlapping mates merged (gce_bam_merge_overlap, gce_ovlmerge.hpp): nothing is sorted; after the last window `rec` is rewritten in place and becomes `out`
+    bool overlap = false;
 };
 
 static int sfail(gce_sort *b, int code, const std::string &m) { if (b) b->err = m; return code; }
 static int sort_oom(gce_sort *b, const char *what, uint64_t add) {
     char m[256];                                                                      // (the footprint first: a long `what` is cut off, not the formula)
-    snprintf(m, sizeof m, b->umi ? "out of device memory: gce_bam_umi_to_mi needs one window + 40 bytes per window record + one piece's deflate buffers + at least one window's output (%lld bytes live, budget %llu, %llu more for %s)" :
+    snprintf(m, sizeof m, b->overlap ? "out of device memory: gce_bam_merge_overlap is in-core and needs the inflated record bytes + 20 bytes per record + one window, then a join table of about 24 bytes per record (%lld bytes live, budget %llu, %llu more for %s)" :
+                          b->umi ? "out of device memory: gce_bam_umi_to_mi needs one window + 40 bytes per window record + one piece's deflate buffers + at least one window's output (%lld bytes live, budget %llu, %llu more for %s)" :
                           b->cm_stream ? "out of device memory: gce_bam_calmd_stream needs the reference bases + one window + 40 bytes per window record + one piece's deflate buffers + at least one window's output (%lld bytes live, budget %llu, %llu more for %s)" :
                           b->calmd ? "out of device memory: calmd is in-core and needs about the output record bytes + the reference bases + 40 bytes per window record + one window (%lld bytes live, budget %llu, %llu more for %s)" :
                           b->sam_text ? "out of device memory: SAM text is sorted in-core only (else gce_sam_to_bam, then gce_bam_sort_passes): 2 x the record bytes + 20 per record + a window of 2 per text byte + 41 per line (%lld live, budget %llu, %llu more for %s)" :

@@ -724,6 +724,35 @@ typedef struct gce_calmd_stream_run {
 int gce_bam_calmd_stream(const char *in_path, const char *out_path, const char *fasta_path, int32_t device, int threads, int level,
                          uint64_t window_bytes, size_t device_budget_bytes, uint64_t resident_bytes,
                          gce_calmd_run *out, gce_calmd_stream_run *run, char err[256]);
+/* Overlapping mates resolved in the file on ONE device, file to file (addition under ABI v3; gencore_amd/csrc/gce_ovlmerge.hpp).
+ * Replaces: nothing in the reference's source -- it stands in for the tool a pipeline runs behind the reference so that a pileup of the
+ * output counts every fragment once (`fgbio ClipBam --clip-overlapping-reads`, `bamUtil clipOverlap`, mpileup's own overlap tweak), and
+ * writes gce_bam_pileup_fragments' rule V into the records.  Nothing but QUAL bytes changes: record sizes, positions, CIGARs, NM / MD, the
+ * record order and the header (copied byte for byte) stay.  Rule P: the file is coordinate-sorted; the first record in front of its
+ * predecessor is GCE_ERR_INVALID ("BAM record %d (counting from 0) lies in front of its predecessor: gce_bam_merge_overlap needs a
+ * coordinate-sorted file").  Rule E: a record takes part when gce_bam_pileup's rule E keeps it under min_mapq (0..255) and exclude_flags; a
+ * record whose fields overrun its block_size refuses the run, in gce_bam_pileup's words, before rule P is looked at.  Rule M:
+ * gce_bam_pileup_fragments' mates without the site test, joined over the whole file at once (the result does not depend on window_bytes);
+ * every member of a group of more than two adds to n_ambiguous and is left alone.  Rule Q, for a pair whose earlier record in the file is a:
+ * a pair with a record without qualities is left alone (n_pairs_no_qual); at every reference column that an M / = / X op of both mates
+ * covers (n_shared_columns), with qualities qa, qb and base classes A C G T N: a column where qa or qb is 0 or above 93 is left as it is
+ * (n_columns_skipped; the pass is idempotent); equal classes: qa' = min(qa + qb, 93), qb' = 0; different classes (n_disagree_columns):
+ * qa >= qb: qa' = (4 qa) / 5, qb' = 0, else qb' = (4 qb) / 5, qa' = 0.  D and N columns, clips and inserted bases are not touched.
+ * n_records_changed: records of which at least one byte differs.  options: GCE_OVERLAP_WEAK_HASH keeps 4 bits of the join's hash (a test's
+ * switch: the same file, long probe runs).  level and the file's layout (rule F): gce_bam_calmd's.  In-core: the inflated record bytes + 20
+ * bytes per record + one window, then a join table of about 24 bytes per record in place of 12 of the 20; device_budget_bytes (0 = no limit
+ * beyond the device) is checked before every growth: GCE_ERR_OOM with a message that states this footprint.  A failed call leaves neither an
+ * output nor a temporary file.  The other refusals: gce_bam_calmd's, with this entry point's name. */
+#define GCE_OVERLAP_WEAK_HASH 1u
+typedef struct gce_overlap_run {
+    int64_t n_records, n_pairs, n_pairs_no_qual, n_ambiguous, n_shared_columns, n_disagree_columns, n_columns_skipped, n_records_changed;
+    int64_t inflated_bytes, out_bytes, peak_device_bytes;   /* record bytes read (and written); size of the file written; gce_device_bytes' peak during the call */
+    int32_t n_ref, pad;
+    double  read_s, inflate_index_s, merge_s, write_s, total_s;   /* merge_s: the check, the join and k_ovl_merge behind the last window */
+} gce_overlap_run;
+int gce_bam_merge_overlap(const char *in_path, const char *out_path, int32_t device, int threads, int level, uint64_t window_bytes,
+                          size_t device_budget_bytes, int32_t min_mapq, uint32_t exclude_flags, uint32_t options, gce_overlap_run *out,
+                          char err[256]);
 /* The UMI of every record moved into an MI:Z field on ONE device, file to file (addition under ABI v3; gencore_amd/csrc/gce_umi.hpp,
  * DESIGN.md 4h).  Replaces: nothing in the reference's source -- it feeds BamUtil::getUMI's MI:Z path (src/bamutil.cpp:23-38), which every
  * runner here follows: a UMI is the last `:`-field of an MI:Z value or of the read name, of A C G T with at most one `_`.  A file whose UMIs are in

@@ -865,9 +865,7 @@ struct Step {
         unsigned long long si_seq1 = 0;
         if ((rc = read_si_begin(e, &si_seq1, true)) != GCE_OK) return rc;
         if (N > 0) {
-#ifndef GCE_DESCRIBE_BLOCKS
 #define GCE_DESCRIBE_BLOCKS 32768        // at most this many blocks: their Stats partial sums end in six global atomics each
-#endif
             const int64_t n_tiles = (N + 255) / 256;
             int tpb = (int)((n_tiles + GCE_DESCRIBE_BLOCKS - 1) / GCE_DESCRIBE_BLOCKS); if (tpb < 1) tpb = 1;
             LAUNCH_EV(k_describe, dim3(cdiv(n_tiles, tpb)), dim3(256), s, e->ev[EV_DESCRIBE], b, p, w, tpb);
@@ -974,7 +972,7 @@ struct Step {
         TAKE(rp_left, w.rp_left, g1 * 4); TAKE(rp_right, w.rp_right, g1 * 4); TAKE(rp_merge, w.rp_merge, g1 * 4); TAKE(rp_rmerge, w.rp_rmerge, g1 * 4); TAKE(rp_umi, w.rp_umi, g1 * 8);
         TAKE(rp_umilen, w.rp_umilen, g1 * 2); TAKE(rp_state, w.rp_state, g1); TAKE(rp_supp, w.rp_supp, g1 * 4); TAKE(rp_nm, w.rp_nm, g1 * 8); TAKE(rp_qsl, w.rp_qsl, g1 * 4); TAKE(rp_qsr, w.rp_qsr, g1 * 4);
         if (NG > 0 && e->dev_error == 0) {
-            {   // argument blocks of the generic consensus kernel in device memory (gce_kernels.hpp); here, where the host has just waited for the GPU anyway: `w` is complete
+            {   // argument blocks of the generic consensus kernel in device memory (gce_consensus.hpp); here, where the host has just waited for the GPU anyway: `w` is complete
                 SlowArgs sa; sa.b = b; sa.p = p; sa.w = w;
                 HIPCHK(e->slow_args.ensure(sizeof sa));
                 HIPCHK(hipMemcpyAsync(e->slow_args.p, &sa, sizeof sa, hipMemcpyHostToDevice, s));      // (pageable source: staged before the call returns)
@@ -984,11 +982,7 @@ struct Step {
                           FillSeg{e->rp_nm.p, g1 * 8, 0xFFu, 0u},                                  // -1: NM untouched
                           FillSeg{e->rp_left.p, g1 * 4, 0xFFu, 0u}, FillSeg{e->rp_right.p, g1 * 4, 0xFFu, 0u}});   // NONE: a group no kernel voted on emits nothing (instead of stale read indices)
             const uint32_t n_live = (uint32_t)e->h_si.n_live;                                    // (with none, vb_start[0] stays NONE32: k_vote's one block returns at once and reads no list)
-#ifdef VB_XCD
-            const unsigned nbatch = (((unsigned)(e->h_si.vote_weight / VB_W) + 1u) + 7u) & ~7u;      // (vb_start is 0xFF-filled up to vb_cap: the extra blocks find no batch)
-#else
             const unsigned nbatch = (unsigned)(e->h_si.vote_weight / VB_W) + 1u;
-#endif
 #ifdef VB_STOP
             return time_vote_and_stop(nbatch, n_live);
 #endif
@@ -1369,7 +1363,7 @@ int gce_get_consensus_counters(gce_engine *e, int64_t out[5]) {
     return GCE_OK;
 }
 
-// groups of the last gce_process that were not evaluated because no setting of the run could write them (d_group_skipped, gce_kernels.hpp):
+// groups of the last gce_process that were not evaluated because no setting of the run could write them (d_group_skipped, gce_groups.hpp):
 // one-pair groups under --supporting_reads > 1 or --duplex_only in clusters that form no duplex.  0 with -s 1 and no --duplex_only.
 // out[1]: the batches k_vote formed over the live groups (vote_weight / VB_W + 1; 0 for a stream without groups).
 int gce_get_skipped_groups(gce_engine *e, int64_t out[2]) {

@@ -23,12 +23,9 @@
 //                  pre-Stats counters (stats.cpp:101-121) that pairing and the vote consume; independent of everything above
 #pragma once
 
-#ifndef SB_T
 #define SB_T 512                         // threads per scan block (round 5: 256 -> 512, scan blocks of 1024 reads: a capture panel spreads a cluster's reads over ~540 reads of the stream,
-#endif                                   // so that a cluster met 2.06 blocks of 512 reads = leader runs = read-modify-writes of k_leaders, and meets 1.5 of 1024)
-#ifndef SB_U
+                                         // so that a cluster met 2.06 blocks of 512 reads = leader runs = read-modify-writes of k_leaders, and meets 1.5 of 1024)
 #define SB_U 2                           // reads per thread
-#endif
 #define SB_READS (SB_T * SB_U)           // reads per scan block
 #define SB_LDS_SLOTS (2 * SB_READS)       // LDS hash slots for the <= SB_READS distinct keys of a block
 #define SB_OFF_BITS (SB_READS == 1024 ? 10 : 9)        // a read's place in its scan block
@@ -575,9 +572,7 @@ __global__ __launch_bounds__(SB_T) void k_scatter(int64_t n, Work w) {
 }
 
 // ===================================================================================================== read descriptors (not formation)
-#ifndef DESC_WPE
 #define DESC_WPE 8                       // (64 VGPRs and 44 bytes of scratch per lane; at seven waves -- 72 VGPRs, no scratch -- the kernel is 14 us SLOWER: profiles/r05_y_ab_round_start_vs_head.log)
-#endif
 __global__ __launch_bounds__(256, DESC_WPE) void k_describe(DevBatch b, DevParams p, Work w, int tiles_per_block) {
     __shared__ long long s_stat[WAVES_PER_BLOCK][6];
     long long st[6] = {0, 0, 0, 0, 0, 0};       // reads, bases, reads_unmapped, bases_unmapped, base_mismatches, reads_with_mismatches

@@ -16,9 +16,7 @@
 #define DV_T 256                 // threads per block
 #define DV_COLS 512              // template columns per block
 #define DV_CHUNK 256             // voters staged per round
-#ifndef DV_UNROLL
-#define DV_UNROLL 2          // rows of four voters in flight per wave
-#endif
+#define DV_UNROLL 2              // rows of four voters in flight per wave
 #define DV_DONE 2                // gen_flag value: side finished here
 
 struct DVoter { uint64_t so, qo; int rl, ld; uint32_t patch, pad; };

@@ -2,7 +2,7 @@
 // clusters of <= 16 reads, then 32 lanes per cluster (two per wave) for the ones that pass flagged on, then k_pairing_fast.
 //
 // k_pairing_fast is VALU-bound with 13 of 64 lanes carrying a read at the benchmark's depth; running two clusters as the two
-// halves of a wave executes the same instruction stream once for both.  Same algorithm as k_pairing_fast (gce_kernels.hpp):
+// halves of a wave executes the same instruction stream once for both.  Same algorithm as k_pairing_fast (gce_pairing.hpp):
 // names as big-endian words, hash-filtered name classes verified exactly, first / last read of a name = mLeft / mRight
 // (pair.cpp:188-216), lexicographic rank against the first read of every other name (std::map order, cluster.cpp:260-273),
 // the setRight UMI check, read -> pair transposition by ds_permute, greedy UMI grouping (cluster.cpp:57-100), group-contiguous

@@ -1,91 +1,60 @@
 // gce_vote.hpp — Pair::computeScore + Group::consensusMergeBam + Group::makeConsensus for the usual groups, one WORKGROUP per batch of
-// groups (pair.cpp:88-172, group.cpp:136-579).
+// groups (pair.cpp:88-172, group.cpp:136-579).  engine.hip launches k_vote_batches behind pairing (stage pair_clusters) and k_vote as the
+// first kernel of stage consensus, one block per batch.
 //
-// The per-group kernels of round 1 (one wave per group, k_score2 in front) were bound by their own instruction stream: ~1800 wave
-// instructions per group, most of them bookkeeping executed with 6-19 of 64 lanes busy.  Here a workgroup of 256 threads takes a
-// batch of ~9 groups (<= 16 groups, <= 95 pairs, weight 64) through a few FLAT phases, every phase with one lane per independent item:
+// One wave per group is bound by its own instruction stream: ~1800 wave instructions per group, most of them bookkeeping executed with
+// 6-19 of 64 lanes busy.  Here a workgroup of VB_T = 256 threads takes a batch of weight VB_W = 96 (<= VB_MAXG = 16 groups, <= VB_MAXP
+// = 128 pairs) through a few FLAT phases, every phase with one lane per independent item.  In the order they run:
+//   P0  lane = group           the batch's entries of the live list (k_vote_batches); a deep group (> 32 pairs, or beyond the
+//                              low-complexity threshold) is handed on at once
 //   P1  lane = pair            the two reads' descriptors into LDS; the pair's mate-overlap window (pair.cpp:108-120); what the sides'
 //                              template choice needs of their reads (masks, position range) by LDS atomics
 //   P2  lane = (pair, side), then lane = (group, side)   consensusMergeBam for the sides this kernel covers: one class of reads with the
 //                              same CIGAR and length -- and position, when the right reads start at different positions (right-aligned
 //                              mode) -- (+ a provably unrelated minority), template = first read of the class, voters = the class
-//   P4  lane = (side, 16 columns)  "pass A": OR / AND of the voters' packed bases (unanimity), packed max of their quals; a column
-//                              all voters agree on with top quality >= moderate takes group.cpp:421-428 (base kept, qual = max qual)
-//   P3  lane = pair (behind pass A, in its phase: the bytes come from the L2)  mismatching bases in the mate overlap -> those columns are forced into the full vote of both sides
-//   P5  lane = (side, voter, contested column)  "pass B": the voter's base, quality and exact score (pair.cpp:132-169 computed on the fly,
-//                              the qualities of mismatching overlap bases rewritten to max(0, own - mate)) go into the column's 5-bin tally
-//                              in LDS (count | biased score sum | quality sum packed into ONE atomic add, one atomic max for the top
-//                              quality: 7.7 KB of tallies instead of 15 KB took the kernel from 5 to 7 waves per SIMD, -1.2 ms, after no
-//                              change of the instruction stream had moved it); consecutive lanes = consecutive contested columns of ONE voter, so a wave's 64 byte loads fall
-//                              into a dozen cache lines (column-major items made every lane touch a line of its own: the texture
-//                              addresser, not HBM, was the limit).  Then lane = contested column: rule cascade + reference arbitration
-//                              (group.cpp:394-501)
-//   P6  lane = (group, side)   mismatchInc -> NM patch or restore (group.cpp:528-573), result records
-//   P7  lane = (side, 16 columns)  write the template back
+//   pass A  lane = (side, 16 columns)   OR / AND of the voters' packed bases (unanimity), packed max of their quals; a column all voters
+//                              agree on with top quality >= moderate takes group.cpp:421-428 (base kept, qual = max qual); the others
+//                              are CONTESTED
+//   P3  lane = pair (behind pass A, in its barrier interval: the bytes come from the L2)   mismatching bases in the mate overlap -> those
+//                              columns are forced into the full vote of both sides
+//   P5  "pass B", in rounds of whole sides whose contested columns fit the tallies (VB_CCAP; usually one round):
+//       a  lane = side         contested columns per side, prefixes of columns and items; a side over VB_SMAX or VB_RCAP hands its group on
+//       b  lane = (side, 32-column mask word)   the list of contested columns, side by side
+//       c  lane = (side, voter, two contested columns half the side's list apart)   the voter's base, quality and exact score
+//                              (pair.cpp:132-169 computed on the fly, the qualities of mismatching overlap bases rewritten to
+//                              max(0, own - mate)) go into the column's 5-bin tally in LDS: count | biased score sum | quality sum packed
+//                              into ONE atomic add, one atomic max for the top quality.  Consecutive lanes = consecutive contested columns
+//                              of ONE voter, so a wave's 64 byte loads fall into a dozen cache lines
+//       d  lane = contested column   rule cascade + reference arbitration (group.cpp:394-501)
+//   P6  lane = (group, side)   mismatchInc -> deferred NM patch or restore (group.cpp:528-573), result records
+//   P7  lane = (side, 16 columns)   write the template back
 // Nothing is written to the reads before P7, and only the templates are: the quality rewrite of pair.cpp:158-159 exists in registers
 // for the vote and persists exactly where the reference's persists in an emitted record (the template's columns are either voted
-// columns, or — after a restore — rewritten here).  Scores are never materialised: no k_score2 launch, no score array traffic.
+// columns, or — after a restore — rewritten here).  Scores are never materialised for the groups voted here.
 //
-// A group with a side outside that scope (related odd reads, several classes of right reads on different positions, > 32 pairs, IUPAC codes, quals >= 128,
-// unusual score constants ...) is handed on UNTOUCHED, both sides: gen_flag (-> k_consensus_fast / k_consensus_slow) and score_list
-// (-> k_score2 scores just those pairs).
+// A group with a side outside that scope (related odd reads, several classes of right reads on different positions, > 32 pairs, IUPAC codes,
+// quals >= 128, unusual score constants, too many contested columns ...) is handed on UNTOUCHED, both sides: its pair slots go on score_list
+// (k_score2 scores just those pairs), its sides on gen_list (k_consensus_fast), and the sides of more than 64 pairs on slow_list
+// (k_deep_prepare, then k_vote_deep; what neither of them takes is left to k_consensus_slow).
+//
+// The geometry below is the one that ships and the one the tests pin; what else was measured is in DESIGN.md 6b and docs/history_r01_r05.md.
 #pragma once
 
-#ifdef VB_WAVE             // experiment: ONE wave per batch of weight 24 (8 groups, 16 sides): no workgroup barrier waits for another wave, the bytes pass A fetched are
-#define VB_T 64            // voted on a few microseconds later
-#define VB_W 24
-#define VB_GDIV 8
-#define VB_CCAP 96
-#define VB_RCAP 160
-#endif
-#ifdef VB_BIG              // experiment: 512 threads per batch of weight 192 (32 groups, 64 sides: still one wave for the per-side phases), four workgroups per CU
-#define VB_T 512
-#define VB_W 192
-#define VB_GDIV 32
-#define VB_CCAP 512
-#define VB_RCAP 768
-#endif
-#ifndef VB_GDIV
-#define VB_GDIV 16
-#endif
-#ifndef VB_T
 #define VB_T 256           // threads per batch
-#endif
-#ifndef VB_W
-#define VB_W 96            // batch capacity in weight units (weight of a group = max(pairs, VB_MINW); a handed-on deep group takes a whole batch).  64 -> 96 in round 4:
-                           // a batch's fixed phases and barriers carry half as many pairs again and pass A fills its lanes (k_vote 3.07 -> 2.89 ms)
-#endif
+#define VB_W 96            // batch capacity in weight units (weight of a group = max(pairs, VB_MINW); a handed-on deep group takes a whole batch): a batch's fixed
+                           // phases and barriers carry half as many pairs again as at 64, and pass A fills its lanes
 static_assert(VB_W + 32 <= 256, "pair indices of a batch are bytes");
-#define VB_MINW (VB_W / VB_GDIV) // smallest weight of a group: <= 16 (32) groups per batch (one lane per (group, side) in a wave)
+#define VB_GDIV 16         // <= 16 groups per batch: one lane per (group, side) in ONE wave for the per-side phases
+#define VB_MINW (VB_W / VB_GDIV) // smallest weight of a group
 #define VB_MAXG (VB_W / VB_MINW)
 #define VB_MAXP (VB_W + 32)                // a batch's last group may reach over the end: < VB_W + 32 pairs
 #define VB_SIDES (2 * VB_MAXG)
 #define VB_COLS 256
-#ifndef VB_CCAP
-#define VB_CCAP 256        // (round 5: 160 -- 47 % of cfg3's batches held more than 128 contested columns and voted a second round, ~0.3 ms of the kernel; the LDS came from the voter lists, now 256 B, and the byte-wide s_wbase)  Round 4, at 128: (with VB_RCAP: LDS stays within 20 KB = EIGHT workgroups per CU, at 64 VGPRs (three dwords spilled): 2.79 -> 2.76 ms against
-                           //  184 / 512 at seven (22.5 KB, 66 VGPRs), although nearly half of the batches now vote in two rounds; batches of weight 80 / 64 at eight
-                           //  workgroups: 2.84 / 3.03 ms.  profiles/r04_q_ab_8waves.log)
-#endif
-//   VB_CCAP: contested columns voted per round (LDS tallies)
-#ifndef VB_WPE
-#define VB_WPE 8
-#endif
-#ifndef VB_TPLANE
-#define VB_TPLANE 1             // tallies as ten planes of VB_CCAP dwords (add / max word of every bin), a pair item's columns half a side apart: consecutive lanes -> consecutive banks
-#endif
-#ifndef VB_COLPAIR
-#define VB_COLPAIR 1          // pass-B items of TWO neighbouring contested columns of one voter (round 6); 0 = one column per item, two items per trip (rounds 2-5)
-#endif
-#if !VB_COLPAIR
-#undef VB_TPLANE
-#define VB_TPLANE 0
-#endif
-#ifndef VB_SMAX
+#define VB_CCAP 256        // contested columns voted per round (LDS tallies): a batch of weight 96 holds ~187, so that nearly every batch votes in ONE round -- a round
+                           // costs every wave of the block its whole instruction stream however few items it has
+#define VB_WPE 8           // waves per SIMD the kernel is compiled for: 64 VGPRs, and with 20 KB of LDS EIGHT workgroups per CU
 #define VB_SMAX 32         // a side with more contested columns than this hands its group on
-#endif
-#ifndef VB_RCAP
 #define VB_RCAP 384        // contested columns of a whole batch (all rounds): a side that does not fit any more hands its group on (32 sides x VB_SMAX would be 1024)
-#endif
 
 // A read of the batch in LDS, in two halves: the blob offsets live through the whole kernel; the rest (first CIGAR word, position, read index, length, CIGAR ops,
 // fl bit 0: isize != 0) is what P1 .. P2 choose templates and voters by -- from pass A on its 4 KB are TALLY space (round 5: with them the tallies take 256
@@ -112,9 +81,6 @@ __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t c) {
     union { uint32_t u; vb_us2 v; } x, y, z; x.u = a; y.u = c; z.v = __builtin_elementwise_max(x.v, y.v); return z.u;
 }
 __device__ __forceinline__ uint64_t ld8_unaligned(const uint8_t *p_) { typedef uint64_t u64u __attribute__((aligned(1))); return *(const u64u *)p_; }
-#ifndef VB_LD16
-#define VB_LD16 1
-#endif
 typedef uint64_t vb_u64x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ vb_u64x2 vb_ld16(const uint8_t *p_) { typedef vb_u64x2 u128u __attribute__((aligned(1))); return *(const u128u *)p_; }   // one global_load_dwordx4
 // gather the top bit of each of the 4 bytes of x into bits 0..3
@@ -179,12 +145,6 @@ __global__ __launch_bounds__(256) void k_vote_batches(Work w, const unsigned lon
     }
 }
 
-__device__ __forceinline__ int vb_find(const uint16_t *pre, int n, int it) {       // largest s < n with pre[s] <= it  (pre ascending, pre[0] = 0)
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if ((int)pre[mid] <= it) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 // The same for the 64 consecutive items base + lane of a wave (all lanes must call it; items past `last` are clamped): the wave's first
 // item is placed by one ballot over the <= 32 prefix entries, every lane then walks on from there FOUR entries per LDS round trip (the
 // entries ascend: those <= the item are a prefix of the four) -- a wave's items span two to ten sides, and one entry per trip made
@@ -192,9 +152,6 @@ __device__ __forceinline__ int vb_find(const uint16_t *pre, int n, int it) {    
 // No bounds tests (each one was an exec-mask branch of its own around one LDS read, four per trip): pre[n] is the total -- larger than every item, as
 // is whatever follows it in the array (the next sides' prefixes, then the 0xFFFF the arrays are padded with: VB_PRE entries) -- so reading up to four
 // entries past n is harmless and never counted.
-#ifndef VB_FIND_ALIGNED
-#define VB_FIND_ALIGNED 1
-#endif
 #define VB_PRE (VB_SIDES + 8)
 static_assert(VB_SIDES % 4 == 0 && VB_PRE >= VB_SIDES + 4, "vb_find_wave reads the aligned 4-entry group that holds pre[VB_SIDES]");
 // The sides searched are arr[s0 .. s0 + n] (a later round of pass B starts at side s0 > 0); the result is relative to s0.
@@ -203,7 +160,6 @@ __device__ __forceinline__ int vb_find_wave(const uint16_t *arr, int s0, int n, 
     const int b0 = min(base, last), it = min(base + lane, last);
     const int pl = (int)arr[s0 + min(lane, n)];
     int s = __popcll(__ballot(pl <= b0)) - 1;
-#if VB_FIND_ALIGNED
     // the four entries of the ALIGNED 8-byte group that holds arr[s0 + s + 1] (round 6: the walk read pre[s + 1 .. s + 4] -- an 8-byte LDS read on a 2-byte boundary three
     // times out of four; SQ_LDS_UNALIGNED_STALL was a third of the kernel's LDS-active cycles).  The groups are formed on the array itself, not on arr + s0: with s0 % 4 != 0
     // that was again an 8-byte read on a 2-byte boundary.  The group's entries up to s0 + s are <= the item like arr[s0 + s] itself (the prefixes ascend over the
@@ -214,15 +170,6 @@ __device__ __forceinline__ int vb_find_wave(const uint16_t *arr, int s0, int n, 
         const int c = ((int)(w2.x & 0xFFFFu) <= it) + ((int)(w2.x >> 16) <= it) + ((int)(w2.y & 0xFFFFu) <= it) + ((int)(w2.y >> 16) <= it);
         if (c < 4) { s = 4 * g + c - 1 - s0; break; }
     }
-#else
-    const uint16_t *pre = arr + s0;
-    for (;;) {
-        const int a1 = (int)pre[s + 1], a2 = (int)pre[s + 2], a3 = (int)pre[s + 3], a4 = (int)pre[s + 4];
-        const int c = (a1 <= it) + (a2 <= it) + (a3 <= it) + (a4 <= it);
-        s += c;
-        if (c < 4) break;
-    }
-#endif
     return s;
 }
 
@@ -238,15 +185,15 @@ __device__ __forceinline__ int vb_find_wave(const uint16_t *arr, int s0, int n, 
 #else
 #define VB_SUBTICK(k) do { } while (0)
 #endif
-#define gb_ gb_
 __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8))) void k_vote(DevBatch b, DevParams p, Work w, uint32_t n_live) {      // n_live: entries of w.vlive (k_vote_batches)
     __shared__ VRead s_rd[2][VB_MAXP];
     __shared__ VOv s_ov[VB_MAXP];
     __shared__ VSide s_side[VB_SIDES];
     __shared__ uint32_t s_cmask[VB_SIDES][VB_COLS / 32];
     __shared__ uint8_t s_vlist[2][VB_MAXP];                                        // voters of a side (pair index in the batch), ascending: the k-th voter of side (group, parity) at [parity][lp0 + k] -- a side has no more voters than its group has pairs
-    __shared__ __attribute__((aligned(16))) uint32_t s_tal[VB_CCAP][5][2];         // pass B: per contested column and bin {count | biased score sum << 6 | qual sum << 20, top qual}:
-                                                                                   // <= 32 voters, biased scores <= 255, quals < 128 on this path => 6 + 14 + 12 bits, one atomic add per vote
+    __shared__ __attribute__((aligned(16))) uint32_t s_tal[10][VB_CCAP];           // pass B: ten planes of one dword per contested column of the round -- plane 2 * bin: count | biased score sum << 6 | qual sum << 20
+                                                                                   // (<= 32 voters, biased scores <= 255, quals < 128 on this path => 6 + 14 + 12 bits, one atomic add per vote), plane 2 * bin + 1: top qual.
+                                                                                   // A pair item's columns lie half a side apart: consecutive lanes -> consecutive banks
     __shared__ uint8_t s_ccol[VB_RCAP], s_cq[VB_RCAP], s_cb[VB_RCAP];              // contested columns (side by side, ascending): column; voted qual, voted base
     __shared__ __attribute__((aligned(8))) uint16_t s_jpre[VB_PRE];                                      // pass B: first (voter, column) item of every side
     __shared__ uint32_t s_ggi[VB_MAXG], s_gbeg[VB_MAXG];
@@ -260,23 +207,18 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
     // P1 -> P3 only, in the (not yet used) tally space: contig of either read of a pair (the template's reference lookup); length of its
     // last CIGAR op if that is an M block (isPartOf from the right end); per side the masks of its reads / its single-M reads, the range of
     // their positions, the voters and "a read outside the scope was seen"; the group of every pair
-    int32_t (*s_ptid)[VB_MAXP] = reinterpret_cast<int32_t (*)[VB_MAXP]>(&s_tal[0][0][0]);
-    uint16_t (*s_lastm)[VB_MAXP] = reinterpret_cast<uint16_t (*)[VB_MAXP]>(&s_tal[0][0][0] + 2 * VB_MAXP);
-    uint32_t *s_hm = &s_tal[0][0][0] + 3 * VB_MAXP, *s_single = s_hm + VB_SIDES, *s_vm = s_single + VB_SIDES, *s_unf = s_vm + VB_SIDES;
+    int32_t (*s_ptid)[VB_MAXP] = reinterpret_cast<int32_t (*)[VB_MAXP]>(&s_tal[0][0]);
+    uint16_t (*s_lastm)[VB_MAXP] = reinterpret_cast<uint16_t (*)[VB_MAXP]>(&s_tal[0][0] + 2 * VB_MAXP);
+    uint32_t *s_hm = &s_tal[0][0] + 3 * VB_MAXP, *s_single = s_hm + VB_SIDES, *s_vm = s_single + VB_SIDES, *s_unf = s_vm + VB_SIDES;
     int32_t *s_pmin = reinterpret_cast<int32_t *>(s_unf + VB_SIDES), *s_pmax = s_pmin + VB_SIDES;
     uint8_t *s_pg = reinterpret_cast<uint8_t *>(s_pmax + VB_SIDES);
     // ... and, in its top 4 KB, the second half of every read (VTail) until P2 is through
-    VTail (*s_rt)[VB_MAXP] = reinterpret_cast<VTail (*)[VB_MAXP]>(reinterpret_cast<char *>(&s_tal[0][0][0]) + sizeof(s_tal) - 2 * VB_MAXP * sizeof(VTail));
+    VTail (*s_rt)[VB_MAXP] = reinterpret_cast<VTail (*)[VB_MAXP]>(reinterpret_cast<char *>(&s_tal[0][0]) + sizeof(s_tal) - 2 * VB_MAXP * sizeof(VTail));
     static_assert(sizeof(s_tal) >= (3 * VB_MAXP + 6 * VB_SIDES) * 4 + VB_MAXP + 2 * VB_MAXP * sizeof(VTail), "P1 scratch and the reads' second halves must fit the tally space");
     // work index of a thread: rotated by the batch number, so that the single-wave phases (P0, P2, P5a, P6) and the half-empty ones
     // do not all land on the same SIMD of the CU (wave k of every workgroup runs on SIMD k)
-#ifdef VB_XCD              // experiment: workgroup i runs on XCD i mod 8 -- give every XCD a CONTIGUOUS eighth of the batches, so that neighbouring batches (whose reads share sectors) share an L2
-    const uint32_t per_x_ = gridDim.x >> 3, bid_ = (blockIdx.x & 7u) * per_x_ + (blockIdx.x >> 3);      // (the grid is a multiple of 8)
-#else
-    const uint32_t bid_ = blockIdx.x;
-#endif
     const int tid = (int)((threadIdx.x + ((blockIdx.x & (VB_T / 64 - 1)) << 6)) & (VB_T - 1)), lane = tid & 63;
-    const uint32_t g0 = w.vb_start[bid_];
+    const uint32_t g0 = w.vb_start[blockIdx.x];
     if (g0 == NONE32) return;
 #if defined(VB_PROF) && !defined(DV_PROF)
     unsigned long long t_prev_ = wall_clock64();
@@ -287,7 +229,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
         const bool maybe = lane < VB_MAXG && g0 + (uint32_t)lane < n_live;             // (ONE 16-byte load per live-list entry: whether the group belongs to the batch only decides who uses it)
         const uint4 lr_ = maybe ? w.vlive[g0 + (uint32_t)lane] : make_uint4(0u, 0u, 0u, 0u);
         const uint32_t gi = lr_.x, gb_ = lr_.y, np_ = lr_.z, wb_ = lr_.w;
-        bool in = maybe && wb_ < (bid_ + 1u) * VB_W;
+        bool in = maybe && wb_ < (blockIdx.x + 1u) * VB_W;
         uint32_t np = in ? np_ : 0u;
         const bool deep = in && (np > 32u || (int)np > p.skip_low_complexity_thr || !p.vote_ok);
         const unsigned long long im = __ballot(in);
@@ -316,7 +258,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
         }
     }
     for (int k = tid; k < VB_SIDES * (VB_COLS / 32); k += VB_T) (&s_cmask[0][0])[k] = 0u;
-    { const int t2 = VB_T > 64 ? tid - 64 : tid; if (t2 >= 0 && t2 < VB_PRE - VB_SIDES - 1) { const int k = VB_SIDES + 1 + t2; s_ipre[k] = 0xFFFF; s_cpre[k] = 0xFFFF; s_jpre[k] = 0xFFFF; } }      // (the second wave, where there is one)
+    { const int t2 = tid - 64; if (t2 >= 0 && t2 < VB_PRE - VB_SIDES - 1) { const int k = VB_SIDES + 1 + t2; s_ipre[k] = 0xFFFF; s_cpre[k] = 0xFFFF; s_jpre[k] = 0xFFFF; } }      // (the second wave)
     if (tid >= VB_T - 4 * VB_SIDES) {                                                  // (the last waves: the first one is busy with the groups)
         const int k = tid - (VB_T - 4 * VB_SIDES);
         s_hm[k] = 0u;                                                                   // s_hm, s_single, s_vm, s_unf are adjacent
@@ -532,16 +474,10 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
                 const VRead *r3 = vm ? rds + (__ffs((int)vm) - 1) : r0; vm &= vm ? vm - 1 : 0u;
                 const uint64_t so0 = r0->so, qo0 = r0->qo, so1 = r1->so, qo1 = r1->qo, so2 = r2->so, qo2 = r2->qo, so3 = r3->so, qo3 = r3->qo;
                 uint64_t sq[4], qa[4], qb[4];
-#if VB_LD16        // the 16 qualities of a voter's chunk in ONE load (round 6: eight vector memory instructions per step instead of twelve)
+                // the 16 qualities of a voter's chunk in ONE load: eight vector memory instructions per step instead of twelve
                 { const vb_u64x2 q0_ = vb_ld16(b.qual + qo0 + c16), q1_ = vb_ld16(b.qual + qo1 + c16), q2_ = vb_ld16(b.qual + qo2 + c16), q3_ = vb_ld16(b.qual + qo3 + c16);
                   sq[0] = ld8_unaligned(b.seq + so0 + 8 * chunk); sq[1] = ld8_unaligned(b.seq + so1 + 8 * chunk); sq[2] = ld8_unaligned(b.seq + so2 + 8 * chunk); sq[3] = ld8_unaligned(b.seq + so3 + 8 * chunk);
                   qa[0] = q0_.x; qb[0] = q0_.y; qa[1] = q1_.x; qb[1] = q1_.y; qa[2] = q2_.x; qb[2] = q2_.y; qa[3] = q3_.x; qb[3] = q3_.y; }
-#else
-                sq[0] = ld8_unaligned(b.seq + so0 + 8 * chunk); qa[0] = ld8_unaligned(b.qual + qo0 + c16); qb[0] = ld8_unaligned(b.qual + qo0 + c16 + 8);
-                sq[1] = ld8_unaligned(b.seq + so1 + 8 * chunk); qa[1] = ld8_unaligned(b.qual + qo1 + c16); qb[1] = ld8_unaligned(b.qual + qo1 + c16 + 8);
-                sq[2] = ld8_unaligned(b.seq + so2 + 8 * chunk); qa[2] = ld8_unaligned(b.qual + qo2 + c16); qb[2] = ld8_unaligned(b.qual + qo2 + c16 + 8);
-                sq[3] = ld8_unaligned(b.seq + so3 + 8 * chunk); qa[3] = ld8_unaligned(b.qual + qo3 + c16); qb[3] = ld8_unaligned(b.qual + qo3 + c16 + 8);
-#endif
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     sor |= sq[k]; sand &= sq[k];
@@ -643,11 +579,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             pre = cnt;
             pre = wave_scan_incl(pre);                                                  // (dropping sides only lowers the prefixes of the others)
         }
-#if VB_COLPAIR
         const int nit = act ? ((cnt + 1) >> 1) * (int)s_side[lane].nvot : 0;          // (voter, column pair) items
-#else
-        const int nit = act ? cnt * (int)s_side[lane].nvot : 0;
-#endif
         int pre2 = nit;
         pre2 = wave_scan_incl(pre2);
         if (lane < VB_SIDES) { s_cpre[lane] = (uint16_t)(pre - cnt); s_jpre[lane] = (uint16_t)(pre2 - nit); }
@@ -680,21 +612,16 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
         const int s1 = nofit_ ? __ffsll((long long)nofit_) - 1 : 64;                            // first side that does not fit (prefixes ascend: every later one does not either); VB_SIDES if all do
         const int c0 = s_cpre[s0], ncol = (int)s_cpre[s1] - c0, j0 = s_jpre[s0], njob = (int)s_jpre[s1] - j0;
         if (s0 > 0 && threadIdx.x == 0) { atomicAdd(&w.si->vote_rounds2, 1ull); if (s0 & 3) atomicAdd(&w.si->vote_rounds2_unaligned, 1ull); }   // (tests: a second round is reached)
-#if VB_TPLANE
         {
-            uint32_t *tp_ = &s_tal[0][0][0];
+            uint32_t *tp_ = &s_tal[0][0];
             for (int c = tid; c < ncol; c += VB_T) {
 #pragma unroll
                 for (int pl = 0; pl < 10; pl++) tp_[pl * VB_CCAP + c] = 0u;
             }
         }
-#else
-        for (int k = tid; k < ncol * 5; k += VB_T) *(uint2 *)(&s_tal[0][0][0] + 2 * k) = make_uint2(0, 0);
-#endif
         __syncthreads();
         VB_TICK(5);
-#if VB_COLPAIR
-        // (c) one lane per (side, voter, PAIR of neighbouring contested columns of the side's list), column pairs fastest (round 6).  What an item pays before it can ask for
+        // (c) one lane per (side, voter, PAIR of contested columns of the side's list, half the list apart), column pairs fastest (round 6).  What an item pays before it can ask for
         //     its bytes -- its side in the prefix, the division by the side's width, the voter, the voter's blob offsets and overlap window -- belongs to the VOTER, not to the
         //     column: two columns share it (rounds 2-5: one column per item, 144 wave instructions per 64 votes of which ~50 are the vote itself; voter quads x one column, round 5,
         //     shared only the side).  A side with an odd number of columns pads half an item per voter.  The byte loads of both columns are in flight together.
@@ -707,15 +634,9 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             if (!x.on) return x;
             x.side = s & 1;
             const int cb = (int)s_cpre[s], ncs = (int)s_cpre[s + 1] - cb, ncs2 = (ncs + 1) >> 1, local = it - (int)s_jpre[s];
-#if VB_TPLANE
             const int kv = (int)(((float)local + 0.5f) * __builtin_amdgcn_rcpf((float)ncs2)), c = local - kv * ncs2;            // local / ncs2 (local < 512, ncs2 <= 16: the half keeps it exact)
             x.ci = cb + c; x.on1 = c + ncs2 < ncs; x.d1 = x.on1 ? ncs2 : 0;                                                  // the item's columns: c and c + half the side's width
             x.col[0] = s_ccol[x.ci]; x.col[1] = s_ccol[x.ci + x.d1];
-#else
-            const int kv = (int)(((float)local + 0.5f) * __builtin_amdgcn_rcpf((float)ncs2)), c = 2 * (local - kv * ncs2);      // local / ncs2 (local < 512, ncs2 <= 16: the half keeps it exact)
-            x.ci = cb + c; x.on1 = c + 1 < ncs; x.d1 = x.on1 ? 1 : 0;
-            x.col[0] = s_ccol[x.ci]; x.col[1] = s_ccol[x.ci + x.d1];
-#endif
             const VSide *sd = &s_side[s];
             x.grp = sd->grp;
             const int lp = s_vlist[x.side][(int)sd->lp0 + kv];
@@ -763,13 +684,8 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             const int bin = (int)((uint32_t)(0x4777777377727107ull >> (nb * 4)) & 7u);        // A,C,G,T,N -> 0..4, anything else 7
             if (bin == 7 || (q & 0x80)) s_gflag[x.grp] = 2;
             else {
-#if VB_TPLANE
-                uint32_t *t2 = &s_tal[0][0][0] + (2 * bin) * VB_CCAP + (x.ci + (u ? x.d1 : 0) - c0);
+                uint32_t *t2 = &s_tal[2 * bin][x.ci + (u ? x.d1 : 0) - c0];
                 atomicAdd(t2, 1u | ((uint32_t)sc << 6) | ((uint32_t)q << 20)); atomicMax(t2 + VB_CCAP, (uint32_t)q);
-#else
-                uint32_t *t2 = &s_tal[x.ci + (u ? x.d1 : 0) - c0][bin][0];
-                atomicAdd(t2, 1u | ((uint32_t)sc << 6) | ((uint32_t)q << 20)); atomicMax(t2 + 1, (uint32_t)q);
-#endif
             }
         };
         for (int itb = j0 + tid - lane; itb < j0 + njob; itb += VB_T) {                 // (wave-uniform trips: the side lookup is a wave operation)
@@ -777,63 +693,6 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             const Item x0 = prep(itb + lane, sa);
             if (x0.on) { vote1(x0, 0); if (x0.on1) vote1(x0, 1); }
         }
-#else
-        // (c) one lane per (side, voter, contested column), columns fastest.  Two items per trip: the byte loads of both are issued
-        //     before either is used (an item is two dependent round trips otherwise: LDS lookups -> its bytes)
-        struct Item { int ci, side, grp, q, sb, mb, mq, mc, col; bool on, inov, cst; };
-        auto prep = [&](int it, int s) -> Item {
-            Item x; x.on = it < j0 + njob; x.ci = 0; x.side = 0; x.grp = 0; x.q = 0; x.sb = 0; x.mb = 0; x.mq = 0; x.mc = 0; x.col = 0; x.inov = false; x.cst = false;
-            if (!x.on) return x;
-            x.side = s & 1;
-            const int ncs = (int)s_cpre[s + 1] - (int)s_cpre[s], local = it - (int)s_jpre[s];
-            const int kv = (int)(((float)local + 0.5f) * __builtin_amdgcn_rcpf((float)ncs)), c = local - kv * ncs;      // local / ncs (local < 1024, ncs <= 32: the half keeps it exact)
-            x.ci = (int)s_cpre[s] + c; x.col = s_ccol[x.ci];
-            const VSide *sd = &s_side[s];
-            x.grp = sd->grp;
-            const int lp = s_vlist[x.side][(int)sd->lp0 + kv];
-            const VRead *r = &s_rd[x.side][lp];
-            const VOv ov = s_ov[lp];
-            const int mystart = x.side ? ov.rs : ov.ls;
-            x.cst = ov.fl & 1;
-            x.inov = (ov.fl & 2) && (unsigned)(x.col - mystart) < (unsigned)ov.cmp;
-            x.sb = b.seq[r->so + (x.col >> 1)];
-            x.q = b.qual[r->qo + x.col];
-            if (x.inov) {                                                               // pair.cpp:132-168: the mate's base and quality on the same reference position
-                const VRead *mt = &s_rd[x.side ^ 1][lp];
-                x.mc = x.col - mystart + (x.side ? ov.ls : ov.rs);
-                x.mb = b.seq[mt->so + (x.mc >> 1)]; x.mq = b.qual[mt->qo + x.mc];
-            }
-            return x;
-        };
-        auto vote = [&](const Item &x) {
-            if (!x.on) return;
-            int q = x.q;
-            const int nb = (x.col & 1) ? (x.sb & 0xF) : (x.sb >> 4);
-            // the three score rules without branches (pair.cpp:89-105 constant; :140-150 match; :151-168 mismatch): one qual2score of the
-            // quality each rule looks at, then the rule's offset
-            const int mn = (x.mc & 1) ? (x.mb & 0xF) : (x.mb >> 4);
-            const bool match = x.inov && nb == mn, mism = x.inov && nb != mn;
-            const bool left_wins = x.side ? (x.mq >= q) : (q >= x.mq);                // `if(lq >= rq)`: the left read keeps a score
-            const int dq = max(0, q - x.mq);
-            const int qlook = match ? (((q + x.mq) / 2) & 0xFF) : mism ? dq : q;
-            const bool scored = !mism || (x.side == 0 ? left_wins : !left_wins);        // the mismatch loser scores 0
-            int sc = d_qual2score(p, qlook) + (match ? 4 : mism ? -3 : 0);
-            sc = scored ? sc : 0;
-            sc = x.cst ? p.s_moderate : sc;
-            q = mism ? dq : q;                                                          // the rewritten quality is what the vote sees
-            const int bin = (int)((uint32_t)(0x4777777377727107ull >> (nb * 4)) & 7u);        // A,C,G,T,N -> 0..4, anything else 7
-            if (bin == 7 || (q & 0x80)) s_gflag[x.grp] = 2;
-            else {
-                uint32_t *t2 = &s_tal[x.ci - c0][bin][0];
-                atomicAdd(t2, 1u | ((uint32_t)(sc + p.score_bias) << 6) | ((uint32_t)q << 20)); atomicMax(t2 + 1, (uint32_t)q);
-            }
-        };
-        for (int itb = j0 + tid - lane; itb < j0 + njob; itb += 2 * VB_T) {             // (wave-uniform trips: the side lookup is a wave operation)
-            const int sa = s0 + vb_find_wave(s_jpre, s0, s1 - s0, itb, lane, j0 + njob - 1), sb2 = s0 + vb_find_wave(s_jpre, s0, s1 - s0, itb + VB_T, lane, j0 + njob - 1);
-            const Item x0 = prep(itb + lane, sa), x1 = prep(itb + lane + VB_T, sb2);
-            vote(x0); vote(x1);
-        }
-#endif
         __syncthreads();
         VB_TICK(6);
         // (d) one lane per column of the round: rule cascade + reference arbitration (group.cpp:394-501)
@@ -852,12 +711,7 @@ __global__ __launch_bounds__(VB_T) __attribute__((amdgpu_waves_per_eu(VB_WPE, 8)
             Tally5 t; t.total = 0;
 #pragma unroll
             for (int k = 0; k < 5; k++) {
-#if VB_TPLANE
-                const uint32_t *tp_ = &s_tal[0][0][0] + (2 * k) * VB_CCAP + (ci - c0);
-                const uint2 v2 = make_uint2(tp_[0], tp_[VB_CCAP]);
-#else
-                const uint2 v2 = *(const uint2 *)(&s_tal[ci - c0][k][0]);
-#endif
+                const uint2 v2 = make_uint2(s_tal[2 * k][ci - c0], s_tal[2 * k + 1][ci - c0]);
                 t.cnt[k] = (int)(v2.x & 63u); t.ss[k] = (int)((v2.x >> 6) & 0x3FFFu) - t.cnt[k] * p.score_bias; t.qs[k] = (int)(v2.x >> 20); t.tq[k] = (int)v2.y;
                 t.total += t.ss[k];
             }

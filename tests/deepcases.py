@@ -19,7 +19,7 @@ import numpy as np
 
 import lencases as lc
 
-DV_CHUNK, DV_COLS, SC2_MAXU = 256, 512, 1280                # gce_deep.hpp, gce_kernels.hpp
+DV_CHUNK, DV_COLS, SC2_MAXU = 256, 512, 1280                # gce_deep.hpp, gce_consensus.hpp
 GCE_ERR_NM_MISSING = -12
 KERNELS = ("vote", "fast", "deep_prepare", "vote_deep", "slow")
 NIB = {"A": 1, "C": 2, "G": 4, "T": 8, "N": 15}

@@ -296,7 +296,7 @@ DEEP_EDGE = (70, 4100)
 
 
 def order_names(tag, kind):
-    """Names that take the unusual branches of the register tiers' name order (gce_pair2.hpp:173-221, gce_kernels.hpp:395-429)."""
+    """Names that take the unusual branches of the register tiers' name order (gce_pair2.hpp:173-221, gce_pairing.hpp:295-329)."""
     t = tag
     if kind == "prefix":                   # names that are prefixes of others
         return [t + b":ab", t + b":abc", t + b":abcd", t + b":ab7", t + b":a", t + b":abc0"]

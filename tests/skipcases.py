@@ -1,4 +1,4 @@
-"""Hand-built streams around the groups the engine does not evaluate (d_group_skipped, gce_kernels.hpp) -- CPU only, no engine.
+"""Hand-built streams around the groups the engine does not evaluate (d_group_skipped, gce_groups.hpp) -- CPU only, no engine.
 
 A one-pair group that no setting of the run can write (--supporting_reads > 1 or --duplex_only, no duplex partner possible) is left out of k_vote's
 batches; its Stats entry is written from the pair slot.  Every stream here is a few dozen to a few hundred reads of 30 bases: clusters lie one behind

@@ -944,7 +944,7 @@ def vote_groups_stream(seed, groups, n_pairs=6, L=(60, 60), gap=None, spacing=10
 
 
 def test_vote_pass_b_odd_and_even_column_counts(built):
-    """Pass B (gce_vote.hpp, VB_COLPAIR): an item votes columns c and c + ncs2 of its side's list, ncs2 = (ncs + 1) / 2; with an odd ncs the last
+    """Pass B (gce_vote.hpp, P5c): an item votes columns c and c + ncs2 of its side's list, ncs2 = (ncs + 1) / 2; with an odd ncs the last
     item's second column does not exist (on1 false).  Sides with 1 and 31 contested columns (odd: the last item of every voter is half an item),
     2 and 32 (even controls; 32 = VB_SMAX, the most a side keeps), and 33 (over VB_SMAX: the group is handed on).  Five groups of 6 pairs
     (weight 30 <= VB_W = 96: one batch), 1 + 31 + 2 + 32 + 31 + 1 + 32 + 2 = 132 contested columns in k_vote <= VB_CCAP = 256: one round."""

@@ -1,4 +1,4 @@
-"""Groups the engine does not evaluate because nothing could write them (d_group_skipped, gce_kernels.hpp; gce_get_skipped_groups).
+"""Groups the engine does not evaluate because nothing could write them (d_group_skipped, gce_groups.hpp; gce_get_skipped_groups).
 
 The CPU tests hold the stream builders (tests/skipcases.py) against the oracle: every stream runs clean and the trap it sets is really there.  The GPU tests
 run every stream through one engine and compare the table, its order and both Stats blocks bit for bit with the oracle, and the skipped count and the

@@ -1,8 +1,13 @@
 """Temporary instrumentation (not for commit): per-phase clock64() deltas of k_pairing_fast, sampled 1/64 clusters,
 printed by gce_process when GCE_PROF is set.  Apply, build, run bench with GCE_PROF=1, then `git checkout` the sources."""
-p='/root/repo/gencore_amd/csrc/gce_kernels.hpp'
+import os
+CSRC=os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'gencore_amd', 'csrc')
+p=os.path.join(CSRC, 'gce_kernels.hpp')          # Work
 s=open(p).read()
 s=s.replace("uint32_t *ev_read; int max_events;","uint32_t *ev_read; int max_events; unsigned long long *prof;")
+open(p,'w').write(s)
+p=os.path.join(CSRC, 'gce_pairing.hpp')          # k_pairing_fast
+s=open(p).read()
 K0 = s.index("void k_pairing_fast")
 def ins(before, text):
     global s
@@ -18,7 +23,7 @@ ins("    // ---- lanes now stand for pairs (qname order)", "    t_[6] = clock64(
 ins("    // ---- lay the pairs out group by group (qname order inside a group)", "    t_[7] = clock64();\n")
 ins("    if (lane == 0) { const bool cross = d_key(b.core[w.members[start]], p).right < 0;", "    t_[8] = clock64();\n    if (w.prof && lane == 0 && (c & 63) == 5) { for (int k = 0; k < 8; k++) atomicAdd(&w.prof[k], (unsigned long long)(t_[k + 1] - t_[k])); atomicAdd(&w.prof[15], 1ull); }\n")
 open(p,'w').write(s)
-p='/root/repo/gencore_amd/csrc/engine.hip'
+p=os.path.join(CSRC, 'engine.hip')
 s=open(p).read()
 s=s.replace("    w.max_events = (int)max_events;","""    w.max_events = (int)max_events;
     static unsigned long long *d_prof = nullptr;
